@@ -262,6 +262,59 @@ def other_config_rate(arch, dev, N, K, S, sigma, dtype, precision, steps=20, war
     return res
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def step_state(trainer):
+    """Everything a training step changes: both networks' state_dicts (parameters, BN buffers), the student optimizer's state
+    (moments, step counter, loss scale) and the host generator of the step's draws.  Copies, for restore_step_state()."""
+    import copy
+    return {"student": copy.deepcopy(trainer.student.state_dict()), "teacher": copy.deepcopy(trainer.teacher.state_dict()),
+            "optimizer": copy.deepcopy(trainer.stu_optimizer.state_dict()), "rng": trainer.rng.get_state()}
+
+
+def restore_step_state(trainer, snap):
+    """In place (load_state_dict keeps the storage the captured launches point at): the step replays from the snapshot on."""
+    import copy
+    trainer.student.load_state_dict(snap["student"])
+    trainer.teacher.load_state_dict(snap["teacher"])
+    trainer.stu_optimizer.load_state_dict(copy.deepcopy(snap["optimizer"]))
+    trainer.rng.set_state(snap["rng"])
+
+
+def dump_outputs(outs, path):
+    """Write the step's outputs (name -> host tensor) as <path>/<name>.npy: floating point as float32 (float64 stays float64),
+    integers and booleans as float64.  Above DUMP_BUDGET_BYTES in all, every array larger than an equal share of the budget is
+    replaced by a fixed seeded sample (flattened, index order) of that many elements.  Returns {name: {shape, dtype, sampled}}."""
+    import numpy as np
+    arrays = {}
+    for k, v in outs.items():
+        arrays[k] = v.to(torch.float64 if v.dtype == torch.float64 or not v.is_floating_point() else torch.float32).contiguous().numpy()
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES
+    os.makedirs(path, exist_ok=True)
+    info = {}
+    for k, a in arrays.items():
+        shape, n = list(a.shape), share // a.itemsize
+        sampled = over and a.size > n
+        if sampled:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), a)
+        info[k] = {"shape": shape, "dtype": str(a.dtype), "sampled": (int(a.size) if sampled else None)}
+    return info
+
+
+def step_outputs(out):
+    """The tensors of a step's result dict on the host (lists of tensors as <name>_<i>; the host-side scalars are left out)."""
+    res = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            res[k] = v.detach().cpu()
+        elif isinstance(v, (list, tuple)) and v and all(torch.is_tensor(t) for t in v):
+            res.update({f"{k}_{i}": t.detach().cpu() for i, t in enumerate(v)})
+    return res
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes of this script (one per GPU, rendezvous on
     127.0.0.1), relay rank 0's stdout (the ONE JSON line), send the other ranks' stdout to stderr, and exit non-zero if any
@@ -389,6 +442,10 @@ def main():
     ap.add_argument("--arena-teacher", action="store_true", help="tuning: no-grad forwards keep the bump-allocated 2.8 GB arena instead of the forward-only "
                     "plan's six rotating scratch buffers (A/B of round 5's default)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the untimed extra legs (fp16 / reference precision mix rates)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step returned "
+                    "(losses, heat-maps, masks) as DIR/<name>.npy, float32 / float64, at most 64 MB (larger outputs: a fixed seeded sample), rank 0; "
+                    "the host generator is seeded and the state the spin-up steps leave is rolled back before the warm-up, so that the same "
+                    "arguments give the same inputs on every run (data parallel: with --dp-form fixed)")
     args = ap.parse_args()
     dp_auto = args.dp_form == "auto" and args.grad_comm is None and not args.one_bucket and not args.eager and not args.split_graphs
     if args.grad_comm is None:
@@ -502,6 +559,8 @@ def main():
     # configs[2] captured: the occlusion decisions are taken on the device (four uniform draws per sample, no read-back);
     # --eager keeps the reference's host draws (one read-back of the confidences per step)
     trainer.device_occlusion = bool(args.config2 and not args.eager)
+    if args.dump_outputs:
+        trainer.rng.seed(0)            # (the style / occlusion draws; the same seed on every rank, as the data-parallel draws expect)
     b = synthetic.mean_teacher_batch(N, num_keypoints=K, image_size=S, heatmap_size=S // 4, sigma=sigma, seed=rank)   # one shard per rank
     g = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in b.items()}
 
@@ -604,6 +663,9 @@ def main():
     # shared with a one-element all-reduce after every step (a rank-local clock test lets ranks disagree by one step at the
     # boundary, after which the collectives of the timed region no longer pair up).
     guard.arm(240 + 2 * args.spinup + 0.5 * (args.warmup + args.steps), "spin-up, warm-up and the timed steps")
+    # --dump-outputs: the spin-up runs as many steps as fit its seconds; the state they leave is rolled back before the warm-up, so that the
+    # timed steps start from the same state on every run
+    snap = step_state(trainer) if args.dump_outputs else None
     t_spin = time.perf_counter()
     spin_ms = []
     go = torch.zeros(1, device=dev) if dist.is_initialized() else None
@@ -623,6 +685,9 @@ def main():
         k = max(1, len(spin_ms) // 10)
         print("spin-up ms/step by tenths: " + " ".join(f"{sum(spin_ms[i:i + k]) / len(spin_ms[i:i + k]):.1f}" for i in range(0, len(spin_ms), k)),
               file=sys.stderr)
+    if snap is not None and spin_ms:
+        restore_step_state(trainer, snap)
+    snap = None
     for _ in range(args.warmup):
         out = step()
     if world > 1:
@@ -638,6 +703,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    # (the static outputs of a captured step are overwritten by the untimed steps below: the last timed step's are copied now)
+    last_outputs = step_outputs(out) if (args.dump_outputs and rank == 0) else None
     if world > 1:
         guard.arm(300, "the untimed legs after the timed region")
     else:
@@ -855,6 +922,8 @@ def main():
             oc["configs[2]_reference_mix"]["workload"] = "the same in the reference's precision mix (fp16 student, f16x2 teacher and style network)"
             oc["configs[4]_workload_1gpu_fp16"]["workload"] = f"{args.arch} K=18, 384x384 (heat-maps 96x96), sigma 1.0, fp16, b={N} on ONE GPU (configs[4] is this workload on 8)"
             res["other_configs"] = oc
+        if last_outputs is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(last_outputs, args.dump_outputs)}
         print(json.dumps(res), flush=True)
     if os.environ.get("UDAPOSE_BENCH_DEBUG_EXIT"):
         import faulthandler

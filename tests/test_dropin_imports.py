@@ -6,10 +6,55 @@ import re
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = "/root/reference"
+
+# A stand-in for the reference checkout's host-side glue, laid out as the reference lays it out (`lib/` WITHOUT an __init__.py,
+# so that _dropin.install merges it into this package's lib.__path__).  Written here, per test, so that the test needs nothing
+# outside the repository; the classes are minimal stand-ins with the names the reference's scripts import.
+_STAND_IN = {
+    "meter.py": '''
+class AverageMeter:
+    def __init__(self, name, fmt=":f"):
+        self.name, self.fmt = name, fmt
+        self.val = self.sum = self.count = self.avg = 0.0
+
+    def update(self, val, n=1):
+        self.val = val
+        self.sum += val * n
+        self.count += n
+        self.avg = self.sum / self.count
+
+
+class AverageMeterList(AverageMeter):
+    pass
+
+
+class ProgressMeter:
+    def __init__(self, num_batches, meters, prefix=""):
+        self.num_batches, self.meters, self.prefix = num_batches, meters, prefix
+''',
+    "data.py": '''
+class ForeverDataIterator:
+    def __init__(self, loader):
+        self.loader = loader
+        self.it = iter(loader)
+
+    def __next__(self):
+        try:
+            return next(self.it)
+        except StopIteration:
+            self.it = iter(self.loader)
+            return next(self.it)
+''',
+}
+
+
+def _reference_stand_in(tmp_path):
+    root = tmp_path / "UDA_PoseEstimation"
+    (root / "lib").mkdir(parents=True)
+    for name, src in _STAND_IN.items():
+        (root / "lib" / name).write_text(src)
+    return str(root)
 
 
 def _recipe():
@@ -53,17 +98,20 @@ print("DROPIN-OK")
     assert r.returncode == 0 and "DROPIN-OK" in r.stdout, r.stdout + r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "lib")), reason="reference checkout not present (GPU box)")
 def test_rest_of_reference_lib_still_resolves(tmp_path):
     """lib.meter / lib.data / lib.logger keep coming from the reference tree next to our lib.models (host-side glue that is
-    out of scope here and imports without torchvision)."""
-    code = _recipe().replace("/path/to/repo", ROOT).replace("/path/to/UDA_PoseEstimation", REFERENCE)
+    out of scope here and imports without torchvision); the reference tree is the stand-in above."""
+    reference = _reference_stand_in(tmp_path)
+    code = _recipe().replace("/path/to/repo", ROOT).replace("/path/to/UDA_PoseEstimation", reference)
     code += r'''
 from lib.meter import AverageMeter, ProgressMeter, AverageMeterList
 from lib.data import ForeverDataIterator
-import lib.meter, os
-assert os.path.realpath(lib.meter.__file__).startswith(os.path.realpath("''' + REFERENCE + r'''"))
+import lib.meter, lib.data, os, sys
+assert os.path.realpath(lib.meter.__file__).startswith(os.path.realpath("''' + reference + r'''"))
+assert os.path.realpath(lib.data.__file__).startswith(os.path.realpath("''' + reference + r'''"))
+assert models is sys.modules["uda_poseestimation_amd.lib.models"], "the second tree must not shadow this package's lib.models"
 m = AverageMeter("x"); m.update(2.0, 4); assert m.avg == 2.0
+it = ForeverDataIterator([1, 2]); assert [next(it) for _ in range(3)] == [1, 2, 1]
 print("DROPIN-OK")
 '''
     r = _run(code, tmp_path)

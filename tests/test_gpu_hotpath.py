@@ -932,6 +932,36 @@ def test_bench_gpus_flag_starts_its_own_ranks():
     assert bad.returncode != 0 and "WORLD_SIZE=2" in (bad.stdout + bad.stderr)
 
 
+def test_bench_dump_outputs_do_not_depend_on_the_spin_up(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MB), the same
+    arrays bit for bit whether the time-bounded spin-up ran no step or several (its state is rolled back before the warm-up), for
+    the replayed step and for the eager one (whose optimizer has no moments yet when the spin-up starts)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    common = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--arch", "pose_resnet50", "--batch", "4",
+              "--no-cpu-baseline"]
+    res = {}
+    for tag, flags in (("cold", ["--spinup", "0"]), ("spun", ["--spinup", "2"]), ("eager_cold", ["--spinup", "0", "--eager"]),
+                       ("eager_spun", ["--spinup", "1", "--eager"])):
+        out = subprocess.run(common + flags + ["--dump-outputs", str(tmp_path / tag)], cwd=root, env=env, capture_output=True, text=True,
+                             timeout=600)
+        assert out.returncode == 0, tag + out.stdout[-2000:] + out.stderr[-4000:]
+        d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / tag))
+        assert files == sorted(k + ".npy" for k in d["dumped_outputs"]["arrays"]) and "y_s.npy" in files and "loss_all.npy" in files
+        res[tag] = {f[:-4]: np.load(tmp_path / tag / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in res[tag].values())
+        assert sum(a.nbytes for a in res[tag].values()) <= 64 * 2 ** 20
+    # (the eager run takes two optimizer steps fewer than the replayed one - GraphedTrainStep's capture warm-up - so the two are not compared)
+    assert res["cold"].keys() == res["spun"].keys() and res["eager_cold"].keys() == res["eager_spun"].keys() <= res["cold"].keys()
+    for a_, b_ in (("cold", "spun"), ("eager_cold", "eager_spun")):
+        for k, a in res[a_].items():
+            d = float(np.abs(a.astype(np.float64) - res[b_][k]).max()) if a.size else 0.0
+            assert np.array_equal(a, res[b_][k], equal_nan=True), f"{b_} {k}: the spin-up changed what the timed steps computed (max|d| {d:.3e})"
+
+
 def test_one_rank_rccl_step():
     """The data-parallel code path on the REAL RCCL backend with a one-rank process group (bench.py's UDAPOSE_FORCE_DIST hook:
     the test box has one GPU, and RCCL refuses two ranks on one device): backend "nccl" initialised with a device id, the

@@ -205,6 +205,31 @@ def test_bench_cpu_share_is_bounded_by_the_affinity_mask():
     assert 1 <= n <= len(os.sched_getaffinity(0))
 
 
+def test_bench_dump_outputs_format_and_budget(tmp_path):
+    """bench.py --dump-outputs' writer: one <name>.npy per tensor (lists as <name>_<i>, host scalars left out), floating point as
+    float32 (float64 kept), integers / booleans as float64, values exact; above 64 MB in all a fixed seeded sample of the large arrays."""
+    import importlib.util, os
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)
+    y = torch.randn(4, 3, 8, 8).to(torch.bfloat16)
+    out = {"loss_all": torch.tensor(1.25), "y_s": y, "tea_mask": torch.rand(4, 3) > 0.5, "cnt": torch.tensor([3, 7]),
+           "recon": [torch.randn(2, 3), torch.randn(2, 3, dtype=torch.float64)], "acc": 0.5, "none": None}
+    info = m.dump_outputs(m.step_outputs(out), str(tmp_path / "small"))
+    assert sorted(os.listdir(tmp_path / "small")) == sorted(k + ".npy" for k in ("loss_all", "y_s", "tea_mask", "cnt", "recon_0", "recon_1"))
+    ld = {k: np.load(tmp_path / "small" / (k + ".npy")) for k in info}
+    assert ld["y_s"].dtype == np.float32 and np.array_equal(ld["y_s"], y.float().numpy())
+    assert ld["tea_mask"].dtype == np.float64 and np.array_equal(ld["tea_mask"], out["tea_mask"].double().numpy())
+    assert ld["cnt"].dtype == np.float64 and ld["recon_1"].dtype == np.float64 and ld["loss_all"].shape == ()
+    assert all(v["sampled"] is None for v in info.values())
+    big = {"y": torch.arange(9 * 2 ** 20, dtype=torch.float64), "z": torch.ones(10)}
+    i1 = m.dump_outputs(big, str(tmp_path / "b1"))
+    i2 = m.dump_outputs(big, str(tmp_path / "b2"))
+    a1, a2 = np.load(tmp_path / "b1" / "y.npy"), np.load(tmp_path / "b2" / "y.npy")
+    assert i1 == i2 and i1["y"]["shape"] == [9 * 2 ** 20] and i1["y"]["sampled"] == a1.size and i1["z"]["sampled"] is None
+    assert np.array_equal(a1, a2) and np.all(np.diff(a1) > 0)          # the same sample every time, in index order, values exact
+    assert sum(os.path.getsize(tmp_path / "b1" / f) for f in os.listdir(tmp_path / "b1")) <= 64 * 2 ** 20 + 4096
+
+
 def test_bench_hang_guard_ends_a_rank_that_waits_for_ever():
     """bench.py's _HangGuard (data-parallel runs): a phase that outlives its bound ends the process with the phase's name on stderr
     (exit code 3; the given code when the result line is already out); a cancelled or disabled guard does nothing."""
