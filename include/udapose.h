@@ -357,6 +357,45 @@ int udapose_adain_split(void* stream, const void* content, const void* style, vo
 int udapose_adain_alpha_dev(void* stream, const void* content, const void* style, void* out, int N, int HWc, int HWs, int C, float eps,
                             const float* alpha_dev, float* stats_out, int is_f32);
 
+/* ---------------------------------------------------------------- AdaIN decoder training (reference adain/net.py:102-162, adain/train/)
+ * The backward of the style network's step on NHWC tensors of the library's element type, fp32 accumulation.  Reflection-padded 3x3
+ * stride-1 convolutions (desc: reflect = 1, pad = 1, K = 3, optional upsample; Ci and Co multiples of 64 - zero-pad the 3-channel end
+ * layers) run their backward on the padded (Hl+2) x (Wl+2) grid, Hl = Hi << upsample.  Every reduction is bit-reproducible.
+ * Workspace: udapose_conv_bwd_ws_bytes(desc) bytes (< 0: geometry unsupported); compute calls never allocate.
+ * udapose_conv_bwd_prepare builds the device tables these calls use (outside stream capture). */
+long long udapose_conv_bwd_ws_bytes(const udapose_conv_desc* d);
+int udapose_conv_bwd_prepare(const udapose_conv_desc* d);
+/* dP [N][Hl+2][Wl+2][Ci] = data gradient of the conv on the padded grid (w_bwd: [Ci][9][Co] as for udapose_conv2d_bwd_data) */
+int udapose_conv2d_bwd_data_reflect_padded(void* stream, const udapose_conv_desc* d, const void* dy, const void* w_bwd, void* dP);
+/* dx [N][H][W][C] = mask * (fold(dP) + style term + content term + add), each optional (NULL):
+ *   fold: reflection adjoint of dP [N][Hl+2][Wl+2][C] then, with upsample, the sum of each 2x2 block;
+ *   style term (mean/std loss): gscale_s[0] * 2/(N*C) * [(m - m_t)/HW + (sd - sd_t) * (x - m) / ((HW - 1) * sd)] with
+ *     stats [N][C][4] = (m, sd, m_t, sd_t) of x and of the target (udapose_adain's statistics output);
+ *   content term: gscale_c[0] * c_scale * (x - t);  add: fp32 NCHW [N][add_c][H][W] added to channels < add_c;
+ *   relu_mask != 0: multiplied by (x > 0).  gscale_* are device scalars (no host synchronisation).  term_scale multiplies the style,
+ *   content and add terms: a constant gradient scale that keeps 16-bit (fp16) gradients out of the subnormal range; the weight and
+ *   bias gradient calls take its inverse as out_scale. */
+int udapose_reflect_fold(void* stream, const void* dP, int upsample, const void* x, int relu_mask, const float* stats, const float* gscale_s,
+                         const void* t, const float* gscale_c, float c_scale, const float* add_nchw, int add_c, void* dx, int N, int H, int W, int C,
+                         float term_scale);
+/* dx [N][Hi][Wi][Ci] = padded dgrad + fold, masked by relu_src > 0 when relu_src != NULL */
+int udapose_conv2d_bwd_data_reflect(void* stream, const udapose_conv_desc* d, const void* dy, const void* w_bwd, void* dx, const void* relu_src,
+                                    void* ws);
+/* dw fp32 [co_valid][Ci][3][3] (torch Conv2d layout) = out_scale * sum over pixels of dy x the reflect/upsample-gathered input x */
+int udapose_conv2d_bwd_weight_reflect(void* stream, const udapose_conv_desc* d, const void* dy, const void* x, float* dw, int co_valid, void* ws,
+                                      float out_scale);
+/* MaxPool2d(2, 2, ceil_mode=True) backward from the saved input x [N][H][W][C]: each output gradient goes to the first maximum of its
+ * window in scan order (torch's tie rule); relu_mask != 0 also applies (x > 0) */
+int udapose_maxpool2x2_ceil_bwd(void* stream, const void* x, const void* dy, void* dx, int N, int H, int W, int C, int relu_mask);
+/* db[c] = out_scale * sum over the M rows of dy [M][C] (C <= 2048), c < c_valid; ws: udapose_bias_grad_ws_bytes(M, C) bytes */
+long long udapose_bias_grad_ws_bytes(long long M, int C);
+int udapose_bias_grad(void* stream, const void* dy, float* db, long long M, int C, int c_valid, void* ws, float out_scale);
+/* out[0] = mean((a - b)^2) over n elements (n % 8 == 0); ws: udapose_feat_mse_ws_bytes() bytes */
+long long udapose_feat_mse_ws_bytes(void);
+int udapose_feat_mse_fwd(void* stream, const void* a, const void* b, long long n, float* out, void* ws);
+/* out[0] (+)= (sum_r (m - m_t)^2 + (sd - sd_t)^2) / R over stats [R][4] (the mean/std style-loss term) */
+int udapose_style_stat_loss(void* stream, const float* stats, int R, float* out, int accumulate);
+
 /* ---------------------------------------------------------------- batched nearest inverse-affine re-warp
  * (torchvision.transforms.functional.affine x3 per sample, train_human.py:366-368,388-390,412,421-423): NCHW fp32;
  * theta [N][nstage][6] = the inverse affine matrices in application order; backward != 0: src = d(out), dst = d(in). */

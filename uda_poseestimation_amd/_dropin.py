@@ -66,3 +66,22 @@ def install(reference_root=None):
         if ref_lib not in mods["lib"].__path__:
             mods["lib"].__path__.append(ref_lib)
     return mods
+
+
+# the reference's adain/ pre-training scripts (adain/train/train_*.py) import `net` and `function` as top-level modules; these generic
+# names are registered only on request, never by alias() / install()
+ADAIN_ALIASES = {
+    "net": _PKG + ".adain.net",
+    "function": _PKG + ".adain.function",
+}
+
+
+def alias_adain():
+    """Register `net` and `function` for this package's adain modules (`from net import decoder, vgg, Net`); returns {name: module}."""
+    _package()
+    out = {}
+    for ref_name, target in ADAIN_ALIASES.items():
+        mod = importlib.import_module(target)
+        sys.modules[ref_name] = mod
+        out[ref_name] = mod
+    return out

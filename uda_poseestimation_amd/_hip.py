@@ -136,6 +136,18 @@ _SIGS = {
     "udapose_prof_end": (ci, [vp]),
     "udapose_affine_nearest": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci]),
     "udapose_recon_thetas": (ci, [vp, vp, ci, cd, vp, vp]),
+    "udapose_conv_bwd_ws_bytes": (ll, [vp]),
+    "udapose_conv_bwd_prepare": (ci, [vp]),
+    "udapose_conv2d_bwd_data_reflect_padded": (ci, [vp, vp, vp, vp, vp]),
+    "udapose_reflect_fold": (ci, [vp, vp, ci, vp, ci, vp, vp, vp, vp, cf, vp, ci, vp, ci, ci, ci, ci, cf]),
+    "udapose_conv2d_bwd_data_reflect": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+    "udapose_conv2d_bwd_weight_reflect": (ci, [vp, vp, vp, vp, vp, ci, vp, cf]),
+    "udapose_maxpool2x2_ceil_bwd": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci]),
+    "udapose_bias_grad_ws_bytes": (ll, [ll, ci]),
+    "udapose_bias_grad": (ci, [vp, vp, vp, ll, ci, ci, vp, cf]),
+    "udapose_feat_mse_ws_bytes": (ll, []),
+    "udapose_feat_mse_fwd": (ci, [vp, vp, vp, ll, vp, vp]),
+    "udapose_style_stat_loss": (ci, [vp, vp, ci, vp, ci]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

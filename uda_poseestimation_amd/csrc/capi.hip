@@ -18,6 +18,21 @@ int pw_bn_bwd_pre(hipStream_t, const void*, int, const elem_t*, elem_t*, size_t,
 int pw_bn_bwd(hipStream_t, const void*, int, const elem_t*, const elem_t*, elem_t*, elem_t*, size_t, int, const float*, const float*, const float*, int,
               float*, float*, float*, float*, float, const float*, int);
 int pw_maxpool3x3s2_fwd(hipStream_t, const elem_t*, elem_t*, unsigned char*, int, int, int, int);
+
+// adain_train.hip (the AdaIN decoder's training step)
+size_t conv_bwd_ws_bytes(const ConvGeom& g);
+int conv_bwd_prepare(const ConvGeom& g);
+int conv_dgrad_reflect_padded(hipStream_t s, const ConvGeom& g, const elem_t* dy, const elem_t* w_bwd, elem_t* dP);
+int reflect_fold(hipStream_t s, const elem_t* dP, int up, const elem_t* x, int mask, const float* stats, const float* gs_s, const elem_t* t,
+                 const float* gs_c, float c_scale, const float* add_nchw, int add_c, elem_t* dx, int N, int H, int W, int C, float term_scale);
+int conv_dgrad_reflect(hipStream_t s, const ConvGeom& g, const elem_t* dy, const elem_t* w_bwd, elem_t* dx, const elem_t* mask_src, void* ws);
+int conv_wgrad_reflect(hipStream_t s, const ConvGeom& g, const elem_t* dy, const elem_t* x, float* dw, int co_valid, void* ws, float out_scale);
+int maxpool2x2_ceil_bwd(hipStream_t s, const elem_t* x, const elem_t* dy, elem_t* dx, int N, int H, int W, int C, int mask);
+size_t bias_grad_ws_bytes(long long M, int C);
+int bias_grad(hipStream_t s, const elem_t* dy, float* db, long long M, int C, int c_valid, void* ws, float out_scale);
+size_t feat_mse_ws_bytes();
+int feat_mse_fwd(hipStream_t s, const elem_t* a, const elem_t* b, long long n, float* out, void* ws);
+int style_stat_loss(hipStream_t s, const float* stats, int R, float* out, int accumulate);
 int pw_maxpool3x3s2_bwd(hipStream_t, const elem_t*, const unsigned char*, elem_t*, int, int, int, int);
 int pw_maxpool2x2_ceil(hipStream_t, const elem_t*, elem_t*, int, int, int, int);
 int hm_sqdiff_rows(hipStream_t, const float*, const float*, const float*, const unsigned char*, int, int, float, float*, float*,
@@ -461,5 +476,50 @@ int udapose_draw_labelmap_ori(void* stream, const float* pt, const float* vis, c
 }
 void udapose_prof_begin(void) { prof_begin(); }
 int udapose_prof_end(double* h_out9) { return prof_end(h_out9); }
+
+long long udapose_conv_bwd_ws_bytes(const udapose_conv_desc* d) {
+    if (!d) return UDAPOSE_ERR_ARG;
+    Geom G(d);
+    const size_t b = conv_bwd_ws_bytes(G.g);
+    return b ? (long long)b : UDAPOSE_ERR_UNSUPPORTED;
+}
+int udapose_conv_bwd_prepare(const udapose_conv_desc* d) { if (!d) return UDAPOSE_ERR_ARG; Geom G(d); return conv_bwd_prepare(G.g); }
+int udapose_conv2d_bwd_data_reflect_padded(void* stream, const udapose_conv_desc* d, const void* dy, const void* w_bwd, void* dP) {
+    if (!d) return UDAPOSE_ERR_ARG;
+    Geom G(d);
+    return conv_dgrad_reflect_padded(S(stream), G.g, CB16(dy), CB16(w_bwd), B16(dP));
+}
+int udapose_reflect_fold(void* stream, const void* dP, int upsample, const void* x, int relu_mask, const float* stats, const float* gscale_s,
+                         const void* t, const float* gscale_c, float c_scale, const float* add_nchw, int add_c, void* dx, int N, int H, int W, int C,
+                         float term_scale) {
+    return reflect_fold(S(stream), CB16(dP), upsample ? 1 : 0, CB16(x), relu_mask, stats, gscale_s, CB16(t), gscale_c, c_scale, add_nchw, add_c,
+                        B16(dx), N, H, W, C, term_scale);
+}
+int udapose_conv2d_bwd_data_reflect(void* stream, const udapose_conv_desc* d, const void* dy, const void* w_bwd, void* dx, const void* relu_src,
+                                    void* ws) {
+    if (!d || !dx) return UDAPOSE_ERR_ARG;
+    Geom G(d);
+    return conv_dgrad_reflect(S(stream), G.g, CB16(dy), CB16(w_bwd), B16(dx), CB16(relu_src), ws);
+}
+int udapose_conv2d_bwd_weight_reflect(void* stream, const udapose_conv_desc* d, const void* dy, const void* x, float* dw, int co_valid, void* ws,
+                                      float out_scale) {
+    if (!d) return UDAPOSE_ERR_ARG;
+    Geom G(d);
+    return conv_wgrad_reflect(S(stream), G.g, CB16(dy), CB16(x), dw, co_valid, ws, out_scale);
+}
+int udapose_maxpool2x2_ceil_bwd(void* stream, const void* x, const void* dy, void* dx, int N, int H, int W, int C, int relu_mask) {
+    return maxpool2x2_ceil_bwd(S(stream), CB16(x), CB16(dy), B16(dx), N, H, W, C, relu_mask);
+}
+long long udapose_bias_grad_ws_bytes(long long M, int C) { return (long long)bias_grad_ws_bytes(M, C); }
+int udapose_bias_grad(void* stream, const void* dy, float* db, long long M, int C, int c_valid, void* ws, float out_scale) {
+    return bias_grad(S(stream), CB16(dy), db, M, C, c_valid, ws, out_scale);
+}
+long long udapose_feat_mse_ws_bytes(void) { return (long long)feat_mse_ws_bytes(); }
+int udapose_feat_mse_fwd(void* stream, const void* a, const void* b, long long n, float* out, void* ws) {
+    return feat_mse_fwd(S(stream), CB16(a), CB16(b), n, out, ws);
+}
+int udapose_style_stat_loss(void* stream, const float* stats, int R, float* out, int accumulate) {
+    return style_stat_loss(S(stream), stats, R, out, accumulate);
+}
 
 }  // extern "C"

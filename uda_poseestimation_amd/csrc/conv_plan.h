@@ -100,6 +100,10 @@ int igemm_stat_rows(int M, int Co, int nclass, int tile);
 int igemm_launch(IgParams& p, int tile, hipStream_t stream, const Policy& pol);
 int wgrad_pick_tile(int Rdim, int Cdim, int smallc, const Policy& pol);
 int wgrad_launch(WgParams& p, int tile, int accumulate, hipStream_t stream, const Policy& pol);
+// bit-reproducible per-layer form: split bz of the pixel reduction stores its partial tile at bz * Co*wtaps*Ci floats of `parts`
+// (wgrad_parts_plan: the split count and tile of a problem; the caller adds the splits in split order)
+int wgrad_parts_plan(int M, int Ci, int Co, int total_taps, int* tile_out);
+int wgrad_launch_parts(WgParams& p, float* parts, hipStream_t stream);
 // Grouped wgrad (many layers, one launch per tile class).  wgrad_group_plan completes p for the group kernels and returns
 // the tile class (0 = 128x128, 1 = 64x64) or < 0 when the layer needs its own launch; stages_per_block bounds a work-group's
 // pixel range (longer reductions are split and accumulated with fp32 atomics into a zeroed dW).

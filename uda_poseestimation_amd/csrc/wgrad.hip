@@ -1005,3 +1005,33 @@ int wgrad_group_launch(hipStream_t stream, int tile, const WgParams* d_tab, cons
     if (tile == 0) return launch_wd_group<128, 128, 2, 2, 2, 32>(d_tab, d_blk, per_xcd, x_base, dy_base, dw_base, stream, d_tab2, d_blk2, x_base2, dy_base2, dw_base2);
     return launch_wd_group<64, 64, 2, 2, 2, 64>(d_tab, d_blk, per_xcd, x_base, dy_base, dw_base, stream, d_tab2, d_blk2, x_base2, dy_base2, dw_base2);
 }
+
+// Bit-reproducible per-layer form (adain_train.hip: the style decoder's weight gradients).  The pixel reduction is split like
+// wgrad_launch's, but split bz stores its partial tile with plain stores at element offset bz * part_stride of `parts` (the
+// grouped launches' partial-tile form); the caller adds the splits in split order.  LDS-DMA tiles only (Ci, Co multiples of 64),
+// through the same kernel instantiations as wgrad_launch: no new kernel.
+int wgrad_parts_plan(int M, int Ci, int Co, int total_taps, int* tile_out) {
+    const int tile = (Co >= 128 && Ci >= 128 && total_taps >= 9) ? 0 : 1;
+    const int RT = tile == 0 ? 128 : 64;
+    const long tiles = (long)((Co + RT - 1) / RT) * ((Ci + RT - 1) / RT) * total_taps;
+    const int ms_total = (M + 63) / 64;
+    const int min_stages = tile == 0 ? 16 : 4;
+    int ks = 1;
+    while (ks < 64 && tiles * ks < 512 && ms_total / (ks * 2) >= min_stages) ks *= 2;
+    if (tile_out) *tile_out = tile;
+    return ks;
+}
+
+int wgrad_launch_parts(WgParams& p, float* parts, hipStream_t stream) {
+    if (p.Ci % 64 || p.Co % 64 || (p.flags & (IG_FLAG_SMALLC | WG_FLAG_SWAP | WG_FLAG_ROW3_OK))) return UDAPOSE_ERR_ARG;
+    int tile = 1;
+    const int ks = wgrad_parts_plan(p.M, p.Ci, p.Co, p.total_taps, &tile);
+    p.div_hw = make_fastdiv((uint32_t)(p.Hg * p.Wg));
+    p.div_w = make_fastdiv((uint32_t)p.Wg);
+    p.ksplit = ks;
+    p.msteps_per_split = ((p.M + 63) / 64 + ks - 1) / ks;
+    p.dw = parts;
+    p.part_stride = (unsigned)((size_t)p.Co * p.wtaps * p.Ci);
+    p.flags &= ~(WG_FLAG_ATOMIC | WG_FLAG_FASTGEO | WG_FLAG_FAST2 | WG_FLAG_ROW3);
+    return tile == 0 ? launch_wd<128, 128, 2, 2, 2>(p, stream) : launch_wd<64, 64, 2, 2, 4>(p, stream);
+}

@@ -266,3 +266,91 @@ def adain(content, style, alpha=1.0, eps=1e-5, want_stats=False, stats_only=Fals
     if stats_only:
         return st
     return (out, st) if want_stats else out
+
+
+# ---- AdaIN decoder training (adain/net.py of the reference; include/udapose.h "AdaIN decoder training").  16-bit NHWC tensors; the
+# reflect-conv calls take a descriptor with reflect=1, pad=1, K=3 (Ci, Co multiples of 64) and a workspace of conv_bwd_ws_bytes(d) bytes.
+def conv_bwd_ws_bytes(d):
+    n = lib().udapose_conv_bwd_ws_bytes(C.byref(d))
+    if n < 0:
+        raise RuntimeError(f"conv_bwd_ws_bytes: geometry unsupported ({n})")
+    return n
+
+
+def conv_bwd_prepare(d, dtype=torch.bfloat16):
+    """builds the device tables of the reflect-conv backward calls in the build of `dtype` (outside stream capture)"""
+    check(lib("fp16" if dtype == torch.float16 else "bf16").udapose_conv_bwd_prepare(C.byref(d)), "conv_bwd_prepare")
+
+
+def conv2d_bwd_data_reflect_padded(dy, w_bwd, d, dP):
+    """dP [N, Hl+2, Wl+2, Ci]: the data gradient on the reflect-padded grid (reflect_fold folds it back)."""
+    require_cuda(dy, w_bwd, dP)
+    check(lib_for(dy).udapose_conv2d_bwd_data_reflect_padded(stream(), C.byref(d), ptr(dy), ptr(w_bwd), ptr(dP)), "conv2d_bwd_data_reflect_padded")
+    return dP
+
+
+def reflect_fold(dx, dP=None, upsample=False, x=None, relu_mask=False, stats=None, gscale_s=None, t=None, gscale_c=None, c_scale=0.0,
+                 add_nchw=None, term_scale=1.0):
+    """dx [N,H,W,C] = mask * (fold(dP) + term_scale * (style term + content term + add)) (udapose_reflect_fold)."""
+    N, H, W, C_ = dx.shape
+    add_c = add_nchw.shape[1] if add_nchw is not None else 0
+    check(lib_for(dx).udapose_reflect_fold(stream(), ptr(dP), int(upsample), ptr(x), int(relu_mask), ptr(stats), ptr(gscale_s), ptr(t), ptr(gscale_c),
+                                           float(c_scale), ptr(add_nchw), add_c, ptr(dx), N, H, W, C_, float(term_scale)), "reflect_fold")
+    return dx
+
+
+def conv2d_bwd_data_reflect(dy, w_bwd, d, ws, relu_src=None):
+    require_cuda(dy, w_bwd, ws)
+    dx = torch.empty(d.N, d.Hi, d.Wi, d.Ci, dtype=dy.dtype, device=dy.device)
+    check(lib_for(dy).udapose_conv2d_bwd_data_reflect(stream(), C.byref(d), ptr(dy), ptr(w_bwd), ptr(dx), ptr(relu_src), ptr(ws)), "conv2d_bwd_data_reflect")
+    return dx
+
+
+def conv2d_bwd_weight_reflect(dy, x, d, ws, co_valid=None, dw=None, out_scale=1.0):
+    """dw fp32 [co_valid, Ci, 3, 3] (torch layout) times out_scale, bit-reproducible."""
+    require_cuda(dy, x, ws)
+    co_valid = d.Co if co_valid is None else co_valid
+    if dw is None:
+        dw = torch.empty(co_valid, d.Ci, 3, 3, dtype=torch.float32, device=x.device)
+    check(lib_for(x).udapose_conv2d_bwd_weight_reflect(stream(), C.byref(d), ptr(dy), ptr(x), ptr(dw), co_valid, ptr(ws), float(out_scale)), "conv2d_bwd_weight_reflect")
+    return dw
+
+
+def maxpool2x2_ceil_bwd(x, dy, relu_mask=False, dx=None):
+    N, H, W, C_ = x.shape
+    if dx is None:
+        dx = torch.empty_like(x)
+    check(lib_for(x).udapose_maxpool2x2_ceil_bwd(stream(), ptr(x), ptr(dy), ptr(dx), N, H, W, C_, int(relu_mask)), "maxpool2x2_ceil_bwd")
+    return dx
+
+
+def bias_grad_ws_bytes(M, C_):
+    return lib().udapose_bias_grad_ws_bytes(M, C_)
+
+
+def bias_grad(dy, ws, c_valid=None, db=None, out_scale=1.0):
+    """db [c_valid] fp32 = out_scale * column sums of dy [.., C] (bit-reproducible)."""
+    C_ = dy.shape[-1]
+    c_valid = C_ if c_valid is None else c_valid
+    if db is None:
+        db = torch.empty(c_valid, dtype=torch.float32, device=dy.device)
+    check(lib_for(dy).udapose_bias_grad(stream(), ptr(dy), ptr(db), dy.numel() // C_, C_, c_valid, ptr(ws), float(out_scale)), "bias_grad")
+    return db
+
+
+def feat_mse_ws_bytes():
+    return lib().udapose_feat_mse_ws_bytes()
+
+
+def feat_mse(a, b, ws, out=None):
+    assert a.shape == b.shape and a.dtype == b.dtype
+    if out is None:
+        out = torch.empty((), dtype=torch.float32, device=a.device)
+    check(lib_for(a).udapose_feat_mse_fwd(stream(), ptr(a), ptr(b), a.numel(), ptr(out), ptr(ws)), "feat_mse_fwd")
+    return out
+
+
+def style_stat_loss(stats, out, accumulate=False):
+    """out (+)= mean over (n, c) of (m - m_t)^2 + (sd - sd_t)^2, stats [N, C, 4] from adain(..., stats_only=True)."""
+    check(lib().udapose_style_stat_loss(stream(), ptr(stats), stats.numel() // 4, ptr(out), int(accumulate)), "style_stat_loss")
+    return out
