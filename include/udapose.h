@@ -192,7 +192,16 @@ typedef void* udapose_net_t;
 /* fp32 == 1: fp32 activations and exact fp32 MFMA, FORWARD ONLY (the reference runs the teacher and validate() in fp32,
  * train_human.py:347-358,461-500); fp32 == 2: the fast fp32-grade form of the same (f16x2 split activations and weight packs,
  * UDAPOSE_EPI_SPLIT; pre-BatchNorm conv outputs and statistics in fp32), FORWARD ONLY; fp32 == 0: the library's 16-bit
- * element type with fp32 accumulation, forward and backward. */
+ * element type with fp32 accumulation, forward and backward.
+ * fp32 == 3 ('strict', the fp16 build only; not with bit 9): a DIFFERENTIABLE plan with the fp32-grade forward of fp32 == 2 and the
+ * 16-bit backward of fp32 == 0.  Its forward's outputs and BatchNorm statistics are bit for bit those of fp32 == 2; its BN apply,
+ * max-pool and image conversion launches also write, in the same pass, the fp16 tensors the 16-bit backward reads (pre-BN y rounded
+ * from the fp32 y, post-BN z = the h half of the split z, the block outputs' ReLU bit mask, the pooled map and its taps, the 8-channel
+ * image) at the offsets of the fp32 == 0 layout, so udapose_net_backward* run unchanged.  The backward is therefore NOT fp32-grade:
+ * its gradients are those of the fp16 backward evaluated at fp32-grade activations, and need loss scaling as in fp32 == 0.  The
+ * forward's split / fp32 tensors live in one set of scratch slots inside the plan's own arena (udapose_net_act_bytes: the 16-bit
+ * arena + ~0.6 GB at N = 32, 256x256).  Weight packs: split forward packs and 16-bit data-gradient packs; udapose_net_fused_update
+ * writes the latter in its sweep and refreshes the former with one pack launch after it (same job table as udapose_net_pack_weights). */
 /* bit 8 of `fp32` (value | 0x100): the three deconvolutions carry a bias parameter (`deconv_with_bias=True`, lib/models/pose_resnet.py:
  * 15,41,96) - parameter order weight, bias, then the BatchNorm's, as in the reference's Upsampling. */
 /* bit 9 of `fp32` (value | 0x200): a FORWARD-ONLY plan (the teacher's forwards under torch.no_grad(), train_human.py:346-372, and

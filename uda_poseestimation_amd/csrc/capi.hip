@@ -44,7 +44,7 @@ int pw_maxpool2x2_ceil_f32(hipStream_t, const float*, float*, int, int, int, int
 int pw_nchw_f32_to_nhwc_f32(hipStream_t, const float*, float*, int, int, int, int);
 int adain_launch_f32(hipStream_t, const float*, const float*, float*, int, int, int, int, float, float, const float*, float*);
 int adain_launch_split(hipStream_t, const void*, const void*, void*, int, int, int, int, float, float, const float*, float*);
-int pw_nchw_f32_to_nhwc_split(hipStream_t, const float*, void*, int, int, int, int);
+int pw_nchw_f32_to_nhwc_split(hipStream_t, const float*, void*, int, int, int, int, void* = nullptr);
 int pw_f32_to_split(hipStream_t, const float*, void*, size_t);
 int pw_split_to_f32(hipStream_t, const void*, float*, size_t);
 int pw_maxpool2x2_ceil_split(hipStream_t, const void*, void*, int, int, int, int);

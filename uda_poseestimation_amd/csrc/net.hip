@@ -6,6 +6,9 @@
 // Data layout in HBM: activations NHWC bf16 (pre-BN conv output y and post-BN/ReLU z both kept for backward), weights
 // bf16 packed [Co][taps][Ci] (fprop) and [Ci][taps][Co] (dgrad) from the fp32 channels_last master copies, BN statistics
 // fp32.  Parameters are addressed by index in torch `.parameters()` order, buffers in `.buffers()` order.
+// 'strict' plans (mode 3) run the f16x2 forward and the 16-bit backward: every offset below that the backward reads (y_off, z_off,
+// in_off, mask_off, pool_off, poolidx_off, x8_off, save_off) holds the fp16 tensor of the 16-bit layout, written by the forward's own
+// apply / pool / conversion launches next to the fp32-grade tensor; the fp32-grade tensors (the f* offsets) live only in the forward.
 #include <algorithm>
 #include <deque>
 #include <cstdio>
@@ -50,14 +53,14 @@ int pw_transpose_f32(hipStream_t, const float*, float*, int, int, int);
 int pw_pack_strided_f32(hipStream_t, const float*, float*, int, int, int, int, int, int, long, long, long, long);
 int pw_bn_apply_f32(hipStream_t, const float*, const float*, float*, size_t, int, const float*, const float*, int);
 int pw_maxpool3x3s2_fwd_f32(hipStream_t, const float*, float*, unsigned char*, int, int, int, int);
-int pw_nchw_f32_to_nhwc_split(hipStream_t, const float*, void*, int, int, int, int);
+int pw_nchw_f32_to_nhwc_split(hipStream_t, const float*, void*, int, int, int, int, void*);
 int pw_f32_to_split(hipStream_t, const float*, void*, size_t);
 int pw_transpose_split(hipStream_t, const float*, void*, int, int, int);
 int pw_pack_strided_split(hipStream_t, const float*, void*, int, int, int, int, int, int, long, long, long, long);
-int pw_bn_apply_split(hipStream_t, const float*, const void*, void*, size_t, int, const float*, const float*, int);
+int pw_bn_apply_split(hipStream_t, const float*, const void*, void*, size_t, int, const float*, const float*, int, void*, void*, unsigned char*, int);
 int pw_bn_train_fused_split(hipStream_t, const float*, const void*, void*, size_t, int, const float*, int, const float*, const float*, float*, float*,
-                            long long*, float, float, float*, int, int);
-int pw_maxpool3x3s2_fwd_split(hipStream_t, const void*, void*, unsigned char*, int, int, int, int);
+                            long long*, float, float, float*, int, int, void*, void*, unsigned char*);
+int pw_maxpool3x3s2_fwd_split(hipStream_t, const void*, void*, unsigned char*, int, int, int, int, void*);
 
 namespace {
 
@@ -78,6 +81,7 @@ struct ConvL {
     size_t wf_off = 0, wb_off = 0;   // bf16 packs inside wpack (bytes)
     size_t in_off = 0;      // activation arena offset of the input (bytes)
     size_t y_off = 0;       // pre-BN output
+    size_t fin_off = 0, fy_off = 0;     // what the FORWARD reads / writes: in_off / y_off, except in 'strict' plans (split input, fp32 y)
     size_t dy_off = 0;      // workspace offset of this layer's own dy buffer (backward)
 };
 struct BnL {
@@ -87,6 +91,7 @@ struct BnL {
     size_t save_off = 0;    // fp32 [3][C] saved mean / invstd / unbiased var in the arena
     size_t z_off = 0;       // post-BN(-ReLU) output
     size_t mask_off = 0;    // bn3 of a block: ReLU bit mask of z (one byte per 8 channels), what the data gradients read instead of z
+    size_t fz_off = 0;      // what the forward writes: z_off, except in 'strict' plans (split z)
     size_t npix = 0;
 };
 struct Block {
@@ -94,6 +99,7 @@ struct Block {
     BnL b1, b2, b3, bd;
     bool has_ds = false;
     size_t in_off = 0, zd_off = 0;
+    size_t fin_off = 0, fzd_off = 0;    // (the forward's residual inputs, as ConvL::fin_off)
     size_t npix_in = 0;
 };
 
@@ -104,6 +110,9 @@ struct Net {
     int f32 = 0;            // 1: fp32 storage + exact fp32 MFMA (forward only: the reference's teacher / validate() precision)
                             // 2: f16x2 split storage (common.h), three fp16 MFMAs per K step: the FAST fp32-grade mode (forward only);
                             //    conv inputs (z, pooled map, image) and weight packs are split tensors, pre-BN conv outputs y are fp32
+    int strict = 0;         // mode 3 ('strict', f32 == 2 as well): the f16x2 forward of a differentiable plan whose backward is the 16-bit one.
+                            // The 16-bit layout is bump-allocated as in mode 0; the forward's split / fp32 tensors (f* offsets) are mapped onto
+                            // the six scratch slots of the forward-only plans (inside this plan's arena), since nothing reads them after the forward
     int fwd_only = 0;       // forward-only plan (mode bit 9; the teacher's no-grad forwards, validate()): nothing is kept for a backward, so the
                             // pre-BN outputs y and the post-BN outputs z of all layers rotate through SIX scratch buffers (y | block input | block
                             // output | bn1 output | bn2 output | downsample output) instead of a bump-allocated arena - layer after layer rewrites the same
@@ -116,6 +125,7 @@ struct Net {
     // stem
     ConvL stem; BnL stem_bn;
     size_t x8_off = 0, pool_off = 0, poolidx_off = 0;
+    size_t fx8_off = 0, fpool_off = 0;    // (the forward's image / pooled map: x8_off / pool_off, except in 'strict' plans)
     int Hs = 0, Ws = 0, Hp = 0, Wp = 0;
     std::vector<Block> blocks;
     ConvL up[3]; BnL up_bn[3];
@@ -169,17 +179,21 @@ size_t sc_take(Net& n, int slot, size_t bytes) {
     if (n.sc.sizing) { n.sc.need[slot] = std::max(n.sc.need[slot], align_up(bytes)); return 0; }
     return n.sc.off[slot];
 }
-void add_conv(Net& n, ConvL& c, int Hi, int Wi, int Ci, int Co, int K, int stride, int pad, int transposed, size_t in_off, bool need_bwd_pack, int y_slot = -1) {
+// (in_off / fin_off: the input the backward / the forward reads, the same offset outside 'strict' plans)
+void add_conv(Net& n, ConvL& c, int Hi, int Wi, int Ci, int Co, int K, int stride, int pad, int transposed, size_t in_off, size_t fin_off, bool need_bwd_pack,
+              int y_slot = -1) {
     c.g = ConvGeom{n.N, Hi, Wi, Ci, Co, K, K, stride, pad, transposed, 0, 0};
     c.w_idx = n.n_params++;
     n.param_numel.push_back((long long)Co * (Ci == 8 ? 3 : Ci) * K * K);
     c.in_off = in_off;
+    c.fin_off = fin_off;
     const size_t welems = (size_t)Co * c.g.wtaps() * Ci;
     // fp32 mode reads plain-conv weights straight from the fp32 master ([Co][taps][Ci] is its physical layout)
-    if (n.f32 != 1 || c.g.smallc() || transposed) c.wf_off = wp_alloc(n, welems * n.es);
-    if (need_bwd_pack && !n.f32) c.wb_off = wp_alloc(n, welems * 2);
+    if (n.f32 != 1 || c.g.smallc() || transposed) c.wf_off = wp_alloc(n, welems * (n.f32 ? 4 : 2));
+    if (need_bwd_pack && (!n.f32 || n.strict)) c.wb_off = wp_alloc(n, welems * 2);
     const size_t ybytes = (size_t)n.N * c.g.Ho() * c.g.Wo() * Co * n.es;
     c.y_off = (n.fwd_only && y_slot >= 0) ? sc_take(n, y_slot, ybytes) : act_alloc(n, ybytes);
+    c.fy_off = n.strict ? sc_take(n, y_slot, (size_t)n.N * c.g.Ho() * c.g.Wo() * Co * 4) : c.y_off;
 }
 void add_bn(Net& n, BnL& b, int C, size_t npix, bool alloc_z = true, int z_slot = -1) {
     b.C = C;
@@ -188,16 +202,20 @@ void add_bn(Net& n, BnL& b, int C, size_t npix, bool alloc_z = true, int z_slot 
     b.rm_idx = n.n_buffers++; b.rv_idx = n.n_buffers++; b.nbt_idx = n.n_buffers++;
     b.save_off = act_alloc(n, (size_t)3 * C * 4);
     b.npix = npix;
-    if (alloc_z) b.z_off = (n.fwd_only && z_slot >= 0) ? sc_take(n, z_slot, npix * C * n.es) : act_alloc(n, npix * C * n.es);
+    if (alloc_z) {
+        b.z_off = (n.fwd_only && z_slot >= 0) ? sc_take(n, z_slot, npix * C * n.es) : act_alloc(n, npix * C * n.es);
+        b.fz_off = n.strict ? sc_take(n, z_slot, npix * C * 4) : b.z_off;
+    }
 }
 
 Net* build(const int layers[4], int K, int N, int H, int W, int mode) {
     Net* np = new Net();
     Net& n = *np;
-    const int f32 = mode & 0xff;          // (mode: low byte = precision 0 / 1 / 2, bit 8 = the deconvolutions carry a bias, bit 9 = forward-only plan)
+    const int f32 = mode & 0xff;          // (mode: low byte = precision 0 / 1 / 2 / 3, bit 8 = the deconvolutions carry a bias, bit 9 = forward-only plan)
     n.deconv_bias = (mode >> 8) & 1;
-    n.f32 = f32 == 2 ? 2 : (f32 ? 1 : 0);
-    n.es = f32 ? 4 : 2;
+    n.strict = f32 == 3;
+    n.f32 = f32 >= 2 ? 2 : (f32 ? 1 : 0);
+    n.es = (f32 && !n.strict) ? 4 : 2;    // (bytes per element of the tensors at the backward's offsets; a strict plan's are fp16)
     for (int i = 0; i < 4; ++i) n.layers[i] = layers[i];
     n.K = K; n.N = N; n.H = H; n.W = W;
     n.fwd_only = (mode >> 9) & 1;
@@ -209,14 +227,16 @@ Net* build(const int layers[4], int K, int N, int H, int W, int mode) {
     auto layout = [&](Net& n) {
     const bool fo = n.fwd_only != 0;
     n.x8_off = fo ? sc_take(n, SC_DS, (size_t)N * H * W * 8 * n.es) : act_alloc(n, (size_t)N * H * W * 8 * n.es);
+    n.fx8_off = n.strict ? sc_take(n, SC_DS, (size_t)N * H * W * 8 * 4) : n.x8_off;
     // stem: conv 7x7 s2 p3 (3 -> padded 8 input channels), bn, relu, maxpool 3x3 s2 p1
-    add_conv(n, n.stem, H, W, 8, 64, 7, 2, 3, 0, n.x8_off, false, SC_Y);
+    add_conv(n, n.stem, H, W, 8, 64, 7, 2, 3, 0, n.x8_off, n.fx8_off, false, SC_Y);
     n.Hs = n.stem.g.Ho(); n.Ws = n.stem.g.Wo();
     add_bn(n, n.stem_bn, 64, (size_t)N * n.Hs * n.Ws, true, SC_B);
     n.Hp = (n.Hs + 2 - 3) / 2 + 1; n.Wp = (n.Ws + 2 - 3) / 2 + 1;
     n.pool_off = fo ? sc_take(n, SC_A, (size_t)N * n.Hp * n.Wp * 64 * n.es) : act_alloc(n, (size_t)N * n.Hp * n.Wp * 64 * n.es);
     n.poolidx_off = fo ? sc_take(n, SC_MID, (size_t)N * n.Hp * n.Wp * 64) : act_alloc(n, (size_t)N * n.Hp * n.Wp * 64);      // (written, never read, by a forward-only plan)
-    size_t cur = n.pool_off;
+    n.fpool_off = n.strict ? sc_take(n, SC_A, (size_t)N * n.Hp * n.Wp * 64 * 4) : n.pool_off;
+    size_t cur = n.pool_off, fcur = n.fpool_off;
     int cur_slot = SC_A;
     int Hc = n.Hp, Wc = n.Wp, Cc = 64;
     const int planes[4] = {64, 128, 256, 512};
@@ -227,46 +247,50 @@ Net* build(const int layers[4], int K, int N, int H, int W, int mode) {
             const int P = planes[L], stride = (bi == 0 && L > 0) ? 2 : 1;
             const int out_slot = cur_slot == SC_A ? SC_B : SC_A;
             b.in_off = cur;
+            b.fin_off = fcur;
             b.npix_in = (size_t)N * Hc * Wc;
             b.has_ds = (bi == 0);
             // parameter order follows torchvision Bottleneck: conv1,bn1,conv2,bn2,conv3,bn3,(downsample.0, downsample.1)
-            add_conv(n, b.c1, Hc, Wc, Cc, P, 1, 1, 0, 0, cur, true, SC_Y);
+            add_conv(n, b.c1, Hc, Wc, Cc, P, 1, 1, 0, 0, cur, fcur, true, SC_Y);
             add_bn(n, b.b1, P, (size_t)N * Hc * Wc, true, SC_MID);
-            add_conv(n, b.c2, Hc, Wc, P, P, 3, stride, 1, 0, b.b1.z_off, true, SC_Y);
+            add_conv(n, b.c2, Hc, Wc, P, P, 3, stride, 1, 0, b.b1.z_off, b.b1.fz_off, true, SC_Y);
             const int Ho = b.c2.g.Ho(), Wo = b.c2.g.Wo();
             add_bn(n, b.b2, P, (size_t)N * Ho * Wo, true, SC_MID2);     // (its own slot: with eval_fold conv2 reads z1 and writes z2 in one launch)
-            add_conv(n, b.c3, Ho, Wo, P, P * 4, 1, 1, 0, 0, b.b2.z_off, true, SC_Y);
+            add_conv(n, b.c3, Ho, Wo, P, P * 4, 1, 1, 0, 0, b.b2.z_off, b.b2.fz_off, true, SC_Y);
             add_bn(n, b.b3, P * 4, (size_t)N * Ho * Wo, true, out_slot);
-            if (!n.f32 && !fo) b.b3.mask_off = act_alloc(n, (size_t)N * Ho * Wo * (P * 4) / 8);     // (the ReLU bit mask is the backward's)
+            if ((!n.f32 || n.strict) && !fo) b.b3.mask_off = act_alloc(n, (size_t)N * Ho * Wo * (P * 4) / 8);     // (the ReLU bit mask is the backward's)
             if (b.has_ds) {
-                add_conv(n, b.cd, Hc, Wc, Cc, P * 4, 1, stride, 0, 0, cur, true, SC_Y);
+                add_conv(n, b.cd, Hc, Wc, Cc, P * 4, 1, stride, 0, 0, cur, fcur, true, SC_Y);
                 add_bn(n, b.bd, P * 4, (size_t)N * Ho * Wo, true, SC_DS);
                 b.zd_off = b.bd.z_off;
+                b.fzd_off = b.bd.fz_off;
             }
-            cur = b.b3.z_off; cur_slot = out_slot; Hc = Ho; Wc = Wo; Cc = P * 4;
+            cur = b.b3.z_off; fcur = b.b3.fz_off; cur_slot = out_slot; Hc = Ho; Wc = Wo; Cc = P * 4;
         }
     n.fc_w_idx = n.n_params++; n.param_numel.push_back(1000LL * 2048);
     n.fc_b_idx = n.n_params++; n.param_numel.push_back(1000);
     for (int i = 0; i < 3; ++i) {
-        add_conv(n, n.up[i], Hc, Wc, Cc, 256, 4, 2, 1, 1, cur, true, SC_Y);
+        add_conv(n, n.up[i], Hc, Wc, Cc, 256, 4, 2, 1, 1, cur, fcur, true, SC_Y);
         if (n.deconv_bias) { n.up[i].bias_idx = n.n_params++; n.param_numel.push_back(256); }      // (.parameters() order: weight, bias, then the BN)
         Hc = n.up[i].g.Ho(); Wc = n.up[i].g.Wo(); Cc = 256;
         cur_slot = cur_slot == SC_A ? SC_B : SC_A;
         add_bn(n, n.up_bn[i], 256, (size_t)N * Hc * Wc, true, cur_slot);
         cur = n.up_bn[i].z_off;
+        fcur = n.up_bn[i].fz_off;
     }
     // head: 1x1 conv with bias -> fp32
     n.head.g = ConvGeom{N, Hc, Wc, 256, K, 1, 1, 1, 0, 0, 0, 0};
     n.head.w_idx = n.n_params++; n.param_numel.push_back((long long)K * 256);
     n.head.bias_idx = n.n_params++; n.param_numel.push_back(K);
     n.head.in_off = cur;
-    n.head.wf_off = wp_alloc(n, (size_t)K * 256 * n.es);
+    n.head.fin_off = fcur;
+    n.head.wf_off = wp_alloc(n, (size_t)K * 256 * (n.f32 ? 4 : 2));
     n.head.wb_off = wp_alloc(n, (size_t)256 * 64 * 2);      // [256][1][64] zero-padded for dgrad
     n.head_out_off = fo ? sc_take(n, SC_Y, (size_t)N * Hc * Wc * K * 4) : act_alloc(n, (size_t)N * Hc * Wc * K * 4);
     n.Hout = Hc; n.Wout = Wc;
     return Hc * 65536 + Wc;
     };
-    if (n.fwd_only) {
+    if (n.fwd_only || n.strict) {
         Net dry = n;
         dry.sc.sizing = true;
         (void)layout(dry);
@@ -377,6 +401,10 @@ int conv_bn_fwd(hipStream_t s, const Net& n, const ConvL& c, const BnL& b, const
     e.bias = pre_bias;
     // block outputs: the apply also saves the ReLU bit mask of z (1/16 of z's bytes) for the data gradients that mask with it
     unsigned char* mask = (b.mask_off && n.policy.bn3_mask && relu) ? (unsigned char*)(act + b.mask_off) : nullptr;
+    // 'strict' training forwards: the split apply also writes the fp16 y, z (and mask) of the 16-bit layout for the backward
+    const bool sh = n.strict && training;
+    void* y16 = sh ? (void*)(act + c.y_off) : nullptr;
+    void* z16 = sh ? (void*)(act + b.z_off) : nullptr;
     const void* wptr = (n.f32 == 1 && !c.g.smallc() && !c.g.transposed) ? params[c.w_idx] : (const void*)(wpack + c.wf_off);
     const float* gamma = (const float*)params[b.g_idx];
     const float* beta = (const float*)params[b.b_idx];
@@ -389,9 +417,9 @@ int conv_bn_fwd(hipStream_t s, const Net& n, const ConvL& c, const BnL& b, const
         e.scale = scale; e.bias = shift; e.relu = relu;
         e.res = res;
         e.out_f32 = 0;                    // (z has the plan's storage type: 16-bit, fp32, or the f16x2 split form)
-        return conv_fprop(s, c.g, (const elem_t*)(act + c.in_off), (const elem_t*)wptr, act + b.z_off, e);
+        return conv_fprop(s, c.g, (const elem_t*)(act + c.fin_off), (const elem_t*)wptr, act + b.fz_off, e);
     }
-    CK(conv_fprop(s, c.g, (const elem_t*)(act + c.in_off), (const elem_t*)wptr, act + c.y_off, e));
+    CK(conv_fprop(s, c.g, (const elem_t*)(act + c.fin_off), (const elem_t*)wptr, act + c.fy_off, e));
     if (training && !n.f32 && !no_apply && !pre_bias) {
         // wide, small-spatial layers: finalize + apply in ONE launch (channel-chunked work-groups, pointwise.hip)
         const int took = pw_bn_train_fused(s, (const elem_t*)(act + c.y_off), res, (elem_t*)(act + b.z_off), b.npix, b.C, slab, conv_stat_rows(c.g), gamma,
@@ -401,9 +429,10 @@ int conv_bn_fwd(hipStream_t s, const Net& n, const ConvL& c, const BnL& b, const
         if (took) return UDAPOSE_OK;
     }
     if (training && n.f32 == 2 && !no_apply && !pre_bias) {
-        const int took = pw_bn_train_fused_split(s, (const float*)(act + c.y_off), res, act + b.z_off, b.npix, b.C, slab, conv_stat_rows(c.g), gamma, beta,
+        const int took = pw_bn_train_fused_split(s, (const float*)(act + c.fy_off), res, act + b.fz_off, b.npix, b.C, slab, conv_stat_rows(c.g), gamma, beta,
                                                  upd ? (float*)buffers[b.rm_idx] : nullptr, upd ? (float*)buffers[b.rv_idx] : nullptr,
-                                                 upd ? (long long*)buffers[b.nbt_idx] : nullptr, momentum, 1e-5f, save, relu, n.policy.bn_fwd_chunked | (n.policy.bn_xcd_rows ? (1 << 30) : 0));
+                                                 upd ? (long long*)buffers[b.nbt_idx] : nullptr, momentum, 1e-5f, save, relu, n.policy.bn_fwd_chunked | (n.policy.bn_xcd_rows ? (1 << 30) : 0),
+                                                 y16, z16, sh ? mask : nullptr);
         if (took < 0) return took;
         if (took) return UDAPOSE_OK;
     }
@@ -415,7 +444,8 @@ int conv_bn_fwd(hipStream_t s, const Net& n, const ConvL& c, const BnL& b, const
         CK(pw_bn_eval_coeff(s, b.C, gamma, beta, (const float*)buffers[b.rm_idx], (const float*)buffers[b.rv_idx], 1e-5f, scale, shift));
     if (no_apply) return UDAPOSE_OK;      // (the caller's next launch applies scale / shift itself: the stem's fused pool)
     if (n.f32 == 2)
-        return pw_bn_apply_split(s, (const float*)(act + c.y_off), res, act + b.z_off, b.npix * b.C, b.C, scale, shift, relu);
+        return pw_bn_apply_split(s, (const float*)(act + c.fy_off), res, act + b.fz_off, b.npix * b.C, b.C, scale, shift, relu, y16, z16, sh ? mask : nullptr,
+                                 n.policy.bn_xcd_rows >= 2);
     if (n.f32)
         return pw_bn_apply_f32(s, (const float*)(act + c.y_off), (const float*)res, (float*)(act + b.z_off), b.npix * b.C, b.C, scale, shift, relu);
     return pw_bn_apply(s, (const elem_t*)(act + c.y_off), res, (elem_t*)(act + b.z_off), b.npix * b.C, b.C, scale, shift, relu, mask, n.policy.bn_xcd_rows >= 2);
@@ -425,7 +455,9 @@ int conv_bn_fwd(hipStream_t s, const Net& n, const ConvL& c, const BnL& b, const
 
 // ============================================================================ public (C++) entry points
 void* net_create(const int layers[4], int K, int N, int H, int W, int mode) {
-    if (K < 1 || K > 64 || N < 1 || H % 32 || W % 32 || (mode & 0xff) > 2 || (mode >> 10)) return nullptr;
+    if (K < 1 || K > 64 || N < 1 || H % 32 || W % 32 || (mode & 0xff) > 3 || (mode >> 10)) return nullptr;
+    // 'strict' (3): differentiable by definition (not with the forward-only bit), and its backward is the fp16 build's (the shadows are fp16)
+    if ((mode & 0xff) == 3 && ((mode >> 9) & 1 || UDAPOSE_ELEM_KIND != 1)) return nullptr;
     return build(layers, K, N, H, W, mode);
 }
 void net_destroy(void* h) {
@@ -450,7 +482,7 @@ size_t net_ws_bytes(void* h) {
     // the partial tiles of the split weight-gradient reductions (policy wgrad_det) close the workspace: their size follows the policy's
     // split length, which udapose_net_set_policy may have changed since the plan was created - sized here, when the caller asks
     Net& n = *(Net*)h;
-    if (n.f32 || n.fwd_only || !n.policy.wgrad_group || !n.policy.wgrad_det) { n.ws_wgpart_bytes = 0; return n.ws_bytes; }
+    if ((n.f32 && !n.strict) || n.fwd_only || !n.policy.wgrad_group || !n.policy.wgrad_det) { n.ws_wgpart_bytes = 0; return n.ws_bytes; }
     n.ws_wgpart_bytes = wg_partial_bytes(n);
     return n.ws_bytes + n.ws_wgpart_bytes;
 }
@@ -465,7 +497,7 @@ void add_pack_jobs(const Net& n, const ConvL& c, const void* const* params, char
     elem_t* wf = (elem_t*)(wpack + c.wf_off);
     elem_t* wb = (elem_t*)(wpack + c.wb_off);
     const int sp = n.f32 == 2 ? 2 : 0;          // (kind bit 1: f16x2 split output, forward packs only)
-    if (sp) with_bwd = false;
+    if (sp && !n.strict) with_bwd = false;     // ('strict': split forward packs, 16-bit data-gradient packs)
     if (!g.transposed) {
         jobs.push_back(PackJobH{w, wf, 0, 0, 0, sp, (long long)g.Co * T * g.Ci});
         if (with_bwd) jobs.push_back(PackJobH{w, wb, g.Co, T, g.Ci, 1, 0});
@@ -537,7 +569,7 @@ int net_bind(void* h, const void* const* params, void* const* buffers, void* wpa
     { ConvGeom hg = n.head.g; CK(conv_prepare(hg)); hg.Co = 64; CK(conv_prepare(hg)); }
     if (n.f32 != 1) {
         CK(build_pack_table(n, n.pack_fwd, params, wpack, false));
-        CK(build_pack_table(n, n.pack_all, params, wpack, n.f32 == 0));
+        CK(build_pack_table(n, n.pack_all, params, wpack, n.f32 == 0 || n.strict));
     }
     if (buffers) CK(build_run_jobs(n, buffers));
     return UDAPOSE_OK;
@@ -549,7 +581,7 @@ int net_pack_weights(void* h, hipStream_t s, const void* const* params, void* wp
     char* wpack = (char*)wpack_;
     if (n.f32 != 1) {
         // ONE launch casts / transposes every weight through the job table net_bind built for these pointers
-        if (n.f32 == 2) with_bwd = 0;
+        if (n.f32 == 2 && !n.strict) with_bwd = 0;
         Net::PackTab& tab = with_bwd ? n.pack_all : n.pack_fwd;
         if (!tab.jobs || tab.key0 != params[0] || tab.key1 != params[n.n_params - 1] || tab.keyw != (const void*)wpack)
             return UDAPOSE_ERR_NOT_PREPARED;
@@ -584,7 +616,9 @@ int net_forward(void* h, hipStream_t s, const float* x_nchw, const void* const* 
     const char* wpack = (const char*)wpack_;
     char* act = (char*)act_;
     char* ws = (char*)ws_;
-    if (n.f32 == 2) CK(pw_nchw_f32_to_nhwc_split(s, x_nchw, act + n.x8_off, n.N, 3, n.H * n.W, 8));
+    // ('strict' training forwards: the conversion, the stem's max-pool and every BN apply also write the fp16 tensors of the 16-bit layout)
+    const bool sh = n.strict && training;
+    if (n.f32 == 2) CK(pw_nchw_f32_to_nhwc_split(s, x_nchw, act + n.fx8_off, n.N, 3, n.H * n.W, 8, sh ? act + n.x8_off : nullptr));
     else if (n.f32) CK(pw_nchw_f32_to_nhwc_f32(s, x_nchw, (float*)(act + n.x8_off), n.N, 3, n.H * n.W, 8));
     else CK(pw_nchw_f32_to_nhwc_bf16(s, x_nchw, (elem_t*)(act + n.x8_off), n.N, 3, n.H * n.W, 8));
     const bool stem_fused = n.policy.stem_fused && !n.f32;
@@ -593,7 +627,8 @@ int net_forward(void* h, hipStream_t s, const float* x_nchw, const void* const* 
         CK(pw_bn_relu_maxpool3x3s2(s, (const elem_t*)(act + n.stem.y_off), (elem_t*)(act + n.pool_off), (unsigned char*)(act + n.poolidx_off), n.N,
                                    n.Hs, n.Ws, 64, (const float*)(ws + n.ws_coef), (const float*)(ws + n.ws_coef) + 2048));
     else if (n.f32 == 2)
-        CK(pw_maxpool3x3s2_fwd_split(s, act + n.stem_bn.z_off, act + n.pool_off, (unsigned char*)(act + n.poolidx_off), n.N, n.Hs, n.Ws, 64));
+        CK(pw_maxpool3x3s2_fwd_split(s, act + n.stem_bn.fz_off, act + n.fpool_off, (unsigned char*)(act + n.poolidx_off), n.N, n.Hs, n.Ws, 64,
+                                     sh ? act + n.pool_off : nullptr));
     else if (n.f32)
         CK(pw_maxpool3x3s2_fwd_f32(s, (const float*)(act + n.stem_bn.z_off), (float*)(act + n.pool_off), (unsigned char*)(act + n.poolidx_off), n.N,
                                    n.Hs, n.Ws, 64));
@@ -603,10 +638,10 @@ int net_forward(void* h, hipStream_t s, const float* x_nchw, const void* const* 
     for (auto& b : n.blocks) {
         CK(conv_bn_fwd(s, n, b.c1, b.b1, params, buffers, wpack, act, ws, training, momentum, nullptr, 1, upd));
         CK(conv_bn_fwd(s, n, b.c2, b.b2, params, buffers, wpack, act, ws, training, momentum, nullptr, 1, upd));
-        const elem_t* res = (const elem_t*)(act + b.in_off);
+        const elem_t* res = (const elem_t*)(act + b.fin_off);
         if (b.has_ds) {
             CK(conv_bn_fwd(s, n, b.cd, b.bd, params, buffers, wpack, act, ws, training, momentum, nullptr, 0, upd));
-            res = (const elem_t*)(act + b.zd_off);
+            res = (const elem_t*)(act + b.fzd_off);
         }
         CK(conv_bn_fwd(s, n, b.c3, b.b3, params, buffers, wpack, act, ws, training, momentum, res, 1, upd));
     }
@@ -617,7 +652,7 @@ int net_forward(void* h, hipStream_t s, const float* x_nchw, const void* const* 
     e.f32 = n.f32 != 0;
     e.split = n.f32 == 2;
     const void* hwp = n.f32 == 1 ? params[n.head.w_idx] : (const void*)(wpack + n.head.wf_off);
-    CK(conv_fprop(s, n.head.g, (const elem_t*)(act + n.head.in_off), (const elem_t*)hwp, act + n.head_out_off, e));
+    CK(conv_fprop(s, n.head.g, (const elem_t*)(act + n.head.fin_off), (const elem_t*)hwp, act + n.head_out_off, e));
     return pw_nhwc_to_nchw_f32(s, act + n.head_out_off, 1, out_nchw, n.N, n.K, n.Hout * n.Wout, n.K, nullptr, nullptr);
 }
 
@@ -954,7 +989,7 @@ int run_wg_pair(hipStream_t s, Net& n, const char* actA, char* wsA, void* const*
 int net_wgrad_pair(void* h, hipStream_t s, const void* actA, void* wsA, void* const* gradsA, float betaA, const void* actB, void* wsB,
                    void* const* gradsB, float betaB, int part) {
     Net& n = *(Net*)h;
-    if (part < 0 || part > 2 || n.f32 || !n.policy.wgrad_group) return UDAPOSE_ERR_ARG;
+    if (part < 0 || part > 2 || (n.f32 && !n.strict) || !n.policy.wgrad_group) return UDAPOSE_ERR_ARG;
     DbgSyncScope dbg(n.policy.debug_sync);
     return run_wg_pair(s, n, (const char*)actA, (char*)wsA, gradsA, betaA, (const char*)actB, (char*)wsB, gradsB, betaB, part);
 }
@@ -974,12 +1009,13 @@ int net_backward(void* h, hipStream_t s, const float* dout_nchw, const void* con
     if (part < 0 || part > 2 || phase < 0 || phase > 2) return UDAPOSE_ERR_ARG;
     if (phase != 0 && !n.policy.wgrad_group) return UDAPOSE_ERR_ARG;
     if (phase == 2) {
-        if (n.f32 || n.fwd_only) return UDAPOSE_ERR_UNSUPPORTED;
+        if ((n.f32 && !n.strict) || n.fwd_only) return UDAPOSE_ERR_UNSUPPORTED;
         DbgSyncScope dbg2(n.policy.debug_sync);
         return run_wg_group(s, n, (const char*)act_, (char*)ws_, grads, beta, part);
     }
     DbgSyncScope dbg(n.policy.debug_sync);
-    if (n.f32 || n.fwd_only) return UDAPOSE_ERR_UNSUPPORTED;   // fp32 / f16x2 modes and forward-only plans keep nothing for a backward
+    // fp32 / f16x2 modes and forward-only plans keep nothing for a backward; a 'strict' plan's forward left the 16-bit layout's tensors
+    if ((n.f32 && !n.strict) || n.fwd_only) return UDAPOSE_ERR_UNSUPPORTED;
     const char* wpack = (const char*)wpack_;
     char* act = (char*)act_;
     char* ws = (char*)ws_;
@@ -1120,7 +1156,7 @@ int net_apply_running(void* h, hipStream_t s, const void* act_, void* const* buf
 }
 int net_bind_grads(void* h, void* const* grads) {
     Net& n = *(Net*)h;
-    if (n.f32) return UDAPOSE_OK;
+    if (n.f32 && !n.strict) return UDAPOSE_OK;
     if (n.fwd_only) return UDAPOSE_ERR_UNSUPPORTED;
     return bind_wg_groups(n, grads);
 }
@@ -1144,7 +1180,11 @@ int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grad
     // teacher in the f16x2 mode (the reference's precision mix: fp16 student, fp32-grade teacher): its split packs are not written
     // by this sweep (the caller re-packs the teacher's plan with udapose_net_pack_weights after it), the EMA still is
     const bool t_split = nt.f32 == 2;
-    if (n.f32 || nt.f32 == 1 || n.n_params != nt.n_params || (!t_split && n.wpack_bytes != nt.wpack_bytes)) return UDAPOSE_ERR_UNSUPPORTED;
+    // a 'strict' student: the sweep writes its 16-bit data-gradient packs; its split forward packs are refreshed by net_fused_update's pack
+    // launch after the sweep (as a split teacher's are by the caller)
+    const bool s_split = n.strict != 0;
+    if ((n.f32 && !s_split) || nt.f32 == 1 || nt.strict || n.n_params != nt.n_params || (!t_split && (s_split || n.wpack_bytes != nt.wpack_bytes)))
+        return UDAPOSE_ERR_UNSUPPORTED;
     char* ws_ = (char*)wpack_s_;
     char* wt_ = (char*)wpack_t_;
     const size_t jb = opt_tail_job_bytes();
@@ -1172,9 +1212,9 @@ int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grad
         const int T = g.KH * g.KW;
         if (g.smallc()) return push(c.w_idx, nullptr, nullptr, nullptr, nullptr, 0, 0, 0);     // stem: packed by its own strided launch
         if (!g.transposed)   // master [Co][T][Ci]: fprop pack = cast, dgrad pack = per-tap transpose; the teacher needs the fprop pack
-            return push(c.w_idx, ws_ + c.wf_off, t_split ? nullptr : wt_ + c.wf_off, ws_ + c.wb_off, nullptr, g.Co, T, g.Ci);
+            return push(c.w_idx, s_split ? nullptr : ws_ + c.wf_off, t_split ? nullptr : wt_ + c.wf_off, ws_ + c.wb_off, nullptr, g.Co, T, g.Ci);
         // ConvTranspose2d master [Ci][T][Co]: dgrad pack = cast, fprop pack = per-tap transpose
-        return push(c.w_idx, ws_ + c.wb_off, nullptr, ws_ + c.wf_off, t_split ? nullptr : wt_ + c.wf_off, g.Ci, T, g.Co);
+        return push(c.w_idx, ws_ + c.wb_off, nullptr, s_split ? nullptr : ws_ + c.wf_off, t_split ? nullptr : wt_ + c.wf_off, g.Ci, T, g.Co);
     };
     CK(conv(n.stem));
     for (auto& b : n.blocks) {
@@ -1182,7 +1222,7 @@ int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grad
         if (b.has_ds) CK(conv(b.cd));
     }
     for (int i = 0; i < 3; ++i) CK(conv(n.up[i]));
-    CK(push(n.head.w_idx, ws_ + n.head.wf_off, t_split ? nullptr : wt_ + n.head.wf_off, nullptr, nullptr, 0, 0, 0));      // [K][256]: the fprop pack is a cast
+    CK(push(n.head.w_idx, s_split ? nullptr : ws_ + n.head.wf_off, t_split ? nullptr : wt_ + n.head.wf_off, nullptr, nullptr, 0, 0, 0));      // [K][256]: the fprop pack is a cast
     for (int i = 0; i < n.n_params; ++i)
         if (!covered[i]) CK(push(i, nullptr, nullptr, nullptr, nullptr, 0, 0, 0));                   // BN vectors, head bias, backbone.fc
     Net::UpdTab& u = n.upd;
@@ -1210,7 +1250,10 @@ int net_fused_update(void* hs, void* ht, hipStream_t s, void* const* params_s, v
     CK(opt_tail(s, u.jobs, u.blk_job, u.blk_sub, u.nblocks, lr, beta1, beta2, eps, wd, step, gscale, dev_state, alpha, oma, do_adam, grad2_delta, 1));
     // the two packs that are not a cast or a per-tap transpose of a whole tensor: the stem's 3 -> 8 channel gather (both
     // networks) and the head's zero-padded dgrad pack (student)
-    CK(pack_conv(s, n, n.stem, (const void* const*)params_s, (char*)wpack_s_, false));
+    if (n.strict)   // 'strict' student: its split forward packs (stem included) from the updated weights, one pack launch (net_bind's table)
+        CK(net_pack_weights(hs, s, (const void* const*)params_s, wpack_s_, 0));
+    else
+        CK(pack_conv(s, n, n.stem, (const void* const*)params_s, (char*)wpack_s_, false));
     if (nt.f32 != 2) CK(pack_conv(s, nt, nt.stem, (const void* const*)params_t, (char*)wpack_t_, false));
     CK(pw_pack_strided(s, (const float*)params_s[n.head.w_idx], (elem_t*)((char*)wpack_s_ + n.head.wb_off), 256, 1, 1, 1, 64, n.K, 1, 0, 0, 256));
     return UDAPOSE_OK;

@@ -48,10 +48,36 @@ template <> __device__ __forceinline__ void st8<float>(float* p, const float (&v
     *(f32x4*)p = (f32x4){v[0], v[1], v[2], v[3]};
     *(f32x4*)(p + 4) = (f32x4){v[4], v[5], v[6], v[7]};
 }
+// 'strict' plans (net.hip): the f16x2 forward also leaves the fp16 tensors the 16-bit backward reads ("shadows").  One 16-byte store each:
+// an fp16 rounding of 8 fp32 values (the pre-BN y), and the split store whose h half is ALSO the fp16 shadow of z (returned for the mask)
+__device__ __forceinline__ void st8_f16(_Float16* p, const float (&v)[8]) {
+    half8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (_Float16)v[e];
+    *(half8*)p = o;
+}
+__device__ __forceinline__ half8 st8_split_shadow(sp32* p, _Float16* h16, const float (&v)[8]) {
+    half8 h, l;
+    sp_split8(v, h, l);
+    char* c = (char*)p;
+    *(half8*)c = h;
+    *(half8*)(c + 16) = l;
+    *(half8*)h16 = h;
+    return h;
+}
+// ReLU bit mask of 8 stored fp16 values (bit e: value e > 0, what a reader of the fp16 z sees)
+__device__ __forceinline__ unsigned char mask_of(const half8& h) {
+    unsigned mb = 0u;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) mb |= ((float)h[e] > 0.f ? 1u : 0u) << e;
+    return (unsigned char)mb;
+}
 
 // src NCHW fp32 [N,C,HW] -> dst NHWC [N,HW,Cp] (channels >= C zero-filled); one thread per (pixel, 8-channel group)
-template <typename T>
-__global__ void nchw_f32_to_nhwc_k(const float* __restrict__ src, T* __restrict__ dst, int N, int C, int HW, int Cp) {
+// (SH: T is sp32 and dst16 receives the fp16 image as well - a 'strict' plan's x8 for the stem's weight gradient)
+template <typename T, bool SH = false>
+__global__ void nchw_f32_to_nhwc_k(const float* __restrict__ src, T* __restrict__ dst, int N, int C, int HW, int Cp,
+                                   _Float16* __restrict__ dst16 = nullptr) {
     const int G = Cp >> 3;
     const size_t total = (size_t)N * HW * G;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
@@ -64,7 +90,8 @@ __global__ void nchw_f32_to_nhwc_k(const float* __restrict__ src, T* __restrict_
             const int c = g * 8 + e;
             o[e] = c < C ? src[(n * C + c) * HW + hw] : 0.f;
         }
-        st8<T>(dst + pix * Cp + g * 8, o);
+        if constexpr (SH) (void)st8_split_shadow((sp32*)(dst + pix * Cp + g * 8), dst16 + pix * Cp + g * 8, o);
+        else st8<T>(dst + pix * Cp + g * 8, o);
     }
 }
 
@@ -300,10 +327,11 @@ __global__ void bn_eval_coeff_k(int C, const float* __restrict__ gamma, const fl
 
 // z = [relu]( y*scale[c] + shift[c] [+ res] ), NHWC (bf16 or fp32 storage), 8 channels per thread
 // (TY: storage of the conv output y; T: storage of the residual and of z - the f16x2 mode keeps y in fp32 and z split)
-template <typename T, typename TY = T>
+// (SH, 'strict' plans: T = sp32, TY = float; also y16 = fp16(y), z16 = the h half of z and, where mask is given, the ReLU bit mask of z16)
+template <typename T, typename TY = T, bool SH = false>
 __global__ void bn_apply_k(const TY* __restrict__ y, const T* __restrict__ res, T* __restrict__ z, size_t n8, int C,
                            const float* __restrict__ scale, const float* __restrict__ shift, int relu, unsigned char* __restrict__ mask = nullptr,
-                           int xcd = 0) {
+                           int xcd = 0, _Float16* __restrict__ y16 = nullptr, _Float16* __restrict__ z16 = nullptr) {
     const int G = C >> 3;
     // the launcher keeps gridDim.x * TPB a multiple of G (G is a power of two <= TPB, or the grid is one block per G-aligned
     // stride), so a thread's channel group never changes: its coefficients are loaded once
@@ -327,6 +355,7 @@ __global__ void bn_apply_k(const TY* __restrict__ y, const T* __restrict__ res, 
     for (; i < iend; i += istep) {
         float v[8];
         ld8<TY>(y + i * 8, v);
+        if constexpr (SH) st8_f16(y16 + i * 8, v);
         float o[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = v[e] * (e < 4 ? sa[e] : sb[e - 4]) + (e < 4 ? ha[e] : hb[e - 4]);
@@ -338,6 +367,10 @@ __global__ void bn_apply_k(const TY* __restrict__ y, const T* __restrict__ res, 
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = (relu && o[e] < 0.f) ? 0.f : o[e];
+        if constexpr (SH) {
+            const half8 h = st8_split_shadow(z + i * 8, z16 + i * 8, o);
+            if (mask) mask[i] = mask_of(h);
+        } else {
         st8<T>(z + i * 8, o);
         if constexpr (sizeof(T) == 2) {
         if (mask) {     // bit e: the STORED value of channel e is > 0 (what a reader of z would see)
@@ -345,6 +378,7 @@ __global__ void bn_apply_k(const TY* __restrict__ y, const T* __restrict__ res, 
 #pragma unroll
             for (int e = 0; e < 8; ++e) mb |= ((float)(T)o[e] > 0.f ? 1u : 0u) << e;
             mask[i] = (unsigned char)mb;
+        }
         }
         }
     }
@@ -520,13 +554,15 @@ __global__ void bn_bwd_apply_k(const DZ* __restrict__ dz, const elem_t* __restri
 // does; the sp == 0 work-groups also write the saved statistics and the running-statistics update.  Then it streams its pixels.
 // (TY / TZ: element types of the pre-BN conv output and of the residual / output: elem_t, elem_t in the 16-bit modes; float, sp32 in the
 // f16x2 mode, whose convolutions leave y in fp32 and whose activations are split tensors)
-template <typename TY, typename TZ>
+// (SH: the 'strict' form of the f16x2 instance - y16 / z16 / mask as in bn_apply_k)
+template <typename TY, typename TZ, bool SH = false>
 __global__ __launch_bounds__(TPB) void bn_apply_chunk_k(const TY* __restrict__ y, const TZ* __restrict__ res, TZ* __restrict__ z,
                                                         size_t npix, int C, const float* __restrict__ slab, int rows, double count,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                         float momentum, float* __restrict__ running_mean, float* __restrict__ running_var,
                                                         long long* __restrict__ nbt, float* __restrict__ save, int relu, int P,
-                                                        unsigned char* __restrict__ mask, int xcd) {
+                                                        unsigned char* __restrict__ mask, int xcd, _Float16* __restrict__ y16 = nullptr,
+                                                        _Float16* __restrict__ z16 = nullptr) {
     __shared__ double part[8][128];
     __shared__ float scs[64], shs[64];
     // xcd: the (chunk, pixel range) pairs are dealt so that XCD k gets the k-th EIGHTH of the pixel rows (all chunks of it) - the rows
@@ -609,6 +645,7 @@ __global__ __launch_bounds__(TPB) void bn_apply_chunk_k(const TY* __restrict__ y
         const size_t off = p * C + c0;
         float v[8], o[8];
         ld8<TY>(y + off, v);
+        if constexpr (SH) st8_f16(y16 + off, v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = v[e] * sc[e] + sh[e];
         if (res) {
@@ -619,8 +656,13 @@ __global__ __launch_bounds__(TPB) void bn_apply_chunk_k(const TY* __restrict__ y
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = (relu && o[e] < 0.f) ? 0.f : o[e];
+        if constexpr (SH) {
+            const half8 h = st8_split_shadow(z + off, z16 + off, o);
+            if (mask) mask[off >> 3] = mask_of(h);
+        } else {
         st8<TZ>(z + off, o);
-        if constexpr (sizeof(TZ) == sizeof(elem_t)) {
+        }
+        if constexpr (!SH && sizeof(TZ) == sizeof(elem_t)) {
             if (mask) {
                 unsigned mb = 0u;
 #pragma unroll
@@ -893,9 +935,10 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_pre_chunk_k(const DZ* __rest
 
 // ------------------------------------------------------------------ max pooling (NHWC bf16)
 // 3x3 stride 2 pad 1 (ResNet stem).  Saves the winning tap (0..8, first max in (kh,kw) scan order like ATen) per element.
-template <typename T>
+// (SH, 'strict' plans: T = sp32 and y16 receives the pooled fp16 map, the h half of y)
+template <typename T, bool SH = false>
 __global__ void maxpool3x3s2_fwd_k(const T* __restrict__ x, T* __restrict__ y, unsigned char* __restrict__ idx, int N, int H,
-                                   int W, int C, int Ho, int Wo) {
+                                   int W, int C, int Ho, int Wo, _Float16* __restrict__ y16 = nullptr) {
     const int G = C >> 3;
     const size_t total = (size_t)N * Ho * Wo * G;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
@@ -925,7 +968,8 @@ __global__ void maxpool3x3s2_fwd_k(const T* __restrict__ x, T* __restrict__ y, u
                     first = false;
                 }
             }
-        st8<T>(y + i * 8, best);
+        if constexpr (SH) (void)st8_split_shadow(y + i * 8, y16 + i * 8, best);     // ('strict': the pooled fp16 map, T = sp32)
+        else st8<T>(y + i * 8, best);
         if (idx) {
             unsigned long long pk = 0;
 #pragma unroll
@@ -1098,9 +1142,13 @@ int pw_nchw_f32_to_nhwc_f32(hipStream_t s, const float* src, float* dst, int N, 
     hipLaunchKernelGGL(nchw_f32_to_nhwc_k<float>, dim3(grid_for((size_t)N * HW * (Cp / 8))), dim3(TPB), 0, s, src, dst, N, C, HW, Cp);
     return udapose_check_launch();
 }
-int pw_nchw_f32_to_nhwc_split(hipStream_t s, const float* src, void* dst, int N, int C, int HW, int Cp) {
+int pw_nchw_f32_to_nhwc_split(hipStream_t s, const float* src, void* dst, int N, int C, int HW, int Cp, void* dst16) {
     if (Cp % 8) return UDAPOSE_ERR_ARG;
-    hipLaunchKernelGGL(nchw_f32_to_nhwc_k<sp32>, dim3(grid_for((size_t)N * HW * (Cp / 8))), dim3(TPB), 0, s, src, (sp32*)dst, N, C, HW, Cp);
+    if (dst16)      // ('strict' plans: the fp16 image for the 16-bit backward in the same pass)
+        hipLaunchKernelGGL((nchw_f32_to_nhwc_k<sp32, true>), dim3(grid_for((size_t)N * HW * (Cp / 8))), dim3(TPB), 0, s, src, (sp32*)dst, N, C, HW, Cp,
+                           (_Float16*)dst16);
+    else
+        hipLaunchKernelGGL(nchw_f32_to_nhwc_k<sp32>, dim3(grid_for((size_t)N * HW * (Cp / 8))), dim3(TPB), 0, s, src, (sp32*)dst, N, C, HW, Cp);
     return udapose_check_launch();
 }
 // src_is_f32: 0 = element type, 1 = fp32, 2 = f16x2 split
@@ -1208,7 +1256,7 @@ int pw_bn_train_fused(hipStream_t s, const elem_t* y, const elem_t* res, elem_t*
 // critical path of a step in the reference precision mix - this removes one launch (bn_finalize_k) per BatchNorm of layer3 / layer4 / deconv1.
 int pw_bn_train_fused_split(hipStream_t s, const float* y, const void* res, void* z, size_t npix, int C, const float* slab, int rows,
                             const float* gamma, const float* beta, float* rm, float* rv, long long* nbt, float momentum, float eps, float* save,
-                            int relu, int enabled) {
+                            int relu, int enabled, void* y16, void* z16, unsigned char* mask) {
     const int xcd = (enabled >> 30) & 1;
     enabled &= ~(1 << 30);
     if (!enabled || C < 256 || C % 64 || npix > 8192 || npix < 1024 || rows > 128) return 0;
@@ -1219,8 +1267,12 @@ int pw_bn_train_fused_split(hipStream_t s, const float* y, const void* res, void
     int P = (int)((npix + S - 1) / S);
     P = (P + 31) & ~31;
     S = (int)((npix + P - 1) / P);
-    hipLaunchKernelGGL((bn_apply_chunk_k<float, sp32>), dim3(chunks, S), dim3(TPB), 0, s, y, (const sp32*)res, (sp32*)z, npix, C, slab, rows, (double)npix,
-                       gamma, beta, eps, momentum, rm, rv, nbt, save, relu, P, (unsigned char*)nullptr, xcd);
+    if (y16)        // ('strict' plans: y16 / z16 / mask are the fp16 tensors the 16-bit backward reads, written in the same pass)
+        hipLaunchKernelGGL((bn_apply_chunk_k<float, sp32, true>), dim3(chunks, S), dim3(TPB), 0, s, y, (const sp32*)res, (sp32*)z, npix, C, slab, rows,
+                           (double)npix, gamma, beta, eps, momentum, rm, rv, nbt, save, relu, P, mask, xcd, (_Float16*)y16, (_Float16*)z16);
+    else
+        hipLaunchKernelGGL((bn_apply_chunk_k<float, sp32>), dim3(chunks, S), dim3(TPB), 0, s, y, (const sp32*)res, (sp32*)z, npix, C, slab, rows, (double)npix,
+                           gamma, beta, eps, momentum, rm, rv, nbt, save, relu, P, (unsigned char*)nullptr, xcd);
     return udapose_check_launch() == UDAPOSE_OK ? 1 : UDAPOSE_ERR_LAUNCH;
 }
 // the same for every BN layer of a net in one launch: jobs[blockIdx.x], channels blockIdx.y*TPB..; save = act + save_off
@@ -1338,9 +1390,18 @@ int pw_bn_apply(hipStream_t s, const elem_t* y, const elem_t* res, elem_t* z, si
     hipLaunchKernelGGL(bn_apply_k<elem_t>, dim3(grid), dim3(TPB), 0, s, y, res, z, n / 8, C, scale, shift, relu, mask, ok);
     return udapose_check_launch();
 }
-// f16x2 mode: y fp32 (the conv epilogue's fp32 output), residual and z split
-int pw_bn_apply_split(hipStream_t s, const float* y, const void* res, void* z, size_t n, int C, const float* scale, const float* shift, int relu) {
+// f16x2 mode: y fp32 (the conv epilogue's fp32 output), residual and z split.  'strict' plans (y16 given): the same pass also writes
+// y16 = fp16(y), z16 = the h half of z and the ReLU bit mask (when given), with the XCD row mapping of pw_bn_apply (xcd)
+int pw_bn_apply_split(hipStream_t s, const float* y, const void* res, void* z, size_t n, int C, const float* scale, const float* shift, int relu,
+                      void* y16, void* z16, unsigned char* mask, int xcd) {
     if (C % 8 || n % 8) return UDAPOSE_ERR_ARG;
+    if (y16) {
+        const int grid = bn_apply_grid(n / 8, C), G = C / 8;
+        const int ok = xcd && (TPB % G) == 0 && (grid % 8) == 0 && (n / 8 / G) >= (size_t)8 * (TPB / G);
+        hipLaunchKernelGGL((bn_apply_k<sp32, float, true>), dim3(grid), dim3(TPB), 0, s, y, (const sp32*)res, (sp32*)z, n / 8, C, scale, shift, relu, mask,
+                           ok, (_Float16*)y16, (_Float16*)z16);
+        return udapose_check_launch();
+    }
     hipLaunchKernelGGL((bn_apply_k<sp32, float>), dim3(bn_apply_grid(n / 8, C)), dim3(TPB), 0, s, y, (const sp32*)res, (sp32*)z, n / 8, C, scale, shift, relu,
                        (unsigned char*)nullptr);
     return udapose_check_launch();
@@ -1484,8 +1545,13 @@ int pw_maxpool3x3s2_fwd_f32(hipStream_t s, const float* x, float* y, unsigned ch
     hipLaunchKernelGGL(maxpool3x3s2_fwd_k<float>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, x, y, idx, N, H, W, C, Ho, Wo);
     return udapose_check_launch();
 }
-int pw_maxpool3x3s2_fwd_split(hipStream_t s, const void* x, void* y, unsigned char* idx, int N, int H, int W, int C) {
+int pw_maxpool3x3s2_fwd_split(hipStream_t s, const void* x, void* y, unsigned char* idx, int N, int H, int W, int C, void* y16) {
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    if (y16) {      // ('strict' plans: the pooled fp16 map as well)
+        hipLaunchKernelGGL((maxpool3x3s2_fwd_k<sp32, true>), dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, (const sp32*)x, (sp32*)y, idx, N, H, W,
+                           C, Ho, Wo, (_Float16*)y16);
+        return udapose_check_launch();
+    }
     hipLaunchKernelGGL(maxpool3x3s2_fwd_k<sp32>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, (const sp32*)x, (sp32*)y, idx, N, H, W, C, Ho, Wo);
     return udapose_check_launch();
 }

@@ -209,6 +209,8 @@ class MeanTeacherTrainer:
         # 'reference' = the reference's own precision mix (train_human.py:346-358,414): the student in fp16 (its autocast dtype)
         #   with GradScaler's dynamic loss scaling kept on the device (optim.py), the teacher and the style network OUTSIDE autocast
         #   in fp32 - here the fp32-grade 'f16x2' mode (three fp16 MFMAs per K step; heat-maps within ~4e-5 of the fp32 oracle).
+        # 'strict' = the same mix with an fp32-grade student FORWARD (PoseResNet precision 'strict': the f16x2 forward, the fp16 backward
+        #   under the same loss scaling - the gradients are not fp32-grade); teacher and style network as in 'reference'.
         # 'bf16' / 'fp16': student AND teacher in that 16-bit type (BASELINE.json's benched configuration is 'bf16'; the style
         #   network keeps its own setting).
         # (the networks may arrive wrapped in a single-device nn.DataParallel, as in the reference: attributes go to the modules)
@@ -221,6 +223,11 @@ class MeanTeacherTrainer:
             sn = getattr(style_net, "module", style_net)
             if sn is not None and hasattr(sn, "precision"):
                 sn.precision = hi
+        elif precision == "strict":
+            stu_m.precision, tea_m.precision = "strict", "f16x2"
+            sn = getattr(style_net, "module", style_net)
+            if sn is not None and hasattr(sn, "precision"):
+                sn.precision = "f16x2"
         elif precision is not None:
             stu_m.precision = precision
             tea_m.precision = precision
@@ -228,10 +235,10 @@ class MeanTeacherTrainer:
         # runs under torch.autocast, the reference's call form) get the device-side GradScaler; a scaled bf16 step is exact (powers of
         # two), an unscaled fp16 step underflows silently - _check_scaler() refuses that combination at step time
         sp = getattr(stu_m, "precision", "bf16")
-        scaled = sp in ("fp16", "auto")
+        scaled = sp in ("fp16", "auto", "strict")       # ('strict': the fp16 backward)
         # the teacher's fp32-grade plans live in the student's library build, so the fused optimizer tail hands both plans to one .so
         if hasattr(tea_m, "aux_lib_kind"):
-            tea_m.aux_lib_kind = "fp16" if sp == "fp16" else "bf16"
+            tea_m.aux_lib_kind = "fp16" if sp in ("fp16", "strict") else "bf16"
         sc = dict(dynamic_loss_scale=True, init_scale=loss_scale_init, growth_interval=loss_scale_interval) if scaled else {}
         if use_sgd:
             self.stu_optimizer = fused_optim.FusedSGD(student.parameters(), lr=lr, momentum=0.9, weight_decay=1e-4, nesterov=True, **sc)
@@ -270,9 +277,10 @@ class MeanTeacherTrainer:
         """An fp16 student forward needs the loss scaler the optimizer was built with (or the caller's own GradScaler: then build the
         trainer's optimizer yourself)."""
         hd = getattr(getattr(self.student, "module", self.student), "_last_hd", None)
-        if hd is not None and hd.precision == "fp16" and getattr(self.stu_optimizer, "_scaler", None) is None:
-            raise RuntimeError("the student ran in fp16 but the trainer's optimizer has no dynamic loss scaling: fp16 heat-map gradients "
-                               "underflow without it - construct MeanTeacherTrainer with precision='fp16' / 'reference' / 'auto'")
+        if hd is not None and hd.precision in ("fp16", "strict") and getattr(self.stu_optimizer, "_scaler", None) is None:
+            raise RuntimeError(f"the student ran in {hd.precision} (an fp16 backward) but the trainer's optimizer has no dynamic loss scaling: fp16 "
+                               "heat-map gradients underflow without it - construct MeanTeacherTrainer with precision='fp16' / 'reference' / "
+                               "'strict' / 'auto'")
 
     # ------------------------------------------------------------------ train_human.py:262-302
     def pretrain_step(self, x_s, label_s, weight_s, x_t=None):

@@ -58,14 +58,14 @@ class _NetHandle:
         # the library build whose element type is this plan's storage / MFMA type.  'fp32' / 'f16x2' plans do not depend on the
         # element type (both builds carry them): they live in the build `aux_lib` names - the STUDENT's build when this network is
         # the teacher of a fused optimizer tail, which hands both plans to one library (a plan is only ever
-        # dereferenced by the .so that created it)
-        L = self.L = lib('fp16' if precision == 'fp16' else ('bf16' if precision == 'bf16' else aux_lib))
+        # dereferenced by the .so that created it).  'strict' plans run the fp16 build's backward: they live in the fp16 build
+        L = self.L = lib('fp16' if precision in ('fp16', 'strict') else ('bf16' if precision == 'bf16' else aux_lib))
         h = C.c_void_p()
         arr = (C.c_int * 4)(*layers)
         # fwd_only (mode bit 9): a plan for no-grad forwards - the teacher, validate() - whose y / z tensors rotate through six scratch
         # buffers instead of a 2.8 GB arena (udapose.h); it refuses a backward
         self.fwd_only = bool(fwd_only)
-        check(L.udapose_net_create(arr, K, N, H, W, {'fp32': 1, 'f16x2': 2}.get(precision, 0) | (0x100 if deconv_bias else 0) | (0x200 if fwd_only else 0),
+        check(L.udapose_net_create(arr, K, N, H, W, {'fp32': 1, 'f16x2': 2, 'strict': 3}.get(precision, 0) | (0x100 if deconv_bias else 0) | (0x200 if fwd_only else 0),
                                    C.byref(h)), "net_create")
         self.h = h
         self.precision = precision
@@ -147,6 +147,10 @@ class PoseResNet(nn.Module):
         # 'f16x2': the FAST fp32-grade mode, forward only: activations and weights as fp16 pairs (h, l), three fp16 MFMAs per K step,
         #         fp32 accumulation / BatchNorm statistics - heat-maps within ~4e-5 of the fp32 CPU oracle, 1.7x the exact mode's speed.
         # 'fp32': exact fp32 MFMA (v_mfma_f32_16x16x4_f32), forward only; 3x slower than bf16.
+        # 'strict': fp32-grade FORWARD for training - a differentiable forward runs the f16x2 forward and also leaves the fp16 tensors the
+        #         fp16 backward reads, so its outputs and BatchNorm statistics are bit for bit those of 'f16x2'; the BACKWARD is the fp16 one
+        #         (the reference's autocast precision for gradients: not fp32-grade) and needs loss scaling like 'fp16'.  No-grad forwards
+        #         run 'f16x2'.
         self.precision = type(self).default_precision
         self.aux_lib_kind = 'bf16'    # build that holds this module's 'fp32' / 'f16x2' plans (engine: the student's build, see _NetHandle)
         self._handles = {}
@@ -239,8 +243,10 @@ class PoseResNet(nn.Module):
     def resolved_precision(self, differentiable):
         """The precision a forward started now would run in ('auto' resolved, see __init__)."""
         prec = self.precision
-        if prec not in ('auto', 'bf16', 'fp16', 'fp32', 'f16x2'):
-            raise ValueError("precision must be 'auto', 'bf16', 'fp16', 'f16x2' or 'fp32'")
+        if prec not in ('auto', 'bf16', 'fp16', 'fp32', 'f16x2', 'strict'):
+            raise ValueError("precision must be 'auto', 'bf16', 'fp16', 'f16x2', 'fp32' or 'strict'")
+        if prec == 'strict':
+            return 'strict' if differentiable else 'f16x2'
         if prec != 'auto':
             return prec
         if torch.is_autocast_enabled():

@@ -216,17 +216,20 @@ class FusedAdam(_FusedBase):
         hd_s, hd_t = getattr(student, "_last_hd", None), getattr(teacher, "_last_hd", None)
         # the teacher either shares the student's 16-bit element type (its packs are written by the sweep) or runs the fp32-grade
         # f16x2 mode (the reference's precision mix: its split packs are refreshed by one pack launch right after the sweep)
-        if hd_s is None or hd_t is None or hd_s.precision not in ("bf16", "fp16"):
+        # (a 'strict' student - f16x2 forward, fp16 backward, fp16 build - gets its fp16 data-gradient packs from the sweep and its split
+        # forward packs from one pack launch inside udapose_net_fused_update)
+        if hd_s is None or hd_t is None or hd_s.precision not in ("bf16", "fp16", "strict"):
             return False
+        s_kind = "fp16" if hd_s.precision == "strict" else hd_s.precision      # (the student's library build)
         t_split = hd_t.precision == "f16x2"
         # both plans are handed to ONE library (the student's): the teacher's must have been created by it (PoseResNet.aux_lib_kind puts an
         # f16x2 teacher's plan into the student's build; a plan of the other .so is never dereferenced here - ADVICE r3)
-        if hd_s.L is not hd_t.L and t_split and hasattr(teacher, "aux_lib_kind") and teacher.aux_lib_kind != hd_s.precision:
+        if hd_s.L is not hd_t.L and t_split and hasattr(teacher, "aux_lib_kind") and teacher.aux_lib_kind != s_kind:
             # an 'auto' student resolved to the other build than the one the teacher's f16x2 plan was created in (the engine guesses the
             # build before the first forward): move the teacher's fp32-grade plans into the student's build - the next teacher forward
             # creates its plan there, and the one-launch tail applies from the following step on
-            teacher.aux_lib_kind = hd_s.precision
-        if hd_s.L is not hd_t.L or (not t_split and hd_t.precision != hd_s.precision):
+            teacher.aux_lib_kind = s_kind
+        if hd_s.L is not hd_t.L or (not t_split and hd_t.precision != hd_s.precision) or (hd_s.precision == "strict" and not t_split):
             if not getattr(self, "_warned_tail_lib", False):
                 self._warned_tail_lib = True
                 import warnings
