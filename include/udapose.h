@@ -217,7 +217,10 @@ size_t udapose_net_wpack_bytes(udapose_net_t net);
 size_t udapose_net_act_bytes(udapose_net_t net);
 size_t udapose_net_ws_bytes(udapose_net_t net);
 void udapose_net_out_shape(udapose_net_t net, int shape[4]);
-/* the plan's dispatch policy (set it before udapose_net_bind_grads: the grouped weight-gradient tables depend on it) */
+/* the plan's dispatch policy (set it before udapose_net_bind_grads: the grouped weight-gradient tables depend on it).  Tables keep
+ * the policy they were built under (split form wgrad_det, split length wgrad_stages, wgrad_group_stem): after a change of these,
+ * the backward returns UDAPOSE_ERR_NOT_PREPARED until udapose_net_ws_bytes has been asked again (size `ws` by its new answer) and
+ * udapose_net_bind_grads has run for each gradient placement; it then equals a plan created with the new policy. */
 int udapose_net_set_policy(udapose_net_t net, const udapose_policy* p);
 int udapose_net_get_policy(udapose_net_t net, udapose_policy* p);
 /* Preparation (allocates + copies synchronously; outside stream capture; repeat when a pointer changes):
@@ -253,7 +256,9 @@ int udapose_net_backward_phase(udapose_net_t net, void* stream, const float* dou
                                void* act, void* ws, void* const* h_grads, float beta, int part, int phase);
 /* The grouped weight-gradient launches (phase 2) of TWO passes of one plan whose gradient chains (phase 1) have run - each with its
  * own act / ws arenas, gradient tensors and beta - as ONE launch per tile class: the two student passes of a mean-teacher step end
- * together and their weight gradients are exposed there; one grid of twice the size has half the tail.
+ * together and their weight gradients are exposed there; one grid of twice the size has half the tail.  The result always equals the two
+ * udapose_net_backward_phase(..., phase 2) calls A then B: when the two passes' gradient tensors share any byte (h_grads_a == h_grads_b,
+ * B accumulating onto A), or their tables differ, the call issues exactly those two launches in that order.
  * Determinism (round 6, udapose_policy.wgrad_det = 1, the default): a layer whose pixel range is split over several work-groups (layer1 / layer2,
  * the last deconvolution, the head, the stem) has every split store its partial tile into `ws`; one launch then adds the splits in split order
  * into the gradient tensor.  Two runs of a backward on the same inputs give the same bits (rounds 1-5 accumulated the splits with fp32

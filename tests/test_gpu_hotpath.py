@@ -1179,3 +1179,95 @@ def test_batchnorm_backward_orthogonality_at_full_size():
         assert float((dy.double().sum((0, 1, 2)) - rounded.double().sum((0, 1, 2))).abs().max()) <= 5e-2
         np.testing.assert_allclose(dbeta.cpu().numpy(), gd.sum((0, 1, 2)).float().cpu().numpy(), rtol=1e-4, atol=1e-2)
         np.testing.assert_allclose(dgamma.cpu().numpy(), (gd * xh).sum((0, 1, 2)).float().cpu().numpy(), rtol=1e-4, atol=1e-2)
+
+
+def _warp_index_map(th, H, W):
+    """The device forward's index map: warp a plane holding 1 + the flat pixel index (exact in fp32 below 2^24); 0 = no source pixel."""
+    from uda_poseestimation_amd import warp
+    n = th.shape[0]
+    plane = (torch.arange(H * W, dtype=torch.float32) + 1).reshape(1, 1, H, W).expand(n, 1, H, W).contiguous()
+    out = warp.warp_chain(plane.cuda(), th).cpu().reshape(n, H * W)
+    assert torch.equal(out, out.round()) and float(out.max()) <= H * W
+    return out.long() - 1
+
+
+def _collapsing_thetas(n):
+    """Chains whose outputs pile onto few input pixels: all-zero matrices (every output on one pixel) with 1 and 3 stages, single zooms
+    of 12 (~144 outputs per input pixel) and 20 (~400), and three stages with small rotations and shifts whose zooms multiply to 18."""
+    from uda_poseestimation_amd import warp
+    three = torch.cat([warp.single_thetas(7.0, (1.5, -2.0), 3.0, (0.0, 0.0), n), warp.single_thetas(-4.0, (0.0, 1.0), 3.0, (2.0, 0.0), n),
+                       warp.single_thetas(0.0, (-1.0, 0.5), 2.0, (0.0, 0.0), n)], dim=1)
+    return {"zero1": torch.zeros(n, 1, 6), "zero3": torch.zeros(n, 3, 6), "zoom12": warp.single_thetas(0.0, (0.0, 0.0), 12.0, (0.0, 0.0), n),
+            "zoom20": warp.single_thetas(0.0, (0.0, 0.0), 20.0, (0.0, 0.0), n), "chain18": three}
+
+
+@pytest.mark.parametrize("HW", [64, 96, 128])
+@pytest.mark.parametrize("kind", ["zero1", "zero3", "zoom12", "zoom20", "chain18"])
+def test_warp_chain_backward_at_collapsing_maps(kind, HW):
+    """The re-warp's backward where many outputs land on one input pixel (up to all H*W of them).  Reference: the index map read off the
+    device forward (tested against the torchvision restatement elsewhere).  64x64 and 96x96 planes take the deterministic LDS form
+    (13 bytes per pixel within 150 KB): its documented order is ascending output index, so d(in) must equal, to the bit, an fp32 sum in
+    that order - and two runs the same bits.  128x128 takes the atomic form: within n * eps of an fp64 index_add.  (Before the fix the LDS
+    form ranked at most 254 outputs per pixel and silently dropped the rest.)"""
+    N, C = 2, 3
+    th = _collapsing_thetas(N)[kind]
+    idx = _warp_index_map(th.cuda(), HW, HW)                     # [N, HW*HW], -1 where the output has no source
+    g = torch.randn(N, C, HW, HW, generator=torch.Generator().manual_seed(HW))
+    det = HW * HW * 13 + 16 <= 150 * 1024
+    from uda_poseestimation_amd import _hip
+    from uda_poseestimation_amd._hip import check, lib, ptr
+
+    def bwd():
+        gd, thd = g.cuda().contiguous(), th.cuda().contiguous()
+        dx = torch.full_like(gd, float("nan"))
+        check(lib().udapose_affine_nearest(_hip.stream(), ptr(gd), ptr(dx), ptr(thd), N, C, HW, HW, th.shape[1], 1), "affine_nearest_bwd")
+        torch.cuda.synchronize()
+        return dx.cpu().reshape(N, C, HW * HW)
+
+    dx = bwd()
+    gf = g.reshape(N, C, HW * HW)
+    most = 0
+    for n in range(N):
+        ok = idx[n] >= 0
+        tgt, src = idx[n][ok].numpy(), torch.nonzero(ok).flatten().numpy()         # (src ascending)
+        most = max(most, int(np.bincount(tgt, minlength=HW * HW).max()))
+        for c in range(C):
+            gv = gf[n, c].numpy()[src]
+            if det:
+                ref = np.zeros(HW * HW, dtype=np.float32)
+                np.add.at(ref, tgt, gv)                  # unbuffered, in index order: an fp32 sum in ascending output index
+                assert np.array_equal(dx[n, c].numpy(), ref), (kind, HW, n, c, float(np.abs(dx[n, c].numpy() - ref).max()))
+            else:
+                ref = np.zeros(HW * HW, dtype=np.float64)
+                np.add.at(ref, tgt, gv.astype(np.float64))
+                cnt = np.bincount(tgt, minlength=HW * HW)
+                mag = np.zeros(HW * HW, dtype=np.float64)
+                np.add.at(mag, tgt, np.abs(gv.astype(np.float64)))
+                err = np.abs(dx[n, c].numpy().astype(np.float64) - ref)
+                assert (err <= cnt * 2.0 ** -23 * mag + 1e-30).all(), (kind, HW, n, c, float(err.max()))
+    print(f"{kind} {HW}x{HW}: up to {most} outputs on one input pixel ({'deterministic' if det else 'atomic'} form)")
+    assert most >= {"zero1": HW * HW, "zero3": HW * HW, "zoom12": 100, "zoom20": 300, "chain18": 255}[kind]
+    if det:
+        assert torch.equal(bwd(), dx), "two runs of the deterministic backward differ"
+
+
+def test_warp_affine_zoom20_under_autograd_keeps_every_gradient():
+    """warp.affine (the torchvision drop-in) at zoom 20 under autograd: ~400 outputs read each input pixel, and the input gradient sums
+    to the upstream gradient over the outputs that have a source pixel (none of it lost), and equals the ordered fp32 sum of the index map."""
+    from uda_poseestimation_amd import warp
+    H = W = 64
+    img = torch.randn(3, H, W, generator=torch.Generator().manual_seed(4)).cuda().requires_grad_(True)
+    up = torch.randn(3, H, W, generator=torch.Generator().manual_seed(5))
+    out = warp.affine(img, 0, [0, 0], 20.0, 0)
+    (out * up.cuda()).sum().backward()
+    idx = _warp_index_map(warp.single_thetas(0.0, (0.0, 0.0), 20.0, (0.0, 0.0), 1, "cuda"), H, W)[0]
+    ok = idx >= 0
+    assert int(np.bincount(idx[ok].numpy()).max()) >= 300
+    gin = img.grad.detach().cpu().double()
+    for c in range(3):
+        want = up[c].reshape(-1)[ok].double().sum()
+        tol = int(ok.sum()) * 2.0 ** -23 * float(up[c].reshape(-1)[ok].abs().double().sum())
+        assert abs(float(gin[c].sum() - want)) <= tol, (c, float(gin[c].sum()), float(want))
+        ref = np.zeros(H * W, dtype=np.float32)
+        np.add.at(ref, idx[ok].numpy(), up[c].reshape(-1)[ok].numpy())
+        assert np.array_equal(img.grad[c].detach().cpu().reshape(-1).numpy(), ref)

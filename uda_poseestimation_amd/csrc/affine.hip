@@ -49,7 +49,10 @@ __global__ void warp_chain_k(const float* __restrict__ src, float* __restrict__ 
 // plane's index map into LDS, RANKS the outputs that share a target by ascending output index (round r: every unranked output proposes itself
 // with an LDS atomicMin on its target's slot - an integer minimum is order-independent - and the winner takes rank r), and then adds
 // rank 0, rank 1, ... into an LDS accumulator with one barrier per rank: every input pixel receives its contributions in ascending output
-// index, whatever the scheduling.  The plane is stored with plain coalesced stores (no clear of dst beforehand).
+// index, whatever the scheduling.  A rank is one byte: an epoch ranks at most 254 outputs per target, adds them, retires them, and a collapsing
+// map (zoom > ~15, an all-zero theta: up to H*W outputs on one pixel) takes further epochs over the outputs still pending - each epoch ranks
+// the smallest pending indices, so the order stays ascending across epochs.  The loop's scales (<= 1 / 0.6 per axis) need one epoch, and
+// then the rounds and barriers are those of a single pass.  The plane is stored with plain coalesced stores (no clear of dst beforehand).
 // LDS: (int target + int slot + float acc) per pixel + 1 byte rank = 13 bytes per pixel (53 KB for 64x64, 120 KB for 96x96).
 __global__ __launch_bounds__(TPB) void warp_chain_bwd_det_k(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ theta,
                                                             int C, int H, int W, int nstage) {
@@ -65,28 +68,32 @@ __global__ __launch_bounds__(TPB) void warp_chain_bwd_det_k(const float* __restr
         bool ok = true;
         for (int s = nstage - 1; s >= 0 && ok; --s) ok = step(theta + ((size_t)n * nstage + s) * 6, W, H, px, py);
         tgt[i] = ok ? py * W + px : -1;
-        rank[i] = ok ? 255 : 254;          // 255: not ranked yet; 254: contributes nothing
+        rank[i] = ok ? 255 : 254;          // 255: not ranked yet; 254: contributes nothing (or already added)
         acc[i] = 0.f;
     }
     __syncthreads();
-    int nrounds = 0;
-    for (int r = 0; r < 254; ++r) {
-        for (int i = threadIdx.x; i < HW; i += TPB) slot[i] = 0x7fffffff;
-        __syncthreads();
-        int pending = 0;
-        for (int i = threadIdx.x; i < HW; i += TPB)
-            if (rank[i] == 255) { atomicMin(&slot[tgt[i]], i); pending = 1; }
-        if (!__syncthreads_or(pending)) break;
-        for (int i = threadIdx.x; i < HW; i += TPB)
-            if (rank[i] == 255 && slot[tgt[i]] == i) rank[i] = (unsigned char)r;
-        nrounds = r + 1;
-        __syncthreads();
-    }
     const float* sp = src + ((size_t)n * C + c) * HW;
-    for (int r = 0; r < nrounds; ++r) {
-        for (int i = threadIdx.x; i < HW; i += TPB)
-            if (rank[i] == r) acc[tgt[i]] += sp[i];        // (one writer per target and round)
-        __syncthreads();
+    for (bool more = true; more;) {
+        more = false;
+        int nrounds = 0;
+        for (int r = 0; r < 254; ++r) {
+            for (int i = threadIdx.x; i < HW; i += TPB) slot[i] = 0x7fffffff;
+            __syncthreads();
+            int pending = 0;
+            for (int i = threadIdx.x; i < HW; i += TPB)
+                if (rank[i] == 255) { atomicMin(&slot[tgt[i]], i); pending = 1; }
+            if (!__syncthreads_or(pending)) break;
+            for (int i = threadIdx.x; i < HW; i += TPB)
+                if (rank[i] == 255 && slot[tgt[i]] == i) rank[i] = (unsigned char)r;
+            nrounds = r + 1;
+            more = r == 253;               // (all 254 ranks taken: outputs may still be pending - another epoch finds out)
+            __syncthreads();
+        }
+        for (int r = 0; r < nrounds; ++r) {
+            for (int i = threadIdx.x; i < HW; i += TPB)
+                if (rank[i] == r) { acc[tgt[i]] += sp[i]; rank[i] = 254; }        // (one writer per target and round)
+            __syncthreads();
+        }
     }
     float* dp = dst + ((size_t)n * C + c) * HW;
     for (int i = threadIdx.x; i < HW; i += TPB) dp[i] = acc[i];
@@ -221,8 +228,9 @@ int affine_warp_chain(hipStream_t s, const float* src, float* dst, const float* 
     if (blocks > 4096) blocks = 4096;
     const int cgroups = C >= 16 ? 16 : (C >= 4 ? 4 : 1);
     if (backward) {
-        // deterministic form (one work-group per (sample, channel) plane, ranks in LDS) wherever the plane fits; more than 253 outputs on one
-        // input pixel cannot happen with the loop's scales (<= 1 / 0.6 per axis), and a plane beyond the LDS budget takes the atomic form
+        // deterministic form (one work-group per (sample, channel) plane, ranks in LDS) wherever the plane fits, at any number of outputs per
+        // input pixel (more than 254 - a zoom past ~15, a collapsed theta - take further ranking epochs); a plane beyond the LDS budget takes the
+        // atomic form
         const size_t lds = (size_t)H * W * 13 + 16;
         if (lds <= 150 * 1024 && (long long)N * C < (1ll << 31)) {
             static std::atomic<unsigned long long> attr_done{0};

@@ -145,7 +145,13 @@ struct Net {
     // grouped weight-gradient launch of one backward pass: device tables, rebuilt when the buffers change
     struct WgGroup {
         float k_beta = -1.f; int k_stages = 0; int k_part = 0;     // part: 0 all layers, 1 upper (head..layer3), 2 lower (layer2..stem)
+        // the policy the tables were built under: the form of the split reductions (1: partial tiles + split sums, 0: atomics into cleared
+        // tensors) and whether they hold the stem.  A later udapose_net_set_policy does not change what a bound table does: find_wg_group
+        // no longer finds it, and the backward returns UDAPOSE_ERR_NOT_PREPARED until udapose_net_bind_grads builds tables for the new policy.
+        bool k_det = false, k_stem = false;
+        size_t part_bytes = 0;                           // workspace bytes of partial tiles the split sums read (k_det)
         std::vector<std::pair<int, ptrdiff_t>> rel;      // (parameter index, byte offset of its gradient from grads[0]) the table assumes
+        std::vector<size_t> rel_bytes;                   // bytes of rel[i]'s gradient tensor (what the launch writes there)
         std::vector<int> rel_cls;                        // tile class of the launch that computes rel[i]'s gradient
         // tile classes of the grouped launch: 0 = 128x128, 1 = 64x64 (and the filter-row form), 2 = 256x128 (128x64 per wave)
         WgParams* d_tab[WG_CLASSES] = {}; WgGroupBlk* d_blk[WG_CLASSES] = {}; int per_xcd[WG_CLASSES] = {};
@@ -744,6 +750,7 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
     std::vector<Unit> units[WG_CLASSES];
     G.zero.clear();
     G.rel.clear();
+    G.rel_bytes.clear();
     G.rel_cls.clear();
     for (int t = 0; t < WG_CLASSES; ++t) G.flops[t] = 0.0;
     // Split reductions: every non-empty split z of a layer stores its partial tile at ws_wgpart + part_cur + z * span (plain stores,
@@ -774,6 +781,7 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
         CK(conv_wgrad_params(g, (const elem_t*)dy_off, (const elem_t*)in_off, (float*)drel, rows_valid, &p, &fl));
         const int t = wgrad_group_plan(p, beta != 0.f, n.policy.wgrad_stages, n.policy);
         if (t < 0) return UDAPOSE_ERR_UNSUPPORTED;
+        G.rel_bytes.push_back((size_t)p.rows_valid * p.wtaps * ((p.flags & WG_FLAG_SWAP) ? p.Co : p.Ci) * sizeof(float));
         if (p.ksplit > 1) {
             const bool swap = (p.flags & WG_FLAG_SWAP) != 0;
             if (det) CK(make_partial(p, (long long)drel, 0, swap ? p.Co : p.Ci));
@@ -878,6 +886,7 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
         G.n_sum_blk = (int)(blk.size() / 2);
     }
     G.k_beta = beta; G.k_stages = n.policy.wgrad_stages; G.k_part = part;
+    G.k_det = det; G.k_stem = n.policy.wgrad_group_stem != 0; G.part_bytes = part_cur;
     return UDAPOSE_OK;
 }
 
@@ -891,9 +900,13 @@ size_t wg_partial_bytes(Net& n) {
 
 // The tables hold OFFSETS (relative to the arenas and to grads[0]), so one pair of tables - overwrite and accumulate mode -
 // serves every pass whose gradient tensors keep their relative placement (both per-pass gradient buffers of a step do).
+// Only tables built under the plan's current policy qualify (split form, split length, stem), and partial tiles only while the
+// workspace size the caller was last given (udapose_net_ws_bytes) holds them.
 Net::WgGroup* find_wg_group(Net& n, void* const* grads, float beta, int part) {
+    const bool det = n.policy.wgrad_det && n.policy.wgrad_group, stem = n.policy.wgrad_group_stem != 0;
     for (auto& g : n.wg_groups) {
-        if (g.k_beta != beta || g.k_stages != n.policy.wgrad_stages || g.k_part != part) continue;
+        if (g.k_beta != beta || g.k_stages != n.policy.wgrad_stages || g.k_part != part || g.k_det != det || g.k_stem != stem) continue;
+        if (g.k_det && g.part_bytes > n.ws_wgpart_bytes) continue;
         bool same = true;
         for (auto& r : g.rel)
             if ((const char*)grads[r.first] - (const char*)grads[0] != r.second) { same = false; break; }
@@ -928,7 +941,7 @@ int wg_before(hipStream_t s, Net& n, Net::WgGroup* G, char* ws, void* const* gra
             if (pw_zero(s, (char*)grads[0] + z.first, z.second) != UDAPOSE_OK) return UDAPOSE_ERR_LAUNCH;
     }
     const ConvGeom& sg = n.stem.g;
-    if (with_stem && !(n.policy.wgrad_det && n.policy.wgrad_group) && pw_zero(s, ws + n.ws_dwtmp, (size_t)sg.Co * sg.KH * 8 * 8 * sizeof(float)) != UDAPOSE_OK) return UDAPOSE_ERR_LAUNCH;
+    if (with_stem && !G->k_det && pw_zero(s, ws + n.ws_dwtmp, (size_t)sg.Co * sg.KH * 8 * 8 * sizeof(float)) != UDAPOSE_OK) return UDAPOSE_ERR_LAUNCH;
     return UDAPOSE_OK;
 }
 int wg_after(hipStream_t s, Net& n, Net::WgGroup* G, char* ws, void* const* grads, float beta, bool with_stem, bool sums_done = false) {
@@ -939,10 +952,28 @@ int wg_after(hipStream_t s, Net& n, Net::WgGroup* G, char* ws, void* const* grad
                              (long)sg.KH * sg.KW * 3, (long)sg.KW * 3, 3, 1, beta));
     return UDAPOSE_OK;
 }
+// does any byte the grouped launches of pass A write (the weight gradients of its table, the stem's) belong to a tensor pass B writes?
+// (compared as the spans [lowest start, highest end) of each pass's tensors: disjoint buffers never overlap, interleaved ones are
+// taken as overlapping - the safe answer)
+bool wg_overlap(const Net& n, const Net::WgGroup* GA, void* const* gradsA, const Net::WgGroup* GB, void* const* gradsB, bool with_stem) {
+    auto span = [&](const Net::WgGroup* G, void* const* grads, uintptr_t& lo, uintptr_t& hi) {
+        lo = UINTPTR_MAX; hi = 0;
+        auto add = [&](int idx, size_t bytes) {
+            const uintptr_t a = (uintptr_t)grads[idx];
+            lo = std::min(lo, a); hi = std::max(hi, a + bytes);
+        };
+        for (size_t i = 0; i < G->rel.size(); ++i) add(G->rel[i].first, G->rel_bytes[i]);
+        if (with_stem) add(n.stem.w_idx, (size_t)n.stem.g.Co * n.stem.g.KH * n.stem.g.KW * 3 * sizeof(float));
+    };
+    uintptr_t la, ha, lb, hb;
+    span(GA, gradsA, la, ha);
+    span(GB, gradsB, lb, hb);
+    return la < hb && lb < ha;
+}
 int run_wg_group(hipStream_t s, Net& n, const char* act, char* ws, void* const* grads, float beta, int part) {
     Net::WgGroup* G = find_wg_group(n, grads, beta, part);
     if (!G) return UDAPOSE_ERR_NOT_PREPARED;
-    const bool with_stem = part_sel(n, part).stem && n.policy.wgrad_group_stem;
+    const bool with_stem = part_sel(n, part).stem && G->k_stem;
     CK(wg_before(s, n, G, ws, grads, with_stem));
     for (int t = 0; t < WG_CLASSES; ++t) {
         if (!G->per_xcd[t]) continue;
@@ -963,11 +994,14 @@ int run_wg_pair(hipStream_t s, Net& n, const char* actA, char* wsA, void* const*
     if (!GA || !GB) return UDAPOSE_ERR_NOT_PREPARED;
     bool same = true;
     for (int t = 0; t < WG_CLASSES; ++t) same = same && GA->per_xcd[t] == GB->per_xcd[t];
-    if (!same) {        // (different table shapes: two launches)
+    const bool with_stem = part_sel(n, part).stem && GA->k_stem;
+    // One grid runs the two passes' tiles in any order, so their gradient tensors must not share a byte: a pass that accumulates onto
+    // the other's result (one buffer, beta 0 then 1) needs the other's stores to have landed - two launches in order.
+    if (same && wg_overlap(n, GA, gradsA, GB, gradsB, with_stem)) same = false;
+    if (!same) {        // (different table shapes, or overlapping tensors: two launches)
         CK(run_wg_group(s, n, actA, wsA, gradsA, betaA, part));
         return run_wg_group(s, n, actB, wsB, gradsB, betaB, part);
     }
-    const bool with_stem = part_sel(n, part).stem && n.policy.wgrad_group_stem;
     CK(wg_before(s, n, GA, wsA, gradsA, with_stem));
     CK(wg_before(s, n, GB, wsB, gradsB, with_stem));
     for (int t = 0; t < WG_CLASSES; ++t) {
@@ -978,8 +1012,9 @@ int run_wg_pair(hipStream_t s, Net& n, const char* actA, char* wsA, void* const*
         conv_prof_after(s, tok);
         CK(rc);
     }
-    // (equal accumulate modes: the two passes' split sums share their job table - one launch over both workspaces)
-    const bool pair_sum = betaA == betaB && GA->n_sum_blk > 0 && GA->n_sum_blk == GB->n_sum_blk;
+    // (one table for both passes - equal accumulate modes and the same relative placement of the gradient tensors, so that the jobs'
+    // destination offsets hold for both: their split sums share it, one launch over both workspaces)
+    const bool pair_sum = GA == GB && GA->n_sum_blk > 0;
     if (pair_sum) CK(pw_split_sum(s, GA->d_sum, GA->d_sum_blk, GA->n_sum_blk, wsA, (char*)gradsA[0], wsB, (char*)gradsB[0]));
     CK(wg_after(s, n, GA, wsA, gradsA, betaA, with_stem, pair_sum));
     return wg_after(s, n, GB, wsB, gradsB, betaB, with_stem, pair_sum);

@@ -499,14 +499,16 @@ class PoseResNet(nn.Module):
 
     def finish_wgrad(self):
         """Launch the grouped weight gradients of the backward passes that ran with merge_wgrad, on the current stream (the caller
-        has made it wait for the streams those passes ran on): two pending passes of one plan go out as ONE launch per tile class."""
+        has made it wait for the streams those passes ran on): two pending passes of one plan go out as ONE launch per tile class when
+        they write different gradient buffers.  Two passes into ONE buffer (both on one stream: the second accumulates, beta 1, onto the
+        first) launch in order - in one grid the second pass's adds could land before the first pass's stores."""
         pend, self._pending_wg = self._pending_wg, []
         if not pend:
             return
         s = _hip.stream()
         cur = torch.cuda.current_stream()
         pa, ba, params = self._pointers()
-        if len(pend) == 2 and pend[0][0] is pend[1][0]:
+        if len(pend) == 2 and pend[0][0] is pend[1][0] and pend[0][3][0] != pend[1][3][0]:
             (hd, actA, wsA, gA, bA, _), (_, actB, wsB, gB, bB, _) = pend
             check(hd.L.udapose_net_wgrad_pair(hd.h, s, ptr(actA), ptr(wsA), gA, bA, ptr(actB), ptr(wsB), gB, bB, 0), "net_wgrad_pair")
         else:
