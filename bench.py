@@ -12,11 +12,15 @@ K=16, 256x256, N=32 per GPU, bf16 compute / fp32 master weights (BASELINE.json c
     python bench.py --gpus 8 --steps 10 --warmup 3      # no launcher: starts its own 8 ranks (fresh child processes, spawned
                                                         # before this process touches the GPU) and relays rank 0's JSON line
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: it
+sets up, spins the device up, runs the W warm-up steps, times the K steps (hipGraph replays and nothing else), writes
+--dump-outputs if given and prints the line.  With --full it then runs, untimed, everything else the line can report:
+  "ms_per_step_synced", "ms_per_step_deferred_readback": the step in loops that synchronise / read back every iteration;
   "roofline":     MFMA roofline of the dominant kernel family (implicit-GEMM fprop/dgrad), from HIP events recorded on the
-                  launch stream around every convolution launch of ONE eager, instrumented step that runs AFTER the timed
-                  region (the timed region is K hipGraph replays and nothing else);
-  "cpu_baseline": the CPU oracle's (oracle/step_ref.py, plain torch fp32) throughput on this host, bounded sample.
+                  launch stream around every convolution launch of ONE eager, instrumented step;
+  "cpu_baseline": the CPU oracle's (oracle/step_ref.py, plain torch fp32) throughput on this host, bounded sample, and the
+                  measured "parity" of the device step against it;
+  "other_configs": the other precisions and BASELINE.json configurations; "replicas_in_sync" (data parallel).
 """
 import argparse
 import ctypes
@@ -58,7 +62,7 @@ def measured_traffic_per_igemm_launch():
 
 def measured_traffic_per_step(eager_steps=9):
     """HBM bytes per step of the three kernel families (igemm, BatchNorm, weight gradients) from the same committed PMC passes
-    (9 eager steps in the profiled run: `--eager --steps 3 --warmup 1` = 1 + 3 timed + 3 synchronised-loop + 2 roofline steps): what the whole step moves, next to the per-launch figure of the dominant kernel."""
+    (9 eager steps in the profiled run: `--eager --steps 3 --warmup 1 --full` = 1 + 3 timed + 3 synchronised-loop + 2 roofline steps): what the whole step moves, next to the per-launch figure of the dominant kernel."""
     try:
         import ast
         d = ast.literal_eval(open(_pmc_traffic_file()).read().strip())
@@ -427,8 +431,11 @@ def main():
                     "--one-bucket) runs the form the flags name")
     ap.add_argument("--grad-comm", default=None, choices=["fp32", "bf16"], help="data parallel: wire format of the gradient buckets (bf16: one "
                     "rounding per contribution, all-to-all + fp32 accumulation on the shard's owner + all-gather: half the bytes per xGMI link)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-trained-parity", action="store_true", help="skip the parity leg on a network trained in this run (~20 s)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run the untimed legs the headline does not need: the "
+                    "synchronising and deferred-read-back loop rates, the instrumented roofline step, the CPU baseline and the measured parity, "
+                    "the other precisions and configurations (one rank, headline configuration) and the data-parallel replica check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity legs")
+    ap.add_argument("--no-trained-parity", action="store_true", help="--full: skip the parity leg on a network trained in this run (~20 s)")
     ap.add_argument("--capture-comm", action="store_true", help="data parallel: capture the RCCL collectives INTO the step's one graph (round 5; +0.4 ms instead of +0.8 ms "
                     "over the plain step at one rank) instead of keeping them eager between four graphs.  Opt-in (round 6, ADVICE r5): the capture rests on a timed "
                     "wait for RCCL's watchdog and replayed collectives are invisible to torch.distributed's timeout; if it fails on any rank all ranks fall back together")
@@ -441,7 +448,7 @@ def main():
                     "data-parallel step (graphs and collectives); device ms per part on stderr")
     ap.add_argument("--arena-teacher", action="store_true", help="tuning: no-grad forwards keep the bump-allocated 2.8 GB arena instead of the forward-only "
                     "plan's six rotating scratch buffers (A/B of round 5's default)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the untimed extra legs (fp16 / reference precision mix rates)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the untimed extra legs (fp16 / reference precision mix rates)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step returned "
                     "(losses, heat-maps, masks) as DIR/<name>.npy, float32 / float64, at most 64 MB (larger outputs: a fixed seeded sample), rank 0; "
                     "the host generator is seeded and the state the spin-up steps leave is rolled back before the warm-up, so that the same "
@@ -717,40 +724,41 @@ def main():
         print("dp segments (device ms per part, mean of 20 steps):", graphed.segment_ms(), file=sys.stderr, flush=True)
         graphed.profile_segments = False
     trainer.sync.profile = False
-    # The synchronous-loop rate (untimed extra, after the timed region): one torch.cuda.synchronize() per step, as a loop that reads
-    # the loss / PCK of every iteration on the host forces (train_human.py:443 moves y_s to the CPU each iteration)
-    sync_ms = []
-    for i in range(min(args.steps, 40)):
-        t_a = time.perf_counter()
-        out = step()
+    ms_synced, ms_deferred, last_metrics, prof = None, None, None, None
+    if args.full:
+        # The synchronous-loop rate (untimed extra, after the timed region): one torch.cuda.synchronize() per step, as a loop that reads
+        # the loss / PCK of every iteration on the host forces (train_human.py:443 moves y_s to the CPU each iteration)
+        sync_ms = []
+        for i in range(min(args.steps, 40)):
+            t_a = time.perf_counter()
+            out = step()
+            torch.cuda.synchronize()
+            sync_ms.append((time.perf_counter() - t_a) * 1e3)
+        sync_ms.sort()
+        ms_synced = sync_ms[len(sync_ms) // 2] if sync_ms else None
+        # The same loop with the read-back DEFERRED by one step (GraphedTrainStep.step_async: losses + device PCK of step i are read from a
+        # pinned double buffer while step i+1 is already queued): what a loop that logs every iteration costs with this engine
+        if not args.eager and host is None and getattr(graphed, "metrics", False):
+            nd = min(args.steps, 40)
+            torch.cuda.synchronize()
+            t_a = time.perf_counter()
+            for i in range(nd):
+                last_metrics = graphed.step_async(None, None, None, None, None, g["aug_param_stu"], g["aug_param_tea"])
+            last_metrics = graphed.flush_metrics()
+            ms_deferred = (time.perf_counter() - t_a) / nd * 1e3
+        # Roofline sample, UNTIMED, after the timed region: one eager step on ONE stream with HIP events recorded on the launch
+        # stream around every convolution launch (events cannot be placed inside a replayed graph; single-stream so that the
+        # per-launch durations are comparable with rocprofv3's, which serialises).  A dry run first creates the profiler's event
+        # pool (~1100 hipEventCreate calls).
+        prof = (ctypes.c_double * 9)()
+        trainer.concurrent = False
+        for dry in (True, False):
+            lib.udapose_prof_begin()
+            out_prof = eager_step()
+            torch.cuda.synchronize()
+            _hip.check(lib.udapose_prof_end(prof), "prof_end")
+        trainer.concurrent = True
         torch.cuda.synchronize()
-        sync_ms.append((time.perf_counter() - t_a) * 1e3)
-    sync_ms.sort()
-    ms_synced = sync_ms[len(sync_ms) // 2] if sync_ms else None
-    # The same loop with the read-back DEFERRED by one step (GraphedTrainStep.step_async: losses + device PCK of step i are read from a
-    # pinned double buffer while step i+1 is already queued): what a loop that logs every iteration costs with this engine
-    ms_deferred, last_metrics = None, None
-    if not args.eager and host is None and getattr(graphed, "metrics", False):
-        nd = min(args.steps, 40)
-        torch.cuda.synchronize()
-        t_a = time.perf_counter()
-        for i in range(nd):
-            last_metrics = graphed.step_async(None, None, None, None, None, g["aug_param_stu"], g["aug_param_tea"])
-        last_metrics = graphed.flush_metrics()
-        ms_deferred = (time.perf_counter() - t_a) / nd * 1e3
-    # Roofline sample, UNTIMED, after the timed region: one eager step on ONE stream with HIP events recorded on the launch
-    # stream around every convolution launch (events cannot be placed inside a replayed graph; single-stream so that the
-    # per-launch durations are comparable with rocprofv3's, which serialises).  A dry run first creates the profiler's event
-    # pool (~1100 hipEventCreate calls).
-    prof = (ctypes.c_double * 9)()
-    trainer.concurrent = False
-    for dry in (True, False):
-        lib.udapose_prof_begin()
-        out_prof = eager_step()
-        torch.cuda.synchronize()
-        _hip.check(lib.udapose_prof_end(prof), "prof_end")
-    trainer.concurrent = True
-    torch.cuda.synchronize()
     rank_ms = None
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -764,7 +772,7 @@ def main():
     loss = float(out["loss_all"])
     assert loss == loss, "loss is NaN"
     in_sync = None
-    if world > 1:
+    if world > 1 and args.full:
         # data-parallel invariant (outside the timed region): every rank holds the same student and teacher after the run
         chk = torch.stack([sum(p.detach().double().sum() for p in m.parameters()) for m in (student, teacher)]).to(dev)
         every = [torch.zeros_like(chk) for _ in range(world)]
@@ -774,11 +782,6 @@ def main():
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         value = world * N * args.steps / elapsed
-        fl, ms_f, fp_f = prof[0], prof[1], prof[2]
-        dl, ms_d, fp_d = prof[3], prof[4], prof[5]
-        wl, ms_w, fp_w = prof[6], prof[7], prof[8]
-        ig_l, ig_ms, ig_fl = fl + dl, ms_f + ms_d, fp_f + fp_d
-        achieved = ig_fl / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
         layers = {"pose_resnet101": [3, 4, 23, 3], "pose_resnet50": [3, 4, 6, 3]}[args.arch]
         if args.eager:
             launch_desc = "eager"
@@ -794,7 +797,7 @@ def main():
             else:
                 what = "1 hipGraph (forwards, losses, backward, Adam + EMA + packs)" if graphed.one_graph else "2 hipGraphs"
             launch_desc = (("2 style-transfer hipGraphs (alpha on the device) + " if args.config2 else "") + what
-                           + "; timed region = graph replays only (the instrumented eager roofline sample runs after it, untimed)")
+                           + "; timed region = graph replays only" + (" (the instrumented eager roofline sample runs after it, untimed)" if args.full else ""))
         res = {
             "metric": f"images/sec (student+teacher step) {S}x{S} b={N}", "value": round(value, 2), "unit": "images/sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
@@ -823,39 +826,46 @@ def main():
             "replicas_in_sync": in_sync, "inputs": "pinned host memory: every step's batch is copied H2D on a copy stream under the previous step" if args.host_inputs else "resident in HBM",
             "step_tflops_per_gpu": round(7 * N * FWD_GFLOP_PER_IMAGE / 1e3 / (ms * 1e-3), 2) if (args.arch, S, K) == ("pose_resnet101", 256, 16) else None,
             "policy_overrides": (tune or None), "valid": True,
-            "roofline": {"bound": "mfma", "kernel": f"igemm_kernel (implicit-GEMM conv fprop+dgrad, {args.dtype} MFMA 16x16x32)",
-                         "bound_note": "priced against the dense MFMA peak as SURVEY.md 8(d) prescribes for the convolutions (>99 % of the FLOPs); the MEASURED "
-                                       "limiter of these launches is neither roof: per-CU L2->LDS operand fill (137-146 GB/s per CU, shared by the step's three "
-                                       "streams) and launch-chain latency (MFMA pipe 4-22 % busy, 44-80 % of wave cycles in s_waitcnt / s_barrier: "
-                                       "profiles/r5_pmc_sq_by_shape.txt, r4_probes.txt, r5_ab_runs.txt); hbm_frac is the same launches priced against HBM",
-                         "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": measured_traffic_per_igemm_launch(),
-                         "traffic_note": "HBM bytes per igemm launch from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes "
-                                         f"(profiles/{os.path.basename(_pmc_traffic_file())}), not collected live",
-                         "launches_per_step": int(ig_l), "avg_launch_us": round(ig_ms * 1e3 / max(ig_l, 1), 2),
-                         "flops_per_launch_avg": ig_fl / max(ig_l, 1), "kernel_ms_per_step": round(ig_ms, 3),
-                         "wgrad": {"launches_per_step": int(wl), "kernel_ms_per_step": round(ms_w, 3),
-                                   "achieved": round(fp_w / (ms_w * 1e-3) / 1e12, 2) if ms_w > 0 else None}},
+            "roofline": None,
         }
-        per_step = measured_traffic_per_step()
-        if per_step and (args.arch, S, K, N, args.dtype, args.precision) == ("pose_resnet101", 256, 16, 32, "bf16", None) and not args.config2:      # (the PMC passes are the headline's)
-            tot = sum(per_step.values())
-            res["roofline"]["step_hbm"] = {"bytes_per_step": tot, "by_family": per_step, "achieved_TBps": round(tot / (ms * 1e-3) / 1e12, 3),
-                                           "peak_TBps": 8.0, "note": "whole-step HBM traffic of the conv / BN / weight-gradient kernels (PMC passes under "
-                                           "profiles/) over this run's step time"}
-            res["roofline"]["hbm_frac"] = round(tot / (ms * 1e-3) / 8e12, 4)       # whole-step HBM bytes / step time / 8 TB/s
-            # the step against the floor of its own traffic: the PMC bytes above + the optimizer sweep's 46 B / parameter + ~0.6 GB of
-            # conversions / packs at the 6.0 TB/s this chip streams through the paths these kernels use, + the L2-hit part of the operand fills
-            # (~66 GB of the implicit GEMMs' ~90 GB, ~0.5 ms for the weight gradients) at the 35 TB/s that path gives - all constants cited from profiles/
-            floor_ms = (tot + 2.5e9 + 0.6e9) / 6.0e12 * 1e3 + 66e9 / 35e12 * 1e3 + 0.5
-            res["roofline"]["step_hbm"]["traffic_floor"] = {
-                "floor_ms": round(floor_ms, 2), "frac_of_floor": round(floor_ms / ms, 4), "cited": True,
-                "note": "what this step's own memory traffic costs with every latency hidden (57 GB at 6.0 TB/s + L2-hit operand fills at 35 TB/s; "
-                        "profiles/r4_probes.txt, r5_probe_lds_fill_tiles.txt, r5_pmc_hbm_traffic.txt) over this run's step time: the statement that goes "
-                        "with 'frac' (the convolutions priced against the MFMA peak)"}
+        if args.full:
+            fl, ms_f, fp_f = prof[0], prof[1], prof[2]
+            dl, ms_d, fp_d = prof[3], prof[4], prof[5]
+            wl, ms_w, fp_w = prof[6], prof[7], prof[8]
+            ig_l, ig_ms, ig_fl = fl + dl, ms_f + ms_d, fp_f + fp_d
+            achieved = ig_fl / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
+            res["roofline"] = {"bound": "mfma", "kernel": f"igemm_kernel (implicit-GEMM conv fprop+dgrad, {args.dtype} MFMA 16x16x32)",
+                               "bound_note": "priced against the dense MFMA peak as SURVEY.md 8(d) prescribes for the convolutions (>99 % of the FLOPs); the MEASURED "
+                                             "limiter of these launches is neither roof: per-CU L2->LDS operand fill (137-146 GB/s per CU, shared by the step's three "
+                                             "streams) and launch-chain latency (MFMA pipe 4-22 % busy, 44-80 % of wave cycles in s_waitcnt / s_barrier: "
+                                             "profiles/r5_pmc_sq_by_shape.txt, r4_probes.txt, r5_ab_runs.txt); hbm_frac is the same launches priced against HBM",
+                               "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                               "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": measured_traffic_per_igemm_launch(),
+                               "traffic_note": "HBM bytes per igemm launch from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes "
+                                               f"(profiles/{os.path.basename(_pmc_traffic_file())}), not collected live",
+                               "launches_per_step": int(ig_l), "avg_launch_us": round(ig_ms * 1e3 / max(ig_l, 1), 2),
+                               "flops_per_launch_avg": ig_fl / max(ig_l, 1), "kernel_ms_per_step": round(ig_ms, 3),
+                               "wgrad": {"launches_per_step": int(wl), "kernel_ms_per_step": round(ms_w, 3),
+                                         "achieved": round(fp_w / (ms_w * 1e-3) / 1e12, 2) if ms_w > 0 else None}}
+            per_step = measured_traffic_per_step()
+            if per_step and (args.arch, S, K, N, args.dtype, args.precision) == ("pose_resnet101", 256, 16, 32, "bf16", None) and not args.config2:      # (the PMC passes are the headline's)
+                tot = sum(per_step.values())
+                res["roofline"]["step_hbm"] = {"bytes_per_step": tot, "by_family": per_step, "achieved_TBps": round(tot / (ms * 1e-3) / 1e12, 3),
+                                               "peak_TBps": 8.0, "note": "whole-step HBM traffic of the conv / BN / weight-gradient kernels (PMC passes under "
+                                               "profiles/) over this run's step time"}
+                res["roofline"]["hbm_frac"] = round(tot / (ms * 1e-3) / 8e12, 4)       # whole-step HBM bytes / step time / 8 TB/s
+                # the step against the floor of its own traffic: the PMC bytes above + the optimizer sweep's 46 B / parameter + ~0.6 GB of
+                # conversions / packs at the 6.0 TB/s this chip streams through the paths these kernels use, + the L2-hit part of the operand fills
+                # (~66 GB of the implicit GEMMs' ~90 GB, ~0.5 ms for the weight gradients) at the 35 TB/s that path gives - all constants cited from profiles/
+                floor_ms = (tot + 2.5e9 + 0.6e9) / 6.0e12 * 1e3 + 66e9 / 35e12 * 1e3 + 0.5
+                res["roofline"]["step_hbm"]["traffic_floor"] = {
+                    "floor_ms": round(floor_ms, 2), "frac_of_floor": round(floor_ms / ms, 4), "cited": True,
+                    "note": "what this step's own memory traffic costs with every latency hidden (57 GB at 6.0 TB/s + L2-hit operand fills at 35 TB/s; "
+                            "profiles/r4_probes.txt, r5_probe_lds_fill_tiles.txt, r5_pmc_hbm_traffic.txt) over this run's step time: the statement that goes "
+                            "with 'frac' (the convolutions priced against the MFMA peak)"}
         # the CPU oracle leg (bounded sample) and, from its first step, the MEASURED parity of this run's precision(s)
         par_ok = (S, K) == (256, 16) and not args.config2
-        if not args.no_cpu_baseline and world == 1:     # (the CPU leg runs on rank 0 of the ONE-rank run only; N > 1 lines carry null)
+        if args.full and not args.no_cpu_baseline and world == 1:     # (the CPU leg runs on rank 0 of the ONE-rank run only; N > 1 lines carry null)
             try:
                 res["cpu_baseline"] = cpu_baseline(args.cpu_images, layers)
             except Exception as e:
@@ -884,7 +894,7 @@ def main():
             res["cpu_baseline"] = None
         # the parity-compliant configurations of the same step, driver-visible (untimed extras after the headline's timed region)
         headline_cfg = (args.arch, S, K, N, args.dtype, args.precision) == ("pose_resnet101", 256, 16, 32, "bf16", None)
-        if world == 1 and headline_cfg and not (args.config2 or args.eager or args.no_other_configs or args.host_inputs or tune):
+        if args.full and world == 1 and headline_cfg and not (args.config2 or args.eager or args.no_other_configs or args.host_inputs or tune):
             try:
                 del graphed
             except NameError:

@@ -785,7 +785,7 @@ def test_two_rank_step_on_one_gpu_gloo(arch, batch):
     env = dict(os.environ, UDAPOSE_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--spinup", "0.7", "--arch", arch, "--batch", str(batch), "--no-cpu-baseline", "--dp-form", "fixed"]
+           "--spinup", "0.7", "--arch", arch, "--batch", str(batch), "--no-cpu-baseline", "--dp-form", "fixed", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -898,7 +898,7 @@ def test_two_rank_config3_step_style_and_occlusion_captured():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(UDAPOSE_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config2", "--steps", "3", "--warmup", "1", "--spinup", "0",
-           "--arch", "pose_resnet50", "--batch", "4", "--no-cpu-baseline", "--dp-form", "fixed"]
+           "--arch", "pose_resnet50", "--batch", "4", "--no-cpu-baseline", "--dp-form", "fixed", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -918,7 +918,7 @@ def test_bench_gpus_flag_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(UDAPOSE_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--spinup", "0",
-           "--arch", "pose_resnet50", "--batch", "4", "--no-cpu-baseline"]
+           "--arch", "pose_resnet50", "--batch", "4", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -960,6 +960,31 @@ def test_bench_dump_outputs_do_not_depend_on_the_spin_up(tmp_path):
         for k, a in res[a_].items():
             d = float(np.abs(a.astype(np.float64) - res[b_][k]).max()) if a.size else 0.0
             assert np.array_equal(a, res[b_][k], equal_nan=True), f"{b_} {k}: the spin-up changed what the timed steps computed (max|d| {d:.3e})"
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_untimed_legs():
+    """A plain `bench.py` run times its steps and prints the line without the untimed legs; `--full` adds the synchronising and
+    deferred-read-back loop rates and the roofline sample (the CPU baseline is left out here: it has a 30 s budget of its own)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    common = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--spinup", "0", "--arch", "pose_resnet50",
+              "--batch", "4"]
+    res = {}
+    for tag, flags in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        out = subprocess.run(common + flags, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, tag + out.stdout[-2000:] + out.stderr[-4000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-2000:]
+        res[tag] = json.loads(lines[0])
+    p, f = res["plain"], res["full"]
+    for d in (p, f):
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["loss"] == d["loss"]
+        assert d["unit"] == "images/sec" and d["higher_is_better"] is True and d["dtype"] == "bf16" and "1 hipGraph (" in d["launch"]
+    assert p["roofline"] is None and p["ms_per_step_synced"] is None and p["ms_per_step_deferred_readback"] is None
+    assert "cpu_baseline" not in p and "other_configs" not in p and "roofline sample" not in p["launch"]
+    assert f["ms_per_step_synced"] > 0 and f["ms_per_step_deferred_readback"] > 0 and f["pck_source_batch"] is not None
+    assert f["roofline"]["launches_per_step"] > 0 and f["roofline"]["achieved"] > 0 and "roofline sample" in f["launch"]
 
 
 def test_one_rank_rccl_step():

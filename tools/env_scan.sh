@@ -6,5 +6,5 @@ for l in sys.stdin:
         d = json.loads(l); print(d["ms_per_step"], d["value"], "synced", d["ms_per_step_synced"])'
 for kv in "$@"; do
   echo -n "[$kv] "
-  env $kv timeout -k 10 200 python bench.py --steps 40 --warmup 3 --spinup 3 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "$P" || echo failed
+  env $kv timeout -k 10 200 python bench.py --full --steps 40 --warmup 3 --spinup 3 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "$P" || echo failed
 done

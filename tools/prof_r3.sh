@@ -1,20 +1,20 @@
 # Round-3 profile collection (one gpurun call): bench lines, kernel stats, HBM traffic PMC passes, SQ counters, precision-mode kernels.
 export TMPDIR=/tmp
 O=gpurun_out/r3prof; mkdir -p $O
-python3 bench.py --steps 20 --warmup 5 > $O/r3_bench_steps20.json 2> $O/r3_bench_steps20.err
-python3 bench.py > $O/r3_bench_default.json 2> $O/r3_bench_default.err
-python3 bench.py --steps 60 --no-cpu-baseline --precision reference > $O/r3_bench_reference.json 2>/dev/null
-python3 bench.py --steps 40 --no-cpu-baseline --config2 > $O/r3_bench_config2_bf16style.json 2>/dev/null
-python3 bench.py --steps 40 --no-cpu-baseline --config2 --precision reference > $O/r3_bench_config2_reference.json 2>/dev/null
-python3 bench.py --steps 60 --no-cpu-baseline --dtype fp16 > $O/r3_bench_config1_fp16.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 > $O/r3_bench_steps20.json 2> $O/r3_bench_steps20.err
+python3 bench.py --full > $O/r3_bench_default.json 2> $O/r3_bench_default.err
+python3 bench.py --full --steps 60 --no-cpu-baseline --precision reference > $O/r3_bench_reference.json 2>/dev/null
+python3 bench.py --full --steps 40 --no-cpu-baseline --config2 > $O/r3_bench_config2_bf16style.json 2>/dev/null
+python3 bench.py --full --steps 40 --no-cpu-baseline --config2 --precision reference > $O/r3_bench_config2_reference.json 2>/dev/null
+python3 bench.py --full --steps 60 --no-cpu-baseline --dtype fp16 > $O/r3_bench_config1_fp16.json 2>/dev/null
 echo "bench lines done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 20 --warmup 3 --spinup 4 --no-cpu-baseline > $O/r3_bench_rocprof_stdout.txt 2> $O/r3_prof_stderr.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --steps 20 --warmup 3 --spinup 4 --no-cpu-baseline > $O/r3_bench_rocprof_stdout.txt 2> $O/r3_prof_stderr.txt
 echo "kernel-trace rc=$?"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 bench.py --eager --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 bench.py --full --eager --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline > /dev/null 2>&1
 echo "pmc fetch rc=$?"
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 bench.py --eager --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 bench.py --full --eager --steps 3 --warmup 1 --spinup 0 --no-cpu-baseline > /dev/null 2>&1
 echo "pmc write rc=$?"
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/pmc_sq -- python3 bench.py --eager --steps 2 --warmup 1 --spinup 0 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/pmc_sq -- python3 bench.py --full --eager --steps 2 --warmup 1 --spinup 0 --no-cpu-baseline > /dev/null 2>&1
 echo "pmc sq rc=$?"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/modes -- python3 tools/time_modes.py bf16,fp32,f16x2 > $O/r3_modes_stdout.txt 2>&1
 echo "modes rc=$?"
