@@ -286,6 +286,43 @@ int udapose_cons_loss_valid_fwd(void* stream, const float* stu, const float* tea
                                 const float* valid_count, int R, int K, int HW, float* rows, float* mean_out);
 int udapose_cons_loss_valid_bwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
                                 const float* valid_count, const float* gscale, int R, int K, int HW, float* dstu);
+/* ---- soft-max losses (lib/models/loss.py:52-173).  Per row r: p_i = exp(s_i - max) / sum_j exp(s_j - max), log p_i = (s_i - max) - log sum.
+ * Every forward writes rows[R] (the per-row loss) and stats (per-row scalars of the backward, layout [n][R]; a row's soft-max is the
+ * triple max, 1 / sum, log sum) and then reduces rows into `out`; every backward is one sweep that needs the forward's stats.  gscale: device scalar (NULL = 1).  No atomics: results are bit-reproducible.
+ * All return UDAPOSE_ERR_ARG for R <= 0, HW <= 0 or a null operand.
+ * JointsKLLoss (loss.py:82-95): q = (g + eps) / sum(g + eps); rows[r] = w[r] * sum_i (xlogy(q_i, q_i) - q_i * log p_i), w optional.
+ * out[R/group] = means over `group` consecutive rows: group = R is reduction='mean', group = K the reference's 'none'
+ * (loss.mean(dim=-1) of the [B,K] rows).  stats [5][R]: the triple, sum(g + eps), sum_i q_i. */
+int udapose_joints_kl_fwd(void* stream, const float* pred, const float* gt, const float* w, float epsilon, int R, int group, int HW, float* rows,
+                          float* stats, float* out);
+/* d pred_i = gscale[0] / R * w[r] * (p_i * sum_j q_j - q_i)   (reduction='mean') */
+int udapose_joints_kl_bwd(void* stream, const float* pred, const float* gt, const float* w, float epsilon, const float* stats,
+                          const float* gscale, int R, int HW, float* dpred);
+/* EntLoss (loss.py:103-117): rows[r] = H_r / log(HW), H_r = -sum_i p_i log p_i.  threshold > 0 selects the rows below it (loss.py:111-112):
+ * out[0] = their mean, count[0] = their number (0 selected: NaN); it needs group = R.  Otherwise out[R/group] = group means and
+ * count[0] = group.  stats [4][R]: the triple, H_r. */
+int udapose_entropy_loss_fwd(void* stream, const float* x, int R, int group, int HW, float threshold, float* rows, float* stats, float* out,
+                             float* count);
+/* dx_i = -gscale[0] / count[0] * sel_r * p_i * (log p_i + H_r) / log(HW), sel_r from rows[r] < threshold */
+int udapose_entropy_loss_bwd(void* stream, const float* x, const float* rows, const float* stats, const float* count, const float* gscale,
+                             float threshold, int R, int HW, float* dx);
+/* ConsSoftmaxLoss (loss.py:139-152): ConsLoss on the two soft-maxes: out[0] = sum_r mask[r] sum_i (p_i - pt_i)^2 / (R*HW); with `valid`
+ * ([R/K][HW], valid_count from udapose_mask_count) only the selected (b,h,w) positions, divided by K * valid_count (loss.py:149-150).
+ * mask, valid optional.  stats [7][R]: the student's triple, the teacher's, A_r = sum_j v_j p_j (p_j - pt_j). */
+int udapose_cons_softmax_fwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
+                             const float* valid_count, int R, int K, int HW, float* rows, float* stats, float* out);
+/* d stu_i = 2 c mask[r] p_i (v_i (p_i - pt_i) - A_r), c = gscale[0] / (R*HW) or gscale[0] / (K * valid_count) */
+int udapose_cons_softmax_bwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
+                             const float* valid_count, const float* stats, const float* gscale, int R, int K, int HW, float* dstu);
+/* ConsKLLoss (loss.py:160-173), reduced like ConsSoftmaxLoss.  log_target = 0 is the reference as written: KLDivLoss(log_target=False) is
+ * handed the teacher's LOG-probabilities t_i = log pt_i as its target and evaluates xlogy(t_i, t_i) - t_i * log p_i, NaN wherever
+ * t_i < 0 (every map of more than one pixel).  log_target = 1 (an extension) is the divergence itself, pt_i * (log pt_i - log p_i).
+ * stats [7][R]: the student's triple, the teacher's, S_r = sum_j v_j u_j with u = pt (log_target) or log pt. */
+int udapose_cons_kl_fwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
+                        const float* valid_count, int log_target, int R, int K, int HW, float* rows, float* stats, float* out);
+/* d stu_i = c mask[r] (p_i S_r - v_i u_i) */
+int udapose_cons_kl_bwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
+                        const float* valid_count, int log_target, const float* stats, const float* gscale, int R, int K, int HW, float* dstu);
 /* get_max_preds(_torch) (lib/keypoint_detection.py:9-37, utils.py:54-75) and rectify (utils.py:77-109): any output may
  * be NULL.  patch: [(2*rad+1)^2] fp32 Gaussian table built by the caller exactly as utils.py:93-98 does. */
 int udapose_heatmap_argmax(void* stream, const float* hm, int R, int H, int W, float* maxvals, int* flat_idx, float* preds_xy,

@@ -107,6 +107,14 @@ _SIGS = {
     "udapose_mask_count": (ci, [vp, vp, sz, vp]),
     "udapose_cons_loss_valid_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp]),
     "udapose_cons_loss_valid_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]),
+    "udapose_joints_kl_fwd": (ci, [vp, vp, vp, vp, cf, ci, ci, ci, vp, vp, vp]),
+    "udapose_joints_kl_bwd": (ci, [vp, vp, vp, vp, cf, vp, vp, ci, ci, vp]),
+    "udapose_entropy_loss_fwd": (ci, [vp, vp, ci, ci, ci, cf, vp, vp, vp, vp]),
+    "udapose_entropy_loss_bwd": (ci, [vp, vp, vp, vp, vp, vp, cf, ci, ci, vp]),
+    "udapose_cons_softmax_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]),
+    "udapose_cons_softmax_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]),
+    "udapose_cons_kl_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
+    "udapose_cons_kl_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, vp]),
     "udapose_heatmap_argmax": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci]),
     "udapose_kth_mask": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, ci]),
     "udapose_pck": (ci, [vp, vp, vp, ci, ci, cf, cf, cf, vp, vp]),

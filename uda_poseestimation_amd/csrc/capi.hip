@@ -40,6 +40,14 @@ int hm_sqdiff_rows(hipStream_t, const float*, const float*, const float*, const 
 int hm_sqdiff_bwd(hipStream_t, const float*, const float*, const float*, const unsigned char*, const float*, float, int, int, float*,
                   const unsigned char*, const float*, int);
 int hm_mask_count(hipStream_t, const unsigned char*, size_t, float*);
+int sml_kl_fwd(hipStream_t, const float*, const float*, const float*, float, int, int, int, float*, float*, float*);
+int sml_kl_bwd(hipStream_t, const float*, const float*, const float*, float, const float*, const float*, int, int, float*);
+int sml_ent_fwd(hipStream_t, const float*, int, int, int, float, float*, float*, float*, float*);
+int sml_ent_bwd(hipStream_t, const float*, const float*, const float*, const float*, const float*, float, int, int, float*);
+int sml_cons_fwd(hipStream_t, int, const float*, const float*, const unsigned char*, const unsigned char*, const float*, int, int, int, float*,
+                 float*, float*);
+int sml_cons_bwd(hipStream_t, int, const float*, const float*, const unsigned char*, const unsigned char*, const float*, const float*,
+                 const float*, int, int, int, float*);
 int pw_maxpool2x2_ceil_f32(hipStream_t, const float*, float*, int, int, int, int);
 int pw_nchw_f32_to_nhwc_f32(hipStream_t, const float*, float*, int, int, int, int);
 int adain_launch_f32(hipStream_t, const float*, const float*, float*, int, int, int, int, float, float, const float*, float*);
@@ -342,6 +350,38 @@ int udapose_cons_loss_valid_bwd(void* stream, const float* stu, const float* tea
                                 const float* valid_count, const float* gscale, int R, int K, int HW, float* dstu) {
     if (!valid || !valid_count) return UDAPOSE_ERR_ARG;
     return hm_sqdiff_bwd(S(stream), stu, tea, nullptr, mask, gscale, (float)(2.0 / ((double)R * HW)), R, HW, dstu, valid, valid_count, K);
+}
+int udapose_joints_kl_fwd(void* stream, const float* pred, const float* gt, const float* w, float epsilon, int R, int group, int HW, float* rows,
+                          float* stats, float* out) {
+    return sml_kl_fwd(S(stream), pred, gt, w, epsilon, R, group, HW, rows, stats, out);
+}
+int udapose_joints_kl_bwd(void* stream, const float* pred, const float* gt, const float* w, float epsilon, const float* stats,
+                          const float* gscale, int R, int HW, float* dpred) {
+    return sml_kl_bwd(S(stream), pred, gt, w, epsilon, stats, gscale, R, HW, dpred);
+}
+int udapose_entropy_loss_fwd(void* stream, const float* x, int R, int group, int HW, float threshold, float* rows, float* stats, float* out,
+                             float* count) {
+    return sml_ent_fwd(S(stream), x, R, group, HW, threshold, rows, stats, out, count);
+}
+int udapose_entropy_loss_bwd(void* stream, const float* x, const float* rows, const float* stats, const float* count, const float* gscale,
+                             float threshold, int R, int HW, float* dx) {
+    return sml_ent_bwd(S(stream), x, rows, stats, count, gscale, threshold, R, HW, dx);
+}
+int udapose_cons_softmax_fwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
+                             const float* valid_count, int R, int K, int HW, float* rows, float* stats, float* out) {
+    return sml_cons_fwd(S(stream), 0, stu, tea, mask, valid, valid_count, R, K, HW, rows, stats, out);
+}
+int udapose_cons_softmax_bwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
+                             const float* valid_count, const float* stats, const float* gscale, int R, int K, int HW, float* dstu) {
+    return sml_cons_bwd(S(stream), 0, stu, tea, mask, valid, valid_count, stats, gscale, R, K, HW, dstu);
+}
+int udapose_cons_kl_fwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
+                        const float* valid_count, int log_target, int R, int K, int HW, float* rows, float* stats, float* out) {
+    return sml_cons_fwd(S(stream), log_target ? 1 : 2, stu, tea, mask, valid, valid_count, R, K, HW, rows, stats, out);
+}
+int udapose_cons_kl_bwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
+                        const float* valid_count, int log_target, const float* stats, const float* gscale, int R, int K, int HW, float* dstu) {
+    return sml_cons_bwd(S(stream), log_target ? 1 : 2, stu, tea, mask, valid, valid_count, stats, gscale, R, K, HW, dstu);
 }
 int udapose_heatmap_argmax(void* stream, const float* hm, int R, int H, int W, float* maxvals, int* flat_idx, float* preds, float* rect,
                            const float* patch, int rad) {

@@ -198,12 +198,18 @@ class MeanTeacherTrainer:
     def __init__(self, student, teacher, lr=1e-4, teacher_alpha=0.999, lambda_c=1.0, mask_ratio=0.5, sigma=2, image_size=256,
                  heatmap_size=64, use_sgd=False, style_net=None, recover=None, s2t_freq=0.5, t2s_freq=0.5, s2t_alpha=(0.0, 1.0),
                  t2s_alpha=(0.0, 1.0), rng=None, occlude_rate=-1.0, occlude_thresh=0.9, occlude_size=10, image_px=None, precision=None,
-                 loss_scale_init=65536.0, loss_scale_interval=2000, grad_comm="fp32"):
+                 loss_scale_init=65536.0, loss_scale_interval=2000, grad_comm="fp32", criterion=None, con_criterion=None, ent_criterion=None,
+                 lambda_ent=0.0):
         # a single-device nn.DataParallel wrap (the reference's call form) is unwrapped: the engine drives the executor's own entry points
         # (prepare / forward_deferred_bn / finish_wgrad ...), which live on the module
         student, teacher = getattr(student, "module", student), getattr(teacher, "module", teacher)
         self.student, self.teacher = student, teacher
-        self.criterion, self.con_criterion = JointsMSELoss(), ConsLoss()
+        # the supervised and the consistency loss, called as the reference calls them (train_human.py:421,432): None = the scripts' own
+        # JointsMSELoss / ConsLoss; any lib.models.loss class of the same call form may be given (JointsKLLoss, ConsSoftmaxLoss, ...).
+        # ent_criterion (optional, e.g. EntLoss): lambda_ent * ent_criterion(student's re-warped target heat-maps) joins loss_all
+        self.criterion = criterion if criterion is not None else JointsMSELoss()
+        self.con_criterion = con_criterion if con_criterion is not None else ConsLoss()
+        self.ent_criterion, self.lambda_ent = ent_criterion, lambda_ent
         # precision: None keeps what the networks are set to (a new PoseResNet is 'auto': a differentiable forward outside
         # autocast runs bf16, the teacher's no-grad forward the fp32-grade 'f16x2' mode).
         # 'reference' = the reference's own precision mix (train_human.py:346-358,414): the student in fp16 (its autocast dtype)
@@ -487,6 +493,10 @@ class MeanTeacherTrainer:
             y_t_tea_rect = st["y_t_tea_rect"] if st.get("y_t_tea_rect") is not None else mt.rectify(st["y_t_tea_recon"], sigma=self.sigma)
         loss_c = self.con_criterion(st["y_t_stu_recon"], y_t_tea_rect, tea_mask=tea_mask)
         loss_all = loss_s + self.lambda_c * loss_c
+        loss_ent = None
+        if self.ent_criterion is not None:
+            loss_ent = self.ent_criterion(st["y_t_stu_recon"])
+            loss_all = loss_all + self.lambda_ent * loss_ent
         self.stu_optimizer.scale_loss(loss_all).backward()      # (scaler.scale(loss_all).backward(), train_human.py:436; identity in bf16)
         if s_stu is not main:
             main.wait_stream(s_stu)             # the target-domain backward ran on its own stream
@@ -505,8 +515,11 @@ class MeanTeacherTrainer:
             # read both buffers itself (one rank: nothing else looks at the gradients in between)
             student.finish_grads(defer=self._tail_sums_grads())
         # (the re-warped heat-maps of both networks are handed out for the parity tests and bench.py's measured parity: references only)
-        return {"loss_all": loss_all.detach(), "loss_s": loss_s.detach(), "loss_c": loss_c.detach(), "y_s": st["y_s"].detach(),
-                "tea_mask": tea_mask, "y_t_tea_recon": st["y_t_tea_recon"], "y_t_stu_recon": st["y_t_stu_recon"].detach()}
+        out = {"loss_all": loss_all.detach(), "loss_s": loss_s.detach(), "loss_c": loss_c.detach(), "y_s": st["y_s"].detach(),
+               "tea_mask": tea_mask, "y_t_tea_recon": st["y_t_tea_recon"], "y_t_stu_recon": st["y_t_stu_recon"].detach()}
+        if loss_ent is not None:
+            out["loss_ent"] = loss_ent.detach()
+        return out
 
     def _forward_backward(self, x_s, label_s, weight_s, x_t_stu, x_t_teas, theta_stu, thetas_tea):
         st = self._forward_part(x_s, label_s, weight_s, x_t_stu, x_t_teas, theta_stu, thetas_tea)
@@ -840,6 +853,8 @@ class GraphedTrainStep:
         else:
             acc, avg_cnt, _ = kd.accuracy_device(self.out["y_s"], self.static["label_s"])
         parts = [self.out["loss_all"].reshape(1), self.out["loss_s"].reshape(1), self.out["loss_c"].reshape(1), avg_cnt.reshape(2), acc.reshape(-1)]
+        if "loss_ent" in self.out:           # (appended: the layout without an entropy criterion is unchanged)
+            parts.append(self.out["loss_ent"].reshape(1))
         self._mk = int(acc.numel())
         self._mvec = torch.cat([p.float() for p in parts])
         self.out["acc_s"], self.out["acc_avg_cnt"] = acc, avg_cnt
@@ -861,7 +876,10 @@ class GraphedTrainStep:
 
     def _metrics_dict(self, v):
         v = v.tolist()
-        return {"loss_all": v[0], "loss_s": v[1], "loss_c": v[2], "acc_s": v[3], "cnt_s": int(v[4]), "acc_per_keypoint": v[5:5 + self._mk]}
+        d = {"loss_all": v[0], "loss_s": v[1], "loss_c": v[2], "acc_s": v[3], "cnt_s": int(v[4]), "acc_per_keypoint": v[5:5 + self._mk]}
+        if len(v) > 5 + self._mk:
+            d["loss_ent"] = v[5 + self._mk]
+        return d
 
     def step_async(self, *args, **kw):
         """step() with the metric read-back DEFERRED by one step: replays this step, queues the copy of its metric vector into a pinned

@@ -1,9 +1,13 @@
-"""Heat-map losses (API mirror of the reference's lib/models/loss.py:11-49,119-132) on MI355X kernels.
+"""Heat-map losses (API mirror of the reference's lib/models/loss.py) on MI355X kernels.
 
-Only the two classes the training scripts instantiate (train_human.py:133-134) exist; the reference's unused
-JointsKLLoss / EntLoss / ConsSoftmaxLoss / ConsKLLoss / CoralLoss are out of scope.
+JointsMSELoss and ConsLoss are what the training scripts instantiate (train_human.py:133-134).  JointsKLLoss, EntLoss,
+ConsSoftmaxLoss and ConsKLLoss (loss.py:52-173) are the soft-max family a user swaps in (csrc/softmax_loss.hip: a row
+soft-max over the H*W pixels of every (b,k) heat-map fused with the loss, its reduction and its backward).  CoralLoss is
+defined and refuses construction: see its docstring.
 Each forward is one sweep over the operands (per-(b,k) row partial + a tiny row reduction), each backward one sweep.
 """
+import warnings
+
 import torch
 import torch.nn as nn
 
@@ -117,3 +121,207 @@ class ConsLoss(nn.Module):
 
     def forward(self, stu_out, tea_out, valid_mask=None, tea_mask=None):
         return _ConsFn.apply(stu_out, tea_out, tea_mask, valid_mask)
+
+
+# ---------------------------------------------------------------------------------------------- the soft-max family
+def _bytes_mask(mask):
+    """(b,k) mask as bytes, _ConsFn's conventions: bool storage is read as it is, anything else is `!= 0`."""
+    if mask is None:
+        return None
+    if mask.dtype == torch.bool and mask.is_contiguous():
+        return mask.detach().view(torch.uint8).reshape(-1)
+    return (mask.detach() != 0).to(torch.uint8).reshape(-1).contiguous()
+
+
+def _gscale(g):
+    return g.detach().float().reshape(1).contiguous()
+
+
+class _JointsKLFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output, target, weight, reduce_mean, eps):
+        _hip.require_cuda(output, target, weight)
+        R, HW = _rows(output)
+        B, K = output.shape[:2]
+        o, t = _f32c(output), _f32c(target)
+        w = None if weight is None else _f32c(weight).reshape(-1)
+        if w is not None and w.numel() != R:
+            raise ValueError("target_weight must have B*K elements")
+        rows = torch.empty(R, dtype=torch.float32, device=o.device)
+        stats = torch.empty(5 * R, dtype=torch.float32, device=o.device)
+        out = torch.empty(() if reduce_mean else (B,), dtype=torch.float32, device=o.device)
+        check(lib().udapose_joints_kl_fwd(_hip.stream(), ptr(o), ptr(t), ptr(w), eps, R, R if reduce_mean else K, HW, ptr(rows), ptr(stats),
+                                          ptr(out)), "joints_kl_fwd")
+        ctx.save_for_backward(o, t, w if w is not None else torch.empty(0, device=o.device), stats)
+        ctx.has_w, ctx.reduce_mean, ctx.eps, ctx.shape, ctx.in_dtype = w is not None, reduce_mean, eps, output.shape, output.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        o, t, w, stats = ctx.saved_tensors
+        if not ctx.reduce_mean:
+            raise NotImplementedError("backward of reduction='none' is not on the hot path")
+        R, HW = _rows(o)
+        d = torch.empty_like(o)
+        gs = _gscale(g)
+        check(lib().udapose_joints_kl_bwd(_hip.stream(), ptr(o), ptr(t), ptr(w) if ctx.has_w else None, ctx.eps, ptr(stats), ptr(gs), R, HW,
+                                          ptr(d)), "joints_kl_bwd")
+        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None, None, None
+
+
+class JointsKLLoss(nn.Module):
+    """KL(q || softmax(pred)) per (b,k) heat-map, q = (gt + epsilon) / sum(gt + epsilon), times target_weight[b,k] (RegDA's supervised
+    loss, loss.py:52-95): the mean over the B*K maps ('mean') or the reference's `loss.mean(dim=-1)`, shape [B] ('none')."""
+
+    def __init__(self, reduction='mean', epsilon=0.):
+        super(JointsKLLoss, self).__init__()
+        self.reduction = reduction
+        self.epsilon = epsilon
+
+    def forward(self, output, target, target_weight=None):
+        if self.reduction == 'mean':
+            return _JointsKLFn.apply(output, target, target_weight, True, float(self.epsilon))
+        elif self.reduction == 'none':
+            return _JointsKLFn.apply(output, target, target_weight, False, float(self.epsilon))
+        # any other string: None, as the reference (loss.py:92-95)
+
+
+class _EntFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, threshold, reduce_mean):
+        _hip.require_cuda(x)
+        R, HW = _rows(x)
+        B, K = x.shape[:2]
+        s = _f32c(x)
+        thr = float(threshold) if threshold > 0 else 0.0
+        scalar = reduce_mean or thr > 0        # (a threshold makes the selection 1-D: its mean(dim=-1) is a scalar too, loss.py:111-117)
+        rows = torch.empty(R, dtype=torch.float32, device=s.device)
+        stats = torch.empty(4 * R, dtype=torch.float32, device=s.device)
+        out = torch.empty(() if scalar else (B,), dtype=torch.float32, device=s.device)
+        cnt = torch.empty((), dtype=torch.float32, device=s.device)
+        check(lib().udapose_entropy_loss_fwd(_hip.stream(), ptr(s), R, R if scalar else K, HW, thr, ptr(rows), ptr(stats), ptr(out), ptr(cnt)),
+              "entropy_loss_fwd")
+        ctx.save_for_backward(s, rows, stats, cnt)
+        ctx.thr, ctx.scalar, ctx.shape, ctx.in_dtype = thr, scalar, x.shape, x.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        s, rows, stats, cnt = ctx.saved_tensors
+        if not ctx.scalar:
+            raise NotImplementedError("backward of reduction='none' is not on the hot path")
+        R, HW = _rows(s)
+        d = torch.empty_like(s)
+        gs = _gscale(g)
+        check(lib().udapose_entropy_loss_bwd(_hip.stream(), ptr(s), ptr(rows), ptr(stats), ptr(cnt), ptr(gs), ctx.thr, R, HW, ptr(d)),
+              "entropy_loss_bwd")
+        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None
+
+
+class EntLoss(nn.Module):
+    """Entropy of softmax(x) over the pixels of every (b,k) map, divided by log(H*W) (loss.py:97-117).  threshold > 0 keeps the maps
+    whose entropy is below it (counted on the device; none kept: NaN, as the mean of an empty tensor)."""
+
+    def __init__(self, reduction='mean'):
+        super(EntLoss, self).__init__()
+        self.reduction = reduction
+
+    def forward(self, x, threshold=-1):
+        if self.reduction == 'mean':
+            return _EntFn.apply(x, threshold, True)
+        elif self.reduction == 'none':
+            return _EntFn.apply(x, threshold, False)
+
+
+class _ConsProbFn(torch.autograd.Function):
+    """mode 0: ConsSoftmaxLoss; 1: ConsKLLoss(log_target=True); 2: ConsKLLoss as the reference evaluates it."""
+
+    @staticmethod
+    def forward(ctx, stu, tea, mask, valid, mode):
+        _hip.require_cuda(stu, tea, mask, valid)
+        R, HW = _rows(stu)
+        K = stu.shape[1]
+        s, t = _f32c(stu), _f32c(tea)
+        m = _bytes_mask(mask)
+        rows = torch.empty(R, dtype=torch.float32, device=s.device)
+        stats = torch.empty(7 * R, dtype=torch.float32, device=s.device)
+        out = torch.empty((), dtype=torch.float32, device=s.device)
+        v = cnt = None
+        if valid is not None:
+            # loss_map[valid_mask].mean() (loss.py:149-150, 170-171): boolean selection over (b, h, w)
+            if tuple(valid.shape) != (stu.shape[0],) + tuple(stu.shape[2:]):
+                raise IndexError(f"valid_mask shape {tuple(valid.shape)} does not index loss_map {(stu.shape[0],) + tuple(stu.shape[2:])}")
+            v = (valid.detach() != 0).to(torch.uint8).reshape(-1).contiguous()
+            cnt = torch.empty((), dtype=torch.float32, device=s.device)
+            check(lib().udapose_mask_count(_hip.stream(), ptr(v), v.numel(), ptr(cnt)), "mask_count")
+        if mode == 0:
+            check(lib().udapose_cons_softmax_fwd(_hip.stream(), ptr(s), ptr(t), ptr(m), ptr(v), ptr(cnt), R, K, HW, ptr(rows), ptr(stats),
+                                                 ptr(out)), "cons_softmax_fwd")
+        else:
+            check(lib().udapose_cons_kl_fwd(_hip.stream(), ptr(s), ptr(t), ptr(m), ptr(v), ptr(cnt), int(mode == 1), R, K, HW, ptr(rows),
+                                            ptr(stats), ptr(out)), "cons_kl_fwd")
+        empty = torch.empty(0, dtype=torch.uint8, device=s.device)
+        ctx.save_for_backward(s, t, m if m is not None else empty, v if v is not None else empty,
+                              cnt if cnt is not None else torch.empty(0, device=s.device), stats)
+        ctx.has_m, ctx.has_v, ctx.mode, ctx.shape, ctx.in_dtype = m is not None, v is not None, mode, stu.shape, stu.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        s, t, m, v, cnt, stats = ctx.saved_tensors
+        R, HW = _rows(s)
+        K = ctx.shape[1]
+        d = torch.empty_like(s)
+        gs = _gscale(g)
+        pm, pv, pc = (ptr(m) if ctx.has_m else None), (ptr(v) if ctx.has_v else None), (ptr(cnt) if ctx.has_v else None)
+        if ctx.mode == 0:
+            check(lib().udapose_cons_softmax_bwd(_hip.stream(), ptr(s), ptr(t), pm, pv, pc, ptr(stats), ptr(gs), R, K, HW, ptr(d)),
+                  "cons_softmax_bwd")
+        else:
+            check(lib().udapose_cons_kl_bwd(_hip.stream(), ptr(s), ptr(t), pm, pv, pc, int(ctx.mode == 1), ptr(stats), ptr(gs), R, K, HW,
+                                            ptr(d)), "cons_kl_bwd")
+        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None, None, None
+
+
+class ConsSoftmaxLoss(nn.Module):
+    """ConsLoss on probabilities: both heat-maps go through a soft-max over their pixels first (loss.py:134-152)."""
+
+    def __init__(self):
+        super(ConsSoftmaxLoss, self).__init__()
+
+    def forward(self, stu_out, tea_out, valid_mask=None, tea_mask=None):
+        return _ConsProbFn.apply(stu_out, tea_out, tea_mask, valid_mask, 0)
+
+
+class ConsKLLoss(nn.Module):
+    """The reference's ConsKLLoss (loss.py:154-173) hands nn.KLDivLoss (log_target=False) the teacher's LOG-probabilities as its target:
+    it evaluates xlogy(t, t) - t * log p with t = log pt < 0, and the logarithm of a negative number is NaN.  Run on the CPU, the
+    reference returns NaN for every input of more than one pixel (tests/golden/softmax_losses.npz records it).  ConsKLLoss() reproduces
+    that arithmetic literally, as this package does with the reference's other quirks, and warns once.
+    ConsKLLoss(log_target=True) is an EXTENSION (the reference's constructor takes no argument): the divergence the code evidently
+    intends, mean over (b,h,w) of mean_k tea_mask[b,k] * pt * (log pt - log p), with the same valid_mask selection."""
+    _warned = False
+
+    def __init__(self, log_target=False):
+        super(ConsKLLoss, self).__init__()
+        self.log_target = bool(log_target)
+
+    def forward(self, stu_out, tea_out, valid_mask=None, tea_mask=None):
+        if not self.log_target and not ConsKLLoss._warned:
+            ConsKLLoss._warned = True
+            warnings.warn("ConsKLLoss() mirrors the reference, whose KLDivLoss takes the teacher's log-probabilities as probabilities: the loss "
+                          "is NaN for every heat-map of more than one pixel.  ConsKLLoss(log_target=True) computes the KL divergence.",
+                          RuntimeWarning, stacklevel=2)
+        return _ConsProbFn.apply(stu_out, tea_out, tea_mask, valid_mask, 1 if self.log_target else 2)
+
+
+class CoralLoss(nn.Module):
+    """Not available.  The reference's CoralLoss (loss.py:176-208) forms the covariance of the flattened heat-maps, a
+    (K*H*W) x (K*H*W) matrix - 65 536 squared, 17 GB in fp32, at K = 16 and 64x64 maps: a dense GEMM workload unrelated to the row
+    kernels of this module, and no script of the reference reaches it.  There is no eager fallback, so the constructor refuses."""
+
+    def __init__(self, coral_downsample, prior=None):
+        super(CoralLoss, self).__init__()
+        raise NotImplementedError("CoralLoss is not implemented on the device: it needs the (K*H*W) x (K*H*W) covariance of the flattened "
+                                  "heat-maps (17 GB in fp32 at K = 16, 64x64), a dense GEMM workload that no training script reaches; "
+                                  "this package has no eager fallback")
