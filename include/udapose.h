@@ -83,7 +83,12 @@ typedef struct {
                            * train_human.py:436 run twice gives the same bits); 0: fp32 atomics into cleared tensors, arrival order */
     int igemm_ns3_k;      /* 64x64 implicit-GEMM tiles take the 3-stage LDS ring from this reduction length on (K = taps x Ci), the 2-stage ring
                            * below it; 0 = the default, 2048 */
-    void* timeline;
+    void* timeline;       /* NULL, or a device buffer of uint64 [work-groups][8] for timeline stamps (tuning).  The grouped weight-gradient launches
+                           * of a plan stamp {start, end (100 MHz), XCD, table slot, problem, stages | form bits, pass, tile rows} per work-group, the 128x128
+                           * class first, the 64x64 class behind it: the buffer must hold 1 << 17 work-groups (8 MiB); a plan with more refuses */
+    int wgrad_order;      /* grouped weight gradients, the deal of work-groups to the XCDs' lists: 1 (default) = layers cut into runs of 32 work-groups, the runs
+                           * with the most stages per work-group first, so every list ends with its share of the short work-groups; 0 = whole
+                           * (layer, split) units in deal order by unit load.  Same work into the same places either way: bit-identical gradients */
 } udapose_policy;
 void udapose_policy_default(udapose_policy* p);
 
@@ -265,6 +270,23 @@ int udapose_net_backward_phase(udapose_net_t net, void* stream, const float* dou
  * atomics in arrival order).  `ws` must have the size udapose_net_ws_bytes returns AFTER udapose_net_set_policy. */
 int udapose_net_wgrad_pair(udapose_net_t net, void* stream, const void* act_a, void* ws_a, void* const* h_grads_a, float beta_a,
                            const void* act_b, void* ws_b, void* const* h_grads_b, float beta_b, int part);
+/* udapose_net_wgrad_pair that MAY leave the split sums of the gradient tensors to the optimizer sweep: when both passes overwrite (beta 0),
+ * share one table, cover the whole backward (part 0) and udapose_net_bind_update has bound an update table for h_grads_a's tensors after
+ * udapose_net_bind_grads, the launch that adds the partial tiles is left out, *deferred = 1, and the NEXT udapose_net_fused_update - which must
+ * be given h_grads_a and grad2_delta_bytes = the distance to h_grads_b's buffer - adds the partial tiles inside its sweep, in the same order, to
+ * the same bits (one launch and the write + re-read of the split layers' sums less).  Until then the split layers' gradient TENSORS hold stale
+ * values: a caller that wants them, or whose update does not run, calls udapose_net_split_sum_flush (the sums as their own launch; no-op
+ * without a pending sum).  Any other weight-gradient call on the plan while a sum is pending fails with UDAPOSE_ERR_NOT_PREPARED.
+ * Otherwise (*deferred = 0) it is udapose_net_wgrad_pair. */
+int udapose_net_wgrad_pair_defer(udapose_net_t net, void* stream, const void* act_a, void* ws_a, void* const* h_grads_a, float beta_a,
+                                 const void* act_b, void* ws_b, void* const* h_grads_b, float beta_b, int part, int* deferred);
+int udapose_net_split_sum_flush(udapose_net_t net, void* stream);
+/* The deal of a grouped weight-gradient launch, as a pure host function (no device): unit i = nblk[i] work-groups of stages[i] 64-pixel stages.
+ * Writes the runs of the eight XCD lists, XCD by XCD in list order, as entries (ent_xcd, ent_unit, ent_first = first work-group of the unit,
+ * ent_count), at most `cap` of them, and returns how many entries there are (< 0: an error code); finish_out[8]: modelled finish time of each
+ * list (128 resident work-groups per XCD, a work-group takes stages + 4).  order: udapose_policy.wgrad_order.  Outputs may be NULL. */
+int udapose_wgrad_deal(const int* nblk, const int* stages, int n_units, int order, int* ent_xcd, int* ent_unit, int* ent_first, int* ent_count, int cap,
+                       double* finish_out);
 long long udapose_net_grad_split_param(udapose_net_t net);
 
 /* ---------------------------------------------------------------- heat-map losses and decode (fp32 NCHW rows [R=B*K][HW]) */

@@ -22,7 +22,7 @@ class Policy(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("igemm_tile", "igemm_h3", "igemm_lean", "igemm_short_lds", "igemm_tap0", "wgrad_tile", "wgrad_ksplit",
                                        "wgrad_fastgeo", "wgrad_group", "wgrad_stages", "wgrad_group_stem", "bn_bwd_fused", "bn_fwd_chunked",
                                        "bn_bwd_chunked", "bn_bwd_pre_legacy", "igemm_wg_min", "wgrad_row3", "bn3_mask", "stem_fused", "debug_sync", "igemm_big_min", "patch_conv",
-                                       "eval_fold", "bn_xcd_rows", "wgrad_det", "igemm_ns3_k")] + [("timeline", C.c_void_p)]
+                                       "eval_fold", "bn_xcd_rows", "wgrad_det", "igemm_ns3_k")] + [("timeline", C.c_void_p), ("wgrad_order", C.c_int)]
 
 
 def policy(**overrides):
@@ -97,6 +97,9 @@ _SIGS = {
     "udapose_net_backward_part": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, cf, ci]),
     "udapose_net_backward_phase": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, cf, ci, ci]),
     "udapose_net_wgrad_pair": (ci, [vp, vp, vp, vp, vp, cf, vp, vp, vp, cf, ci]),
+    "udapose_net_wgrad_pair_defer": (ci, [vp, vp, vp, vp, vp, cf, vp, vp, vp, cf, ci, vp]),
+    "udapose_net_split_sum_flush": (ci, [vp, vp]),
+    "udapose_wgrad_deal": (ci, [vp, vp, ci, ci, vp, vp, vp, vp, ci, vp]),
     "udapose_net_grad_split_param": (ll, [vp]),
     "udapose_net_bind_update": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "udapose_net_fused_update": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, cf, cf, ci, ll]),

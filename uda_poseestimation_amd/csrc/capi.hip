@@ -113,6 +113,9 @@ int net_pack_weights(void*, hipStream_t, const void* const*, void*, int);
 int net_forward(void*, hipStream_t, const float*, const void* const*, void* const*, const void*, void*, void*, float*, int, float);
 int net_backward(void*, hipStream_t, const float*, const void* const*, const void*, void*, void*, void* const*, float, int, int);
 int net_wgrad_pair(void*, hipStream_t, const void*, void*, void* const*, float, const void*, void*, void* const*, float, int);
+int net_wgrad_pair_defer(void*, hipStream_t, const void*, void*, void* const*, float, const void*, void*, void* const*, float, int, int*);
+int net_split_sum_flush(void*, hipStream_t);
+int net_wgrad_deal(const int*, const int*, int, int, int*, int*, int*, int*, int, double*);
 
 static Policy from_c(const udapose_policy& c) {
     Policy p;
@@ -120,7 +123,7 @@ static Policy from_c(const udapose_policy& c) {
     p.igemm_tap0 = c.igemm_tap0; p.wgrad_tile = c.wgrad_tile; p.wgrad_ksplit = c.wgrad_ksplit; p.wgrad_fastgeo = c.wgrad_fastgeo;
     p.wgrad_group = c.wgrad_group; p.wgrad_stages = c.wgrad_stages > 0 ? c.wgrad_stages : 128; p.wgrad_group_stem = c.wgrad_group_stem;
     p.bn_bwd_fused = c.bn_bwd_fused; p.bn_fwd_chunked = c.bn_fwd_chunked; p.bn_bwd_chunked = c.bn_bwd_chunked;
-    p.bn_bwd_pre_legacy = c.bn_bwd_pre_legacy; p.igemm_wg_min = c.igemm_wg_min; p.wgrad_row3 = c.wgrad_row3; p.bn3_mask = c.bn3_mask; p.stem_fused = c.stem_fused; p.debug_sync = c.debug_sync; p.igemm_big_min = c.igemm_big_min; p.patch_conv = c.patch_conv; p.eval_fold = c.eval_fold; p.bn_xcd_rows = c.bn_xcd_rows; p.igemm_ns3_k = c.igemm_ns3_k; p.wgrad_det = c.wgrad_det; p.timeline = (unsigned long long*)c.timeline;
+    p.bn_bwd_pre_legacy = c.bn_bwd_pre_legacy; p.igemm_wg_min = c.igemm_wg_min; p.wgrad_row3 = c.wgrad_row3; p.bn3_mask = c.bn3_mask; p.stem_fused = c.stem_fused; p.debug_sync = c.debug_sync; p.igemm_big_min = c.igemm_big_min; p.patch_conv = c.patch_conv; p.eval_fold = c.eval_fold; p.bn_xcd_rows = c.bn_xcd_rows; p.igemm_ns3_k = c.igemm_ns3_k; p.wgrad_det = c.wgrad_det; p.wgrad_order = c.wgrad_order; p.timeline = (unsigned long long*)c.timeline;
     return p;
 }
 static void to_c(const Policy& p, udapose_policy* c) {
@@ -128,7 +131,7 @@ static void to_c(const Policy& p, udapose_policy* c) {
     c->igemm_tap0 = p.igemm_tap0; c->wgrad_tile = p.wgrad_tile; c->wgrad_ksplit = p.wgrad_ksplit; c->wgrad_fastgeo = p.wgrad_fastgeo;
     c->wgrad_group = p.wgrad_group; c->wgrad_stages = p.wgrad_stages; c->wgrad_group_stem = p.wgrad_group_stem;
     c->bn_bwd_fused = p.bn_bwd_fused; c->bn_fwd_chunked = p.bn_fwd_chunked; c->bn_bwd_chunked = p.bn_bwd_chunked;
-    c->bn_bwd_pre_legacy = p.bn_bwd_pre_legacy; c->igemm_wg_min = p.igemm_wg_min; c->wgrad_row3 = p.wgrad_row3; c->bn3_mask = p.bn3_mask; c->stem_fused = p.stem_fused; c->debug_sync = p.debug_sync; c->igemm_big_min = p.igemm_big_min; c->patch_conv = p.patch_conv; c->eval_fold = p.eval_fold; c->bn_xcd_rows = p.bn_xcd_rows; c->igemm_ns3_k = p.igemm_ns3_k; c->wgrad_det = p.wgrad_det; c->timeline = p.timeline;
+    c->bn_bwd_pre_legacy = p.bn_bwd_pre_legacy; c->igemm_wg_min = p.igemm_wg_min; c->wgrad_row3 = p.wgrad_row3; c->bn3_mask = p.bn3_mask; c->stem_fused = p.stem_fused; c->debug_sync = p.debug_sync; c->igemm_big_min = p.igemm_big_min; c->patch_conv = p.patch_conv; c->eval_fold = p.eval_fold; c->bn_xcd_rows = p.bn_xcd_rows; c->igemm_ns3_k = p.igemm_ns3_k; c->wgrad_det = p.wgrad_det; c->wgrad_order = p.wgrad_order; c->timeline = p.timeline;
 }
 // a convolution descriptor and the policy it names, as the host-side geometry (the policy lives as long as this object)
 struct Geom {
@@ -304,6 +307,16 @@ int udapose_net_wgrad_pair(udapose_net_t n, void* stream, const void* act_a, voi
                            void* ws_b, void* const* grads_b, float beta_b, int part) {
     if (!n || !act_a || !ws_a || !grads_a || !act_b || !ws_b || !grads_b) return UDAPOSE_ERR_ARG;
     return net_wgrad_pair(n, S(stream), act_a, ws_a, grads_a, beta_a, act_b, ws_b, grads_b, beta_b, part);
+}
+int udapose_net_wgrad_pair_defer(udapose_net_t n, void* stream, const void* act_a, void* ws_a, void* const* grads_a, float beta_a, const void* act_b,
+                                 void* ws_b, void* const* grads_b, float beta_b, int part, int* deferred) {
+    if (!n || !act_a || !ws_a || !grads_a || !act_b || !ws_b || !grads_b) return UDAPOSE_ERR_ARG;
+    return net_wgrad_pair_defer(n, S(stream), act_a, ws_a, grads_a, beta_a, act_b, ws_b, grads_b, beta_b, part, deferred);
+}
+int udapose_net_split_sum_flush(udapose_net_t n, void* stream) { return n ? net_split_sum_flush(n, S(stream)) : UDAPOSE_ERR_ARG; }
+int udapose_wgrad_deal(const int* nblk, const int* stages, int n_units, int order, int* ent_xcd, int* ent_unit, int* ent_first, int* ent_count, int cap,
+                       double* finish_out) {
+    return net_wgrad_deal(nblk, stages, n_units, order, ent_xcd, ent_unit, ent_first, ent_count, cap, finish_out);
 }
 int udapose_net_backward_phase(udapose_net_t n, void* stream, const float* dout, const void* const* params, const void* wpack, void* act,
                                void* ws, void* const* grads, float beta, int part, int phase) {

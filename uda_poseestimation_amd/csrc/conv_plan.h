@@ -47,6 +47,8 @@ struct Policy {
     int wgrad_det = 1;          // grouped weight gradients: split pixel reductions store per-split partial tiles that ONE launch adds in split order
                                 // (bit-reproducible gradients; 0: fp32 atomics into cleared tensors, arrival order - rounds 1-5)
     int igemm_ns3_k = 0;        // 64x64 igemm tiles: 3-stage ring from this K on, 2-stage below (0 = 2048)
+    int wgrad_order = 1;        // grouped weight gradients, the deal to the XCDs' lists (net.hip wg_deal): 1 = runs of 32 work-groups, most stages first;
+                                // 0 = whole units in deal order by unit load (rounds 1-6).  The gradients do not depend on it.
     int debug_sync = 0;         // net calls: synchronise after every stage and report the first failing source line
     unsigned long long* timeline = nullptr;   // device buffer for per-work-group timeline stamps (tuning), normally null
 };
@@ -107,12 +109,14 @@ int wgrad_launch_parts(WgParams& p, float* parts, hipStream_t stream);
 // Grouped wgrad (many layers, one launch per tile class).  wgrad_group_plan completes p for the group kernels and returns
 // the tile class (0 = 128x128, 1 = 64x64) or < 0 when the layer needs its own launch; stages_per_block bounds a work-group's
 // pixel range (longer reductions are split and accumulated with fp32 atomics into a zeroed dW).
+#define WG_STAMP_BLOCKS (1 << 17)   // work-groups of one plan's grouped launches (both classes, both passes) a Policy::timeline buffer must hold
 #define WG_CLASSES 2      // tile classes of a grouped launch: 0 = 128x128, 1 = 64x64 (+ filter-row form)
 int wgrad_group_plan(WgParams& p, int accumulate, int stages_per_block, const Policy& pol);
 // the x / dy / dw fields of the table entries are byte offsets from the three bases
 int wgrad_group_launch(hipStream_t stream, int tile, const WgParams* d_tab, const WgGroupBlk* d_blk, int per_xcd, const void* x_base,
                        const void* dy_base, void* dw_base, const WgParams* d_tab2 = nullptr, const WgGroupBlk* d_blk2 = nullptr,
-                       const void* x_base2 = nullptr, const void* dy_base2 = nullptr, void* dw_base2 = nullptr);
+                       const void* x_base2 = nullptr, const void* dy_base2 = nullptr, void* dw_base2 = nullptr,
+                       unsigned long long* stamps = nullptr);     // stamps: [work-groups][8] timeline stamps (tuning), normally null
 
 struct ConvEpilogue {
     const elem_t* res = nullptr;

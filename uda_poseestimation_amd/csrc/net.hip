@@ -11,6 +11,8 @@
 // apply / pool / conversion launches next to the fp32-grade tensor; the fp32-grade tensors (the f* offsets) live only in the forward.
 #include <algorithm>
 #include <deque>
+#include <functional>
+#include <queue>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -48,7 +50,9 @@ int pw_nchw_f32_to_nhwc_f32(hipStream_t, const float*, float*, int, int, int, in
 size_t opt_tail_job_bytes();
 int opt_chunk();
 void opt_tail_job_fill(void*, float*, const float*, float*, float*, float*, void*, void*, void*, void*, int, int, int, int, long long);
-int opt_tail(hipStream_t, const void*, const int*, const int*, int, float, float, float, float, float, int, float, float*, float, float, int, long long, int);
+void opt_tail_job_split(void*, long long, unsigned, int);
+int opt_tail(hipStream_t, const void*, const int*, const int*, int, float, float, float, float, float, int, float, float*, float, float, int, long long, int,
+             const void*, const void*);
 int pw_transpose_f32(hipStream_t, const float*, float*, int, int, int);
 int pw_pack_strided_f32(hipStream_t, const float*, float*, int, int, int, int, int, int, long, long, long, long);
 int pw_bn_apply_f32(hipStream_t, const float*, const float*, float*, size_t, int, const float*, const float*, int);
@@ -148,7 +152,7 @@ struct Net {
         // the policy the tables were built under: the form of the split reductions (1: partial tiles + split sums, 0: atomics into cleared
         // tensors) and whether they hold the stem.  A later udapose_net_set_policy does not change what a bound table does: find_wg_group
         // no longer finds it, and the backward returns UDAPOSE_ERR_NOT_PREPARED until udapose_net_bind_grads builds tables for the new policy.
-        bool k_det = false, k_stem = false;
+        bool k_det = false, k_stem = false; int k_order = 0;      // (k_order: the work order of the lists, policy wgrad_order)
         size_t part_bytes = 0;                           // workspace bytes of partial tiles the split sums read (k_det)
         std::vector<std::pair<int, ptrdiff_t>> rel;      // (parameter index, byte offset of its gradient from grads[0]) the table assumes
         std::vector<size_t> rel_bytes;                   // bytes of rel[i]'s gradient tensor (what the launch writes there)
@@ -162,6 +166,10 @@ struct Net {
         // deconvolution, head, stem) has every split store its PARTIAL tile into the pass's workspace (ws_wgpart); one launch then adds the
         // splits of all such layers in split order into the gradient tensors (pw_split_sum): no atomics, no clears, bit-reproducible
         SumJob* d_sum = nullptr; int* d_sum_blk = nullptr; int n_sum_blk = 0;
+        // (the blocks of the jobs that sum into the workspace - the stem's row-tap scratch - are the LAST n_sum_ws_blk of d_sum_blk: a pair call that
+        // leaves the sums of the gradient TENSORS to the optimizer sweep still runs those; h_sum: the jobs, for net_bind_update)
+        int n_sum_ws_blk = 0;
+        std::vector<SumJob> h_sum;
         unsigned long long last_use = 0;
     };
     std::deque<WgGroup> wg_groups;       // (stable addresses, never evicted: a captured hipGraph may reference any table built so far)
@@ -170,6 +178,11 @@ struct Net {
                     const void* k_ps = nullptr; const void* k_pt = nullptr; const void* k_g = nullptr; const void* k_m = nullptr;
                     const void* k_ws = nullptr; const void* k_wt = nullptr; };
     UpdTab upd;
+    // Split sums left to the optimizer sweep (udapose_net_wgrad_pair_defer): the pair call records the two passes' workspaces and gradient bases
+    // here, the next udapose_net_fused_update consumes and clears the mark (its sweep adds the partial tiles itself), udapose_net_split_sum_flush
+    // runs the sums as their own launch instead.  Any other weight-gradient call while the mark stands is refused.
+    struct Deferred { const WgGroup* G = nullptr; char* wsA = nullptr; char* wsB = nullptr; char* gA = nullptr; char* gB = nullptr; } deferred;
+    const WgGroup* upd_sum_group = nullptr;     // the table whose split jobs the bound update's job table carries (null: none)
     // batched deferred running-statistics update: device job table, rebuilt when the buffer pointers change
     BnRunJob* d_runjobs = nullptr; int n_runjobs = 0; const void* runjobs_key = nullptr;
     unsigned long long wg_tick = 0;
@@ -741,13 +754,65 @@ PartSel part_sel(const Net& n, int part) {
     return PartSel{true, nb - 1, 0, true};
 }
 
+// ---- the deal of a grouped launch: which XCD runs which work-groups, and in which order ----------------------------------------
+// A unit is one (layer, split): `nblk` work-groups (local indices base .. base + nblk - 1) of `st` 64-pixel stages each (+ 4: prologue,
+// epilogue and stores, in stage units).  The hardware starts an XCD's list in list order on its 128 resident slots (32 CUs x 4).
+// order 0 (rounds 1-6): whole units sorted by unit load nblk * (st + 4), each dealt to the least loaded XCD, lists kept in deal order.
+//   Measured on the benched plan (profiles/tail_timeline.txt): nearly every work-group of both classes has 128 stages (~300 / ~170 us of
+//   lifetime), the few 32-stage layers (layer4) sit on ONE XCD each in the middle of its list, every list ends with 128-stage work-groups
+//   and the launches drain for 260 / 160 us; what a stage costs depends on what else is resident on the XCD (1.7 - 3.1 us for the same
+//   tile), so lists levelled by st + 4 still finish up to 200 us apart.
+// order 1: units are cut into runs of at most WG_DEAL_RUN consecutive work-groups (neighbouring tiles of one tap: they still share their
+//   operands in that XCD's L2; a layer that is cut re-reads its dy / x once per XCD it lands on - the short layers this matters for hold
+//   2048 pixels), the runs are sorted by stages per work-group, longest first (ties: larger run first), and dealt in that order to the
+//   least loaded XCD.  Every list is then longest-first by construction and ends with its share of the SHORT work-groups, which level
+//   the lists; and because every XCD gets the same mix of layers, a stage's true cost need not be known for the lists to finish together.
+// The model (wg_model_finish): work-groups start in list order, each on the slot that frees first, and run st + 4 time units.
+#define WG_DEAL_RUN 32
+struct WgUnit { int prob, base, nblk, st; long load; };
+double wg_model_finish(const std::vector<WgUnit>& runs, const std::vector<int>& lst, int slots = 128) {
+    std::priority_queue<double, std::vector<double>, std::greater<double>> free_at;
+    for (int i = 0; i < slots; ++i) free_at.push(0.0);
+    double end = 0.0;
+    for (int ui : lst)
+        for (int l = 0; l < runs[ui].nblk; ++l) {
+            const double t = free_at.top() + runs[ui].st + 4;
+            free_at.pop();
+            free_at.push(t);
+            end = std::max(end, t);
+        }
+    return end;
+}
+// units -> runs (order 0: the units themselves) and the list of run indices of each XCD
+void wg_deal(const std::vector<WgUnit>& units, int order, std::vector<WgUnit>& runs, std::vector<int> lst[8]) {
+    runs.clear();
+    for (const WgUnit& u : units) {
+        const int step = order == 0 ? u.nblk : WG_DEAL_RUN;
+        for (int l0 = 0; l0 < u.nblk; l0 += step) {
+            const int cnt = std::min(step, u.nblk - l0);
+            runs.push_back(WgUnit{u.prob, u.base + l0, cnt, u.st, (long)cnt * (u.st + 4)});
+        }
+    }
+    std::vector<int> idx(runs.size());
+    for (size_t i = 0; i < idx.size(); ++i) idx[i] = (int)i;
+    if (order == 0) std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return runs[a].load > runs[b].load; });
+    else std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return runs[a].st != runs[b].st ? runs[a].st > runs[b].st : runs[a].load > runs[b].load; });
+    long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < 8; ++k) lst[k].clear();
+    for (int ui : idx) {
+        int x = 0;
+        for (int k = 1; k < 8; ++k) if (load[k] < load[x]) x = k;
+        load[x] += runs[ui].load;
+        lst[x].push_back(ui);
+    }
+}
+
 // (sizing = true: a dry walk that only adds up the bytes of partial tiles the part's split reductions need, into *need)
 int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int part, bool sizing = false, size_t* need = nullptr) {
     const PartSel sel = part_sel(n, part);
     const bool upper = sel.head_up, lower = sel.stem;
     std::vector<WgParams> tab[WG_CLASSES];
-    struct Unit { int prob, z, nblk; long load; };
-    std::vector<Unit> units[WG_CLASSES];
+    std::vector<WgUnit> units[WG_CLASSES];
     G.zero.clear();
     G.rel.clear();
     G.rel_bytes.clear();
@@ -795,7 +860,7 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
         const int ms_total = (p.M + 63) / 64, per = (ms_total + p.ksplit - 1) / p.ksplit;
         for (int z = 0; z < p.ksplit; ++z) {
             const int st = std::min(per, ms_total - z * per);
-            if (st > 0) units[t].push_back(Unit{prob, z, nblk, (long)nblk * (st + 4)});
+            if (st > 0) units[t].push_back(WgUnit{prob, z * nblk, nblk, st, (long)nblk * (st + 4)});
         }
         return UDAPOSE_OK;
     };
@@ -823,7 +888,7 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
         const int ms_total = (p.M + 63) / 64, per = (ms_total + p.ksplit - 1) / p.ksplit;
         for (int z = 0; z < p.ksplit; ++z) {
             const int st = std::min(per, ms_total - z * per);
-            if (st > 0) units[t].push_back(Unit{prob, z, nblk, (long)nblk * (st + 4)});
+            if (st > 0) units[t].push_back(WgUnit{prob, z * nblk, nblk, st, (long)nblk * (st + 4)});
         }
     }
     if (upper) for (int i = 2; i >= 0; --i) CK(add(n.up[i]));
@@ -840,16 +905,16 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
         if (G.d_blk[t]) { (void)hipFree(G.d_blk[t]); G.d_blk[t] = nullptr; }
         G.per_xcd[t] = 0;
         if (tab[t].empty()) continue;
-        // deal whole (layer, split) units to the 8 XCDs, largest first, each to the least loaded XCD
-        std::stable_sort(units[t].begin(), units[t].end(), [](const Unit& a, const Unit& b) { return a.load > b.load; });
+        // deal the units' work-groups to the 8 XCDs' lists (wg_deal above)
+        std::vector<int> deal[8];
+        std::vector<WgUnit> runs;
+        wg_deal(units[t], n.policy.wgrad_order, runs, deal);
         std::vector<WgGroupBlk> lst[8];
-        long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (const Unit& u : units[t]) {
-            int x = 0;
-            for (int k = 1; k < 8; ++k) if (load[k] < load[x]) x = k;
-            load[x] += u.load;
-            for (int l = 0; l < u.nblk; ++l) lst[x].push_back(WgGroupBlk{u.prob, u.z * u.nblk + l});
-        }
+        for (int x = 0; x < 8; ++x)
+            for (int ui : deal[x]) {
+                const WgUnit& u = runs[ui];
+                for (int l = 0; l < u.nblk; ++l) lst[x].push_back(WgGroupBlk{u.prob, u.base + l});
+            }
         size_t per = 0;
         for (int k = 0; k < 8; ++k) per = std::max(per, lst[k].size());
         std::vector<WgGroupBlk> flat(8 * per, WgGroupBlk{-1, 0});
@@ -874,19 +939,26 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
     // the split-sum launch's tables: jobs, and one block per UDAPOSE_SPLIT_SUM_CHUNK elements of a job
     if (G.d_sum) { (void)hipFree(G.d_sum); G.d_sum = nullptr; }
     if (G.d_sum_blk) { (void)hipFree(G.d_sum_blk); G.d_sum_blk = nullptr; }
-    G.n_sum_blk = 0;
+    G.n_sum_blk = 0; G.n_sum_ws_blk = 0;
     if (!sums.empty()) {
         std::vector<int> blk;
-        for (size_t j = 0; j < sums.size(); ++j)
-            for (unsigned c = 0; c < (sums[j].n + UDAPOSE_SPLIT_SUM_CHUNK - 1u) / UDAPOSE_SPLIT_SUM_CHUNK; ++c) { blk.push_back((int)j); blk.push_back((int)c); }
+        for (const int ws_jobs : {0, 1})
+            for (size_t j = 0; j < sums.size(); ++j) {
+                if ((sums[j].dst_ws != 0) != (ws_jobs != 0)) continue;
+                for (unsigned c = 0; c < (sums[j].n + UDAPOSE_SPLIT_SUM_CHUNK - 1u) / UDAPOSE_SPLIT_SUM_CHUNK; ++c) {
+                    blk.push_back((int)j); blk.push_back((int)c);
+                    G.n_sum_ws_blk += ws_jobs;
+                }
+            }
         if (hipMalloc((void**)&G.d_sum, sums.size() * sizeof(SumJob)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
         if (hipMalloc((void**)&G.d_sum_blk, blk.size() * sizeof(int)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
         if (hipMemcpy(G.d_sum, sums.data(), sums.size() * sizeof(SumJob), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
         if (hipMemcpy(G.d_sum_blk, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
         G.n_sum_blk = (int)(blk.size() / 2);
     }
+    G.h_sum = sums;
     G.k_beta = beta; G.k_stages = n.policy.wgrad_stages; G.k_part = part;
-    G.k_det = det; G.k_stem = n.policy.wgrad_group_stem != 0; G.part_bytes = part_cur;
+    G.k_det = det; G.k_stem = n.policy.wgrad_group_stem != 0; G.part_bytes = part_cur; G.k_order = n.policy.wgrad_order;
     return UDAPOSE_OK;
 }
 
@@ -905,7 +977,8 @@ size_t wg_partial_bytes(Net& n) {
 Net::WgGroup* find_wg_group(Net& n, void* const* grads, float beta, int part) {
     const bool det = n.policy.wgrad_det && n.policy.wgrad_group, stem = n.policy.wgrad_group_stem != 0;
     for (auto& g : n.wg_groups) {
-        if (g.k_beta != beta || g.k_stages != n.policy.wgrad_stages || g.k_part != part || g.k_det != det || g.k_stem != stem) continue;
+        if (g.k_beta != beta || g.k_stages != n.policy.wgrad_stages || g.k_part != part || g.k_det != det || g.k_stem != stem ||
+            g.k_order != n.policy.wgrad_order) continue;
         if (g.k_det && g.part_bytes > n.ws_wgpart_bytes) continue;
         bool same = true;
         for (auto& r : g.rel)
@@ -971,14 +1044,22 @@ bool wg_overlap(const Net& n, const Net::WgGroup* GA, void* const* gradsA, const
     return la < hb && lb < ha;
 }
 int run_wg_group(hipStream_t s, Net& n, const char* act, char* ws, void* const* grads, float beta, int part) {
+    if (n.deferred.G) return UDAPOSE_ERR_NOT_PREPARED;      // (split sums of an earlier pair call are still waiting for their update or flush)
     Net::WgGroup* G = find_wg_group(n, grads, beta, part);
     if (!G) return UDAPOSE_ERR_NOT_PREPARED;
     const bool with_stem = part_sel(n, part).stem && G->k_stem;
     CK(wg_before(s, n, G, ws, grads, with_stem));
+    size_t stamped = 0;     // (work-groups of the classes before this one: each launch stamps behind the last, policy.timeline)
     for (int t = 0; t < WG_CLASSES; ++t) {
         if (!G->per_xcd[t]) continue;
+        unsigned long long* stamps = nullptr;
+        if (n.policy.timeline) {
+            if (stamped + 8 * (size_t)G->per_xcd[t] > WG_STAMP_BLOCKS) return UDAPOSE_ERR_ARG;
+            stamps = n.policy.timeline + stamped * 8;
+            stamped += 8 * (size_t)G->per_xcd[t];
+        }
         const int tok = conv_prof_before(s, 2, G->flops[t]);
-        const int rc = wgrad_group_launch(s, t, G->d_tab[t], G->d_blk[t], G->per_xcd[t], act, ws, grads[0]);
+        const int rc = wgrad_group_launch(s, t, G->d_tab[t], G->d_blk[t], G->per_xcd[t], act, ws, grads[0], nullptr, nullptr, nullptr, nullptr, nullptr, stamps);
         conv_prof_after(s, tok);
         CK(rc);
     }
@@ -987,11 +1068,18 @@ int run_wg_group(hipStream_t s, Net& n, const char* act, char* ws, void* const* 
 // The grouped weight gradients of TWO passes of this plan (each with its own arenas, gradient tensors and accumulate mode) as ONE
 // launch per tile class: the step's two student passes end at about the same time and their weight-gradient launches are fully
 // exposed there; one grid of twice the size has half the tail (measured on the launches alone: 2498 us for 64 images against 2 x 1353).
+// defer (udapose_net_wgrad_pair_defer): leave the split sums of the gradient tensors to the optimizer sweep of the next udapose_net_fused_update,
+// which reads the partial tiles itself - one launch and 2 x (read + write) of the split layers' gradients less on the step's serial tail.  Taken
+// only where the sweep can stand in for the sums exactly: one table for both passes, overwriting passes (beta 0: a pass that accumulates needs
+// its tensor updated for the NEXT accumulation), whole backward, and an update table bound for these gradient tensors that knows the split jobs.
+// *deferred tells the caller whether it was taken.  The stem's sum goes into the workspace and feeds its unpack launch: it still runs here.
 int run_wg_pair(hipStream_t s, Net& n, const char* actA, char* wsA, void* const* gradsA, float betaA, const char* actB, char* wsB,
-                void* const* gradsB, float betaB, int part) {
+                void* const* gradsB, float betaB, int part, bool defer = false, int* deferred = nullptr) {
+    if (deferred) *deferred = 0;
     Net::WgGroup* GA = find_wg_group(n, gradsA, betaA, part);
     Net::WgGroup* GB = find_wg_group(n, gradsB, betaB, part);
     if (!GA || !GB) return UDAPOSE_ERR_NOT_PREPARED;
+    if (n.deferred.G) return UDAPOSE_ERR_NOT_PREPARED;
     bool same = true;
     for (int t = 0; t < WG_CLASSES; ++t) same = same && GA->per_xcd[t] == GB->per_xcd[t];
     const bool with_stem = part_sel(n, part).stem && GA->k_stem;
@@ -1004,18 +1092,34 @@ int run_wg_pair(hipStream_t s, Net& n, const char* actA, char* wsA, void* const*
     }
     CK(wg_before(s, n, GA, wsA, gradsA, with_stem));
     CK(wg_before(s, n, GB, wsB, gradsB, with_stem));
+    size_t stamped = 0;
     for (int t = 0; t < WG_CLASSES; ++t) {
         if (!GA->per_xcd[t]) continue;
+        unsigned long long* stamps = nullptr;
+        if (n.policy.timeline) {
+            if (stamped + 16 * (size_t)GA->per_xcd[t] > WG_STAMP_BLOCKS) return UDAPOSE_ERR_ARG;
+            stamps = n.policy.timeline + stamped * 8;
+            stamped += 16 * (size_t)GA->per_xcd[t];
+        }
         const int tok = conv_prof_before(s, 2, GA->flops[t] + GB->flops[t]);
         const int rc = wgrad_group_launch(s, t, GA->d_tab[t], GA->d_blk[t], GA->per_xcd[t], actA, wsA, gradsA[0], GB->d_tab[t], GB->d_blk[t], actB, wsB,
-                                          gradsB[0]);
+                                          gradsB[0], stamps);
         conv_prof_after(s, tok);
         CK(rc);
     }
     // (one table for both passes - equal accumulate modes and the same relative placement of the gradient tensors, so that the jobs'
     // destination offsets hold for both: their split sums share it, one launch over both workspaces)
     const bool pair_sum = GA == GB && GA->n_sum_blk > 0;
-    if (pair_sum) CK(pw_split_sum(s, GA->d_sum, GA->d_sum_blk, GA->n_sum_blk, wsA, (char*)gradsA[0], wsB, (char*)gradsB[0]));
+    const bool leave = defer && pair_sum && part == 0 && betaA == 0.f && n.upd.jobs && n.upd_sum_group == GA && n.upd.k_g == gradsA[0] &&
+                       GA->n_sum_blk > GA->n_sum_ws_blk;
+    if (leave) {
+        const int rest = GA->n_sum_blk - GA->n_sum_ws_blk;
+        CK(pw_split_sum(s, GA->d_sum, GA->d_sum_blk + 2 * rest, GA->n_sum_ws_blk, wsA, (char*)gradsA[0], wsB, (char*)gradsB[0]));
+        n.deferred = Net::Deferred{GA, wsA, wsB, (char*)gradsA[0], (char*)gradsB[0]};
+        if (deferred) *deferred = 1;
+    } else if (pair_sum) {
+        CK(pw_split_sum(s, GA->d_sum, GA->d_sum_blk, GA->n_sum_blk, wsA, (char*)gradsA[0], wsB, (char*)gradsB[0]));
+    }
     CK(wg_after(s, n, GA, wsA, gradsA, betaA, with_stem, pair_sum));
     return wg_after(s, n, GB, wsB, gradsB, betaB, with_stem, pair_sum);
 }
@@ -1027,6 +1131,44 @@ int net_wgrad_pair(void* h, hipStream_t s, const void* actA, void* wsA, void* co
     if (part < 0 || part > 2 || (n.f32 && !n.strict) || !n.policy.wgrad_group) return UDAPOSE_ERR_ARG;
     DbgSyncScope dbg(n.policy.debug_sync);
     return run_wg_pair(s, n, (const char*)actA, (char*)wsA, gradsA, betaA, (const char*)actB, (char*)wsB, gradsB, betaB, part);
+}
+int net_wgrad_pair_defer(void* h, hipStream_t s, const void* actA, void* wsA, void* const* gradsA, float betaA, const void* actB, void* wsB,
+                         void* const* gradsB, float betaB, int part, int* deferred) {
+    Net& n = *(Net*)h;
+    if (part < 0 || part > 2 || (n.f32 && !n.strict) || !n.policy.wgrad_group) return UDAPOSE_ERR_ARG;
+    DbgSyncScope dbg(n.policy.debug_sync);
+    return run_wg_pair(s, n, (const char*)actA, (char*)wsA, gradsA, betaA, (const char*)actB, (char*)wsB, gradsB, betaB, part, true, deferred);
+}
+// the split sums a pair call left to an update that is not going to run: their own launch after all (no mark: nothing to do)
+int net_split_sum_flush(void* h, hipStream_t s) {
+    Net& n = *(Net*)h;
+    const Net::Deferred d = n.deferred;
+    if (!d.G) return UDAPOSE_OK;
+    n.deferred = Net::Deferred{};
+    return pw_split_sum(s, d.G->d_sum, d.G->d_sum_blk, d.G->n_sum_blk - d.G->n_sum_ws_blk, d.wsA, d.gA, d.wsB, d.gB);
+}
+// the deal of a grouped launch as a pure host function (tests): units (nblk, stages) -> the runs of every XCD's list in list order, as
+// entries (xcd, unit, first work-group of the unit, count), at most `cap` of them; returns the number of entries; modelled finish per XCD
+int net_wgrad_deal(const int* nblk, const int* stages, int n_units, int order, int* ent_xcd, int* ent_unit, int* ent_first, int* ent_count, int cap,
+                   double* finish_out) {
+    if (!nblk || !stages || n_units < 0 || order < 0 || order > 1 || cap < 0) return UDAPOSE_ERR_ARG;
+    std::vector<WgUnit> units;
+    for (int i = 0; i < n_units; ++i) {
+        if (nblk[i] < 1 || stages[i] < 1) return UDAPOSE_ERR_ARG;
+        units.push_back(WgUnit{i, 0, nblk[i], stages[i], (long)nblk[i] * (stages[i] + 4)});
+    }
+    std::vector<WgUnit> runs;
+    std::vector<int> lst[8];
+    wg_deal(units, order, runs, lst);
+    int ne = 0;
+    for (int x = 0; x < 8; ++x) {
+        for (int ri : lst[x]) {
+            if (ne < cap && ent_xcd && ent_unit && ent_first && ent_count) { ent_xcd[ne] = x; ent_unit[ne] = runs[ri].prob; ent_first[ne] = runs[ri].base; ent_count[ne] = runs[ri].nblk; }
+            ++ne;
+        }
+        if (finish_out) finish_out[x] = wg_model_finish(runs, lst[x]);
+    }
+    return ne;
 }
 
 // grads[i] (fp32, same physical layout as params[i]) = beta*grads[i] + d loss / d params[i]; beta in {0,1}
@@ -1226,6 +1368,11 @@ int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grad
     std::vector<char> jobs;
     std::vector<int> bj, bs;
     std::vector<char> covered(n.n_params, 0);
+    // the split jobs of these gradient tensors' weight-gradient table (overwriting whole backward, current policy), if it is bound already: a job
+    // whose gradient is split carries where the partial tensors lie, so that a sweep can add them itself (udapose_net_wgrad_pair_defer)
+    const Net::WgGroup* SG = grads[0] ? find_wg_group(n, grads, 0.f, 0) : nullptr;
+    if (SG && (!SG->k_det || SG->n_sum_blk <= SG->n_sum_ws_blk)) SG = nullptr;
+    size_t split_found = 0;
     auto push = [&](int idx, void* sd, void* td, void* sx, void* tx, int A, int T, int B) -> int {
         const long long numel = n.param_numel[idx];
         const int adam = (h_m[idx] && h_v[idx] && grads[idx]) ? 1 : 0;
@@ -1236,6 +1383,13 @@ int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grad
         jobs.resize(jobs.size() + jb);
         opt_tail_job_fill(jobs.data() + jobs.size() - jb, (float*)params_s[idx], (const float*)grads[idx], (float*)h_m[idx], (float*)h_v[idx],
                           (float*)params_t[idx], sd, td, sx, tx, A, T, B, adam, numel);
+        if (SG && adam)
+            for (const SumJob& sj : SG->h_sum)
+                if (!sj.dst_ws && sj.dst_off == (const char*)grads[idx] - (const char*)grads[0]) {
+                    if ((long long)sj.n != numel) return UDAPOSE_ERR_UNSUPPORTED;
+                    opt_tail_job_split(jobs.data() + jobs.size() - jb, sj.part_off, sj.stride, sj.ks);
+                    ++split_found;
+                }
         const int j = (int)(jobs.size() / jb) - 1;
         const long nb = A ? (long)(A / 64) * (B / 64) * T : (long)((numel + opt_chunk() - 1) / opt_chunk());
         for (long k = 0; k < nb; ++k) { bj.push_back(j); bs.push_back((int)k); }
@@ -1260,6 +1414,12 @@ int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grad
     CK(push(n.head.w_idx, s_split ? nullptr : ws_ + n.head.wf_off, t_split ? nullptr : wt_ + n.head.wf_off, nullptr, nullptr, 0, 0, 0));      // [K][256]: the fprop pack is a cast
     for (int i = 0; i < n.n_params; ++i)
         if (!covered[i]) CK(push(i, nullptr, nullptr, nullptr, nullptr, 0, 0, 0));                   // BN vectors, head bias, backbone.fc
+    if (SG) {       // (every split job of the table must have found its parameter, or no sweep may stand in for the sums)
+        size_t want = 0;
+        for (const SumJob& sj : SG->h_sum) want += sj.dst_ws ? 0 : 1;
+        if (split_found != want) SG = nullptr;
+    }
+    n.upd_sum_group = nullptr;
     Net::UpdTab& u = n.upd;
     if (u.jobs) { (void)hipFree(u.jobs); (void)hipFree(u.blk_job); (void)hipFree(u.blk_sub); u.jobs = nullptr; }
     if (hipMalloc(&u.jobs, jobs.size()) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
@@ -1270,6 +1430,7 @@ int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grad
     if (hipMemcpy(u.blk_sub, bs.data(), bs.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
     u.nblocks = (int)bj.size();
     u.k_ps = params_s[0]; u.k_pt = params_t[0]; u.k_g = grads[0]; u.k_m = h_m[0]; u.k_ws = wpack_s_; u.k_wt = wpack_t_;
+    n.upd_sum_group = SG;
     return UDAPOSE_OK;
 }
 
@@ -1282,7 +1443,12 @@ int net_fused_update(void* hs, void* ht, hipStream_t s, void* const* params_s, v
     const Net::UpdTab& u = n.upd;
     if (!u.jobs || u.k_ps != params_s[0] || u.k_pt != params_t[0] || u.k_g != grads[0] || u.k_m != h_m[0] || u.k_ws != wpack_s_ || u.k_wt != wpack_t_)
         return UDAPOSE_ERR_NOT_PREPARED;
-    CK(opt_tail(s, u.jobs, u.blk_job, u.blk_sub, u.nblocks, lr, beta1, beta2, eps, wd, step, gscale, dev_state, alpha, oma, do_adam, grad2_delta, 1));
+    // split sums a pair call left to this sweep: it must be the sweep of exactly those two gradient buffers
+    const Net::Deferred d = n.deferred;
+    if (d.G && (d.G != n.upd_sum_group || d.gA != (char*)grads[0] || grad2_delta != (long long)(d.gB - d.gA))) return UDAPOSE_ERR_NOT_PREPARED;
+    n.deferred = Net::Deferred{};
+    CK(opt_tail(s, u.jobs, u.blk_job, u.blk_sub, u.nblocks, lr, beta1, beta2, eps, wd, step, gscale, dev_state, alpha, oma, do_adam, grad2_delta, 1,
+                d.G ? d.wsA : nullptr, d.G ? d.wsB : nullptr));
     // the two packs that are not a cast or a per-tap transpose of a whole tensor: the stem's 3 -> 8 channel gather (both
     // networks) and the head's zero-padded dgrad pack (student)
     if (n.strict)   // 'strict' student: its split forward packs (stem included) from the updated weights, one pack launch (net_bind's table)

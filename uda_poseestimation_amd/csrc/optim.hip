@@ -176,9 +176,27 @@ struct TailJob {
     elem_t* sd; elem_t* td; elem_t* sx; elem_t* tx;             // packs: student / teacher same-layout, student / teacher transposed
     int A, T, B, adam;                                          // A == 0: linear job; adam == 0: no gradient (EMA + packs only)
     long long n;
+    // a gradient whose pixel reduction was split (net.hip make_partial): `ks` partial tensors in the gradient's own layout, `stride` floats apart,
+    // at byte offset part_off of a pass's workspace (ks == 0: not split)
+    long long part_off; unsigned stride; int ks;
 };
 
-struct TailHyper { float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, gscale, alpha, oma; int do_adam; long long g2; };   // g2: byte distance to a second gradient buffer (0: none)
+// g2: byte distance to a second gradient buffer (0: none).  ws1 / ws2 (SPLIT sweeps): the workspaces of the two passes whose split sums were left to
+// this sweep (udapose_net_wgrad_pair_defer): a split job's g and g + g2 are then NOT read - the sweep adds the partial tensors itself.
+struct TailHyper { float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, gscale, alpha, oma; int do_adam; long long g2; const char* ws1; const char* ws2; };
+
+// the split sum of pointwise.hip's split_sum_k for an overwriting pass (beta = 0), expression for expression: ((p0 + p1) + p2) + ... in split order
+__device__ __forceinline__ float split_sum1(const float* __restrict__ part, size_t e, unsigned stride, int ks) {
+    float a = part[e];
+    for (int z = 1; z < ks; ++z) a += part[(size_t)z * stride + e];
+    return a;
+}
+__device__ __forceinline__ f32x4 split_sum4(const float* __restrict__ part, size_t e, unsigned stride, int ks) {
+    f32x4 a = *(const f32x4*)(part + e);
+#pragma unroll 4
+    for (int z = 1; z < ks; ++z) a += *(const f32x4*)(part + (size_t)z * stride + e);
+    return a;
+}
 
 __device__ __forceinline__ void tail1(const TailHyper& h, bool adam, float& pv, float gr, float& mi, float& vi, float& tv) {
     if (adam) {
@@ -191,6 +209,9 @@ __device__ __forceinline__ void tail1(const TailHyper& h, bool adam, float& pv, 
     tv = ema1(tv, pv, h.alpha, h.oma);
 }
 
+// SPLIT: the sweep that also takes over the split sums of the two passes (h.ws1 / h.ws2 set); the plain sweep is its own instantiation and
+// keeps its registers.
+template <bool SPLIT>
 __global__ __launch_bounds__(TPB) void opt_tail_k(const TailJob* __restrict__ jobs, const int* __restrict__ blk_job, const int* __restrict__ blk_sub,
                                                   TailHyper h, const float* __restrict__ dev_state) {
     __shared__ elem_t ts[64][66], tt[64][66];
@@ -207,8 +228,14 @@ __global__ __launch_bounds__(TPB) void opt_tail_k(const TailJob* __restrict__ jo
         for (long long i = off + threadIdx.x; i < end; i += TPB) {
             float pv = j.p[i], tv = j.t[i], mi = 0.f, vi = 0.f;
             if (adam) { mi = j.m[i]; vi = j.v[i]; }
-            float gr = adam ? j.g[i] : 0.f;
-            if (adam && h.g2) gr += *(const float*)((const char*)(j.g + i) + h.g2);      // (the two passes' gradients: g1 + g2 as axpy would)
+            float gr = 0.f;
+            if (SPLIT && adam && j.ks) {          // (each pass's split sum as split_sum_k forms it, then g1 + g2 as below)
+                gr = split_sum1((const float*)(h.ws1 + j.part_off), (size_t)i, j.stride, j.ks);
+                gr += split_sum1((const float*)(h.ws2 + j.part_off), (size_t)i, j.stride, j.ks);
+            } else if (adam) {
+                gr = j.g[i];
+                if (h.g2) gr += *(const float*)((const char*)(j.g + i) + h.g2);      // (the two passes' gradients: g1 + g2 as axpy would)
+            }
             tail1(h, adam, pv, gr, mi, vi, tv);
             if (adam) { j.p[i] = pv; j.m[i] = mi; j.v[i] = vi; }
             j.t[i] = tv;
@@ -228,8 +255,15 @@ __global__ __launch_bounds__(TPB) void opt_tail_k(const TailJob* __restrict__ jo
         f32x4 pv = *(const f32x4*)(j.p + idx), tv = *(const f32x4*)(j.t + idx);
         f32x4 mi = {0.f, 0.f, 0.f, 0.f}, vi = mi, gr = mi;
         if (adam) {
-            mi = *(const f32x4*)(j.m + idx); vi = *(const f32x4*)(j.v + idx); gr = *(const f32x4*)(j.g + idx);
-            if (h.g2) { const f32x4 g2 = *(const f32x4*)((const char*)(j.g + idx) + h.g2); gr[0] += g2[0]; gr[1] += g2[1]; gr[2] += g2[2]; gr[3] += g2[3]; }
+            mi = *(const f32x4*)(j.m + idx); vi = *(const f32x4*)(j.v + idx);
+            if (SPLIT && j.ks) {
+                gr = split_sum4((const float*)(h.ws1 + j.part_off), idx, j.stride, j.ks);
+                const f32x4 g2 = split_sum4((const float*)(h.ws2 + j.part_off), idx, j.stride, j.ks);
+                gr[0] += g2[0]; gr[1] += g2[1]; gr[2] += g2[2]; gr[3] += g2[3];
+            } else {
+                gr = *(const f32x4*)(j.g + idx);
+                if (h.g2) { const f32x4 g2 = *(const f32x4*)((const char*)(j.g + idx) + h.g2); gr[0] += g2[0]; gr[1] += g2[1]; gr[2] += g2[2]; gr[3] += g2[3]; }
+            }
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -263,20 +297,28 @@ size_t opt_tail_job_bytes() { return sizeof(TailJob); }
 // host-side filler of one table entry (net.hip builds the table: it knows the pack offsets)
 void opt_tail_job_fill(void* dst, float* p, const float* g, float* m, float* v, float* t, void* sd, void* td, void* sx, void* tx, int A, int T, int B,
                        int adam, long long n) {
-    TailJob j{p, g, m, v, t, (elem_t*)sd, (elem_t*)td, (elem_t*)sx, (elem_t*)tx, A, T, B, adam, n};
+    TailJob j{p, g, m, v, t, (elem_t*)sd, (elem_t*)td, (elem_t*)sx, (elem_t*)tx, A, T, B, adam, n, 0, 0u, 0};
     *(TailJob*)dst = j;
+}
+// ... and where its gradient's partial tensors lie, when the weight-gradient launches split its pixel reduction
+void opt_tail_job_split(void* dst, long long part_off, unsigned stride, int ks) {
+    TailJob& j = *(TailJob*)dst;
+    j.part_off = part_off; j.stride = stride; j.ks = ks;
 }
 // tick: advance the device-side step counter / bias corrections in front of the sweep (once per optimizer step: a step whose sweep is
 // issued in two parts ticks with the first)
 int opt_tail(hipStream_t s, const void* d_jobs, const int* blk_job, const int* blk_sub, int nblocks, float lr, float beta1, float beta2, float eps,
-             float wd, int step, float gscale, float* dev_state, float alpha, float oma, int do_adam, long long grad2_delta, int tick) {
+             float wd, int step, float gscale, float* dev_state, float alpha, float oma, int do_adam, long long grad2_delta, int tick,
+             const void* split_ws1, const void* split_ws2) {
     if (grad2_delta % 16) return UDAPOSE_ERR_ARG;
+    if ((split_ws1 == nullptr) != (split_ws2 == nullptr)) return UDAPOSE_ERR_ARG;
     double bc1 = 1.0, bc2 = 1.0;
     if (dev_state) { if (do_adam && tick) hipLaunchKernelGGL(adam_tick_k, dim3(1), dim3(1), 0, s, dev_state, beta1, beta2); }
     else { bc1 = 1.0 - pow((double)beta1, (double)step); bc2 = 1.0 - pow((double)beta2, (double)step); }
     if (nblocks <= 0) return UDAPOSE_OK;
-    TailHyper h{lr, beta1, beta2, eps, wd, (float)bc1, (float)sqrt(bc2), gscale, alpha, oma, do_adam, grad2_delta};
-    hipLaunchKernelGGL(opt_tail_k, dim3(nblocks), dim3(TPB), 0, s, (const TailJob*)d_jobs, blk_job, blk_sub, h, dev_state);
+    TailHyper h{lr, beta1, beta2, eps, wd, (float)bc1, (float)sqrt(bc2), gscale, alpha, oma, do_adam, grad2_delta, (const char*)split_ws1, (const char*)split_ws2};
+    if (split_ws1) hipLaunchKernelGGL(opt_tail_k<true>, dim3(nblocks), dim3(TPB), 0, s, (const TailJob*)d_jobs, blk_job, blk_sub, h, dev_state);
+    else hipLaunchKernelGGL(opt_tail_k<false>, dim3(nblocks), dim3(TPB), 0, s, (const TailJob*)d_jobs, blk_job, blk_sub, h, dev_state);
     return udapose_check_launch();
 }
 int opt_grad_check(hipStream_t s, const long long* g, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks,

@@ -810,15 +810,14 @@ __global__ __launch_bounds__(256) void wgrad_dma_kernel(const WgParams p) {
 
 // Grouped form: ONE launch computes the weight gradients of many layers.  blk is an [8][per_xcd] table (work-group b runs
 // on XCD b & 7, the hardware's round-robin, and takes entry [b & 7][b >> 3]); an entry names a problem of `tab` and the
-// work-group's linear index inside that problem's (tile, tap, split) grid, or prob < 0 = padding.  The host deals whole
-// (problem, split) units to XCDs by load, so the tiles that re-read one pixel range share an L2.  The table holds byte
+// work-group's linear index inside that problem's (tile, tap, split) grid, or prob < 0 = padding.  The host deals runs of
+// consecutive work-groups of a (problem, split) unit to XCDs by load (net.hip wg_deal), so the tiles that re-read one pixel range share an L2.  The table holds byte
 // OFFSETS in its x / dy / dw fields, relative to the three bases passed per launch, so one table serves every pass.
 template <int RT, int CT, int WR, int WC, int NS, int PX>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void wgrad_dma_group_kernel(const WgParams* __restrict__ tab, const WgGroupBlk* __restrict__ blk,
-                                                              const uint32_t per_xcd, const char* x_base, const char* dy_base, char* dw_base,
-                                                              const WgParams* __restrict__ tab2, const WgGroupBlk* __restrict__ blk2,
-                                                              const char* x_base2, const char* dy_base2, char* dw_base2) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void wgrad_group_dispatch(const WgParams* __restrict__ tab, const WgGroupBlk* __restrict__ blk, const uint32_t per_xcd,
+                                                     const char* x_base, const char* dy_base, char* dw_base, const WgParams* __restrict__ tab2,
+                                                     const WgGroupBlk* __restrict__ blk2, const char* x_base2, const char* dy_base2, char* dw_base2,
+                                                     char* smem) {
     // PAIR launch (tab2 != null): the groups of TWO passes of one plan (same table shape, their own arenas and gradient buffers) in one
     // grid, interleaved slot by slot - the second pass's heavy work-groups start beside the first's instead of behind its tail.
     uint32_t slot = blockIdx.x >> 3;
@@ -840,20 +839,57 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void w
     else wgrad_dma_body<RT, CT, WR, WC, NS, PX>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base);
 }
 
-template <int RT, int CT, int WR, int WC, int NS, int PX>
+// STAMP (tuning, policy.timeline): every work-group also records when it started and ended - stamps[blockIdx.x][8] =
+// {start, end (s_memrealtime, 100 MHz), XCD = blockIdx.x & 7, table slot, problem, 64-pixel stages, pass, tile rows} - written by one lane
+// with plain vector stores.  A separate instantiation: the production kernel (STAMP = false) keeps its registers and LDS.
+template <int RT, int CT, int WR, int WC, int NS, int PX, bool STAMP = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void wgrad_dma_group_kernel(const WgParams* __restrict__ tab, const WgGroupBlk* __restrict__ blk,
+                                                              const uint32_t per_xcd, const char* x_base, const char* dy_base, char* dw_base,
+                                                              const WgParams* __restrict__ tab2, const WgGroupBlk* __restrict__ blk2,
+                                                              const char* x_base2, const char* dy_base2, char* dw_base2,
+                                                              unsigned long long* __restrict__ stamps) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if constexpr (STAMP) {
+        // (the timed twin: the same dispatch through the production kernel's code below, bracketed by the two stamps)
+        unsigned long long* const st = stamps + (size_t)blockIdx.x * 8;
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        uint32_t slot = blockIdx.x >> 3, pass = 0;
+        if (tab2) { pass = slot & 1u; slot >>= 1; }
+        const WgGroupBlk b = (pass ? blk2 : blk)[(blockIdx.x & 7u) * per_xcd + slot];
+        long long stages = 0;
+        if (b.prob >= 0) {
+            const WgParams& p = (pass ? tab2 : tab)[b.prob];
+            const uint32_t gxy = (uint32_t)(p.r_tiles * p.c_tiles) * (uint32_t)p.total_taps;
+            const int bz = (int)((uint32_t)b.local / gxy), ms_total = (p.M + 63) / 64;
+            stages = ms_total - bz * p.msteps_per_split < p.msteps_per_split ? ms_total - bz * p.msteps_per_split : p.msteps_per_split;
+            if (p.flags & WG_FLAG_ROW3) stages |= 1ll << 32;        // (bit 32: filter-row form, bit 33: stem row-tap form)
+            if (p.flags & IG_FLAG_SMALLC) stages |= 1ll << 33;
+        }
+        wgrad_group_dispatch<RT, CT, WR, WC, NS, PX>(tab, blk, per_xcd, x_base, dy_base, dw_base, tab2, blk2, x_base2, dy_base2, dw_base2, smem);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            st[0] = t0; st[1] = __builtin_amdgcn_s_memrealtime(); st[2] = blockIdx.x & 7u; st[3] = slot;
+            st[4] = (unsigned long long)(long long)b.prob; st[5] = (unsigned long long)stages; st[6] = pass; st[7] = RT;
+        }
+    } else {
+        wgrad_group_dispatch<RT, CT, WR, WC, NS, PX>(tab, blk, per_xcd, x_base, dy_base, dw_base, tab2, blk2, x_base2, dy_base2, dw_base2, smem);
+    }
+}
+
+template <int RT, int CT, int WR, int WC, int NS, int PX, bool STAMP = false>
 int launch_wd_group(const WgParams* d_tab, const WgGroupBlk* d_blk, int per_xcd, const void* x_base, const void* dy_base, void* dw_base,
                     hipStream_t stream, const WgParams* d_tab2 = nullptr, const WgGroupBlk* d_blk2 = nullptr, const void* x_base2 = nullptr,
-                    const void* dy_base2 = nullptr, void* dw_base2 = nullptr) {
+                    const void* dy_base2 = nullptr, void* dw_base2 = nullptr, unsigned long long* stamps = nullptr) {
     using C = WdCfg<RT, CT, WR, WC, NS, PX>;
     constexpr int LDS = (RT == 64 && CT == 64 && PX == 64 && Row3Cfg::lds_bytes(NS) > C::LDS_BYTES) ? Row3Cfg::lds_bytes(NS) : C::LDS_BYTES;
     static std::atomic<unsigned long long> attr_done{0};
     static std::mutex attr_mu;
     once_per_device(attr_done, attr_mu, [] {
-        (void)hipFuncSetAttribute((const void*)wgrad_dma_group_kernel<RT, CT, WR, WC, NS, PX>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        (void)hipFuncSetAttribute((const void*)wgrad_dma_group_kernel<RT, CT, WR, WC, NS, PX, STAMP>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     });
-    hipLaunchKernelGGL((wgrad_dma_group_kernel<RT, CT, WR, WC, NS, PX>), dim3(8 * per_xcd * (d_tab2 ? 2 : 1)), dim3(256), LDS, stream, d_tab, d_blk,
+    hipLaunchKernelGGL((wgrad_dma_group_kernel<RT, CT, WR, WC, NS, PX, STAMP>), dim3(8 * per_xcd * (d_tab2 ? 2 : 1)), dim3(256), LDS, stream, d_tab, d_blk,
                        (uint32_t)per_xcd, (const char*)x_base, (const char*)dy_base, (char*)dw_base, d_tab2, d_blk2, (const char*)x_base2,
-                       (const char*)dy_base2, (char*)dw_base2);
+                       (const char*)dy_base2, (char*)dw_base2, stamps);
     return udapose_check_launch();
 }
 
@@ -995,8 +1031,12 @@ int wgrad_group_plan(WgParams& p, int accumulate, int stages_per_block, const Po
 
 int wgrad_group_launch(hipStream_t stream, int tile, const WgParams* d_tab, const WgGroupBlk* d_blk, int per_xcd, const void* x_base,
                        const void* dy_base, void* dw_base, const WgParams* d_tab2, const WgGroupBlk* d_blk2, const void* x_base2,
-                       const void* dy_base2, void* dw_base2) {
+                       const void* dy_base2, void* dw_base2, unsigned long long* stamps) {
     if (per_xcd <= 0) return UDAPOSE_OK;
+    if (stamps) {       // (tuning: the timed twins of the two kernels below)
+        if (tile == 0) return launch_wd_group<128, 128, 2, 2, 2, 32, true>(d_tab, d_blk, per_xcd, x_base, dy_base, dw_base, stream, d_tab2, d_blk2, x_base2, dy_base2, dw_base2, stamps);
+        return launch_wd_group<64, 64, 2, 2, 2, 64, true>(d_tab, d_blk, per_xcd, x_base, dy_base, dw_base, stream, d_tab2, d_blk2, x_base2, dy_base2, dw_base2, stamps);
+    }
     // 32-pixel stages for the 128x128 tile (32 KB of LDS, 128 VGPRs: four resident work-groups per CU instead of two with
     // 64-pixel stages) and a 2-stage ring of 64-pixel stages for the 64x64 tile (35 KB with the filter-row form's reserve: four per
     // CU; round 1 ran three stages = three per CU, with the buffer-load loader two measure -4.5 % alone and -0.05 ms in the step):

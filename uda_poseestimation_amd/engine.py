@@ -277,6 +277,9 @@ class MeanTeacherTrainer:
         self.merge_wgrad = True             # one rank: both passes' grouped weight gradients in one launch (pose_resnet.finish_wgrad)
         self.single_graph = True            # one rank: the optimizer tail is captured into the step's graph (one launch per step)
         self.sum_grads_in_tail = True       # ... which also adds the two passes' gradient buffers (no separate axpy; one rank only)
+        self.sum_splits_in_tail = False     # opt-in: the sweep also adds the partial tiles of the split weight-gradient reductions (udapose_net_wgrad_pair_defer):
+                                            # no split-sum launch, no write + re-read of those sums - bit-identical, but measured SLOWER in the step (the
+                                            # sweep's split blocks wait on ks dependent loads per row; profiles/tail_ab_runs.txt), so it stays off
         self.fused_last = False
 
     def _check_scaler(self):
@@ -503,7 +506,7 @@ class MeanTeacherTrainer:
         student.split_backward = False
         if merge:
             student.merge_wgrad = False
-            student.finish_wgrad()
+            student.finish_wgrad(defer_sum=self._tail_sums_splits())
         if overlap:
             student.finish_grads(part=1)    # the suffix of both passes is final: sum it ...
             if not torch.cuda.is_current_stream_capturing() or getattr(self, "capture_comm", False):
@@ -528,6 +531,10 @@ class MeanTeacherTrainer:
     def _tail_sums_grads(self):
         return bool(self.fuse_tail and self.sum_grads_in_tail and not _dist_on() and hasattr(self.stu_optimizer, "fused_tail_step")
                     and hasattr(self.student, "pending_grad_sum"))
+
+    def _tail_sums_splits(self):
+        # (a loss scaler's inf / nan check reads the gradient tensors between the weight gradients and the sweep: the fp16 step keeps the launch)
+        return bool(self.sum_splits_in_tail and self._tail_sums_grads() and getattr(self.stu_optimizer, "_scaler", None) is None)
 
     def _update(self):
         # Adam, the EMA and the next forwards' weight packs of both networks in ONE sweep when the layout allows ...

@@ -177,6 +177,8 @@ class PoseResNet(nn.Module):
         # (udapose_net_wgrad_pair): the passes end together and their weight-gradient launches are exposed at the step's end
         self.merge_wgrad = False
         self._pending_wg = []
+        self._split_sum_hd = None     # the plan whose split sums finish_wgrad(defer_sum=True) left to the optimizer sweep (None: nothing pending)
+        self.split_sums_deferred = 0  # how often that happened (tests)
         self._to_channels_last()
 
     # ------------------------------------------------------------------ layout / pointer bookkeeping
@@ -198,6 +200,7 @@ class PoseResNet(nn.Module):
         self._handles = {}
         self._pending_lower = []
         self._pending_wg = []
+        self._split_sum_hd = None
         self._split_off = None
         return r
 
@@ -396,12 +399,20 @@ class PoseResNet(nn.Module):
         st = self._grad_state
         if defer and part == 0:
             return
+        self.flush_split_sum()
         if st is not None and st[1]:
             n, off = self._flat_grad.numel(), (self.grad_split_offset() if part else 0)
             lo, cnt = (0, n) if part == 0 else ((off, n - off) if part == 1 else (0, off))
             check(lib().udapose_axpy_f32(_hip.stream(), self._flat_grad.data_ptr() + 4 * lo, self._flat_grad2.data_ptr() + 4 * lo, cnt), "axpy")
         if part != 1:
             self._grad_state = None
+
+    def flush_split_sum(self):
+        """Run the split sums that finish_wgrad(defer_sum=True) left to the optimizer sweep as their own launch after all (someone wants the
+        gradient tensors themselves, or the fused sweep is not going to run).  No-op when nothing is pending."""
+        hd, self._split_sum_hd = getattr(self, "_split_sum_hd", None), None
+        if hd is not None:
+            check(hd.L.udapose_net_split_sum_flush(hd.h, _hip.stream()), "net_split_sum_flush")
 
     def pending_grad_sum(self, take=False):
         """Byte distance from p.grad's buffer to the second per-pass buffer whose sum is still pending (0: nothing pending)."""
@@ -411,6 +422,7 @@ class PoseResNet(nn.Module):
         delta = self._flat_grad2.data_ptr() - self._flat_grad.data_ptr()
         if take:
             self._grad_state = None
+            self._split_sum_hd = None      # (the sweep that takes the buffers' sum takes the deferred split sums with it: the library consumes its mark)
         return delta
 
     def grad_split_offset(self):
@@ -497,11 +509,13 @@ class PoseResNet(nn.Module):
             if p.requires_grad and id(p) not in nograd:
                 p.grad = v
 
-    def finish_wgrad(self):
+    def finish_wgrad(self, defer_sum=False):
         """Launch the grouped weight gradients of the backward passes that ran with merge_wgrad, on the current stream (the caller
         has made it wait for the streams those passes ran on): two pending passes of one plan go out as ONE launch per tile class when
         they write different gradient buffers.  Two passes into ONE buffer (both on one stream: the second accumulates, beta 1, onto the
-        first) launch in order - in one grid the second pass's adds could land before the first pass's stores."""
+        first) launch in order - in one grid the second pass's adds could land before the first pass's stores.
+        defer_sum: the caller's next fused optimizer sweep reads both gradient buffers itself (pending_grad_sum), so the pair launch may leave
+        the split layers' sums to it as well (udapose_net_wgrad_pair_defer; flush_split_sum() undoes the deferral)."""
         pend, self._pending_wg = self._pending_wg, []
         if not pend:
             return
@@ -510,7 +524,13 @@ class PoseResNet(nn.Module):
         pa, ba, params = self._pointers()
         if len(pend) == 2 and pend[0][0] is pend[1][0] and pend[0][3][0] != pend[1][3][0]:
             (hd, actA, wsA, gA, bA, _), (_, actB, wsB, gB, bB, _) = pend
-            check(hd.L.udapose_net_wgrad_pair(hd.h, s, ptr(actA), ptr(wsA), gA, bA, ptr(actB), ptr(wsB), gB, bB, 0), "net_wgrad_pair")
+            if defer_sum:
+                took = C.c_int(0)
+                check(hd.L.udapose_net_wgrad_pair_defer(hd.h, s, ptr(actA), ptr(wsA), gA, bA, ptr(actB), ptr(wsB), gB, bB, 0, C.byref(took)), "net_wgrad_pair_defer")
+                self._split_sum_hd = hd if took.value else None
+                self.split_sums_deferred += int(took.value)
+            else:
+                check(hd.L.udapose_net_wgrad_pair(hd.h, s, ptr(actA), ptr(wsA), gA, bA, ptr(actB), ptr(wsB), gB, bB, 0), "net_wgrad_pair")
         else:
             for hd, act, ws, gptrs, beta, _ in pend:
                 check(hd.L.udapose_net_backward_phase(hd.h, s, None, pa, ptr(hd.wpack), ptr(act), ptr(ws), gptrs, beta, 0, 2), "net_backward weight gradients")
