@@ -474,6 +474,14 @@ int udapose_style_stat_loss(void* stream, const float* stats, int R, float* out,
  * theta [N][nstage][6] = the inverse affine matrices in application order; backward != 0: src = d(out), dst = d(in). */
 int udapose_affine_nearest(void* stream, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage,
                            int backward);
+/* the same chain with InterpolationMode.BILINEAR per stage (grid_sample bilinear, zeros, align_corners=False; every stage clips against
+ * the plane on its own), same theta tensor, nstage 1..8; src and dst must not overlap.  backward != 0: the exact transpose of the forward's
+ * weights as a gather - no float atomics, a fixed summation order, no limit on the outputs per input pixel: bit-reproducible.
+ * Planes with 2 * H * W * 4 <= 150 KB (every heat-map size) take one launch and allocate nothing.  Larger planes run stage by stage from
+ * global memory and, for nstage > 1, allocate one scratch tensor in stream order: inside a stream capture they are refused
+ * (UDAPOSE_ERR_UNSUPPORTED). */
+int udapose_affine_bilinear(void* stream, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage,
+                            int backward);
 /* f16x2 (UDAPOSE_EPI_SPLIT / split tensors) range check: the number of split STORES, since the last reset, of a value outside fp16's range
  * (|v| > 65504, which the format saturates, or NaN) by any kernel of THIS library on the current device.  Synchronous (reads device
  * counters): call it at an evaluation boundary - engine.validate() does and warns - never inside a stream capture. */

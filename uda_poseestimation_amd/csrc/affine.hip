@@ -4,6 +4,7 @@
 // as a chain of index maps p3 -> p2 -> p1 -> p0 (NOT as one composed matrix: that would change results).
 // Arithmetic follows torchvision/_gen_affine_grid + ATen grid_sampler(nearest, zeros, align_corners=False) in fp32:
 // theta / (0.5*[W,H]); base grid at half-integers; ix = ((x+1)*W-1)/2; nearbyint.
+// The same chain with bilinear interpolation per stage (affine_warp_chain_bilinear) follows further down.
 #include "conv_plan.h"
 
 namespace {
@@ -247,6 +248,185 @@ int affine_warp_chain(hipStream_t s, const float* src, float* dst, const float* 
         hipLaunchKernelGGL(warp_chain_k<false>, dim3(blocks, cgroups), dim3(TPB), 0, s, src, dst, theta, N, C, H, W, nstage);
     }
     return udapose_check_launch();
+}
+
+// ---------------------------------------------------------------- BILINEAR chain (tF.affine with InterpolationMode.BILINEAR per stage)
+// Per stage: _gen_affine_grid + grid_sample(bilinear, zeros, align_corners=False) - the coordinate expressions of step() above, then floor,
+// four taps with weights (x0+1-ix | ix-x0) * (y0+1-iy | iy-y0), a tap outside the plane contributing 0.  Every stage clips against the plane
+// on its own (the matrices are NOT composed).  All multiply-adds of the coordinates, the weights and the tap sums are written as explicit
+// fmaf, so that forward and backward evaluate one and the same instruction sequence wherever they are inlined: the backward's weights are
+// bitwise the forward's.
+// Backward = the exact transpose as a GATHER: d_in[r] = sum over the outputs q whose sample point lies in the open 2x2 box around r of
+// w(q -> r) * d_out[q], the q visited in raster order by the one thread that owns r - no atomics, no rank limit, the same bits every run.
+// In pixel units a stage maps q to ix = t0*bx + t1*by + t2 + (W-1)/2, iy = t3*bx + t4*by + t5 + (H-1)/2 (bx, by = q minus the plane
+// centre), so the q that can touch r lie in the image of r's box under the inverse of [[t0,t1],[t3,t4]]: a parallelogram, whose bounding
+// box - widened by the forward's fp32 coordinate error and by one output pixel - is enumerated; every candidate's ix, iy, floor and weight
+// are recomputed with the forward's expressions, and a candidate that does not touch r adds nothing.  A singular or near-singular matrix
+// (an all-zero theta) has no finite box: that stage scans the whole plane - slow, and correct.
+namespace {
+struct BilinStage { float a, b, c, d, e, f; };
+__device__ __forceinline__ BilinStage bilin_stage(const float* __restrict__ th, int W, int H) {
+    const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;
+    return {th[0] / hw, th[1] / hw, th[2] / hw, th[3] / hh, th[4] / hh, th[5] / hh};
+}
+__device__ __forceinline__ void bilin_coords(const BilinStage& m, int W, int H, int px, int py, float& ix, float& iy) {
+    const float bx = (float)px - 0.5f * (float)W + 0.5f, by = (float)py - 0.5f * (float)H + 0.5f;
+    const float gx = fmaf(bx, m.a, fmaf(by, m.b, m.c));
+    const float gy = fmaf(bx, m.d, fmaf(by, m.e, m.f));
+    ix = fmaf(gx + 1.f, (float)W, -1.f) * 0.5f;
+    iy = fmaf(gy + 1.f, (float)H, -1.f) * 0.5f;
+}
+// one output pixel of a stage: p = the stage's input plane
+__device__ __forceinline__ float bilin_sample(const float* p, const BilinStage& m, int W, int H, int px, int py) {
+    float ix, iy;
+    bilin_coords(m, W, H, px, py, ix, iy);
+    if (!(ix > -1.f && ix < (float)W && iy > -1.f && iy < (float)H)) return 0.f;        // (all four taps outside; also NaN / infinite coordinates)
+    const float fx0 = floorf(ix), fy0 = floorf(iy);
+    const int x0 = (int)fx0, y0 = (int)fy0;
+    const float wx0 = (fx0 + 1.f) - ix, wx1 = ix - fx0, wy0 = (fy0 + 1.f) - iy, wy1 = iy - fy0;
+    const bool xl = x0 >= 0, xr = x0 + 1 < W, yt = y0 >= 0, yb = y0 + 1 < H;
+    float acc = 0.f;
+    if (yt && xl) acc = fmaf(wx0 * wy0, p[y0 * W + x0], acc);
+    if (yt && xr) acc = fmaf(wx1 * wy0, p[y0 * W + x0 + 1], acc);
+    if (yb && xl) acc = fmaf(wx0 * wy1, p[(y0 + 1) * W + x0], acc);
+    if (yb && xr) acc = fmaf(wx1 * wy1, p[(y0 + 1) * W + x0 + 1], acc);
+    return acc;
+}
+// the candidate box of a stage's gather: q = Minv * (r - centre - t) + centre, +- (ex, ey)
+struct BilinBox { double i00, i01, i10, i11, tx, ty, ex, ey; int full; };
+__device__ __forceinline__ BilinBox bilin_box(const float* __restrict__ th, int W, int H) {
+    const double t0 = th[0], t1 = th[1], t2 = th[2], t3 = th[3], t4 = th[4], t5 = th[5];
+    const double det = t0 * t4 - t1 * t3, nrm = t0 * t0 + t1 * t1 + t3 * t3 + t4 * t4;
+    BilinBox b;
+    b.full = !(fabs(det) > 1e-6 * nrm) || !(nrm < 1e30) || !(fabs(t2) < 1e30) || !(fabs(t5) < 1e30);
+    if (b.full) { b.i00 = b.i01 = b.i10 = b.i11 = b.tx = b.ty = b.ex = b.ey = 0.0; return b; }
+    b.i00 = t4 / det; b.i01 = -t1 / det; b.i10 = -t3 / det; b.i11 = t0 / det;
+    b.tx = t2 + 0.5 * (double)(W - 1); b.ty = t5 + 0.5 * (double)(H - 1);
+    // half-size of r's box in input pixels: 1, plus a bound on the forward's fp32 error of ix / iy (a few roundings of terms this large)
+    const double eps = 16.0 * 5.97e-8;
+    const double hx = 1.0 + eps * (fabs(t0) * W + fabs(t1) * H + fabs(t2) + W), hy = 1.0 + eps * (fabs(t3) * W + fabs(t4) * H + fabs(t5) + H);
+    b.ex = fabs(b.i00) * hx + fabs(b.i01) * hy + 1.0;
+    b.ey = fabs(b.i10) * hx + fabs(b.i11) * hy + 1.0;
+    return b;
+}
+// one input pixel r = (rx, ry) of a stage's backward: g = d(out) of the stage
+__device__ __forceinline__ float bilin_gather(const float* g, const BilinStage& m, const BilinBox& b, int W, int H, int rx, int ry) {
+    int x_lo = 0, x_hi = W - 1, y_lo = 0, y_hi = H - 1;
+    if (!b.full) {
+        const double u = (double)rx - b.tx, v = (double)ry - b.ty;
+        const double qx = b.i00 * u + b.i01 * v + 0.5 * (double)(W - 1), qy = b.i10 * u + b.i11 * v + 0.5 * (double)(H - 1);
+        // (clamped as doubles: a centre far outside the plane must not overflow the conversion; an empty range runs no iteration)
+        x_lo = (int)fmax(0.0, fmin((double)W, ceil(qx - b.ex)));
+        x_hi = (int)fmin((double)(W - 1), fmax(-1.0, floor(qx + b.ex)));
+        y_lo = (int)fmax(0.0, fmin((double)H, ceil(qy - b.ey)));
+        y_hi = (int)fmin((double)(H - 1), fmax(-1.0, floor(qy + b.ey)));
+    }
+    float acc = 0.f;
+    for (int qy = y_lo; qy <= y_hi; ++qy)
+        for (int qx = x_lo; qx <= x_hi; ++qx) {
+            float ix, iy;
+            bilin_coords(m, W, H, qx, qy, ix, iy);
+            const float fx0 = floorf(ix), fy0 = floorf(iy);
+            const float dx = (float)rx - fx0, dy = (float)ry - fy0;         // 0: r is the tap at floor; 1: the tap after it
+            if (!((dx == 0.f || dx == 1.f) && (dy == 0.f || dy == 1.f))) continue;
+            if (!(ix > -1.f && iy > -1.f)) continue;                        // (the forward's own refusal; r is inside, so < W / < H hold)
+            const float wx = dx == 0.f ? (fx0 + 1.f) - ix : ix - fx0, wy = dy == 0.f ? (fy0 + 1.f) - iy : iy - fy0;
+            acc = fmaf(wx * wy, g[qy * W + qx], acc);
+        }
+    return acc;
+}
+// One work-group owns one (sample, channel) plane: it stages the plane in LDS and runs the stages ping-pong between two LDS planes (the
+// backward: the stages in reverse, each as the gather above); the last stage is stored with coalesced stores.  LDS: 2 * H * W * 4 bytes.
+template <bool BWD>
+__global__ __launch_bounds__(TPB) void bilin_chain_lds_k(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ theta,
+                                                         int C, int H, int W, int nstage) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int HW = H * W;
+    float* A = (float*)smem;
+    float* B = A + HW;
+    const int n = blockIdx.x / C;
+    const float* sp = src + (size_t)blockIdx.x * HW;
+    float* dp = dst + (size_t)blockIdx.x * HW;
+    for (int i = threadIdx.x; i < HW; i += TPB) A[i] = sp[i];
+    __syncthreads();
+    for (int k = 0; k < nstage; ++k) {
+        const float* th = theta + ((size_t)n * nstage + (BWD ? nstage - 1 - k : k)) * 6;
+        const BilinStage m = bilin_stage(th, W, H);
+        BilinBox box;
+        if (BWD) box = bilin_box(th, W, H);
+        const bool last = k == nstage - 1;
+        for (int i = threadIdx.x; i < HW; i += TPB) {
+            const int py = i / W, px = i % W;
+            float v;
+            if (BWD) v = bilin_gather(A, m, box, W, H, px, py);
+            else v = bilin_sample(A, m, W, H, px, py);
+            if (last) dp[i] = v; else B[i] = v;
+        }
+        __syncthreads();
+        float* t = A; A = B; B = t;
+    }
+}
+// A plane beyond the LDS budget (the 256x256 images warp.affine may be handed): one stage per launch, from and to global memory
+template <bool BWD>
+__global__ __launch_bounds__(TPB) void bilin_stage_global_k(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ theta,
+                                                            int C, int H, int W, int nstage, int s, int tiles) {
+    const int HW = H * W;
+    const int plane = blockIdx.x / tiles, i = (blockIdx.x % tiles) * TPB + threadIdx.x;
+    if (i >= HW) return;
+    const float* th = theta + ((size_t)(plane / C) * nstage + s) * 6;
+    const BilinStage m = bilin_stage(th, W, H);
+    const float* sp = src + (size_t)plane * HW;
+    const int py = i / W, px = i % W;
+    float v;
+    if (BWD) {
+        const BilinBox box = bilin_box(th, W, H);
+        v = bilin_gather(sp, m, box, W, H, px, py);
+    } else {
+        v = bilin_sample(sp, m, W, H, px, py);
+    }
+    dst[(size_t)plane * HW + i] = v;
+}
+}  // namespace
+
+// src and dst must not overlap.  Planes within the LDS budget (2 * H * W * 4 <= 150 KB: every heat-map size) take one launch and allocate
+// nothing.  Larger planes run stage by stage from global memory; with more than one stage they go through one scratch tensor allocated
+// and freed in stream order - never inside a stream capture, where such planes are refused (UDAPOSE_ERR_UNSUPPORTED).
+int affine_warp_chain_bilinear(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward) {
+    if (nstage < 1 || nstage > 8 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || !src || !dst || !theta) return UDAPOSE_ERR_ARG;
+    if ((long long)H * W > (1ll << 26) || (long long)N * C >= (1ll << 31)) return UDAPOSE_ERR_ARG;
+    const int HW = H * W;
+    const size_t lds = (size_t)HW * 2 * sizeof(float);
+    if (lds <= 150 * 1024) {
+        static std::atomic<unsigned long long> attr_done{0};
+        static std::mutex attr_mu;
+        once_per_device(attr_done, attr_mu, [] {
+            (void)hipFuncSetAttribute((const void*)bilin_chain_lds_k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+            (void)hipFuncSetAttribute((const void*)bilin_chain_lds_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        });
+        const unsigned bytes = (unsigned)((lds + 15) & ~(size_t)15);
+        if (backward) hipLaunchKernelGGL(bilin_chain_lds_k<true>, dim3(N * C), dim3(TPB), bytes, s, src, dst, theta, C, H, W, nstage);
+        else hipLaunchKernelGGL(bilin_chain_lds_k<false>, dim3(N * C), dim3(TPB), bytes, s, src, dst, theta, C, H, W, nstage);
+        return udapose_check_launch();
+    }
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
+    if (cap != hipStreamCaptureStatusNone) return UDAPOSE_ERR_UNSUPPORTED;
+    const int tiles = (HW + TPB - 1) / TPB;
+    if ((long long)N * C * tiles >= (1ll << 31)) return UDAPOSE_ERR_ARG;
+    float* scratch = nullptr;
+    if (nstage > 1 && hipMallocAsync((void**)&scratch, (size_t)N * C * HW * sizeof(float), s) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
+    const float* in = src;
+    int rc = UDAPOSE_OK;
+    for (int k = 0; k < nstage && rc == UDAPOSE_OK; ++k) {
+        float* out = (nstage - 1 - k) % 2 == 0 ? dst : scratch;        // (the stages alternate between the two; the last one writes dst)
+        const int st = backward ? nstage - 1 - k : k;
+        if (backward) hipLaunchKernelGGL(bilin_stage_global_k<true>, dim3(N * C * tiles), dim3(TPB), 0, s, in, out, theta, C, H, W, nstage, st, tiles);
+        else hipLaunchKernelGGL(bilin_stage_global_k<false>, dim3(N * C * tiles), dim3(TPB), 0, s, in, out, theta, C, H, W, nstage, st, tiles);
+        rc = udapose_check_launch();
+        in = out;
+    }
+    if (scratch && hipFreeAsync(scratch, s) != hipSuccess && rc == UDAPOSE_OK) rc = UDAPOSE_ERR_LAUNCH;
+    return rc;
 }
 
 // mean over k re-warped teacher views (train_human.py:361-372 with --k > 1: `torch.mean(recons, dim=0)`): the k values of an element

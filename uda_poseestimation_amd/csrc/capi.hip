@@ -79,6 +79,7 @@ int aug_to_tensor(hipStream_t, const unsigned char*, float*, int, int, const flo
 int aug_gaussian_labels(hipStream_t, const double*, const float*, float*, float*, int, int, int, double, double, const float*, int);
 int aug_draw_labelmap_ori(hipStream_t, const float*, const float*, const unsigned char*, float*, float*, int, int, int, float, const float*, int);
 int affine_warp_chain(hipStream_t, const float*, float*, const float*, int, int, int, int, int, int);
+int affine_warp_chain_bilinear(hipStream_t, const float*, float*, const float*, int, int, int, int, int, int);
 int affine_recon_thetas(hipStream_t, const double*, int, double, float*, float*);
 int affine_mean_views(hipStream_t, const float* const*, int, float*, size_t);
 unsigned long long sp_sat_read_adain(int);
@@ -494,6 +495,9 @@ int udapose_mean_views(void* stream, const float* const* h_views, int k, float* 
 }
 int udapose_affine_nearest(void* stream, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward) {
     return affine_warp_chain(S(stream), src, dst, theta, N, C, H, W, nstage, backward);
+}
+int udapose_affine_bilinear(void* stream, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward) {
+    return affine_warp_chain_bilinear(S(stream), src, dst, theta, N, C, H, W, nstage, backward);
 }
 
 int udapose_aug_affine_u8(void* stream, const unsigned char* src, unsigned char* dst, const long long* coef, int N, int H, int W) {

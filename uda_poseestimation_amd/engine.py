@@ -199,7 +199,13 @@ class MeanTeacherTrainer:
                  heatmap_size=64, use_sgd=False, style_net=None, recover=None, s2t_freq=0.5, t2s_freq=0.5, s2t_alpha=(0.0, 1.0),
                  t2s_alpha=(0.0, 1.0), rng=None, occlude_rate=-1.0, occlude_thresh=0.9, occlude_size=10, image_px=None, precision=None,
                  loss_scale_init=65536.0, loss_scale_interval=2000, grad_comm="fp32", criterion=None, con_criterion=None, ent_criterion=None,
-                 lambda_ent=0.0):
+                 lambda_ent=0.0, warp_mode="nearest"):
+        """warp_mode: "nearest" (the reference's) or "bilinear" - the interpolation of the two heat-map re-warps of a step: the teacher's
+        views before their mean, and the student's y_t_stu_recon (under autograd).  The occlusion path's IMAGE warps stay nearest in either
+        mode: they paste patches at integer boxes and are not under autograd."""
+        if warp_mode not in warp.MODES:
+            raise ValueError(f"warp_mode {warp_mode!r}: one of {warp.MODES}")
+        self.warp_mode = warp_mode
         # a single-device nn.DataParallel wrap (the reference's call form) is unwrapped: the engine drives the executor's own entry points
         # (prepare / forward_deferred_bn / finish_wgrad ...), which live on the module
         student, teacher = getattr(student, "module", student), getattr(teacher, "module", teacher)
@@ -408,7 +414,7 @@ class MeanTeacherTrainer:
         s_stu.wait_stream(main)
         with torch.cuda.stream(s_tea), torch.no_grad():
             y_t_teas = [teacher(x_t) for x_t in x_t_teas]
-            recons = [warp.warp_chain(y, th) for y, th in zip(y_t_teas, thetas_tea)]
+            recons = [warp.warp_chain(y, th, self.warp_mode) for y, th in zip(y_t_teas, thetas_tea)]
             y_t_tea_recon = warp.mean_views(recons)          # (k teacher views, train_human.py:361-372: one launch; k = 1: the view itself)
         if occl is not None:
             # the occlusion needs the teacher's re-warped heat-maps: the source-domain forward is issued first (it runs under
@@ -428,7 +434,7 @@ class MeanTeacherTrainer:
                         x_t_stu, self.occluded = warp.occlude_keypoints(x_t_stu, y_t_tea_recon, occl[1], self.ratio, self.image_px,
                                                                         self.occlude_rate, self.occlude_thresh, self.occlude_size, self.occl_rng)
             y_t_stu = student.forward_deferred_bn(x_t_stu)     # separate forwards: separate BN statistics per domain
-            y_t_stu_recon = warp.warp_chain(y_t_stu, theta_stu)
+            y_t_stu_recon = warp.warp_chain(y_t_stu, theta_stu, self.warp_mode)
         if occl is None:
             y_s = student(x_s)
         main.wait_stream(s_stu)
@@ -616,6 +622,12 @@ class GraphedTrainStep:
         if self.occl and not trainer.device_occlusion:
             raise RuntimeError("GraphedTrainStep with occlusion needs trainer.device_occlusion = True (the reference's host draws read "
                                "the confidences back every step, which a captured step cannot do)")
+        if trainer.warp_mode == "bilinear":
+            hm = [int(round(v / trainer.ratio)) for v in x_t_stu.shape[-2:]]
+            if not warp.bilinear_fits_lds(*hm):
+                raise RuntimeError(f"GraphedTrainStep with warp_mode='bilinear': {hm[0]}x{hm[1]} heat-map planes exceed the re-warp's "
+                                   f"{warp.BILINEAR_LDS_BYTES // 1024} KB LDS budget; the stage-by-stage form allocates scratch memory, which a "
+                                   "captured step must not do - use the eager train_step for heat-maps this large")
         self.t = trainer
         self._stage, self._have_staged = None, False
         dev = x_s.device
@@ -1029,7 +1041,7 @@ class GraphedTrainStep:
         opt = t.stu_optimizer
         frozen = [("teacher_alpha", float(t.tea_optimizer.alpha)), ("lambda_c", float(t.lambda_c)), ("mask_ratio", float(t.mask_ratio)),
                   ("sigma", float(t.sigma)), ("bn_momentum", float(t.student.bn_momentum)), ("occlude_rate", float(t.occlude_rate)),
-                  ("occlude_thresh", float(t.occlude_thresh)), ("occlude_size", int(t.occlude_size))]
+                  ("occlude_thresh", float(t.occlude_thresh)), ("occlude_size", int(t.occlude_size)), ("warp_mode", str(t.warp_mode))]
         for gi, g in enumerate(opt.param_groups):
             for k in ("betas", "eps", "weight_decay", "momentum", "nesterov"):
                 if k in g:

@@ -1,8 +1,10 @@
 """Batched heat-map / image re-warp on the device.
 
 Stands in for the per-sample `tF.affine` triplets of the training loop (train_human.py:361-372, 385-391, 412, 418-423):
-translate by (tx/ratio, ty/ratio); rotate by `angle` and scale; shear by (sx, sy) - three sequential nearest-neighbour
-resamplings, evaluated by ONE kernel as a chain of index maps (results identical to the sequential form).  The inverse
+translate by (tx/ratio, ty/ratio); rotate by `angle` and scale; shear by (sx, sy) - three sequential resamplings in ONE launch
+(results identical to the sequential form).  mode "nearest" (the default, the reference's) evaluates the chain as index maps;
+mode "bilinear" (`InterpolationMode.BILINEAR` per stage: four taps, zero padding, every stage clipped on its own) runs the stages
+ping-pong in LDS, and its backward is the exact transpose as a gather - no float atomics, bit-reproducible.  The inverse
 affine matrices are built on the host in double precision exactly like torchvision's `_get_inverse_affine_matrix`
 (torchvision itself is not a dependency); parameters arrive as the collated `aug_param` structure of
 lib/transforms/keypoint_detection.py:139: [angle[N], [tx[N], ty[N]], [sx[N], sy[N]], scale[N]].
@@ -103,18 +105,51 @@ def single_thetas(angle, translate, scale, shear, n, device=None):
     return th.to(device) if device is not None else th
 
 
+MODES = ("nearest", "bilinear")
+BILINEAR_LDS_BYTES = 150 * 1024         # two fp32 planes must fit (csrc/affine.hip); larger planes run stage by stage from global memory
+
+
+def interpolation_mode(interpolation):
+    """torchvision's `interpolation` argument -> "nearest" | "bilinear": None, 0, "nearest" or an enum whose .value is "nearest";
+    2, "bilinear" or an enum whose .value is "bilinear" (InterpolationMode, or PIL's integer codes).  Anything else is refused."""
+    v = getattr(interpolation, "value", interpolation)
+    if v is None or (isinstance(v, str) and v == "nearest") or (isinstance(v, int) and not isinstance(v, bool) and v == 0):
+        return "nearest"
+    if (isinstance(v, str) and v == "bilinear") or (isinstance(v, int) and not isinstance(v, bool) and v == 2):
+        return "bilinear"
+    raise NotImplementedError(f"interpolation {interpolation!r}: only nearest (torchvision's default, the one the reference uses) and "
+                              "bilinear have device kernels")
+
+
+def bilinear_fits_lds(H, W):
+    """Whether a bilinear chain over H x W planes takes the one-launch LDS form (which allocates nothing: capturable)."""
+    return 2 * int(H) * int(W) * 4 <= BILINEAR_LDS_BYTES
+
+
+def _chain_call(mode, H, W):
+    if mode == "nearest":
+        return lib().udapose_affine_nearest
+    if mode != "bilinear":
+        raise ValueError(f"warp mode {mode!r}: one of {MODES}")
+    if not bilinear_fits_lds(H, W) and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"bilinear re-warp of {H}x{W} planes inside a stream capture: two planes exceed the {BILINEAR_LDS_BYTES // 1024} KB "
+                           "LDS budget, and the stage-by-stage form allocates scratch memory - run it outside the capture")
+    return lib().udapose_affine_bilinear
+
+
 class _WarpFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, theta):
+    def forward(ctx, x, theta, mode):
         _hip.require_cuda(x, theta)
         xin = x.detach().float().contiguous()
         N, C, H, W = xin.shape
         th = theta.detach().float().contiguous()
         assert th.shape[0] == N and th.shape[2] == 6
         out = torch.empty_like(xin)
-        check(lib().udapose_affine_nearest(_hip.stream(), ptr(xin), ptr(out), ptr(th), N, C, H, W, th.shape[1], 0), "affine_nearest")
+        check(_chain_call(mode, H, W)(_hip.stream(), ptr(xin), ptr(out), ptr(th), N, C, H, W, th.shape[1], 0), f"affine_{mode}")
         ctx.save_for_backward(th)
         ctx.in_dtype = x.dtype
+        ctx.mode = mode
         return out.to(x.dtype)
 
     @staticmethod
@@ -123,13 +158,16 @@ class _WarpFn(torch.autograd.Function):
         gin = g.detach().float().contiguous()
         N, C, H, W = gin.shape
         dx = torch.empty_like(gin)
-        check(lib().udapose_affine_nearest(_hip.stream(), ptr(gin), ptr(dx), ptr(th), N, C, H, W, th.shape[1], 1), "affine_nearest_bwd")
-        return dx.to(ctx.in_dtype), None
+        check(_chain_call(ctx.mode, H, W)(_hip.stream(), ptr(gin), ptr(dx), ptr(th), N, C, H, W, th.shape[1], 1), f"affine_{ctx.mode}_bwd")
+        return dx.to(ctx.in_dtype), None, None
 
 
-def warp_chain(x, theta):
-    """x [N,C,H,W]; theta [N,S,6] inverse affine matrices applied in order 0..S-1 (nearest, zero fill); differentiable."""
-    return _WarpFn.apply(x, theta)
+def warp_chain(x, theta, mode="nearest"):
+    """x [N,C,H,W]; theta [N,S,6] inverse affine matrices applied in order 0..S-1 (zero fill); differentiable.  mode: "nearest" or
+    "bilinear" (the backward of either is deterministic)."""
+    if mode not in MODES:
+        raise ValueError(f"warp mode {mode!r}: one of {MODES}")
+    return _WarpFn.apply(x, theta, mode)
 
 
 def mean_views(views):
@@ -150,11 +188,11 @@ def mean_views(views):
 
 def affine(img, angle, translate, scale, shear, interpolation=None, fill=None):
     """`torchvision.transforms.functional.affine` for CUDA tensors as the reference's loop calls it (train_human.py:366-368,
-    388-390, 412, 421-423): img [C,H,W] or [N,C,H,W], nearest interpolation, zero fill, centre of rotation = image centre;
+    388-390, 412, 421-423): img [C,H,W] or [N,C,H,W], nearest (the default) or bilinear interpolation (`interpolation_mode` lists the
+    accepted spellings; bicubic is refused), zero fill, centre of rotation = image centre;
     differentiable (the student's heat-maps are warped under autograd, :421-423).  One launch of the batched kernel with a
     single stage; the loop's three-call chains can use `warp_chain` / `recon_heatmaps` instead (one launch for the batch)."""
-    if interpolation not in (None, 0, "nearest") and getattr(interpolation, "value", interpolation) != "nearest":
-        raise NotImplementedError("only nearest interpolation (torchvision's default, the one the reference uses)")
+    mode = interpolation_mode(interpolation)
     if fill not in (None, 0, 0.0):
         raise NotImplementedError("only zero fill")
     if not isinstance(shear, (list, tuple)):
@@ -163,13 +201,13 @@ def affine(img, angle, translate, scale, shear, interpolation=None, fill=None):
     x = img.unsqueeze(0) if squeeze else img
     m = inverse_affine_matrix(float(angle), [float(translate[0]), float(translate[1])], float(scale), [float(shear[0]), float(shear[1])])
     theta = torch.tensor(m, dtype=torch.float32).reshape(1, 1, 6).expand(x.shape[0], 1, 6).contiguous().to(x.device, non_blocking=True)
-    out = warp_chain(x, theta)
+    out = warp_chain(x, theta, mode)
     return out.squeeze(0) if squeeze else out
 
 
-def recon_heatmaps(y, aug_param, ratio):
+def recon_heatmaps(y, aug_param, ratio, mode="nearest"):
     """The loop's heat-map re-warp (train_human.py:361-372 / 418-423) for the whole batch."""
-    return warp_chain(y, recon_thetas(aug_param, y.shape[0], ratio, y.device))
+    return warp_chain(y, recon_thetas(aug_param, y.shape[0], ratio, y.device), mode)
 
 
 def occlude_keypoints(x_t_stu, y_t_tea_recon, aug_param_stu, ratio, image_size, occlude_rate, occlude_thresh, occlude_size, rng):
