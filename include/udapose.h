@@ -182,9 +182,48 @@ int udapose_bn_bwd_pre(void* stream, const void* g, int g_is_f32, const void* y,
                        const float* save_mean, const float* save_invstd, const float* slab, int rows, float* coef, float* dgamma,
                        float* dbeta, float beta_acc);
 
+/* Every BatchNorm form by explicit selectors instead of the default policy (what the executor picks from its plan's policy).  Each
+ * returns a form code >= 0 - bit 0: the channel-chunked form took the layer, bit 1: the XCD row mapping was engaged - or a negative
+ * error.
+ * udapose_bn_train_fwd_ex: finalize + apply of one training-mode layer from the convolution's statistics slab[rows][2][C]; count = npix.
+ * kind 0: y, res, z 16-bit; 1: fp32; 2: y fp32, res / z f16x2 split; 3: kind 2 plus the 'strict' shadows y16 = fp16(y), z16 = the
+ * h half of z and, when mask is given, the ReLU bit mask of z16 (fp16 build only: UDAPOSE_ERR_UNSUPPORTED otherwise).  pre_bias: a
+ * per-channel bias the producer added after its statistics (streaming form only).  fwd_chunked / xcd_rows: the policy fields
+ * bn_fwd_chunked / bn_xcd_rows.  mask (kinds 0 and 3): one byte per 8 channels, bit e = stored z > 0.  scale, shift: [C] scratch of the
+ * streaming form; save: [3][C] = mean, invstd, unbiased variance. */
+int udapose_bn_train_fwd_ex(void* stream, int kind, const void* y, const void* res, void* z, size_t npix, int C, const float* slab, int rows,
+                            const float* gamma, const float* beta, const float* pre_bias, float* running_mean, float* running_var,
+                            long long* num_batches_tracked, float momentum, float eps, float* scale, float* shift, float* save, int relu,
+                            int fwd_chunked, int xcd_rows, unsigned char* mask, void* y16, void* z16);
+/* udapose_bn_bwd / udapose_bn_bwd_pre with the policy fields as arguments: chunked = bn_bwd_chunked (udapose_bn_bwd_pre_ex: | 1 << 30 for
+ * XCD-aligned pixel ranges in the chunked form, | 1 << 29 in the streaming form), legacy = bn_bwd_pre_legacy. */
+int udapose_bn_bwd_ex(void* stream, const void* dz, int dz_is_f32, const void* z, const void* y, void* dy, void* gout, size_t npix, int C,
+                      const float* gamma, const float* save_mean, const float* save_invstd, int relu, float* slab, float* coef,
+                      float* dgamma, float* dbeta, float beta_acc, const float* beta, int chunked);
+int udapose_bn_bwd_pre_ex(void* stream, const void* g, int g_is_f32, const void* y, void* dy, size_t npix, int C, const float* gamma,
+                          const float* save_mean, const float* save_invstd, const float* slab, int rows, float* coef, float* dgamma,
+                          float* dbeta, float beta_acc, int chunked, int legacy);
+/* The stem's fused forms (16-bit): y = maxpool3x3s2(relu(x*scale + shift)) with the winning taps, z never written; and the BatchNorm
+ * backward (ReLU mask recomputed from y) whose incoming gradient is the max-pool backward of (pool_dy, pool_idx), gathered on the fly.
+ * H x W: the pool's input size; npix = N*H*W; slab: [bn_bwd_rows(npix)][2][C]. */
+int udapose_bn_relu_maxpool3x3s2(void* stream, const void* x, void* y, unsigned char* idx, int N, int H, int W, int C, const float* scale,
+                                 const float* shift);
+int udapose_bn_bwd_pooled(void* stream, const void* pool_dy, const unsigned char* pool_idx, int H, int W, const void* y, void* dy, size_t npix,
+                          int C, const float* gamma, const float* save_mean, const float* save_invstd, float* slab, float* coef,
+                          float* dgamma, float* dbeta, float beta_acc, const float* beta);
+/* The deferred running-statistics update on its own: running = (1 - momentum) * running + momentum * saved, counter += 1, from the
+ * statistics save[3][C] (mean, invstd, unbiased variance) a forward left.  _multi: njobs layers in one launch, as
+ * udapose_net_apply_running does; d_jobs is a device table of njobs records { size_t save_off; float* running_mean; float* running_var;
+ * long long* num_batches_tracked; int C; int pad; } whose save is at act + save_off; max_c >= every record's C. */
+int udapose_bn_running_update(void* stream, const float* save, int C, float* running_mean, float* running_var,
+                              long long* num_batches_tracked, float momentum);
+int udapose_bn_running_update_multi(void* stream, const void* d_jobs, int njobs, int max_c, const void* act, float momentum);
+
 /* ---------------------------------------------------------------- pooling (ResNet stem maxpool 3x3 s2 p1, resnet.py:30;
  * VGG MaxPool2d(2,2,ceil_mode=True), Style_net.py:72) */
 int udapose_maxpool3x3s2_fwd(void* stream, const void* x, void* y, unsigned char* idx, int N, int H, int W, int C);
+/* kind 0: 16-bit; 1: fp32; 2: f16x2 split; 3: split plus y16 = the pooled fp16 map (fp16 build only) */
+int udapose_maxpool3x3s2_fwd_ex(void* stream, int kind, const void* x, void* y, unsigned char* idx, int N, int H, int W, int C, void* y16);
 int udapose_maxpool3x3s2_bwd(void* stream, const void* dy, const unsigned char* idx, void* dx, int N, int H, int W, int C);
 int udapose_maxpool2x2_ceil(void* stream, const void* x, void* y, int N, int H, int W, int C);
 int udapose_maxpool2x2_ceil_f32(void* stream, const float* x, float* y, int N, int H, int W, int C);   /* fp32 NHWC (Style_net.py:72) */

@@ -18,6 +18,11 @@ import torch
 
 MANT = {torch.bfloat16: 8, torch.float16: 11, torch.float32: 24, torch.float64: 53}
 MIN_EXP = {torch.bfloat16: -126, torch.float16: -14, torch.float32: -126, torch.float64: -1022}
+# "split": the f16x2 storage h + l * 2^-11 (two fp16 numbers) read back as fp32: l = fp16((v - h) * 2^11) is off by at most 2^(e - 23) of v = m * 2^e,
+# and the fp32 join h + l * 2^-11 rounds once more (2^(e - 24)): within half an ulp of a 22-bit significand; l's subnormal spacing 2^-24 scaled by 2^-11
+# gives the floor 2^-36
+MANT["split"] = 22
+MIN_EXP["split"] = -14
 
 
 @dataclass(frozen=True)

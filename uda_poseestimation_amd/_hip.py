@@ -76,6 +76,14 @@ _SIGS = {
     "udapose_bn_bwd_rows": (ci, [sz]),
     "udapose_bn_bwd": (ci, [vp, vp, ci, vp, vp, vp, vp, sz, ci, vp, vp, vp, ci, vp, vp, vp, vp, cf, vp]),
     "udapose_bn_bwd_pre": (ci, [vp, vp, ci, vp, vp, sz, ci, vp, vp, vp, vp, ci, vp, vp, vp, cf]),
+    "udapose_bn_train_fwd_ex": (ci, [vp, ci, vp, vp, vp, sz, ci, vp, ci, vp, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, ci, ci, ci, vp, vp, vp]),
+    "udapose_bn_bwd_ex": (ci, [vp, vp, ci, vp, vp, vp, vp, sz, ci, vp, vp, vp, ci, vp, vp, vp, vp, cf, vp, ci]),
+    "udapose_bn_bwd_pre_ex": (ci, [vp, vp, ci, vp, vp, sz, ci, vp, vp, vp, vp, ci, vp, vp, vp, cf, ci, ci]),
+    "udapose_bn_relu_maxpool3x3s2": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp]),
+    "udapose_bn_bwd_pooled": (ci, [vp, vp, vp, ci, ci, vp, vp, sz, ci, vp, vp, vp, vp, vp, vp, vp, cf, vp]),
+    "udapose_bn_running_update": (ci, [vp, vp, ci, vp, vp, vp, cf]),
+    "udapose_bn_running_update_multi": (ci, [vp, vp, ci, ci, vp, cf]),
+    "udapose_maxpool3x3s2_fwd_ex":(ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, vp]),
     "udapose_maxpool3x3s2_fwd": (ci, [vp, vp, vp, vp, ci, ci, ci, ci]),
     "udapose_maxpool3x3s2_bwd": (ci, [vp, vp, vp, vp, ci, ci, ci, ci]),
     "udapose_maxpool2x2_ceil": (ci, [vp, vp, vp, ci, ci, ci, ci]),

@@ -18,6 +18,23 @@ int pw_bn_bwd_pre(hipStream_t, const void*, int, const elem_t*, elem_t*, size_t,
 int pw_bn_bwd(hipStream_t, const void*, int, const elem_t*, const elem_t*, elem_t*, elem_t*, size_t, int, const float*, const float*, const float*, int,
               float*, float*, float*, float*, float, const float*, int);
 int pw_maxpool3x3s2_fwd(hipStream_t, const elem_t*, elem_t*, unsigned char*, int, int, int, int);
+// the BatchNorm / pooling forms the executor reaches through its plan (net.hip), for the *_ex entry points below
+int pw_bn_train_fused(hipStream_t, const elem_t*, const elem_t*, elem_t*, size_t, int, const float*, int, const float*, const float*, float*, float*,
+                      long long*, float, float, float*, int, int, unsigned char*);
+int pw_bn_train_fused_split(hipStream_t, const float*, const void*, void*, size_t, int, const float*, int, const float*, const float*, float*, float*,
+                            long long*, float, float, float*, int, int, void*, void*, unsigned char*);
+int pw_bn_apply_split(hipStream_t, const float*, const void*, void*, size_t, int, const float*, const float*, int, void*, void*, unsigned char*, int);
+int pw_bn_apply_f32(hipStream_t, const float*, const float*, float*, size_t, int, const float*, const float*, int);
+int pw_bn_apply_xcd_ok(size_t, int);
+int pw_bn_bwd_takes_chunked(size_t, int, int);
+int pw_bn_bwd_pre_takes_chunked(size_t, int, int, int);
+int pw_bn_relu_maxpool3x3s2(hipStream_t, const elem_t*, elem_t*, unsigned char*, int, int, int, int, const float*, const float*);
+int pw_bn_bwd_pooled(hipStream_t, const elem_t*, const unsigned char*, int, int, const elem_t*, elem_t*, size_t, int, const float*, const float*,
+                     const float*, float*, float*, float*, float*, float, const float*);
+int pw_maxpool3x3s2_fwd_f32(hipStream_t, const float*, float*, unsigned char*, int, int, int, int);
+int pw_maxpool3x3s2_fwd_split(hipStream_t, const void*, void*, unsigned char*, int, int, int, int, void*);
+int pw_bn_running_update(hipStream_t, const float*, int, float*, float*, long long*, float);
+int pw_bn_running_update_multi(hipStream_t, const BnRunJob*, int, int, const void*, float);
 
 // adain_train.hip (the AdaIN decoder's training step)
 size_t conv_bwd_ws_bytes(const ConvGeom& g);
@@ -220,6 +237,82 @@ int udapose_bn_bwd_pre(void* stream, const void* g, int g_is_f32, const void* y,
     if (!g || !y || !dy || !gamma || !mean || !invstd || !slab || !coef) return UDAPOSE_ERR_ARG;
     return pw_bn_bwd_pre(S(stream), g, g_is_f32, CB16(y), B16(dy), npix, C, gamma, mean, invstd, slab, rows, coef, dgamma, dbeta, beta_acc,
                          default_policy().bn_bwd_chunked, default_policy().bn_bwd_pre_legacy);
+}
+// ---- every BatchNorm / pooling form by explicit selectors (what the executor picks from its policy): each returns a form code >= 0
+// (bit 0: the channel-chunked form took the layer, bit 1: the XCD row mapping was engaged) or a negative error
+int udapose_bn_train_fwd_ex(void* stream, int kind, const void* y, const void* res, void* z, size_t npix, int C, const float* slab, int rows,
+                            const float* gamma, const float* beta, const float* pre_bias, float* running_mean, float* running_var,
+                            long long* num_batches_tracked, float momentum, float eps, float* scale, float* shift, float* save, int relu,
+                            int fwd_chunked, int xcd_rows, unsigned char* mask, void* y16, void* z16) {
+    if (!y || !z || !slab || !gamma || !beta || !scale || !shift || !save || npix < 1 || rows < 1 || C < 8 || C % 8 || kind < 0 || kind > 3)
+        return UDAPOSE_ERR_ARG;
+    if ((kind == 3) != (y16 != nullptr) || (kind == 3) != (z16 != nullptr) || (mask && (kind == 1 || kind == 2))) return UDAPOSE_ERR_ARG;
+    if (kind == 3 && UDAPOSE_ELEM_KIND != 1) return UDAPOSE_ERR_UNSUPPORTED;      // (the shadows are the fp16 build's backward operands)
+    const int chunked = fwd_chunked | (xcd_rows ? (1 << 30) : 0);
+    int took = 0;
+    if (kind == 0 && !pre_bias)
+        took = pw_bn_train_fused(S(stream), CB16(y), CB16(res), B16(z), npix, C, slab, rows, gamma, beta, running_mean, running_var,
+                                 num_batches_tracked, momentum, eps, save, relu, chunked, mask);
+    else if (kind >= 2 && !pre_bias)
+        took = pw_bn_train_fused_split(S(stream), (const float*)y, res, z, npix, C, slab, rows, gamma, beta, running_mean, running_var,
+                                       num_batches_tracked, momentum, eps, save, relu, chunked, y16, z16, mask);
+    if (took < 0) return took;
+    if (took) return 1 | (xcd_rows ? 2 : 0);
+    int rc = pw_bn_finalize(S(stream), slab, rows, C, (double)npix, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale,
+                            shift, save, save + C, pre_bias);
+    if (rc != UDAPOSE_OK) return rc;
+    const int xcd = xcd_rows >= 2;
+    if (kind == 0) rc = pw_bn_apply(S(stream), CB16(y), CB16(res), B16(z), npix * C, C, scale, shift, relu, mask, xcd);
+    else if (kind == 1) rc = pw_bn_apply_f32(S(stream), (const float*)y, (const float*)res, (float*)z, npix * C, C, scale, shift, relu);
+    else rc = pw_bn_apply_split(S(stream), (const float*)y, res, z, npix * C, C, scale, shift, relu, y16, z16, mask, xcd);
+    if (rc != UDAPOSE_OK) return rc;
+    return (xcd && (kind == 0 || kind == 3) && pw_bn_apply_xcd_ok(npix * (C / 8), C)) ? 2 : 0;
+}
+int udapose_bn_bwd_ex(void* stream, const void* dz, int dz_is_f32, const void* z, const void* y, void* dy, void* gout, size_t npix, int C,
+                      const float* gamma, const float* mean, const float* invstd, int relu, float* slab, float* coef, float* dgamma, float* dbeta,
+                      float beta_acc, const float* beta, int chunked) {
+    if (!dz || !y || !dy || !gamma || !mean || !invstd || !slab || !coef || npix < 1 || C < 8) return UDAPOSE_ERR_ARG;
+    const int rc = pw_bn_bwd(S(stream), dz, dz_is_f32, CB16(z), CB16(y), B16(dy), B16(gout), npix, C, gamma, mean, invstd, relu, slab, coef, dgamma,
+                             dbeta, beta_acc, beta, chunked);
+    return rc != UDAPOSE_OK ? rc : pw_bn_bwd_takes_chunked(npix, C, chunked);
+}
+int udapose_bn_bwd_pre_ex(void* stream, const void* g, int g_is_f32, const void* y, void* dy, size_t npix, int C, const float* gamma,
+                          const float* mean, const float* invstd, const float* slab, int rows, float* coef, float* dgamma, float* dbeta,
+                          float beta_acc, int chunked, int legacy) {
+    if (!g || !y || !dy || !gamma || !mean || !invstd || !slab || !coef || npix < 1 || C < 8) return UDAPOSE_ERR_ARG;
+    const int rc = pw_bn_bwd_pre(S(stream), g, g_is_f32, CB16(y), B16(dy), npix, C, gamma, mean, invstd, slab, rows, coef, dgamma, dbeta, beta_acc,
+                                 chunked, legacy);
+    if (rc != UDAPOSE_OK) return rc;
+    if (pw_bn_bwd_pre_takes_chunked(npix, C, rows, chunked)) return 1 | (((chunked >> 30) & 1) ? 2 : 0);
+    return (!legacy && ((chunked >> 29) & 1) && pw_bn_apply_xcd_ok(npix * (C / 8), C)) ? 2 : 0;
+}
+int udapose_bn_relu_maxpool3x3s2(void* stream, const void* x, void* y, unsigned char* idx, int N, int H, int W, int C, const float* scale,
+                                 const float* shift) {
+    if (!x || !y || !scale || !shift || N < 1 || H < 1 || W < 1 || C < 8) return UDAPOSE_ERR_ARG;
+    return pw_bn_relu_maxpool3x3s2(S(stream), CB16(x), B16(y), idx, N, H, W, C, scale, shift);
+}
+int udapose_bn_bwd_pooled(void* stream, const void* pool_dy, const unsigned char* pool_idx, int H, int W, const void* y, void* dy, size_t npix, int C,
+                          const float* gamma, const float* mean, const float* invstd, float* slab, float* coef, float* dgamma, float* dbeta,
+                          float beta_acc, const float* beta) {
+    if (!pool_dy || !pool_idx || !y || !dy || !gamma || !mean || !invstd || !slab || !coef || H < 1 || W < 1 || npix < 1 || C < 8) return UDAPOSE_ERR_ARG;
+    return pw_bn_bwd_pooled(S(stream), CB16(pool_dy), pool_idx, H, W, CB16(y), B16(dy), npix, C, gamma, mean, invstd, slab, coef, dgamma, dbeta,
+                            beta_acc, beta);
+}
+int udapose_bn_running_update(void* stream, const float* save, int C, float* running_mean, float* running_var, long long* num_batches_tracked,
+                              float momentum) {
+    if (!save || !running_mean || !running_var || C < 1) return UDAPOSE_ERR_ARG;
+    return pw_bn_running_update(S(stream), save, C, running_mean, running_var, num_batches_tracked, momentum);
+}
+int udapose_bn_running_update_multi(void* stream, const void* d_jobs, int njobs, int max_c, const void* act, float momentum) {
+    if (!d_jobs || !act || njobs < 1 || max_c < 1) return UDAPOSE_ERR_ARG;
+    return pw_bn_running_update_multi(S(stream), (const BnRunJob*)d_jobs, njobs, max_c, act, momentum);
+}
+int udapose_maxpool3x3s2_fwd_ex(void* stream, int kind, const void* x, void* y, unsigned char* idx, int N, int H, int W, int C, void* y16) {
+    if (!x || !y || N < 1 || H < 1 || W < 1 || C < 8 || C % 8 || kind < 0 || kind > 3 || (kind == 3) != (y16 != nullptr)) return UDAPOSE_ERR_ARG;
+    if (kind == 3 && UDAPOSE_ELEM_KIND != 1) return UDAPOSE_ERR_UNSUPPORTED;
+    if (kind == 0) return pw_maxpool3x3s2_fwd(S(stream), CB16(x), B16(y), idx, N, H, W, C);
+    if (kind == 1) return pw_maxpool3x3s2_fwd_f32(S(stream), (const float*)x, (float*)y, idx, N, H, W, C);
+    return pw_maxpool3x3s2_fwd_split(S(stream), x, y, idx, N, H, W, C, y16);
 }
 int udapose_maxpool3x3s2_fwd(void* stream, const void* x, void* y, unsigned char* idx, int N, int H, int W, int C) {
     return pw_maxpool3x3s2_fwd(S(stream), CB16(x), B16(y), idx, N, H, W, C);

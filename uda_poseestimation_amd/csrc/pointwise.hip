@@ -1079,7 +1079,10 @@ __global__ void maxpool2x2_ceil_k(const T* __restrict__ x, T* __restrict__ y, in
                     float v[8];
                     ld8<T>(x + (((size_t)n * H + h) * W + w) * C + g * 8, v);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) best[e] = fmaxf(best[e], v[e]);
+                    for (int e = 0; e < 8; ++e) {
+                        const float f = v[e];
+                        if (f > best[e] || f != f) best[e] = f;     // (a NaN wins, as in maxpool3x3s2_fwd_k and ATen; fmaxf would drop it)
+                    }
                 }
             }
         st8<T>(y + i * 8, best);
@@ -1381,12 +1384,17 @@ static int bn_apply_grid(size_t n8, int C) {
     }
     return g;
 }
+// XCD-aligned rows in bn_apply_k / bn_bwd_apply_pre_k: needs whole rows per block pass, a grid that is a multiple of the 8 XCDs and enough
+// rows to give every XCD work (n8 = 16-byte groups of the tensor)
+int pw_bn_apply_xcd_ok(size_t n8, int C) {
+    const int grid = bn_apply_grid(n8, C), G = C / 8;
+    return (TPB % G) == 0 && (grid % 8) == 0 && (n8 / G) >= (size_t)8 * (TPB / G);
+}
 int pw_bn_apply(hipStream_t s, const elem_t* y, const elem_t* res, elem_t* z, size_t n, int C, const float* scale, const float* shift, int relu,
                 unsigned char* mask, int xcd) {
     if (C % 8 || n % 8) return UDAPOSE_ERR_ARG;
-    const int grid = bn_apply_grid(n / 8, C), G = C / 8;
-    // (XCD-aligned rows: needs whole rows per block pass, a grid that is a multiple of the 8 XCDs and enough rows to give every XCD work)
-    const int ok = xcd && (TPB % G) == 0 && (grid % 8) == 0 && (n / 8 / G) >= (size_t)8 * (TPB / G);
+    const int grid = bn_apply_grid(n / 8, C);
+    const int ok = xcd && pw_bn_apply_xcd_ok(n / 8, C);
     hipLaunchKernelGGL(bn_apply_k<elem_t>, dim3(grid), dim3(TPB), 0, s, y, res, z, n / 8, C, scale, shift, relu, mask, ok);
     return udapose_check_launch();
 }
@@ -1396,8 +1404,8 @@ int pw_bn_apply_split(hipStream_t s, const float* y, const void* res, void* z, s
                       void* y16, void* z16, unsigned char* mask, int xcd) {
     if (C % 8 || n % 8) return UDAPOSE_ERR_ARG;
     if (y16) {
-        const int grid = bn_apply_grid(n / 8, C), G = C / 8;
-        const int ok = xcd && (TPB % G) == 0 && (grid % 8) == 0 && (n / 8 / G) >= (size_t)8 * (TPB / G);
+        const int grid = bn_apply_grid(n / 8, C);
+        const int ok = xcd && pw_bn_apply_xcd_ok(n / 8, C);
         hipLaunchKernelGGL((bn_apply_k<sp32, float, true>), dim3(grid), dim3(TPB), 0, s, y, (const sp32*)res, (sp32*)z, n / 8, C, scale, shift, relu, mask,
                            ok, (_Float16*)y16, (_Float16*)z16);
         return udapose_check_launch();
@@ -1415,6 +1423,11 @@ int pw_bn_bwd_rows(size_t npix) {
     // upper bound used to size the scratch slab; the launch picks rows = min(1024, ceil(npix / pixels-per-iteration))
     return (int)(npix < 1024 ? (npix < 1 ? 1 : npix) : 1024);
 }
+// the layers the channel-chunked backward forms take (wide, small-spatial; the pre-reduced form also needs a slab of <= 128 rows)
+int pw_bn_bwd_takes_chunked(size_t npix, int C, int chunked) { return chunked && C >= 256 && npix <= 32768 && npix >= 1024; }
+int pw_bn_bwd_pre_takes_chunked(size_t npix, int C, int rows, int chunked) {
+    return pw_bn_bwd_takes_chunked(npix, C, chunked & ~(3 << 29)) && rows <= 128;
+}
 int pw_bn_bwd(hipStream_t s, const void* dz, int dz_is_f32, const elem_t* z, const elem_t* y, elem_t* dy, elem_t* gout, size_t npix, int C,
               const float* gamma, const float* mean, const float* invstd, int relu, float* slab, float* coef, float* dgamma, float* dbeta,
               float beta_acc, const float* beta, int chunked) {
@@ -1423,7 +1436,7 @@ int pw_bn_bwd(hipStream_t s, const void* dz, int dz_is_f32, const elem_t* z, con
     if (relu == 1 && !z) return UDAPOSE_ERR_ARG;
     const int G = C / 8;
     if (C % 8 || G > 256 || (G & (G - 1))) return UDAPOSE_ERR_UNSUPPORTED;
-    if (chunked && C >= 256 && npix <= 32768 && npix >= 1024) {
+    if (pw_bn_bwd_takes_chunked(npix, C, chunked)) {
         // channel-chunked form without a finalize launch (see bn_bwd_reduce_chunk_k)
         const int chunks = C / 64;
         int S = 1024 / chunks;
@@ -1472,7 +1485,7 @@ int pw_bn_bwd_pre(hipStream_t s, const void* g, int g_is_f32, const elem_t* y, e
     const int xcd = (chunked >> 30) & 1, xcd_stream = (chunked >> 29) & 1;     // (bit 30: XCD-aligned pixel ranges in the chunked form; bit 29: in the streaming form too)
     chunked &= ~(3 << 29);
     const int skip_finalize = 0;
-    if (chunked && C >= 256 && npix <= 32768 && npix >= 1024 && rows <= 128) {
+    if (pw_bn_bwd_pre_takes_chunked(npix, C, rows, chunked)) {
         const int chunks = C / 64;
         int S = (chunked > 1 ? chunked : 1024) / chunks;
         if (S > 64) S = 64;
@@ -1501,7 +1514,7 @@ int pw_bn_bwd_pre(hipStream_t s, const void* g, int g_is_f32, const elem_t* y, e
         return udapose_check_launch();
     }
     const int grid = bn_apply_grid(npix * G, C);
-    const int ok = xcd_stream && (TPB % G) == 0 && (grid % 8) == 0 && npix >= (size_t)8 * (TPB / G);
+    const int ok = xcd_stream && pw_bn_apply_xcd_ok(npix * G, C);
     if (g_is_f32)
         hipLaunchKernelGGL(bn_bwd_apply_pre_k<float>, dim3(grid), dim3(TPB), 0, s, (const float*)g, y, dy, npix * G, C, mean, invstd, coef, ok);
     else

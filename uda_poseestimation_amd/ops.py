@@ -216,6 +216,59 @@ def bn_bwd_pre(g, y, gamma, mean, invstd, slab):
     return dy, dgamma, dbeta
 
 
+# ---- every BatchNorm / pooling form by explicit selectors (udapose_*_ex): the caller owns every tensor, outputs included, so that a test
+# can place them inside guarded allocations; each returns the library's form code (bit 0: chunked form, bit 1: XCD row mapping)
+BN_KINDS = {"16bit": 0, "f32": 1, "split": 2, "strict": 3}
+
+
+def _form(code, what):
+    if code < 0:
+        check(code, what)
+    return code
+
+
+def bn_train_fwd_ex(kind, y, z, slab, gamma, beta, scale, shift, save, res=None, pre_bias=None, running_mean=None, running_var=None, nbt=None,
+                    momentum=0.1, eps=1e-5, relu=True, fwd_chunked=1, xcd_rows=1, mask=None, y16=None, z16=None, build=None):
+    """Finalize + apply of one training-mode layer (udapose_bn_train_fwd_ex).  y [npix, C] in the kind's storage; count = npix."""
+    npix, C_ = y.shape
+    L = lib(build) if build else lib_for(y, z)
+    return _form(L.udapose_bn_train_fwd_ex(stream(), BN_KINDS[kind], ptr(y), ptr(res), ptr(z), npix, C_, ptr(slab), slab.shape[0], ptr(gamma),
+                                           ptr(beta), ptr(pre_bias), ptr(running_mean), ptr(running_var), ptr(nbt), momentum, eps, ptr(scale),
+                                           ptr(shift), ptr(save), int(relu), int(fwd_chunked), int(xcd_rows), ptr(mask), ptr(y16), ptr(z16)),
+                 "bn_train_fwd_ex")
+
+
+def bn_bwd_ex(dz, z, y, dy, gamma, mean, invstd, slab, coef, dgamma, dbeta, relu=1, gout=None, beta=None, beta_acc=0.0, chunked=1):
+    npix, C_ = y.shape
+    return _form(lib_for(y).udapose_bn_bwd_ex(stream(), ptr(dz), int(dz.dtype == torch.float32), ptr(z), ptr(y), ptr(dy), ptr(gout), npix, C_,
+                                              ptr(gamma), ptr(mean), ptr(invstd), int(relu), ptr(slab), ptr(coef), ptr(dgamma), ptr(dbeta),
+                                              float(beta_acc), ptr(beta), int(chunked)), "bn_bwd_ex")
+
+
+def bn_bwd_pre_ex(g, y, dy, gamma, mean, invstd, slab, coef, dgamma, dbeta, beta_acc=0.0, chunked=1, legacy=0):
+    npix, C_ = y.shape
+    return _form(lib_for(y).udapose_bn_bwd_pre_ex(stream(), ptr(g), int(g.dtype == torch.float32), ptr(y), ptr(dy), npix, C_, ptr(gamma), ptr(mean),
+                                                  ptr(invstd), ptr(slab), slab.shape[0], ptr(coef), ptr(dgamma), ptr(dbeta), float(beta_acc),
+                                                  int(chunked), int(legacy)), "bn_bwd_pre_ex")
+
+
+def bn_relu_maxpool3x3s2(x, y, idx, scale, shift):
+    N, H, W, C_ = x.shape
+    check(lib_for(x).udapose_bn_relu_maxpool3x3s2(stream(), ptr(x), ptr(y), ptr(idx), N, H, W, C_, ptr(scale), ptr(shift)), "bn_relu_maxpool3x3s2")
+
+
+def bn_bwd_pooled(pool_dy, pool_idx, y, dy, gamma, mean, invstd, beta, slab, coef, dgamma, dbeta, beta_acc=0.0):
+    N, H, W, C_ = y.shape
+    check(lib_for(y).udapose_bn_bwd_pooled(stream(), ptr(pool_dy), ptr(pool_idx), H, W, ptr(y), ptr(dy), N * H * W, C_, ptr(gamma), ptr(mean),
+                                           ptr(invstd), ptr(slab), ptr(coef), ptr(dgamma), ptr(dbeta), float(beta_acc), ptr(beta)), "bn_bwd_pooled")
+
+
+def maxpool3x3s2_fwd_ex(kind, x, y, idx, y16=None, build=None):
+    N, H, W, C_ = x.shape
+    L = lib(build) if build else lib_for(x)
+    check(L.udapose_maxpool3x3s2_fwd_ex(stream(), BN_KINDS[kind], ptr(x), ptr(y), ptr(idx), N, H, W, C_, ptr(y16)), "maxpool3x3s2_fwd_ex")
+
+
 def maxpool3x3s2_fwd(x):
     N, H, W, C_ = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
