@@ -431,6 +431,28 @@ int udapose_net_fused_update(udapose_net_t student, udapose_net_t teacher, void*
  * of a step whose two backward passes ran on different streams; a multiple of 16): the sum udapose_axpy_f32 would have written
  * first, taken in the same sweep.  h_grads itself is left holding the first pass's share. */
 
+/* The same sweep for either optimizer and for parameter groups (PoseResNet.get_parameters(lr): the backbone at a tenth of the rate).
+ * kind: UDAPOSE_OPT_ADAM - h_state1 / h_state2 = exp_avg / exp_avg_sq, (beta1, beta2, eps) - or UDAPOSE_OPT_SGD = torch.optim.SGD with
+ * momentum (train_human.py:136-137) - h_state1 = the momentum buffers, h_state2 is not read (may be NULL), beta1 is the momentum, nesterov
+ * 0 / 1; arithmetic identical to udapose_sgd_multi followed by udapose_ema_multi (bit for bit): 38 bytes per parameter instead of 62
+ * (axpy 12, SGD 20, EMA 12, packs 18).  group_idx[i] (NULL: one group) is the parameter group of parameter i, at most 8 groups
+ * (UDAPOSE_ERR_UNSUPPORTED beyond).  dev_states[g] / weight_decays[g], g < n_groups: every group's 8-float device state (required: lr,
+ * grad_scale, the step counter and found_inf are read from it - for SGD the first step is `counter == 1` after the tick, as in
+ * udapose_sgd_multi) and its weight decay, read when the call is made.  ONE tick launch advances every group's counter.  A found_inf
+ * step neither ticks nor updates; the EMA and the packs still run.  A table bound for SGD never takes over split sums
+ * (udapose_net_wgrad_pair_defer then defers nothing).  Contract as above: bind allocates (outside capture), the update only launches
+ * and returns UDAPOSE_ERR_NOT_PREPARED when the table is stale or was bound for another kind or group count.  One Adam group through
+ * these gives the bits of udapose_net_fused_update. */
+#define UDAPOSE_OPT_ADAM 0
+#define UDAPOSE_OPT_SGD 1
+int udapose_net_bind_update_groups(udapose_net_t student, udapose_net_t teacher, int kind, void* const* h_params_s, void* const* h_grads,
+                                   void* const* h_state1, void* const* h_state2, void* const* h_params_t, void* wpack_s, void* wpack_t,
+                                   const int* group_idx);
+int udapose_net_fused_update_groups(udapose_net_t student, udapose_net_t teacher, void* stream, int kind, void* const* h_params_s,
+                                    void* const* h_grads, void* const* h_state1, void* const* h_params_t, void* wpack_s, void* wpack_t,
+                                    float beta1, float beta2, float eps, int nesterov, int n_groups, float* const* dev_states,
+                                    const float* weight_decays, float alpha, float one_minus_alpha, int do_opt, long long grad2_delta_bytes);
+
 /* Dynamic loss scaling = torch.cuda.amp.GradScaler (train_human.py:260,285-287,324,436-440) on the device, for the fp16 build.
  * dev_state is the optimizer's 8-float state: [5] = found_inf, [6] = loss scale S, [7] = growth tracker, [4] = 1/S.
  * check: raises found_inf if any gradient is inf / nan (then adam_multi / sgd_multi skip the step, counter included);

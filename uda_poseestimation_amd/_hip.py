@@ -111,6 +111,8 @@ _SIGS = {
     "udapose_net_grad_split_param": (ll, [vp]),
     "udapose_net_bind_update": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "udapose_net_fused_update": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, cf, cf, ci, ll]),
+    "udapose_net_bind_update_groups": (ci, [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "udapose_net_fused_update_groups": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, ci, ci, vp, vp, cf, cf, ci, ll]),
     "udapose_joints_mse_fwd": (ci, [vp, vp, vp, vp, ci, ci, vp, vp]),
     "udapose_joints_mse_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, vp]),
     "udapose_cons_loss_fwd": (ci, [vp, vp, vp, vp, ci, ci, vp, vp]),

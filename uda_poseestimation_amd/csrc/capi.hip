@@ -120,6 +120,9 @@ long long net_grad_split_param(void*);
 int net_bind_update(void*, void*, void* const*, void* const*, void* const*, void* const*, void* const*, void*, void*);
 int net_fused_update(void*, void*, hipStream_t, void* const*, void* const*, void* const*, void* const*, void*, void*, float, float, float, float, float,
                      int, float, float*, float, float, int, long long);
+int net_bind_update_groups(void*, void*, int, void* const*, void* const*, void* const*, void* const*, void* const*, void*, void*, const int*);
+int net_fused_update_groups(void*, void*, hipStream_t, int, void* const*, void* const*, void* const*, void* const*, void*, void*, float, float, float, int,
+                            int, float* const*, const float*, float, float, int, long long);
 int net_num_params(void*);
 int net_num_buffers(void*);
 long long net_param_numel(void*, int);
@@ -430,6 +433,21 @@ int udapose_net_fused_update(udapose_net_t student, udapose_net_t teacher, void*
     if (!student || !teacher) return UDAPOSE_ERR_ARG;
     return net_fused_update(student, teacher, S(stream), params_s, grads, exp_avg, params_t, wpack_s, wpack_t, lr, beta1, beta2, eps, weight_decay,
                             step, grad_scale, dev_state, alpha, one_minus_alpha, do_adam, grad2_delta_bytes);
+}
+int udapose_net_bind_update_groups(udapose_net_t student, udapose_net_t teacher, int kind, void* const* params_s, void* const* grads,
+                                   void* const* state1, void* const* state2, void* const* params_t, void* wpack_s, void* wpack_t,
+                                   const int* group_idx) {
+    if (!student || !teacher || !params_s || !grads || !state1 || (kind == UDAPOSE_OPT_ADAM && !state2) || !params_t || !wpack_s || !wpack_t)
+        return UDAPOSE_ERR_ARG;
+    return net_bind_update_groups(student, teacher, kind, params_s, grads, state1, state2, params_t, wpack_s, wpack_t, group_idx);
+}
+int udapose_net_fused_update_groups(udapose_net_t student, udapose_net_t teacher, void* stream, int kind, void* const* params_s,
+                                    void* const* grads, void* const* state1, void* const* params_t, void* wpack_s, void* wpack_t, float beta1,
+                                    float beta2, float eps, int nesterov, int n_groups, float* const* dev_states, const float* weight_decays,
+                                    float alpha, float one_minus_alpha, int do_opt, long long grad2_delta_bytes) {
+    if (!student || !teacher || !params_s || !grads || !state1 || !params_t) return UDAPOSE_ERR_ARG;
+    return net_fused_update_groups(student, teacher, S(stream), kind, params_s, grads, state1, params_t, wpack_s, wpack_t, beta1, beta2, eps, nesterov,
+                                   n_groups, dev_states, weight_decays, alpha, one_minus_alpha, do_opt, grad2_delta_bytes);
 }
 
 int udapose_joints_mse_fwd(void* stream, const float* pred, const float* gt, const float* w, int R, int HW, float* rows, float* mean_out) {

@@ -51,8 +51,10 @@ size_t opt_tail_job_bytes();
 int opt_chunk();
 void opt_tail_job_fill(void*, float*, const float*, float*, float*, float*, void*, void*, void*, void*, int, int, int, int, long long);
 void opt_tail_job_split(void*, long long, unsigned, int);
-int opt_tail(hipStream_t, const void*, const int*, const int*, int, float, float, float, float, float, int, float, float*, float, float, int, long long, int,
-             const void*, const void*);
+void opt_tail_job_group(void*, int);
+int opt_tail_max_groups();
+int opt_tail(hipStream_t, const void*, const int*, const int*, int, int, float, float, float, float, int, int, float, int, float* const*, const float*, float,
+             float, int, long long, int, const void*, const void*);
 int pw_transpose_f32(hipStream_t, const float*, float*, int, int, int);
 int pw_pack_strided_f32(hipStream_t, const float*, float*, int, int, int, int, int, int, long, long, long, long);
 int pw_bn_apply_f32(hipStream_t, const float*, const float*, float*, size_t, int, const float*, const float*, int);
@@ -176,7 +178,8 @@ struct Net {
     // fused optimizer tail (Adam + EMA + weight packs of student and teacher in one sweep): device job table
     struct UpdTab { void* jobs = nullptr; int* blk_job = nullptr; int* blk_sub = nullptr; int nblocks = 0;
                     const void* k_ps = nullptr; const void* k_pt = nullptr; const void* k_g = nullptr; const void* k_m = nullptr;
-                    const void* k_ws = nullptr; const void* k_wt = nullptr; };
+                    const void* k_ws = nullptr; const void* k_wt = nullptr;
+                    int kind = 0, ngroups = 1; };       // (optimizer the table was bound for: 0 Adam, 1 SGD; number of parameter groups)
     UpdTab upd;
     // Split sums left to the optimizer sweep (udapose_net_wgrad_pair_defer): the pair call records the two passes' workspaces and gradient bases
     // here, the next udapose_net_fused_update consumes and clears the mark (its sweep adds the partial tiles itself), udapose_net_split_sum_flush
@@ -1350,9 +1353,20 @@ long long net_grad_split_param(void* h) {
 // plans in one sweep (optim.hip opt_tail_k).  hs / ht: the student's and the teacher's plans (same architecture).
 // h_m / h_v: host arrays of the Adam moments per parameter index, NULL entries for parameters without gradient (backbone.fc:
 // EMA only).  bind builds the device job table (allocates: outside capture); the update itself only launches.
-int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grads, void* const* h_m, void* const* h_v, void* const* params_t,
-                    void* wpack_s_, void* wpack_t_) {
+// kind 1 (SGD with momentum): h_m holds the momentum buffers, h_v is not read.  group_idx (NULL: one group): the parameter group of every
+// parameter, at most opt_tail_max_groups() of them.
+int net_bind_update_groups(void* hs, void* ht, int kind, void* const* params_s, void* const* grads, void* const* h_m, void* const* h_v,
+                           void* const* params_t, void* wpack_s_, void* wpack_t_, const int* group_idx) {
     Net& n = *(Net*)hs;
+    if (kind != 0 && kind != 1) return UDAPOSE_ERR_ARG;
+    if (kind == 0 && !h_v) return UDAPOSE_ERR_ARG;
+    int ngroups = 1;
+    if (group_idx)
+        for (int i = 0; i < n.n_params; ++i) {
+            if (group_idx[i] < 0) return UDAPOSE_ERR_ARG;
+            if (group_idx[i] >= opt_tail_max_groups()) return UDAPOSE_ERR_UNSUPPORTED;
+            ngroups = std::max(ngroups, group_idx[i] + 1);
+        }
     const Net& nt = *(const Net*)ht;
     // teacher in the f16x2 mode (the reference's precision mix: fp16 student, fp32-grade teacher): its split packs are not written
     // by this sweep (the caller re-packs the teacher's plan with udapose_net_pack_weights after it), the EMA still is
@@ -1370,19 +1384,22 @@ int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grad
     std::vector<char> covered(n.n_params, 0);
     // the split jobs of these gradient tensors' weight-gradient table (overwriting whole backward, current policy), if it is bound already: a job
     // whose gradient is split carries where the partial tensors lie, so that a sweep can add them itself (udapose_net_wgrad_pair_defer)
-    const Net::WgGroup* SG = grads[0] ? find_wg_group(n, grads, 0.f, 0) : nullptr;
+    // (the sweep that adds split sums itself has no SGD form: a table bound for SGD never offers it, and udapose_net_wgrad_pair_defer defers nothing)
+    const Net::WgGroup* SG = grads[0] && kind == 0 ? find_wg_group(n, grads, 0.f, 0) : nullptr;
     if (SG && (!SG->k_det || SG->n_sum_blk <= SG->n_sum_ws_blk)) SG = nullptr;
     size_t split_found = 0;
     auto push = [&](int idx, void* sd, void* td, void* sx, void* tx, int A, int T, int B) -> int {
         const long long numel = n.param_numel[idx];
-        const int adam = (h_m[idx] && h_v[idx] && grads[idx]) ? 1 : 0;
+        void* const v_idx = kind == 0 ? h_v[idx] : nullptr;
+        const int adam = (h_m[idx] && (kind == 1 || v_idx) && grads[idx]) ? 1 : 0;
         if (A) {
-            const uintptr_t al = (uintptr_t)params_s[idx] | (uintptr_t)params_t[idx] | (adam ? ((uintptr_t)grads[idx] | (uintptr_t)h_m[idx] | (uintptr_t)h_v[idx]) : 0);
+            const uintptr_t al = (uintptr_t)params_s[idx] | (uintptr_t)params_t[idx] | (adam ? ((uintptr_t)grads[idx] | (uintptr_t)h_m[idx] | (uintptr_t)v_idx) : 0);
             if ((al & 15) || (A & 63) || (B & 63) || (long long)A * T * B != numel) return UDAPOSE_ERR_UNSUPPORTED;
         }
         jobs.resize(jobs.size() + jb);
-        opt_tail_job_fill(jobs.data() + jobs.size() - jb, (float*)params_s[idx], (const float*)grads[idx], (float*)h_m[idx], (float*)h_v[idx],
+        opt_tail_job_fill(jobs.data() + jobs.size() - jb, (float*)params_s[idx], (const float*)grads[idx], (float*)h_m[idx], (float*)v_idx,
                           (float*)params_t[idx], sd, td, sx, tx, A, T, B, adam, numel);
+        opt_tail_job_group(jobs.data() + jobs.size() - jb, group_idx ? group_idx[idx] : 0);
         if (SG && adam)
             for (const SumJob& sj : SG->h_sum)
                 if (!sj.dst_ws && sj.dst_off == (const char*)grads[idx] - (const char*)grads[0]) {
@@ -1430,25 +1447,33 @@ int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grad
     if (hipMemcpy(u.blk_sub, bs.data(), bs.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
     u.nblocks = (int)bj.size();
     u.k_ps = params_s[0]; u.k_pt = params_t[0]; u.k_g = grads[0]; u.k_m = h_m[0]; u.k_ws = wpack_s_; u.k_wt = wpack_t_;
+    u.kind = kind; u.ngroups = ngroups;
     n.upd_sum_group = SG;
     return UDAPOSE_OK;
 }
+int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grads, void* const* h_m, void* const* h_v, void* const* params_t,
+                    void* wpack_s_, void* wpack_t_) {
+    return net_bind_update_groups(hs, ht, 0, params_s, grads, h_m, h_v, params_t, wpack_s_, wpack_t_, nullptr);
+}
 
-int net_fused_update(void* hs, void* ht, hipStream_t s, void* const* params_s, void* const* grads, void* const* h_m, void* const* params_t,
-                     void* wpack_s_, void* wpack_t_, float lr, float beta1, float beta2, float eps, float wd, int step, float gscale,
-                     float* dev_state, float alpha, float oma, int do_adam, long long grad2_delta) {
+namespace {
+// lr / step / gscale: the host's values, read only where states[0] is NULL (one Adam group without device state)
+int fused_update(void* hs, void* ht, hipStream_t s, int kind, void* const* params_s, void* const* grads, void* const* h_m, void* const* params_t,
+                 void* wpack_s_, void* wpack_t_, float lr, float beta1, float beta2, float eps, int nesterov, int step, float gscale, int ngroups,
+                 float* const* states, const float* wds, float alpha, float oma, int do_adam, long long grad2_delta) {
     Net& n = *(Net*)hs;
     const Net& nt = *(const Net*)ht;
     DbgSyncScope dbg(n.policy.debug_sync);
     const Net::UpdTab& u = n.upd;
-    if (!u.jobs || u.k_ps != params_s[0] || u.k_pt != params_t[0] || u.k_g != grads[0] || u.k_m != h_m[0] || u.k_ws != wpack_s_ || u.k_wt != wpack_t_)
+    if (!u.jobs || u.k_ps != params_s[0] || u.k_pt != params_t[0] || u.k_g != grads[0] || u.k_m != h_m[0] || u.k_ws != wpack_s_ || u.k_wt != wpack_t_ ||
+        u.kind != kind || u.ngroups != ngroups)
         return UDAPOSE_ERR_NOT_PREPARED;
     // split sums a pair call left to this sweep: it must be the sweep of exactly those two gradient buffers
     const Net::Deferred d = n.deferred;
     if (d.G && (d.G != n.upd_sum_group || d.gA != (char*)grads[0] || grad2_delta != (long long)(d.gB - d.gA))) return UDAPOSE_ERR_NOT_PREPARED;
     n.deferred = Net::Deferred{};
-    CK(opt_tail(s, u.jobs, u.blk_job, u.blk_sub, u.nblocks, lr, beta1, beta2, eps, wd, step, gscale, dev_state, alpha, oma, do_adam, grad2_delta, 1,
-                d.G ? d.wsA : nullptr, d.G ? d.wsB : nullptr));
+    CK(opt_tail(s, u.jobs, u.blk_job, u.blk_sub, u.nblocks, kind, lr, beta1, beta2, eps, nesterov, step, gscale, ngroups, states, wds, alpha, oma, do_adam,
+                grad2_delta, 1, d.G ? d.wsA : nullptr, d.G ? d.wsB : nullptr));
     // the two packs that are not a cast or a per-tap transpose of a whole tensor: the stem's 3 -> 8 channel gather (both
     // networks) and the head's zero-padded dgrad pack (student)
     if (n.strict)   // 'strict' student: its split forward packs (stem included) from the updated weights, one pack launch (net_bind's table)
@@ -1458,4 +1483,23 @@ int net_fused_update(void* hs, void* ht, hipStream_t s, void* const* params_s, v
     if (nt.f32 != 2) CK(pack_conv(s, nt, nt.stem, (const void* const*)params_t, (char*)wpack_t_, false));
     CK(pw_pack_strided(s, (const float*)params_s[n.head.w_idx], (elem_t*)((char*)wpack_s_ + n.head.wb_off), 256, 1, 1, 1, 64, n.K, 1, 0, 0, 256));
     return UDAPOSE_OK;
+}
+}  // namespace
+
+int net_fused_update(void* hs, void* ht, hipStream_t s, void* const* params_s, void* const* grads, void* const* h_m, void* const* params_t,
+                     void* wpack_s_, void* wpack_t_, float lr, float beta1, float beta2, float eps, float wd, int step, float gscale,
+                     float* dev_state, float alpha, float oma, int do_adam, long long grad2_delta) {
+    return fused_update(hs, ht, s, 0, params_s, grads, h_m, params_t, wpack_s_, wpack_t_, lr, beta1, beta2, eps, 0, step, gscale, 1, &dev_state, &wd, alpha,
+                        oma, do_adam, grad2_delta);
+}
+// kind 0: Adam (beta1, beta2, eps); kind 1: SGD (beta1 = momentum, nesterov).  Every group's device state is required: lr, grad_scale, the counter
+// and the found-inf mark are read from it.
+int net_fused_update_groups(void* hs, void* ht, hipStream_t s, int kind, void* const* params_s, void* const* grads, void* const* h_m,
+                            void* const* params_t, void* wpack_s_, void* wpack_t_, float beta1, float beta2, float eps, int nesterov, int ngroups,
+                            float* const* states, const float* wds, float alpha, float oma, int do_opt, long long grad2_delta) {
+    if (ngroups < 1 || ngroups > opt_tail_max_groups() || !states || !wds) return UDAPOSE_ERR_ARG;
+    for (int g = 0; g < ngroups; ++g)
+        if (!states[g]) return UDAPOSE_ERR_ARG;
+    return fused_update(hs, ht, s, kind, params_s, grads, h_m, params_t, wpack_s_, wpack_t_, 0.f, beta1, beta2, eps, nesterov, 0, 1.f, ngroups, states, wds,
+                        alpha, oma, do_opt, grad2_delta);
 }

@@ -179,11 +179,31 @@ struct TailJob {
     // a gradient whose pixel reduction was split (net.hip make_partial): `ks` partial tensors in the gradient's own layout, `stride` floats apart,
     // at byte offset part_off of a pass's workspace (ks == 0: not split)
     long long part_off; unsigned stride; int ks;
+    int group;                                                  // parameter group: index into TailGroups
 };
 
 // g2: byte distance to a second gradient buffer (0: none).  ws1 / ws2 (SPLIT sweeps): the workspaces of the two passes whose split sums were left to
 // this sweep (udapose_net_wgrad_pair_defer): a split job's g and g + g2 are then NOT read - the sweep adds the partial tensors itself.
-struct TailHyper { float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, gscale, alpha, oma; int do_adam; long long g2; const char* ws1; const char* ws2; };
+// An SGD sweep (KIND_SGD) keeps its momentum buffer in TailJob.m, leaves v alone, and reads beta1 as the momentum.
+struct TailHyper { float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, gscale, alpha, oma; int do_adam; long long g2; const char* ws1; const char* ws2;
+                   int nesterov, first; };
+// Parameter groups (PoseResNet.get_parameters: the backbone at a tenth of the rate): a job reads lr - and for Adam the bias corrections -
+// from its group's 8-float device state and weight_decay from this table, passed by value.  state[g] == NULL: the by-value TailHyper holds.
+constexpr int TAIL_GROUPS = 8;
+struct TailGroups { const float* state[TAIL_GROUPS]; float wd[TAIL_GROUPS]; };
+enum { KIND_ADAM = 0, KIND_SGD = 1 };
+// one launch advances every group's counter (adam_tick_k / sgd_tick_k per group, one thread each)
+__global__ void tail_tick_k(TailGroups G, int ngroups, int kind, float beta1, float beta2) {
+    const int g = threadIdx.x;
+    if (g >= ngroups) return;
+    float* state = const_cast<float*>(G.state[g]);
+    if (state[5] != 0.f) return;
+    if (kind == KIND_SGD) { state[0] += 1.f; return; }
+    const double t = (double)state[0] + 1.0;
+    state[0] = (float)t;
+    state[1] = (float)(1.0 - pow((double)beta1, t));
+    state[2] = (float)sqrt(1.0 - pow((double)beta2, t));
+}
 
 // the split sum of pointwise.hip's split_sum_k for an overwriting pass (beta = 0), expression for expression: ((p0 + p1) + p2) + ... in split order
 __device__ __forceinline__ float split_sum1(const float* __restrict__ part, size_t e, unsigned stride, int ks) {
@@ -198,8 +218,17 @@ __device__ __forceinline__ f32x4 split_sum4(const float* __restrict__ part, size
     return a;
 }
 
+template <int KIND>
 __device__ __forceinline__ void tail1(const TailHyper& h, bool adam, float& pv, float gr, float& mi, float& vi, float& tv) {
-    if (adam) {
+    if (KIND == KIND_SGD) {
+        if (adam) {                     // sgd_k, expression for expression (mi: the momentum buffer)
+            gr = gr * h.gscale + h.wd * pv;
+            const float b = h.first ? gr : mi * h.beta1 + gr;
+            mi = b;
+            gr = h.nesterov ? gr + h.beta1 * b : b;
+            pv -= h.lr * gr;
+        }
+    } else if (adam) {
         gr *= h.gscale;
         if (h.wd != 0.f) gr += h.wd * pv;
         mi = mi * h.beta1 + (1.f - h.beta1) * gr;
@@ -209,25 +238,30 @@ __device__ __forceinline__ void tail1(const TailHyper& h, bool adam, float& pv, 
     tv = ema1(tv, pv, h.alpha, h.oma);
 }
 
+// KIND: the optimizer (Adam / SGD with momentum), a template parameter so that the Adam instantiations stay what they were.
 // SPLIT: the sweep that also takes over the split sums of the two passes (h.ws1 / h.ws2 set); the plain sweep is its own instantiation and
 // keeps its registers.
-template <bool SPLIT>
+template <int KIND, bool SPLIT>
 __global__ __launch_bounds__(TPB) void opt_tail_k(const TailJob* __restrict__ jobs, const int* __restrict__ blk_job, const int* __restrict__ blk_sub,
-                                                  TailHyper h, const float* __restrict__ dev_state) {
+                                                  TailHyper h, TailGroups G) {
     __shared__ elem_t ts[64][66], tt[64][66];
-    if (dev_state) {
-        h.bc1 = dev_state[1]; h.bc2_sqrt = dev_state[2]; h.lr = dev_state[3]; h.gscale = dev_state[4];
-        if (dev_state[5] != 0.f) h.do_adam = 0;          // inf / nan gradients: the optimizer step is skipped, the EMA is not
-    }
     const TailJob j = jobs[blk_job[blockIdx.x]];
     const int sub = blk_sub[blockIdx.x];
+    const float* __restrict__ dev_state = G.state[j.group];
+    h.wd = G.wd[j.group];
+    if (dev_state) {
+        if (KIND == KIND_SGD) h.first = dev_state[0] == 1.f;        // (after the tick: torch initialises the buffer with the first gradient)
+        else { h.bc1 = dev_state[1]; h.bc2_sqrt = dev_state[2]; }
+        h.lr = dev_state[3]; h.gscale = dev_state[4];
+        if (dev_state[5] != 0.f) h.do_adam = 0;          // inf / nan gradients: the optimizer step is skipped, the EMA is not
+    }
     const bool adam = j.adam && h.do_adam;
     if (j.A == 0) {
         const long long off = (long long)sub * CHUNK;
         const long long end = off + CHUNK < j.n ? off + CHUNK : j.n;
         for (long long i = off + threadIdx.x; i < end; i += TPB) {
             float pv = j.p[i], tv = j.t[i], mi = 0.f, vi = 0.f;
-            if (adam) { mi = j.m[i]; vi = j.v[i]; }
+            if (adam) { mi = j.m[i]; if (KIND == KIND_ADAM) vi = j.v[i]; }
             float gr = 0.f;
             if (SPLIT && adam && j.ks) {          // (each pass's split sum as split_sum_k forms it, then g1 + g2 as below)
                 gr = split_sum1((const float*)(h.ws1 + j.part_off), (size_t)i, j.stride, j.ks);
@@ -236,8 +270,8 @@ __global__ __launch_bounds__(TPB) void opt_tail_k(const TailJob* __restrict__ jo
                 gr = j.g[i];
                 if (h.g2) gr += *(const float*)((const char*)(j.g + i) + h.g2);      // (the two passes' gradients: g1 + g2 as axpy would)
             }
-            tail1(h, adam, pv, gr, mi, vi, tv);
-            if (adam) { j.p[i] = pv; j.m[i] = mi; j.v[i] = vi; }
+            tail1<KIND>(h, adam, pv, gr, mi, vi, tv);
+            if (adam) { j.p[i] = pv; j.m[i] = mi; if (KIND == KIND_ADAM) j.v[i] = vi; }
             j.t[i] = tv;
             if (j.sd) j.sd[i] = (elem_t)pv;
             if (j.td) j.td[i] = (elem_t)tv;
@@ -255,7 +289,8 @@ __global__ __launch_bounds__(TPB) void opt_tail_k(const TailJob* __restrict__ jo
         f32x4 pv = *(const f32x4*)(j.p + idx), tv = *(const f32x4*)(j.t + idx);
         f32x4 mi = {0.f, 0.f, 0.f, 0.f}, vi = mi, gr = mi;
         if (adam) {
-            mi = *(const f32x4*)(j.m + idx); vi = *(const f32x4*)(j.v + idx);
+            mi = *(const f32x4*)(j.m + idx);
+            if (KIND == KIND_ADAM) vi = *(const f32x4*)(j.v + idx);
             if (SPLIT && j.ks) {
                 gr = split_sum4((const float*)(h.ws1 + j.part_off), idx, j.stride, j.ks);
                 const f32x4 g2 = split_sum4((const float*)(h.ws2 + j.part_off), idx, j.stride, j.ks);
@@ -268,10 +303,10 @@ __global__ __launch_bounds__(TPB) void opt_tail_k(const TailJob* __restrict__ jo
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float p1 = pv[e], m1 = mi[e], v1 = vi[e], t1 = tv[e];
-            tail1(h, adam, p1, gr[e], m1, v1, t1);
+            tail1<KIND>(h, adam, p1, gr[e], m1, v1, t1);
             pv[e] = p1; mi[e] = m1; vi[e] = v1; tv[e] = t1;
         }
-        if (adam) { *(f32x4*)(j.p + idx) = pv; *(f32x4*)(j.m + idx) = mi; *(f32x4*)(j.v + idx) = vi; }
+        if (adam) { *(f32x4*)(j.p + idx) = pv; *(f32x4*)(j.m + idx) = mi; if (KIND == KIND_ADAM) *(f32x4*)(j.v + idx) = vi; }
         *(f32x4*)(j.t + idx) = tv;
         const elem4 ps = {(elem_t)pv[0], (elem_t)pv[1], (elem_t)pv[2], (elem_t)pv[3]};
         const elem4 pt = {(elem_t)tv[0], (elem_t)tv[1], (elem_t)tv[2], (elem_t)tv[3]};
@@ -297,7 +332,7 @@ size_t opt_tail_job_bytes() { return sizeof(TailJob); }
 // host-side filler of one table entry (net.hip builds the table: it knows the pack offsets)
 void opt_tail_job_fill(void* dst, float* p, const float* g, float* m, float* v, float* t, void* sd, void* td, void* sx, void* tx, int A, int T, int B,
                        int adam, long long n) {
-    TailJob j{p, g, m, v, t, (elem_t*)sd, (elem_t*)td, (elem_t*)sx, (elem_t*)tx, A, T, B, adam, n, 0, 0u, 0};
+    TailJob j{p, g, m, v, t, (elem_t*)sd, (elem_t*)td, (elem_t*)sx, (elem_t*)tx, A, T, B, adam, n, 0, 0u, 0, 0};
     *(TailJob*)dst = j;
 }
 // ... and where its gradient's partial tensors lie, when the weight-gradient launches split its pixel reduction
@@ -305,20 +340,35 @@ void opt_tail_job_split(void* dst, long long part_off, unsigned stride, int ks) 
     TailJob& j = *(TailJob*)dst;
     j.part_off = part_off; j.stride = stride; j.ks = ks;
 }
+void opt_tail_job_group(void* dst, int group) { ((TailJob*)dst)->group = group; }
+int opt_tail_max_groups() { return TAIL_GROUPS; }
+// kind: 0 = Adam, 1 = SGD (beta1 is then the momentum; beta2 / eps unused).  states[g] / wds[g]: the 8-float device state and the weight decay of
+// parameter group g, ngroups <= 8.  Either every state is given (lr, grad_scale, counter and found-inf are read from it; SGD needs that) or none
+// (one group, Adam: `lr`, `step`, `gscale` are the host's).
 // tick: advance the device-side step counter / bias corrections in front of the sweep (once per optimizer step: a step whose sweep is
 // issued in two parts ticks with the first)
-int opt_tail(hipStream_t s, const void* d_jobs, const int* blk_job, const int* blk_sub, int nblocks, float lr, float beta1, float beta2, float eps,
-             float wd, int step, float gscale, float* dev_state, float alpha, float oma, int do_adam, long long grad2_delta, int tick,
-             const void* split_ws1, const void* split_ws2) {
+int opt_tail(hipStream_t s, const void* d_jobs, const int* blk_job, const int* blk_sub, int nblocks, int kind, float lr, float beta1, float beta2,
+             float eps, int nesterov, int step, float gscale, int ngroups, float* const* states, const float* wds, float alpha, float oma, int do_adam,
+             long long grad2_delta, int tick, const void* split_ws1, const void* split_ws2) {
     if (grad2_delta % 16) return UDAPOSE_ERR_ARG;
     if ((split_ws1 == nullptr) != (split_ws2 == nullptr)) return UDAPOSE_ERR_ARG;
+    if ((kind != KIND_ADAM && kind != KIND_SGD) || ngroups < 1 || ngroups > TAIL_GROUPS || !states || !wds) return UDAPOSE_ERR_ARG;
+    if (kind == KIND_SGD && split_ws1) return UDAPOSE_ERR_UNSUPPORTED;        // (the SPLIT sweep has no SGD form)
+    TailGroups G{};
+    int with_state = 0;
+    for (int g = 0; g < ngroups; ++g) { G.state[g] = states[g]; G.wd[g] = wds[g]; with_state += states[g] != nullptr; }
+    if (with_state != 0 && with_state != ngroups) return UDAPOSE_ERR_ARG;
+    if (!with_state && (ngroups != 1 || kind == KIND_SGD)) return UDAPOSE_ERR_ARG;
     double bc1 = 1.0, bc2 = 1.0;
-    if (dev_state) { if (do_adam && tick) hipLaunchKernelGGL(adam_tick_k, dim3(1), dim3(1), 0, s, dev_state, beta1, beta2); }
+    if (with_state) { if (do_adam && tick) hipLaunchKernelGGL(tail_tick_k, dim3(1), dim3(TAIL_GROUPS), 0, s, G, ngroups, kind, beta1, beta2); }
     else { bc1 = 1.0 - pow((double)beta1, (double)step); bc2 = 1.0 - pow((double)beta2, (double)step); }
     if (nblocks <= 0) return UDAPOSE_OK;
-    TailHyper h{lr, beta1, beta2, eps, wd, (float)bc1, (float)sqrt(bc2), gscale, alpha, oma, do_adam, grad2_delta, (const char*)split_ws1, (const char*)split_ws2};
-    if (split_ws1) hipLaunchKernelGGL(opt_tail_k<true>, dim3(nblocks), dim3(TPB), 0, s, (const TailJob*)d_jobs, blk_job, blk_sub, h, dev_state);
-    else hipLaunchKernelGGL(opt_tail_k<false>, dim3(nblocks), dim3(TPB), 0, s, (const TailJob*)d_jobs, blk_job, blk_sub, h, dev_state);
+    TailHyper h{lr, beta1, beta2, eps, wds[0], (float)bc1, (float)sqrt(bc2), gscale, alpha, oma, do_adam, grad2_delta, (const char*)split_ws1, (const char*)split_ws2,
+                nesterov, 0};
+    const dim3 grid(nblocks), block(TPB);
+    if (kind == KIND_SGD) hipLaunchKernelGGL((opt_tail_k<KIND_SGD, false>), grid, block, 0, s, (const TailJob*)d_jobs, blk_job, blk_sub, h, G);
+    else if (split_ws1) hipLaunchKernelGGL((opt_tail_k<KIND_ADAM, true>), grid, block, 0, s, (const TailJob*)d_jobs, blk_job, blk_sub, h, G);
+    else hipLaunchKernelGGL((opt_tail_k<KIND_ADAM, false>), grid, block, 0, s, (const TailJob*)d_jobs, blk_job, blk_sub, h, G);
     return udapose_check_launch();
 }
 int opt_grad_check(hipStream_t s, const long long* g, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks,

@@ -199,8 +199,11 @@ class MeanTeacherTrainer:
                  heatmap_size=64, use_sgd=False, style_net=None, recover=None, s2t_freq=0.5, t2s_freq=0.5, s2t_alpha=(0.0, 1.0),
                  t2s_alpha=(0.0, 1.0), rng=None, occlude_rate=-1.0, occlude_thresh=0.9, occlude_size=10, image_px=None, precision=None,
                  loss_scale_init=65536.0, loss_scale_interval=2000, grad_comm="fp32", criterion=None, con_criterion=None, ent_criterion=None,
-                 lambda_ent=0.0, warp_mode="nearest"):
-        """warp_mode: "nearest" (the reference's) or "bilinear" - the interpolation of the two heat-map re-warps of a step: the teacher's
+                 lambda_ent=0.0, params=None, warp_mode="nearest"):
+        """params: what the student's optimizer is built from - an iterable of parameters or of group dicts, e.g.
+        student.get_parameters(lr) (pose_resnet.py:572-577: the backbone at a tenth of the rate when finetune=True); None:
+        student.parameters().  Group dicts carry their own lr; dynamic loss scaling needs a single group.
+        warp_mode: "nearest" (the reference's) or "bilinear" - the interpolation of the two heat-map re-warps of a step: the teacher's
         views before their mean, and the student's y_t_stu_recon (under autograd).  The occlusion path's IMAGE warps stay nearest in either
         mode: they paste patches at integer boxes and are not under autograd."""
         if warp_mode not in warp.MODES:
@@ -252,10 +255,11 @@ class MeanTeacherTrainer:
         if hasattr(tea_m, "aux_lib_kind"):
             tea_m.aux_lib_kind = "fp16" if sp in ("fp16", "strict") else "bf16"
         sc = dict(dynamic_loss_scale=True, init_scale=loss_scale_init, growth_interval=loss_scale_interval) if scaled else {}
+        opt_params = params if params is not None else student.parameters()
         if use_sgd:
-            self.stu_optimizer = fused_optim.FusedSGD(student.parameters(), lr=lr, momentum=0.9, weight_decay=1e-4, nesterov=True, **sc)
+            self.stu_optimizer = fused_optim.FusedSGD(opt_params, lr=lr, momentum=0.9, weight_decay=1e-4, nesterov=True, **sc)
         else:
-            self.stu_optimizer = fused_optim.FusedAdam(student.parameters(), lr=lr, **sc)
+            self.stu_optimizer = fused_optim.FusedAdam(opt_params, lr=lr, **sc)
         self.tea_optimizer = mt.OldWeightEMA(teacher, student, alpha=teacher_alpha)   # ctor copies student -> teacher
         self.sync = GradSync(student, comm_dtype=grad_comm)
         self.lambda_c, self.mask_ratio, self.sigma = lambda_c, mask_ratio, sigma
@@ -278,7 +282,7 @@ class MeanTeacherTrainer:
         # data parallel: cut the backward after layer3 and all-reduce the finished 94 % of the gradient under the rest of it
         # (None: whenever a process group is active and the network has the layer3 boundary)
         self.overlap_allreduce = None
-        self.fuse_tail = True               # Adam + EMA + weight packs in one sweep (optim.FusedAdam.fused_tail_step)
+        self.fuse_tail = True               # Adam / SGD + EMA + weight packs in one sweep (optim.FusedAdam / FusedSGD.fused_tail_step)
         self.stream_priority = 0            # priority of the branch streams (and of a captured step's origin stream): -1 = high
         self.merge_wgrad = True             # one rank: both passes' grouped weight gradients in one launch (pose_resnet.finish_wgrad)
         self.single_graph = True            # one rank: the optimizer tail is captured into the step's graph (one launch per step)
@@ -540,10 +544,12 @@ class MeanTeacherTrainer:
 
     def _tail_sums_splits(self):
         # (a loss scaler's inf / nan check reads the gradient tensors between the weight gradients and the sweep: the fp16 step keeps the launch)
-        return bool(self.sum_splits_in_tail and self._tail_sums_grads() and getattr(self.stu_optimizer, "_scaler", None) is None)
+        # (the sweep that adds the split sums has an Adam form only: FusedSGD.tail_takes_split_sums is False)
+        return bool(self.sum_splits_in_tail and self._tail_sums_grads() and getattr(self.stu_optimizer, "_scaler", None) is None
+                    and getattr(self.stu_optimizer, "tail_takes_split_sums", False))
 
     def _update(self):
-        # Adam, the EMA and the next forwards' weight packs of both networks in ONE sweep when the layout allows ...
+        # the optimizer, the EMA and the next forwards' weight packs of both networks in ONE sweep when the layout allows ...
         fuse = self.fuse_tail and hasattr(self.stu_optimizer, "fused_tail_step")
         self.fused_last = bool(fuse and self.stu_optimizer.fused_tail_step(self.student, self.teacher, self.tea_optimizer))
         if not self.fused_last:

@@ -1,6 +1,8 @@
 """Fused multi-tensor optimizers on MI355X kernels: drop-in torch.optim.Optimizer subclasses for the reference's
 `Adam(student.parameters(), lr)` / `SGD(..., momentum=0.9, weight_decay=1e-4, nesterov=True)` (train_human.py:136-139).
 One kernel launch sweeps all parameter tensors (28 B/param for Adam), instead of torch's per-group foreach chains.
+In a mean-teacher step `fused_tail_step` runs either optimizer, the EMA into the teacher and both networks' weight packs as ONE
+sweep (Adam 46 B/param, SGD 38), for one parameter group or for `PoseResNet.get_parameters(lr)`'s three.
 
 Graph-replay safe: the step counter, the learning rate and the gradient scale live in an 8-float device tensor per
 parameter group (`udapose_adam_multi`'s dev_state).  `sync_hyper()` uploads lr / grad_scale when the host values changed
@@ -20,6 +22,21 @@ import torch
 from . import _hip
 from ._hip import check, lib, ptr
 from .utils import _MultiTensorTable, _bump_versions
+
+
+def _norm(v):
+    return tuple(v) if isinstance(v, (list, tuple)) else v
+
+
+def group_partition(param_groups, params):
+    """The parameter-group index of every parameter of `params`, if the groups' parameters, concatenated, ARE `params` in order (what
+    PoseResNet.get_parameters(lr) yields for list(net.parameters())); None for a reordered, incomplete or overlapping grouping.  Host
+    only: the fused optimizer tail walks the parameters in this order and carries the index in its job table."""
+    params = list(params)
+    flat = [(gi, p) for gi, g in enumerate(param_groups) for p in g["params"]]
+    if len(flat) != len(params) or any(a is not b for (_, a), b in zip(flat, params)):
+        return None
+    return [gi for gi, _ in flat]
 
 
 class _FusedBase(torch.optim.Optimizer):
@@ -122,6 +139,105 @@ class _FusedBase(torch.optim.Optimizer):
                 ent[0][3:5].copy_(torch.tensor(hyper, dtype=torch.float32), non_blocking=True)
                 ent[1] = hyper
 
+    # ------------------------------------------------------------------ fused tail: optimizer + EMA + weight packs in one sweep
+    _tail_kind = None               # the library's optimizer kind (include/udapose.h UDAPOSE_OPT_*); None: no fused tail
+    _tail_agree = ()                # hyper-parameters the sweep takes by value once: they must agree across the groups
+    tail_takes_split_sums = False
+    MAX_TAIL_GROUPS = 8
+
+    def fused_tail_step(self, student, teacher, ema):
+        """One launch for the optimizer step on the student (torch.optim.Adam / SGD with momentum), OldWeightEMA.step into the teacher
+        and the weight packs of the two executor plans their last forwards used (udapose_net_fused_update_groups).  Several parameter
+        groups are served when, concatenated, they are list(student.parameters()) in order (PoseResNet.get_parameters) and agree on
+        everything but lr and weight_decay.  Returns False - nothing done - when the layout is not the one the kernel serves (then
+        step() and ema.step() apply)."""
+        import ctypes as C
+        if self._tail_kind is None or not 1 <= len(self.param_groups) <= self.MAX_TAIL_GROUPS:
+            return False
+        groups = self.param_groups
+        if any(_norm(g[k]) != _norm(groups[0][k]) for g in groups[1:] for k in self._tail_agree):
+            return False
+        ps = list(student.parameters())
+        hd_s, hd_t = getattr(student, "_last_hd", None), getattr(teacher, "_last_hd", None)
+        # the teacher either shares the student's 16-bit element type (its packs are written by the sweep) or runs the fp32-grade
+        # f16x2 mode (the reference's precision mix: its split packs are refreshed by one pack launch right after the sweep)
+        # (a 'strict' student - f16x2 forward, fp16 backward, fp16 build - gets its fp16 data-gradient packs from the sweep and its split
+        # forward packs from one pack launch inside udapose_net_fused_update)
+        if hd_s is None or hd_t is None or hd_s.precision not in ("bf16", "fp16", "strict"):
+            return False
+        s_kind = "fp16" if hd_s.precision == "strict" else hd_s.precision      # (the student's library build)
+        t_split = hd_t.precision == "f16x2"
+        # both plans are handed to ONE library (the student's): the teacher's must have been created by it (PoseResNet.aux_lib_kind puts an
+        # f16x2 teacher's plan into the student's build; a plan of the other .so is never dereferenced here - ADVICE r3)
+        if hd_s.L is not hd_t.L and t_split and hasattr(teacher, "aux_lib_kind") and teacher.aux_lib_kind != s_kind:
+            # an 'auto' student resolved to the other build than the one the teacher's f16x2 plan was created in (the engine guesses the
+            # build before the first forward): move the teacher's fp32-grade plans into the student's build - the next teacher forward
+            # creates its plan there, and the one-launch tail applies from the following step on (ADVICE r4)
+            teacher.aux_lib_kind = s_kind
+        if hd_s.L is not hd_t.L or (not t_split and hd_t.precision != hd_s.precision) or (hd_s.precision == "strict" and not t_split):
+            if not getattr(self, "_warned_tail_lib", False):
+                self._warned_tail_lib = True
+                import warnings
+                warnings.warn("fused optimizer tail refused: the student's and the teacher's plans live in different library builds "
+                              f"({hd_s.precision} / {hd_t.precision}); falling back to separate optimizer + EMA + pack launches for this step")
+            return False
+        part = group_partition(groups, ps)
+        if part is None:
+            return False
+        if len(ema.source_params) != len(ps) or any(a is not b for a, b in zip(ema.source_params, ps)):
+            return False
+        got = [self._gather(gi, group) for gi, group in enumerate(groups)]
+        if any(g is None for g in got):         # (a group without any gradient: step() would leave its counter alone)
+            return False
+        with_grad = [p for g in got for p in g[0]]
+        ents = [self._dev_state(gi, group, ps[0].device) for gi, group in enumerate(groups)]
+        tps = ema.target_params
+        names = self._state_names
+        key = (ps[0].data_ptr(), tps[0].data_ptr(), with_grad[0].grad.data_ptr(), self.state[with_grad[0]][names[0]].data_ptr(),
+               hd_s.wpack.data_ptr(), hd_t.wpack.data_ptr(), len(with_grad), tuple(part), tuple(e[0].data_ptr() for e in ents))
+        cache = getattr(self, "_tail", None)
+        if cache is None or cache[0] != key:
+            n = len(ps)
+            arr = lambda vals: (C.c_void_p * n)(*vals)
+            st = [self.state[p] if p.grad is not None else None for p in ps]
+            cache = (key, arr([p.data_ptr() for p in ps]), arr([p.grad.data_ptr() if p.grad is not None else None for p in ps]),
+                     arr([s_[names[0]].data_ptr() if s_ else None for s_ in st]),
+                     arr([s_[names[1]].data_ptr() if s_ else None for s_ in st]) if len(names) > 1 else None,
+                     arr([p.data_ptr() for p in tps]), (C.c_int * n)(*part), (C.c_void_p * len(ents))(*[e[0].data_ptr() for e in ents]))
+            rc = hd_s.L.udapose_net_bind_update_groups(hd_s.h, hd_t.h, self._tail_kind, cache[1], cache[2], cache[3], cache[4], cache[5],
+                                                       ptr(hd_s.wpack), ptr(hd_t.wpack), cache[6])
+            if rc == -3:        # unsupported layout (unaligned tensors, channel counts that are not multiples of 64)
+                self._tail = None
+                return False
+            check(rc, "net_bind_update_groups")
+            self._tail = cache
+        _, pa_s, ga, ma, va, pa_t, _, states = cache
+        for group in groups:
+            group["step"] = group.get("step", 0) + 1
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_hyper()
+        # a pending sum of the two passes' gradient buffers is taken in the sweep itself (no separate axpy over 220 MB) - and by the loss
+        # scaler's inf / nan check in front of it, which looks at g + g2 (round 4: the fp16 step used to force the sum first)
+        delta = student.pending_grad_sum(take=True) if hasattr(student, "pending_grad_sum") else 0
+        self._pre_sweep(got[0][1], ents[0], delta)         # (loss scaling: one group)
+        b1, b2, eps, nesterov = self._tail_hyper(groups[0])
+        wds = (C.c_float * len(groups))(*[float(g["weight_decay"]) for g in groups])
+        check(hd_s.L.udapose_net_fused_update_groups(hd_s.h, hd_t.h, _hip.stream(), self._tail_kind, pa_s, ga, ma, pa_t, ptr(hd_s.wpack),
+                                                     ptr(hd_t.wpack), b1, b2, eps, nesterov, len(groups), states, wds, float(ema.alpha),
+                                                     float(1.0 - ema.alpha), 1, int(delta)), "net_fused_update_groups")
+        return self._tail_finish(student, teacher, hd_s, hd_t, ps, tps, t_split, ents[0])
+
+    def _tail_finish(self, student, teacher, hd_s, hd_t, ps, tps, t_split, ent):
+        self._post_sweep(ent)
+        _bump_versions(ps)
+        _bump_versions(tps)
+        student.packs_refreshed(hd_s, True)
+        if t_split:
+            pa_t_ = teacher._pointers()[0]
+            check(hd_t.L.udapose_net_pack_weights(hd_t.h, _hip.stream(), pa_t_, ptr(hd_t.wpack), 0), "net_pack_weights (teacher, f16x2)")
+        teacher.packs_refreshed(hd_t, False)
+        return True
+
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self):
         for gi, group in enumerate(self.param_groups):
@@ -172,6 +288,14 @@ class _FusedBase(torch.optim.Optimizer):
 
 class FusedAdam(_FusedBase):
     _state_names = ("exp_avg", "exp_avg_sq")
+    _tail_kind = 0                              # UDAPOSE_OPT_ADAM
+    _tail_agree = ("betas", "eps")
+    tail_takes_split_sums = True                # (the sweep that adds the split weight-gradient sums itself exists for Adam only)
+
+    @staticmethod
+    def _tail_hyper(group):
+        b1, b2 = group["betas"]
+        return float(b1), float(b2), float(group["eps"]), 0
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, dynamic_loss_scale=False,
                  init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
@@ -203,94 +327,14 @@ class FusedAdam(_FusedBase):
         return loss
 
 
-    # ------------------------------------------------------------------ fused tail: Adam + EMA + weight packs in one sweep
-    def fused_tail_step(self, student, teacher, ema):
-        """One launch for torch.optim.Adam.step on the student, OldWeightEMA.step into the teacher and the weight packs of the
-        two executor plans their last forwards used (udapose_net_fused_update).  Returns False - nothing done - when the
-        layout is not the one the kernel serves (then step() and ema.step() apply)."""
-        import ctypes as C
-        if len(self.param_groups) != 1:
-            return False
-        group = self.param_groups[0]
-        ps = list(student.parameters())
-        hd_s, hd_t = getattr(student, "_last_hd", None), getattr(teacher, "_last_hd", None)
-        # the teacher either shares the student's 16-bit element type (its packs are written by the sweep) or runs the fp32-grade
-        # f16x2 mode (the reference's precision mix: its split packs are refreshed by one pack launch right after the sweep)
-        # (a 'strict' student - f16x2 forward, fp16 backward, fp16 build - gets its fp16 data-gradient packs from the sweep and its split
-        # forward packs from one pack launch inside udapose_net_fused_update)
-        if hd_s is None or hd_t is None or hd_s.precision not in ("bf16", "fp16", "strict"):
-            return False
-        s_kind = "fp16" if hd_s.precision == "strict" else hd_s.precision      # (the student's library build)
-        t_split = hd_t.precision == "f16x2"
-        # both plans are handed to ONE library (the student's): the teacher's must have been created by it (PoseResNet.aux_lib_kind puts an
-        # f16x2 teacher's plan into the student's build; a plan of the other .so is never dereferenced here - ADVICE r3)
-        if hd_s.L is not hd_t.L and t_split and hasattr(teacher, "aux_lib_kind") and teacher.aux_lib_kind != s_kind:
-            # an 'auto' student resolved to the other build than the one the teacher's f16x2 plan was created in (the engine guesses the
-            # build before the first forward): move the teacher's fp32-grade plans into the student's build - the next teacher forward
-            # creates its plan there, and the one-launch tail applies from the following step on (ADVICE r4)
-            teacher.aux_lib_kind = s_kind
-        if hd_s.L is not hd_t.L or (not t_split and hd_t.precision != hd_s.precision) or (hd_s.precision == "strict" and not t_split):
-            if not getattr(self, "_warned_tail_lib", False):
-                self._warned_tail_lib = True
-                import warnings
-                warnings.warn("fused optimizer tail refused: the student's and the teacher's plans live in different library builds "
-                              f"({hd_s.precision} / {hd_t.precision}); falling back to Adam + EMA + pack launches for this step")
-            return False
-        if len(group["params"]) != len(ps) or any(a is not b for a, b in zip(group["params"], ps)):
-            return False
-        if len(ema.source_params) != len(ps) or any(a is not b for a, b in zip(ema.source_params, ps)):
-            return False
-        got = self._gather(0, group)
-        if got is None:
-            return False
-        with_grad, tab = got
-        ent = self._dev_state(0, group, ps[0].device)
-        tps = ema.target_params
-        key = (ps[0].data_ptr(), tps[0].data_ptr(), with_grad[0].grad.data_ptr(), self.state[with_grad[0]]["exp_avg"].data_ptr(),
-               hd_s.wpack.data_ptr(), hd_t.wpack.data_ptr(), len(with_grad))
-        cache = getattr(self, "_tail", None)
-        if cache is None or cache[0] != key:
-            n = len(ps)
-            arr = lambda vals: (C.c_void_p * n)(*vals)
-            st = [self.state[p] if p.grad is not None else None for p in ps]
-            cache = (key, arr([p.data_ptr() for p in ps]), arr([p.grad.data_ptr() if p.grad is not None else None for p in ps]),
-                     arr([s_["exp_avg"].data_ptr() if s_ else None for s_ in st]), arr([s_["exp_avg_sq"].data_ptr() if s_ else None for s_ in st]),
-                     arr([p.data_ptr() for p in tps]))
-            rc = hd_s.L.udapose_net_bind_update(hd_s.h, hd_t.h, cache[1], cache[2], cache[3], cache[4], cache[5], ptr(hd_s.wpack), ptr(hd_t.wpack))
-            if rc == -3:        # unsupported layout (unaligned tensors, channel counts that are not multiples of 64)
-                self._tail = None
-                return False
-            check(rc, "net_bind_update")
-            self._tail = cache
-        _, pa_s, ga, ma, va, pa_t = cache
-        group["step"] = group.get("step", 0) + 1
-        b1, b2 = group["betas"]
-        if not torch.cuda.is_current_stream_capturing():
-            self.sync_hyper()
-        # a pending sum of the two passes' gradient buffers is taken in the sweep itself (no separate axpy over 220 MB) - and by the loss
-        # scaler's inf / nan check in front of it, which looks at g + g2 (round 4: the fp16 step used to force the sum first)
-        delta = student.pending_grad_sum(take=True) if hasattr(student, "pending_grad_sum") else 0
-        self._pre_sweep(tab, ent, delta)
-        args = (hd_s.h, hd_t.h, None, pa_s, ga, ma, pa_t, ptr(hd_s.wpack), ptr(hd_t.wpack), float(group["lr"]),
-                float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), int(group["step"]),
-                float(group.get("grad_scale", 1.0)), ptr(ent[0]), float(ema.alpha), float(1.0 - ema.alpha), 1, int(delta))
-        check(hd_s.L.udapose_net_fused_update(*(args[:2] + (_hip.stream(),) + args[3:])), "net_fused_update")
-        return self._tail_finish(student, teacher, hd_s, hd_t, ps, tps, t_split, ent)
-
-    def _tail_finish(self, student, teacher, hd_s, hd_t, ps, tps, t_split, ent):
-        self._post_sweep(ent)
-        _bump_versions(ps)
-        _bump_versions(tps)
-        student.packs_refreshed(hd_s, True)
-        if t_split:
-            pa_t_ = teacher._pointers()[0]
-            check(hd_t.L.udapose_net_pack_weights(hd_t.h, _hip.stream(), pa_t_, ptr(hd_t.wpack), 0), "net_pack_weights (teacher, f16x2)")
-        teacher.packs_refreshed(hd_t, False)
-        return True
-
-
 class FusedSGD(_FusedBase):
     _state_names = ("momentum_buffer",)
+    _tail_kind = 1                              # UDAPOSE_OPT_SGD
+    _tail_agree = ("momentum", "nesterov")
+
+    @staticmethod
+    def _tail_hyper(group):
+        return float(group["momentum"]), 0.0, 0.0, int(bool(group["nesterov"]))
 
     def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, nesterov=False, grad_scale=1.0, dynamic_loss_scale=False,
                  init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
