@@ -384,6 +384,29 @@ int udapose_cons_kl_fwd(void* stream, const float* stu, const float* tea, const 
 /* d stu_i = c mask[r] (p_i S_r - v_i u_i) */
 int udapose_cons_kl_bwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
                         const float* valid_count, int log_target, const float* stats, const float* gscale, int R, int K, int HW, float* dstu);
+/* Soft-argmax decode (no counterpart in the reference: lib.keypoint_detection.soft_argmax).  Per row h_i of hm [R][H*W], i = y*W + x:
+ * (x*, y*) = the first flat arg-max in udapose_heatmap_argmax's order (NaN is the largest value), m = h_i*; O = the whole map
+ * (window < 0) or {|x - x*| <= window, |y - y*| <= window} clipped to the map (window 0: the arg-max itself);
+ * p_i = exp(beta (h_i - m)) / Z over O; coords[r] = (cx, cy) = (sum p_i x_i, sum p_i y_i) in pixel-index units, NOT zeroed where the
+ * maximum is <= 0; maxvals[r] = m, the number udapose_heatmap_argmax returns.  A row whose maximum is NaN or +-inf gives NaN
+ * coordinates.  beta must be finite and > 0 (UDAPOSE_ERR_ARG otherwise).  flat_idx [R] and stats [4][R] = (m, 1/Z, cx, cy) are what
+ * the backward reads.  One block per row, sums in double, no atomics. */
+int udapose_soft_argmax_fwd(void* stream, const float* hm, int R, int H, int W, float beta, int window, float* coords, float* maxvals,
+                            int* flat_idx, float* stats);
+/* d hm_i = beta p_i ((x_i - cx) dcoords[r][0] + (y_i - cy) dcoords[r][1]) in O, 0 outside (the full row is written); the arg-max
+ * selection is a constant: nothing flows through the choice of window. */
+int udapose_soft_argmax_bwd(void* stream, const float* hm, const float* dcoords, const int* flat_idx, const float* stats, int R, int H, int W,
+                            float beta, int window, float* dhm);
+/* Coordinate loss on the soft-argmax of hm (JointsSoftArgmaxLoss / ConsSoftArgmaxLoss): target [R][2] (x, y) in heat-map pixels,
+ * rows[r] = f_r (l((cx - tx_r) / W) + l((cy - ty_r) / H)), l(d) = |d| (norm 0, "l1") or 0.5 d^2 (norm 1, "l2"),
+ * f_r = weight[r] (float, may be NULL) * (mask[r] != 0) (bytes, may be NULL); out[g] = sum of the `group` rows of g / group
+ * (group = R: the mean; group = K: per-sample means).  flat_idx [R] and stats [4][R] as above. */
+int udapose_coord_loss_fwd(void* stream, const float* hm, const float* target, const float* weight, const unsigned char* mask, int R, int group,
+                           int H, int W, float beta, int window, int norm, float* rows, int* flat_idx, float* stats, float* out);
+/* d hm of the mean (group = R): the sweep of udapose_soft_argmax_bwd with dcoords[r] = gscale[0] / R * f_r *
+ * (l'((cx - tx_r) / W) / W, l'((cy - ty_r) / H) / H); gscale is a device scalar (NULL: 1), so nothing is read back. */
+int udapose_coord_loss_bwd(void* stream, const float* hm, const float* target, const float* weight, const unsigned char* mask, const int* flat_idx,
+                           const float* stats, const float* gscale, int R, int H, int W, float beta, int window, int norm, float* dhm);
 /* get_max_preds(_torch) (lib/keypoint_detection.py:9-37, utils.py:54-75) and rectify (utils.py:77-109): any output may
  * be NULL.  patch: [(2*rad+1)^2] fp32 Gaussian table built by the caller exactly as utils.py:93-98 does. */
 int udapose_heatmap_argmax(void* stream, const float* hm, int R, int H, int W, float* maxvals, int* flat_idx, float* preds_xy,

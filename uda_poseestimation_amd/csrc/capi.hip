@@ -65,6 +65,12 @@ int sml_cons_fwd(hipStream_t, int, const float*, const float*, const unsigned ch
                  float*, float*);
 int sml_cons_bwd(hipStream_t, int, const float*, const float*, const unsigned char*, const unsigned char*, const float*, const float*,
                  const float*, int, int, int, float*);
+int sa_fwd(hipStream_t, const float*, int, int, int, float, int, float*, float*, int*, float*);
+int sa_bwd(hipStream_t, const float*, const float*, const int*, const float*, int, int, int, float, int, float*);
+int sa_coord_fwd(hipStream_t, const float*, const float*, const float*, const unsigned char*, int, int, int, int, float, int, int, float*, int*,
+                 float*, float*);
+int sa_coord_bwd(hipStream_t, const float*, const float*, const float*, const unsigned char*, const int*, const float*, const float*, int, int, int,
+                 float, int, int, float*);
 int pw_maxpool2x2_ceil_f32(hipStream_t, const float*, float*, int, int, int, int);
 int pw_nchw_f32_to_nhwc_f32(hipStream_t, const float*, float*, int, int, int, int);
 int adain_launch_f32(hipStream_t, const float*, const float*, float*, int, int, int, int, float, float, const float*, float*);
@@ -507,6 +513,22 @@ int udapose_cons_kl_fwd(void* stream, const float* stu, const float* tea, const 
 int udapose_cons_kl_bwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
                         const float* valid_count, int log_target, const float* stats, const float* gscale, int R, int K, int HW, float* dstu) {
     return sml_cons_bwd(S(stream), log_target ? 1 : 2, stu, tea, mask, valid, valid_count, stats, gscale, R, K, HW, dstu);
+}
+int udapose_soft_argmax_fwd(void* stream, const float* hm, int R, int H, int W, float beta, int window, float* coords, float* maxvals,
+                            int* flat_idx, float* stats) {
+    return sa_fwd(S(stream), hm, R, H, W, beta, window, coords, maxvals, flat_idx, stats);
+}
+int udapose_soft_argmax_bwd(void* stream, const float* hm, const float* dcoords, const int* flat_idx, const float* stats, int R, int H, int W,
+                            float beta, int window, float* dhm) {
+    return sa_bwd(S(stream), hm, dcoords, flat_idx, stats, R, H, W, beta, window, dhm);
+}
+int udapose_coord_loss_fwd(void* stream, const float* hm, const float* target, const float* weight, const unsigned char* mask, int R, int group,
+                           int H, int W, float beta, int window, int norm, float* rows, int* flat_idx, float* stats, float* out) {
+    return sa_coord_fwd(S(stream), hm, target, weight, mask, R, group, H, W, beta, window, norm, rows, flat_idx, stats, out);
+}
+int udapose_coord_loss_bwd(void* stream, const float* hm, const float* target, const float* weight, const unsigned char* mask, const int* flat_idx,
+                           const float* stats, const float* gscale, int R, int H, int W, float beta, int window, int norm, float* dhm) {
+    return sa_coord_bwd(S(stream), hm, target, weight, mask, flat_idx, stats, gscale, R, H, W, beta, window, norm, dhm);
 }
 int udapose_heatmap_argmax(void* stream, const float* hm, int R, int H, int W, float* maxvals, int* flat_idx, float* preds, float* rect,
                            const float* patch, int rad) {

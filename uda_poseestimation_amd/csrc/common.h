@@ -140,6 +140,15 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t total) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
 }
 
+// torch's total order on floats for max / kthvalue: NaN is the LARGEST value (and all NaNs are equal); the first index wins a tie.
+// The one arg-max order of heatmap.hip (argmax_rectify_k) and softargmax.hip.
+__device__ __forceinline__ bool hm_better(float v, int i, float bv, int bi) {
+    const bool vn = v != v, bn = bv != bv;
+    if (vn != bn) return vn;
+    if (vn) return i < bi;
+    return v > bv || (v == bv && i < bi);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

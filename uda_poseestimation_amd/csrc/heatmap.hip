@@ -104,13 +104,7 @@ __global__ void sqdiff_bwd_scalar_k(const float* __restrict__ a, const float* __
     }
 }
 
-// torch's total order on floats for max / kthvalue: NaN is the LARGEST value (and all NaNs are equal)
-__device__ __forceinline__ bool hm_better(float v, int i, float bv, int bi) {
-    const bool vn = v != v, bn = bv != bv;
-    if (vn != bn) return vn;
-    if (vn) return i < bi;
-    return v > bv || (v == bv && i < bi);
-}
+// (hm_better, the arg-max order: common.h)
 // order-preserving float -> uint32 key (NaN -> 0xffffffff, the largest: torch.kthvalue's order)
 __device__ __forceinline__ unsigned int hm_key(float v) {
     if (v != v) return 0xffffffffu;

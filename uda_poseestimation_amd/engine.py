@@ -559,13 +559,14 @@ class MeanTeacherTrainer:
             self.tea_optimizer.step()       # EMA after the optimizer step (train_human.py:437-438)
 
 
-def validate(batches, model, criterion=None):
+def validate(batches, model, criterion=None, decode="argmax"):
     """The reference's validate() (train_human.py:461-500) on the device: eval mode, no grad; per-key-point PCK@0.05
     averaged over the set with batch-size weights, entries of -1 (key point absent from a batch) ignored exactly like
     `AverageMeterList(ignore_val=-1)` (lib/meter.py:18-36,65-82), and the batch-size weighted mean loss.  `batches` yields
     (x, label, weight[, meta]).  Decode and PCK run on the device and are ACCUMULATED there: one read-back at the end
     instead of the reference's 2 x 8.4 MB device->host copy + sync per batch.  Returns (acc_per_keypoint list, mean_loss)
-    (the caller applies its dataset's group_accuracy)."""
+    (the caller applies its dataset's group_accuracy).  decode: how the predictions are decoded for the PCK, as in
+    lib.keypoint_detection.accuracy ("argmax", "soft" or a callable)."""
     criterion = criterion or JointsMSELoss()
     was_training = model.training
     model.eval()
@@ -578,7 +579,7 @@ def validate(batches, model, criterion=None):
             x, label, weight = x.to(dev, non_blocking=True), label.to(dev, non_blocking=True), weight.to(dev, non_blocking=True)
             y = model(x)
             loss = criterion(y, label, weight)
-            acc, _, _ = kd.accuracy_device(y, label)
+            acc, _, _ = kd.accuracy_device(y, label, decode=decode)
             n = x.shape[0]
             present = (acc != -1).to(torch.float32)
             if acc_sum is None:

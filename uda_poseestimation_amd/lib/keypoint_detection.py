@@ -1,4 +1,5 @@
-"""Arg-max decode and PCK (API mirror of the reference's lib/keypoint_detection.py:9-94) on MI355X kernels.
+"""Arg-max decode and PCK (API mirror of the reference's lib/keypoint_detection.py:9-94) on MI355X kernels, and the soft-argmax
+decode the reference lacks (`soft_argmax`, csrc/softargmax.hip: sub-pixel coordinates, differentiable).
 
 The reference takes numpy arrays (it is called on `.cpu().numpy()` copies, train_human.py:289,443).  The same calls work
 here; torch CUDA tensors are accepted as well and avoid the 2 x 8.4 MB device->host copy per iteration: decode and PCK
@@ -41,13 +42,93 @@ def get_max_preds(batch_heatmaps):
     return preds, maxv
 
 
-def accuracy_device(output, target, thr=0.5):
+class _SoftArgmaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hm, beta, window):
+        B, K, H, W = hm.shape
+        h = hm.detach().float().contiguous()
+        coords = torch.empty(B, K, 2, dtype=torch.float32, device=h.device)
+        maxv = torch.empty(B, K, 1, dtype=torch.float32, device=h.device)
+        idx = torch.empty(B * K, dtype=torch.int32, device=h.device)
+        stats = torch.empty(4 * B * K, dtype=torch.float32, device=h.device)
+        check(lib().udapose_soft_argmax_fwd(_hip.stream(), ptr(h), B * K, H, W, beta, window, ptr(coords), ptr(maxv), ptr(idx), ptr(stats)),
+              "soft_argmax_fwd")
+        ctx.save_for_backward(h, idx, stats)
+        ctx.beta, ctx.window, ctx.shape, ctx.in_dtype = beta, window, hm.shape, hm.dtype
+        ctx.mark_non_differentiable(maxv)
+        return coords, maxv
+
+    @staticmethod
+    def backward(ctx, g, _gmax):
+        h, idx, stats = ctx.saved_tensors
+        B, K, H, W = ctx.shape
+        d = torch.empty_like(h)
+        gc = g.detach().float().contiguous()
+        check(lib().udapose_soft_argmax_bwd(_hip.stream(), ptr(h), ptr(gc), ptr(idx), ptr(stats), B * K, H, W, ctx.beta, ctx.window, ptr(d)),
+              "soft_argmax_bwd")
+        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None
+
+
+def _soft_args(beta, window):
+    """(beta, window) as the kernels take them: beta finite and > 0, window None (the whole map) -> -1."""
+    beta = float(beta)
+    if not (beta > 0.0 and beta < float("inf")):
+        raise ValueError(f"soft-argmax needs a finite beta > 0, got {beta}")
+    if window is None:
+        return beta, -1
+    if int(window) != window or window < 0:
+        raise ValueError(f"window must be None (the whole map) or an integer >= 0, got {window!r}")
+    return beta, int(window)
+
+
+def soft_argmax(batch_heatmaps, beta=10.0, window=None):
+    """[B,K,H,W] -> (coords [B,K,2] float32 (x,y) in pixel-index units, maxvals [B,K,1]); numpy in -> numpy out, tensor in -> tensor out.
+    coords = sum p_i (x_i, y_i) with p = softmax(beta * h) over the pixels within `window` (Chebyshev distance) of the first arg-max,
+    the whole map for window=None.  MSE-trained maps have a flat background of thousands of pixels: decode them with a window
+    (beta=10, window=5 is what accuracy(decode="soft") uses).  Differentiable for a tensor that requires grad (the arg-max that places
+    the window is a constant; the gradient comes back in the input's dtype).  Coordinates are NOT zeroed where maxvals <= 0."""
+    is_np = isinstance(batch_heatmaps, np.ndarray)
+    if not is_np and not torch.is_tensor(batch_heatmaps):
+        raise AssertionError('batch_heatmaps should be numpy.ndarray or a 4-d tensor')
+    beta, window = _soft_args(beta, window)
+    if is_np:
+        coords, maxv = _SoftArgmaxFn.apply(_dev_f32(batch_heatmaps), beta, window)
+        return coords.cpu().numpy(), maxv.cpu().numpy().astype(batch_heatmaps.dtype, copy=False)
+    assert batch_heatmaps.dim() == 4, 'batch_heatmaps should be numpy.ndarray or a 4-d tensor'
+    _hip.require_cuda(batch_heatmaps)
+    return _SoftArgmaxFn.apply(batch_heatmaps, beta, window)
+
+
+def _dev_f32c(a, like):
+    """What a decode callable returned (tensor or numpy) as an fp32 tensor on `like`'s device."""
+    if isinstance(a, np.ndarray):
+        a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    return a.detach().to(device=like.device, dtype=torch.float32)
+
+
+def _decode_pred(o, decode):
+    """The prediction's coordinates under `decode`: "argmax", "soft" (soft_argmax(beta=10, window=5)) or a callable hm -> (coords, maxvals).
+    The soft decodes get the reference's `maxval > 0` zeroing, so every decode agrees on which joints are absent."""
+    if decode == "argmax":
+        return _decode(o)[0]
+    if decode == "soft":
+        coords, maxv = _SoftArgmaxFn.apply(o, 10.0, 5)
+    elif callable(decode):
+        coords, maxv = decode(o)
+        coords, maxv = _dev_f32c(coords, o), _dev_f32c(maxv, o)
+    else:
+        raise ValueError(f"decode must be 'argmax', 'soft' or a callable, got {decode!r}")
+    B, K = o.shape[:2]
+    return (coords.detach().reshape(B, K, 2) * (maxv.detach().reshape(B, K, 1) > 0).to(torch.float32)).contiguous()
+
+
+def accuracy_device(output, target, thr=0.5, decode="argmax"):
     """`accuracy` without the read-back: (acc [K] float32 with -1 for key points absent from the batch, [avg_acc, cnt],
     pred [B,K,2]) as CUDA tensors on the current stream - no host synchronisation (validate() accumulates them on the
-    device and reads the set's averages back once)."""
+    device and reads the set's averages back once).  decode: how the PREDICTION is decoded (see `accuracy`)."""
     o, t = _dev_f32(output), _dev_f32(target)
     B, K, H, W = o.shape
-    pred, _ = _decode(o)
+    pred = _decode_pred(o, decode)
     gt, _ = _decode(t)
     acc = torch.empty(K, dtype=torch.float32, device=o.device)
     avg_cnt = torch.empty(2, dtype=torch.float32, device=o.device)
@@ -55,18 +136,15 @@ def accuracy_device(output, target, thr=0.5):
     return acc, avg_cnt, pred
 
 
-def accuracy(output, target, hm_type='gaussian', thr=0.5):
-    """PCK@(thr/10 of the heat-map size) from GT heat-maps; returns (acc[K], avg_acc, cnt, pred[B,K,2]) like the reference."""
+def accuracy(output, target, hm_type='gaussian', thr=0.5, decode="argmax"):
+    """PCK@(thr/10 of the heat-map size) from GT heat-maps; returns (acc[K], avg_acc, cnt, pred[B,K,2]) like the reference.
+    decode: "argmax" (the reference's decode), "soft" (soft_argmax(beta=10, window=5): sub-pixel predictions) or a callable
+    hm -> (coords, maxvals).  Only the prediction is decoded softly - the target heat-maps keep the arg-max - and the soft
+    coordinates are zeroed where maxvals <= 0, as the arg-max's are."""
     if hm_type != 'gaussian':
         raise NotImplementedError("only hm_type='gaussian' is used by the reference scripts")
     is_np = isinstance(output, np.ndarray)
-    o, t = _dev_f32(output), _dev_f32(target)
-    B, K, H, W = o.shape
-    pred, _ = _decode(o)
-    gt, _ = _decode(t)
-    acc = torch.empty(K, dtype=torch.float32, device=o.device)
-    avg_cnt = torch.empty(2, dtype=torch.float32, device=o.device)
-    check(lib().udapose_pck(_hip.stream(), ptr(pred), ptr(gt), B, K, H / 10.0, W / 10.0, float(thr), ptr(acc), ptr(avg_cnt)), "pck")
+    acc, avg_cnt, pred = accuracy_device(output, target, thr, decode)
     ac = avg_cnt.cpu()
     acc_np = acc.cpu().numpy().astype(np.float64)
     return acc_np, float(ac[0]), int(ac[1]), (pred.cpu().numpy() if is_np else pred)

@@ -3,7 +3,8 @@
 JointsMSELoss and ConsLoss are what the training scripts instantiate (train_human.py:133-134).  JointsKLLoss, EntLoss,
 ConsSoftmaxLoss and ConsKLLoss (loss.py:52-173) are the soft-max family a user swaps in (csrc/softmax_loss.hip: a row
 soft-max over the H*W pixels of every (b,k) heat-map fused with the loss, its reduction and its backward).  CoralLoss is
-defined and refuses construction: see its docstring.
+defined and refuses construction: see its docstring.  JointsSoftArgmaxLoss and ConsSoftArgmaxLoss have no counterpart in the reference:
+they are losses on the soft-argmax COORDINATES of the student's heat-maps (csrc/softargmax.hip), a gradient on where the peak is.
 Each forward is one sweep over the operands (per-(b,k) row partial + a tiny row reduction), each backward one sweep.
 """
 import warnings
@@ -313,6 +314,118 @@ class ConsKLLoss(nn.Module):
                           "is NaN for every heat-map of more than one pixel.  ConsKLLoss(log_target=True) computes the KL divergence.",
                           RuntimeWarning, stacklevel=2)
         return _ConsProbFn.apply(stu_out, tea_out, tea_mask, valid_mask, 1 if self.log_target else 2)
+
+
+# ---------------------------------------------------------------------------------------------- coordinate losses (soft-argmax)
+_NORMS = {"l1": 0, "l2": 1}
+
+
+class _CoordLossFn(torch.autograd.Function):
+    """f_r * (l((cx - tx) / W) + l((cy - ty) / H)) per (b,k) row, (cx, cy) the soft-argmax of the row; f_r = weight[r] * (mask[r] != 0)."""
+
+    @staticmethod
+    def forward(ctx, output, coords, weight, mask, reduce_mean, beta, window, norm):
+        _hip.require_cuda(output, coords, weight, mask)
+        B, K, H, W = output.shape
+        R = B * K
+        o, t = _f32c(output), _f32c(coords)
+        if t.numel() != 2 * R:
+            raise ValueError("target coordinates must be [B,K,2]")
+        w = None if weight is None else _f32c(weight).reshape(-1)
+        if w is not None and w.numel() != R:
+            raise ValueError("target_weight must have B*K elements")
+        m = _bytes_mask(mask)
+        if m is not None and m.numel() != R:
+            raise ValueError("the (b,k) mask must have B*K elements")
+        rows = torch.empty(R, dtype=torch.float32, device=o.device)
+        idx = torch.empty(R, dtype=torch.int32, device=o.device)
+        stats = torch.empty(4 * R, dtype=torch.float32, device=o.device)
+        out = torch.empty(() if reduce_mean else (B,), dtype=torch.float32, device=o.device)
+        check(lib().udapose_coord_loss_fwd(_hip.stream(), ptr(o), ptr(t), ptr(w), ptr(m), R, R if reduce_mean else K, H, W, beta, window, norm,
+                                           ptr(rows), ptr(idx), ptr(stats), ptr(out)), "coord_loss_fwd")
+        ctx.save_for_backward(o, t, w if w is not None else torch.empty(0, device=o.device),
+                              m if m is not None else torch.empty(0, dtype=torch.uint8, device=o.device), idx, stats)
+        ctx.has_w, ctx.has_m, ctx.reduce_mean, ctx.shape, ctx.in_dtype = w is not None, m is not None, reduce_mean, output.shape, output.dtype
+        ctx.beta, ctx.window, ctx.norm = beta, window, norm
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        o, t, w, m, idx, stats = ctx.saved_tensors
+        if not ctx.reduce_mean:
+            raise NotImplementedError("backward of reduction='none' is not on the hot path")
+        B, K, H, W = ctx.shape
+        d = torch.empty_like(o)
+        gs = _gscale(g)
+        check(lib().udapose_coord_loss_bwd(_hip.stream(), ptr(o), ptr(t), ptr(w) if ctx.has_w else None, ptr(m) if ctx.has_m else None, ptr(idx),
+                                           ptr(stats), ptr(gs), B * K, H, W, ctx.beta, ctx.window, ctx.norm, ptr(d)), "coord_loss_bwd")
+        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None, None, None, None, None, None
+
+
+def _coord_args(beta, window, norm):
+    from ..keypoint_detection import _soft_args
+    if norm not in _NORMS:
+        raise ValueError(f"norm must be 'l1' or 'l2', got {norm!r}")
+    return _soft_args(beta, window) + (_NORMS[norm],)
+
+
+def _argmax_decode(hm):
+    """(coords [B,K,2], maxvals [B,K,1]) of get_max_preds, on fp32 rows and without a graph."""
+    from ..keypoint_detection import _decode
+    _hip.require_cuda(hm)
+    with torch.no_grad():
+        return _decode(_f32c(hm))
+
+
+class JointsSoftArgmaxLoss(nn.Module):
+    """Supervised loss on the soft-argmax coordinates of `output` (lib.keypoint_detection.soft_argmax(output, beta, window)):
+    target_weight[b,k] * (l((cx - tx) / W) + l((cy - ty) / H)) per key point, l = |d| (norm='l1') or 0.5 d^2 ('l2'); the mean over the
+    B*K key points ('mean') or per-sample means, shape [B] ('none', forward only), the conventions of JointsMSELoss.
+    `target` is [B,K,2] (x, y) in heat-map pixels, or [B,K,H,W] heat-maps: those are decoded by the arg-max kernel, and a key point
+    whose target maximum is <= 0 gets factor 0 (it carries no position).  MSE-trained maps need a window (beta=10, window=5).
+    beta, window and norm are read at every call and are baked into a captured step's launches: build a new capture to change them."""
+
+    def __init__(self, beta=10.0, window=None, norm="l1", reduction='mean'):
+        super(JointsSoftArgmaxLoss, self).__init__()
+        _coord_args(beta, window, norm)
+        self.beta, self.window, self.norm, self.reduction = beta, window, norm, reduction
+
+    def forward(self, output, target, target_weight=None):
+        if self.reduction not in ('mean', 'none'):
+            return None         # (as the other classes of this module)
+        beta, window, norm = _coord_args(self.beta, self.window, self.norm)
+        present = None
+        if target.dim() == 4:
+            target, maxv = _argmax_decode(target)
+            present = maxv > 0
+        return _CoordLossFn.apply(output, target, target_weight, present, self.reduction == 'mean', beta, window, norm)
+
+
+class ConsSoftArgmaxLoss(nn.Module):
+    """Consistency on coordinates: the student's soft-argmax coordinates against the teacher's decoded ones (never a gradient into the
+    teacher), tea_mask[b,k] * (l((cx - tx) / W) + l((cy - ty) / H)), mean over all B*K key points as in ConsLoss.  tea_decode='argmax'
+    takes get_max_preds's coordinates of `tea_out` ((0, 0) where its maximum is <= 0), 'soft' the soft-argmax with this loss's beta and
+    window.  A pixel selection has no meaning for a coordinate: a `valid_mask` is refused.
+    beta, window, norm and tea_decode are baked into a captured step's launches: build a new capture to change them."""
+
+    def __init__(self, beta=10.0, window=None, norm="l1", tea_decode="argmax"):
+        super(ConsSoftArgmaxLoss, self).__init__()
+        _coord_args(beta, window, norm)
+        if tea_decode not in ("argmax", "soft"):
+            raise ValueError(f"tea_decode must be 'argmax' or 'soft', got {tea_decode!r}")
+        self.beta, self.window, self.norm, self.tea_decode = beta, window, norm, tea_decode
+
+    def forward(self, stu_out, tea_out, valid_mask=None, tea_mask=None):
+        if valid_mask is not None:
+            raise ValueError("ConsSoftArgmaxLoss compares coordinates: a per-pixel valid_mask selects nothing there (use tea_mask)")
+        beta, window, norm = _coord_args(self.beta, self.window, self.norm)
+        if self.tea_decode == "argmax":
+            tea_xy, _ = _argmax_decode(tea_out)
+        else:
+            from ..keypoint_detection import soft_argmax
+            with torch.no_grad():
+                tea_xy, _ = soft_argmax(tea_out.detach(), beta, None if window < 0 else window)
+        return _CoordLossFn.apply(stu_out, tea_xy, None, tea_mask, True, beta, window, norm)
 
 
 class CoralLoss(nn.Module):
