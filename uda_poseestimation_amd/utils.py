@@ -26,7 +26,7 @@ class _MultiTensorTable:
             for off in range(0, n, chunk):
                 blk_t.append(i)
                 blk_o.append(off)
-        self.key = tuple(t.data_ptr() for lst in tensor_lists for t in (lst[0], lst[-1])) + (len(sizes),)
+        self.key = self.key_of(tensor_lists)
         self.ptrs = [torch.tensor([t.data_ptr() for t in lst], dtype=torch.int64, device=dev) for lst in tensor_lists]
         self.sizes = torch.tensor(sizes, dtype=torch.int64, device=dev)
         self.blk_t = torch.tensor(blk_t, dtype=torch.int32, device=dev)
@@ -35,7 +35,11 @@ class _MultiTensorTable:
 
     @staticmethod
     def key_of(tensor_lists):
-        return tuple(t.data_ptr() for lst in tensor_lists for t in (lst[0], lst[-1])) + (len(tensor_lists[0]),)
+        """What a table was built from: the address of EVERY tensor of every list, and the sizes.  (The first and last address of a list
+        do not identify it: a middle gradient reallocated after zero_grad(set_to_none=True), or one parameter losing its gradient while
+        another gains one, leaves both in place - and the sweep would go on reading the old addresses.)"""
+        ptr_of, numel = torch.Tensor.data_ptr, torch.Tensor.numel
+        return tuple(tuple(map(ptr_of, lst)) for lst in tensor_lists) + (tuple(map(numel, tensor_lists[0])),)
 
 
 class OldWeightEMA(object):
