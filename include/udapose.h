@@ -411,6 +411,21 @@ int udapose_coord_loss_bwd(void* stream, const float* hm, const float* target, c
  * be NULL.  patch: [(2*rad+1)^2] fp32 Gaussian table built by the caller exactly as utils.py:93-98 does. */
 int udapose_heatmap_argmax(void* stream, const float* hm, int R, int H, int W, float* maxvals, int* flat_idx, float* preds_xy,
                            float* rectified, const float* patch, int rad);
+/* Flip test (the -f/--flip evaluation of the reference's animal scripts, train_animal.py:556; pairing tables lib/datasets/util.py:186-224):
+ * the image side.  src [N][rows_per_image][W] fp32 (an NCHW image batch: rows_per_image = 3*H).  keep_original = 1: dst [2N][rows][W],
+ * dst[0:N] = src and dst[N:2N][r][x] = src[r][W-1-x] - the batch and its mirror image in one launch; keep_original = 0: dst [N][rows][W]
+ * holds the mirrored rows only.  16-byte accesses when W % 4 == 0 and both pointers are 16-byte aligned, element by element otherwise.
+ * dst must not overlap src (UDAPOSE_ERR_ARG). */
+int udapose_hflip_batch(void* stream, const float* src, float* dst, int N, size_t rows_per_image, int W, int keep_original);
+/* Flip test: the heat-map side.  a, f, out [N][K][H][W] fp32; perm [K] a device table of partner joints (NULL: no pairs), an entry outside
+ * [0, K) counts as k itself, so nothing outside f is ever read.  fb[n][k][y][x] = f[n][perm[k]][y][W-1-x] (flip back + channel swap);
+ * s = fb (shift 0), or s[..][x] = fb[..][x-1] for x >= 1 and s[..][0] = fb[..][0] (shift 1: the one-pixel shift Simple Baselines gives the
+ * flipped output).  mode 0: out = s (a may be NULL); mode 1: out = (a + s) * 0.5f, in fp32 in that order.  out may BE a (same thread, same
+ * element); it must not overlap f, nor a partially (UDAPOSE_ERR_ARG).  maxvals [N*K], flat_idx [N*K], preds_xy [N*K][2] (each may be NULL)
+ * are what udapose_heatmap_argmax returns for out, bit for bit, reduced in the same pass from the values just written: first flat index on
+ * ties, NaN as the maximum, coordinates zeroed where the maximum is <= 0.  One work-group per (n, k) plane, no atomics, no scratch. */
+int udapose_flip_merge(void* stream, const float* a, const float* f, const int* perm, int N, int K, int H, int W, int shift, int mode,
+                       float* out, float* maxvals, int* flat_idx, float* preds_xy);
 /* confidence mask (train_human.py:427-430): thr = k-th smallest of act[n]; mask[i] = (tea_mask[i]*act_local[i]) > thr */
 int udapose_kth_mask(void* stream, const float* act, const float* tea_mask, int n, int k, float* thr_out, unsigned char* mask,
                      const float* act_local, int n_local);

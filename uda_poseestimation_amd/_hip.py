@@ -133,6 +133,8 @@ _SIGS = {
     "udapose_coord_loss_fwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp]),
     "udapose_coord_loss_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, ci, ci, vp]),
     "udapose_heatmap_argmax": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci]),
+    "udapose_hflip_batch": (ci, [vp, vp, vp, ci, sz, ci, ci]),
+    "udapose_flip_merge": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
     "udapose_kth_mask": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, ci]),
     "udapose_pck": (ci, [vp, vp, vp, ci, ci, cf, cf, cf, vp, vp]),
     "udapose_multi_chunk": (ci, []),

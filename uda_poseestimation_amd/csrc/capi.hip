@@ -71,6 +71,8 @@ int sa_coord_fwd(hipStream_t, const float*, const float*, const float*, const un
                  float*, float*);
 int sa_coord_bwd(hipStream_t, const float*, const float*, const float*, const unsigned char*, const int*, const float*, const float*, int, int, int,
                  float, int, int, float*);
+int flip_hbatch(hipStream_t, const float*, float*, int, size_t, int, int);
+int flip_merge(hipStream_t, const float*, const float*, const int*, int, int, int, int, int, int, float*, float*, int*, float*);
 int pw_maxpool2x2_ceil_f32(hipStream_t, const float*, float*, int, int, int, int);
 int pw_nchw_f32_to_nhwc_f32(hipStream_t, const float*, float*, int, int, int, int);
 int adain_launch_f32(hipStream_t, const float*, const float*, float*, int, int, int, int, float, float, const float*, float*);
@@ -534,6 +536,13 @@ int udapose_heatmap_argmax(void* stream, const float* hm, int R, int H, int W, f
                            const float* patch, int rad) {
     if (rect && !patch) return UDAPOSE_ERR_ARG;
     return hm_argmax_rectify(S(stream), hm, R, H, W, maxvals, flat_idx, preds, rect, patch, rad);
+}
+int udapose_hflip_batch(void* stream, const float* src, float* dst, int N, size_t rows_per_image, int W, int keep_original) {
+    return flip_hbatch(S(stream), src, dst, N, rows_per_image, W, keep_original);
+}
+int udapose_flip_merge(void* stream, const float* a, const float* f, const int* perm, int N, int K, int H, int W, int shift, int mode, float* out,
+                       float* maxvals, int* flat_idx, float* preds_xy) {
+    return flip_merge(S(stream), a, f, perm, N, K, H, W, shift, mode, out, maxvals, flat_idx, preds_xy);
 }
 int udapose_kth_mask(void* stream, const float* act, const float* tm, int n, int k, float* thr_out, unsigned char* mask, const float* act_local,
                      int n_local) {

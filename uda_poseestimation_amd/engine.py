@@ -19,6 +19,7 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import ops
 from . import optim as fused_optim
 from . import utils as mt
 from . import warp
@@ -559,6 +560,36 @@ class MeanTeacherTrainer:
             self.tea_optimizer.step()       # EMA after the optimizer step (train_human.py:437-438)
 
 
+# How the flip test runs its two evaluation forwards: "batched" = one forward of the 2N batch [x; mirror(x)] that
+# udapose_hflip_batch(keep_original=1) writes, "two" = model(x) and model(mirror(x)).  The folded evaluation forward has no cross-image
+# term: the two forms give the same bits, image for image, and the 2N form is the faster one (it holds a plan of 2N images).
+FLIP_FORWARD_FORM = "batched"
+
+
+def _flip_forward(model, x, perm, shift_heatmap, decode):
+    """Both evaluation forwards and the merge launch: (merged [N,K,H,W], preds, maxvals), the last two None without decode.  The merge
+    writes over the plain forward's heat-maps (the executor hands out a fresh output tensor per forward)."""
+    if model.training:
+        raise RuntimeError("the flip test is an evaluation forward: call model.eval() first (train-mode BatchNorm would mix the two views)")
+    with torch.no_grad():
+        x = x.float().contiguous()
+        N = x.shape[0]
+        if FLIP_FORWARD_FORM == "batched":
+            y2 = model(ops.hflip_batch(x, keep_original=True))
+            y, yf = y2[:N], y2[N:]
+        else:
+            y, yf = model(x), model(ops.hflip_batch(x))
+        return kd._flip_merge(y, yf, perm, shift_heatmap, decode, out=y)
+
+
+def flip_forward(model, x, flip_pairs, shift_heatmap=False):
+    """Flip-test heat-maps of an eval-mode model: (model(x) + flip_back(model(mirror(x)), flip_pairs, shift_heatmap)) * 0.5, the mirror
+    image made by udapose_hflip_batch and flip-back, joint swap and average by one udapose_flip_merge launch.  flip_pairs: a sequence of
+    left / right joint pairs or a key of lib.keypoint_detection.FLIP_PAIRS."""
+    perm = kd._perm_device(flip_pairs, model.num_keypoints, x.device)
+    return _flip_forward(model, x, perm, shift_heatmap, False)[0]
+
+
 def validate(batches, model, criterion=None, decode="argmax"):
     """The reference's validate() (train_human.py:461-500) on the device: eval mode, no grad; per-key-point PCK@0.05
     averaged over the set with batch-size weights, entries of -1 (key point absent from a batch) ignored exactly like
@@ -601,6 +632,39 @@ def validate(batches, model, criterion=None, decode="argmax"):
         warnings.warn(f"validate(): {sat} f16x2 stores saturated at |x| = 65504 (or were NaN) since the last check - activations outside fp16's "
                       "range; run the model with precision='fp32' (exact, slower) to rule the format out")
     return out[:-1], out[-1]
+
+
+class _FlipTestModel(torch.nn.Module):
+    """What validate_flip() hands to validate() as its model: a call returns flip_forward()'s merged heat-maps and keeps the decode that came
+    out of the merge launch, which `decoded` gives back as validate()'s decode callable."""
+
+    def __init__(self, model, flip_pairs, shift_heatmap, decode):
+        super().__init__()
+        self.model, self.flip_pairs, self.shift_heatmap, self.decode = model, flip_pairs, shift_heatmap, decode
+        self._last = None
+        self.train(model.training)      # (validate() restores the mode it finds: the wrapped model's)
+
+    def forward(self, x):
+        perm = kd._perm_device(self.flip_pairs, self.model.num_keypoints, x.device)
+        merged, preds, maxv = _flip_forward(self.model, x, perm, self.shift_heatmap, self.decode)
+        self._last = (merged.data_ptr(), preds, maxv)
+        return merged
+
+    def decoded(self, heatmaps):
+        if self._last is None or self._last[0] != heatmaps.data_ptr():
+            raise RuntimeError("the merge launch's decode belongs to the heat-maps of the last flip-test forward")
+        return self._last[1], self._last[2]
+
+
+def validate_flip(batches, model, flip_pairs, criterion=None, decode="argmax", shift_heatmap=False):
+    """validate() with the flip test (the reference's -f/--flip, train_animal.py:556): loss and PCK of flip_forward()'s merged heat-maps.
+    flip_pairs: a sequence of left / right joint pairs or a key of lib.keypoint_detection.FLIP_PAIRS; shift_heatmap: Simple Baselines'
+    one-pixel shift of the flipped output.  With decode="argmax" the predictions are the ones the merge launch decoded as it wrote; "soft"
+    or a callable decode the merged map as in validate().  validate() itself is unchanged: this hands it a model that runs the flip test."""
+    kd.flip_perm(flip_pairs, model.num_keypoints)       # (a bad table fails here, before any forward)
+    fused = isinstance(decode, str) and decode == "argmax"
+    flipped = _FlipTestModel(model, flip_pairs, shift_heatmap, fused)
+    return validate(batches, flipped, criterion, decode=flipped.decoded if fused else decode)
 
 
 class GraphedTrainStep:

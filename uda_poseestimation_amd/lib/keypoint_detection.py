@@ -1,5 +1,6 @@
 """Arg-max decode and PCK (API mirror of the reference's lib/keypoint_detection.py:9-94) on MI355X kernels, and the soft-argmax
-decode the reference lacks (`soft_argmax`, csrc/softargmax.hip: sub-pixel coordinates, differentiable).
+decode the reference lacks (`soft_argmax`, csrc/softargmax.hip: sub-pixel coordinates, differentiable), and the flip test's heat-map side
+(`flip_perm`, `flip_back`, `flip_merge`, csrc/flip.hip: flip back, swap left / right joints, average, decode - one launch).
 
 The reference takes numpy arrays (it is called on `.cpu().numpy()` copies, train_human.py:289,443).  The same calls work
 here; torch CUDA tensors are accepted as well and avoid the 2 x 8.4 MB device->host copy per iteration: decode and PCK
@@ -148,3 +149,87 @@ def accuracy(output, target, hm_type='gaussian', thr=0.5, decode="argmax"):
     ac = avg_cnt.cpu()
     acc_np = acc.cpu().numpy().astype(np.float64)
     return acc_np, float(ac[0]), int(ac[1]), (pred.cpu().numpy() if is_np else pred)
+
+
+# ---------------------------------------------------------------------------------------------------------------- flip test
+# Left / right partner joints per key-point layout (lib/datasets/util.py:186-224 `shufflelr_ori`; the left / right groups of
+# lib/datasets/keypoint_dataset.py:93-97,170-177,214-217).  A mirrored hand has no partner joints.
+FLIP_PAIRS = {
+    "body16": ((0, 5), (1, 4), (2, 3), (10, 15), (11, 14), (12, 13)),
+    "animal18": ((0, 1), (3, 4), (5, 6), (8, 9), (10, 11), (12, 13), (14, 15), (16, 17)),
+    "animal14": ((0, 1), (2, 3), (4, 5), (6, 7), (8, 9), (10, 11), (12, 13)),
+    "hand21": (),
+}
+_PERM_CACHE = {}      # (permutation, device) -> its device copy: a loop uploads a table once
+
+
+def flip_perm(flip_pairs, num_keypoints):
+    """The channel permutation of a horizontal flip as a CPU int32 tensor [K]: perm[i] = j and perm[j] = i for every pair (i, j), perm[k] = k
+    for unpaired joints.  flip_pairs: a sequence of pairs or a key of FLIP_PAIRS.  ValueError for an index outside [0, K), a joint in two
+    pairs or a pair (i, i)."""
+    if isinstance(flip_pairs, str):
+        if flip_pairs not in FLIP_PAIRS:
+            raise ValueError(f"unknown flip-pair table {flip_pairs!r}: one of {sorted(FLIP_PAIRS)} or a sequence of pairs")
+        flip_pairs = FLIP_PAIRS[flip_pairs]
+    K = int(num_keypoints)
+    perm = list(range(K))
+    for pair in flip_pairs:
+        i, j = (int(v) for v in pair)
+        if not (0 <= i < K and 0 <= j < K):
+            raise ValueError(f"flip pair ({i}, {j}) is out of range for {K} key points")
+        if i == j:
+            raise ValueError(f"flip pair ({i}, {j}) pairs a joint with itself")
+        if perm[i] != i or perm[j] != j:
+            raise ValueError(f"flip pair ({i}, {j}): a joint is in two pairs")
+        perm[i], perm[j] = j, i
+    return torch.tensor(perm, dtype=torch.int32)
+
+
+def _perm_device(flip_pairs, num_keypoints, device):
+    perm = flip_perm(flip_pairs, num_keypoints)
+    key = (tuple(perm.tolist()), device)
+    d = _PERM_CACHE.get(key)
+    if d is None:
+        d = _PERM_CACHE[key] = perm.to(device)
+    return d
+
+
+def _flip_merge(a, f, perm, shift, decode, out=None):
+    """udapose_flip_merge on fp32 contiguous CUDA heat-maps: a None -> flip back only.  Returns (out, preds, maxvals); the last two None
+    without decode.  out: where to write (may be `a`), a new tensor by default."""
+    B, K, H, W = f.shape
+    if out is None:
+        out = torch.empty_like(f)
+    preds = maxv = None
+    if decode:
+        preds = torch.empty(B, K, 2, dtype=torch.float32, device=f.device)
+        maxv = torch.empty(B, K, 1, dtype=torch.float32, device=f.device)
+    check(lib().udapose_flip_merge(_hip.stream(), ptr(a), ptr(f), ptr(perm), B, K, H, W, int(bool(shift)), int(a is not None), ptr(out),
+                                   ptr(maxv), None, ptr(preds)), "flip_merge")
+    return out, preds, maxv
+
+
+def flip_back(output_flipped, flip_pairs, shift=False):
+    """The network's heat-maps [B,K,H,W] of a mirrored batch, flipped back: columns reversed and left / right channels swapped
+    (`flip_pairs`: a sequence of pairs or a key of FLIP_PAIRS); shift=True moves the result one pixel to the right (column 0 is kept), as
+    Simple Baselines does before averaging.  numpy in -> numpy out, tensor in -> tensor out."""
+    is_np = isinstance(output_flipped, np.ndarray)
+    f = _dev_f32(output_flipped)
+    out, _, _ = _flip_merge(None, f, _perm_device(flip_pairs, f.shape[1], f.device), shift, False)
+    return out.cpu().numpy().astype(output_flipped.dtype, copy=False) if is_np else out
+
+
+def flip_merge(output, output_flipped, flip_pairs, shift=False, decode=False):
+    """The flip test's average: (output + flip_back(output_flipped, flip_pairs, shift)) * 0.5 as [B,K,H,W] fp32.  decode=True returns
+    (merged, preds [B,K,2], maxvals [B,K,1]) with the arg-max decode of `merged` (what get_max_preds gives for it) out of the same
+    launch.  numpy in -> numpy out, tensor in -> tensor out."""
+    is_np = isinstance(output, np.ndarray)
+    a, f = _dev_f32(output), _dev_f32(output_flipped)
+    if a.shape != f.shape:
+        raise ValueError(f"output {tuple(a.shape)} and output_flipped {tuple(f.shape)} differ in shape")
+    out, preds, maxv = _flip_merge(a, f, _perm_device(flip_pairs, f.shape[1], f.device), shift, decode)
+    if is_np:
+        out = out.cpu().numpy().astype(output.dtype, copy=False)
+        return (out, preds.cpu().numpy(), maxv.cpu().numpy().astype(output.dtype, copy=False)) if decode else out
+    return (out, preds, maxv) if decode else out
+

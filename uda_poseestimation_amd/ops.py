@@ -407,3 +407,16 @@ def style_stat_loss(stats, out, accumulate=False):
     """out (+)= mean over (n, c) of (m - m_t)^2 + (sd - sd_t)^2, stats [N, C, 4] from adain(..., stats_only=True)."""
     check(lib().udapose_style_stat_loss(stream(), ptr(stats), stats.numel() // 4, ptr(out), int(accumulate)), "style_stat_loss")
     return out
+
+
+def hflip_batch(x, keep_original=False):
+    """[N,C,H,W] fp32 -> the batch mirrored left-right (torch.flip(x, [3])); keep_original: [2N,C,H,W], the batch followed by its
+    mirror image, written by one launch (the flip test's 2N input without a torch.cat)."""
+    require_cuda(x)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("hflip_batch expects a 4-d fp32 tensor")
+    x = x.contiguous()
+    N, Cc, H, W = x.shape
+    out = torch.empty((2 * N if keep_original else N, Cc, H, W), dtype=torch.float32, device=x.device)
+    check(lib().udapose_hflip_batch(stream(), ptr(x), ptr(out), N, Cc * H, W, int(bool(keep_original))), "hflip_batch")
+    return out
