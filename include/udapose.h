@@ -384,6 +384,22 @@ int udapose_cons_kl_fwd(void* stream, const float* stu, const float* tea, const 
 /* d stu_i = c mask[r] (p_i S_r - v_i u_i) */
 int udapose_cons_kl_bwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
                         const float* valid_count, int log_target, const float* stats, const float* gscale, int R, int K, int HW, float* dstu);
+/* CORAL through n x n Gram matrices (GramCoralLoss; the reference's CoralLoss, lib/models/loss.py:176-208, without its D x D covariances).
+ * src, tgt: fp32 NCHW [N][K][H][W].  down >= 1 is the reference's coral_downsample folded into the loads: maps of floor(H/down) x floor(W/down),
+ * each element the mean of the central 2x2 pixels of its down x down block (even down) or the centre pixel (odd down).  D = K * floor(H/down) *
+ * floor(W/down), Xc the batch-centred N x D data, Gab = Xa_c Xb_c^T, S = sum(Gss^2 + Gtt^2 - 2 Gst^2) / (N-1)^2 (clamped at 0):
+ * loss[0] = sqrt(S) / (4 D^2).  The Gram matrices are accumulated by exact-fp32 MFMA in chains of 16 products that are added in fp64, one fp64
+ * partial per work-group, added in fp64 in work-group order (a fixed association) and finished in fp64: no atomics, two runs agree to the bit.
+ * coef: [MP][MP] floats, MP = 2N rounded up to a multiple of 32, written by the forward and read by the backward: k [Gss, -Gst; -Gst^T, Gtt],
+ * k = 1 / (2 D^2 sqrt(S) (N-1)^2), and all zero where S == 0 (a zero gradient where torch's autograd gives NaN).
+ * ws: udapose_coral_ws_bytes bytes, 8-byte aligned.
+ * All three return UDAPOSE_ERR_ARG for a null pointer, N < 2, N > 64, down < 1, or a down-sampled map with no pixels. */
+long long udapose_coral_ws_bytes(int N, int K, int H, int W, int down);
+int udapose_coral_fwd(void* stream, const float* src, const float* tgt, int N, int K, int H, int W, int down, void* ws, float* coef, float* loss);
+/* dsrc, dtgt [N][K][H][W]: gscale[0] (device scalar, NULL = 1) * d loss / d src, d tgt.  Every pixel is written (explicit zeros off the
+ * down-sampling footprints): no prior clear. */
+int udapose_coral_bwd(void* stream, const float* src, const float* tgt, const float* coef, const float* gscale, int N, int K, int H, int W,
+                      int down, float* dsrc, float* dtgt);
 /* Soft-argmax decode (no counterpart in the reference: lib.keypoint_detection.soft_argmax).  Per row h_i of hm [R][H*W], i = y*W + x:
  * (x*, y*) = the first flat arg-max in udapose_heatmap_argmax's order (NaN is the largest value), m = h_i*; O = the whole map
  * (window < 0) or {|x - x*| <= window, |y - y*| <= window} clipped to the map (window 0: the arg-max itself);

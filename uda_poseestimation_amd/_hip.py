@@ -128,6 +128,9 @@ _SIGS = {
     "udapose_cons_softmax_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]),
     "udapose_cons_kl_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
     "udapose_cons_kl_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, vp]),
+    "udapose_coral_ws_bytes": (ll, [ci, ci, ci, ci, ci]),
+    "udapose_coral_fwd": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
+    "udapose_coral_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp]),
     "udapose_soft_argmax_fwd": (ci, [vp, vp, ci, ci, ci, cf, ci, vp, vp, vp, vp]),
     "udapose_soft_argmax_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, cf, ci, vp]),
     "udapose_coord_loss_fwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp]),

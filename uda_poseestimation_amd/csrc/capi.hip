@@ -66,6 +66,9 @@ int sml_cons_fwd(hipStream_t, int, const float*, const float*, const unsigned ch
 int sml_cons_bwd(hipStream_t, int, const float*, const float*, const unsigned char*, const unsigned char*, const float*, const float*,
                  const float*, int, int, int, float*);
 int sa_fwd(hipStream_t, const float*, int, int, int, float, int, float*, float*, int*, float*);
+long long coral_ws_bytes(int, int, int, int, int);
+int coral_fwd(hipStream_t, const float*, const float*, int, int, int, int, int, void*, float*, float*);
+int coral_bwd(hipStream_t, const float*, const float*, const float*, const float*, int, int, int, int, int, float*, float*);
 int sa_bwd(hipStream_t, const float*, const float*, const int*, const float*, int, int, int, float, int, float*);
 int sa_coord_fwd(hipStream_t, const float*, const float*, const float*, const unsigned char*, int, int, int, int, float, int, int, float*, int*,
                  float*, float*);
@@ -515,6 +518,14 @@ int udapose_cons_kl_fwd(void* stream, const float* stu, const float* tea, const 
 int udapose_cons_kl_bwd(void* stream, const float* stu, const float* tea, const unsigned char* mask, const unsigned char* valid,
                         const float* valid_count, int log_target, const float* stats, const float* gscale, int R, int K, int HW, float* dstu) {
     return sml_cons_bwd(S(stream), log_target ? 1 : 2, stu, tea, mask, valid, valid_count, stats, gscale, R, K, HW, dstu);
+}
+long long udapose_coral_ws_bytes(int N, int K, int H, int W, int down) { return coral_ws_bytes(N, K, H, W, down); }
+int udapose_coral_fwd(void* stream, const float* src, const float* tgt, int N, int K, int H, int W, int down, void* ws, float* coef, float* loss) {
+    return coral_fwd(S(stream), src, tgt, N, K, H, W, down, ws, coef, loss);
+}
+int udapose_coral_bwd(void* stream, const float* src, const float* tgt, const float* coef, const float* gscale, int N, int K, int H, int W,
+                      int down, float* dsrc, float* dtgt) {
+    return coral_bwd(S(stream), src, tgt, coef, gscale, N, K, H, W, down, dsrc, dtgt);
 }
 int udapose_soft_argmax_fwd(void* stream, const float* hm, int R, int H, int W, float beta, int window, float* coords, float* maxvals,
                             int* flat_idx, float* stats) {

@@ -220,6 +220,13 @@ class MeanTeacherTrainer:
         self.criterion = criterion if criterion is not None else JointsMSELoss()
         self.con_criterion = con_criterion if con_criterion is not None else ConsLoss()
         self.ent_criterion, self.lambda_ent = ent_criterion, lambda_ent
+        # coral_criterion (optional, e.g. GramCoralLoss): lambda_coral * coral_criterion(y_s, y_t_stu) joins loss_all - the student's source
+        # heat-maps against its OWN output on the target view BEFORE the re-warp (the re-warp zero-fills borders, and CORAL aligns output
+        # statistics).  The covariances are over this rank's batch, like the BatchNorm statistics: no collective.  Both are ATTRIBUTES, set
+        # after construction like the switches below (trainer.coral_criterion = GramCoralLoss(2); trainer.lambda_coral = 0.5) and before a
+        # GraphedTrainStep is built from the trainer: the constructor's parameter list is pinned by tests/test_soft_argmax_cpu.py and
+        # tests/test_warp_bilinear_cpu.py.
+        self.coral_criterion, self.lambda_coral = None, 0.0
         # precision: None keeps what the networks are set to (a new PoseResNet is 'auto': a differentiable forward outside
         # autocast runs bf16, the teacher's no-grad forward the fp32-grade 'f16x2' mode).
         # 'reference' = the reference's own precision mix (train_human.py:346-358,414): the student in fp16 (its autocast dtype)
@@ -455,7 +462,7 @@ class MeanTeacherTrainer:
                 activates, y_t_tea_rect = mt.activations_and_rectify(y_t_tea_recon, self.sigma)
             else:
                 activates, y_t_tea_rect = mt.heatmap_activations(y_t_tea_recon), None
-        return {"y_s": y_s, "y_t_stu_recon": y_t_stu_recon, "y_t_tea_recon": y_t_tea_recon, "activates": activates, "y_t_tea_rect": y_t_tea_rect,
+        return {"y_s": y_s, "y_t_stu": y_t_stu, "y_t_stu_recon": y_t_stu_recon, "y_t_tea_recon": y_t_tea_recon, "activates": activates, "y_t_tea_rect": y_t_tea_rect,
                 "label_s": label_s, "weight_s": weight_s, "main": main, "s_stu": s_stu}
 
     def _overlap(self):
@@ -511,6 +518,10 @@ class MeanTeacherTrainer:
         if self.ent_criterion is not None:
             loss_ent = self.ent_criterion(st["y_t_stu_recon"])
             loss_all = loss_all + self.lambda_ent * loss_ent
+        loss_coral = None
+        if self.coral_criterion is not None:
+            loss_coral = self.coral_criterion(st["y_s"], st["y_t_stu"])
+            loss_all = loss_all + self.lambda_coral * loss_coral
         self.stu_optimizer.scale_loss(loss_all).backward()      # (scaler.scale(loss_all).backward(), train_human.py:436; identity in bf16)
         if s_stu is not main:
             main.wait_stream(s_stu)             # the target-domain backward ran on its own stream
@@ -533,6 +544,9 @@ class MeanTeacherTrainer:
                "tea_mask": tea_mask, "y_t_tea_recon": st["y_t_tea_recon"], "y_t_stu_recon": st["y_t_stu_recon"].detach()}
         if loss_ent is not None:
             out["loss_ent"] = loss_ent.detach()
+        if loss_coral is not None:
+            out["loss_coral"] = loss_coral.detach()
+            out["y_t_stu"] = st["y_t_stu"].detach()      # (what the criterion saw beside y_s: the target heat-maps before the re-warp)
         return out
 
     def _forward_backward(self, x_s, label_s, weight_s, x_t_stu, x_t_teas, theta_stu, thetas_tea):
@@ -688,6 +702,7 @@ class GraphedTrainStep:
         # it back one step late through a pinned double buffer, so a loop that logs every iteration never drains the device
         self.metrics = bool(metrics)
         self._mvec, self._mpin, self._mev, self._mi, self._mk, self._macc = None, None, [None, None], 0, 0, None
+        self._mextra = []
         self.styled = trainer.style_net is not None
         self.occl = trainer.occlude_rate > -1
         if self.occl and not trainer.device_occlusion:
@@ -943,8 +958,8 @@ class GraphedTrainStep:
         else:
             acc, avg_cnt, _ = kd.accuracy_device(self.out["y_s"], self.static["label_s"])
         parts = [self.out["loss_all"].reshape(1), self.out["loss_s"].reshape(1), self.out["loss_c"].reshape(1), avg_cnt.reshape(2), acc.reshape(-1)]
-        if "loss_ent" in self.out:           # (appended: the layout without an entropy criterion is unchanged)
-            parts.append(self.out["loss_ent"].reshape(1))
+        self._mextra = [k for k in ("loss_ent", "loss_coral") if k in self.out]      # (appended in this order: the layout without them is unchanged)
+        parts += [self.out[k].reshape(1) for k in self._mextra]
         self._mk = int(acc.numel())
         self._mvec = torch.cat([p.float() for p in parts])
         self.out["acc_s"], self.out["acc_avg_cnt"] = acc, avg_cnt
@@ -967,8 +982,8 @@ class GraphedTrainStep:
     def _metrics_dict(self, v):
         v = v.tolist()
         d = {"loss_all": v[0], "loss_s": v[1], "loss_c": v[2], "acc_s": v[3], "cnt_s": int(v[4]), "acc_per_keypoint": v[5:5 + self._mk]}
-        if len(v) > 5 + self._mk:
-            d["loss_ent"] = v[5 + self._mk]
+        for i, k in enumerate(self._mextra):
+            d[k] = v[5 + self._mk + i]
         return d
 
     def step_async(self, *args, **kw):

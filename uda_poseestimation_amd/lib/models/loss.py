@@ -3,7 +3,8 @@
 JointsMSELoss and ConsLoss are what the training scripts instantiate (train_human.py:133-134).  JointsKLLoss, EntLoss,
 ConsSoftmaxLoss and ConsKLLoss (loss.py:52-173) are the soft-max family a user swaps in (csrc/softmax_loss.hip: a row
 soft-max over the H*W pixels of every (b,k) heat-map fused with the loss, its reduction and its backward).  CoralLoss is
-defined and refuses construction: see its docstring.  JointsSoftArgmaxLoss and ConsSoftArgmaxLoss have no counterpart in the reference:
+defined and refuses construction: see its docstring; GramCoralLoss is the same loss through n x n Gram matrices (csrc/coral.hip).
+JointsSoftArgmaxLoss and ConsSoftArgmaxLoss have no counterpart in the reference:
 they are losses on the soft-argmax COORDINATES of the student's heat-maps (csrc/softargmax.hip), a gradient on where the peak is.
 Each forward is one sweep over the operands (per-(b,k) row partial + a tiny row reduction), each backward one sweep.
 """
@@ -431,10 +432,64 @@ class ConsSoftArgmaxLoss(nn.Module):
 class CoralLoss(nn.Module):
     """Not available.  The reference's CoralLoss (loss.py:176-208) forms the covariance of the flattened heat-maps, a
     (K*H*W) x (K*H*W) matrix - 65 536 squared, 17 GB in fp32, at K = 16 and 64x64 maps: a dense GEMM workload unrelated to the row
-    kernels of this module, and no script of the reference reaches it.  There is no eager fallback, so the constructor refuses."""
+    kernels of this module, and no script of the reference reaches it.  There is no eager fallback, so the constructor refuses.
+    The loss itself (without `prior`, a D x D matrix that cannot exist here) is GramCoralLoss below: the same value and gradients
+    through n x n Gram matrices."""
 
     def __init__(self, coral_downsample, prior=None):
         super(CoralLoss, self).__init__()
         raise NotImplementedError("CoralLoss is not implemented on the device: it needs the (K*H*W) x (K*H*W) covariance of the flattened "
                                   "heat-maps (17 GB in fp32 at K = 16, 64x64), a dense GEMM workload that no training script reaches; "
                                   "this package has no eager fallback")
+
+
+class _GramCoralFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, tgt, down):
+        _hip.require_cuda(src, tgt)
+        if src.dim() != 4 or tuple(src.shape) != tuple(tgt.shape):
+            raise ValueError(f"GramCoralLoss needs two [N,K,H,W] heat-map batches of one shape, got {tuple(src.shape)} and {tuple(tgt.shape)}")
+        N, K, H, W = src.shape
+        if N < 2 or N > 64:
+            raise ValueError(f"GramCoralLoss: the batch size must be 2 ... 64 (a covariance needs two samples; the kernels hold 2N <= 128 rows), got {N}")
+        if H // down < 1 or W // down < 1:
+            raise ValueError(f"GramCoralLoss: coral_downsample {down} leaves no pixel of a {H}x{W} map")
+        s, t = _f32c(src), _f32c(tgt)
+        mp = (2 * N + 31) // 32 * 32
+        ws = torch.empty(int(lib().udapose_coral_ws_bytes(N, K, H, W, down)) // 8, dtype=torch.float64, device=s.device)
+        coef = torch.empty(mp * mp, dtype=torch.float32, device=s.device)
+        out = torch.empty((), dtype=torch.float32, device=s.device)
+        check(lib().udapose_coral_fwd(_hip.stream(), ptr(s), ptr(t), N, K, H, W, down, ptr(ws), ptr(coef), ptr(out)), "coral_fwd")
+        ctx.save_for_backward(s, t, coef)
+        ctx.down, ctx.shape, ctx.dtypes = down, src.shape, (src.dtype, tgt.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        s, t, coef = ctx.saved_tensors
+        N, K, H, W = ctx.shape
+        ds, dt = torch.empty_like(s), torch.empty_like(t)
+        gs = _gscale(g)
+        check(lib().udapose_coral_bwd(_hip.stream(), ptr(s), ptr(t), ptr(coef), ptr(gs), N, K, H, W, ctx.down, ptr(ds), ptr(dt)), "coral_bwd")
+        return ds.to(ctx.dtypes[0]), dt.to(ctx.dtypes[1]), None
+
+
+class GramCoralLoss(nn.Module):
+    """The reference's CoralLoss (loss.py:176-208, without `prior`), called as it is: loss = crit(src_out, tgt_out) on two [N,K,H,W] batches,
+    || Cs - Ct ||_F / (4 D^2) with Cs, Ct the D x D covariances over the batch of the flattened (down-sampled) maps, D = K*H'*W'.
+    Those matrices are never formed: with Xc the batch-centred N x D data and Gab = Xa_c Xb_c^T (N x N),
+    ||Cs - Ct||_F^2 = sum(Gss^2 + Gtt^2 - 2 Gst^2) / (N-1)^2, and the gradients are k (Gss Xs - Gst Xt) and k (Gtt Xt - Gst^T Xs): one
+    streaming pass over the 2N x D data forward (exact-fp32 MFMA, finished in fp64), one backward; gradients flow to BOTH inputs.
+    coral_downsample = d > 1 is F.interpolate(scale_factor=1/d, mode='bilinear') folded into the loads: the mean of the central 2x2
+    pixels of every d x d block (even d), the centre pixel (odd d), floor(H/d) x floor(W/d) of them.
+    N must be 2 ... 64.  Where the two covariances are equal (S == 0: e.g. crit(x, x)) the loss is 0 and the gradients are ZERO; torch's
+    autograd of the reference's expression gives NaN there (the derivative of sqrt at 0).  Covariances are per rank under data parallel."""
+
+    def __init__(self, coral_downsample=1):
+        super(GramCoralLoss, self).__init__()
+        if int(coral_downsample) != coral_downsample or coral_downsample < 1:
+            raise ValueError(f"coral_downsample must be an integer >= 1, got {coral_downsample!r}")
+        self.coral_downsample = int(coral_downsample)
+
+    def forward(self, src_out, tgt_out):
+        return _GramCoralFn.apply(src_out, tgt_out, self.coral_downsample)
