@@ -427,6 +427,32 @@ int udapose_coord_loss_bwd(void* stream, const float* hm, const float* target, c
  * be NULL.  patch: [(2*rad+1)^2] fp32 Gaussian table built by the caller exactly as utils.py:93-98 does. */
 int udapose_heatmap_argmax(void* stream, const float* hm, int R, int H, int W, float* maxvals, int* flat_idx, float* preds_xy,
                            float* rectified, const float* patch, int rad);
+/* Skeleton-prior maps: generate_prior_map (utils.py:111-145) without its [B][K][K][H][W] tensors.  Every joint i decoded from a heat-map casts a
+ * ring of radius mean[i][j] round itself for every joint j: t_ij(x, y) = exp(-(d_i - mean[i][j])^2 / (2 sigma^2)), d_i = |(x, y) - (cx_i, cy_i)|
+ * (x pairs with preds_xy[..][0], y with [..][1]), and out[b][j] = sum_i f[i][j] t_ij.
+ * udapose_prior_weights writes the [K][K] table w in one small launch.  Default mode (v3 = 0, utils.py:139-141): the soft-max over i of
+ * -std[i][j] / gamma with the diagonal set to epsilon first, max subtracted: std = +inf weighs exactly 0, and so does the diagonal for K > 1
+ * with the reference's epsilon = -10e10 (at K = 1 it weighs 1).  v3 = 1 (utils.py:132): 1 / (1 + std[i][j]), diagonal included; gamma and
+ * epsilon are not read.  UDAPOSE_ERR_ARG: a null pointer, K < 1, gamma 0 or not finite, epsilon NaN; UDAPOSE_ERR_UNSUPPORTED: K > 64. */
+int udapose_prior_weights(void* stream, const float* std_table, int K, float gamma, float epsilon, int v3, float* w);
+/* coords [B][K][2], conf [B][K]: preds_xy and maxvals of udapose_heatmap_argmax (a row with a maximum <= 0 casts its rings from (0, 0), as in the
+ * reference).  f = w (v3 = 0; conf may be NULL) or conf[b][i] * w[i][j] (v3 = 1, utils.py:133-136: negative and NaN confidences pass through).
+ * out [B][K][H][W]; with hm [B][K][H][W] given, out = hm * map (one fp32 multiply; the reference's "multiplier for the original prediction map").
+ * One work-group per image and run of 256 pixels; coordinates and tables staged in LDS ((2 K ceil8(K) + 2 K) * 4 bytes), d_i once per pixel and
+ * pass of 8 outputs, one hardware exponential per term with log2(e) / (2 sigma^2) folded in.  Every element of out is written; no atomics, no
+ * scratch, no allocation (capturable).  UDAPOSE_ERR_ARG: a null pointer (hm may be NULL), B, K, H or W < 1, sigma not finite or <= 0;
+ * UDAPOSE_ERR_UNSUPPORTED: K > 64, H * W > 2^30.  Nothing is launched on an error. */
+int udapose_prior_map(void* stream, const float* coords, const float* conf, const float* mean, const float* w, const float* hm, int B, int K, int H,
+                      int W, float sigma, int v3, float* out);
+/* The tables of a prior (the reference builds none: `prior` of utils.py:111 arrives from nowhere).  coords [M][K][2] fp32, visible [M][K] bytes
+ * (non-zero = visible); acc fp64 [3][K][K] = (count, sum d, sum d^2) per pair (i, j) over the samples where both joints are visible, d in fp64
+ * from the fp32 coordinates; the call ADDS to acc (the caller clears it once).  One work-group per pair, a fixed-order tree, one thread adds the
+ * partial into acc: the same batches in the same order give the same bits.  UDAPOSE_ERR_ARG: a null pointer, M < 1, K < 1;
+ * UDAPOSE_ERR_UNSUPPORTED: K > 64. */
+int udapose_pair_dist_accumulate(void* stream, const float* coords, const unsigned char* visible, int M, int K, double* acc);
+/* mean [K][K], std_table [K][K] fp32: sum d / n and the population standard deviation sqrt(max(sum d^2 / n - mean^2, 0)), computed in fp64
+ * and rounded once.  A pair never seen: mean 0, std +inf, which weighs 0 in both modes of udapose_prior_weights. */
+int udapose_pair_dist_finish(void* stream, const double* acc, int K, float* mean, float* std_table);
 /* Flip test (the -f/--flip evaluation of the reference's animal scripts, train_animal.py:556; pairing tables lib/datasets/util.py:186-224):
  * the image side.  src [N][rows_per_image][W] fp32 (an NCHW image batch: rows_per_image = 3*H).  keep_original = 1: dst [2N][rows][W],
  * dst[0:N] = src and dst[N:2N][r][x] = src[r][W-1-x] - the batch and its mirror image in one launch; keep_original = 0: dst [N][rows][W]

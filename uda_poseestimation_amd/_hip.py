@@ -136,6 +136,10 @@ _SIGS = {
     "udapose_coord_loss_fwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp]),
     "udapose_coord_loss_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, ci, ci, vp]),
     "udapose_heatmap_argmax": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci]),
+    "udapose_prior_weights": (ci, [vp, vp, ci, cf, cf, ci, vp]),
+    "udapose_prior_map": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, ci, vp]),
+    "udapose_pair_dist_accumulate": (ci, [vp, vp, vp, ci, ci, vp]),
+    "udapose_pair_dist_finish": (ci, [vp, vp, ci, vp, vp]),
     "udapose_hflip_batch": (ci, [vp, vp, vp, ci, sz, ci, ci]),
     "udapose_flip_merge": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
     "udapose_kth_mask": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, ci]),

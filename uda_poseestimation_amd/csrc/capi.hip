@@ -86,6 +86,10 @@ int pw_split_to_f32(hipStream_t, const void*, float*, size_t);
 int pw_maxpool2x2_ceil_split(hipStream_t, const void*, void*, int, int, int, int);
 int hm_argmax_rectify(hipStream_t, const float*, int, int, int, float*, int*, float*, float*, const float*, int);
 int hm_kth_mask(hipStream_t, const float*, const float*, int, int, float*, unsigned char*, const float*, int);
+int pm_weights(hipStream_t, const float*, int, float, float, int, float*);
+int pm_map(hipStream_t, const float*, const float*, const float*, const float*, const float*, int, int, int, int, float, int, float*);
+int pm_pair_accumulate(hipStream_t, const float*, const unsigned char*, int, int, double*);
+int pm_pair_finish(hipStream_t, const double*, int, float*, float*);
 int hm_pck(hipStream_t, const float*, const float*, int, int, float, float, float, float*, float*);
 int opt_chunk();
 int opt_ema(hipStream_t, const long long*, const long long*, const long long*, const int*, const long long*, int, float, float);
@@ -547,6 +551,19 @@ int udapose_heatmap_argmax(void* stream, const float* hm, int R, int H, int W, f
                            const float* patch, int rad) {
     if (rect && !patch) return UDAPOSE_ERR_ARG;
     return hm_argmax_rectify(S(stream), hm, R, H, W, maxvals, flat_idx, preds, rect, patch, rad);
+}
+int udapose_prior_weights(void* stream, const float* std_table, int K, float gamma, float epsilon, int v3, float* w) {
+    return pm_weights(S(stream), std_table, K, gamma, epsilon, v3, w);
+}
+int udapose_prior_map(void* stream, const float* coords, const float* conf, const float* mean, const float* w, const float* hm, int B, int K, int H,
+                      int W, float sigma, int v3, float* out) {
+    return pm_map(S(stream), coords, conf, mean, w, hm, B, K, H, W, sigma, v3, out);
+}
+int udapose_pair_dist_accumulate(void* stream, const float* coords, const unsigned char* visible, int M, int K, double* acc) {
+    return pm_pair_accumulate(S(stream), coords, visible, M, K, acc);
+}
+int udapose_pair_dist_finish(void* stream, const double* acc, int K, float* mean, float* std_table) {
+    return pm_pair_finish(S(stream), acc, K, mean, std_table);
 }
 int udapose_hflip_batch(void* stream, const float* src, float* dst, int N, size_t rows_per_image, int W, int keep_original) {
     return flip_hbatch(S(stream), src, dst, N, rows_per_image, W, keep_original);

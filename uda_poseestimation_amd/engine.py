@@ -227,6 +227,12 @@ class MeanTeacherTrainer:
         # GraphedTrainStep is built from the trainer: the constructor's parameter list is pinned by tests/test_soft_argmax_cpu.py and
         # tests/test_warp_bilinear_cpu.py.
         self.coral_criterion, self.lambda_coral = None, 0.0
+        # skeleton_prior (optional): {'mean', 'std'} [K,K] tables, e.g. utils.SkeletonPrior(K, device).finalize() over source labels.  When set,
+        # the teacher's re-warped mean heat-map is replaced by generate_prior_map(prior, it, prior_gamma, prior_sigma, v3=prior_v3,
+        # multiply=True) - the map times the structural prior of its own decoded joints (utils.py:111-145) - and everything downstream sees the
+        # product: the occlusion picks, `activates`, the confidence mask, rectify.  Attributes like the two above, set before a GraphedTrainStep
+        # is built.  Data parallel: the tables are the same on every rank; nothing is communicated.
+        self.skeleton_prior, self.prior_gamma, self.prior_sigma, self.prior_v3 = None, 2, 2, False
         # precision: None keeps what the networks are set to (a new PoseResNet is 'auto': a differentiable forward outside
         # autocast runs bf16, the teacher's no-grad forward the fp32-grade 'f16x2' mode).
         # 'reference' = the reference's own precision mix (train_human.py:346-358,414): the student in fp16 (its autocast dtype)
@@ -428,12 +434,18 @@ class MeanTeacherTrainer:
             y_t_teas = [teacher(x_t) for x_t in x_t_teas]
             recons = [warp.warp_chain(y, th, self.warp_mode) for y, th in zip(y_t_teas, thetas_tea)]
             y_t_tea_recon = warp.mean_views(recons)          # (k teacher views, train_human.py:361-372: one launch; k = 1: the view itself)
+            tea_out = [y_t_tea_recon]
+            if self.skeleton_prior is not None:
+                y_t_tea_raw = y_t_tea_recon
+                y_t_tea_recon = mt.generate_prior_map(self.skeleton_prior, y_t_tea_raw, self.prior_gamma, self.prior_sigma, v3=self.prior_v3,
+                                                      multiply=True)
+                tea_out = [y_t_tea_raw, y_t_tea_recon]
         if occl is not None:
             # the occlusion needs the teacher's re-warped heat-maps: the source-domain forward is issued first (it runs under
             # the teacher's), the target-domain branch waits for the teacher
             y_s = student(x_s)
             s_stu.wait_stream(s_tea)
-            for t in y_t_teas + recons + [y_t_tea_recon]:
+            for t in y_t_teas + recons + tea_out:
                 t.record_stream(s_stu)
         with torch.cuda.stream(s_stu):
             if occl is not None:
@@ -454,7 +466,7 @@ class MeanTeacherTrainer:
         for t in (y_t_stu, y_t_stu_recon, x_t_stu):
             t.record_stream(main)
         main.wait_stream(s_tea)
-        for t in y_t_teas + recons + [y_t_tea_recon]:
+        for t in y_t_teas + recons + tea_out:
             t.record_stream(main)
         with torch.no_grad():
             # activates from the heat-maps BEFORE rectify (train_human.py:427); the rectified maps (:431) come out of the same arg-max sweep
@@ -462,8 +474,11 @@ class MeanTeacherTrainer:
                 activates, y_t_tea_rect = mt.activations_and_rectify(y_t_tea_recon, self.sigma)
             else:
                 activates, y_t_tea_rect = mt.heatmap_activations(y_t_tea_recon), None
-        return {"y_s": y_s, "y_t_stu": y_t_stu, "y_t_stu_recon": y_t_stu_recon, "y_t_tea_recon": y_t_tea_recon, "activates": activates, "y_t_tea_rect": y_t_tea_rect,
-                "label_s": label_s, "weight_s": weight_s, "main": main, "s_stu": s_stu}
+        st = {"y_s": y_s, "y_t_stu": y_t_stu, "y_t_stu_recon": y_t_stu_recon, "y_t_tea_recon": y_t_tea_recon, "activates": activates, "y_t_tea_rect": y_t_tea_rect,
+              "label_s": label_s, "weight_s": weight_s, "main": main, "s_stu": s_stu}
+        if self.skeleton_prior is not None:
+            st["y_t_tea_raw"] = y_t_tea_raw
+        return st
 
     def _overlap(self):
         on = self.overlap_allreduce
@@ -547,6 +562,9 @@ class MeanTeacherTrainer:
         if loss_coral is not None:
             out["loss_coral"] = loss_coral.detach()
             out["y_t_stu"] = st["y_t_stu"].detach()      # (what the criterion saw beside y_s: the target heat-maps before the re-warp)
+        if "y_t_tea_raw" in st:
+            # (y_t_tea_recon above IS the product: the teacher's map as the rest of the step saw it)
+            out["prior_map"], out["y_t_tea_raw"] = st["y_t_tea_recon"], st["y_t_tea_raw"]
         return out
 
     def _forward_backward(self, x_s, label_s, weight_s, x_t_stu, x_t_teas, theta_stu, thetas_tea):

@@ -175,6 +175,122 @@ def confidence_mask(recon, mask_ratio, tea_mask=None, gathered_activates=None, a
     return mask.view(torch.bool), act, thr        # (the kernel writes 0 / 1: a bool view, not a conversion launch)
 
 
+PRIOR_MAX_KEYPOINTS = 64
+_PRIOR_CACHE = {}       # (tables' storage and version, gamma, epsilon, v3, device) -> (the caller's tensors, mean and weight table on the device)
+
+
+def _prior_tables(prior, K, gamma, epsilon, v3, device):
+    """fp32 device copies of prior['mean'] and of the [K,K] weight table udapose_prior_weights makes of prior['std'].  Cached on what they were
+    made from, so a second call uploads and launches nothing (a captured step must find its tables here: call once before capturing)."""
+    mean, std = prior["mean"], prior["std"]
+    for name, t in (("mean", mean), ("std", std)):
+        if not torch.is_tensor(t) or tuple(t.shape) != (K, K):
+            raise ValueError(f"generate_prior_map: prior[{name!r}] must be a [{K}, {K}] tensor for {K} heat-map channels, got "
+                             f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    key = (mean.data_ptr(), mean._version, str(mean.device), std.data_ptr(), std._version, str(std.device), float(gamma), float(epsilon), bool(v3),
+           str(device))
+    hit = _PRIOR_CACHE.get(key)
+    if hit is None:
+        mean_d = mean.detach().to(device=device, dtype=torch.float32).contiguous()
+        std_d = std.detach().to(device=device, dtype=torch.float32).contiguous()
+        w = torch.empty(K, K, dtype=torch.float32, device=device)
+        check(lib().udapose_prior_weights(_hip.stream(), ptr(std_d), K, float(gamma), float(epsilon), int(bool(v3)), ptr(w)), "prior_weights")
+        while len(_PRIOR_CACHE) >= 16:
+            _PRIOR_CACHE.pop(next(iter(_PRIOR_CACHE)))
+        # (the caller's tensors are held too: while the entry lives their addresses cannot be handed to other tables)
+        hit = _PRIOR_CACHE[key] = (mean, std, mean_d, w)
+    return hit[2], hit[3]
+
+
+def generate_prior_map(prior, preds, gamma=2, sigma=2, epsilon=-10e10, v3=False, *, multiply=False):
+    """utils.py:111-145 as ONE kernel behind the arg-max decode.  prior: {'mean': [K,K], 'std': [K,K]} (CPU or device); preds [B,K,H,W] heat-maps
+    (fp32 / fp16 / bf16 on the device).  Joint i, decoded as get_max_preds_torch does, casts a ring of radius mean[i,j] and width sigma for joint j;
+    the rings are ensembled with soft-max(-std / gamma) weights over i (diagonal excluded), or with v3=True with conf_i / (1 + std[i,j]).
+    multiply=True returns preds.float() * map - what the reference's comment says the map is for - from the same launch.
+    Computed in fp32, returned in preds' dtype, without autograd."""
+    _hip.require_cuda(preds)
+    if preds.dim() != 4:
+        raise ValueError(f"generate_prior_map: preds must be [B, K, H, W], got {tuple(preds.shape)}")
+    B, K, H, W = preds.shape
+    if K > PRIOR_MAX_KEYPOINTS:
+        raise ValueError(f"generate_prior_map: {K} key-points (the kernel stages two K x K tables in LDS: K <= {PRIOR_MAX_KEYPOINTS})")
+    if B < 1 or K < 1 or H < 1 or W < 1:
+        raise ValueError(f"generate_prior_map: empty preds {tuple(preds.shape)}")
+    if not (float(sigma) > 0 and np.isfinite(float(sigma))):
+        raise ValueError(f"generate_prior_map: sigma must be finite and > 0, got {sigma}")
+    if not v3 and not (np.isfinite(float(gamma)) and float(gamma) != 0):
+        raise ValueError(f"generate_prior_map: gamma must be finite and non-zero, got {gamma}")
+    mean_d, w = _prior_tables(prior, K, gamma, epsilon, v3, preds.device)
+    hm = preds.detach().float().contiguous()
+    coords = torch.empty(B, K, 2, dtype=torch.float32, device=hm.device)
+    conf = torch.empty(B, K, dtype=torch.float32, device=hm.device)
+    check(lib().udapose_heatmap_argmax(_hip.stream(), ptr(hm), B * K, H, W, ptr(conf), None, ptr(coords), None, None, 0), "heatmap_argmax")
+    out = torch.empty_like(hm)
+    check(lib().udapose_prior_map(_hip.stream(), ptr(coords), ptr(conf), ptr(mean_d), ptr(w), ptr(hm) if multiply else None, B, K, H, W, float(sigma),
+                                  int(bool(v3)), ptr(out)), "prior_map")
+    return out.to(preds.dtype)
+
+
+class SkeletonPrior(object):
+    """Builds the `prior` of generate_prior_map - which the reference takes as given and no script of it computes - from source labels: mean and
+    population standard deviation of the distance between every pair of joints, over the samples where both are visible, in heat-map pixels.
+    Sums are kept in fp64 on the device (count, sum d, sum d^2 per pair); nothing is read back until the caller asks for a value.
+    A pair never seen together gets mean 0 and std +inf, which weighs 0 in both modes of generate_prior_map."""
+
+    def __init__(self, num_keypoints, device="cuda"):
+        self.num_keypoints = int(num_keypoints)
+        if not 1 <= self.num_keypoints <= PRIOR_MAX_KEYPOINTS:
+            raise ValueError(f"SkeletonPrior: num_keypoints must be in [1, {PRIOR_MAX_KEYPOINTS}], got {num_keypoints}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            _hip.require_cuda(torch.empty(0))
+        self._acc = None        # fp64 [3][K][K], allocated by the first update
+
+    def update_coords(self, coords, visible):
+        """coords [M,K,2] (x, y), visible [M,K] (non-zero = visible)."""
+        _hip.require_cuda(coords, visible)
+        K = self.num_keypoints
+        if coords.dim() != 3 or tuple(coords.shape[1:]) != (K, 2) or tuple(visible.shape) != (coords.shape[0], K):
+            raise ValueError(f"SkeletonPrior: coords [M, {K}, 2] and visible [M, {K}] expected, got {tuple(coords.shape)} and {tuple(visible.shape)}")
+        M = coords.shape[0]
+        if M == 0:
+            return self
+        c = coords.detach().float().contiguous()
+        v = visible.detach().ne(0).to(torch.uint8).contiguous()
+        if self._acc is None:
+            self._acc = torch.zeros(3, K, K, dtype=torch.float64, device=c.device)
+        check(lib().udapose_pair_dist_accumulate(_hip.stream(), ptr(c), ptr(v), M, K, ptr(self._acc)), "pair_dist_accumulate")
+        return self
+
+    def update(self, label_s, weight_s=None):
+        """label_s [N,K,H,W] heat-map labels, weight_s [N,K] or [N,K,1] (the loaders' target_weight): a joint is visible where its weight is > 0
+        and its label's maximum is > 0; its position is the label's arg-max (get_max_preds_torch)."""
+        _hip.require_cuda(label_s, weight_s)
+        coords, maxv = get_max_preds_torch(label_s)
+        visible = maxv.float().reshape(maxv.shape[0], maxv.shape[1]) > 0
+        if weight_s is not None:
+            visible = visible & (weight_s.detach().reshape(visible.shape) > 0)
+        return self.update_coords(coords, visible)
+
+    @property
+    def count(self):
+        """[K,K] int64 device tensor: how many samples every pair was seen in."""
+        K = self.num_keypoints
+        if self._acc is None:
+            return torch.zeros(K, K, dtype=torch.int64, device=self.device)
+        return self._acc[0].to(torch.int64)
+
+    def finalize(self):
+        """{'mean', 'std'}: fp32 [K,K] device tensors (new ones on every call) that generate_prior_map accepts."""
+        K = self.num_keypoints
+        if self._acc is None:
+            self._acc = torch.zeros(3, K, K, dtype=torch.float64, device=self.device)
+        mean = torch.empty(K, K, dtype=torch.float32, device=self._acc.device)
+        std = torch.empty_like(mean)
+        check(lib().udapose_pair_dist_finish(_hip.stream(), ptr(self._acc), K, ptr(mean), ptr(std)), "pair_dist_finish")
+        return {"mean": mean, "std": std}
+
+
 def split_saturations(reset=True):
     """How many f16x2 ('fp32-grade' mode) stores since the last reset hit a value outside fp16's range (|v| > 65504 saturates; NaN) - the
     teacher / validate() / style-network forwards of the reference's precision mix.  Sums both library builds; synchronises the device."""
