@@ -46,49 +46,64 @@ int udapose_elem_kind(void);
  * Replaces torch.nn.Conv2d / ConvTranspose2d as used by torchvision Bottleneck (lib/models/resnet.py:8-10,25-40),
  * Upsampling (lib/models/pose_resnet.py:33-43), the head (pose_resnet.py:74) and the VGG encoder / decoder
  * (lib/models/Style_net.py:32-118). */
-/* Explicit dispatch policy (tests force a code path with it, bench.py's tuning flags run A/B comparisons through it).
- * udapose_policy_default fills in the production policy; fields: igemm_tile / wgrad_tile / wgrad_ksplit -1 = heuristics;
- * igemm_h3: run-staged 3x3 form 0 off, 1 measured per-shape policy, 2 / 3 force the 64- / 128-row form; wgrad_group: one grouped weight-gradient launch per tile class in udapose_net_backward (0: layer by layer),
- * wgrad_stages: 64-pixel stages a work-group reduces before a layer's pixel range is split; bn_bwd_fused: dgrad epilogues
- * mask for the consumer BatchNorm and reduce its backward sums; bn_fwd_chunked / bn_bwd_chunked: finalize + apply of the wide,
- * small-spatial BatchNorm layers in one launch (0 off, 1 on, > 1: on with that target work-group count instead of 1024);
- * wgrad_fastgeo: loader of the weight-gradient kernels on power-of-two maps (0 general, 1 bit-field coordinates, 2 buffer loads
- * with out-of-range zero fill and an unrolled ring: the production form); wgrad_row3: weight gradients of 3x3 stride-1 convolutions with one work-group per (64x64 tile, filter row) - the row's three taps
- * share one staged dy tile and one x window (3x the FLOPs per byte filled into LDS, which is what bounds these kernels);
- * igemm_wg_min: 128x64 tiles as soon as they give that many work-groups, else 64x64; bn3_mask: block outputs save a ReLU bit mask
- * that the masking data gradients read instead of z; stem_fused: 1 = the stem's BN + ReLU + max-pool in one sweep, 2 = also the max-pool
- * backward gathered inside the BN backward; timeline: device buffer ([work-groups][8] uint64) for
- * per-work-group s_memrealtime stamps, or NULL. */
+/* Explicit dispatch policy.  The production policy - every default named below, what udapose_policy_default fills in - IS the measured one;
+ * nothing in the library reads an environment variable or a mutable global to choose a kernel.  A network plan owns a copy
+ * (udapose_net_set_policy), a single convolution call names one through its descriptor (udapose_conv_desc.policy, NULL = production).
+ * The other values exist for tests (force a code path) and tuning (A/B runs through bench.py's flags).  One field per line: this list is
+ * the one statement of the fields, and of their order, that the library and its ctypes binding are checked against. */
 typedef struct {
-    int igemm_tile, igemm_h3, igemm_lean, igemm_short_lds, igemm_tap0;
-    int wgrad_tile, wgrad_ksplit, wgrad_fastgeo;
-    int wgrad_group, wgrad_stages, wgrad_group_stem;
-    int bn_bwd_fused, bn_fwd_chunked, bn_bwd_chunked, bn_bwd_pre_legacy;
-    int igemm_wg_min;
-    int wgrad_row3;
-    int bn3_mask;
-    int stem_fused;
-    int debug_sync;
-    int igemm_big_min;    /* > 0: 128x128 tiles (2-stage ring) for single-class launches with Co % 128 == 0 whose 128x64 grid has at least this
-                           * many work-groups - the style network's large maps, run on one stream (+13-18 % there); 0 (default): never */
-    int patch_conv;       /* reflection-padded 3x3 stride-1 convolutions (the style network) through the patch-staged kernels (input patch staged once,
-                           * not once per tap): 0 never (the implicit GEMM for every layer), 1 the 64 -> 3 and 3 -> 64 end layers, 2 (default)
-                           * the trunk layers too, 3 = 2 with 128 output channels per work-group in the 16-bit form */
-    int eval_fold;        /* 1 (default): eval-mode network forwards (validate(), train_human.py:461-500) apply BatchNorm's running-statistics scale /
-                           * shift, the residual and the ReLU in the convolution's epilogue: no BN-apply launch, no pre-BN tensor; 0: conv + apply */
-    int bn_xcd_rows;      /* 1 (default): the BatchNorm apply kernels give XCD k the k-th eighth of the pixel rows - what the implicit GEMMs' work-groups on
-                           * XCD k wrote and will read - so activations cross the conv <-> BatchNorm kernel boundaries through one L2; 0: interleaved */
-    int wgrad_det;        /* 1 (default, round 6): split weight-gradient reductions of the grouped launches store per-split partial tiles into the pass's
-                           * workspace and ONE launch adds them in split order (bit-reproducible gradients; the `loss.backward()` of
-                           * train_human.py:436 run twice gives the same bits); 0: fp32 atomics into cleared tensors, arrival order */
-    int igemm_ns3_k;      /* 64x64 implicit-GEMM tiles take the 3-stage LDS ring from this reduction length on (K = taps x Ci), the 2-stage ring
-                           * below it; 0 = the default, 2048 */
-    void* timeline;       /* NULL, or a device buffer of uint64 [work-groups][8] for timeline stamps (tuning).  The grouped weight-gradient launches
-                           * of a plan stamp {start, end (100 MHz), XCD, table slot, problem, stages | form bits, pass, tile rows} per work-group, the 128x128
-                           * class first, the 64x64 class behind it: the buffer must hold 1 << 17 work-groups (8 MiB); a plan with more refuses */
-    int wgrad_order;      /* grouped weight gradients, the deal of work-groups to the XCDs' lists: 1 (default) = layers cut into runs of 32 work-groups, the runs
-                           * with the most stages per work-group first, so every list ends with its share of the short work-groups; 0 = whole
-                           * (layer, split) units in deal order by unit load.  Same work into the same places either way: bit-identical gradients */
+    int igemm_tile;        /* default -1: the tile heuristics of the implicit GEMM; >= 0 forces that tile configuration id */
+    int igemm_h3;          /* run-staged 3x3 form: 0 off, 1 (default) the measured per-shape policy, 2 / 3 force the 64- / 128-row form */
+    int igemm_lean;        /* 1 (default): the lean 1x1 form (saddr LDS-DMA loads) where eligible */
+    int igemm_short_lds;   /* 1 (default): one-stage LDS request for launches whose K loop is one stage */
+    int igemm_tap0;        /* 1 (default): 1x1 kernels skip the tap-table read */
+    int wgrad_tile;        /* default -1: heuristics; >= 0 forces that weight-gradient tile id */
+    int wgrad_ksplit;      /* default -1: heuristics; > 0 forces the pixel-split count of a per-layer weight-gradient launch */
+    int wgrad_fastgeo;     /* weight-gradient loader on power-of-two maps: 0 general, 1 bit-field pixel coordinates (pointer selects), 2 (default, the
+                            * production form) the same through buffer loads to LDS with out-of-range zero fill and an unrolled ring (wgrad_fast2_body) */
+    int wgrad_group;       /* 1 (default): udapose_net_backward runs one grouped weight-gradient launch per tile class; 0: layer by layer */
+    int wgrad_stages;      /* default 128 (also what a value <= 0 means): 64-pixel stages a work-group of a grouped launch reduces before a layer's
+                            * pixel range is split */
+    int wgrad_group_stem;  /* 1 (default): the Ci == 8 stem joins the 64x64 group in its row-tap form */
+    int bn_bwd_fused;      /* 1 (default): in the network backward, dgrad epilogues mask for the consumer BatchNorm and reduce its backward sums */
+    int bn_fwd_chunked;    /* BatchNorm forward, finalize + apply of the wide, small-spatial layers in one channel-chunked launch where it pays: 0 off,
+                            * 1 (default) on, > 1 on with that target work-group count instead of 1024 */
+    int bn_bwd_chunked;    /* BatchNorm backward, channel-chunked forms without a finalize launch: 0 off, 1 (default) on, > 1 as bn_fwd_chunked's */
+    int bn_bwd_pre_legacy; /* 0 (default); 1: BatchNorm backward from pre-reduced sums through the generic apply kernel (A/B) */
+    int igemm_wg_min;      /* default 512: 128x64 tiles as soon as they give this many work-groups, else 64x64 (2 per CU measured best in-step) */
+    int wgrad_row3;        /* 1 (default): weight gradients of 3x3 stride-1 convolutions with one work-group per (64x64 tile, filter row) - the row's
+                            * three taps share one staged dy tile and one x window (a third of the LDS fill per FLOP, which is what bounds these
+                            * kernels).  As fast as the 128x128 one-tap form alone; in the grouped launch with the 64x64 kernel at four work-groups
+                            * per CU: 1366 vs 1387 us per pass alone, -0.10 ms per step */
+    int bn3_mask;          /* 1 (default): block outputs save a ReLU bit mask in the forward that the masking data gradients read instead of z; 0: read z */
+    int stem_fused;        /* stem: 0 separate launches, 1 (default) BN apply + ReLU + max-pool in one sweep, 2 = also the max-pool backward gathered
+                            * inside the BN backward's two sweeps (0.2 GB less traffic, but 99 + 87 us against 55 + 30 + 48 us for the three separate
+                            * launches: neutral in the step) */
+    int debug_sync;        /* 0 (default); 1: network calls synchronise after every stage and report the first failing source line */
+    int igemm_big_min;     /* > 0: 128x128 tiles (2-stage ring) for single-class launches with Co % 128 == 0 whose 128x64 grid has at least this
+                            * many work-groups - the style network's large maps, run on one stream (+13-18 % there); 0 (default): never */
+    int patch_conv;        /* reflection-padded 3x3 stride-1 convolutions (the style network) through the patch-staged kernels (input patch staged once,
+                            * not once per tap): 0 never (the implicit GEMM for every layer), 1 the 64 -> 3 and 3 -> 64 end layers, 2 (default)
+                            * the trunk layers too (128 pixels x 64 channels per work-group), 3 = 2 with 128 output channels per work-group in the
+                            * 16-bit form where Co % 128 == 0 (measured equal to 2) */
+    int eval_fold;         /* 1 (default): eval-mode network forwards (validate(), train_human.py:461-500) apply BatchNorm's running-statistics scale /
+                            * shift, the residual and the ReLU in the convolution's epilogue: no BN-apply launch, no pre-BN tensor; 0: conv + apply */
+    int bn_xcd_rows;       /* 1 (default): the BatchNorm apply kernels (forward and backward, chunked and streaming forms) give XCD k the k-th eighth of
+                            * the pixel rows - what the implicit GEMMs' work-groups on XCD k wrote and will read (each XCD owns a contiguous range of
+                            * m-tiles there) - so activations cross the conv <-> BatchNorm kernel boundaries through one L2
+                            * (tools/probe/l2_handoff.hip: 17.9 against 6.7 TB/s); bit-identical results, -0.06..-0.15 ms per step
+                            * (r4_ab_runs.txt); 0: interleaved */
+    int wgrad_det;         /* 1 (default, round 6): split weight-gradient reductions of the grouped launches store per-split partial tiles into the pass's
+                            * workspace and ONE launch adds them in split order (bit-reproducible gradients; the `loss.backward()` of
+                            * train_human.py:436 run twice gives the same bits); 0: fp32 atomics into cleared tensors, arrival order (rounds 1-5) */
+    int igemm_ns3_k;       /* 64x64 implicit-GEMM tiles take the 3-stage LDS ring from this reduction length on (K = taps x Ci), the 2-stage ring
+                            * below it; 0 = the default, 2048 */
+    void* timeline;        /* NULL (default), or a device buffer of uint64 [work-groups][8] for timeline stamps (tuning).  The grouped weight-gradient launches
+                            * of a plan stamp {start, end (100 MHz), XCD, table slot, problem, stages | form bits, pass, tile rows} per work-group, the 128x128
+                            * class first, the 64x64 class behind it: the buffer must hold 1 << 17 work-groups (8 MiB); a plan with more refuses */
+    int wgrad_order;       /* grouped weight gradients, the deal of work-groups to the XCDs' lists (net.hip wg_deal): 1 (default) = layers cut into runs of 32 work-groups, the runs
+                            * with the most stages per work-group first, so every list ends with its share of the short work-groups; 0 = whole
+                            * (layer, split) units in deal order by unit load (rounds 1-6).  Same work into the same places either way: bit-identical gradients */
 } udapose_policy;
 void udapose_policy_default(udapose_policy* p);
 

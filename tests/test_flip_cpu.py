@@ -84,13 +84,9 @@ def test_restatement_self_checks():
     assert torch.equal(R.flip_merge(a, R.flip_back(a, perm), perm), a)
 
 
-def test_declared_exported_and_bound():
-    from uda_poseestimation_amd import _hip
-    hdr = open(os.path.join(ROOT, "include", "udapose.h")).read()
-    capi = open(os.path.join(ROOT, "uda_poseestimation_amd", "csrc", "capi.hip")).read()
+def test_the_source_is_built():
+    """(The two exports' prototypes and ctypes rows: test_host_cpu.py::test_ctypes_signatures_and_policy_fields_match_the_header.)"""
     mk = open(os.path.join(ROOT, "uda_poseestimation_amd", "csrc", "Makefile")).read()
-    for n in ("udapose_hflip_batch", "udapose_flip_merge"):
-        assert n in _hip.EXPORTS and f"int {n}(" in hdr and f"int {n}(" in capi, n
     assert " flip.hip " in mk
 
 

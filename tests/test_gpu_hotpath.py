@@ -292,7 +292,7 @@ def test_captured_loss_section_backward_is_right_on_every_replay():
     """The consistency branch of the loss section - re-warp (autograd), ConsLoss, backward to dL/dy_t - captured alone into a small
     hipGraph and replayed with eager device work between the replays: every replay equals the eager result.  (With the re-warp's
     backward clearing its output by hipMemsetAsync the third and later replays ran the clear AFTER the scatter on ROCm 7.2:
-    tools/probe/graph_memset_order.py; the clears are kernels now, csrc/common.h pw_zero.)"""
+    tools/probe/graph_memset_order.py; the clears are kernels now, csrc/pointwise.h pw_zero.)"""
     from uda_poseestimation_amd import synthetic, warp
     from uda_poseestimation_amd.lib.models.loss import ConsLoss
     torch.manual_seed(0)

@@ -38,6 +38,43 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.udapose_multi_chunk() > 0          # a pure host query (no GPU needed)
 
 
+def _ctype_of(decl):
+    """The ctypes type of one C parameter or return type as include/udapose.h spells it (with or without a parameter name)."""
+    import ctypes as C
+    if "*" in decl or "[" in decl or "udapose_net_t" in decl.split():
+        return C.c_void_p
+    scalars = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long": C.c_long, "long long": C.c_longlong,
+               "void": None}
+    words = [w for w in decl.split() if w != "const"]
+    for n in (len(words), len(words) - 1):        # the type alone (a return type), or the type followed by the parameter's name
+        if " ".join(words[:n]) in scalars:
+            return scalars[" ".join(words[:n])]
+    raise AssertionError(f"no ctypes mapping for {decl!r}")
+
+
+def test_ctypes_signatures_and_policy_fields_match_the_header():
+    """The one check of the ABI as Python binds it: every row of _hip._SIGS has the return and argument types of its prototype in
+    include/udapose.h, capi.hip defines the function with that return type, and _hip.Policy has the fields of the udapose_policy
+    typedef, in order and in type.  (A float bound as c_int is silent garbage at run time.)"""
+    from uda_poseestimation_amd import _hip
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "udapose.h")).read(), flags=re.S)
+    capi = open(os.path.join(ROOT, "uda_poseestimation_amd", "csrc", "capi.hip")).read()
+    assert len(_hip._SIGS) >= 142
+    for name, (ret, args) in _hip._SIGS.items():
+        m = re.search(r"^([\w \*]+?)\b" + name + r"\s*\(([^;{]*)\)\s*;", hdr, flags=re.M)
+        assert m, f"{name} has no prototype in include/udapose.h"
+        c_ret, c_params = " ".join(m.group(1).split()), " ".join(m.group(2).split())
+        params = [] if c_params in ("", "void") else [p.strip() for p in c_params.split(",")]
+        assert (_ctype_of(c_ret), [_ctype_of(p) for p in params]) == (ret, list(args)), f"{name}: _SIGS disagrees with '{m.group(0)}'"
+        assert f"{c_ret} {name}(" in capi, f"capi.hip does not define '{c_ret} {name}('"
+    body = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*udapose_policy\s*;", hdr).group(1)
+    fields = []
+    for stmt in filter(None, (s.strip() for s in body.split(";"))):
+        ctype, first = stmt.rsplit(None, 1) if "," not in stmt else stmt.split(",")[0].rsplit(None, 1)
+        fields += [(n.strip(), _ctype_of(ctype)) for n in [first] + stmt.split(",")[1:]]
+    assert len(fields) >= 28 and fields == list(_hip.Policy._fields_)
+
+
 def test_conv_geometry_queries_run_on_host(lib):
     import ctypes as C
     from uda_poseestimation_amd import ops

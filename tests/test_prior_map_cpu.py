@@ -125,9 +125,7 @@ def test_pair_statistics_of_three_samples_by_hand():
         assert bool(torch.isfinite(P64.prior_map(torch.from_numpy(mu), std_t, preds, v3=v3)).all())
 
 
-def test_the_four_exports_are_declared_in_the_header_and_cite_the_reference():
-    from uda_poseestimation_amd import _hip
+def test_the_header_cites_the_reference():
+    """(The four exports' prototypes and ctypes rows: test_host_cpu.py::test_ctypes_signatures_and_policy_fields_match_the_header.)"""
     text = open(os.path.join(ROOT, "include", "udapose.h")).read()
-    for n in ("udapose_prior_weights", "udapose_prior_map", "udapose_pair_dist_accumulate", "udapose_pair_dist_finish"):
-        assert n in _hip.EXPORTS and f"int {n}(" in text, n
     assert "utils.py:111-145" in text

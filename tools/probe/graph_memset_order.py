@@ -2,7 +2,7 @@
 eager device work between the replays.  On this image (ROCm 7.2.0, torch 2.10) the THIRD and later replays run the clear AFTER the kernel
 (the buffer reads 0 instead of 0 + 1) with the runtime's default DEBUG_CLR_GRAPH_PACKET_CAPTURE=1; with that variable 0, or with the clear
 done by a kernel (`zero`), every replay is right.  Nothing of the package is involved: torch + libamdhip64 only.  This is why every clear
-on a capturable path of csrc/ goes through pw_zero (common.h) instead of hipMemsetAsync.
+on a capturable path of csrc/ goes through pw_zero (pointwise.h) instead of hipMemsetAsync.
 
 `copy`: the same question for a memcpy node (dx.copy_(zeros): torch issues hipMemcpyAsync for a contiguous device-to-device copy).
 

@@ -1,7 +1,7 @@
 // AdaIN feature re-normalisation (lib/models/Style_net.py:4-29,167-168) on NHWC features (element type or fp32):
 // out = alpha*((c-mu_c)/sd_c*sd_s+mu_s) + (1-alpha)*c with per-(n,c) statistics over H*W.  HBM-bound: the algorithmic minimum
 // is content + style in, result out (201 MB for [32,512,32,32] fp32, 100 MB in bf16).
-#include "common.h"
+#include "style.h"
 
 namespace {
 constexpr int TPB = 256;

@@ -9,7 +9,7 @@
 // terms).  Its weight gradient gathers the padded input once (the forward's own addressing) and runs the existing LDS-DMA
 // weight-gradient kernels on it with per-split partial tiles that one launch adds in split order: every reduction here is
 // bit-reproducible (no atomics in arrival order).
-#include "conv_plan.h"
+#include "style.h"
 
 namespace {
 constexpr int TPB = 256;

@@ -6,6 +6,8 @@
 // theta / (0.5*[W,H]); base grid at half-integers; ix = ((x+1)*W-1)/2; nearbyint.
 // The same chain with bilinear interpolation per stage (affine_warp_chain_bilinear) follows further down.
 #include "conv_plan.h"
+#include "data.h"
+#include "pointwise.h"      // pw_zero
 
 namespace {
 constexpr int TPB = 256;

@@ -8,7 +8,7 @@
 //     degenerate = black (brightness), the rounded mean of the L image (contrast), the L image (saturation);
 //     L = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16.
 // All kernels are byte / float sweeps (HBM-bound, 196 KB per 256x256 image); images are uint8 NHWC as PIL arrays are.
-#include "common.h"
+#include "data.h"
 
 // no FMA contraction: PIL's blend rounds the product and the sum separately (d + f * (v - d) in C float); a fused
 // multiply-add lands on the other side of an integer for ~1 % of the bytes and the truncation to uint8 then differs

@@ -1,174 +1,21 @@
 // extern "C" surface of libudapose_hip.so (declared in include/udapose.h).
 #include <cstdio>
-#include "conv_plan.h"
+#include "net.h"
+#include "pointwise.h"
+#include "losses.h"
+#include "optim.h"
+#include "style.h"
+#include "data.h"
 #include "../../include/udapose.h"
 
-int pw_nchw_f32_to_nhwc_bf16(hipStream_t, const float*, elem_t*, int, int, int, int);
-int pw_nhwc_to_nchw_f32(hipStream_t, const void*, int, float*, int, int, int, int, const float*, const float*);
-int pw_cast_f32_bf16(hipStream_t, const float*, elem_t*, size_t);
-int pw_transpose_cast(hipStream_t, const float*, elem_t*, int, int, int);
-int pw_pack_strided(hipStream_t, const float*, elem_t*, int, int, int, int, int, int, long, long, long, long);
-int pw_bn_finalize(hipStream_t, const float*, int, int, double, const float*, const float*, float*, float*, long long*, float, float, float*, float*,
-                   float*, float*, const float*);
-int pw_bn_eval_coeff(hipStream_t, int, const float*, const float*, const float*, const float*, float, float*, float*);
-int pw_bn_apply(hipStream_t, const elem_t*, const elem_t*, elem_t*, size_t, int, const float*, const float*, int, unsigned char*, int);
-int pw_bn_bwd_rows(size_t);
-int pw_bn_bwd_pre(hipStream_t, const void*, int, const elem_t*, elem_t*, size_t, int, const float*, const float*, const float*, const float*, int, float*,
-                  float*, float*, float, int, int);
-int pw_bn_bwd(hipStream_t, const void*, int, const elem_t*, const elem_t*, elem_t*, elem_t*, size_t, int, const float*, const float*, const float*, int,
-              float*, float*, float*, float*, float, const float*, int);
-int pw_maxpool3x3s2_fwd(hipStream_t, const elem_t*, elem_t*, unsigned char*, int, int, int, int);
-// the BatchNorm / pooling forms the executor reaches through its plan (net.hip), for the *_ex entry points below
-int pw_bn_train_fused(hipStream_t, const elem_t*, const elem_t*, elem_t*, size_t, int, const float*, int, const float*, const float*, float*, float*,
-                      long long*, float, float, float*, int, int, unsigned char*);
-int pw_bn_train_fused_split(hipStream_t, const float*, const void*, void*, size_t, int, const float*, int, const float*, const float*, float*, float*,
-                            long long*, float, float, float*, int, int, void*, void*, unsigned char*);
-int pw_bn_apply_split(hipStream_t, const float*, const void*, void*, size_t, int, const float*, const float*, int, void*, void*, unsigned char*, int);
-int pw_bn_apply_f32(hipStream_t, const float*, const float*, float*, size_t, int, const float*, const float*, int);
-int pw_bn_apply_xcd_ok(size_t, int);
-int pw_bn_bwd_takes_chunked(size_t, int, int);
-int pw_bn_bwd_pre_takes_chunked(size_t, int, int, int);
-int pw_bn_relu_maxpool3x3s2(hipStream_t, const elem_t*, elem_t*, unsigned char*, int, int, int, int, const float*, const float*);
-int pw_bn_bwd_pooled(hipStream_t, const elem_t*, const unsigned char*, int, int, const elem_t*, elem_t*, size_t, int, const float*, const float*,
-                     const float*, float*, float*, float*, float*, float, const float*);
-int pw_maxpool3x3s2_fwd_f32(hipStream_t, const float*, float*, unsigned char*, int, int, int, int);
-int pw_maxpool3x3s2_fwd_split(hipStream_t, const void*, void*, unsigned char*, int, int, int, int, void*);
-int pw_bn_running_update(hipStream_t, const float*, int, float*, float*, long long*, float);
-int pw_bn_running_update_multi(hipStream_t, const BnRunJob*, int, int, const void*, float);
-
-// adain_train.hip (the AdaIN decoder's training step)
-size_t conv_bwd_ws_bytes(const ConvGeom& g);
-int conv_bwd_prepare(const ConvGeom& g);
-int conv_dgrad_reflect_padded(hipStream_t s, const ConvGeom& g, const elem_t* dy, const elem_t* w_bwd, elem_t* dP);
-int reflect_fold(hipStream_t s, const elem_t* dP, int up, const elem_t* x, int mask, const float* stats, const float* gs_s, const elem_t* t,
-                 const float* gs_c, float c_scale, const float* add_nchw, int add_c, elem_t* dx, int N, int H, int W, int C, float term_scale);
-int conv_dgrad_reflect(hipStream_t s, const ConvGeom& g, const elem_t* dy, const elem_t* w_bwd, elem_t* dx, const elem_t* mask_src, void* ws);
-int conv_wgrad_reflect(hipStream_t s, const ConvGeom& g, const elem_t* dy, const elem_t* x, float* dw, int co_valid, void* ws, float out_scale);
-int maxpool2x2_ceil_bwd(hipStream_t s, const elem_t* x, const elem_t* dy, elem_t* dx, int N, int H, int W, int C, int mask);
-size_t bias_grad_ws_bytes(long long M, int C);
-int bias_grad(hipStream_t s, const elem_t* dy, float* db, long long M, int C, int c_valid, void* ws, float out_scale);
-size_t feat_mse_ws_bytes();
-int feat_mse_fwd(hipStream_t s, const elem_t* a, const elem_t* b, long long n, float* out, void* ws);
-int style_stat_loss(hipStream_t s, const float* stats, int R, float* out, int accumulate);
-int pw_maxpool3x3s2_bwd(hipStream_t, const elem_t*, const unsigned char*, elem_t*, int, int, int, int);
-int pw_maxpool2x2_ceil(hipStream_t, const elem_t*, elem_t*, int, int, int, int);
-int hm_sqdiff_rows(hipStream_t, const float*, const float*, const float*, const unsigned char*, int, int, float, float*, float*,
-                   const unsigned char*, const float*, int);
-int hm_sqdiff_bwd(hipStream_t, const float*, const float*, const float*, const unsigned char*, const float*, float, int, int, float*,
-                  const unsigned char*, const float*, int);
-int hm_mask_count(hipStream_t, const unsigned char*, size_t, float*);
-int sml_kl_fwd(hipStream_t, const float*, const float*, const float*, float, int, int, int, float*, float*, float*);
-int sml_kl_bwd(hipStream_t, const float*, const float*, const float*, float, const float*, const float*, int, int, float*);
-int sml_ent_fwd(hipStream_t, const float*, int, int, int, float, float*, float*, float*, float*);
-int sml_ent_bwd(hipStream_t, const float*, const float*, const float*, const float*, const float*, float, int, int, float*);
-int sml_cons_fwd(hipStream_t, int, const float*, const float*, const unsigned char*, const unsigned char*, const float*, int, int, int, float*,
-                 float*, float*);
-int sml_cons_bwd(hipStream_t, int, const float*, const float*, const unsigned char*, const unsigned char*, const float*, const float*,
-                 const float*, int, int, int, float*);
-int sa_fwd(hipStream_t, const float*, int, int, int, float, int, float*, float*, int*, float*);
-long long coral_ws_bytes(int, int, int, int, int);
-int coral_fwd(hipStream_t, const float*, const float*, int, int, int, int, int, void*, float*, float*);
-int coral_bwd(hipStream_t, const float*, const float*, const float*, const float*, int, int, int, int, int, float*, float*);
-int sa_bwd(hipStream_t, const float*, const float*, const int*, const float*, int, int, int, float, int, float*);
-int sa_coord_fwd(hipStream_t, const float*, const float*, const float*, const unsigned char*, int, int, int, int, float, int, int, float*, int*,
-                 float*, float*);
-int sa_coord_bwd(hipStream_t, const float*, const float*, const float*, const unsigned char*, const int*, const float*, const float*, int, int, int,
-                 float, int, int, float*);
-int flip_hbatch(hipStream_t, const float*, float*, int, size_t, int, int);
-int flip_merge(hipStream_t, const float*, const float*, const int*, int, int, int, int, int, int, float*, float*, int*, float*);
-int pw_maxpool2x2_ceil_f32(hipStream_t, const float*, float*, int, int, int, int);
-int pw_nchw_f32_to_nhwc_f32(hipStream_t, const float*, float*, int, int, int, int);
-int adain_launch_f32(hipStream_t, const float*, const float*, float*, int, int, int, int, float, float, const float*, float*);
-int adain_launch_split(hipStream_t, const void*, const void*, void*, int, int, int, int, float, float, const float*, float*);
-int pw_nchw_f32_to_nhwc_split(hipStream_t, const float*, void*, int, int, int, int, void* = nullptr);
-int pw_f32_to_split(hipStream_t, const float*, void*, size_t);
-int pw_split_to_f32(hipStream_t, const void*, float*, size_t);
-int pw_maxpool2x2_ceil_split(hipStream_t, const void*, void*, int, int, int, int);
-int hm_argmax_rectify(hipStream_t, const float*, int, int, int, float*, int*, float*, float*, const float*, int);
-int hm_kth_mask(hipStream_t, const float*, const float*, int, int, float*, unsigned char*, const float*, int);
-int pm_weights(hipStream_t, const float*, int, float, float, int, float*);
-int pm_map(hipStream_t, const float*, const float*, const float*, const float*, const float*, int, int, int, int, float, int, float*);
-int pm_pair_accumulate(hipStream_t, const float*, const unsigned char*, int, int, double*);
-int pm_pair_finish(hipStream_t, const double*, int, float*, float*);
-int hm_pck(hipStream_t, const float*, const float*, int, int, float, float, float, float*, float*);
-int opt_chunk();
-int opt_ema(hipStream_t, const long long*, const long long*, const long long*, const int*, const long long*, int, float, float);
-int opt_adam(hipStream_t, const long long*, const long long*, const long long*, const long long*, const long long*, const int*, const long long*, int,
-             float, float, float, float, float, int, float, float*);
-int opt_sgd(hipStream_t, const long long*, const long long*, const long long*, const long long*, const int*, const long long*, int, float, float, float,
-            int, int, float, float*);
-int opt_grad_check(hipStream_t, const long long*, const long long*, const int*, const long long*, int, float*, long long);
-int opt_scaler_update(hipStream_t, float*, float, float, int);
-int comm_pack_bf16(hipStream_t, const float*, long long, void*, long long);
-int comm_shard_mean(hipStream_t, const void*, int, long long, void*);
-int comm_unpack_bf16(hipStream_t, const void*, float*, long long);
-int adain_launch(hipStream_t, const elem_t*, const elem_t*, elem_t*, int, int, int, int, float, float, const float*, float*);
-int aug_affine_u8(hipStream_t, const unsigned char*, unsigned char*, const long long*, int, int, int);
-int aug_color_op(hipStream_t, unsigned char*, const int*, const float*, int*, int, int);
-int aug_gaussian_blur_u8(hipStream_t, unsigned char*, unsigned char*, const unsigned int*, int, int, int);
-int aug_resized_crop_u8(hipStream_t, const unsigned char*, unsigned char*, unsigned char*, const int*, const int*, const int*, int, int, int, int, int);
-int aug_to_tensor(hipStream_t, const unsigned char*, float*, int, int, const float*, const float*);
-int aug_gaussian_labels(hipStream_t, const double*, const float*, float*, float*, int, int, int, double, double, const float*, int);
-int aug_draw_labelmap_ori(hipStream_t, const float*, const float*, const unsigned char*, float*, float*, int, int, int, float, const float*, int);
-int affine_warp_chain(hipStream_t, const float*, float*, const float*, int, int, int, int, int, int);
-int affine_warp_chain_bilinear(hipStream_t, const float*, float*, const float*, int, int, int, int, int, int);
-int affine_recon_thetas(hipStream_t, const double*, int, double, float*, float*);
-int affine_mean_views(hipStream_t, const float* const*, int, float*, size_t);
-unsigned long long sp_sat_read_adain(int);
-unsigned long long sp_sat_read_igemm(int);
-unsigned long long sp_sat_read_patchconv(int);
-unsigned long long sp_sat_read_pointwise(int);
-int patch_paste(hipStream_t, float*, const int*, int, int, int, int, int);
-int occlusion_pick(hipStream_t, const float*, const int*, const float*, int, int, int, double, int, float, float, int, int*, unsigned char*);
-int select_rows(hipStream_t, float*, const float*, const float*, const unsigned char*, int, size_t);
-int net_apply_running(void*, hipStream_t, const void*, void* const*, float);
-int pw_axpy(hipStream_t, float*, const float*, size_t);
-void prof_begin();
-int prof_end(double*);
-void* net_create(const int layers[4], int K, int N, int H, int W, int mode);
-void net_destroy(void*);
-void net_set_policy(void*, const Policy&);
-const Policy& net_get_policy(void*);
-int net_bind(void*, const void* const*, void* const*, void*);
-int net_bind_grads(void*, void* const*);
-long long net_grad_split_param(void*);
-int net_bind_update(void*, void*, void* const*, void* const*, void* const*, void* const*, void* const*, void*, void*);
-int net_fused_update(void*, void*, hipStream_t, void* const*, void* const*, void* const*, void* const*, void*, void*, float, float, float, float, float,
-                     int, float, float*, float, float, int, long long);
-int net_bind_update_groups(void*, void*, int, void* const*, void* const*, void* const*, void* const*, void* const*, void*, void*, const int*);
-int net_fused_update_groups(void*, void*, hipStream_t, int, void* const*, void* const*, void* const*, void* const*, void*, void*, float, float, float, int,
-                            int, float* const*, const float*, float, float, int, long long);
-int net_num_params(void*);
-int net_num_buffers(void*);
-long long net_param_numel(void*, int);
-size_t net_wpack_bytes(void*);
-size_t net_act_bytes(void*);
-size_t net_ws_bytes(void*);
-void net_out_shape(void*, int*);
-int net_pack_weights(void*, hipStream_t, const void* const*, void*, int);
-int net_forward(void*, hipStream_t, const float*, const void* const*, void* const*, const void*, void*, void*, float*, int, float);
-int net_backward(void*, hipStream_t, const float*, const void* const*, const void*, void*, void*, void* const*, float, int, int);
-int net_wgrad_pair(void*, hipStream_t, const void*, void*, void* const*, float, const void*, void*, void* const*, float, int);
-int net_wgrad_pair_defer(void*, hipStream_t, const void*, void*, void* const*, float, const void*, void*, void* const*, float, int, int*);
-int net_split_sum_flush(void*, hipStream_t);
-int net_wgrad_deal(const int*, const int*, int, int, int*, int*, int*, int*, int, double*);
-
+// a caller's policy as the library's: a whole-struct copy, plus the one normalisation (wgrad_stages <= 0 means the default)
 static Policy from_c(const udapose_policy& c) {
     Policy p;
-    p.igemm_tile = c.igemm_tile; p.igemm_h3 = c.igemm_h3; p.igemm_lean = c.igemm_lean; p.igemm_short_lds = c.igemm_short_lds;
-    p.igemm_tap0 = c.igemm_tap0; p.wgrad_tile = c.wgrad_tile; p.wgrad_ksplit = c.wgrad_ksplit; p.wgrad_fastgeo = c.wgrad_fastgeo;
-    p.wgrad_group = c.wgrad_group; p.wgrad_stages = c.wgrad_stages > 0 ? c.wgrad_stages : 128; p.wgrad_group_stem = c.wgrad_group_stem;
-    p.bn_bwd_fused = c.bn_bwd_fused; p.bn_fwd_chunked = c.bn_fwd_chunked; p.bn_bwd_chunked = c.bn_bwd_chunked;
-    p.bn_bwd_pre_legacy = c.bn_bwd_pre_legacy; p.igemm_wg_min = c.igemm_wg_min; p.wgrad_row3 = c.wgrad_row3; p.bn3_mask = c.bn3_mask; p.stem_fused = c.stem_fused; p.debug_sync = c.debug_sync; p.igemm_big_min = c.igemm_big_min; p.patch_conv = c.patch_conv; p.eval_fold = c.eval_fold; p.bn_xcd_rows = c.bn_xcd_rows; p.igemm_ns3_k = c.igemm_ns3_k; p.wgrad_det = c.wgrad_det; p.wgrad_order = c.wgrad_order; p.timeline = (unsigned long long*)c.timeline;
+    static_cast<udapose_policy&>(p) = c;
+    if (p.wgrad_stages <= 0) p.wgrad_stages = 128;
     return p;
 }
-static void to_c(const Policy& p, udapose_policy* c) {
-    c->igemm_tile = p.igemm_tile; c->igemm_h3 = p.igemm_h3; c->igemm_lean = p.igemm_lean; c->igemm_short_lds = p.igemm_short_lds;
-    c->igemm_tap0 = p.igemm_tap0; c->wgrad_tile = p.wgrad_tile; c->wgrad_ksplit = p.wgrad_ksplit; c->wgrad_fastgeo = p.wgrad_fastgeo;
-    c->wgrad_group = p.wgrad_group; c->wgrad_stages = p.wgrad_stages; c->wgrad_group_stem = p.wgrad_group_stem;
-    c->bn_bwd_fused = p.bn_bwd_fused; c->bn_fwd_chunked = p.bn_fwd_chunked; c->bn_bwd_chunked = p.bn_bwd_chunked;
-    c->bn_bwd_pre_legacy = p.bn_bwd_pre_legacy; c->igemm_wg_min = p.igemm_wg_min; c->wgrad_row3 = p.wgrad_row3; c->bn3_mask = p.bn3_mask; c->stem_fused = p.stem_fused; c->debug_sync = p.debug_sync; c->igemm_big_min = p.igemm_big_min; c->patch_conv = p.patch_conv; c->eval_fold = p.eval_fold; c->bn_xcd_rows = p.bn_xcd_rows; c->igemm_ns3_k = p.igemm_ns3_k; c->wgrad_det = p.wgrad_det; c->wgrad_order = p.wgrad_order; c->timeline = p.timeline;
-}
+static void to_c(const Policy& p, udapose_policy* c) { *c = p; }
 // a convolution descriptor and the policy it names, as the host-side geometry (the policy lives as long as this object)
 struct Geom {
     Policy pol;

@@ -3,12 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#define UDAPOSE_OK 0
-#define UDAPOSE_ERR_ARG (-1)
-#define UDAPOSE_ERR_LAUNCH (-2)
-#define UDAPOSE_ERR_UNSUPPORTED (-3)
-#define UDAPOSE_ERR_NOT_PREPARED (-4)   // a device table this call needs was not built (udapose_net_bind / udapose_conv_prepare)
+#include "../../include/udapose.h"      // the UDAPOSE_* return codes
 
 // Storage / MFMA-operand element type of this build of the library.  The same sources are compiled twice:
 //   libudapose_hip.so      elem_t = bf16  (v_mfma_f32_16x16x32_bf16)   - BASELINE.json's benched precision
@@ -113,23 +108,6 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
     uint32_t t = __umulhi(n, f.magic);
     return (t + ((n - t) >> 1)) >> (f.shift - 1);
 }
-
-// one BN layer of the batched running-statistics update (pw_bn_running_update_multi)
-struct BnRunJob { size_t save_off; float* rm; float* rv; long long* nbt; int C, pad; };
-
-// Clears `bytes` (a multiple of 4, 4-byte aligned) at p with a KERNEL.  Every clear on a capturable path goes through this instead of
-// hipMemsetAsync: on ROCm 7.2 a hipGraph memset node can be replayed out of order with the kernel node that depends on it (from the
-// third replay of a small captured graph on, with the runtime's default DEBUG_CLR_GRAPH_PACKET_CAPTURE=1: the clear lands AFTER the
-// scatter that follows it; tools/probe/graph_memset_order.py reproduces it with torch alone).  pointwise.hip.
-int pw_zero(hipStream_t s, void* p, size_t bytes);
-
-// one range of the multi-range clear (pw_zero_multi): byte offset from a base pointer, length in 16-byte units
-struct ZeroJob { long long off; long long n16; };
-// one layer of the split-sum launch (pw_split_sum): `ks` partial tiles of `n` floats, `stride` floats apart, at byte offset part_off of the pass's
-// workspace, are added in split order into the tensor at byte offset dst_off of the gradient base (dst_ws: of the workspace); beta 1 accumulates
-#define UDAPOSE_SPLIT_SUM_CHUNK 1024u      // floats of a job one work-group of pw_split_sum adds (one 16-byte column per thread)
-struct SumJob { long long part_off; long long dst_off; unsigned n; unsigned stride; int ks; int dst_ws; float beta; int pad; };
-int pw_split_sum(hipStream_t s, const SumJob* d_jobs, const int* d_blk, int nblk, void* ws, void* grad_base, void* ws2 = nullptr, void* grad_base2 = nullptr);
 
 // XCD-aware work-group remap (MI355X: 8 XCDs, each with a private 4 MiB L2; work-groups are dealt round-robin, so b and
 // b+8 share an L2).  Returns a bijective permutation of the linear block id that gives every XCD one CONTIGUOUS range of

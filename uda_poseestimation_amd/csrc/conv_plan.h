@@ -5,52 +5,18 @@
 #include <vector>
 #include "igemm.h"
 
-// Explicit dispatch policy.  A default-constructed Policy IS the measured production policy; nothing in the library reads an
-// environment variable or a mutable global to choose a kernel.  A network plan owns a copy (udapose_net_set_policy), a
-// single convolution call names one through its descriptor (udapose_conv_desc.policy, NULL = default).  The non-default
-// values exist for tests (force a code path) and tuning (A/B runs through bench.py flags).
-struct Policy {
-    int igemm_tile = -1;        // force one igemm tile configuration id (-1: the heuristics of igemm_pick_tile)
-    int igemm_h3 = 1;           // run-staged 3x3 form: 0 off, 1 measured per-shape policy, 2 / 3: force the 64- / 128-row form
-    int igemm_lean = 1;         // lean 1x1 form (saddr LDS-DMA loads) where eligible
-    int igemm_short_lds = 1;    // one-stage LDS request for launches whose K loop is one stage
-    int igemm_tap0 = 1;         // 1x1 kernels skip the tap-table read
-    int wgrad_tile = -1;        // force a weight-gradient tile id (-1: heuristics)
-    int wgrad_ksplit = -1;      // force the pixel-split count of a per-layer weight-gradient launch
-    int wgrad_fastgeo = 2;      // weight-gradient loader on power-of-two maps: 0 general, 1 bit-field pixel coordinates (pointer selects),
-                                // 2 the same through buffer_load ... lds with out-of-range zero fill and an unrolled ring (wgrad_fast2_body)
-    int wgrad_group = 1;        // net backward: one grouped weight-gradient launch per tile class (0: layer by layer)
-    int wgrad_stages = 128;     // grouped launch: 64-pixel stages a work-group reduces before a layer's pixel range is split
-    int wgrad_group_stem = 1;   // the Ci == 8 stem joins the 64x64 group in its row-tap form
-    int bn_bwd_fused = 1;       // net backward: dgrad epilogues mask for the consumer BatchNorm and reduce its backward sums
-    int bn_fwd_chunked = 1;     // BN forward: finalize + apply in one channel-chunked launch where it pays
-    int bn_bwd_chunked = 1;     // BN backward: channel-chunked forms without a finalize launch
-    int bn_bwd_pre_legacy = 0;  // BN backward from pre-reduced sums through the generic apply kernel (A/B)
-    int igemm_wg_min = 512;     // 128x64 tiles as soon as they give this many work-groups (else 64x64): 2 per CU measured best in-step
-    int wgrad_row3 = 1;         // 3x3 stride-1 convs: one weight-gradient work-group per (64x64 tile, filter row), three taps sharing the staged
-                                // operands (a third of the LDS fill per FLOP).  As fast as the 128x128 one-tap form alone; in the grouped launch
-                                // with the 64x64 kernel at four work-groups per CU: 1366 vs 1387 us per pass alone, -0.10 ms per step
-    int bn3_mask = 1;           // block outputs: the forward saves the ReLU bit mask, the data gradients read it instead of z (0: read z)
-    int stem_fused = 1;         // stem: 1 = BN apply + ReLU + max-pool in one sweep; 2 = also the max-pool backward gathered inside the BN backward's
-                                // two sweeps (0.2 GB less traffic, but 99 + 87 us against 55 + 30 + 48 us for the three separate launches: neutral in the step)
-    int igemm_big_min = 0;      // > 0: tile 4 (128x128, 2-stage ring) when Co % 128 == 0 and the 128x64 grid has >= this many work-groups
-    int patch_conv = 2;         // reflection-padded 3x3 stride-1 convolutions (the style network) through the patch-staged kernels of patchconv.hip
-                                // (the input patch staged once instead of once per tap): 0 = never (the igemm for every layer), 1 = the 64 -> 3
-                                // and 3 -> 64 end layers only, 2 = the trunk layers too (128 pixels x 64 channels per work-group), 3 = 128
-                                // channels per work-group in the 16-bit form where Co % 128 == 0 (measured equal to 2)
-    int eval_fold = 1;          // eval-mode forwards (validate()): BatchNorm's running-statistics scale / shift, the residual and the ReLU are applied in
-                                // the convolution's epilogue - z is written by the conv, no BN-apply launch, no pre-BN tensor (0: conv + apply launches)
-    int bn_xcd_rows = 1;        // BatchNorm apply kernels (forward and backward, chunked and streaming forms): XCD k processes the k-th eighth of the pixel
-                                // rows, the rows the implicit GEMMs' work-groups on XCD k produce and consume (each XCD owns a contiguous range of
-                                // m-tiles there), so activations cross the conv <-> BatchNorm kernel boundaries through that XCD's L2
-                                // (tools/probe/l2_handoff.hip: 17.9 against 6.7 TB/s); bit-identical results, -0.06..-0.15 ms per step (r4_ab_runs.txt)
-    int wgrad_det = 1;          // grouped weight gradients: split pixel reductions store per-split partial tiles that ONE launch adds in split order
-                                // (bit-reproducible gradients; 0: fp32 atomics into cleared tensors, arrival order - rounds 1-5)
-    int igemm_ns3_k = 0;        // 64x64 igemm tiles: 3-stage ring from this K on, 2-stage below (0 = 2048)
-    int wgrad_order = 1;        // grouped weight gradients, the deal to the XCDs' lists (net.hip wg_deal): 1 = runs of 32 work-groups, most stages first;
-                                // 0 = whole units in deal order by unit load (rounds 1-6).  The gradients do not depend on it.
-    int debug_sync = 0;         // net calls: synchronise after every stage and report the first failing source line
-    unsigned long long* timeline = nullptr;   // device buffer for per-work-group timeline stamps (tuning), normally null
+// The dispatch policy inside the library: the public udapose_policy (every field is documented there, once) constructed with the
+// measured production defaults.  A network plan owns a copy, a convolution call names one through ConvGeom::pol.
+struct Policy : udapose_policy {
+    Policy() : udapose_policy{} {
+        igemm_tile = -1; igemm_h3 = 1; igemm_lean = 1; igemm_short_lds = 1; igemm_tap0 = 1;
+        wgrad_tile = -1; wgrad_ksplit = -1; wgrad_fastgeo = 2;
+        wgrad_group = 1; wgrad_stages = 128; wgrad_group_stem = 1;
+        bn_bwd_fused = 1; bn_fwd_chunked = 1; bn_bwd_chunked = 1; bn_bwd_pre_legacy = 0;
+        igemm_wg_min = 512; wgrad_row3 = 1; bn3_mask = 1; stem_fused = 1; debug_sync = 0;
+        igemm_big_min = 0; patch_conv = 2; eval_fold = 1; bn_xcd_rows = 1; wgrad_det = 1; igemm_ns3_k = 0;
+        timeline = nullptr; wgrad_order = 1;
+    }
 };
 inline const Policy& default_policy() { static const Policy p; return p; }
 
@@ -154,3 +120,6 @@ int conv_prof_before(hipStream_t s, int kind, double flops);
 void conv_prof_after(hipStream_t s, int token);
 int conv_stat_rows(const ConvGeom& g);
 int conv_dgrad_stat_rows(const ConvGeom& g);   // rows of a DgradBnStat slab for this layer's dgrad
+// saturation counters of the f16x2 stores in igemm.hip / patchconv.hip (common.h UDAPOSE_SP_SAT_READER)
+unsigned long long sp_sat_read_igemm(int reset);
+unsigned long long sp_sat_read_patchconv(int reset);

@@ -3,10 +3,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
-#include "conv_plan.h"
-
-int prof_before(hipStream_t s, int kind, double flops);
-void prof_after(hipStream_t s, int token);
+#include "net.h"      // prof_before / prof_after
 
 static double alg_flops(const ConvGeom& g) {
     // algorithmic FLOPs of the convolution (true channel count: 8-channel inputs are 3-channel images padded)

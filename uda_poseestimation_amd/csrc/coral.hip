@@ -17,7 +17,7 @@
 // the central 2x2 pixels of each d x d block (rows and columns d/2-1, d/2); odd d: the centre pixel.  The backward hands 0.25 of an element's
 // gradient to each of its four pixels (all of it to the centre pixel) and writes an explicit 0 to every other pixel of the full-resolution
 // gradient: footprints are disjoint and cover the map (the last block of a row / column takes the remainder), so nothing is cleared beforehand.
-#include "common.h"
+#include "losses.h"
 
 namespace {
 typedef __attribute__((ext_vector_type(16))) float f32x16;

@@ -1,0 +1,24 @@
+// Host launchers of the data pipeline: warps, occlusion and patches (affine.hip), image augmentation and label maps (augment.hip).
+#pragma once
+#include "common.h"
+
+// affine.hip
+int occlusion_pick(hipStream_t s, const float* conf, const int* idx, const float* u, int N, int K, int w, double ratio, int image_size, float rate,
+                   float thresh, int occ, int* boxes, unsigned char* apply);
+int select_rows(hipStream_t s, float* dst, const float* a, const float* b, const unsigned char* flag, int N, size_t row);
+int patch_paste(hipStream_t s, float* img, const int* boxes, int n, int C, int H, int W, int max_patch_elems);
+int affine_recon_thetas(hipStream_t s, const double* params, int N, double ratio, float* fwd, float* back);
+int affine_warp_chain(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward);
+int affine_warp_chain_bilinear(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward);
+int affine_mean_views(hipStream_t s, const float* const* srcs, int k, float* dst, size_t n);
+// augment.hip
+int aug_resized_crop_u8(hipStream_t s, const unsigned char* src, unsigned char* dst, unsigned char* tmp, const int* box, const int* bounds,
+                        const int* coef, int N, int Hs, int Ws, int S, int ksize);
+int aug_gaussian_blur_u8(hipStream_t s, unsigned char* img, unsigned char* tmp, const unsigned int* prm, int N, int H, int W);
+int aug_affine_u8(hipStream_t s, const unsigned char* src, unsigned char* dst, const long long* coef, int N, int H, int W);
+int aug_color_op(hipStream_t s, unsigned char* img, const int* op, const float* factor, int* mean_scratch, int N, int HW);
+int aug_to_tensor(hipStream_t s, const unsigned char* img, float* out, int N, int HW, const float* mean3, const float* std3);
+int aug_gaussian_labels(hipStream_t s, const double* kp, const float* vis, float* target, float* weight, int R, int Hh, int Wh, double stride_x,
+                        double stride_y, const float* patch, int rad);
+int aug_draw_labelmap_ori(hipStream_t s, const float* pt, const float* vis, const unsigned char* gate, float* target, float* weight, int R, int Hh,
+                          int Wh, float r3, const float* patch, int psize);

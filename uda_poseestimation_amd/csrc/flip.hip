@@ -3,7 +3,7 @@
 //   flip_merge_k             : flip the heat-maps of the mirrored batch back (columns reversed, left / right channels swapped, optional
 //                              one-pixel shift), average them with the plain batch's and decode the result in the same pass
 // Pure HBM sweeps: every operand is read once, every output written once.  No atomics, no scratch: capturable.
-#include "common.h"
+#include "losses.h"
 
 namespace {
 constexpr int TPB = 256;

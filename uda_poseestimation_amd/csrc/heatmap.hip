@@ -1,7 +1,7 @@
 // Heat-map kernels (fp32 NCHW [B,K,H*W] rows): JointsMSE / consistency losses (fwd+bwd), arg-max decode, Gaussian
 // "rectify" stamping, k-th value confidence mask, PCK.  Pure HBM sweeps: one pass over each operand, one block per
 // (b,k) row where a per-row result is needed.  Deterministic (no atomics).
-#include "common.h"
+#include "losses.h"
 
 namespace {
 constexpr int TPB = 256;

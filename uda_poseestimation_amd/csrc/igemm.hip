@@ -896,7 +896,7 @@ int igemm_stat_rows(int M, int Co, int nclass, int tile) {
 }
 
 int igemm_launch(IgParams& p, int tile, hipStream_t stream, const Policy& pol) {
-    p.dbg = pol.timeline;
+    p.dbg = (unsigned long long*)pol.timeline;
     if (p.flags & IG_FLAG_TAP0) p.flags &= ~IG_FLAG_TAP0;
     if (pol.igemm_tap0 && p.tap0) p.flags |= IG_FLAG_TAP0;
     const int bke = (p.flags & IG_FLAG_F32) ? 32 : 64;

@@ -1,0 +1,50 @@
+// Host launchers of the heat-map, loss and evaluation kernels.
+#pragma once
+#include "common.h"
+
+// heatmap.hip
+int hm_sqdiff_rows(hipStream_t s, const float* a, const float* b, const float* w, const unsigned char* mask, int R, int HW, float half,
+                   float* rows, float* mean_out, const unsigned char* valid, const float* count, int Kc);
+int hm_sqdiff_bwd(hipStream_t s, const float* a, const float* b, const float* w, const unsigned char* mask, const float* gscale, float coef,
+                  int R, int HW, float* da, const unsigned char* valid, const float* count, int Kc);
+int hm_mask_count(hipStream_t s, const unsigned char* m, size_t n, float* count);
+int hm_argmax_rectify(hipStream_t s, const float* hm, int R, int H, int W, float* maxv, int* idx, float* preds, float* rect, const float* patch,
+                      int rad);
+int hm_kth_mask(hipStream_t s, const float* act, const float* tm, int n, int k, float* thr_out, unsigned char* mask, const float* act_local,
+                int n_local);
+int hm_pck(hipStream_t s, const float* pred, const float* gt, int B, int K, float nh, float nw, float thr, float* acc, float* avg_cnt);
+// softmax_loss.hip
+int sml_kl_fwd(hipStream_t st, const float* s, const float* g, const float* w, float eps, int R, int group, int HW, float* rows, float* stats,
+               float* out);
+int sml_kl_bwd(hipStream_t st, const float* s, const float* g, const float* w, float eps, const float* stats, const float* gscale, int R, int HW,
+               float* ds);
+int sml_ent_fwd(hipStream_t st, const float* s, int R, int group, int HW, float thr, float* rows, float* stats, float* out, float* count);
+int sml_ent_bwd(hipStream_t st, const float* s, const float* rows, const float* stats, const float* count, const float* gscale, float thr, int R,
+                int HW, float* ds);
+int sml_cons_fwd(hipStream_t st, int mode, const float* s, const float* t, const unsigned char* mask, const unsigned char* valid,
+                 const float* count, int R, int Kc, int HW, float* rows, float* stats, float* out);
+int sml_cons_bwd(hipStream_t st, int mode, const float* s, const float* t, const unsigned char* mask, const unsigned char* valid,
+                 const float* count, const float* stats, const float* gscale, int R, int Kc, int HW, float* ds);
+// softargmax.hip
+int sa_fwd(hipStream_t st, const float* hm, int R, int H, int W, float beta, int window, float* coords, float* maxv, int* idx, float* stats);
+int sa_bwd(hipStream_t st, const float* hm, const float* g, const int* idx, const float* stats, int R, int H, int W, float beta, int window,
+           float* dh);
+int sa_coord_fwd(hipStream_t st, const float* hm, const float* tgt, const float* w, const unsigned char* mask, int R, int group, int H, int W,
+                 float beta, int window, int norm, float* rows, int* idx, float* stats, float* out);
+int sa_coord_bwd(hipStream_t st, const float* hm, const float* tgt, const float* w, const unsigned char* mask, const int* idx, const float* stats,
+                 const float* gscale, int R, int H, int W, float beta, int window, int norm, float* dh);
+// coral.hip
+long long coral_ws_bytes(int N, int K, int H, int W, int down);
+int coral_fwd(hipStream_t st, const float* src, const float* tgt, int N, int K, int H, int W, int down, void* ws, float* coef, float* loss);
+int coral_bwd(hipStream_t st, const float* src, const float* tgt, const float* coef, const float* gscale, int N, int K, int H, int W, int down,
+              float* dsrc, float* dtgt);
+// prior_map.hip
+int pm_weights(hipStream_t s, const float* sd, int K, float gamma, float epsilon, int v3, float* w);
+int pm_map(hipStream_t s, const float* coords, const float* conf, const float* mean, const float* w, const float* hm, int B, int K, int H, int W,
+           float sigma, int v3, float* out);
+int pm_pair_accumulate(hipStream_t s, const float* coords, const unsigned char* vis, int M, int K, double* acc);
+int pm_pair_finish(hipStream_t s, const double* acc, int K, float* mean, float* sd);
+// flip.hip
+int flip_hbatch(hipStream_t s, const float* src, float* dst, int N, size_t rows_per_image, int W, int keep_original);
+int flip_merge(hipStream_t s, const float* a, const float* f, const int* perm, int N, int K, int H, int W, int shift, int mode, float* out,
+               float* maxv, int* idx, float* preds);

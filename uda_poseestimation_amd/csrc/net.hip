@@ -17,56 +17,9 @@
 #include <cstdlib>
 #include <string>
 #include <vector>
-#include "conv_plan.h"
-
-int pw_nchw_f32_to_nhwc_bf16(hipStream_t, const float*, elem_t*, int, int, int, int);
-int pw_nhwc_to_nchw_f32(hipStream_t, const void*, int, float*, int, int, int, int, const float*, const float*);
-int pw_cast_f32_bf16(hipStream_t, const float*, elem_t*, size_t);
-int pw_transpose_cast(hipStream_t, const float*, elem_t*, int, int, int);
-int pw_pack_strided(hipStream_t, const float*, elem_t*, int, int, int, int, int, int, long, long, long, long);
-int pw_unpack_strided(hipStream_t, const float*, float*, int, int, int, int, int, int, long, long, long, long, float);
-int pw_bn_finalize(hipStream_t, const float*, int, int, double, const float*, const float*, float*, float*, long long*, float, float, float*, float*,
-                   float*, float*, const float*);
-int pw_bn_eval_coeff(hipStream_t, int, const float*, const float*, const float*, const float*, float, float*, float*);
-int pw_bn_apply(hipStream_t, const elem_t*, const elem_t*, elem_t*, size_t, int, const float*, const float*, int, unsigned char*, int);
-int pw_bn_bwd_rows(size_t);
-int pw_bn_bwd(hipStream_t, const void*, int, const elem_t*, const elem_t*, elem_t*, elem_t*, size_t, int, const float*, const float*, const float*, int,
-              float*, float*, float*, float*, float, const float*, int);
-int pw_bn_bwd_pre(hipStream_t, const void*, int, const elem_t*, elem_t*, size_t, int, const float*, const float*, const float*, const float*, int, float*,
-                  float*, float*, float, int, int);
-int pw_maxpool3x3s2_fwd(hipStream_t, const elem_t*, elem_t*, unsigned char*, int, int, int, int);
-int pw_maxpool3x3s2_bwd(hipStream_t, const elem_t*, const unsigned char*, elem_t*, int, int, int, int);
-int pw_bn_relu_maxpool3x3s2(hipStream_t, const elem_t*, elem_t*, unsigned char*, int, int, int, int, const float*, const float*);
-int pw_bn_bwd_pooled(hipStream_t, const elem_t*, const unsigned char*, int, int, const elem_t*, elem_t*, size_t, int, const float*, const float*,
-                     const float*, float*, float*, float*, float*, float, const float*);
-int pw_plane_sum(hipStream_t, const float*, float*, int, int, int, float);
-int pw_bn_running_update(hipStream_t, const float*, int, float*, float*, long long*, float);
-int pw_bn_running_update_multi(hipStream_t, const BnRunJob*, int, int, const void*, float);
-int pw_bn_train_fused(hipStream_t, const elem_t*, const elem_t*, elem_t*, size_t, int, const float*, int, const float*, const float*, float*, float*,
-                      long long*, float, float, float*, int, int, unsigned char*);
-int pw_zero_multi(hipStream_t, const ZeroJob*, int, void*);
-int pw_pack_multi(hipStream_t, const void*, const int*, const int*, int);
-int pw_nchw_f32_to_nhwc_f32(hipStream_t, const float*, float*, int, int, int, int);
-size_t opt_tail_job_bytes();
-int opt_chunk();
-void opt_tail_job_fill(void*, float*, const float*, float*, float*, float*, void*, void*, void*, void*, int, int, int, int, long long);
-void opt_tail_job_split(void*, long long, unsigned, int);
-void opt_tail_job_group(void*, int);
-int opt_tail_max_groups();
-int opt_tail(hipStream_t, const void*, const int*, const int*, int, int, float, float, float, float, int, int, float, int, float* const*, const float*, float,
-             float, int, long long, int, const void*, const void*);
-int pw_transpose_f32(hipStream_t, const float*, float*, int, int, int);
-int pw_pack_strided_f32(hipStream_t, const float*, float*, int, int, int, int, int, int, long, long, long, long);
-int pw_bn_apply_f32(hipStream_t, const float*, const float*, float*, size_t, int, const float*, const float*, int);
-int pw_maxpool3x3s2_fwd_f32(hipStream_t, const float*, float*, unsigned char*, int, int, int, int);
-int pw_nchw_f32_to_nhwc_split(hipStream_t, const float*, void*, int, int, int, int, void*);
-int pw_f32_to_split(hipStream_t, const float*, void*, size_t);
-int pw_transpose_split(hipStream_t, const float*, void*, int, int, int);
-int pw_pack_strided_split(hipStream_t, const float*, void*, int, int, int, int, int, int, long, long, long, long);
-int pw_bn_apply_split(hipStream_t, const float*, const void*, void*, size_t, int, const float*, const float*, int, void*, void*, unsigned char*, int);
-int pw_bn_train_fused_split(hipStream_t, const float*, const void*, void*, size_t, int, const float*, int, const float*, const float*, float*, float*,
-                            long long*, float, float, float*, int, int, void*, void*, unsigned char*);
-int pw_maxpool3x3s2_fwd_split(hipStream_t, const void*, void*, unsigned char*, int, int, int, int, void*);
+#include "net.h"
+#include "pointwise.h"
+#include "optim.h"
 
 namespace {
 
@@ -176,7 +129,7 @@ struct Net {
     };
     std::deque<WgGroup> wg_groups;       // (stable addresses, never evicted: a captured hipGraph may reference any table built so far)
     // fused optimizer tail (Adam + EMA + weight packs of student and teacher in one sweep): device job table
-    struct UpdTab { void* jobs = nullptr; int* blk_job = nullptr; int* blk_sub = nullptr; int nblocks = 0;
+    struct UpdTab { TailJob* jobs = nullptr; int* blk_job = nullptr; int* blk_sub = nullptr; int nblocks = 0;
                     const void* k_ps = nullptr; const void* k_pt = nullptr; const void* k_g = nullptr; const void* k_m = nullptr;
                     const void* k_ws = nullptr; const void* k_wt = nullptr;
                     int kind = 0, ngroups = 1; };       // (optimizer the table was bound for: 0 Adam, 1 SGD; number of parameter groups)
@@ -1058,7 +1011,7 @@ int run_wg_group(hipStream_t s, Net& n, const char* act, char* ws, void* const* 
         unsigned long long* stamps = nullptr;
         if (n.policy.timeline) {
             if (stamped + 8 * (size_t)G->per_xcd[t] > WG_STAMP_BLOCKS) return UDAPOSE_ERR_ARG;
-            stamps = n.policy.timeline + stamped * 8;
+            stamps = (unsigned long long*)n.policy.timeline + stamped * 8;
             stamped += 8 * (size_t)G->per_xcd[t];
         }
         const int tok = conv_prof_before(s, 2, G->flops[t]);
@@ -1101,7 +1054,7 @@ int run_wg_pair(hipStream_t s, Net& n, const char* actA, char* wsA, void* const*
         unsigned long long* stamps = nullptr;
         if (n.policy.timeline) {
             if (stamped + 16 * (size_t)GA->per_xcd[t] > WG_STAMP_BLOCKS) return UDAPOSE_ERR_ARG;
-            stamps = n.policy.timeline + stamped * 8;
+            stamps = (unsigned long long*)n.policy.timeline + stamped * 8;
             stamped += 16 * (size_t)GA->per_xcd[t];
         }
         const int tok = conv_prof_before(s, 2, GA->flops[t] + GB->flops[t]);
@@ -1354,7 +1307,7 @@ long long net_grad_split_param(void* h) {
 // h_m / h_v: host arrays of the Adam moments per parameter index, NULL entries for parameters without gradient (backbone.fc:
 // EMA only).  bind builds the device job table (allocates: outside capture); the update itself only launches.
 // kind 1 (SGD with momentum): h_m holds the momentum buffers, h_v is not read.  group_idx (NULL: one group): the parameter group of every
-// parameter, at most opt_tail_max_groups() of them.
+// parameter, at most TAIL_GROUPS of them.
 int net_bind_update_groups(void* hs, void* ht, int kind, void* const* params_s, void* const* grads, void* const* h_m, void* const* h_v,
                            void* const* params_t, void* wpack_s_, void* wpack_t_, const int* group_idx) {
     Net& n = *(Net*)hs;
@@ -1364,7 +1317,7 @@ int net_bind_update_groups(void* hs, void* ht, int kind, void* const* params_s, 
     if (group_idx)
         for (int i = 0; i < n.n_params; ++i) {
             if (group_idx[i] < 0) return UDAPOSE_ERR_ARG;
-            if (group_idx[i] >= opt_tail_max_groups()) return UDAPOSE_ERR_UNSUPPORTED;
+            if (group_idx[i] >= TAIL_GROUPS) return UDAPOSE_ERR_UNSUPPORTED;
             ngroups = std::max(ngroups, group_idx[i] + 1);
         }
     const Net& nt = *(const Net*)ht;
@@ -1378,8 +1331,7 @@ int net_bind_update_groups(void* hs, void* ht, int kind, void* const* params_s, 
         return UDAPOSE_ERR_UNSUPPORTED;
     char* ws_ = (char*)wpack_s_;
     char* wt_ = (char*)wpack_t_;
-    const size_t jb = opt_tail_job_bytes();
-    std::vector<char> jobs;
+    std::vector<TailJob> jobs;
     std::vector<int> bj, bs;
     std::vector<char> covered(n.n_params, 0);
     // the split jobs of these gradient tensors' weight-gradient table (overwriting whole backward, current policy), if it is bound already: a job
@@ -1396,20 +1348,21 @@ int net_bind_update_groups(void* hs, void* ht, int kind, void* const* params_s, 
             const uintptr_t al = (uintptr_t)params_s[idx] | (uintptr_t)params_t[idx] | (adam ? ((uintptr_t)grads[idx] | (uintptr_t)h_m[idx] | (uintptr_t)v_idx) : 0);
             if ((al & 15) || (A & 63) || (B & 63) || (long long)A * T * B != numel) return UDAPOSE_ERR_UNSUPPORTED;
         }
-        jobs.resize(jobs.size() + jb);
-        opt_tail_job_fill(jobs.data() + jobs.size() - jb, (float*)params_s[idx], (const float*)grads[idx], (float*)h_m[idx], (float*)v_idx,
-                          (float*)params_t[idx], sd, td, sx, tx, A, T, B, adam, numel);
-        opt_tail_job_group(jobs.data() + jobs.size() - jb, group_idx ? group_idx[idx] : 0);
+        jobs.emplace_back();      // (value-initialised: every byte the table upload copies is defined, padding included)
+        TailJob& j = jobs.back();
+        j.p = (float*)params_s[idx]; j.g = (const float*)grads[idx]; j.m = (float*)h_m[idx]; j.v = (float*)v_idx; j.t = (float*)params_t[idx];
+        j.sd = (elem_t*)sd; j.td = (elem_t*)td; j.sx = (elem_t*)sx; j.tx = (elem_t*)tx;
+        j.A = A; j.T = T; j.B = B; j.adam = adam; j.n = numel;
+        j.group = group_idx ? group_idx[idx] : 0;
         if (SG && adam)
             for (const SumJob& sj : SG->h_sum)
                 if (!sj.dst_ws && sj.dst_off == (const char*)grads[idx] - (const char*)grads[0]) {
                     if ((long long)sj.n != numel) return UDAPOSE_ERR_UNSUPPORTED;
-                    opt_tail_job_split(jobs.data() + jobs.size() - jb, sj.part_off, sj.stride, sj.ks);
+                    j.part_off = sj.part_off; j.stride = sj.stride; j.ks = sj.ks;
                     ++split_found;
                 }
-        const int j = (int)(jobs.size() / jb) - 1;
         const long nb = A ? (long)(A / 64) * (B / 64) * T : (long)((numel + opt_chunk() - 1) / opt_chunk());
-        for (long k = 0; k < nb; ++k) { bj.push_back(j); bs.push_back((int)k); }
+        for (long k = 0; k < nb; ++k) { bj.push_back((int)jobs.size() - 1); bs.push_back((int)k); }
         covered[idx] = 1;
         return UDAPOSE_OK;
     };
@@ -1439,10 +1392,10 @@ int net_bind_update_groups(void* hs, void* ht, int kind, void* const* params_s, 
     n.upd_sum_group = nullptr;
     Net::UpdTab& u = n.upd;
     if (u.jobs) { (void)hipFree(u.jobs); (void)hipFree(u.blk_job); (void)hipFree(u.blk_sub); u.jobs = nullptr; }
-    if (hipMalloc(&u.jobs, jobs.size()) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
+    if (hipMalloc((void**)&u.jobs, jobs.size() * sizeof(TailJob)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
     if (hipMalloc((void**)&u.blk_job, bj.size() * sizeof(int)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
     if (hipMalloc((void**)&u.blk_sub, bs.size() * sizeof(int)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMemcpy(u.jobs, jobs.data(), jobs.size(), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
+    if (hipMemcpy(u.jobs, jobs.data(), jobs.size() * sizeof(TailJob), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
     if (hipMemcpy(u.blk_job, bj.data(), bj.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
     if (hipMemcpy(u.blk_sub, bs.data(), bs.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
     u.nblocks = (int)bj.size();
@@ -1497,7 +1450,7 @@ int net_fused_update(void* hs, void* ht, hipStream_t s, void* const* params_s, v
 int net_fused_update_groups(void* hs, void* ht, hipStream_t s, int kind, void* const* params_s, void* const* grads, void* const* h_m,
                             void* const* params_t, void* wpack_s_, void* wpack_t_, float beta1, float beta2, float eps, int nesterov, int ngroups,
                             float* const* states, const float* wds, float alpha, float oma, int do_opt, long long grad2_delta) {
-    if (ngroups < 1 || ngroups > opt_tail_max_groups() || !states || !wds) return UDAPOSE_ERR_ARG;
+    if (ngroups < 1 || ngroups > TAIL_GROUPS || !states || !wds) return UDAPOSE_ERR_ARG;
     for (int g = 0; g < ngroups; ++g)
         if (!states[g]) return UDAPOSE_ERR_ARG;
     return fused_update(hs, ht, s, kind, params_s, grads, h_m, params_t, wpack_s_, wpack_t_, 0.f, beta1, beta2, eps, nesterov, 0, 1.f, ngroups, states, wds,

@@ -1,6 +1,6 @@
 // Multi-tensor optimizer kernels: EMA teacher update, Adam, SGD(nesterov).  One launch sweeps every parameter tensor
 // through a block -> (tensor, offset) table; 16-byte accesses; HBM-roofline bound (EMA 12 B/param, Adam 28 B/param).
-#include "common.h"
+#include "optim.h"
 
 // no FMA contraction in this file: the EMA must round p*alpha and src*(1-alpha) separately to be bit-identical with the
 // reference's two-step update (hipcc contracts a*b+c by default, and __fmul_rn/__fadd_rn do not prevent it)
@@ -171,16 +171,7 @@ __global__ void scaler_update_k(float* __restrict__ state, float growth, float b
 // Linear jobs (BatchNorm vectors, biases, stem / head / fc weights): 4096-element chunks, optional same-layout packs.
 // Tiled jobs (conv / deconv weights [A][T][B], A and B multiples of 64): one 64 x 64 tile of one tap per block; the
 // same-layout pack is written from registers, the transposed pack [B][T][A] goes through an LDS tile.
-struct TailJob {
-    float* p; const float* g; float* m; float* v; float* t;   // student parameter, gradient, moments, teacher parameter
-    elem_t* sd; elem_t* td; elem_t* sx; elem_t* tx;             // packs: student / teacher same-layout, student / teacher transposed
-    int A, T, B, adam;                                          // A == 0: linear job; adam == 0: no gradient (EMA + packs only)
-    long long n;
-    // a gradient whose pixel reduction was split (net.hip make_partial): `ks` partial tensors in the gradient's own layout, `stride` floats apart,
-    // at byte offset part_off of a pass's workspace (ks == 0: not split)
-    long long part_off; unsigned stride; int ks;
-    int group;                                                  // parameter group: index into TailGroups
-};
+// (struct TailJob, the table entry: optim.h)
 
 // g2: byte distance to a second gradient buffer (0: none).  ws1 / ws2 (SPLIT sweeps): the workspaces of the two passes whose split sums were left to
 // this sweep (udapose_net_wgrad_pair_defer): a split job's g and g + g2 are then NOT read - the sweep adds the partial tensors itself.
@@ -189,7 +180,6 @@ struct TailHyper { float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, gscale, alpha
                    int nesterov, first; };
 // Parameter groups (PoseResNet.get_parameters: the backbone at a tenth of the rate): a job reads lr - and for Adam the bias corrections -
 // from its group's 8-float device state and weight_decay from this table, passed by value.  state[g] == NULL: the by-value TailHyper holds.
-constexpr int TAIL_GROUPS = 8;
 struct TailGroups { const float* state[TAIL_GROUPS]; float wd[TAIL_GROUPS]; };
 enum { KIND_ADAM = 0, KIND_SGD = 1 };
 // one launch advances every group's counter (adam_tick_k / sgd_tick_k per group, one thread each)
@@ -328,26 +318,12 @@ __global__ __launch_bounds__(TPB) void opt_tail_k(const TailJob* __restrict__ jo
 }  // namespace
 
 int opt_chunk() { return CHUNK; }
-size_t opt_tail_job_bytes() { return sizeof(TailJob); }
-// host-side filler of one table entry (net.hip builds the table: it knows the pack offsets)
-void opt_tail_job_fill(void* dst, float* p, const float* g, float* m, float* v, float* t, void* sd, void* td, void* sx, void* tx, int A, int T, int B,
-                       int adam, long long n) {
-    TailJob j{p, g, m, v, t, (elem_t*)sd, (elem_t*)td, (elem_t*)sx, (elem_t*)tx, A, T, B, adam, n, 0, 0u, 0, 0};
-    *(TailJob*)dst = j;
-}
-// ... and where its gradient's partial tensors lie, when the weight-gradient launches split its pixel reduction
-void opt_tail_job_split(void* dst, long long part_off, unsigned stride, int ks) {
-    TailJob& j = *(TailJob*)dst;
-    j.part_off = part_off; j.stride = stride; j.ks = ks;
-}
-void opt_tail_job_group(void* dst, int group) { ((TailJob*)dst)->group = group; }
-int opt_tail_max_groups() { return TAIL_GROUPS; }
 // kind: 0 = Adam, 1 = SGD (beta1 is then the momentum; beta2 / eps unused).  states[g] / wds[g]: the 8-float device state and the weight decay of
 // parameter group g, ngroups <= 8.  Either every state is given (lr, grad_scale, counter and found-inf are read from it; SGD needs that) or none
 // (one group, Adam: `lr`, `step`, `gscale` are the host's).
 // tick: advance the device-side step counter / bias corrections in front of the sweep (once per optimizer step: a step whose sweep is
 // issued in two parts ticks with the first)
-int opt_tail(hipStream_t s, const void* d_jobs, const int* blk_job, const int* blk_sub, int nblocks, int kind, float lr, float beta1, float beta2,
+int opt_tail(hipStream_t s, const TailJob* d_jobs, const int* blk_job, const int* blk_sub, int nblocks, int kind, float lr, float beta1, float beta2,
              float eps, int nesterov, int step, float gscale, int ngroups, float* const* states, const float* wds, float alpha, float oma, int do_adam,
              long long grad2_delta, int tick, const void* split_ws1, const void* split_ws2) {
     if (grad2_delta % 16) return UDAPOSE_ERR_ARG;
@@ -366,9 +342,9 @@ int opt_tail(hipStream_t s, const void* d_jobs, const int* blk_job, const int* b
     TailHyper h{lr, beta1, beta2, eps, wds[0], (float)bc1, (float)sqrt(bc2), gscale, alpha, oma, do_adam, grad2_delta, (const char*)split_ws1, (const char*)split_ws2,
                 nesterov, 0};
     const dim3 grid(nblocks), block(TPB);
-    if (kind == KIND_SGD) hipLaunchKernelGGL((opt_tail_k<KIND_SGD, false>), grid, block, 0, s, (const TailJob*)d_jobs, blk_job, blk_sub, h, G);
-    else if (split_ws1) hipLaunchKernelGGL((opt_tail_k<KIND_ADAM, true>), grid, block, 0, s, (const TailJob*)d_jobs, blk_job, blk_sub, h, G);
-    else hipLaunchKernelGGL((opt_tail_k<KIND_ADAM, false>), grid, block, 0, s, (const TailJob*)d_jobs, blk_job, blk_sub, h, G);
+    if (kind == KIND_SGD) hipLaunchKernelGGL((opt_tail_k<KIND_SGD, false>), grid, block, 0, s, d_jobs, blk_job, blk_sub, h, G);
+    else if (split_ws1) hipLaunchKernelGGL((opt_tail_k<KIND_ADAM, true>), grid, block, 0, s, d_jobs, blk_job, blk_sub, h, G);
+    else hipLaunchKernelGGL((opt_tail_k<KIND_ADAM, false>), grid, block, 0, s, d_jobs, blk_job, blk_sub, h, G);
     return udapose_check_launch();
 }
 int opt_grad_check(hipStream_t s, const long long* g, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks,

@@ -2,7 +2,7 @@
 // (finalize / apply / backward), 3x3 s2 and 2x2 ceil max-pooling.  All activation tensors are NHWC bf16 and every
 // thread moves 16 bytes (8 channels) per access.  These kernels are HBM-roofline bound (8 TB/s peak).
 #include <stdlib.h>
-#include "common.h"
+#include "pointwise.h"
 
 namespace {
 

@@ -1,7 +1,7 @@
 // Skeleton-prior maps (the reference's generate_prior_map, utils.py:111-145) and the pairwise joint-distance statistics that feed them.
 // The reference materialises five [B][K][K][H][W] tensors; here one launch reads B*K decoded coordinates and two K x K tables and writes
 // the [B][K][H][W] result once.  fp32 throughout the map (the statistics accumulate in fp64), no atomics, no scratch, nothing allocated.
-#include "common.h"
+#include "losses.h"
 #include <math.h>
 
 namespace {

@@ -5,7 +5,7 @@
 #include <atomic>
 #include <mutex>
 #include <vector>
-#include "common.h"
+#include "net.h"
 
 namespace {
 struct Rec { hipEvent_t a, b; double flops; int kind; };

@@ -8,6 +8,7 @@
 // gradient: dh_i = beta p_i ((x_i - cx) gx + (y_i - cy) gy) in O, 0 outside.  m = NaN / +-inf makes exp(beta (h - m)) NaN: NaN coordinates.
 // The forward stores per row what the backward needs (arg-max index; m, 1 / Z, cx, cy), so the backward is one sweep.
 #include "softmax_rows.h"
+#include "losses.h"
 
 namespace {
 // O as inclusive column bounds and the flat range [lo, hi) of its lines: most pixels are turned away by two compares, before any division

@@ -8,6 +8,7 @@
 // thread and operand) across the max / sum / loss passes; longer or ragged rows are re-read (L2-resident).  The forward stores per row
 // what the backward needs (the triple of each operand and one or two scalars), so the backward is one sweep.
 #include "softmax_rows.h"      // Row / each2 / row_map, the block reductions, reduce_rows_k
+#include "losses.h"
 
 namespace {
 // The soft-max of one row: p_i = exp(x_i - mx) * inv, log p_i = (x_i - mx) - lsum.  Kept per row in `stats` as three floats.

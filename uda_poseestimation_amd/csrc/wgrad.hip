@@ -10,6 +10,7 @@
 // grid = (r_tiles*c_tiles, taps (or tap groups of 4 when Ci==8), ksplit).  ksplit>1 or accumulate -> fp32 atomics.
 #include <stdlib.h>
 #include "conv_plan.h"
+#include "pointwise.h"      // pw_zero
 
 namespace {
 
