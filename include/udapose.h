@@ -483,6 +483,28 @@ int udapose_hflip_batch(void* stream, const float* src, float* dst, int N, size_
  * ties, NaN as the maximum, coordinates zeroed where the maximum is <= 0.  One work-group per (n, k) plane, no atomics, no scratch. */
 int udapose_flip_merge(void* stream, const float* a, const float* f, const int* perm, int N, int K, int H, int W, int shift, int mode,
                        float* out, float* maxvals, int* flat_idx, float* preds_xy);
+/* Sub-pixel decodes of hm [R][H*W] fp32 (no counterpart in the reference; the two decodes published with Simple Baselines and DARK,
+ * "Distribution-Aware Coordinate Representation for Human Pose Estimation").  (x*, y*), m = maxvals[r] and flat_idx[r] are exactly what
+ * udapose_heatmap_argmax returns for the row (first flat index on ties, NaN as the largest value; maxvals and flat_idx may be NULL).
+ * Where m > 0 is false coords[r] = (0, 0), as get_max_preds gives, and nothing is refined; otherwise coords[r] = (x*, y*) + offset:
+ * mode 0 (quarter): if 1 < x* < W-1 and 1 < y* < H-1 (both), offset = 0.25 * (sign(h[y*][x*+1] - h[y*][x*-1]),
+ *   sign(h[y*+1][x*] - h[y*-1][x*])) with sign(0) = 0 and a NaN difference adding nothing.  Nothing is staged; kernel and sigma are ignored.
+ * mode 1 (DARK): kernel odd, 3 <= kernel <= 31; sigma <= 0 selects 0.3 * ((kernel - 1) / 2 - 1) + 0.8 (2.0 at 11).  Taps
+ *   t_i = exp(-(i - c)^2 / 2 sigma^2) / sum, c = (kernel - 1) / 2, computed in double and rounded to fp32.  g = the separable blur of the map
+ *   (rows, then columns; zero padding of c on every side; taps added in ascending order), g *= m / max(g), g = log(max(g, 1e-10)).
+ *   If 1 < x* < W-2 and 1 < y* < H-2, with the central differences at (x*, y*)
+ *     dx = (g[y][x+1] - g[y][x-1]) / 2, dy likewise, dxx = (g[y][x+2] - 2 g[y][x] + g[y][x-2]) / 4, dyy likewise,
+ *     dxy = (g[y+1][x+1] - g[y-1][x+1] - g[y+1][x-1] + g[y-1][x-1]) / 4,
+ *   offset = -Hess^-1 (dx, dy)^T, Hess = [[dxx, dxy], [dxy, dyy]].  Three guards leave (x*, y*) unrefined where the published code divides
+ *   regardless: max(g) > 0 is false (a positive peak in a negative surround: the scale m / max(g) has no meaning), det Hess == 0 (a flat or
+ *   clamped neighbourhood), and an offset that is not finite (inf or NaN in the map).
+ * One launch, one work-group per map.  Mode 1 stages the map in LDS and blurs it there (2 * H * W * 4 bytes: the map, then g, and the
+ * row-blurred map), so g never reaches memory; it takes H * W <= UDAPOSE_REFINE_MAX_PIXELS (every kernel size; 64x64 and 96x96 fit) and
+ * returns UDAPOSE_ERR_ARG beyond it, as for a null hm or coords, R, H or W < 1, a mode other than 0 or 1, a bad kernel or a sigma that is
+ * NaN or +inf, with nothing launched.  No atomics, no scratch, fixed summation order: capturable, and two calls give the same bits. */
+#define UDAPOSE_REFINE_MAX_PIXELS 19200
+int udapose_refine_decode(void* stream, const float* hm, int R, int H, int W, int mode, int kernel, float sigma, float* coords, float* maxvals,
+                          int* flat_idx);
 /* confidence mask (train_human.py:427-430): thr = k-th smallest of act[n]; mask[i] = (tea_mask[i]*act_local[i]) > thr */
 int udapose_kth_mask(void* stream, const float* act, const float* tea_mask, int n, int k, float* thr_out, unsigned char* mask,
                      const float* act_local, int n_local);
@@ -693,6 +715,13 @@ int udapose_aug_resized_crop_u8(void* stream, const unsigned char* src, unsigned
 int udapose_aug_to_tensor(void* stream, const unsigned char* img, float* out, int N, int HW, const float* mean3, const float* std3);
 int udapose_gaussian_labels(void* stream, const double* kp, const float* vis, float* target, float* weight, int R, int Hh, int Wh,
                             double stride_x, double stride_y, const float* patch, int rad);
+/* The un-quantised label encoding (DARK's second half; no counterpart in the reference).  Centre c = int(kp / stride + 0.5) and weight
+ * exactly as udapose_gaussian_labels finds them (weight = vis, 0 when c is outside the map); target[y][x] =
+ * exp(-((x - mx)^2 + (y - my)^2) / (2 sigma^2)) with m = kp / stride NOT rounded, computed in double and rounded to fp32, where
+ * |x - cx| <= rad, |y - cy| <= rad and weight > 0.5; 0 elsewhere.  Every element of target and weight is written.
+ * UDAPOSE_ERR_ARG: a null pointer, R, Hh or Wh < 1, rad < 0, sigma not finite or <= 0. */
+int udapose_gaussian_labels_subpixel(void* stream, const double* kp, const float* vis, float* target, float* weight, int R, int Hh, int Wh,
+                                     double stride_x, double stride_y, double sigma, int rad);
 /* draw_labelmap_ori (lib/datasets/util.py:326-363), the animal pipelines' label generator as their datasets call it
  * (lib/datasets/real_animal_all_mt.py:274-283, animal_pose_mt.py:169-177,200-205; BASELINE.json configs[4]): pt [R][2] float32 = the 0-based
  * centres the datasets pass (`tpts[i] - 1`), truncated to int32 inside; vis [R] = pts[:, 2]; gate [R] uint8 = the datasets' `tpts[i, 1] > 0`

@@ -142,6 +142,7 @@ _SIGS = {
     "udapose_pair_dist_finish": (ci, [vp, vp, ci, vp, vp]),
     "udapose_hflip_batch": (ci, [vp, vp, vp, ci, sz, ci, ci]),
     "udapose_flip_merge": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
+    "udapose_refine_decode": (ci, [vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, vp]),
     "udapose_kth_mask": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, ci]),
     "udapose_pck": (ci, [vp, vp, vp, ci, ci, cf, cf, cf, vp, vp]),
     "udapose_multi_chunk": (ci, []),
@@ -163,6 +164,7 @@ _SIGS = {
     "udapose_aug_gaussian_blur_u8": (ci, [vp, vp, vp, vp, ci, ci, ci]),
     "udapose_aug_resized_crop_u8": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci]),
     "udapose_gaussian_labels": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, cd, cd, vp, ci]),
+    "udapose_gaussian_labels_subpixel": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, cd, cd, cd, ci]),
     "udapose_split_saturations": (ci, [ci, vp]),
     "udapose_mean_views": (ci, [vp, vp, ci, vp, sz]),
     "udapose_draw_labelmap_ori": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, vp, ci]),

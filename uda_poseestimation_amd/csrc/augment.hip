@@ -118,6 +118,29 @@ __global__ void gaussian_labels_k(const double* __restrict__ kp, const float* __
         t[i] = (draw && gx >= 0 && gx < size && gy >= 0 && gy < size) ? patch[gy * size + gx] : 0.f;
     }
 }
+// The un-quantised encoding: centre and weight as above, but the Gaussian sits on kp / stride itself.  exp in double, rounded once;
+// written inside the (2*rad+1)^2 window round the integer centre, 0 elsewhere.  c = -1 / (2 sigma^2).
+__global__ void gaussian_labels_subpixel_k(const double* __restrict__ kp, const float* __restrict__ vis, float* __restrict__ target,
+                                           float* __restrict__ weight, int Hh, int Wh, double stride_x, double stride_y, double c, int rad) {
+    const size_t r = blockIdx.x;
+    const double ux = kp[r * 2] / stride_x, uy = kp[r * 2 + 1] / stride_y;
+    const int mx = (int)(ux + 0.5), my = (int)(uy + 0.5);
+    float w = vis[r];
+    const bool outside = mx >= Wh || my >= Hh || mx < 0 || my < 0;
+    if (outside) w = 0.f;
+    if (threadIdx.x == 0) weight[r] = w;
+    const bool draw = !outside && w > 0.5f;
+    float* t = target + r * (size_t)Hh * Wh;
+    for (int i = threadIdx.x; i < Hh * Wh; i += TPB) {
+        const int y = i / Wh, x = i - y * Wh;
+        float v = 0.f;
+        if (draw && abs(x - mx) <= rad && abs(y - my) <= rad) {
+            const double ex = (double)x - ux, ey = (double)y - uy;
+            v = (float)exp((ex * ex + ey * ey) * c);
+        }
+        t[i] = v;
+    }
+}
 // draw_labelmap_ori (lib/datasets/util.py:326-363), the label generator of the animal `_mt` datasets (call loop:
 // lib/datasets/real_animal_all_mt.py:274-283, animal_pose_mt.py:169-177,200-205): row r's centre is pt[r] truncated to int32
 // (`pt.to(torch.int32)`), the stamp's corners are int(centre -+ r3 (+ 1)) with the sums in float32 (an int32 tensor and a Python
@@ -276,6 +299,14 @@ int aug_gaussian_labels(hipStream_t s, const double* kp, const float* vis, float
                         double stride_y, const float* patch, int rad) {
     if (R <= 0 || Hh <= 0 || Wh <= 0 || rad < 0 || !patch) return UDAPOSE_ERR_ARG;
     hipLaunchKernelGGL(gaussian_labels_k, dim3(R), dim3(TPB), 0, s, kp, vis, target, weight, Hh, Wh, stride_x, stride_y, patch, rad);
+    return udapose_check_launch();
+}
+int aug_gaussian_labels_subpixel(hipStream_t s, const double* kp, const float* vis, float* target, float* weight, int R, int Hh, int Wh,
+                                 double stride_x, double stride_y, double sigma, int rad) {
+    if (!kp || !vis || !target || !weight || R <= 0 || Hh <= 0 || Wh <= 0 || rad < 0 || (long long)Hh * Wh > 0x7fffffffLL) return UDAPOSE_ERR_ARG;
+    if (!(sigma > 0.0) || !(sigma <= 1.7976931348623157e308)) return UDAPOSE_ERR_ARG;
+    hipLaunchKernelGGL(gaussian_labels_subpixel_k, dim3(R), dim3(TPB), 0, s, kp, vis, target, weight, Hh, Wh, stride_x, stride_y,
+                       -1.0 / (2.0 * sigma * sigma), rad);
     return udapose_check_launch();
 }
 int aug_draw_labelmap_ori(hipStream_t s, const float* pt, const float* vis, const unsigned char* gate, float* target, float* weight, int R, int Hh,

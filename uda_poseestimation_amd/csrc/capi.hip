@@ -419,6 +419,10 @@ int udapose_flip_merge(void* stream, const float* a, const float* f, const int* 
                        float* maxvals, int* flat_idx, float* preds_xy) {
     return flip_merge(S(stream), a, f, perm, N, K, H, W, shift, mode, out, maxvals, flat_idx, preds_xy);
 }
+int udapose_refine_decode(void* stream, const float* hm, int R, int H, int W, int mode, int kernel, float sigma, float* coords, float* maxvals,
+                          int* flat_idx) {
+    return refine_decode(S(stream), hm, R, H, W, mode, kernel, sigma, coords, maxvals, flat_idx);
+}
 int udapose_kth_mask(void* stream, const float* act, const float* tm, int n, int k, float* thr_out, unsigned char* mask, const float* act_local,
                      int n_local) {
     return hm_kth_mask(S(stream), act, tm, n, k, thr_out, mask, act_local, n_local);
@@ -542,6 +546,11 @@ int udapose_gaussian_labels(void* stream, const double* kp, const float* vis, fl
                             double stride_x, double stride_y, const float* patch, int rad) {
     if (!kp || !vis || !target || !weight) return UDAPOSE_ERR_ARG;
     return aug_gaussian_labels(S(stream), kp, vis, target, weight, R, Hh, Wh, stride_x, stride_y, patch, rad);
+}
+int udapose_gaussian_labels_subpixel(void* stream, const double* kp, const float* vis, float* target, float* weight, int R, int Hh, int Wh,
+                                     double stride_x, double stride_y, double sigma, int rad) {
+    if (!kp || !vis || !target || !weight) return UDAPOSE_ERR_ARG;
+    return aug_gaussian_labels_subpixel(S(stream), kp, vis, target, weight, R, Hh, Wh, stride_x, stride_y, sigma, rad);
 }
 int udapose_draw_labelmap_ori(void* stream, const float* pt, const float* vis, const unsigned char* gate, float* target, float* weight, int R,
                               int Hh, int Wh, float r3, const float* patch, int psize) {

@@ -20,5 +20,7 @@ int aug_color_op(hipStream_t s, unsigned char* img, const int* op, const float* 
 int aug_to_tensor(hipStream_t s, const unsigned char* img, float* out, int N, int HW, const float* mean3, const float* std3);
 int aug_gaussian_labels(hipStream_t s, const double* kp, const float* vis, float* target, float* weight, int R, int Hh, int Wh, double stride_x,
                         double stride_y, const float* patch, int rad);
+int aug_gaussian_labels_subpixel(hipStream_t s, const double* kp, const float* vis, float* target, float* weight, int R, int Hh, int Wh,
+                                 double stride_x, double stride_y, double sigma, int rad);
 int aug_draw_labelmap_ori(hipStream_t s, const float* pt, const float* vis, const unsigned char* gate, float* target, float* weight, int R, int Hh,
                           int Wh, float r3, const float* patch, int psize);

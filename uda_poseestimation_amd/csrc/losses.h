@@ -48,3 +48,5 @@ int pm_pair_finish(hipStream_t s, const double* acc, int K, float* mean, float* 
 int flip_hbatch(hipStream_t s, const float* src, float* dst, int N, size_t rows_per_image, int W, int keep_original);
 int flip_merge(hipStream_t s, const float* a, const float* f, const int* perm, int N, int K, int H, int W, int shift, int mode, float* out,
                float* maxv, int* idx, float* preds);
+// refine.hip
+int refine_decode(hipStream_t s, const float* hm, int R, int H, int W, int mode, int kernel, float sigma, float* coords, float* maxv, int* idx);

@@ -188,8 +188,11 @@ class TargetViewPipeline:
     """Batched device pipeline for the `_mt` datasets' student / teacher views."""
 
     def __init__(self, image_size=256, heatmap_size=64, sigma=2, k=1, student=None, teacher=None, mean=IMAGENET_MEAN, std=IMAGENET_STD,
-                 rng=None, resize_scale=(0.6, 1.3), np_rng=None):
+                 rng=None, resize_scale=(0.6, 1.3), np_rng=None, subpixel_labels=False):
         self.image_size, self.heatmap_size, self.sigma, self.k = int(image_size), int(heatmap_size), sigma, int(k)
+        # labels(): False = generate_target's Gaussian on the rounded position (the reference); True = on the position itself, the encoding
+        # that lib.keypoint_detection.dark_decode inverts (no counterpart in the reference)
+        self.subpixel_labels = bool(subpixel_labels)
         self.stu, self.tea = student or ViewConfig(), teacher or ViewConfig()
         self.mean, self.std = tuple(mean), tuple(std)
         self.rng = rng if rng is not None else random
@@ -302,7 +305,9 @@ class TargetViewPipeline:
         return out
 
     def labels(self, keypoints, visible, device):
-        """generate_target for [N,K,2] key points (numpy float64, image pixels) -> (target [N,K,Hh,Wh], weight [N,K,1]) on device."""
+        """generate_target for [N,K,2] key points (numpy float64, image pixels) -> (target [N,K,Hh,Wh], weight [N,K,1]) on device.
+        With subpixel_labels the Gaussian is evaluated round keypoint / stride itself (udapose_gaussian_labels_subpixel): same window, same
+        weights, no half-pixel rounding of the position."""
         c = self._consts(device)
         N, K, _ = keypoints.shape
         kp = torch.from_numpy(np.ascontiguousarray(keypoints, dtype=np.float64)).to(device, non_blocking=True)
@@ -311,6 +316,10 @@ class TargetViewPipeline:
         target = torch.empty(N, K, Hh, Wh, dtype=torch.float32, device=device)
         weight = torch.empty(N, K, 1, dtype=torch.float32, device=device)
         stride = self.image_size / self.heatmap_size
+        if self.subpixel_labels:
+            check(lib().udapose_gaussian_labels_subpixel(_hip.stream(), ptr(kp), ptr(vis), ptr(target), ptr(weight), N * K, Hh, Wh, float(stride),
+                                                         float(stride), float(self.sigma), c["rad"]), "gaussian_labels_subpixel")
+            return target, weight
         check(lib().udapose_gaussian_labels(_hip.stream(), ptr(kp), ptr(vis), ptr(target), ptr(weight), N * K, Hh, Wh, float(stride), float(stride),
                                             ptr(c["patch"]), c["rad"]), "gaussian_labels")
         return target, weight

@@ -629,7 +629,7 @@ def validate(batches, model, criterion=None, decode="argmax"):
     (x, label, weight[, meta]).  Decode and PCK run on the device and are ACCUMULATED there: one read-back at the end
     instead of the reference's 2 x 8.4 MB device->host copy + sync per batch.  Returns (acc_per_keypoint list, mean_loss)
     (the caller applies its dataset's group_accuracy).  decode: how the predictions are decoded for the PCK, as in
-    lib.keypoint_detection.accuracy ("argmax", "soft" or a callable)."""
+    lib.keypoint_detection.accuracy ("argmax", "soft", "quarter", "dark" or a callable)."""
     criterion = criterion or JointsMSELoss()
     was_training = model.training
     model.eval()
@@ -691,8 +691,8 @@ class _FlipTestModel(torch.nn.Module):
 def validate_flip(batches, model, flip_pairs, criterion=None, decode="argmax", shift_heatmap=False):
     """validate() with the flip test (the reference's -f/--flip, train_animal.py:556): loss and PCK of flip_forward()'s merged heat-maps.
     flip_pairs: a sequence of left / right joint pairs or a key of lib.keypoint_detection.FLIP_PAIRS; shift_heatmap: Simple Baselines'
-    one-pixel shift of the flipped output.  With decode="argmax" the predictions are the ones the merge launch decoded as it wrote; "soft"
-    or a callable decode the merged map as in validate().  validate() itself is unchanged: this hands it a model that runs the flip test."""
+    one-pixel shift of the flipped output.  With decode="argmax" the predictions are the ones the merge launch decoded as it wrote; "soft",
+    "quarter", "dark" or a callable decode the merged map as in validate().  validate() itself is unchanged: this hands it a model that runs the flip test."""
     kd.flip_perm(flip_pairs, model.num_keypoints)       # (a bad table fails here, before any forward)
     fused = isinstance(decode, str) and decode == "argmax"
     flipped = _FlipTestModel(model, flip_pairs, shift_heatmap, fused)

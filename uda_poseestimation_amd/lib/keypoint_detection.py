@@ -1,5 +1,6 @@
 """Arg-max decode and PCK (API mirror of the reference's lib/keypoint_detection.py:9-94) on MI355X kernels, and the soft-argmax
-decode the reference lacks (`soft_argmax`, csrc/softargmax.hip: sub-pixel coordinates, differentiable), and the flip test's heat-map side
+decode the reference lacks (`soft_argmax`, csrc/softargmax.hip: sub-pixel coordinates, differentiable), the two published sub-pixel
+decodes (`quarter_decode`, `dark_decode`, csrc/refine.hip: one launch, not differentiable), and the flip test's heat-map side
 (`flip_perm`, `flip_back`, `flip_merge`, csrc/flip.hip: flip back, swap left / right joints, average, decode - one launch).
 
 The reference takes numpy arrays (it is called on `.cpu().numpy()` copies, train_human.py:289,443).  The same calls work
@@ -100,6 +101,62 @@ def soft_argmax(batch_heatmaps, beta=10.0, window=None):
     return _SoftArgmaxFn.apply(batch_heatmaps, beta, window)
 
 
+DARK_MAX_PIXELS = 19200      # UDAPOSE_REFINE_MAX_PIXELS (include/udapose.h): the map and its row-blurred copy share one CU's LDS
+
+
+def _refine(hm, mode, kernel=0, sigma=0.0):
+    """udapose_refine_decode on an fp32 contiguous CUDA batch [B,K,H,W]: (coords [B,K,2], maxvals [B,K,1])."""
+    B, K, H, W = hm.shape
+    coords = torch.empty(B, K, 2, dtype=torch.float32, device=hm.device)
+    maxv = torch.empty(B, K, 1, dtype=torch.float32, device=hm.device)
+    check(lib().udapose_refine_decode(_hip.stream(), ptr(hm), B * K, H, W, mode, kernel, sigma, ptr(coords), ptr(maxv), None), "refine_decode")
+    return coords, maxv
+
+
+def _dark_args(kernel, sigma, H, W):
+    """(kernel, sigma) as the kernel takes them, refused here - before any launch - where it would refuse them."""
+    if int(kernel) != kernel or kernel < 3 or kernel > 31 or kernel % 2 == 0:
+        raise ValueError(f"DARK needs an odd blur kernel in [3, 31], got {kernel!r}")
+    sigma = 0.0 if sigma is None else float(sigma)
+    if not sigma < float("inf"):
+        raise ValueError(f"DARK needs a finite sigma (None or <= 0: 0.3 * ((kernel - 1) / 2 - 1) + 0.8), got {sigma}")
+    if H * W > DARK_MAX_PIXELS:
+        raise ValueError(f"DARK decodes maps of up to {DARK_MAX_PIXELS} pixels (the map is blurred in LDS), got {H} x {W}")
+    return int(kernel), sigma
+
+
+def _refine_public(batch_heatmaps, mode, kernel=0, sigma=None):
+    """numpy in -> numpy out, tensor in -> tensor out; the arguments are checked before anything is copied or launched."""
+    is_np = isinstance(batch_heatmaps, np.ndarray)
+    if not is_np and not torch.is_tensor(batch_heatmaps):
+        raise AssertionError('batch_heatmaps should be numpy.ndarray or a 4-d tensor')
+    assert batch_heatmaps.ndim == 4, 'batch_heatmaps should be numpy.ndarray or a 4-d tensor'
+    kernel, sigma = _dark_args(kernel, sigma, *batch_heatmaps.shape[2:]) if mode == 1 else (0, 0.0)
+    coords, maxv = _refine(_dev_f32(batch_heatmaps), mode, kernel, sigma)
+    if is_np:
+        return coords.cpu().numpy(), maxv.cpu().numpy().astype(batch_heatmaps.dtype, copy=False)
+    return coords, maxv
+
+
+def quarter_decode(batch_heatmaps):
+    """[B,K,H,W] -> (coords [B,K,2] float32 (x,y), maxvals [B,K,1]); numpy in -> numpy out, tensor in -> tensor out.  The arg-max of
+    get_max_preds moved a quarter pixel towards the higher neighbour in x and in y (the decode of Simple Baselines), where the arg-max has
+    both neighbours well inside the map (1 < x < W-1, 1 < y < H-1); equal neighbours move nothing.  (0, 0) where maxvals <= 0, as
+    get_max_preds gives.  Not differentiable: the result is detached."""
+    return _refine_public(batch_heatmaps, 0)
+
+
+def dark_decode(batch_heatmaps, kernel=11, sigma=None):
+    """[B,K,H,W] -> (coords [B,K,2] float32 (x,y), maxvals [B,K,1]); numpy in -> numpy out, tensor in -> tensor out.  DARK, the
+    distribution-aware decode: the map is blurred with a `kernel` x `kernel` Gaussian (odd, 3..31; sigma None: OpenCV's
+    0.3 * ((kernel - 1) / 2 - 1) + 0.8, 2.0 at 11), rescaled to its old maximum, and the arg-max of the ORIGINAL map moves by one Newton
+    step on the blurred map's logarithm (1 < x < W-2, 1 < y < H-2; left alone where the blurred maximum is <= 0, the Hessian is singular
+    or the step is not finite).  With labels drawn at the un-rounded position (TargetViewPipeline(subpixel_labels=True)) it recovers the
+    position to < 0.01 px.  One launch, the blurred map never leaves the CU: maps of up to DARK_MAX_PIXELS pixels (ValueError beyond, and
+    for a bad kernel, before any launch).  (0, 0) where maxvals <= 0.  Not differentiable: the result is detached."""
+    return _refine_public(batch_heatmaps, 1, kernel, sigma)
+
+
 def _dev_f32c(a, like):
     """What a decode callable returned (tensor or numpy) as an fp32 tensor on `like`'s device."""
     if isinstance(a, np.ndarray):
@@ -108,17 +165,22 @@ def _dev_f32c(a, like):
 
 
 def _decode_pred(o, decode):
-    """The prediction's coordinates under `decode`: "argmax", "soft" (soft_argmax(beta=10, window=5)) or a callable hm -> (coords, maxvals).
-    The soft decodes get the reference's `maxval > 0` zeroing, so every decode agrees on which joints are absent."""
+    """The prediction's coordinates under `decode`: "argmax", "soft" (soft_argmax(beta=10, window=5)), "quarter" (quarter_decode), "dark"
+    (dark_decode(kernel=11)) or a callable hm -> (coords, maxvals).  The soft decodes get the reference's `maxval > 0` zeroing, so every
+    decode agrees on which joints are absent ("quarter" and "dark" zero them in their own launch)."""
     if decode == "argmax":
         return _decode(o)[0]
+    if decode == "quarter":
+        return _refine(o, 0)[0]
+    if decode == "dark":
+        return _refine(o, 1, *_dark_args(11, None, *o.shape[2:]))[0]
     if decode == "soft":
         coords, maxv = _SoftArgmaxFn.apply(o, 10.0, 5)
     elif callable(decode):
         coords, maxv = decode(o)
         coords, maxv = _dev_f32c(coords, o), _dev_f32c(maxv, o)
     else:
-        raise ValueError(f"decode must be 'argmax', 'soft' or a callable, got {decode!r}")
+        raise ValueError(f"decode must be 'argmax', 'soft', 'quarter', 'dark' or a callable, got {decode!r}")
     B, K = o.shape[:2]
     return (coords.detach().reshape(B, K, 2) * (maxv.detach().reshape(B, K, 1) > 0).to(torch.float32)).contiguous()
 
@@ -139,9 +201,10 @@ def accuracy_device(output, target, thr=0.5, decode="argmax"):
 
 def accuracy(output, target, hm_type='gaussian', thr=0.5, decode="argmax"):
     """PCK@(thr/10 of the heat-map size) from GT heat-maps; returns (acc[K], avg_acc, cnt, pred[B,K,2]) like the reference.
-    decode: "argmax" (the reference's decode), "soft" (soft_argmax(beta=10, window=5): sub-pixel predictions) or a callable
-    hm -> (coords, maxvals).  Only the prediction is decoded softly - the target heat-maps keep the arg-max - and the soft
-    coordinates are zeroed where maxvals <= 0, as the arg-max's are."""
+    decode: "argmax" (the reference's decode), "soft" (soft_argmax(beta=10, window=5): sub-pixel predictions), "quarter"
+    (quarter_decode: Simple Baselines' quarter-pixel offset), "dark" (dark_decode(kernel=11): the distribution-aware decode) or a
+    callable hm -> (coords, maxvals).  Only the prediction is decoded that way - the target heat-maps keep the arg-max - and the
+    sub-pixel coordinates are zeroed where maxvals <= 0, as the arg-max's are."""
     if hm_type != 'gaussian':
         raise NotImplementedError("only hm_type='gaussian' is used by the reference scripts")
     is_np = isinstance(output, np.ndarray)
