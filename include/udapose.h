@@ -99,11 +99,18 @@ typedef struct {
     int igemm_ns3_k;       /* 64x64 implicit-GEMM tiles take the 3-stage LDS ring from this reduction length on (K = taps x Ci), the 2-stage ring
                             * below it; 0 = the default, 2048 */
     void* timeline;        /* NULL (default), or a device buffer of uint64 [work-groups][8] for timeline stamps (tuning).  The grouped weight-gradient launches
-                            * of a plan stamp {start, end (100 MHz), XCD, table slot, problem, stages | form bits, pass, tile rows} per work-group, the 128x128
+                            * of a plan stamp {start, end (100 MHz), XCD, table slot, problem, stages | form bits (from bit 32: filter-row form, stem row-tap form, strided
+                            * bit-field loader, transposed, stride 2), pass, tile rows} per work-group, the 128x128
                             * class first, the 64x64 class behind it: the buffer must hold 1 << 17 work-groups (8 MiB); a plan with more refuses */
     int wgrad_order;       /* grouped weight gradients, the deal of work-groups to the XCDs' lists (net.hip wg_deal): 1 (default) = layers cut into runs of 32 work-groups, the runs
                             * with the most stages per work-group first, so every list ends with its share of the short work-groups; 0 = whole
                             * (layer, split) units in deal order by unit load (rounds 1-6).  Same work into the same places either way: bit-identical gradients */
+    int wgrad_fastgeo_strided; /* 1 (default): the weight-gradient layers that wgrad_fastgeo's loaders do not take although every map is a power of two - stride-2
+                            * convolutions, stride-2 transposed convolutions (four sub-pixel classes), the stem's row-tap form - load through a bit-field
+                            * geometry of their own (shifts for the two strides, 32-bit offsets, no divisions) instead of the general loader;
+                            * 0: the general loader (exact divisions, 64-bit addresses).  No effect with wgrad_fastgeo = 0 or on other maps (384x384
+                            * inputs: 96 / 48 / 24 wide).  Address generation only: bit-identical gradients.  Honoured by the grouped launches' plan and
+                            * by the per-layer launch; like every field it takes effect when a plan's tables are built (udapose_net_bind_grads) */
 } udapose_policy;
 void udapose_policy_default(udapose_policy* p);
 

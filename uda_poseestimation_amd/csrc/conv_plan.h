@@ -15,7 +15,7 @@ struct Policy : udapose_policy {
         bn_bwd_fused = 1; bn_fwd_chunked = 1; bn_bwd_chunked = 1; bn_bwd_pre_legacy = 0;
         igemm_wg_min = 512; wgrad_row3 = 1; bn3_mask = 1; stem_fused = 1; debug_sync = 0;
         igemm_big_min = 0; patch_conv = 2; eval_fold = 1; bn_xcd_rows = 1; wgrad_det = 1; igemm_ns3_k = 0;
-        timeline = nullptr; wgrad_order = 1;
+        timeline = nullptr; wgrad_order = 1; wgrad_fastgeo_strided = 1;
     }
 };
 inline const Policy& default_policy() { static const Policy p; return p; }

@@ -107,7 +107,7 @@ struct Net {
         // the policy the tables were built under: the form of the split reductions (1: partial tiles + split sums, 0: atomics into cleared
         // tensors) and whether they hold the stem.  A later udapose_net_set_policy does not change what a bound table does: find_wg_group
         // no longer finds it, and the backward returns UDAPOSE_ERR_NOT_PREPARED until udapose_net_bind_grads builds tables for the new policy.
-        bool k_det = false, k_stem = false; int k_order = 0;      // (k_order: the work order of the lists, policy wgrad_order)
+        bool k_det = false, k_stem = false; int k_order = 0, k_geo_s = 0;      // (k_order: the work order of the lists, policy wgrad_order)
         size_t part_bytes = 0;                           // workspace bytes of partial tiles the split sums read (k_det)
         std::vector<std::pair<int, ptrdiff_t>> rel;      // (parameter index, byte offset of its gradient from grads[0]) the table assumes
         std::vector<size_t> rel_bytes;                   // bytes of rel[i]'s gradient tensor (what the launch writes there)
@@ -914,7 +914,7 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
     }
     G.h_sum = sums;
     G.k_beta = beta; G.k_stages = n.policy.wgrad_stages; G.k_part = part;
-    G.k_det = det; G.k_stem = n.policy.wgrad_group_stem != 0; G.part_bytes = part_cur; G.k_order = n.policy.wgrad_order;
+    G.k_det = det; G.k_stem = n.policy.wgrad_group_stem != 0; G.part_bytes = part_cur; G.k_order = n.policy.wgrad_order; G.k_geo_s = n.policy.wgrad_fastgeo_strided;
     return UDAPOSE_OK;
 }
 
@@ -934,7 +934,7 @@ Net::WgGroup* find_wg_group(Net& n, void* const* grads, float beta, int part) {
     const bool det = n.policy.wgrad_det && n.policy.wgrad_group, stem = n.policy.wgrad_group_stem != 0;
     for (auto& g : n.wg_groups) {
         if (g.k_beta != beta || g.k_stages != n.policy.wgrad_stages || g.k_part != part || g.k_det != det || g.k_stem != stem ||
-            g.k_order != n.policy.wgrad_order) continue;
+            g.k_order != n.policy.wgrad_order || g.k_geo_s != n.policy.wgrad_fastgeo_strided) continue;
         if (g.k_det && g.part_bytes > n.ws_wgpart_bytes) continue;
         bool same = true;
         for (auto& r : g.rel)

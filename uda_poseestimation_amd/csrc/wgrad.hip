@@ -236,7 +236,9 @@ struct WdCfg {
 // Split reductions (ksplit > 1) come in two forms: fp32 atomics into a zeroed dW (WG_FLAG_ATOMIC; the per-layer launches), or - the grouped
 // launches' form, round 6 - PARTIAL TILES: gp.part_stride != 0, dw points into the pass's workspace and split bz stores its tile with plain
 // stores at element offset bz * part_stride; pw_split_sum adds the splits in split order afterwards (bit-reproducible).
-template <int RT, int CT, int WR, int WC, int NS, int PX = 64, bool FAST = false>
+// GEO: the operand loader, one instantiation of the body each - 0 the general one (exact divisions, 64-bit addresses), 1 the bit-field one of
+// stride-1 same-size layers (WG_FLAG_FASTGEO), 2 the bit-field one of strided, transposed and stem row-tap layers (WG_FLAG_FASTGEO_S).
+template <int RT, int CT, int WR, int WC, int NS, int PX = 64, int GEO = 0>
 __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_t bx, const uint32_t by, const uint32_t bz, char* smem,
                                                const uintptr_t x_base = 0, const uintptr_t dy_base = 0, const uintptr_t dw_base = 0) {
     // scalar copies of the fields used below (gp may live in global memory: read it once, up front, into SGPRs)
@@ -287,18 +289,51 @@ __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_
     // a stage's four source addresses cost ~35 vector instructions instead of ~200 (64-bit multiplies, two exact divisions per
     // row): the loop has 16 MFMAs (256 cycles) per wave and stage and was issue-bound on its address arithmetic (18 % MFMA use).
     const bool pow2hw = ((p.Hi & (p.Hi - 1)) | (p.Wi & (p.Wi - 1))) == 0;
-    // (FAST: a separate instantiation of the body, chosen per problem from WG_FLAG_FASTGEO - set by wg_fastgeo_ok - so that the two
+    // (GEO = 1: a separate instantiation of the body, chosen per problem from WG_FLAG_FASTGEO - set by wg_fastgeo_ok - so that the
     // loaders do not add up their registers: the kernel sits at its 128-register budget)
     (void)pow2hw;
     const int toff = tp.dy * p.Wi + tp.dx;
     const bool center = tp.dy == 0 && tp.dx == 0;
     const unsigned w_mask = (unsigned)p.Wi - 1u, hw_mask = (unsigned)(p.Hi * p.Wi) - 1u;
     const int lgw = 31 - __builtin_clz((unsigned)(p.Wi > 0 ? p.Wi : 1));
+    // Strided geometry (GEO = 2; the stride-2 3x3 and downsample 1x1 convolutions, the stride-2 deconvolutions' four sub-pixel classes, the
+    // stem's row-tap form - every map a power of two, s and os 1 or 2, the row grid Hg x Wg with Ho = Hg * os, Wo = Wg * os: checked by
+    // wg_fastgeo_strided_ok): (n, i, j) are bit fields of m over the ROW GRID, the two strides are shifts, pixel indices are assembled by
+    // shifts and adds and element offsets fit 32 bits with 24-bit factors.  The same sources as the general loader, to the byte.
+    const auto lg2 = [](int v) { return 31 - __builtin_clz((unsigned)(v > 0 ? v : 1)); };
+    const int lg_wg = lg2(p.Wg), lg_hwg = lg_wg + lg2(p.Hg), lg_hwi = lgw + lg2(p.Hi), lg_wo = lg2(p.Wo), lg_hwo = lg_wo + lg2(p.Ho);
+    const int lgs = p.s >> 1, lgos = p.os >> 1;                       // (strides 1 or 2)
     auto issue_stage = [&](int st, int buf) {
         const int mb = (ms0 + st) * PX;
         char* P = smem + buf * C::STAGE1;
         char* Q = P + C::P_BYTES;
-        if constexpr (FAST) {
+        if constexpr (GEO == 2) {
+            // (P and Q have one layout and one row mapping - RT == CT - so WG_FLAG_SWAP only exchanges the two tile origins, which are scalars, and
+            // the two sources at the loads)
+            const int d0 = swap ? c0 : r0, x0 = swap ? r0 : c0;
+#pragma unroll
+            for (int i = 0; i < P_PW; ++i) {
+                const int row = (i * 4 + wid) * P_RPI + lrow;
+                const int lc = pch ^ wswz<RT>(row);
+                const unsigned m = (unsigned)(mb + row);
+                const bool okm = m < (unsigned)p.M;
+                const unsigned n = m >> lg_hwg, ii = (m >> lg_wg) & (unsigned)(p.Hg - 1), jj = m & (unsigned)(p.Wg - 1);
+                const unsigned hi = (ii << lgs) + (unsigned)tp.dy;
+                const unsigned wl = (jj << lgs) + (unsigned)tp.dx + (rowtap ? (unsigned)lc : 0u);      // row-tap form: this lane's chunk is column tap lc
+                const bool okx = okm && hi < (unsigned)p.Hi && wl < (unsigned)p.Wi && (!rowtap || lc < p.kw);
+                const unsigned xpix = (n << lg_hwi) + (hi << lgw) + wl;
+                const unsigned opix = (n << lg_hwo) + (((ii << lgos) + (unsigned)cls.oa) << lg_wo) + (jj << lgos) + (unsigned)cls.ob;
+                const int dch = d0 + lc * 8, xch = rowtap ? 0 : x0 + lc * 8;  // (row-tap: the column tap is in the pixel, its 8 channels are the chunk)
+                const unsigned od = __umul24(opix, (unsigned)p.Co) + (unsigned)dch;
+                const unsigned ox = __umul24(xpix, (unsigned)p.Ci) + (unsigned)xch;
+                const char* sd = (okm && dch < p.Co) ? (const char*)p.dy + (size_t)od * 2 : zsrc;
+                const char* sx = (okx && xch < p.Ci) ? (const char*)p.x + (size_t)ox * 2 : zsrc;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(swap ? sx : sd),
+                                                 (__attribute__((address_space(3))) void*)(P + (i * 4 + wid) * 1024), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(swap ? sd : sx),
+                                                 (__attribute__((address_space(3))) void*)(Q + (i * 4 + wid) * 1024), 16, 0, 0);
+            }
+        } else if constexpr (GEO == 1) {
 #pragma unroll
             for (int i = 0; i < P_PW; ++i) {
                 const int row = (i * 4 + wid) * P_RPI + lrow;
@@ -805,7 +840,8 @@ __global__ __launch_bounds__(256) void wgrad_dma_kernel(const WgParams p) {
         if (p.flags & WG_FLAG_ROW3) { wgrad_row3_body<NS>(p, bx, by, bz, smem); return; }
     }
     if (p.flags & WG_FLAG_FAST2) wgrad_fast2_body<RT, CT, WR, WC, NS, 64>(p, bx, by, bz, smem);
-    else if (p.flags & WG_FLAG_FASTGEO) wgrad_dma_body<RT, CT, WR, WC, NS, 64, true>(p, bx, by, bz, smem);
+    else if (p.flags & WG_FLAG_FASTGEO) wgrad_dma_body<RT, CT, WR, WC, NS, 64, 1>(p, bx, by, bz, smem);
+    else if (p.flags & WG_FLAG_FASTGEO_S) wgrad_dma_body<RT, CT, WR, WC, NS, 64, 2>(p, bx, by, bz, smem);
     else wgrad_dma_body<RT, CT, WR, WC, NS>(p, bx, by, bz, smem);
 }
 
@@ -836,7 +872,8 @@ __device__ __forceinline__ void wgrad_group_dispatch(const WgParams* __restrict_
         if (p.flags & WG_FLAG_ROW3) { wgrad_row3_body<NS>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base); return; }
     }
     if (p.flags & WG_FLAG_FAST2) wgrad_fast2_body<RT, CT, WR, WC, NS, PX>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base);
-    else if (p.flags & WG_FLAG_FASTGEO) wgrad_dma_body<RT, CT, WR, WC, NS, PX, true>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base);
+    else if (p.flags & WG_FLAG_FASTGEO) wgrad_dma_body<RT, CT, WR, WC, NS, PX, 1>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base);
+    else if (p.flags & WG_FLAG_FASTGEO_S) wgrad_dma_body<RT, CT, WR, WC, NS, PX, 2>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base);
     else wgrad_dma_body<RT, CT, WR, WC, NS, PX>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base);
 }
 
@@ -865,6 +902,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void w
             stages = ms_total - bz * p.msteps_per_split < p.msteps_per_split ? ms_total - bz * p.msteps_per_split : p.msteps_per_split;
             if (p.flags & WG_FLAG_ROW3) stages |= 1ll << 32;        // (bit 32: filter-row form, bit 33: stem row-tap form)
             if (p.flags & IG_FLAG_SMALLC) stages |= 1ll << 33;
+            if (p.flags & WG_FLAG_FASTGEO_S) stages |= 1ll << 34;   // (bit 34: strided bit-field loader; bit 35: transposed; bit 36: stride 2)
+            if (p.flags & WG_FLAG_SWAP) stages |= 1ll << 35;
+            if (p.s == 2) stages |= 1ll << 36;
         }
         wgrad_group_dispatch<RT, CT, WR, WC, NS, PX>(tab, blk, per_xcd, x_base, dy_base, dw_base, tab2, blk2, x_base2, dy_base2, dw_base2, smem);
         __syncthreads();
@@ -936,6 +976,26 @@ static bool wg_fastgeo_ok(const WgParams& p, const Policy& pol) {
            (long long)p.M * (p.Ci > p.Co ? p.Ci : p.Co) < (1ll << 31);
 }
 
+// host side of the strided bit-field geometry (wgrad_dma_body<.., GEO = 2>): what wg_fastgeo_ok leaves to the general loader although every map
+// is a power of two - stride-2 convolutions, stride-2 transposed convolutions (row grid = the input map, four sub-pixel classes) and the
+// stem's row-tap form.  The row grid tiles the dy map exactly (Ho = Hg * os), the classes' offsets lie inside one output step, pixel
+// indices of both tensors are 24-bit factors and element offsets fit 31 bits.
+static bool wg_fastgeo_strided_ok(const WgParams& p, const Policy& pol) {
+    if (!pol.wgrad_fastgeo || !pol.wgrad_fastgeo_strided || wg_fastgeo_ok(p, pol)) return false;
+    const int dims[6] = {p.Hg, p.Wg, p.Hi, p.Wi, p.Ho, p.Wo};
+    for (int d : dims) if (d <= 0 || (d & (d - 1))) return false;
+    if ((p.s != 1 && p.s != 2) || (p.os != 1 && p.os != 2) || p.Ho != p.Hg * p.os || p.Wo != p.Wg * p.os) return false;
+    if (p.nclass < 1 || p.nclass > 4) return false;
+    for (int c = 0; c < p.nclass; ++c)
+        if (p.cls[c].oa < 0 || p.cls[c].oa >= p.os || p.cls[c].ob < 0 || p.cls[c].ob >= p.os) return false;
+    if (p.flags & IG_FLAG_SMALLC) {         // only the grouped launches' row-tap form: 8 channels, the column taps are the row's chunks
+        if ((p.flags & WG_FLAG_SWAP) || p.Ci != 8 || p.kw <= 0 || p.kw > 8) return false;
+    }
+    const long long xpix = (long long)p.N * p.Hi * p.Wi, dpix = (long long)p.N * p.Ho * p.Wo;
+    return p.N > 0 && p.M == p.N * p.Hg * p.Wg && p.M < (1 << 24) && xpix < (1 << 24) && dpix < (1 << 24) && p.Ci < (1 << 24) && p.Co < (1 << 24) &&
+           xpix * p.Ci < (1ll << 31) && dpix * p.Co < (1ll << 31);
+}
+
 // the filter-row form (wgrad_row3_body): 3x3 stride-1 pad-1 plain conv in the loader's fast geometry, W <= 64 (a 64-pixel stage
 // holds whole image rows, so the column-wrap masks are loop invariants), 64-channel tiles on both sides
 static bool wg_row3_ok(const WgParams& p, const Policy& pol) {
@@ -989,6 +1049,7 @@ int wgrad_launch(WgParams& p, int tile, int accumulate, hipStream_t stream, cons
     }
     if (wg_fastgeo_ok(p, pol)) p.flags |= WG_FLAG_FASTGEO; else p.flags &= ~WG_FLAG_FASTGEO;
     if ((p.flags & WG_FLAG_FASTGEO) && !(p.flags & WG_FLAG_ROW3) && pol.wgrad_fastgeo >= 2 && p.M % 64 == 0) p.flags |= WG_FLAG_FAST2; else p.flags &= ~WG_FLAG_FAST2;
+    if (dma && wg_fastgeo_strided_ok(p, pol)) p.flags |= WG_FLAG_FASTGEO_S; else p.flags &= ~WG_FLAG_FASTGEO_S;
     if (dma) return tile == 0 ? launch_wd<128, 128, 2, 2, 2>(p, stream) : launch_wd<64, 64, 2, 2, 4>(p, stream);
     switch (tile) {
         case 0: return launch_wg<128, 128, 2, 2>(p, stream);
@@ -1027,6 +1088,7 @@ int wgrad_group_plan(WgParams& p, int accumulate, int stages_per_block, const Po
     if (ks > 1 || accumulate) p.flags |= WG_FLAG_ATOMIC; else p.flags &= ~WG_FLAG_ATOMIC;
     if (wg_fastgeo_ok(p, pol)) p.flags |= WG_FLAG_FASTGEO; else p.flags &= ~WG_FLAG_FASTGEO;
     if ((p.flags & WG_FLAG_FASTGEO) && !(p.flags & WG_FLAG_ROW3) && pol.wgrad_fastgeo >= 2 && p.M % 64 == 0) p.flags |= WG_FLAG_FAST2; else p.flags &= ~WG_FLAG_FAST2;
+    if (wg_fastgeo_strided_ok(p, pol)) p.flags |= WG_FLAG_FASTGEO_S; else p.flags &= ~WG_FLAG_FASTGEO_S;
     return tile;
 }
 
@@ -1073,6 +1135,6 @@ int wgrad_launch_parts(WgParams& p, float* parts, hipStream_t stream) {
     p.msteps_per_split = ((p.M + 63) / 64 + ks - 1) / ks;
     p.dw = parts;
     p.part_stride = (unsigned)((size_t)p.Co * p.wtaps * p.Ci);
-    p.flags &= ~(WG_FLAG_ATOMIC | WG_FLAG_FASTGEO | WG_FLAG_FAST2 | WG_FLAG_ROW3);
+    p.flags &= ~(WG_FLAG_ATOMIC | WG_FLAG_FASTGEO | WG_FLAG_FAST2 | WG_FLAG_FASTGEO_S | WG_FLAG_ROW3);
     return tile == 0 ? launch_wd<128, 128, 2, 2, 2>(p, stream) : launch_wd<64, 64, 2, 2, 4>(p, stream);
 }
