@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "net.h"
 #include "pointwise.h"
@@ -62,6 +63,36 @@ struct Block {
     size_t npix_in = 0;
 };
 
+// A device table its holder owns: upload replaces what it holds (allocation + synchronous copy: never inside a stream capture), the
+// destructor frees it.  After a failed upload it holds nothing.  The only device allocation, copy and free of this file.
+template <class T> struct DevTable {
+    T* d = nullptr; size_t n = 0;
+    DevTable() = default;
+    DevTable(DevTable&& o) noexcept : d(o.d), n(o.n) { o.d = nullptr; o.n = 0; }
+    DevTable& operator=(DevTable&& o) noexcept { if (this != &o) { reset(); d = o.d; n = o.n; o.d = nullptr; o.n = 0; } return *this; }
+    ~DevTable() { reset(); }
+    void reset() { if (d) (void)hipFree(d); d = nullptr; n = 0; }
+    int upload(const std::vector<T>& v) {
+        reset();
+        if (hipMalloc((void**)&d, v.size() * sizeof(T)) != hipSuccess) { d = nullptr; return UDAPOSE_ERR_LAUNCH; }
+        if (hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { reset(); return UDAPOSE_ERR_LAUNCH; }
+        n = v.size();
+        return UDAPOSE_OK;
+    }
+};
+// the job table of a multi-job launch with its work-group -> (job, sub-block) maps: all three live, or none
+template <class J> struct JobTab {
+    DevTable<J> jobs; DevTable<int> blk_job, blk_sub;
+    int nblocks() const { return (int)blk_job.n; }
+    void reset() { jobs.reset(); blk_job.reset(); blk_sub.reset(); }
+    int upload(const std::vector<J>& j, const std::vector<int>& bj, const std::vector<int>& bs) {
+        if (jobs.upload(j) == UDAPOSE_OK && blk_job.upload(bj) == UDAPOSE_OK && blk_sub.upload(bs) == UDAPOSE_OK) return UDAPOSE_OK;
+        reset();
+        return UDAPOSE_ERR_LAUNCH;
+    }
+};
+struct PackJobH { const float* src; elem_t* dst; int A, T, B, kind; long long n; };
+
 struct Net {
     int layers[4], K, N, H, W;
     int split_dz_idx = -1;  // pool buffer holding the gradient that net_backward part 1 hands to part 2 (a function of the plan)
@@ -98,8 +129,7 @@ struct Net {
     size_t gbuf_bytes = 0;
     int Hout = 0, Wout = 0;
     // batched weight packing: device job tables, rebuilt when the parameter / pack pointers change
-    struct PackTab { void* jobs = nullptr; int* blk_job = nullptr; int* blk_sub = nullptr; int nblocks = 0; const void* key0 = nullptr;
-                     const void* key1 = nullptr; const void* keyw = nullptr; };
+    struct PackTab : JobTab<PackJobH> { const void* key0 = nullptr; const void* key1 = nullptr; const void* keyw = nullptr; };
     PackTab pack_fwd, pack_all;
     // grouped weight-gradient launch of one backward pass: device tables, rebuilt when the buffers change
     struct WgGroup {
@@ -113,14 +143,14 @@ struct Net {
         std::vector<size_t> rel_bytes;                   // bytes of rel[i]'s gradient tensor (what the launch writes there)
         std::vector<int> rel_cls;                        // tile class of the launch that computes rel[i]'s gradient
         // tile classes of the grouped launch: 0 = 128x128, 1 = 64x64 (and the filter-row form), 2 = 256x128 (128x64 per wave)
-        WgParams* d_tab[WG_CLASSES] = {}; WgGroupBlk* d_blk[WG_CLASSES] = {}; int per_xcd[WG_CLASSES] = {};
+        DevTable<WgParams> d_tab[WG_CLASSES]; DevTable<WgGroupBlk> d_blk[WG_CLASSES]; int per_xcd[WG_CLASSES] = {};
         double flops[WG_CLASSES] = {};
         std::vector<std::pair<ptrdiff_t, size_t>> zero;  // dW ranges (offset from grads[0], bytes) cleared first (split reductions, when overwriting)
-        ZeroJob* d_zero = nullptr; int n_zero = 0;       // the same ranges as a device job table, when all are 16-byte granular
+        DevTable<ZeroJob> d_zero;                        // the same ranges as a device job table, when all are 16-byte granular
         // Deterministic split reductions (round 6): a layer whose pixel range is split over several work-groups (layer1 / layer2, the last
         // deconvolution, head, stem) has every split store its PARTIAL tile into the pass's workspace (ws_wgpart); one launch then adds the
         // splits of all such layers in split order into the gradient tensors (pw_split_sum): no atomics, no clears, bit-reproducible
-        SumJob* d_sum = nullptr; int* d_sum_blk = nullptr; int n_sum_blk = 0;
+        DevTable<SumJob> d_sum; DevTable<int> d_sum_blk; int n_sum_blk = 0;
         // (the blocks of the jobs that sum into the workspace - the stem's row-tap scratch - are the LAST n_sum_ws_blk of d_sum_blk: a pair call that
         // leaves the sums of the gradient TENSORS to the optimizer sweep still runs those; h_sum: the jobs, for net_bind_update)
         int n_sum_ws_blk = 0;
@@ -129,7 +159,7 @@ struct Net {
     };
     std::deque<WgGroup> wg_groups;       // (stable addresses, never evicted: a captured hipGraph may reference any table built so far)
     // fused optimizer tail (Adam + EMA + weight packs of student and teacher in one sweep): device job table
-    struct UpdTab { TailJob* jobs = nullptr; int* blk_job = nullptr; int* blk_sub = nullptr; int nblocks = 0;
+    struct UpdTab : JobTab<TailJob> {
                     const void* k_ps = nullptr; const void* k_pt = nullptr; const void* k_g = nullptr; const void* k_m = nullptr;
                     const void* k_ws = nullptr; const void* k_wt = nullptr;
                     int kind = 0, ngroups = 1; };       // (optimizer the table was bound for: 0 Adam, 1 SGD; number of parameter groups)
@@ -140,10 +170,29 @@ struct Net {
     struct Deferred { const WgGroup* G = nullptr; char* wsA = nullptr; char* wsB = nullptr; char* gA = nullptr; char* gB = nullptr; } deferred;
     const WgGroup* upd_sum_group = nullptr;     // the table whose split jobs the bound update's job table carries (null: none)
     // batched deferred running-statistics update: device job table, rebuilt when the buffer pointers change
-    BnRunJob* d_runjobs = nullptr; int n_runjobs = 0; const void* runjobs_key = nullptr;
+    DevTable<BnRunJob> d_runjobs; const void* runjobs_key = nullptr;
     unsigned long long wg_tick = 0;
 };
-struct PackJobH { const float* src; elem_t* dst; int A, T, B, kind; long long n; };
+
+// The plan's layers in .parameters() order: stem; per block c1 / b1, c2 / b2, c3 / b3 and, with a downsample branch, cd / bd; up[i] / up_bn[i].
+// fn returns void, or an int status: the walk stops at the first that is not UDAPOSE_OK and returns it.  The head is not part of the walks:
+// every site treats it apart (output channels padded to 64, no BatchNorm, fp32 output).
+template <class F, class... A> int walk_rc(F& fn, A&... a) {
+    if constexpr (std::is_void_v<decltype(fn(a...))>) { fn(a...); return UDAPOSE_OK; }
+    else return fn(a...);
+}
+template <class N, class F> int for_each_layer(N& n, F fn) {
+    int rc = walk_rc(fn, n.stem, n.stem_bn);
+    for (size_t i = 0; rc == UDAPOSE_OK && i < n.blocks.size(); ++i) {
+        auto& b = n.blocks[i];
+        if ((rc = walk_rc(fn, b.c1, b.b1)) == UDAPOSE_OK && (rc = walk_rc(fn, b.c2, b.b2)) == UDAPOSE_OK && (rc = walk_rc(fn, b.c3, b.b3)) == UDAPOSE_OK && b.has_ds)
+            rc = walk_rc(fn, b.cd, b.bd);
+    }
+    for (int i = 0; rc == UDAPOSE_OK && i < 3; ++i) rc = walk_rc(fn, n.up[i], n.up_bn[i]);
+    return rc;
+}
+template <class N, class F> int for_each_conv(N& n, F fn) { return for_each_layer(n, [&](auto& c, auto&) { return walk_rc(fn, c); }); }
+template <class N, class F> int for_each_bn(N& n, F fn) { return for_each_layer(n, [&](auto&, auto& b) { return walk_rc(fn, b); }); }
 
 size_t act_alloc(Net& n, size_t bytes) { size_t o = n.act_bytes; n.act_bytes = align_up(o + bytes); return o; }
 size_t wp_alloc(Net& n, size_t bytes) { size_t o = n.wpack_bytes; n.wpack_bytes = align_up(o + bytes); return o; }
@@ -198,7 +247,7 @@ Net* build(const int layers[4], int K, int N, int H, int W, int mode) {
     // SAME walk with the y / z tensors mapped onto six scratch slots by liveness - one live pre-BN output at a time (SC_Y), the
     // block's input and output ping-pong between SC_A and SC_B (the input is the residual: live until bn3), bn1 / bn2 outputs
     // in SC_MID / SC_MID2, the downsample branch's output waits in SC_DS for bn3.  The walk runs twice:
-    // a dry pass on a copy sizes each slot by its largest tenant, the second assigns the offsets.
+    // a dry pass sizes each slot by its largest tenant and is rewound, the second assigns the offsets.
     auto layout = [&](Net& n) {
     const bool fo = n.fwd_only != 0;
     n.x8_off = fo ? sc_take(n, SC_DS, (size_t)N * H * W * 8 * n.es) : act_alloc(n, (size_t)N * H * W * 8 * n.es);
@@ -266,10 +315,12 @@ Net* build(const int layers[4], int K, int N, int H, int W, int mode) {
     return Hc * 65536 + Wc;
     };
     if (n.fwd_only || n.strict) {
-        Net dry = n;
-        dry.sc.sizing = true;
-        (void)layout(dry);
-        for (int k = 0; k < SC_COUNT; ++k) { n.sc.need[k] = dry.sc.need[k]; n.sc.off[k] = act_alloc(n, dry.sc.need[k]); }
+        n.sc.sizing = true;
+        (void)layout(n);
+        n.sc.sizing = false;
+        // (rewind what the dry pass advanced; every offset it assigned is assigned again below)
+        n.act_bytes = n.wpack_bytes = 0; n.n_params = n.n_buffers = 0; n.param_numel.clear(); n.blocks.clear();
+        for (int k = 0; k < SC_COUNT; ++k) n.sc.off[k] = act_alloc(n, n.sc.need[k]);
     }
     const int hw_out = layout(n);
     const int Hc = hw_out >> 16, Wc = hw_out & 0xffff;
@@ -282,20 +333,18 @@ Net* build(const int layers[4], int K, int N, int H, int W, int mode) {
         max_act = std::max(max_act, (size_t)n.N * c.g.Ho() * c.g.Wo() * c.g.Co * 2);
         max_act = std::max(max_act, (size_t)n.N * c.g.Hi * c.g.Wi * c.g.Ci * 2);
     };
-    upd(n.stem);
-    for (auto& b : n.blocks) { upd(b.c1); upd(b.c2); upd(b.c3); if (b.has_ds) upd(b.cd); }
-    for (int i = 0; i < 3; ++i) upd(n.up[i]);
+    for_each_conv(n, upd);
     max_slab = std::max(max_slab, (size_t)1024 * 2 * 2048 * 4);   // bn backward partials: <=1024 rows x 2 x C
     size_t o = 0;
     n.ws_slab = o; o = align_up(o + max_slab);
     n.ws_slabf = o; o = align_up(o + max_slab);     // partial sums written by dgrad epilogues (the downsample BN keeps ws_slab)
     n.ws_coef = o; o = align_up(o + (size_t)3 * 2048 * 4 + 2 * 2048 * 4);
+    // every convolution of the plan dispatches with the plan's policy
+    // (the walk skips the unused `cd` of blocks without a downsample branch: its default geometry keeps pol == nullptr and is never dispatched)
+    for_each_conv(n, [&](ConvL& c) { c.g.pol = &n.policy; });
+    n.head.g.pol = &n.policy;
     if (n.fwd_only) {           // (no backward: statistics slabs and coefficient vectors only)
         n.ws_bytes = o;
-        n.stem.g.pol = &n.policy;
-        for (auto& b : n.blocks) { b.c1.g.pol = b.c2.g.pol = b.c3.g.pol = b.cd.g.pol = &n.policy; }
-        for (int i = 0; i < 3; ++i) n.up[i].g.pol = &n.policy;
-        n.head.g.pol = &n.policy;
         return np;
     }
     n.gbuf_bytes = align_up(2 * max_act);   // x2: the deconv-stage gradients are fp32
@@ -305,16 +354,9 @@ Net* build(const int layers[4], int K, int N, int H, int W, int mode) {
     // every conv layer owns its dy buffer: the weight gradients of the whole pass are computed by ONE grouped launch after
     // the dgrad / BN-backward chain, so every dy must still be there
     auto dyb = [&](ConvL& c) { c.dy_off = o; o = align_up(o + (size_t)n.N * c.g.Ho() * c.g.Wo() * c.g.Co * 2); };
-    dyb(n.stem);
-    for (auto& b : n.blocks) { dyb(b.c1); dyb(b.c2); dyb(b.c3); if (b.has_ds) dyb(b.cd); }
-    for (int i = 0; i < 3; ++i) dyb(n.up[i]);
+    for_each_conv(n, dyb);
     n.ws_wgpart = o;          // (last: its size follows the policy's split length, net_ws_bytes)
     n.ws_bytes = o;
-    // every convolution of the plan dispatches with the plan's policy
-    n.stem.g.pol = &n.policy;
-    for (auto& b : n.blocks) { b.c1.g.pol = b.c2.g.pol = b.c3.g.pol = b.cd.g.pol = &n.policy; }
-    for (int i = 0; i < 3; ++i) n.up[i].g.pol = &n.policy;
-    n.head.g.pol = &n.policy;
     return np;
 }
 
@@ -324,39 +366,19 @@ struct Pool {
     void put(const void* p) { for (int i = 0; i < 6; ++i) if ((char*)p == base + off[i]) used[i] = false; }
 };
 
-int pack_conv(hipStream_t s, const Net& n, const ConvL& c, const void* const* params, char* wpack, bool with_bwd) {
+// The weight packs that are not jobs of the plan's pack table (pw_pack_multi) or of the optimizer sweep: the stem's 3 -> 8 channel gather in
+// every mode and, in the exact-fp32 mode, the deconvolutions' transposes (plain convolutions and the head read their fp32 masters there)
+int pack_conv(hipStream_t s, const Net& n, const ConvL& c, const void* const* params, char* wpack) {
     const float* w = (const float*)params[c.w_idx];
     const ConvGeom& g = c.g;
-    elem_t* wf = (elem_t*)(wpack + c.wf_off);
-    elem_t* wb = (elem_t*)(wpack + c.wb_off);
-    const int T = g.KH * g.KW;
-    if (n.f32 == 2) {
-        // f16x2 packs: the fp32 GEMM layouts, every group of 8 values split into [8 h][8 l]
-        if (g.smallc())
-            return pw_pack_strided_split(s, w, wpack + c.wf_off, g.Co, g.KH, g.KWp(), g.KW, 8, 3, (long)g.KH * g.KW * 3, (long)g.KW * 3, 3, 1);
-        if (g.transposed) return pw_transpose_split(s, w, wpack + c.wf_off, g.Ci, T, g.Co);
-        return pw_f32_to_split(s, w, wpack + c.wf_off, (size_t)g.Co * T * g.Ci);
-    }
-    if (n.f32) {
-        if (g.smallc())
-            return pw_pack_strided_f32(s, w, (float*)(wpack + c.wf_off), g.Co, g.KH, g.KWp(), g.KW, 8, 3, (long)g.KH * g.KW * 3, (long)g.KW * 3, 3, 1);
-        if (g.transposed) return pw_transpose_f32(s, w, (float*)(wpack + c.wf_off), g.Ci, T, g.Co);
-        return UDAPOSE_OK;
-    }
     if (g.smallc()) {
-        // master: [Co][KH][KW][3] (channels_last of [Co,3,KH,KW]) -> [Co][KH][KWp][8]
-        return pw_pack_strided(s, w, wf, g.Co, g.KH, g.KWp(), g.KW, 8, 3, (long)g.KH * g.KW * 3, (long)g.KW * 3, 3, 1);
+        // master: [Co][KH][KW][3] (channels_last of [Co,3,KH,KW]) -> [Co][KH][KWp][8]; f16x2: every group of 8 values split into [8 h][8 l]
+        if (n.f32 == 2) return pw_pack_strided_split(s, w, wpack + c.wf_off, g.Co, g.KH, g.KWp(), g.KW, 8, 3, (long)g.KH * g.KW * 3, (long)g.KW * 3, 3, 1);
+        if (n.f32) return pw_pack_strided_f32(s, w, (float*)(wpack + c.wf_off), g.Co, g.KH, g.KWp(), g.KW, 8, 3, (long)g.KH * g.KW * 3, (long)g.KW * 3, 3, 1);
+        return pw_pack_strided(s, w, (elem_t*)(wpack + c.wf_off), g.Co, g.KH, g.KWp(), g.KW, 8, 3, (long)g.KH * g.KW * 3, (long)g.KW * 3, 3, 1);
     }
-    if (!g.transposed) {
-        // master physical [Co][T][Ci]: fprop pack is a cast, dgrad pack [Ci][T][Co] a per-tap transpose
-        CK(pw_cast_f32_bf16(s, w, wf, (size_t)g.Co * T * g.Ci));
-        if (with_bwd) CK(pw_transpose_cast(s, w, wb, g.Co, T, g.Ci));
-    } else {
-        // ConvTranspose2d master physical [Ci][T][Co] (channels_last of [Ci,Co,KH,KW]): dgrad pack is the cast
-        CK(pw_transpose_cast(s, w, wf, g.Ci, T, g.Co));
-        if (with_bwd) CK(pw_cast_f32_bf16(s, w, wb, (size_t)g.Ci * T * g.Co));
-    }
-    return UDAPOSE_OK;
+    if (n.f32 != 1) return UDAPOSE_ERR_UNSUPPORTED;       // (16-bit and f16x2 packs of every other layer are table jobs)
+    return g.transposed ? pw_transpose_f32(s, w, (float*)(wpack + c.wf_off), g.Ci, g.KH * g.KW, g.Co) : UDAPOSE_OK;
 }
 
 int conv_bn_fwd(hipStream_t s, const Net& n, const ConvL& c, const BnL& b, const void* const* params, void* const* buffers, const char* wpack,
@@ -383,6 +405,11 @@ int conv_bn_fwd(hipStream_t s, const Net& n, const ConvL& c, const BnL& b, const
     const void* wptr = (n.f32 == 1 && !c.g.smallc() && !c.g.transposed) ? params[c.w_idx] : (const void*)(wpack + c.wf_off);
     const float* gamma = (const float*)params[b.g_idx];
     const float* beta = (const float*)params[b.b_idx];
+    // (the running statistics a training forward updates, unless the update is deferred; the chunking word of the one-launch finalize + apply)
+    float* rm = upd ? (float*)buffers[b.rm_idx] : nullptr;
+    float* rv = upd ? (float*)buffers[b.rv_idx] : nullptr;
+    long long* nbt = upd ? (long long*)buffers[b.nbt_idx] : nullptr;
+    const int chunked = n.policy.bn_fwd_chunked | (n.policy.bn_xcd_rows ? (1 << 30) : 0);
     if (!training && !no_apply && !pre_bias && n.policy.eval_fold) {
         // Eval mode (validate(), train_human.py:461-500): the BatchNorm is a per-channel affine map known BEFORE the convolution, so the
         // conv's epilogue applies it from the fp32 accumulators - z = relu(conv * scale + shift (+ residual)) is written by the conv
@@ -398,23 +425,19 @@ int conv_bn_fwd(hipStream_t s, const Net& n, const ConvL& c, const BnL& b, const
     if (training && !n.f32 && !no_apply && !pre_bias) {
         // wide, small-spatial layers: finalize + apply in ONE launch (channel-chunked work-groups, pointwise.hip)
         const int took = pw_bn_train_fused(s, (const elem_t*)(act + c.y_off), res, (elem_t*)(act + b.z_off), b.npix, b.C, slab, conv_stat_rows(c.g), gamma,
-                                           beta, upd ? (float*)buffers[b.rm_idx] : nullptr, upd ? (float*)buffers[b.rv_idx] : nullptr,
-                                           upd ? (long long*)buffers[b.nbt_idx] : nullptr, momentum, 1e-5f, save, relu, n.policy.bn_fwd_chunked | (n.policy.bn_xcd_rows ? (1 << 30) : 0), mask);
+                                           beta, rm, rv, nbt, momentum, 1e-5f, save, relu, chunked, mask);
         if (took < 0) return took;
         if (took) return UDAPOSE_OK;
     }
     if (training && n.f32 == 2 && !no_apply && !pre_bias) {
         const int took = pw_bn_train_fused_split(s, (const float*)(act + c.fy_off), res, act + b.fz_off, b.npix, b.C, slab, conv_stat_rows(c.g), gamma, beta,
-                                                 upd ? (float*)buffers[b.rm_idx] : nullptr, upd ? (float*)buffers[b.rv_idx] : nullptr,
-                                                 upd ? (long long*)buffers[b.nbt_idx] : nullptr, momentum, 1e-5f, save, relu, n.policy.bn_fwd_chunked | (n.policy.bn_xcd_rows ? (1 << 30) : 0),
-                                                 y16, z16, sh ? mask : nullptr);
+                                                 rm, rv, nbt, momentum, 1e-5f, save, relu, chunked, y16, z16, sh ? mask : nullptr);
         if (took < 0) return took;
         if (took) return UDAPOSE_OK;
     }
     if (training)
-        CK(pw_bn_finalize(s, slab, conv_stat_rows(c.g), b.C, (double)b.npix, gamma, beta, upd ? (float*)buffers[b.rm_idx] : nullptr,
-                          upd ? (float*)buffers[b.rv_idx] : nullptr, upd ? (long long*)buffers[b.nbt_idx] : nullptr, momentum, 1e-5f, scale, shift,
-                          save, save + b.C, pre_bias));
+        CK(pw_bn_finalize(s, slab, conv_stat_rows(c.g), b.C, (double)b.npix, gamma, beta, rm, rv, nbt, momentum, 1e-5f, scale, shift, save,
+                          save + b.C, pre_bias));
     else
         CK(pw_bn_eval_coeff(s, b.C, gamma, beta, (const float*)buffers[b.rm_idx], (const float*)buffers[b.rv_idx], 1e-5f, scale, shift));
     if (no_apply) return UDAPOSE_OK;      // (the caller's next launch applies scale / shift itself: the stem's fused pool)
@@ -436,14 +459,7 @@ void* net_create(const int layers[4], int K, int N, int H, int W, int mode) {
     return build(layers, K, N, H, W, mode);
 }
 void net_destroy(void* h) {
-    Net* n = (Net*)h;
-    if (!n) return;
-    if (n->d_runjobs) (void)hipFree(n->d_runjobs);
-    if (n->upd.jobs) { (void)hipFree(n->upd.jobs); (void)hipFree(n->upd.blk_job); (void)hipFree(n->upd.blk_sub); }
-    for (auto& g : n->wg_groups)
-        for (int t = 0; t < WG_CLASSES; ++t) { if (g.d_tab[t]) (void)hipFree(g.d_tab[t]); if (g.d_blk[t]) (void)hipFree(g.d_blk[t]); }
-    for (auto& g : n->wg_groups) { if (g.d_zero) (void)hipFree(g.d_zero); if (g.d_sum) (void)hipFree(g.d_sum); if (g.d_sum_blk) (void)hipFree(g.d_sum_blk); }
-    delete n;
+    delete (Net*)h;       // (every device table goes with its holder)
 }
 void net_set_policy(void* h, const Policy& p) { ((Net*)h)->policy = p; }
 const Policy& net_get_policy(void* h) { return ((Net*)h)->policy; }
@@ -483,13 +499,7 @@ void add_pack_jobs(const Net& n, const ConvL& c, const void* const* params, char
 }
 int build_pack_table(Net& n, Net::PackTab& tab, const void* const* params, char* wpack, bool with_bwd) {
     std::vector<PackJobH> jobs;
-    for (auto& b : n.blocks) {
-        add_pack_jobs(n, b.c1, params, wpack, with_bwd, jobs);
-        add_pack_jobs(n, b.c2, params, wpack, with_bwd, jobs);
-        add_pack_jobs(n, b.c3, params, wpack, with_bwd, jobs);
-        if (b.has_ds) add_pack_jobs(n, b.cd, params, wpack, with_bwd, jobs);
-    }
-    for (int i = 0; i < 3; ++i) add_pack_jobs(n, n.up[i], params, wpack, with_bwd, jobs);
+    for_each_conv(n, [&](const ConvL& c) { add_pack_jobs(n, c, params, wpack, with_bwd, jobs); });
     jobs.push_back(PackJobH{(const float*)params[n.head.w_idx], (elem_t*)(wpack + n.head.wf_off), 0, 0, 0, n.f32 == 2 ? 2 : 0, (long long)n.K * 256});
     std::vector<int> bj, bs;
     for (size_t j = 0; j < jobs.size(); ++j) {
@@ -497,32 +507,16 @@ int build_pack_table(Net& n, Net::PackTab& tab, const void* const* params, char*
         const long nb = (q.kind & 1) == 0 ? (long)((q.n + 8191) / 8192) : (long)((q.A + 31) / 32) * ((q.B + 31) / 32) * q.T;
         for (long k = 0; k < nb; ++k) { bj.push_back((int)j); bs.push_back((int)k); }
     }
-    if (tab.jobs) { (void)hipFree(tab.jobs); (void)hipFree(tab.blk_job); (void)hipFree(tab.blk_sub); }
-    if (hipMalloc(&tab.jobs, jobs.size() * sizeof(PackJobH)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMalloc((void**)&tab.blk_job, bj.size() * sizeof(int)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMalloc((void**)&tab.blk_sub, bs.size() * sizeof(int)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMemcpy(tab.jobs, jobs.data(), jobs.size() * sizeof(PackJobH), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMemcpy(tab.blk_job, bj.data(), bj.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMemcpy(tab.blk_sub, bs.data(), bs.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    tab.nblocks = (int)bj.size();
+    CK(tab.upload(jobs, bj, bs));
     tab.key0 = params[0]; tab.key1 = params[n.n_params - 1]; tab.keyw = wpack;
     return UDAPOSE_OK;
 }
 int build_run_jobs(Net& n, void* const* buffers) {
     std::vector<BnRunJob> jobs;
-    auto one = [&](const BnL& b) {
+    for_each_bn(n, [&](const BnL& b) {
         jobs.push_back(BnRunJob{b.save_off, (float*)buffers[b.rm_idx], (float*)buffers[b.rv_idx], (long long*)buffers[b.nbt_idx], b.C, 0});
-    };
-    one(n.stem_bn);
-    for (auto& b : n.blocks) {
-        one(b.b1); one(b.b2); one(b.b3);
-        if (b.has_ds) one(b.bd);
-    }
-    for (int i = 0; i < 3; ++i) one(n.up_bn[i]);
-    if (n.d_runjobs) { (void)hipFree(n.d_runjobs); n.d_runjobs = nullptr; }
-    if (hipMalloc((void**)&n.d_runjobs, jobs.size() * sizeof(BnRunJob)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMemcpy(n.d_runjobs, jobs.data(), jobs.size() * sizeof(BnRunJob), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    n.n_runjobs = (int)jobs.size();
+    });
+    CK(n.d_runjobs.upload(jobs));
     n.runjobs_key = buffers[0];
     return UDAPOSE_OK;
 }
@@ -535,12 +529,7 @@ int build_run_jobs(Net& n, void* const* buffers) {
 int net_bind(void* h, const void* const* params, void* const* buffers, void* wpack_) {
     Net& n = *(Net*)h;
     char* wpack = (char*)wpack_;
-    CK(conv_prepare(n.stem.g));
-    for (auto& b : n.blocks) {
-        CK(conv_prepare(b.c1.g)); CK(conv_prepare(b.c2.g)); CK(conv_prepare(b.c3.g));
-        if (b.has_ds) CK(conv_prepare(b.cd.g));
-    }
-    for (int i = 0; i < 3; ++i) CK(conv_prepare(n.up[i].g));
+    CK(for_each_conv(n, [](const ConvL& c) { return conv_prepare(c.g); }));
     { ConvGeom hg = n.head.g; CK(conv_prepare(hg)); hg.Co = 64; CK(conv_prepare(hg)); }
     if (n.f32 != 1) {
         CK(build_pack_table(n, n.pack_fwd, params, wpack, false));
@@ -558,28 +547,18 @@ int net_pack_weights(void* h, hipStream_t s, const void* const* params, void* wp
         // ONE launch casts / transposes every weight through the job table net_bind built for these pointers
         if (n.f32 == 2 && !n.strict) with_bwd = 0;
         Net::PackTab& tab = with_bwd ? n.pack_all : n.pack_fwd;
-        if (!tab.jobs || tab.key0 != params[0] || tab.key1 != params[n.n_params - 1] || tab.keyw != (const void*)wpack)
+        if (!tab.jobs.d || tab.key0 != params[0] || tab.key1 != params[n.n_params - 1] || tab.keyw != (const void*)wpack)
             return UDAPOSE_ERR_NOT_PREPARED;
-        CK(pack_conv(s, n, n.stem, params, wpack, false));
-        CK(pw_pack_multi(s, tab.jobs, tab.blk_job, tab.blk_sub, tab.nblocks));
+        CK(pack_conv(s, n, n.stem, params, wpack));
+        CK(pw_pack_multi(s, tab.jobs.d, tab.blk_job.d, tab.blk_sub.d, tab.nblocks()));
         if (with_bwd)   // head dgrad pack [256][1][64]: wb[ci][k] = w[k][ci], zero for k >= K
             CK(pw_pack_strided(s, (const float*)params[n.head.w_idx], (elem_t*)(wpack + n.head.wb_off), 256, 1, 1, 1, 64, n.K, 1, 0, 0, 256));
         return UDAPOSE_OK;
     }
-    CK(pack_conv(s, n, n.stem, params, wpack, false));
-    for (auto& b : n.blocks) {
-        CK(pack_conv(s, n, b.c1, params, wpack, with_bwd));
-        CK(pack_conv(s, n, b.c2, params, wpack, with_bwd));
-        CK(pack_conv(s, n, b.c3, params, wpack, with_bwd));
-        if (b.has_ds) CK(pack_conv(s, n, b.cd, params, wpack, with_bwd));
-    }
-    for (int i = 0; i < 3; ++i) CK(pack_conv(s, n, n.up[i], params, wpack, with_bwd));
-    const float* hw = (const float*)params[n.head.w_idx];
-    if (n.f32) return UDAPOSE_OK;      // the head reads its fp32 master directly
-    CK(pw_cast_f32_bf16(s, hw, (elem_t*)(wpack + n.head.wf_off), (size_t)n.K * 256));
-    if (with_bwd)   // [256][1][64]: wb[ci][k] = w[k][ci], zero for k >= K
-        CK(pw_pack_strided(s, hw, (elem_t*)(wpack + n.head.wb_off), 256, 1, 1, 1, 64, n.K, 1, 0, 0, 256));
-    return UDAPOSE_OK;
+    // exact fp32: the stem's gather and the deconvolutions' transposes, layer by layer; plain convolutions and the head read their fp32
+    // masters directly, and there is no backward to pack for
+    // (CK inside the walk: with debug_sync every layer's launch is synchronised and reported under this line)
+    return for_each_conv(n, [&](const ConvL& c) -> int { CK(pack_conv(s, n, c, params, wpack)); return UDAPOSE_OK; });
 }
 
 int net_forward(void* h, hipStream_t s, const float* x_nchw, const void* const* params, void* const* buffers, const void* wpack_, void* act_, void* ws_,
@@ -709,6 +688,18 @@ PartSel part_sel(const Net& n, int part) {
     if (part == 2) return PartSel{false, split - 1, 0, true};
     return PartSel{true, nb - 1, 0, true};
 }
+// the convolutions of a part in the order of the grouped table's entries (after the head and the stem, which every site treats apart):
+// up[2..0], then the blocks from last to first, each as c3, c2, cd, c1.  fn as in the walks above: void, or an int status that stops the walk.
+template <class N, class F> int for_each_conv_wgrad(N& n, const PartSel& sel, F fn) {
+    int rc = UDAPOSE_OK;
+    for (int i = 2; sel.head_up && rc == UDAPOSE_OK && i >= 0; --i) rc = walk_rc(fn, n.up[i]);
+    for (int bi = sel.hi; rc == UDAPOSE_OK && bi >= sel.lo; --bi) {
+        auto& b = n.blocks[bi];
+        if ((rc = walk_rc(fn, b.c3)) == UDAPOSE_OK && (rc = walk_rc(fn, b.c2)) == UDAPOSE_OK && (!b.has_ds || (rc = walk_rc(fn, b.cd)) == UDAPOSE_OK))
+            rc = walk_rc(fn, b.c1);
+    }
+    return rc;
+}
 
 // ---- the deal of a grouped launch: which XCD runs which work-groups, and in which order ----------------------------------------
 // A unit is one (layer, split): `nblk` work-groups (local indices base .. base + nblk - 1) of `st` 64-pixel stages each (+ 4: prologue,
@@ -792,6 +783,18 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
         part_cur = align_up(part_cur + (size_t)ks_eff * span * sizeof(float));
         return UDAPOSE_OK;
     };
+    // one table entry of class t: the layer's parameters, its flops, and one unit per split that owns at least one stage
+    auto emit = [&](int t, const WgParams& p, double fl) {
+        const int prob = (int)tab[t].size();
+        tab[t].push_back(p);
+        G.flops[t] += fl;
+        const int nblk = p.r_tiles * p.c_tiles * p.total_taps;
+        const int ms_total = (p.M + 63) / 64, per = (ms_total + p.ksplit - 1) / p.ksplit;
+        for (int z = 0; z < p.ksplit; ++z) {
+            const int st = std::min(per, ms_total - z * per);
+            if (st > 0) units[t].push_back(WgUnit{prob, z * nblk, nblk, st, (long)nblk * (st + 4)});
+        }
+    };
     auto add_geom = [&](const ConvGeom& g, int w_idx, size_t dy_off, size_t in_off, int rows_valid) -> int {
         if (g.smallc()) return UDAPOSE_OK;
         WgParams p;
@@ -808,19 +811,10 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
             if (det) CK(make_partial(p, (long long)drel, 0, swap ? p.Co : p.Ci));
             else if (beta == 0.f) G.zero.push_back({drel, (size_t)p.rows_valid * p.wtaps * (swap ? p.Co : p.Ci) * sizeof(float)});
         }
-        const int prob = (int)tab[t].size();
         G.rel_cls.push_back(t);
-        tab[t].push_back(p);
-        G.flops[t] += fl;
-        const int nblk = p.r_tiles * p.c_tiles * p.total_taps;
-        const int ms_total = (p.M + 63) / 64, per = (ms_total + p.ksplit - 1) / p.ksplit;
-        for (int z = 0; z < p.ksplit; ++z) {
-            const int st = std::min(per, ms_total - z * per);
-            if (st > 0) units[t].push_back(WgUnit{prob, z * nblk, nblk, st, (long)nblk * (st + 4)});
-        }
+        emit(t, p, fl);
         return UDAPOSE_OK;
     };
-    auto add = [&](const ConvL& c) -> int { return add_geom(c.g, c.w_idx, c.dy_off, c.in_off, -1); };
     if (upper) {   // head: dy is channel-padded to 64, only the K real rows of dW exist
         ConvGeom hg = n.head.g;
         hg.Co = 64;
@@ -837,28 +831,14 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
         const int t = wgrad_group_plan(p, 1, n.policy.wgrad_stages, n.policy);      // (accumulate = 1: atomics into the zeroed scratch)
         if (t != 1) return UDAPOSE_ERR_UNSUPPORTED;
         if (det) CK(make_partial(p, (long long)n.ws_dwtmp, 1, 64));     // ... or partial tiles, summed into the scratch
-        const int prob = (int)tab[t].size();
-        tab[t].push_back(p);
-        G.flops[t] += fl;
-        const int nblk = p.r_tiles * p.c_tiles * p.total_taps;
-        const int ms_total = (p.M + 63) / 64, per = (ms_total + p.ksplit - 1) / p.ksplit;
-        for (int z = 0; z < p.ksplit; ++z) {
-            const int st = std::min(per, ms_total - z * per);
-            if (st > 0) units[t].push_back(WgUnit{prob, z * nblk, nblk, st, (long)nblk * (st + 4)});
-        }
+        emit(t, p, fl);
     }
-    if (upper) for (int i = 2; i >= 0; --i) CK(add(n.up[i]));
-    for (int bi = sel.hi; bi >= sel.lo; --bi) {
-        Block& b = n.blocks[bi];
-        CK(add(b.c3)); CK(add(b.c2));
-        if (b.has_ds) CK(add(b.cd));
-        CK(add(b.c1));
-    }
+    CK(for_each_conv_wgrad(n, sel, [&](const ConvL& c) { return add_geom(c.g, c.w_idx, c.dy_off, c.in_off, -1); }));
     if (sizing) { if (need) *need = part_cur; return UDAPOSE_OK; }
     if (part_cur > n.ws_wgpart_bytes) return UDAPOSE_ERR_NOT_PREPARED;      // (the policy's split length changed after the workspace was sized: udapose_net_ws_bytes)
     for (int t = 0; t < WG_CLASSES; ++t) {
-        if (G.d_tab[t]) { (void)hipFree(G.d_tab[t]); G.d_tab[t] = nullptr; }
-        if (G.d_blk[t]) { (void)hipFree(G.d_blk[t]); G.d_blk[t] = nullptr; }
+        G.d_tab[t].reset();
+        G.d_blk[t].reset();
         G.per_xcd[t] = 0;
         if (tab[t].empty()) continue;
         // deal the units' work-groups to the 8 XCDs' lists (wg_deal above)
@@ -875,26 +855,21 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
         for (int k = 0; k < 8; ++k) per = std::max(per, lst[k].size());
         std::vector<WgGroupBlk> flat(8 * per, WgGroupBlk{-1, 0});
         for (int k = 0; k < 8; ++k) std::copy(lst[k].begin(), lst[k].end(), flat.begin() + k * per);
-        if (hipMalloc((void**)&G.d_tab[t], tab[t].size() * sizeof(WgParams)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-        if (hipMalloc((void**)&G.d_blk[t], flat.size() * sizeof(WgGroupBlk)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-        if (hipMemcpy(G.d_tab[t], tab[t].data(), tab[t].size() * sizeof(WgParams), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-        if (hipMemcpy(G.d_blk[t], flat.data(), flat.size() * sizeof(WgGroupBlk), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
+        CK(G.d_tab[t].upload(tab[t]));
+        CK(G.d_blk[t].upload(flat));
         G.per_xcd[t] = (int)per;
     }
-    if (G.d_zero) { (void)hipFree(G.d_zero); G.d_zero = nullptr; }
-    G.n_zero = 0;
+    G.d_zero.reset();
     bool granular = !G.zero.empty();
     for (auto& z : G.zero) granular = granular && (z.second % 16 == 0) && ((((size_t)(const char*)grads[0]) + (size_t)z.first) % 16 == 0);
     if (granular) {
         std::vector<ZeroJob> zj;
         for (auto& z : G.zero) zj.push_back(ZeroJob{(long long)z.first, (long long)(z.second / 16)});
-        if (hipMalloc((void**)&G.d_zero, zj.size() * sizeof(ZeroJob)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-        if (hipMemcpy(G.d_zero, zj.data(), zj.size() * sizeof(ZeroJob), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-        G.n_zero = (int)zj.size();
+        CK(G.d_zero.upload(zj));
     }
     // the split-sum launch's tables: jobs, and one block per UDAPOSE_SPLIT_SUM_CHUNK elements of a job
-    if (G.d_sum) { (void)hipFree(G.d_sum); G.d_sum = nullptr; }
-    if (G.d_sum_blk) { (void)hipFree(G.d_sum_blk); G.d_sum_blk = nullptr; }
+    G.d_sum.reset();
+    G.d_sum_blk.reset();
     G.n_sum_blk = 0; G.n_sum_ws_blk = 0;
     if (!sums.empty()) {
         std::vector<int> blk;
@@ -906,10 +881,8 @@ int build_wg_group(Net& n, Net::WgGroup& G, void* const* grads, float beta, int 
                     G.n_sum_ws_blk += ws_jobs;
                 }
             }
-        if (hipMalloc((void**)&G.d_sum, sums.size() * sizeof(SumJob)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-        if (hipMalloc((void**)&G.d_sum_blk, blk.size() * sizeof(int)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-        if (hipMemcpy(G.d_sum, sums.data(), sums.size() * sizeof(SumJob), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-        if (hipMemcpy(G.d_sum_blk, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
+        CK(G.d_sum.upload(sums));
+        CK(G.d_sum_blk.upload(blk));
         G.n_sum_blk = (int)(blk.size() / 2);
     }
     G.h_sum = sums;
@@ -963,8 +936,8 @@ int bind_wg_groups(Net& n, void* const* grads) {
 // what precedes the grouped launches of one pass (the clears of the atomic form) and what follows them (the split sums, the stem's unpack)
 int wg_before(hipStream_t s, Net& n, Net::WgGroup* G, char* ws, void* const* grads, bool with_stem) {
     G->last_use = ++n.wg_tick;
-    if (G->d_zero) {
-        CK(pw_zero_multi(s, G->d_zero, G->n_zero, grads[0]));
+    if (G->d_zero.d) {
+        CK(pw_zero_multi(s, G->d_zero.d, (int)G->d_zero.n, grads[0]));
     } else {
         for (auto& z : G->zero)
             if (pw_zero(s, (char*)grads[0] + z.first, z.second) != UDAPOSE_OK) return UDAPOSE_ERR_LAUNCH;
@@ -974,7 +947,7 @@ int wg_before(hipStream_t s, Net& n, Net::WgGroup* G, char* ws, void* const* gra
     return UDAPOSE_OK;
 }
 int wg_after(hipStream_t s, Net& n, Net::WgGroup* G, char* ws, void* const* grads, float beta, bool with_stem, bool sums_done = false) {
-    if (G->n_sum_blk && !sums_done) CK(pw_split_sum(s, G->d_sum, G->d_sum_blk, G->n_sum_blk, ws, (char*)grads[0]));
+    if (G->n_sum_blk && !sums_done) CK(pw_split_sum(s, G->d_sum.d, G->d_sum_blk.d, G->n_sum_blk, ws, (char*)grads[0]));
     const ConvGeom& sg = n.stem.g;
     if (with_stem)
         CK(pw_unpack_strided(s, (const float*)(ws + n.ws_dwtmp), (float*)grads[n.stem.w_idx], sg.Co, sg.KH, sg.KWp(), sg.KW, 8, 3,
@@ -999,26 +972,35 @@ bool wg_overlap(const Net& n, const Net::WgGroup* GA, void* const* gradsA, const
     span(GB, gradsB, lb, hb);
     return la < hb && lb < ha;
 }
+// The grouped launches of one pass (GB == nullptr), or of two passes with equal table shapes as ONE grid per tile class, each inside the
+// profiler's bracket.  With policy.timeline every launch stamps behind the last: 8 stamp blocks per list entry and pass.
+int launch_wg_classes(hipStream_t s, const Net& n, const Net::WgGroup* GA, const char* actA, char* wsA, void* gA, const Net::WgGroup* GB = nullptr,
+                      const char* actB = nullptr, char* wsB = nullptr, void* gB = nullptr) {
+    size_t stamped = 0;     // (work-groups of the classes before this one)
+    for (int t = 0; t < WG_CLASSES; ++t) {
+        if (!GA->per_xcd[t]) continue;
+        unsigned long long* stamps = nullptr;
+        if (n.policy.timeline) {
+            const size_t blocks = (GB ? 16 : 8) * (size_t)GA->per_xcd[t];
+            if (stamped + blocks > WG_STAMP_BLOCKS) return UDAPOSE_ERR_ARG;
+            stamps = (unsigned long long*)n.policy.timeline + stamped * 8;
+            stamped += blocks;
+        }
+        const int tok = conv_prof_before(s, 2, GB ? GA->flops[t] + GB->flops[t] : GA->flops[t]);
+        const int rc = wgrad_group_launch(s, t, GA->d_tab[t].d, GA->d_blk[t].d, GA->per_xcd[t], actA, wsA, gA, GB ? GB->d_tab[t].d : nullptr,
+                                          GB ? GB->d_blk[t].d : nullptr, actB, wsB, gB, stamps);
+        conv_prof_after(s, tok);
+        CK(rc);
+    }
+    return UDAPOSE_OK;
+}
 int run_wg_group(hipStream_t s, Net& n, const char* act, char* ws, void* const* grads, float beta, int part) {
     if (n.deferred.G) return UDAPOSE_ERR_NOT_PREPARED;      // (split sums of an earlier pair call are still waiting for their update or flush)
     Net::WgGroup* G = find_wg_group(n, grads, beta, part);
     if (!G) return UDAPOSE_ERR_NOT_PREPARED;
     const bool with_stem = part_sel(n, part).stem && G->k_stem;
     CK(wg_before(s, n, G, ws, grads, with_stem));
-    size_t stamped = 0;     // (work-groups of the classes before this one: each launch stamps behind the last, policy.timeline)
-    for (int t = 0; t < WG_CLASSES; ++t) {
-        if (!G->per_xcd[t]) continue;
-        unsigned long long* stamps = nullptr;
-        if (n.policy.timeline) {
-            if (stamped + 8 * (size_t)G->per_xcd[t] > WG_STAMP_BLOCKS) return UDAPOSE_ERR_ARG;
-            stamps = (unsigned long long*)n.policy.timeline + stamped * 8;
-            stamped += 8 * (size_t)G->per_xcd[t];
-        }
-        const int tok = conv_prof_before(s, 2, G->flops[t]);
-        const int rc = wgrad_group_launch(s, t, G->d_tab[t], G->d_blk[t], G->per_xcd[t], act, ws, grads[0], nullptr, nullptr, nullptr, nullptr, nullptr, stamps);
-        conv_prof_after(s, tok);
-        CK(rc);
-    }
+    CK(launch_wg_classes(s, n, G, act, ws, grads[0]));
     return wg_after(s, n, G, ws, grads, beta, with_stem);
 }
 // The grouped weight gradients of TWO passes of this plan (each with its own arenas, gradient tensors and accumulate mode) as ONE
@@ -1030,7 +1012,9 @@ int run_wg_group(hipStream_t s, Net& n, const char* act, char* ws, void* const* 
 // its tensor updated for the NEXT accumulation), whole backward, and an update table bound for these gradient tensors that knows the split jobs.
 // *deferred tells the caller whether it was taken.  The stem's sum goes into the workspace and feeds its unpack launch: it still runs here.
 int run_wg_pair(hipStream_t s, Net& n, const char* actA, char* wsA, void* const* gradsA, float betaA, const char* actB, char* wsB,
-                void* const* gradsB, float betaB, int part, bool defer = false, int* deferred = nullptr) {
+                void* const* gradsB, float betaB, int part, bool defer, int* deferred) {
+    if (part < 0 || part > 2 || (n.f32 && !n.strict) || !n.policy.wgrad_group) return UDAPOSE_ERR_ARG;
+    DbgSyncScope dbg(n.policy.debug_sync);
     if (deferred) *deferred = 0;
     Net::WgGroup* GA = find_wg_group(n, gradsA, betaA, part);
     Net::WgGroup* GB = find_wg_group(n, gradsB, betaB, part);
@@ -1048,33 +1032,19 @@ int run_wg_pair(hipStream_t s, Net& n, const char* actA, char* wsA, void* const*
     }
     CK(wg_before(s, n, GA, wsA, gradsA, with_stem));
     CK(wg_before(s, n, GB, wsB, gradsB, with_stem));
-    size_t stamped = 0;
-    for (int t = 0; t < WG_CLASSES; ++t) {
-        if (!GA->per_xcd[t]) continue;
-        unsigned long long* stamps = nullptr;
-        if (n.policy.timeline) {
-            if (stamped + 16 * (size_t)GA->per_xcd[t] > WG_STAMP_BLOCKS) return UDAPOSE_ERR_ARG;
-            stamps = (unsigned long long*)n.policy.timeline + stamped * 8;
-            stamped += 16 * (size_t)GA->per_xcd[t];
-        }
-        const int tok = conv_prof_before(s, 2, GA->flops[t] + GB->flops[t]);
-        const int rc = wgrad_group_launch(s, t, GA->d_tab[t], GA->d_blk[t], GA->per_xcd[t], actA, wsA, gradsA[0], GB->d_tab[t], GB->d_blk[t], actB, wsB,
-                                          gradsB[0], stamps);
-        conv_prof_after(s, tok);
-        CK(rc);
-    }
+    CK(launch_wg_classes(s, n, GA, actA, wsA, gradsA[0], GB, actB, wsB, gradsB[0]));
     // (one table for both passes - equal accumulate modes and the same relative placement of the gradient tensors, so that the jobs'
     // destination offsets hold for both: their split sums share it, one launch over both workspaces)
     const bool pair_sum = GA == GB && GA->n_sum_blk > 0;
-    const bool leave = defer && pair_sum && part == 0 && betaA == 0.f && n.upd.jobs && n.upd_sum_group == GA && n.upd.k_g == gradsA[0] &&
+    const bool leave = defer && pair_sum && part == 0 && betaA == 0.f && n.upd.jobs.d && n.upd_sum_group == GA && n.upd.k_g == gradsA[0] &&
                        GA->n_sum_blk > GA->n_sum_ws_blk;
     if (leave) {
         const int rest = GA->n_sum_blk - GA->n_sum_ws_blk;
-        CK(pw_split_sum(s, GA->d_sum, GA->d_sum_blk + 2 * rest, GA->n_sum_ws_blk, wsA, (char*)gradsA[0], wsB, (char*)gradsB[0]));
+        CK(pw_split_sum(s, GA->d_sum.d, GA->d_sum_blk.d + 2 * rest, GA->n_sum_ws_blk, wsA, (char*)gradsA[0], wsB, (char*)gradsB[0]));
         n.deferred = Net::Deferred{GA, wsA, wsB, (char*)gradsA[0], (char*)gradsB[0]};
         if (deferred) *deferred = 1;
     } else if (pair_sum) {
-        CK(pw_split_sum(s, GA->d_sum, GA->d_sum_blk, GA->n_sum_blk, wsA, (char*)gradsA[0], wsB, (char*)gradsB[0]));
+        CK(pw_split_sum(s, GA->d_sum.d, GA->d_sum_blk.d, GA->n_sum_blk, wsA, (char*)gradsA[0], wsB, (char*)gradsB[0]));
     }
     CK(wg_after(s, n, GA, wsA, gradsA, betaA, with_stem, pair_sum));
     return wg_after(s, n, GB, wsB, gradsB, betaB, with_stem, pair_sum);
@@ -1083,17 +1053,11 @@ int run_wg_pair(hipStream_t s, Net& n, const char* actA, char* wsA, void* const*
 
 int net_wgrad_pair(void* h, hipStream_t s, const void* actA, void* wsA, void* const* gradsA, float betaA, const void* actB, void* wsB,
                    void* const* gradsB, float betaB, int part) {
-    Net& n = *(Net*)h;
-    if (part < 0 || part > 2 || (n.f32 && !n.strict) || !n.policy.wgrad_group) return UDAPOSE_ERR_ARG;
-    DbgSyncScope dbg(n.policy.debug_sync);
-    return run_wg_pair(s, n, (const char*)actA, (char*)wsA, gradsA, betaA, (const char*)actB, (char*)wsB, gradsB, betaB, part);
+    return run_wg_pair(s, *(Net*)h, (const char*)actA, (char*)wsA, gradsA, betaA, (const char*)actB, (char*)wsB, gradsB, betaB, part, false, nullptr);
 }
 int net_wgrad_pair_defer(void* h, hipStream_t s, const void* actA, void* wsA, void* const* gradsA, float betaA, const void* actB, void* wsB,
                          void* const* gradsB, float betaB, int part, int* deferred) {
-    Net& n = *(Net*)h;
-    if (part < 0 || part > 2 || (n.f32 && !n.strict) || !n.policy.wgrad_group) return UDAPOSE_ERR_ARG;
-    DbgSyncScope dbg(n.policy.debug_sync);
-    return run_wg_pair(s, n, (const char*)actA, (char*)wsA, gradsA, betaA, (const char*)actB, (char*)wsB, gradsB, betaB, part, true, deferred);
+    return run_wg_pair(s, *(Net*)h, (const char*)actA, (char*)wsA, gradsA, betaA, (const char*)actB, (char*)wsB, gradsB, betaB, part, true, deferred);
 }
 // the split sums a pair call left to an update that is not going to run: their own launch after all (no mark: nothing to do)
 int net_split_sum_flush(void* h, hipStream_t s) {
@@ -1101,7 +1065,7 @@ int net_split_sum_flush(void* h, hipStream_t s) {
     const Net::Deferred d = n.deferred;
     if (!d.G) return UDAPOSE_OK;
     n.deferred = Net::Deferred{};
-    return pw_split_sum(s, d.G->d_sum, d.G->d_sum_blk, d.G->n_sum_blk - d.G->n_sum_ws_blk, d.wsA, d.gA, d.wsB, d.gB);
+    return pw_split_sum(s, d.G->d_sum.d, d.G->d_sum_blk.d, d.G->n_sum_blk - d.G->n_sum_ws_blk, d.wsA, d.gA, d.wsB, d.gB);
 }
 // the deal of a grouped launch as a pure host function (tests): units (nblk, stages) -> the runs of every XCD's list in list order, as
 // entries (xcd, unit, first work-group of the unit, count), at most `cap` of them; returns the number of entries; modelled finish per XCD
@@ -1284,8 +1248,8 @@ int net_backward(void* h, hipStream_t s, const float* dout_nchw, const void* con
 int net_apply_running(void* h, hipStream_t s, const void* act_, void* const* buffers, float momentum) {
     Net& n = *(Net*)h;
     // one launch for all layers through the job table net_bind built for these buffers
-    if (!n.d_runjobs || n.runjobs_key != buffers[0]) return UDAPOSE_ERR_NOT_PREPARED;
-    return pw_bn_running_update_multi(s, n.d_runjobs, n.n_runjobs, 2048, act_, momentum);
+    if (!n.d_runjobs.d || n.runjobs_key != buffers[0]) return UDAPOSE_ERR_NOT_PREPARED;
+    return pw_bn_running_update_multi(s, n.d_runjobs.d, (int)n.d_runjobs.n, 2048, act_, momentum);
 }
 int net_bind_grads(void* h, void* const* grads) {
     Net& n = *(Net*)h;
@@ -1375,12 +1339,7 @@ int net_bind_update_groups(void* hs, void* ht, int kind, void* const* params_s, 
         // ConvTranspose2d master [Ci][T][Co]: dgrad pack = cast, fprop pack = per-tap transpose
         return push(c.w_idx, ws_ + c.wb_off, nullptr, s_split ? nullptr : ws_ + c.wf_off, t_split ? nullptr : wt_ + c.wf_off, g.Ci, T, g.Co);
     };
-    CK(conv(n.stem));
-    for (auto& b : n.blocks) {
-        CK(conv(b.c1)); CK(conv(b.c2)); CK(conv(b.c3));
-        if (b.has_ds) CK(conv(b.cd));
-    }
-    for (int i = 0; i < 3; ++i) CK(conv(n.up[i]));
+    CK(for_each_conv(n, conv));
     CK(push(n.head.w_idx, s_split ? nullptr : ws_ + n.head.wf_off, t_split ? nullptr : wt_ + n.head.wf_off, nullptr, nullptr, 0, 0, 0));      // [K][256]: the fprop pack is a cast
     for (int i = 0; i < n.n_params; ++i)
         if (!covered[i]) CK(push(i, nullptr, nullptr, nullptr, nullptr, 0, 0, 0));                   // BN vectors, head bias, backbone.fc
@@ -1391,14 +1350,7 @@ int net_bind_update_groups(void* hs, void* ht, int kind, void* const* params_s, 
     }
     n.upd_sum_group = nullptr;
     Net::UpdTab& u = n.upd;
-    if (u.jobs) { (void)hipFree(u.jobs); (void)hipFree(u.blk_job); (void)hipFree(u.blk_sub); u.jobs = nullptr; }
-    if (hipMalloc((void**)&u.jobs, jobs.size() * sizeof(TailJob)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMalloc((void**)&u.blk_job, bj.size() * sizeof(int)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMalloc((void**)&u.blk_sub, bs.size() * sizeof(int)) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMemcpy(u.jobs, jobs.data(), jobs.size() * sizeof(TailJob), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMemcpy(u.blk_job, bj.data(), bj.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    if (hipMemcpy(u.blk_sub, bs.data(), bs.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
-    u.nblocks = (int)bj.size();
+    CK(u.upload(jobs, bj, bs));
     u.k_ps = params_s[0]; u.k_pt = params_t[0]; u.k_g = grads[0]; u.k_m = h_m[0]; u.k_ws = wpack_s_; u.k_wt = wpack_t_;
     u.kind = kind; u.ngroups = ngroups;
     n.upd_sum_group = SG;
@@ -1418,22 +1370,22 @@ int fused_update(void* hs, void* ht, hipStream_t s, int kind, void* const* param
     const Net& nt = *(const Net*)ht;
     DbgSyncScope dbg(n.policy.debug_sync);
     const Net::UpdTab& u = n.upd;
-    if (!u.jobs || u.k_ps != params_s[0] || u.k_pt != params_t[0] || u.k_g != grads[0] || u.k_m != h_m[0] || u.k_ws != wpack_s_ || u.k_wt != wpack_t_ ||
+    if (!u.jobs.d || u.k_ps != params_s[0] || u.k_pt != params_t[0] || u.k_g != grads[0] || u.k_m != h_m[0] || u.k_ws != wpack_s_ || u.k_wt != wpack_t_ ||
         u.kind != kind || u.ngroups != ngroups)
         return UDAPOSE_ERR_NOT_PREPARED;
     // split sums a pair call left to this sweep: it must be the sweep of exactly those two gradient buffers
     const Net::Deferred d = n.deferred;
     if (d.G && (d.G != n.upd_sum_group || d.gA != (char*)grads[0] || grad2_delta != (long long)(d.gB - d.gA))) return UDAPOSE_ERR_NOT_PREPARED;
     n.deferred = Net::Deferred{};
-    CK(opt_tail(s, u.jobs, u.blk_job, u.blk_sub, u.nblocks, kind, lr, beta1, beta2, eps, nesterov, step, gscale, ngroups, states, wds, alpha, oma, do_adam,
+    CK(opt_tail(s, u.jobs.d, u.blk_job.d, u.blk_sub.d, u.nblocks(), kind, lr, beta1, beta2, eps, nesterov, step, gscale, ngroups, states, wds, alpha, oma, do_adam,
                 grad2_delta, 1, d.G ? d.wsA : nullptr, d.G ? d.wsB : nullptr));
     // the two packs that are not a cast or a per-tap transpose of a whole tensor: the stem's 3 -> 8 channel gather (both
     // networks) and the head's zero-padded dgrad pack (student)
     if (n.strict)   // 'strict' student: its split forward packs (stem included) from the updated weights, one pack launch (net_bind's table)
         CK(net_pack_weights(hs, s, (const void* const*)params_s, wpack_s_, 0));
     else
-        CK(pack_conv(s, n, n.stem, (const void* const*)params_s, (char*)wpack_s_, false));
-    if (nt.f32 != 2) CK(pack_conv(s, nt, nt.stem, (const void* const*)params_t, (char*)wpack_t_, false));
+        CK(pack_conv(s, n, n.stem, (const void* const*)params_s, (char*)wpack_s_));
+    if (nt.f32 != 2) CK(pack_conv(s, nt, nt.stem, (const void* const*)params_t, (char*)wpack_t_));
     CK(pw_pack_strided(s, (const float*)params_s[n.head.w_idx], (elem_t*)((char*)wpack_s_ + n.head.wb_off), 256, 1, 1, 1, 64, n.K, 1, 0, 0, 256));
     return UDAPOSE_OK;
 }
