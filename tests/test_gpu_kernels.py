@@ -264,8 +264,12 @@ def test_adain_matches_oracle(dev, golden_dir):
     ref = 0.6 * style_ref.adain_ref(c, s) + 0.4 * c
     close(nchw(out), ref, 1.2e-2)
     m, sd = style_ref.calc_mean_std_ref(c)
-    np.testing.assert_allclose(st[..., 0].cpu().numpy(), m.reshape(2, 512).numpy(), rtol=1e-4, atol=1e-5)
-    np.testing.assert_allclose(st[..., 1].cpu().numpy(), sd.reshape(2, 512).numpy(), rtol=1e-4)
+    # the statistics against the float64 ones under their derived bars (helpers.fp64_adain.stat_bars: on this tensor at most 1.7e-5 relative
+    # for a std, 1.1e-5 absolute for a mean), and against the oracle's fp32 ones (within 1e-7 of float64) at those bars rounded up
+    from helpers import fp64_adain as fa
+    fa.check_stats(st[..., 0].cpu(), st[..., 1].cpu(), fa.stats(c.permute(0, 2, 3, 1).reshape(2, 64, 512).double(), 1e-5), "adain golden")
+    np.testing.assert_allclose(st[..., 0].cpu().numpy(), m.reshape(2, 512).numpy(), rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(st[..., 1].cpu().numpy(), sd.reshape(2, 512).numpy(), rtol=2e-5)
 
 
 @pytest.mark.parametrize("case", [("1x1", 2, 16, 16, 64, 256, 1, 1, 0), ("3x3_s2", 2, 16, 16, 128, 128, 3, 2, 1), ("3x3_ragged", 3, 12, 12, 32, 64, 3, 1, 1)],

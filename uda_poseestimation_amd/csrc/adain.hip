@@ -49,6 +49,10 @@ template <> __device__ __forceinline__ void st8<float>(float* p, const float (&v
 // CACHE pixels of each lane's content stay in registers, so for feature maps up to 128 * CACHE = 1024 pixels (relu4_1 of a
 // 256x256 image: the training shape) pass 2 re-reads nothing: the kernel moves the algorithmic minimum (content + style in,
 // result out).  Larger maps re-read the uncached remainder.  Unbiased variance + eps like the reference.
+// The sums are taken about a per-channel pivot k = the channel's first pixel (every lane of a channel group loads the same 16 / 32
+// bytes of pixel 0: one line, one extra load): sum (x - k) and sum (x - k)^2, mean = k + s1 / HW, var = (s2 - s1^2 / HW) / (HW - 1).
+// The one-pass form about zero loses mean^2 / var of its precision (a channel at 100 +- 0.01 came out with a non-positive variance
+// and NaN outputs); about a pivot inside the data the loss is at most 1 + max|x - mean|^2 / var, whatever the mean.
 constexpr int ATPB = 1024, APL = ATPB / 8, CACHE = 8;
 
 // the cached pixels stay in their STORAGE form (4 registers per 8 bf16 values, 8 per 8 floats)
@@ -75,6 +79,7 @@ __global__ __launch_bounds__(ATPB) void adain_k(const T* __restrict__ content, c
     if (alpha_dev) alpha = *alpha_dev;      // (a captured launch reads the step's blend factor from device memory)
     __shared__ float red[ATPB / 64][8][4][8];   // [wave][cg][stat][e]  16 KiB
     __shared__ float coef[64][2];
+    __shared__ float piv[2][64];                // the pivots of content and style
     const int slabs = C / 64;
     const int n = blockIdx.x / slabs, sl = blockIdx.x % slabs;
     const int cg = threadIdx.x & 7, pl = threadIdx.x >> 3;
@@ -83,8 +88,13 @@ __global__ __launch_bounds__(ATPB) void adain_k(const T* __restrict__ content, c
     const T* sp = style + (size_t)n * HWs * C + c0;
     const int wave = threadIdx.x >> 6;
     Raw8<T> keep[CACHE];
-    {   // content: sums + register cache
-        float s1[8], s2[8];
+    {   // content: sums about the pivot + register cache
+        float s1[8], s2[8], kv[8];
+        ld8<T>(cp, kv);
+        if (pl == 0) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) piv[0][cg * 8 + e] = kv[e];
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
 #pragma unroll
@@ -95,14 +105,14 @@ __global__ __launch_bounds__(ATPB) void adain_k(const T* __restrict__ content, c
                 ldraw(cp + (size_t)p * C, keep[k]);
                 unraw(keep[k], v);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { s1[e] += v[e]; s2[e] += v[e] * v[e]; }
+                for (int e = 0; e < 8; ++e) { const float d = v[e] - kv[e]; s1[e] += d; s2[e] += d * d; }
             }
         }
         for (int p = pl + CACHE * APL; p < HWc; p += APL) {
             float v[8];
             ld8<T>(cp + (size_t)p * C, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { s1[e] += v[e]; s2[e] += v[e] * v[e]; }
+            for (int e = 0; e < 8; ++e) { const float d = v[e] - kv[e]; s1[e] += d; s2[e] += d * d; }
         }
         // lanes of a wave with equal cg (lane & 7) hold partials of the same channels: xor over lane bits 3..5
 #pragma unroll
@@ -115,14 +125,19 @@ __global__ __launch_bounds__(ATPB) void adain_k(const T* __restrict__ content, c
         }
     }
     {   // style: sums only
-        float s1[8], s2[8];
+        float s1[8], s2[8], kv[8];
+        ld8<T>(sp, kv);
+        if (pl == 0) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) piv[1][cg * 8 + e] = kv[e];
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
         for (int p = pl; p < HWs; p += APL) {
             float v[8];
             ld8<T>(sp + (size_t)p * C, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { s1[e] += v[e]; s2[e] += v[e] * v[e]; }
+            for (int e = 0; e < 8; ++e) { const float d = v[e] - kv[e]; s1[e] += d; s2[e] += d * d; }
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e)
@@ -140,12 +155,14 @@ __global__ __launch_bounds__(ATPB) void adain_k(const T* __restrict__ content, c
         for (int k = 0; k < ATPB / 64; ++k)
 #pragma unroll
             for (int q = 0; q < 4; ++q) a[q] += (double)red[k][g][q][e];
-        const double mc = a[0] / HWc, ms = a[2] / HWs;
-        const double vc = (a[1] - a[0] * mc) / (HWc - 1) + eps, vs = (a[3] - a[2] * ms) / (HWs - 1) + eps;
+        const double dc = a[0] / HWc, ds = a[2] / HWs;      // mean - pivot
+        const double mc = (double)piv[0][threadIdx.x] + dc, ms = (double)piv[1][threadIdx.x] + ds;
+        const double vc = (a[1] - a[0] * dc) / (HWc - 1) + eps, vs = (a[3] - a[2] * ds) / (HWs - 1) + eps;
         const float sdc = (float)sqrt(vc > 0 ? vc : 0), sds = (float)sqrt(vs > 0 ? vs : 0);
         // out = alpha*((x-mc)/sdc*sds+ms) + (1-alpha)*x = x*(alpha*sds/sdc + 1-alpha) + alpha*(ms - mc*sds/sdc)
-        coef[threadIdx.x][0] = alpha * (sds / sdc) + (1.f - alpha);
-        coef[threadIdx.x][1] = alpha * ((float)ms - (float)mc * (sds / sdc));
+        // (alpha == 0 returns the content bit for bit: x * 1 + (-0) keeps both zeros' signs, whatever the statistics are)
+        coef[threadIdx.x][0] = alpha == 0.f ? 1.f : alpha * (sds / sdc) + (1.f - alpha);
+        coef[threadIdx.x][1] = alpha == 0.f ? -0.f : alpha * ((float)ms - (float)mc * (sds / sdc));
         if (stats_out) {
             float* so = stats_out + ((size_t)n * C + sl * 64 + threadIdx.x) * 4;
             so[0] = (float)mc; so[1] = sdc; so[2] = (float)ms; so[3] = sds;
