@@ -118,6 +118,21 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t total) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
 }
 
+// Training-mode BatchNorm's scale and shift of one channel: z = y * sc + sh.  The forward (bn_finalize_k, bn_apply_chunk_k) and every
+// backward that rebuilds the ReLU mask z > 0 from y instead of reading z (pointwise.hip relu == 2, the BS epilogue of igemm.hip) form
+// them HERE, so the rebuilt mask is the forward's bit for bit.
+__device__ __forceinline__ float bn_scale(float gamma, float invstd) { return gamma * invstd; }
+__device__ __forceinline__ float bn_shift(float beta, float mean, float sc) { return beta - mean * sc; }
+__device__ __forceinline__ void bn_scale_shift(float gamma, float beta, float mean, float invstd, float& sc, float& sh) {
+    sc = bn_scale(gamma, invstd);
+    sh = bn_shift(beta, mean, sc);
+}
+__device__ __forceinline__ void bn_scale_shift8(const float (&gamma)[8], const float (&beta)[8], const float (&mean)[8], const float (&invstd)[8],
+                                                float (&sc)[8], float (&sh)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bn_scale_shift(gamma[e], beta[e], mean[e], invstd[e], sc[e], sh[e]);
+}
+
 // torch's total order on floats for max / kthvalue: NaN is the LARGEST value (and all NaNs are equal); the first index wins a tie.
 // The one arg-max order of heatmap.hip (argmax_rectify_k) and softargmax.hip.
 __device__ __forceinline__ bool hm_better(float v, int i, float bv, int bi) {

@@ -592,7 +592,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
         if (!p.bs_z && cok) {
             // the forward's own scale / shift expressions (bn_finalize_k): the mask is z > 0 without reading z
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { bsc[e] = p.bs_gamma[cbase + e] * bis[e]; bsh[e] = p.bs_beta[cbase + e] - bmu[e] * bsc[e]; }
+            for (int e = 0; e < 8; ++e) { bsc[e] = bn_scale(p.bs_gamma[cbase + e], bis[e]); bsh[e] = bn_shift(p.bs_beta[cbase + e], bmu[e], bsc[e]); }
         }
     }
 

@@ -2,6 +2,7 @@
 // (finalize / apply / backward), 3x3 s2 and 2x2 ceil max-pooling.  All activation tensors are NHWC bf16 and every
 // thread moves 16 bytes (8 channels) per access.  These kernels are HBM-roofline bound (8 TB/s peak).
 #include <stdlib.h>
+#include <type_traits>
 #include "pointwise.h"
 
 namespace {
@@ -70,6 +71,13 @@ __device__ __forceinline__ unsigned char mask_of(const half8& h) {
     unsigned mb = 0u;
 #pragma unroll
     for (int e = 0; e < 8; ++e) mb |= ((float)h[e] > 0.f ? 1u : 0u) << e;
+    return (unsigned char)mb;
+}
+// the same of 8 fp32 values as a reader of their 16-bit stored form sees them (bit e: the STORED value of channel e is > 0)
+__device__ __forceinline__ unsigned char mask_of_stored(const float (&o)[8]) {
+    unsigned mb = 0u;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) mb |= ((float)(elem_t)o[e] > 0.f ? 1u : 0u) << e;
     return (unsigned char)mb;
 }
 
@@ -261,6 +269,125 @@ __device__ __forceinline__ void slab_colsum(const float* __restrict__ slab, int 
     }
     s1 = red[0][cl][0]; s2 = red[0][cl][1];
 }
+// The building blocks of the BatchNorm kernels below.  Each expression that several kernels must agree on bit for bit is stated once here
+// (the scale / shift pair itself: bn_scale_shift, common.h); device code is compiled with the default contraction, so a * b + c fuses.
+// batch statistics of one channel from its fp64 sums: mean and clamped biased variance; from the variance, invstd and the unbiased variance.
+// (three functions, so that a kernel forms each value where it did before they were shared: the finalize kernels are pure latency)
+__device__ __forceinline__ void bn_stats_finish(double s1, double s2, double count, double& mean, double& var) {
+    mean = s1 / count;
+    var = s2 / count - mean * mean;
+    if (var < 0.0) var = 0.0;
+}
+__device__ __forceinline__ float bn_invstd(double var, float eps) { return (float)(1.0 / sqrt(var + (double)eps)); }
+__device__ __forceinline__ double bn_unbiased_var(double var, double count) { return count > 1.0 ? var * count / (count - 1.0) : var; }
+// momentum update of one channel's running statistics, like torch.nn.BatchNorm2d in train()
+__device__ __forceinline__ void bn_running_update1(float* __restrict__ rm, float* __restrict__ rv, int c, float momentum, float mean, float unb) {
+    rm[c] = (1.f - momentum) * rm[c] + momentum * mean;
+    rv[c] = (1.f - momentum) * rv[c] + momentum * unb;
+}
+// the forward's two scalar steps ...
+__device__ __forceinline__ float bn_affine(float v, float sc, float sh) { return v * sc + sh; }
+__device__ __forceinline__ float bn_relu(float o, int relu) { return (relu && o < 0.f) ? 0.f : o; }
+// ... and o = [relu]( v * sc + sh [+ res] ): the forward of 8 channels, before the rounding of the store
+template <typename T>
+__device__ __forceinline__ void bn_apply8(const float (&v)[8], const float (&sc)[8], const float (&sh)[8], const T* __restrict__ res, size_t off, int relu,
+                                          float (&o)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = bn_affine(v[e], sc[e], sh[e]);
+    if (res) {
+        float r[8];
+        ld8<T>(res + off, r);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] += r[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = bn_relu(o[e], relu);
+}
+// ... and its store at element offset off: z, the 'strict' fp16 shadow z16 (SH) and the ReLU bit mask of the stored values at mask[mi]
+template <typename T, bool SH>
+__device__ __forceinline__ void bn_store8(T* __restrict__ z, _Float16* __restrict__ z16, unsigned char* __restrict__ mask, size_t off, size_t mi,
+                                          const float (&o)[8]) {
+    if constexpr (SH) {
+        const half8 h = st8_split_shadow(z + off, z16 + off, o);
+        if (mask) mask[mi] = mask_of(h);
+    } else {
+        st8<T>(z + off, o);
+        if constexpr (sizeof(T) == sizeof(elem_t)) {
+            if (mask) mask[mi] = mask_of_stored(o);
+        }
+    }
+}
+// pixels [p0, p1) of work-group sp when each takes P of npix
+__device__ __forceinline__ void pix_range(size_t sp, int P, size_t npix, size_t& p0, size_t& p1) {
+    p0 = sp * P;
+    p1 = p0 + P;
+    if (p1 > npix) p1 = npix;
+}
+// Streaming kernels (bn_apply_k, bn_bwd_apply_pre_k) walk i = first, first + istep, .. < iend over the tensor's n8 16-byte groups, G per pixel row.
+// xcd (launcher: TPB % G == 0, gridDim.x % 8 == 0): work-group b runs on XCD b mod 8 (round-robin dealing), and XCD k takes the
+// k-th EIGHTH of the pixel rows - the rows the implicit GEMM's work-groups on XCD k wrote just before and will read next (each
+// XCD owns a contiguous range of m-tiles there): y comes from, and z stays in, that XCD's L2 (tools/probe/l2_handoff.hip)
+__device__ __forceinline__ void xcd_stream_range(size_t n8, int G, int xcd, size_t& i, size_t& iend, size_t& istep) {
+    i = (size_t)blockIdx.x * TPB + threadIdx.x, iend = n8, istep = (size_t)gridDim.x * TPB;
+    if (xcd) {
+        const size_t rows = n8 / G, per = (rows + 7) / 8;
+        const unsigned x = blockIdx.x & 7u, local = blockIdx.x >> 3, nb = gridDim.x >> 3;
+        const unsigned RB = TPB / G;
+        size_t rend = (size_t)(x + 1) * per;
+        if (rend > rows) rend = rows;
+        i = ((size_t)x * per + (size_t)local * RB + threadIdx.x / G) * G + threadIdx.x % G;
+        iend = rend * G;
+        istep = (size_t)nb * RB * G;
+    }
+}
+// Chunked kernels, grid (C/64, S): the work-group's 64-channel chunk and pixel range sp.
+// xcd: the (chunk, pixel range) pairs are dealt so that XCD k gets the k-th EIGHTH of the pixel rows (all chunks of it) - the rows
+// the implicit GEMMs' work-groups on XCD k produced and will consume (igemm.hip: each XCD owns a contiguous range of m-tiles):
+// y is then read from, and z left in, that XCD's L2 (tools/probe/l2_handoff.hip: 17.9 against 6.7 TB/s across a kernel boundary)
+__device__ __forceinline__ void xcd_chunk_of(int xcd, int& chunk, int& sp) {
+    chunk = blockIdx.x, sp = blockIdx.y;
+    if (xcd) {
+        const uint32_t w = xcd_remap(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y);
+        sp = (int)(w / gridDim.x);
+        chunk = (int)(w - (uint32_t)sp * gridDim.x);
+    }
+}
+// Chunked kernels' prelude: fp64 column sums of the work-group's 64 channels of a partial-sum slab [rows][2][C] (rows <= 128: <= 64 KB of
+// L2-resident data, read as 16-byte vectors), 8 row groups of 32 threads; part[rg][st * 64 + col] = row group rg's sum of statistic st.
+// The order of the loads and of the additions is part of the result.
+__device__ __forceinline__ void slab_colsum64(const float* __restrict__ slab, int rows, int C, int chunk, double (*part)[128]) {
+    const int q = threadIdx.x & 31, rg = threadIdx.x >> 5;          // 16-byte column quad (16 per statistic), row group
+    const float* base = slab + (size_t)(q >> 4) * C + chunk * 64 + (q & 15) * 4;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    int r = rg;
+    for (; r + 56 < rows; r += 64) {      // eight independent 16-byte loads in flight (same order of additions as the four-load form)
+        const f32x4 u = *(const f32x4*)(base + (size_t)r * 2 * C), v = *(const f32x4*)(base + (size_t)(r + 8) * 2 * C);
+        const f32x4 w = *(const f32x4*)(base + (size_t)(r + 16) * 2 * C), x = *(const f32x4*)(base + (size_t)(r + 24) * 2 * C);
+        const f32x4 u2 = *(const f32x4*)(base + (size_t)(r + 32) * 2 * C), v2 = *(const f32x4*)(base + (size_t)(r + 40) * 2 * C);
+        const f32x4 w2 = *(const f32x4*)(base + (size_t)(r + 48) * 2 * C), x2 = *(const f32x4*)(base + (size_t)(r + 56) * 2 * C);
+        a0 += ((double)u[0] + (double)v[0]) + ((double)w[0] + (double)x[0]);
+        a1 += ((double)u[1] + (double)v[1]) + ((double)w[1] + (double)x[1]);
+        a2 += ((double)u[2] + (double)v[2]) + ((double)w[2] + (double)x[2]);
+        a3 += ((double)u[3] + (double)v[3]) + ((double)w[3] + (double)x[3]);
+        a0 += ((double)u2[0] + (double)v2[0]) + ((double)w2[0] + (double)x2[0]);
+        a1 += ((double)u2[1] + (double)v2[1]) + ((double)w2[1] + (double)x2[1]);
+        a2 += ((double)u2[2] + (double)v2[2]) + ((double)w2[2] + (double)x2[2]);
+        a3 += ((double)u2[3] + (double)v2[3]) + ((double)w2[3] + (double)x2[3]);
+    }
+    for (; r + 24 < rows; r += 32) {      // four independent 16-byte loads in flight
+        const f32x4 u = *(const f32x4*)(base + (size_t)r * 2 * C), v = *(const f32x4*)(base + (size_t)(r + 8) * 2 * C);
+        const f32x4 w = *(const f32x4*)(base + (size_t)(r + 16) * 2 * C), x = *(const f32x4*)(base + (size_t)(r + 24) * 2 * C);
+        a0 += ((double)u[0] + (double)v[0]) + ((double)w[0] + (double)x[0]);
+        a1 += ((double)u[1] + (double)v[1]) + ((double)w[1] + (double)x[1]);
+        a2 += ((double)u[2] + (double)v[2]) + ((double)w[2] + (double)x[2]);
+        a3 += ((double)u[3] + (double)v[3]) + ((double)w[3] + (double)x[3]);
+    }
+    for (; r < rows; r += 8) {
+        const f32x4 u = *(const f32x4*)(base + (size_t)r * 2 * C);
+        a0 += (double)u[0]; a1 += (double)u[1]; a2 += (double)u[2]; a3 += (double)u[3];
+    }
+    part[rg][q * 4 + 0] = a0; part[rg][q * 4 + 1] = a1; part[rg][q * 4 + 2] = a2; part[rg][q * 4 + 3] = a3;
+}
 // Finalize: reduce the conv epilogue's partial sums in fp64, produce scale/shift and saved mean/invstd, update running
 // stats (momentum, unbiased variance) exactly like torch.nn.BatchNorm2d in train().
 __global__ __launch_bounds__(FIN_T) void bn_finalize_k(const float* __restrict__ slab, int rows, int C, double count, const float* __restrict__ gamma,
@@ -274,24 +401,20 @@ __global__ __launch_bounds__(FIN_T) void bn_finalize_k(const float* __restrict__
     double s1, s2;
     slab_colsum(slab, rows, C, c, c < C, s1, s2, red);
     if ((threadIdx.x / FIN_C) != 0 || c >= C) return;
-    double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    if (var < 0.0) var = 0.0;
+    double mean, var;
+    bn_stats_finish(s1, s2, count, mean, var);
     // pre_bias: the producing convolution adds a per-channel bias AFTER its statistics epilogue (the sums are those of the raw
     // accumulators): the mean of what it stored is shifted by it, the variance is not (Upsampling(bias=True), pose_resnet.py:15,41)
     if (pre_bias) mean += (double)pre_bias[c];
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float sc = gamma[c] * invstd;
+    const float invstd = bn_invstd(var, eps);
+    const float sc = bn_scale(gamma[c], invstd);
     scale[c] = sc;
-    shift[c] = beta[c] - (float)mean * sc;
+    shift[c] = bn_shift(beta[c], (float)mean, sc);
     save_mean[c] = (float)mean;
     save_invstd[c] = invstd;
-    const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
+    const double unb = bn_unbiased_var(var, count);
     save_invstd[C + c] = (float)unb;          // third saved vector: unbiased variance (deferred running-stat update)
-    if (running_mean) {
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-    }
+    if (running_mean) bn_running_update1(running_mean, running_var, c, momentum, (float)mean, (float)unb);
 }
 // deferred running-statistics update of one BN layer from its saved batch statistics [3][C] (mean, invstd, unbiased var):
 // used when a forward ran concurrently with another forward of the same module and must not race on the buffers
@@ -300,8 +423,7 @@ __global__ void bn_running_update_k(const float* __restrict__ save, int C, float
     const int c = blockIdx.x * TPB + threadIdx.x;
     if (c == 0 && nbt) *nbt += 1;
     if (c >= C) return;
-    rm[c] = (1.f - momentum) * rm[c] + momentum * save[c];
-    rv[c] = (1.f - momentum) * rv[c] + momentum * save[2 * C + c];
+    bn_running_update1(rm, rv, c, momentum, save[c], save[2 * C + c]);
 }
 // y += x over n floats (n % 4 == 0): sum of the two per-pass flat gradient buffers
 __global__ void axpy_k(float* __restrict__ y, const float* __restrict__ x, size_t n4) {
@@ -336,83 +458,37 @@ __global__ void bn_apply_k(const TY* __restrict__ y, const T* __restrict__ res, 
     // the launcher keeps gridDim.x * TPB a multiple of G (G is a power of two <= TPB, or the grid is one block per G-aligned
     // stride), so a thread's channel group never changes: its coefficients are loaded once
     const int c0 = (int)(((size_t)blockIdx.x * TPB + threadIdx.x) % G) * 8;
-    const f32x4 sa = *(const f32x4*)(scale + c0), sb = *(const f32x4*)(scale + c0 + 4);
-    const f32x4 ha = *(const f32x4*)(shift + c0), hb = *(const f32x4*)(shift + c0 + 4);
-    // xcd (launcher: TPB % G == 0, gridDim.x % 8 == 0): work-group b runs on XCD b mod 8 (round-robin dealing), and XCD k takes the
-    // k-th EIGHTH of the pixel rows - the rows the implicit GEMM's work-groups on XCD k wrote just before and will read next (each
-    // XCD owns a contiguous range of m-tiles there): y comes from, and z stays in, that XCD's L2 (tools/probe/l2_handoff.hip)
-    size_t i = (size_t)blockIdx.x * TPB + threadIdx.x, iend = n8, istep = (size_t)gridDim.x * TPB;
-    if (xcd) {
-        const size_t rows = n8 / G, per = (rows + 7) / 8;
-        const unsigned x = blockIdx.x & 7u, local = blockIdx.x >> 3, nb = gridDim.x >> 3;
-        const unsigned RB = TPB / G;
-        size_t rend = (size_t)(x + 1) * per;
-        if (rend > rows) rend = rows;
-        i = ((size_t)x * per + (size_t)local * RB + threadIdx.x / G) * G + threadIdx.x % G;
-        iend = rend * G;
-        istep = (size_t)nb * RB * G;
-    }
+    float sc[8], sh[8];
+    ld8<float>(scale + c0, sc);
+    ld8<float>(shift + c0, sh);
+    size_t i, iend, istep;
+    xcd_stream_range(n8, G, xcd, i, iend, istep);
     for (; i < iend; i += istep) {
-        float v[8];
+        float v[8], o[8];
         ld8<TY>(y + i * 8, v);
         if constexpr (SH) st8_f16(y16 + i * 8, v);
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = v[e] * (e < 4 ? sa[e] : sb[e - 4]) + (e < 4 ? ha[e] : hb[e - 4]);
-        if (res) {
-            float r[8];
-            ld8<T>(res + i * 8, r);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] += r[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (relu && o[e] < 0.f) ? 0.f : o[e];
-        if constexpr (SH) {
-            const half8 h = st8_split_shadow(z + i * 8, z16 + i * 8, o);
-            if (mask) mask[i] = mask_of(h);
-        } else {
-        st8<T>(z + i * 8, o);
-        if constexpr (sizeof(T) == 2) {
-        if (mask) {     // bit e: the STORED value of channel e is > 0 (what a reader of z would see)
-            unsigned mb = 0u;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) mb |= ((float)(T)o[e] > 0.f ? 1u : 0u) << e;
-            mask[i] = (unsigned char)mb;
-        }
-        }
-        }
+        bn_apply8<T>(v, sc, sh, res, i * 8, relu, o);
+        bn_store8<T, SH>(z, z16, mask, i * 8, i, o);
     }
 }
 
-// 8 consecutive gradient values as fp32 (the gradient entering a BN backward may be kept in fp32 near the loss, where
-// g - mean(g) - xhat*mean(g*xhat) cancels most of g and bf16 rounding of g would dominate the result)
-template <typename T> __device__ __forceinline__ void load8(const T* p, float (&o)[8]);
-template <> __device__ __forceinline__ void load8<elem_t>(const elem_t* p, float (&o)[8]) {
-    const elem8 v = *(const elem8*)p;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (float)v[e];
-}
-template <> __device__ __forceinline__ void load8<float>(const float* p, float (&o)[8]) {
-    const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o[e] = a[e]; o[4 + e] = b[e]; }
-}
-
+// output height / width of the 3x3 stride-2 pad-1 max-pool
+__host__ __device__ inline int pool3x3s2_out(int H) { return (H + 2 - 3) / 2 + 1; }
 // The gradient entering the stem's BatchNorm, gathered on the fly from the gradient of the 3x3 stride-2 max-pool's OUTPUT and the
-// saved winning taps (what maxpool3x3s2_bwd_k would have written: the <= 4 windows that contain the pixel, fp32 sum, rounded to
-// the storage type exactly as that kernel stores it) - the full-resolution gradient tensor (67 MB per pass at 256x256, b=32) is
-// never written or re-read.  pix = flat NHW index of the pool INPUT.
+// saved winning taps (the <= 4 windows that contain the pixel, fp32 sum, rounded to the storage type; no atomics) - the full-resolution
+// gradient tensor (67 MB per pass at 256x256, b=32) is never written or re-read; maxpool3x3s2_bwd_k writes exactly these values where a
+// plan does keep that tensor.  pix = flat NHW index of the pool INPUT.
 struct PoolSrc { const elem_t* dy; const unsigned char* idx; int H, W; };
 __device__ __forceinline__ void pool_grad8(const PoolSrc& ps, size_t pix, int C, int c0, float (&d)[8]) {
     const int w = (int)(pix % ps.W);
     const size_t r = pix / ps.W;
     const int h = (int)(r % ps.H);
     const size_t n = r / ps.H;
-    const int Ho = (ps.H - 1) / 2 + 1, Wo = (ps.W - 1) / 2 + 1;
+    const int Ho = pool3x3s2_out(ps.H), Wo = pool3x3s2_out(ps.W);
     float acc[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-    for (int ho = h >> 1; ho <= ((h + 1) >> 1); ++ho)
+    for (int ho = h >> 1; ho <= ((h + 1) >> 1); ++ho)       // windows with ho in {h/2, h/2 + 1 if h odd}: 2ho-1 <= h <= 2ho+1
         for (int wo = w >> 1; wo <= ((w + 1) >> 1); ++wo) {
             if (ho >= Ho || wo >= Wo) continue;
             const int kh = h - (ho * 2 - 1), kw = w - (wo * 2 - 1);
@@ -429,6 +505,87 @@ __device__ __forceinline__ void pool_grad8(const PoolSrc& ps, size_t pix, int C,
     for (int e = 0; e < 8; ++e) d[e] = (float)(elem_t)acc[e];
 }
 
+// ---- building blocks of the BatchNorm backward.  The gradient entering it (DZ) may be kept in fp32 near the loss, where
+// g - mean(g) - xhat*mean(g*xhat) cancels most of g and bf16 rounding of g would dominate the result.
+// scale / shift for the ReLU mask rebuilt from y (relu == 2: the forward's own, z is not read); zero otherwise
+__device__ __forceinline__ void bn_bwd_mask_coef8(int relu, const float* __restrict__ gamma, const float* __restrict__ beta, int c0, const float (&mu)[8],
+                                                  const float (&is)[8], float (&sc)[8], float (&sh)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { sc[e] = 0.f; sh[e] = 0.f; }
+    if (relu == 2) {
+        float ga[8], be[8];
+        ld8<float>(gamma + c0, ga);
+        ld8<float>(beta + c0, be);
+        bn_scale_shift8(ga, be, mu, is, sc, sh);
+    }
+}
+// the stored z of a 16-byte group where the mask is read from it (relu == 1)
+__device__ __forceinline__ elem8 bn_bwd_ldz8(int relu, const elem_t* __restrict__ z, size_t off) {
+    elem8 zz = {};
+    if (relu == 1) zz = *(const elem8*)(z + off);
+    return zz;
+}
+// g = d under the ReLU mask: relu 0 none, 1 the stored z > 0, 2 y * sc + sh > 0 (the forward's z rebuilt: bn_bwd_mask_coef8)
+__device__ __forceinline__ float bn_bwd_g(int relu, float d, float y, float z, float sc, float sh) {
+    float gv = d;
+    if (relu == 1 && !(z > 0.f)) gv = 0.f;
+    if (relu == 2 && !(y * sc + sh > 0.f)) gv = 0.f;
+    return gv;
+}
+__device__ __forceinline__ float bn_xhat(float y, float mu, float is) { return (y - mu) * is; }
+// dy = ca*(g - cb - xhat*cc)
+__device__ __forceinline__ elem_t bn_bwd_dy(float g, float y, float mu, float is, float ca, float cb, float cc) {
+    const float xh = bn_xhat(y, mu, is);
+    return (elem_t)(ca * (g - cb - xh * cc));
+}
+// 8 channels of a pixel, element by element (the order the expressions are formed in is kept per element):
+// the reduce's s1 += g, s2 += g * xhat
+__device__ __forceinline__ void bn_bwd_sums8(int relu, const float (&d)[8], const elem8& yy, const elem8& zz, const float (&sc)[8], const float (&sh)[8],
+                                             const float (&mu)[8], const float (&is)[8], float (&s1)[8], float (&s2)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float gv = bn_bwd_g(relu, d[e], (float)yy[e], (float)zz[e], sc[e], sh[e]);
+        s1[e] += gv;
+        s2[e] += gv * bn_xhat((float)yy[e], mu[e], is[e]);
+    }
+}
+// the apply's dy and g (the masked d, for the skip branch)
+__device__ __forceinline__ void bn_bwd_g8_dy8(int relu, const float (&d)[8], const elem8& yy, const elem8& zz, const float (&sc)[8], const float (&sh)[8],
+                                              const float (&mu)[8], const float (&is)[8], const float (&ca)[8], const float (&cb)[8],
+                                              const float (&cc)[8], elem8& o, elem8& go) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float gv = bn_bwd_g(relu, d[e], (float)yy[e], (float)zz[e], sc[e], sh[e]);
+        o[e] = bn_bwd_dy(gv, (float)yy[e], mu[e], is[e], ca[e], cb[e], cc[e]);
+        go[e] = (elem_t)gv;
+    }
+}
+// dy of an already masked g
+__device__ __forceinline__ elem8 bn_bwd_dy8(const float (&g)[8], const elem8& yy, const float (&mu)[8], const float (&is)[8], const float (&ca)[8],
+                                            const float (&cb)[8], const float (&cc)[8]) {
+    elem8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = bn_bwd_dy(g[e], (float)yy[e], mu[e], is[e], ca[e], cb[e], cc[e]);
+    return o;
+}
+// apply coefficients of one channel from its sums over the M = count pixels: ca = gamma*invstd, cb = sum(g)/M, cc = sum(g*xhat)/M
+__device__ __forceinline__ void bn_bwd_coef(float gamma, float invstd, double s1, double s2, double count, float& ca, float& cb, float& cc) {
+    ca = bn_scale(gamma, invstd);
+    cb = (float)(s1 / count);
+    cc = (float)(s2 / count);
+}
+// dgamma, dbeta (beta_acc*old + new) of channel c from s1 = sum(g), s2 = sum(g*xhat)
+__device__ __forceinline__ void bwd_param_acc(float* __restrict__ dgamma, float* __restrict__ dbeta, int c, float beta_acc, double s1, double s2) {
+    dgamma[c] = (beta_acc != 0.f ? beta_acc * dgamma[c] : 0.f) + (float)s2;
+    dbeta[c] = (beta_acc != 0.f ? beta_acc * dbeta[c] : 0.f) + (float)s1;
+}
+// chunked kernels: a thread's apply coefficients from the chunk totals tot[2][64] = (sum(g), sum(g*xhat)) of its 64 channels
+__device__ __forceinline__ void chunk_bwd_coef8(const double (*tot)[64], int cg, double count, const float (&ga)[8], const float (&is)[8], float (&ca)[8],
+                                                float (&cb)[8], float (&cc)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bn_bwd_coef(ga[e], is[e], tot[0][cg * 8 + e], tot[1][cg * 8 + e], count, ca[e], cb[e], cc[e]);
+}
+
 // Backward reduce: per-channel sum(g) and sum(g*xhat), g = dz * (z>0) when relu.  Partial slab [blocks][2][C].
 // Requires C/8 to be a power of two <= 256 (thread's channel group is loop-invariant).
 template <typename DZ, bool POOL = false>
@@ -442,30 +599,17 @@ __global__ void bn_bwd_reduce_k(const DZ* __restrict__ dz, const elem_t* __restr
     const int c0 = g * 8;
     float mu[8], is[8], s1[8], s2[8], sc[8], sh[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { mu[e] = mean[c0 + e]; is[e] = invstd[c0 + e]; s1[e] = 0.f; s2[e] = 0.f; sc[e] = 0.f; sh[e] = 0.f; }
-    if (relu == 2) {   // ReLU mask recomputed from y with the forward's own scale / shift expressions (z is not read)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { sc[e] = gamma[c0 + e] * is[e]; sh[e] = beta[c0 + e] - mu[e] * sc[e]; }
-    }
-    const size_t p0 = (size_t)blockIdx.x * pix_per_block;
-    size_t p1 = p0 + pix_per_block;
-    if (p1 > npix) p1 = npix;
+    for (int e = 0; e < 8; ++e) { mu[e] = mean[c0 + e]; is[e] = invstd[c0 + e]; s1[e] = 0.f; s2[e] = 0.f; }
+    bn_bwd_mask_coef8(relu, gamma, beta, c0, mu, is, sc, sh);
+    size_t p0, p1;
+    pix_range(blockIdx.x, pix_per_block, npix, p0, p1);
     for (size_t p = p0 + prow; p < p1; p += pstep) {
         const size_t off = p * C + c0;
         float d[8];
         if constexpr (POOL) pool_grad8(ps, p, C, c0, d);
-        else load8<DZ>(dz + off, d);
+        else ld8<DZ>(dz + off, d);
         const elem8 yy = *(const elem8*)(y + off);
-        elem8 zz = {};
-        if (relu == 1) zz = *(const elem8*)(z + off);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float gv = d[e];
-            if (relu == 1 && !((float)zz[e] > 0.f)) gv = 0.f;
-            if (relu == 2 && !((float)yy[e] * sc[e] + sh[e] > 0.f)) gv = 0.f;
-            s1[e] += gv;
-            s2[e] += gv * (((float)yy[e] - mu[e]) * is[e]);
-        }
+        bn_bwd_sums8(relu, d, yy, bn_bwd_ldz8(relu, z, off), sc, sh, mu, is, s1, s2);
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) { red[threadIdx.x][e] = s1[e]; red[threadIdx.x][8 + e] = s2[e]; }
@@ -482,8 +626,7 @@ __global__ void bn_bwd_reduce_k(const DZ* __restrict__ dz, const elem_t* __restr
         for (int e = 0; e < 8; ++e) { sp[c0 + e] = a[e]; sp[C + c0 + e] = a[8 + e]; }
     }
 }
-// Finalize backward: dgamma, dbeta (beta_acc*old + new) and the apply coefficients ca = gamma*invstd, cb = sum(g)/M,
-// cc = sum(g*xhat)/M.
+// Finalize backward: dgamma, dbeta and the apply coefficients coef[3][C] = (ca, cb, cc).
 __global__ __launch_bounds__(FIN_T) void bn_bwd_finalize_k(const float* __restrict__ slab, int rows, int C, double count, const float* __restrict__ gamma,
                                   const float* __restrict__ invstd, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                   float beta_acc, float* __restrict__ coef) {
@@ -492,13 +635,8 @@ __global__ __launch_bounds__(FIN_T) void bn_bwd_finalize_k(const float* __restri
     double s1, s2;
     slab_colsum(slab, rows, C, c, c < C, s1, s2, red);
     if ((threadIdx.x / FIN_C) != 0 || c >= C) return;
-    if (dgamma) {
-        dgamma[c] = (beta_acc != 0.f ? beta_acc * dgamma[c] : 0.f) + (float)s2;
-        dbeta[c] = (beta_acc != 0.f ? beta_acc * dbeta[c] : 0.f) + (float)s1;
-    }
-    coef[c] = gamma[c] * invstd[c];
-    coef[C + c] = (float)(s1 / count);
-    coef[2 * C + c] = (float)(s2 / count);
+    if (dgamma) bwd_param_acc(dgamma, dbeta, c, beta_acc, s1, s2);
+    bn_bwd_coef(gamma[c], invstd[c], s1, s2, count, coef[c], coef[C + c], coef[2 * C + c]);
 }
 // dy = ca*(g - cb - xhat*cc); optionally also write g (masked dz) for the skip branch
 template <typename DZ, bool POOL = false>
@@ -511,37 +649,19 @@ __global__ void bn_bwd_apply_k(const DZ* __restrict__ dz, const elem_t* __restri
         const int c0 = (int)(i % G) * 8;
         float d[8];
         if constexpr (POOL) pool_grad8(ps, i / G, C, c0, d);
-        else load8<DZ>(dz + i * 8, d);
+        else ld8<DZ>(dz + i * 8, d);
         const elem8 yy = *(const elem8*)(y + i * 8);
-        elem8 zz = {};
-        if (relu == 1) zz = *(const elem8*)(z + i * 8);
-        // per-channel coefficients as 16-byte loads (8 consecutive channels)
+        const elem8 zz = bn_bwd_ldz8(relu, z, i * 8);
+        // per-channel coefficients as 16-byte loads (8 consecutive channels), per iteration: the channel group changes with i
         float mu[8], is[8], ca[8], cb[8], cc[8], sc[8], sh[8];
-        load8<float>(mean + c0, mu);
-        load8<float>(invstd + c0, is);
-        load8<float>(coef + c0, ca);
-        load8<float>(coef + C + c0, cb);
-        load8<float>(coef + 2 * C + c0, cc);
-        if (relu == 2) {
-            float ga[8], be[8];
-            load8<float>(gamma + c0, ga);
-            load8<float>(beta + c0, be);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { sc[e] = ga[e] * is[e]; sh[e] = be[e] - mu[e] * sc[e]; }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { sc[e] = 0.f; sh[e] = 0.f; }
-        }
+        ld8<float>(mean + c0, mu);
+        ld8<float>(invstd + c0, is);
+        ld8<float>(coef + c0, ca);
+        ld8<float>(coef + C + c0, cb);
+        ld8<float>(coef + 2 * C + c0, cc);
+        bn_bwd_mask_coef8(relu, gamma, beta, c0, mu, is, sc, sh);
         elem8 o, go;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float gv = d[e];
-            if (relu == 1 && !((float)zz[e] > 0.f)) gv = 0.f;
-            if (relu == 2 && !((float)yy[e] * sc[e] + sh[e] > 0.f)) gv = 0.f;
-            const float xh = ((float)yy[e] - mu[e]) * is[e];
-            o[e] = (elem_t)(ca[e] * (gv - cb[e] - xh * cc[e]));
-            go[e] = (elem_t)gv;
-        }
+        bn_bwd_g8_dy8(relu, d, yy, zz, sc, sh, mu, is, ca, cb, cc, o, go);
         *(elem8*)(dy + i * 8) = o;
         if (gout) *(elem8*)(gout + i * 8) = go;
     }
@@ -549,9 +669,9 @@ __global__ void bn_bwd_apply_k(const DZ* __restrict__ dz, const elem_t* __restri
 
 // ---- channel-chunked BN forward: finalize + apply in one launch (wide, small-spatial layers) ---------------------------
 // Work-group = 64 channels x one pixel range, grid (C/64, S).  Prelude: the work-group column-sums its 64 channels of the conv
-// epilogue's partial-statistics slab ([rows][2][C], rows <= 128 since the igemm adds its wave rows itself: <= 64 KB of
-// L2-resident data, read as 16-byte vectors) in fp64 with a fixed order and derives scale / shift exactly as bn_finalize_k
-// does; the sp == 0 work-groups also write the saved statistics and the running-statistics update.  Then it streams its pixels.
+// epilogue's partial-statistics slab ([rows][2][C], rows <= 128 since the igemm adds its wave rows itself) in fp64 with a fixed
+// order (slab_colsum64) and derives scale / shift with the functions bn_finalize_k uses; the sp == 0 work-groups also write the
+// saved statistics and the running-statistics update.  Then it streams its pixels.
 // (TY / TZ: element types of the pre-BN conv output and of the residual / output: elem_t, elem_t in the 16-bit modes; float, sp32 in the
 // f16x2 mode, whose convolutions leave y in fp32 and whose activations are split tensors)
 // (SH: the 'strict' form of the f16x2 instance - y16 / z16 / mask as in bn_apply_k)
@@ -565,70 +685,27 @@ __global__ __launch_bounds__(TPB) void bn_apply_chunk_k(const TY* __restrict__ y
                                                         _Float16* __restrict__ z16 = nullptr) {
     __shared__ double part[8][128];
     __shared__ float scs[64], shs[64];
-    // xcd: the (chunk, pixel range) pairs are dealt so that XCD k gets the k-th EIGHTH of the pixel rows (all chunks of it) - the rows
-    // the implicit GEMMs' work-groups on XCD k produced and will consume (igemm.hip: each XCD owns a contiguous range of m-tiles):
-    // y is then read from, and z left in, that XCD's L2 (tools/probe/l2_handoff.hip: 17.9 against 6.7 TB/s across a kernel boundary)
-    int chunk = blockIdx.x, sp = blockIdx.y;
-    if (xcd) {
-        const uint32_t w = xcd_remap(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y);
-        sp = (int)(w / gridDim.x);
-        chunk = (int)(w - (uint32_t)sp * gridDim.x);
-    }
-    {
-        const int q = threadIdx.x & 31, rg = threadIdx.x >> 5;          // 16-byte column quad (16 per statistic), row group
-        const float* base = slab + (size_t)(q >> 4) * C + chunk * 64 + (q & 15) * 4;
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        int r = rg;
-        for (; r + 56 < rows; r += 64) {      // eight independent 16-byte loads in flight (same order of additions as the four-load form)
-            const f32x4 u = *(const f32x4*)(base + (size_t)r * 2 * C), v = *(const f32x4*)(base + (size_t)(r + 8) * 2 * C);
-            const f32x4 w = *(const f32x4*)(base + (size_t)(r + 16) * 2 * C), x = *(const f32x4*)(base + (size_t)(r + 24) * 2 * C);
-            const f32x4 u2 = *(const f32x4*)(base + (size_t)(r + 32) * 2 * C), v2 = *(const f32x4*)(base + (size_t)(r + 40) * 2 * C);
-            const f32x4 w2 = *(const f32x4*)(base + (size_t)(r + 48) * 2 * C), x2 = *(const f32x4*)(base + (size_t)(r + 56) * 2 * C);
-            a0 += ((double)u[0] + (double)v[0]) + ((double)w[0] + (double)x[0]);
-            a1 += ((double)u[1] + (double)v[1]) + ((double)w[1] + (double)x[1]);
-            a2 += ((double)u[2] + (double)v[2]) + ((double)w[2] + (double)x[2]);
-            a3 += ((double)u[3] + (double)v[3]) + ((double)w[3] + (double)x[3]);
-            a0 += ((double)u2[0] + (double)v2[0]) + ((double)w2[0] + (double)x2[0]);
-            a1 += ((double)u2[1] + (double)v2[1]) + ((double)w2[1] + (double)x2[1]);
-            a2 += ((double)u2[2] + (double)v2[2]) + ((double)w2[2] + (double)x2[2]);
-            a3 += ((double)u2[3] + (double)v2[3]) + ((double)w2[3] + (double)x2[3]);
-        }
-        for (; r + 24 < rows; r += 32) {      // four independent 16-byte loads in flight
-            const f32x4 u = *(const f32x4*)(base + (size_t)r * 2 * C), v = *(const f32x4*)(base + (size_t)(r + 8) * 2 * C);
-            const f32x4 w = *(const f32x4*)(base + (size_t)(r + 16) * 2 * C), x = *(const f32x4*)(base + (size_t)(r + 24) * 2 * C);
-            a0 += ((double)u[0] + (double)v[0]) + ((double)w[0] + (double)x[0]);
-            a1 += ((double)u[1] + (double)v[1]) + ((double)w[1] + (double)x[1]);
-            a2 += ((double)u[2] + (double)v[2]) + ((double)w[2] + (double)x[2]);
-            a3 += ((double)u[3] + (double)v[3]) + ((double)w[3] + (double)x[3]);
-        }
-        for (; r < rows; r += 8) {
-            const f32x4 u = *(const f32x4*)(base + (size_t)r * 2 * C);
-            a0 += (double)u[0]; a1 += (double)u[1]; a2 += (double)u[2]; a3 += (double)u[3];
-        }
-        part[rg][q * 4 + 0] = a0; part[rg][q * 4 + 1] = a1; part[rg][q * 4 + 2] = a2; part[rg][q * 4 + 3] = a3;
-    }
+    int chunk, sp;
+    xcd_chunk_of(xcd, chunk, sp);
+    slab_colsum64(slab, rows, C, chunk, part);
     __syncthreads();
     if (threadIdx.x < 64) {
         const int col = threadIdx.x, c = chunk * 64 + col;
         double s1 = 0.0, s2 = 0.0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) { s1 += part[k][col]; s2 += part[k][64 + col]; }
-        const double mean = s1 / count;
-        double var = s2 / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        const float sc = gamma[c] * invstd;
+        double mean, var;
+        bn_stats_finish(s1, s2, count, mean, var);
+        const float invstd = bn_invstd(var, eps);
+        const float sc = bn_scale(gamma[c], invstd);
         scs[col] = sc;
-        shs[col] = beta[c] - (float)mean * sc;
+        shs[col] = bn_shift(beta[c], (float)mean, sc);
         if (sp == 0) {
-            const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
+            const double unb = bn_unbiased_var(var, count);
             save[c] = (float)mean;
             save[C + c] = invstd;
             save[2 * C + c] = (float)unb;
-            if (running_mean) {
-                running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-                running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-            }
+            if (running_mean) bn_running_update1(running_mean, running_var, c, momentum, (float)mean, (float)unb);
             if (c == 0 && nbt) *nbt += 1;
         }
     }
@@ -638,38 +715,15 @@ __global__ __launch_bounds__(TPB) void bn_apply_chunk_k(const TY* __restrict__ y
     float sc[8], sh[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { sc[e] = scs[cg * 8 + e]; sh[e] = shs[cg * 8 + e]; }
-    const size_t p0 = (size_t)sp * P;
-    size_t p1 = p0 + P;
-    if (p1 > npix) p1 = npix;
+    size_t p0, p1;
+    pix_range(sp, P, npix, p0, p1);
     for (size_t p = p0 + prow; p < p1; p += 32) {
         const size_t off = p * C + c0;
         float v[8], o[8];
         ld8<TY>(y + off, v);
         if constexpr (SH) st8_f16(y16 + off, v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = v[e] * sc[e] + sh[e];
-        if (res) {
-            float r8[8];
-            ld8<TZ>(res + off, r8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] += r8[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (relu && o[e] < 0.f) ? 0.f : o[e];
-        if constexpr (SH) {
-            const half8 h = st8_split_shadow(z + off, z16 + off, o);
-            if (mask) mask[off >> 3] = mask_of(h);
-        } else {
-        st8<TZ>(z + off, o);
-        }
-        if constexpr (!SH && sizeof(TZ) == sizeof(elem_t)) {
-            if (mask) {
-                unsigned mb = 0u;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) mb |= ((float)(elem_t)o[e] > 0.f ? 1u : 0u) << e;
-                mask[off >> 3] = (unsigned char)mb;
-            }
-        }
+        bn_apply8<TZ>(v, sc, sh, res, off, relu, o);
+        bn_store8<TZ, SH>(z, z16, mask, off, off >> 3, o);
     }
 }
 
@@ -688,35 +742,19 @@ __global__ __launch_bounds__(TPB) void bn_bwd_reduce_chunk_k(const DZ* __restric
     const int cg = threadIdx.x & 7, prow = threadIdx.x >> 3;
     const int c0 = chunk * 64 + cg * 8;
     float mu[8], is[8], s1[8], s2[8], sc[8], sh[8];
-    load8<float>(mean + c0, mu);
-    load8<float>(invstd + c0, is);
+    ld8<float>(mean + c0, mu);
+    ld8<float>(invstd + c0, is);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; sc[e] = 0.f; sh[e] = 0.f; }
-    if (relu == 2) {
-        float ga[8], be[8];
-        load8<float>(gamma + c0, ga);
-        load8<float>(beta + c0, be);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { sc[e] = ga[e] * is[e]; sh[e] = be[e] - mu[e] * sc[e]; }
-    }
-    const size_t p0 = (size_t)sp * P;
-    size_t p1 = p0 + P;
-    if (p1 > npix) p1 = npix;
+    for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+    bn_bwd_mask_coef8(relu, gamma, beta, c0, mu, is, sc, sh);
+    size_t p0, p1;
+    pix_range(sp, P, npix, p0, p1);
     for (size_t p = p0 + prow; p < p1; p += 32) {
         const size_t off = p * C + c0;
         float d[8];
-        load8<DZ>(dz + off, d);
+        ld8<DZ>(dz + off, d);
         const elem8 yy = *(const elem8*)(y + off);
-        elem8 zz = {};
-        if (relu == 1) zz = *(const elem8*)(z + off);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float gv = d[e];
-            if (relu == 1 && !((float)zz[e] > 0.f)) gv = 0.f;
-            if (relu == 2 && !((float)yy[e] * sc[e] + sh[e] > 0.f)) gv = 0.f;
-            s1[e] += gv;
-            s2[e] += gv * (((float)yy[e] - mu[e]) * is[e]);
-        }
+        bn_bwd_sums8(relu, d, yy, bn_bwd_ldz8(relu, z, off), sc, sh, mu, is, s1, s2);
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) { red[prow][cg][e] = s1[e]; red[prow][cg][8 + e] = s2[e]; }
@@ -748,51 +786,24 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_chunk_k(const DZ* __restrict
         tot[st][col] = a;
     }
     __syncthreads();
-    if (sp == 0 && threadIdx.x < 64 && dgamma) {
-        const int c = chunk * 64 + threadIdx.x;
-        dgamma[c] = (beta_acc != 0.f ? beta_acc * dgamma[c] : 0.f) + (float)tot[1][threadIdx.x];
-        dbeta[c] = (beta_acc != 0.f ? beta_acc * dbeta[c] : 0.f) + (float)tot[0][threadIdx.x];
-    }
+    if (sp == 0 && threadIdx.x < 64 && dgamma) bwd_param_acc(dgamma, dbeta, chunk * 64 + threadIdx.x, beta_acc, tot[0][threadIdx.x], tot[1][threadIdx.x]);
     const int cg = threadIdx.x & 7, prow = threadIdx.x >> 3;
     const int c0 = chunk * 64 + cg * 8;
-    const double count = (double)npix;
-    float mu[8], is[8], ca[8], cb[8], cc[8], sc[8], sh[8], ga[8];
-    load8<float>(mean + c0, mu);
-    load8<float>(invstd + c0, is);
-    load8<float>(gamma + c0, ga);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        ca[e] = ga[e] * is[e];
-        cb[e] = (float)(tot[0][cg * 8 + e] / count);
-        cc[e] = (float)(tot[1][cg * 8 + e] / count);
-        sc[e] = 0.f; sh[e] = 0.f;
-    }
-    if (relu == 2) {
-        float be[8];
-        load8<float>(beta + c0, be);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { sc[e] = ga[e] * is[e]; sh[e] = be[e] - mu[e] * sc[e]; }
-    }
-    const size_t p0 = (size_t)sp * P;
-    size_t p1 = p0 + P;
-    if (p1 > npix) p1 = npix;
+    float mu[8], is[8], ga[8], ca[8], cb[8], cc[8], sc[8], sh[8];
+    ld8<float>(mean + c0, mu);
+    ld8<float>(invstd + c0, is);
+    ld8<float>(gamma + c0, ga);
+    chunk_bwd_coef8(tot, cg, (double)npix, ga, is, ca, cb, cc);
+    bn_bwd_mask_coef8(relu, gamma, beta, c0, mu, is, sc, sh);
+    size_t p0, p1;
+    pix_range(sp, P, npix, p0, p1);
     for (size_t p = p0 + prow; p < p1; p += 32) {
         const size_t off = p * C + c0;
         float d[8];
-        load8<DZ>(dz + off, d);
+        ld8<DZ>(dz + off, d);
         const elem8 yy = *(const elem8*)(y + off);
-        elem8 zz = {};
-        if (relu == 1) zz = *(const elem8*)(z + off);
         elem8 o, go;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float gv = d[e];
-            if (relu == 1 && !((float)zz[e] > 0.f)) gv = 0.f;
-            if (relu == 2 && !((float)yy[e] * sc[e] + sh[e] > 0.f)) gv = 0.f;
-            const float xh = ((float)yy[e] - mu[e]) * is[e];
-            o[e] = (elem_t)(ca[e] * (gv - cb[e] - xh * cc[e]));
-            go[e] = (elem_t)gv;
-        }
+        bn_bwd_g8_dy8(relu, d, yy, bn_bwd_ldz8(relu, z, off), sc, sh, mu, is, ca, cb, cc, o, go);
         *(elem8*)(dy + off) = o;
         if (gout) *(elem8*)(gout + off) = go;
     }
@@ -808,40 +819,25 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_pre_k(const DZ* __restrict__
     const int G = C >> 3;
     const int c0 = (int)(((size_t)blockIdx.x * TPB + threadIdx.x) % G) * 8;
     float mu[8], is[8], ca[8], cb[8], cc[8];
-    load8<float>(mean + c0, mu);
-    load8<float>(invstd + c0, is);
-    load8<float>(coef + c0, ca);
-    load8<float>(coef + C + c0, cb);
-    load8<float>(coef + 2 * C + c0, cc);
-    size_t i = (size_t)blockIdx.x * TPB + threadIdx.x, iend = n8, istep = (size_t)gridDim.x * TPB;
-    if (xcd) {      // (XCD k <- the k-th eighth of the pixel rows, as in bn_apply_k)
-        const size_t rows = n8 / G, per = (rows + 7) / 8;
-        const unsigned x = blockIdx.x & 7u, local = blockIdx.x >> 3, nb = gridDim.x >> 3;
-        const unsigned RB = TPB / G;
-        size_t rend = (size_t)(x + 1) * per;
-        if (rend > rows) rend = rows;
-        i = ((size_t)x * per + (size_t)local * RB + threadIdx.x / G) * G + threadIdx.x % G;
-        iend = rend * G;
-        istep = (size_t)nb * RB * G;
-    }
+    ld8<float>(mean + c0, mu);
+    ld8<float>(invstd + c0, is);
+    ld8<float>(coef + c0, ca);
+    ld8<float>(coef + C + c0, cb);
+    ld8<float>(coef + 2 * C + c0, cc);
+    size_t i, iend, istep;
+    xcd_stream_range(n8, G, xcd, i, iend, istep);
     for (; i < iend; i += istep) {
         float d[8];
-        load8<DZ>(g + i * 8, d);
+        ld8<DZ>(g + i * 8, d);
         const elem8 yy = *(const elem8*)(y + i * 8);
-        elem8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float xh = ((float)yy[e] - mu[e]) * is[e];
-            o[e] = (elem_t)(ca[e] * (d[e] - cb[e] - xh * cc[e]));
-        }
-        *(elem8*)(dy + i * 8) = o;
+        *(elem8*)(dy + i * 8) = bn_bwd_dy8(d, yy, mu, is, ca, cb, cc);
     }
 }
 
 // ---- BN backward whose reduction was done by the producing dgrad's epilogue (igemm.hip, BS mode) -----------------------
 // dz already carries the ReLU mask (g), and slab[rows][2][C] holds one partial row of (sum g, sum g*xhat) per m-tile of that
 // dgrad launch.  Work-group = 64 channels x one pixel range, grid (C/64, S): prelude = fp64 column sums of the work-group's 64
-// channels (rows <= 128: <= 64 KB of L2-resident data read as 16-byte vectors, fixed order), then dy = ca*(g - cb - xhat*cc).
+// channels (slab_colsum64, rows <= 128), then dy = ca*(g - cb - xhat*cc).
 template <typename DZ>
 __global__ __launch_bounds__(TPB) void bn_bwd_apply_pre_chunk_k(const DZ* __restrict__ g, const elem_t* __restrict__ y, elem_t* __restrict__ dy,
                                                                 size_t npix, int C, const float* __restrict__ mean,
@@ -850,45 +846,9 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_pre_chunk_k(const DZ* __rest
                                                                 float* __restrict__ dbeta, float beta_acc, int xcd) {
     __shared__ double part[8][128];
     __shared__ double tot[2][64];
-    int chunk = blockIdx.x, sp = blockIdx.y;
-    if (xcd) {      // (XCD k <- the k-th eighth of the pixel rows, as in bn_apply_chunk_k)
-        const uint32_t w = xcd_remap(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y);
-        sp = (int)(w / gridDim.x);
-        chunk = (int)(w - (uint32_t)sp * gridDim.x);
-    }
-    {
-        const int q = threadIdx.x & 31, rg = threadIdx.x >> 5;          // 16-byte column quad (16 per statistic), row group
-        const float* base = slab + (size_t)(q >> 4) * C + chunk * 64 + (q & 15) * 4;
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        int r = rg;
-        for (; r + 56 < rows; r += 64) {      // eight independent 16-byte loads in flight (same order of additions as the four-load form)
-            const f32x4 u = *(const f32x4*)(base + (size_t)r * 2 * C), v = *(const f32x4*)(base + (size_t)(r + 8) * 2 * C);
-            const f32x4 w = *(const f32x4*)(base + (size_t)(r + 16) * 2 * C), x = *(const f32x4*)(base + (size_t)(r + 24) * 2 * C);
-            const f32x4 u2 = *(const f32x4*)(base + (size_t)(r + 32) * 2 * C), v2 = *(const f32x4*)(base + (size_t)(r + 40) * 2 * C);
-            const f32x4 w2 = *(const f32x4*)(base + (size_t)(r + 48) * 2 * C), x2 = *(const f32x4*)(base + (size_t)(r + 56) * 2 * C);
-            a0 += ((double)u[0] + (double)v[0]) + ((double)w[0] + (double)x[0]);
-            a1 += ((double)u[1] + (double)v[1]) + ((double)w[1] + (double)x[1]);
-            a2 += ((double)u[2] + (double)v[2]) + ((double)w[2] + (double)x[2]);
-            a3 += ((double)u[3] + (double)v[3]) + ((double)w[3] + (double)x[3]);
-            a0 += ((double)u2[0] + (double)v2[0]) + ((double)w2[0] + (double)x2[0]);
-            a1 += ((double)u2[1] + (double)v2[1]) + ((double)w2[1] + (double)x2[1]);
-            a2 += ((double)u2[2] + (double)v2[2]) + ((double)w2[2] + (double)x2[2]);
-            a3 += ((double)u2[3] + (double)v2[3]) + ((double)w2[3] + (double)x2[3]);
-        }
-        for (; r + 24 < rows; r += 32) {      // four independent 16-byte loads in flight
-            const f32x4 u = *(const f32x4*)(base + (size_t)r * 2 * C), v = *(const f32x4*)(base + (size_t)(r + 8) * 2 * C);
-            const f32x4 w = *(const f32x4*)(base + (size_t)(r + 16) * 2 * C), x = *(const f32x4*)(base + (size_t)(r + 24) * 2 * C);
-            a0 += ((double)u[0] + (double)v[0]) + ((double)w[0] + (double)x[0]);
-            a1 += ((double)u[1] + (double)v[1]) + ((double)w[1] + (double)x[1]);
-            a2 += ((double)u[2] + (double)v[2]) + ((double)w[2] + (double)x[2]);
-            a3 += ((double)u[3] + (double)v[3]) + ((double)w[3] + (double)x[3]);
-        }
-        for (; r < rows; r += 8) {
-            const f32x4 u = *(const f32x4*)(base + (size_t)r * 2 * C);
-            a0 += (double)u[0]; a1 += (double)u[1]; a2 += (double)u[2]; a3 += (double)u[3];
-        }
-        part[rg][q * 4 + 0] = a0; part[rg][q * 4 + 1] = a1; part[rg][q * 4 + 2] = a2; part[rg][q * 4 + 3] = a3;
-    }
+    int chunk, sp;
+    xcd_chunk_of(xcd, chunk, sp);
+    slab_colsum64(slab, rows, C, chunk, part);
     __syncthreads();
     if (threadIdx.x < 128) {
         double a = 0.0;
@@ -897,44 +857,76 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_pre_chunk_k(const DZ* __rest
         tot[threadIdx.x >> 6][threadIdx.x & 63] = a;
     }
     __syncthreads();
-    if (sp == 0 && threadIdx.x < 64 && dgamma) {
-        const int c = chunk * 64 + threadIdx.x;
-        dgamma[c] = (beta_acc != 0.f ? beta_acc * dgamma[c] : 0.f) + (float)tot[1][threadIdx.x];
-        dbeta[c] = (beta_acc != 0.f ? beta_acc * dbeta[c] : 0.f) + (float)tot[0][threadIdx.x];
-    }
+    if (sp == 0 && threadIdx.x < 64 && dgamma) bwd_param_acc(dgamma, dbeta, chunk * 64 + threadIdx.x, beta_acc, tot[0][threadIdx.x], tot[1][threadIdx.x]);
     const int cg = threadIdx.x & 7, prow = threadIdx.x >> 3;
     const int c0 = chunk * 64 + cg * 8;
-    const double count = (double)npix;
-    float mu[8], is[8], ca[8], cb[8], cc[8], ga[8];
-    load8<float>(mean + c0, mu);
-    load8<float>(invstd + c0, is);
-    load8<float>(gamma + c0, ga);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        ca[e] = ga[e] * is[e];
-        cb[e] = (float)(tot[0][cg * 8 + e] / count);
-        cc[e] = (float)(tot[1][cg * 8 + e] / count);
-    }
-    const size_t p0 = (size_t)sp * P;
-    size_t p1 = p0 + P;
-    if (p1 > npix) p1 = npix;
+    float mu[8], is[8], ga[8], ca[8], cb[8], cc[8];
+    ld8<float>(mean + c0, mu);
+    ld8<float>(invstd + c0, is);
+    ld8<float>(gamma + c0, ga);
+    chunk_bwd_coef8(tot, cg, (double)npix, ga, is, ca, cb, cc);
+    size_t p0, p1;
+    pix_range(sp, P, npix, p0, p1);
     for (size_t p = p0 + prow; p < p1; p += 32) {
         const size_t off = p * C + c0;
         float d[8];
-        load8<DZ>(g + off, d);
+        ld8<DZ>(g + off, d);
         const elem8 yy = *(const elem8*)(y + off);
-        elem8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float xh = ((float)yy[e] - mu[e]) * is[e];
-            o[e] = (elem_t)(ca[e] * (d[e] - cb[e] - xh * cc[e]));
-        }
-        *(elem8*)(dy + off) = o;
+        *(elem8*)(dy + off) = bn_bwd_dy8(d, yy, mu, is, ca, cb, cc);
     }
 }
 
 // ------------------------------------------------------------------ max pooling (NHWC bf16)
-// 3x3 stride 2 pad 1 (ResNet stem).  Saves the winning tap (0..8, first max in (kh,kw) scan order like ATen) per element.
+// 16-byte group i of an NHWC tensor with G groups per pixel -> (n, h, w, g)
+__device__ __forceinline__ void nhwg_of(size_t i, int G, int H, int W, int& n, int& h, int& w, int& g) {
+    g = (int)(i % G);
+    size_t r = i / G;
+    w = (int)(r % W); r /= W;
+    h = (int)(r % H);
+    n = (int)(r / H);
+}
+// The 3x3 stride-2 pad-1 window (ho, wo) of 8 channels: the maximum of tap(v) over the in-range taps and the winning tap (0..8, first
+// max in (kh,kw) scan order, a NaN wins: like ATen).  tap transforms a loaded value before it competes.
+template <typename T, typename F>
+__device__ __forceinline__ void pool3x3s2_scan(const T* __restrict__ x, int n, int ho, int wo, int g, int H, int W, int C, const F& tap, float (&best)[8],
+                                               unsigned char (&bi)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = 0; }
+    bool first = true;
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+            const int h = ho * 2 - 1 + kh, w = wo * 2 - 1 + kw;
+            if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) {
+                float v[8];
+                ld8<T>(x + (((size_t)n * H + h) * W + w) * C + g * 8, v);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float f = tap(v[e], e);
+                    if (first || f > best[e] || f != f) { best[e] = f; bi[e] = (unsigned char)(kh * 3 + kw); }
+                }
+                first = false;
+            }
+        }
+}
+// the 8 winning taps of a 16-byte group as stored: one byte per channel
+__device__ __forceinline__ unsigned long long pack_taps(const unsigned char (&bi)[8]) {
+    unsigned long long pk = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) pk |= (unsigned long long)bi[e] << (8 * e);
+    return pk;
+}
+// the per-tap transforms of channel e's value: none (the plain pool), and the stem's BatchNorm + ReLU (bn_apply8's steps without a residual)
+// with the rounding of bn_apply_k's 16-bit store
+struct TapIdentity {
+    __device__ __forceinline__ float operator()(float v, int) const { return v; }
+};
+struct TapBnRelu {
+    float sc[8], sh[8];
+    __device__ __forceinline__ float operator()(float v, int e) const { return (float)(elem_t)bn_relu(bn_affine(v, sc[e], sh[e]), 1); }
+};
+// 3x3 stride 2 pad 1 (ResNet stem).  Saves the winning tap per element.
 // (SH, 'strict' plans: T = sp32 and y16 receives the pooled fp16 map, the h half of y)
 template <typename T, bool SH = false>
 __global__ void maxpool3x3s2_fwd_k(const T* __restrict__ x, T* __restrict__ y, unsigned char* __restrict__ idx, int N, int H,
@@ -942,120 +934,47 @@ __global__ void maxpool3x3s2_fwd_k(const T* __restrict__ x, T* __restrict__ y, u
     const int G = C >> 3;
     const size_t total = (size_t)N * Ho * Wo * G;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
-        const int g = (int)(i % G);
-        size_t r = i / G;
-        const int wo = (int)(r % Wo); r /= Wo;
-        const int ho = (int)(r % Ho);
-        const int n = (int)(r / Ho);
+        int n, ho, wo, g;
+        nhwg_of(i, G, Ho, Wo, n, ho, wo, g);
         float best[8];
         unsigned char bi[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = 0; }
-        bool first = true;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int h = ho * 2 - 1 + kh, w = wo * 2 - 1 + kw;
-                if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) {
-                    float v[8];
-                    ld8<T>(x + (((size_t)n * H + h) * W + w) * C + g * 8, v);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float f = v[e];
-                        if (first || f > best[e] || f != f) { best[e] = f; bi[e] = (unsigned char)(kh * 3 + kw); }
-                    }
-                    first = false;
-                }
-            }
+        pool3x3s2_scan<T>(x, n, ho, wo, g, H, W, C, TapIdentity{}, best, bi);
         if constexpr (SH) (void)st8_split_shadow(y + i * 8, y16 + i * 8, best);     // ('strict': the pooled fp16 map, T = sp32)
         else st8<T>(y + i * 8, best);
-        if (idx) {
-            unsigned long long pk = 0;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) pk |= (unsigned long long)bi[e] << (8 * e);
-            *(unsigned long long*)(idx + i * 8) = pk;
-        }
+        if (idx) *(unsigned long long*)(idx + i * 8) = pack_taps(bi);
     }
 }
-// The stem's BatchNorm apply + ReLU + 3x3 stride-2 max-pool in ONE sweep: z = relu(y*scale + shift) is formed per tap in registers,
-// rounded to the storage type (so values, ties and winning taps are exactly those of bn_apply_k followed by maxpool3x3s2_fwd_k) and
-// never written: the backward recomputes the ReLU mask from y.  Saves one 67 MB write and one (1.5x amplified) read per pass.
+// The stem's BatchNorm apply + ReLU + 3x3 stride-2 max-pool in ONE sweep: z = relu(y*scale + shift) is formed per tap in registers by
+// TapBnRelu - bn_affine and bn_relu, the scalar steps bn_apply8 is made of - and rounded to the storage type (so values, ties and winning
+// taps are exactly those of bn_apply_k followed by maxpool3x3s2_fwd_k) and never written: the backward recomputes the ReLU mask from y.
+// Saves one 67 MB write and one (1.5x amplified) read per pass.
 __global__ void bn_relu_maxpool3x3s2_k(const elem_t* __restrict__ x, elem_t* __restrict__ y, unsigned char* __restrict__ idx, int N, int H, int W,
                                        int C, int Ho, int Wo, const float* __restrict__ scale, const float* __restrict__ shift) {
     const int G = C >> 3;
     const size_t total = (size_t)N * Ho * Wo * G;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
-        const int g = (int)(i % G);
-        size_t r = i / G;
-        const int wo = (int)(r % Wo); r /= Wo;
-        const int ho = (int)(r % Ho);
-        const int n = (int)(r / Ho);
-        float sc[8], sh[8];
-        load8<float>(scale + g * 8, sc);
-        load8<float>(shift + g * 8, sh);
+        int n, ho, wo, g;
+        nhwg_of(i, G, Ho, Wo, n, ho, wo, g);
+        TapBnRelu bn;
+        ld8<float>(scale + g * 8, bn.sc);
+        ld8<float>(shift + g * 8, bn.sh);
         float best[8];
         unsigned char bi[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = 0; }
-        bool first = true;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int h = ho * 2 - 1 + kh, w = wo * 2 - 1 + kw;
-                if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) {
-                    float v[8];
-                    ld8<elem_t>(x + (((size_t)n * H + h) * W + w) * C + g * 8, v);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        float o = v[e] * sc[e] + sh[e];
-                        o = o < 0.f ? 0.f : o;                       // (bn_apply_k's expression and ReLU)
-                        const float f = (float)(elem_t)o;            // ... and its rounding to the storage type
-                        if (first || f > best[e] || f != f) { best[e] = f; bi[e] = (unsigned char)(kh * 3 + kw); }
-                    }
-                    first = false;
-                }
-            }
+        pool3x3s2_scan<elem_t>(x, n, ho, wo, g, H, W, C, bn, best, bi);
         st8<elem_t>(y + i * 8, best);
-        unsigned long long pk = 0;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) pk |= (unsigned long long)bi[e] << (8 * e);
-        *(unsigned long long*)(idx + i * 8) = pk;
+        *(unsigned long long*)(idx + i * 8) = pack_taps(bi);
     }
 }
 // gather-style backward (no atomics): each input pixel checks the <=4 windows that contain it
 __global__ void maxpool3x3s2_bwd_k(const elem_t* __restrict__ dy, const unsigned char* __restrict__ idx, elem_t* __restrict__ dx, int N,
-                                   int H, int W, int C, int Ho, int Wo) {
+                                   int H, int W, int C) {
     const int G = C >> 3;
     const size_t total = (size_t)N * H * W * G;
+    const PoolSrc ps{dy, idx, H, W};
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
-        const int g = (int)(i % G);
-        size_t r = i / G;
-        const int w = (int)(r % W); r /= W;
-        const int h = (int)(r % H);
-        const int n = (int)(r / H);
-        float acc[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-        const int ho0 = h >> 1, wo0 = w >> 1;     // windows with ho in {ho0, ho0+1 if h odd}: 2ho-1 <= h <= 2ho+1
-        for (int ho = ho0; ho <= ((h + 1) >> 1); ++ho)
-            for (int wo = wo0; wo <= ((w + 1) >> 1); ++wo) {
-                if (ho >= Ho || wo >= Wo) continue;
-                const int kh = h - (ho * 2 - 1), kw = w - (wo * 2 - 1);
-                if (kh < 0 || kh > 2 || kw < 0 || kw > 2) continue;
-                const size_t o = (((size_t)n * Ho + ho) * Wo + wo) * C + g * 8;
-                const unsigned long long pk = *(const unsigned long long*)(idx + o);
-                const elem8 d = *(const elem8*)(dy + o);
-                const unsigned tap = (unsigned)(kh * 3 + kw);
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    if (((pk >> (8 * e)) & 0xFF) == tap) acc[e] += (float)d[e];
-            }
-        elem8 o8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o8[e] = (elem_t)acc[e];
-        *(elem8*)(dx + i * 8) = o8;
+        float d[8];
+        pool_grad8(ps, i / G, C, (int)(i % G) * 8, d);
+        st8<elem_t>(dx + i * 8, d);
     }
 }
 // 2x2 stride 2 ceil-mode (VGG encoder, inference only)
@@ -1064,11 +983,8 @@ __global__ void maxpool2x2_ceil_k(const T* __restrict__ x, T* __restrict__ y, in
     const int G = C >> 3;
     const size_t total = (size_t)N * Ho * Wo * G;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
-        const int g = (int)(i % G);
-        size_t r = i / G;
-        const int wo = (int)(r % Wo); r /= Wo;
-        const int ho = (int)(r % Ho);
-        const int n = (int)(r / Ho);
+        int n, ho, wo, g;
+        nhwg_of(i, G, Ho, Wo, n, ho, wo, g);
         float best[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) best[e] = -INFINITY;
@@ -1233,26 +1149,39 @@ int pw_bn_finalize(hipStream_t s, const float* slab, int rows, int C, double cou
                        save_mean, save_invstd, pre_bias);
     return udapose_check_launch();
 }
-// finalize + apply in one launch where the chunked form applies; returns 1 when it took the layer, 0 when the caller must use
-// pw_bn_finalize + pw_bn_apply, < 0 on error
-int pw_bn_train_fused(hipStream_t s, const elem_t* y, const elem_t* res, elem_t* z, size_t npix, int C, const float* slab, int rows,
-                      const float* gamma, const float* beta, float* rm, float* rv, long long* nbt, float momentum, float eps, float* save,
-                      int relu, int enabled, unsigned char* mask) {
-    // layer3 / layer4 / the first deconv (<= 8 K pixels, <= 128 slab rows): measured -0.1 ms per step; with the 32 K-pixel
-    // layers included the 128-byte row segments of the chunked layout cost what the saved launches gain
-    // (enabled: Policy::bn_fwd_chunked)
-    const int xcd = (enabled >> 30) & 1;                   // (policy bit 30: XCD-aligned pixel ranges)
-    enabled &= ~(1 << 30);
-    if (!enabled || C < 256 || C % 64 || npix > 8192 || npix < 1024 || rows > 128) return 0;
+// launch geometry of the channel-chunked kernels, grid (chunks, S): 64-channel chunks x S pixel ranges of P pixels (a multiple of the 32 pixel
+// rows a work-group covers per iteration), about `target` work-groups in all (a policy value <= 1 means the default, 1024; others are tuning)
+struct ChunkGeom { int chunks, S, P; };
+static ChunkGeom chunk_geometry(size_t npix, int C, int target) {
     const int chunks = C / 64;
-    int S = (enabled > 1 ? enabled : 1024) / chunks;      // (policy value > 1: the target work-group count; tuning)
+    int S = (target > 1 ? target : 1024) / chunks;
     if (S > 64) S = 64;
     if (S < 1) S = 1;
     int P = (int)((npix + S - 1) / S);
     P = (P + 31) & ~31;
     S = (int)((npix + P - 1) / P);
-    hipLaunchKernelGGL((bn_apply_chunk_k<elem_t, elem_t>), dim3(chunks, S), dim3(TPB), 0, s, y, res, z, npix, C, slab, rows, (double)npix, gamma, beta, eps,
-                       momentum, rm, rv, nbt, save, relu, P, mask, xcd);
+    return {chunks, S, P};
+}
+// whether pw_bn_train_fused* take a layer, and how (enabled: Policy::bn_fwd_chunked; bit 30: XCD-aligned pixel ranges).
+// layer3 / layer4 / the first deconv (<= 8 K pixels, <= 128 slab rows): measured -0.1 ms per step; with the 32 K-pixel
+// layers included the 128-byte row segments of the chunked layout cost what the saved launches gain
+static bool fused_fwd_geometry(size_t npix, int C, int rows, int enabled, ChunkGeom& g, int& xcd) {
+    xcd = (enabled >> 30) & 1;
+    enabled &= ~(1 << 30);
+    if (!enabled || C < 256 || C % 64 || npix > 8192 || npix < 1024 || rows > 128) return false;
+    g = chunk_geometry(npix, C, enabled);
+    return true;
+}
+// finalize + apply in one launch where the chunked form applies; returns 1 when it took the layer, 0 when the caller must use
+// pw_bn_finalize + pw_bn_apply, < 0 on error
+int pw_bn_train_fused(hipStream_t s, const elem_t* y, const elem_t* res, elem_t* z, size_t npix, int C, const float* slab, int rows,
+                      const float* gamma, const float* beta, float* rm, float* rv, long long* nbt, float momentum, float eps, float* save,
+                      int relu, int enabled, unsigned char* mask) {
+    ChunkGeom g;
+    int xcd;
+    if (!fused_fwd_geometry(npix, C, rows, enabled, g, xcd)) return 0;
+    hipLaunchKernelGGL((bn_apply_chunk_k<elem_t, elem_t>), dim3(g.chunks, g.S), dim3(TPB), 0, s, y, res, z, npix, C, slab, rows, (double)npix, gamma, beta, eps,
+                       momentum, rm, rv, nbt, save, relu, g.P, mask, xcd);
     return udapose_check_launch() == UDAPOSE_OK ? 1 : UDAPOSE_ERR_LAUNCH;
 }
 // the same for the f16x2 mode: y fp32 (the split convolutions' pre-BN output), res / z split tensors.  On the teacher's forward - the
@@ -1260,22 +1189,15 @@ int pw_bn_train_fused(hipStream_t s, const elem_t* y, const elem_t* res, elem_t*
 int pw_bn_train_fused_split(hipStream_t s, const float* y, const void* res, void* z, size_t npix, int C, const float* slab, int rows,
                             const float* gamma, const float* beta, float* rm, float* rv, long long* nbt, float momentum, float eps, float* save,
                             int relu, int enabled, void* y16, void* z16, unsigned char* mask) {
-    const int xcd = (enabled >> 30) & 1;
-    enabled &= ~(1 << 30);
-    if (!enabled || C < 256 || C % 64 || npix > 8192 || npix < 1024 || rows > 128) return 0;
-    const int chunks = C / 64;
-    int S = (enabled > 1 ? enabled : 1024) / chunks;
-    if (S > 64) S = 64;
-    if (S < 1) S = 1;
-    int P = (int)((npix + S - 1) / S);
-    P = (P + 31) & ~31;
-    S = (int)((npix + P - 1) / P);
+    ChunkGeom g;
+    int xcd;
+    if (!fused_fwd_geometry(npix, C, rows, enabled, g, xcd)) return 0;
     if (y16)        // ('strict' plans: y16 / z16 / mask are the fp16 tensors the 16-bit backward reads, written in the same pass)
-        hipLaunchKernelGGL((bn_apply_chunk_k<float, sp32, true>), dim3(chunks, S), dim3(TPB), 0, s, y, (const sp32*)res, (sp32*)z, npix, C, slab, rows,
-                           (double)npix, gamma, beta, eps, momentum, rm, rv, nbt, save, relu, P, mask, xcd, (_Float16*)y16, (_Float16*)z16);
+        hipLaunchKernelGGL((bn_apply_chunk_k<float, sp32, true>), dim3(g.chunks, g.S), dim3(TPB), 0, s, y, (const sp32*)res, (sp32*)z, npix, C, slab, rows,
+                           (double)npix, gamma, beta, eps, momentum, rm, rv, nbt, save, relu, g.P, mask, xcd, (_Float16*)y16, (_Float16*)z16);
     else
-        hipLaunchKernelGGL((bn_apply_chunk_k<float, sp32>), dim3(chunks, S), dim3(TPB), 0, s, y, (const sp32*)res, (sp32*)z, npix, C, slab, rows, (double)npix,
-                           gamma, beta, eps, momentum, rm, rv, nbt, save, relu, P, (unsigned char*)nullptr, xcd);
+        hipLaunchKernelGGL((bn_apply_chunk_k<float, sp32>), dim3(g.chunks, g.S), dim3(TPB), 0, s, y, (const sp32*)res, (sp32*)z, npix, C, slab, rows, (double)npix,
+                           gamma, beta, eps, momentum, rm, rv, nbt, save, relu, g.P, (unsigned char*)nullptr, xcd);
     return udapose_check_launch() == UDAPOSE_OK ? 1 : UDAPOSE_ERR_LAUNCH;
 }
 // the same for every BN layer of a net in one launch: jobs[blockIdx.x], channels blockIdx.y*TPB..; save = act + save_off
@@ -1285,8 +1207,7 @@ __global__ void bn_running_update_multi_k(const BnRunJob* __restrict__ jobs, con
     if (c == 0 && j.nbt) *j.nbt += 1;
     if (c >= j.C) return;
     const float* save = (const float*)(act + j.save_off);
-    j.rm[c] = (1.f - momentum) * j.rm[c] + momentum * save[c];
-    j.rv[c] = (1.f - momentum) * j.rv[c] + momentum * save[2 * j.C + c];
+    bn_running_update1(j.rm, j.rv, c, momentum, save[c], save[2 * j.C + c]);
 }
 int pw_bn_running_update_multi(hipStream_t s, const BnRunJob* d_jobs, int njobs, int maxC, const void* act, float momentum) {
     hipLaunchKernelGGL(bn_running_update_multi_k, dim3(njobs, nblk(maxC)), dim3(TPB), 0, s, d_jobs, (const char*)act, momentum);
@@ -1428,6 +1349,26 @@ int pw_bn_bwd_takes_chunked(size_t npix, int C, int chunked) { return chunked &&
 int pw_bn_bwd_pre_takes_chunked(size_t npix, int C, int rows, int chunked) {
     return pw_bn_bwd_takes_chunked(npix, C, chunked & ~(3 << 29)) && rows <= 128;
 }
+// grid of the streaming reduce (bn_bwd_reduce_k): one slab row per block, each over ppb pixels
+struct ReduceGeom { int rows, ppb; };
+static ReduceGeom stream_reduce_geometry(size_t npix, int G) {
+    const int pstep = TPB / G;                                  // pixels a block covers per iteration
+    size_t want = (npix + pstep - 1) / pstep;
+    if (want > 1024) want = 1024;
+    const int rows = (int)(want < 1 ? 1 : want);
+    return {rows, (int)((npix + rows - 1) / rows)};
+}
+static void launch_bwd_finalize(hipStream_t s, const float* slab, int rows, int C, size_t npix, const float* gamma, const float* invstd, float* dgamma,
+                                float* dbeta, float beta_acc, float* coef) {
+    hipLaunchKernelGGL(bn_bwd_finalize_k, dim3((C + FIN_C - 1) / FIN_C), dim3(FIN_T), 0, s, slab, rows, C, (double)npix, gamma, invstd, dgamma, dbeta, beta_acc, coef);
+}
+// f(typed pointer): the gradient entering a BN backward is fp32 or the element type; pointee_t names the kernels' DZ inside f
+template <typename F>
+static void with_grad_type(const void* g, int is_f32, F&& f) {
+    if (is_f32) f((const float*)g);
+    else f((const elem_t*)g);
+}
+template <typename P> using pointee_t = std::remove_const_t<std::remove_pointer_t<P>>;
 int pw_bn_bwd(hipStream_t s, const void* dz, int dz_is_f32, const elem_t* z, const elem_t* y, elem_t* dy, elem_t* gout, size_t npix, int C,
               const float* gamma, const float* mean, const float* invstd, int relu, float* slab, float* coef, float* dgamma, float* dbeta,
               float beta_acc, const float* beta, int chunked) {
@@ -1438,41 +1379,23 @@ int pw_bn_bwd(hipStream_t s, const void* dz, int dz_is_f32, const elem_t* z, con
     if (C % 8 || G > 256 || (G & (G - 1))) return UDAPOSE_ERR_UNSUPPORTED;
     if (pw_bn_bwd_takes_chunked(npix, C, chunked)) {
         // channel-chunked form without a finalize launch (see bn_bwd_reduce_chunk_k)
-        const int chunks = C / 64;
-        int S = 1024 / chunks;
-        if (S > 64) S = 64;
-        if (S < 1) S = 1;
-        int P = (int)((npix + S - 1) / S);
-        P = (P + 31) & ~31;
-        S = (int)((npix + P - 1) / P);
-        const dim3 grid(chunks, S);
-        if (dz_is_f32) {
-            hipLaunchKernelGGL(bn_bwd_reduce_chunk_k<float>, grid, dim3(TPB), 0, s, (const float*)dz, z, y, npix, C, mean, invstd, relu, slab, P, gamma, beta);
-            hipLaunchKernelGGL(bn_bwd_apply_chunk_k<float>, grid, dim3(TPB), 0, s, (const float*)dz, z, y, dy, gout, npix, C, mean, invstd, relu, gamma,
-                               beta, slab, P, dgamma, dbeta, beta_acc);
-        } else {
-            hipLaunchKernelGGL(bn_bwd_reduce_chunk_k<elem_t>, grid, dim3(TPB), 0, s, (const elem_t*)dz, z, y, npix, C, mean, invstd, relu, slab, P, gamma, beta);
-            hipLaunchKernelGGL(bn_bwd_apply_chunk_k<elem_t>, grid, dim3(TPB), 0, s, (const elem_t*)dz, z, y, dy, gout, npix, C, mean, invstd, relu, gamma,
-                               beta, slab, P, dgamma, dbeta, beta_acc);
-        }
+        const ChunkGeom cg = chunk_geometry(npix, C, 1024);
+        const dim3 grid(cg.chunks, cg.S);
+        with_grad_type(dz, dz_is_f32, [&](auto d) {
+            using DZ = pointee_t<decltype(d)>;
+            hipLaunchKernelGGL(bn_bwd_reduce_chunk_k<DZ>, grid, dim3(TPB), 0, s, d, z, y, npix, C, mean, invstd, relu, slab, cg.P, gamma, beta);
+            hipLaunchKernelGGL(bn_bwd_apply_chunk_k<DZ>, grid, dim3(TPB), 0, s, d, z, y, dy, gout, npix, C, mean, invstd, relu, gamma, beta, slab, cg.P, dgamma,
+                               dbeta, beta_acc);
+        });
         return udapose_check_launch();
     }
-    const int pstep = TPB / G;                                  // pixels a block covers per iteration
-    size_t want = (npix + pstep - 1) / pstep;
-    if (want > 1024) want = 1024;
-    const int rows = (int)(want < 1 ? 1 : want);
-    const int ppb = (int)((npix + rows - 1) / rows);
-    if (dz_is_f32)
-        hipLaunchKernelGGL(bn_bwd_reduce_k<float>, dim3(rows), dim3(TPB), 0, s, (const float*)dz, z, y, npix, C, mean, invstd, relu, slab, ppb, gamma, beta);
-    else
-        hipLaunchKernelGGL(bn_bwd_reduce_k<elem_t>, dim3(rows), dim3(TPB), 0, s, (const elem_t*)dz, z, y, npix, C, mean, invstd, relu, slab, ppb, gamma, beta);
-    hipLaunchKernelGGL(bn_bwd_finalize_k, dim3((C + FIN_C - 1) / FIN_C), dim3(FIN_T), 0, s, slab, rows, C, (double)npix, gamma, invstd, dgamma, dbeta, beta_acc, coef);
-    if (dz_is_f32)
-        hipLaunchKernelGGL(bn_bwd_apply_k<float>, dim3(grid_for(npix * G)), dim3(TPB), 0, s, (const float*)dz, z, y, dy, gout, npix * G, C, mean, invstd,
-                           coef, relu, gamma, beta);
-    else
-        hipLaunchKernelGGL(bn_bwd_apply_k<elem_t>, dim3(grid_for(npix * G)), dim3(TPB), 0, s, (const elem_t*)dz, z, y, dy, gout, npix * G, C, mean,
-                           invstd, coef, relu, gamma, beta);
+    const ReduceGeom rg = stream_reduce_geometry(npix, G);
+    with_grad_type(dz, dz_is_f32, [&](auto d) {
+        using DZ = pointee_t<decltype(d)>;
+        hipLaunchKernelGGL(bn_bwd_reduce_k<DZ>, dim3(rg.rows), dim3(TPB), 0, s, d, z, y, npix, C, mean, invstd, relu, slab, rg.ppb, gamma, beta);
+        launch_bwd_finalize(s, slab, rg.rows, C, npix, gamma, invstd, dgamma, dbeta, beta_acc, coef);
+        hipLaunchKernelGGL(bn_bwd_apply_k<DZ>, dim3(grid_for(npix * G)), dim3(TPB), 0, s, d, z, y, dy, gout, npix * G, C, mean, invstd, coef, relu, gamma, beta);
+    });
     return udapose_check_launch();
 }
 // BN backward after a dgrad that already masked dz and reduced it (DgradBnStat): slab[rows][2][C] -> dgamma / dbeta and
@@ -1484,52 +1407,38 @@ int pw_bn_bwd_pre(hipStream_t s, const void* g, int g_is_f32, const elem_t* y, e
     if (C % 8 || G > 256 || (G & (G - 1)) || rows < 1) return UDAPOSE_ERR_UNSUPPORTED;
     const int xcd = (chunked >> 30) & 1, xcd_stream = (chunked >> 29) & 1;     // (bit 30: XCD-aligned pixel ranges in the chunked form; bit 29: in the streaming form too)
     chunked &= ~(3 << 29);
-    const int skip_finalize = 0;
     if (pw_bn_bwd_pre_takes_chunked(npix, C, rows, chunked)) {
-        const int chunks = C / 64;
-        int S = (chunked > 1 ? chunked : 1024) / chunks;
-        if (S > 64) S = 64;
-        if (S < 1) S = 1;
-        int P = (int)((npix + S - 1) / S);
-        P = (P + 31) & ~31;
-        S = (int)((npix + P - 1) / P);
-        const dim3 grid(chunks, S);
-        if (g_is_f32)
-            hipLaunchKernelGGL(bn_bwd_apply_pre_chunk_k<float>, grid, dim3(TPB), 0, s, (const float*)g, y, dy, npix, C, mean, invstd, gamma, slab, rows, P,
-                               dgamma, dbeta, beta_acc, xcd);
-        else
-            hipLaunchKernelGGL(bn_bwd_apply_pre_chunk_k<elem_t>, grid, dim3(TPB), 0, s, (const elem_t*)g, y, dy, npix, C, mean, invstd, gamma, slab, rows, P,
-                               dgamma, dbeta, beta_acc, xcd);
+        const ChunkGeom cg = chunk_geometry(npix, C, chunked);
+        with_grad_type(g, g_is_f32, [&](auto d) {
+            hipLaunchKernelGGL(bn_bwd_apply_pre_chunk_k<pointee_t<decltype(d)>>, dim3(cg.chunks, cg.S), dim3(TPB), 0, s, d, y, dy, npix, C, mean, invstd, gamma, slab,
+                               rows, cg.P, dgamma, dbeta, beta_acc, xcd);
+        });
         return udapose_check_launch();
     }
-    if (!skip_finalize)
-        hipLaunchKernelGGL(bn_bwd_finalize_k, dim3((C + FIN_C - 1) / FIN_C), dim3(FIN_T), 0, s, slab, rows, C, (double)npix, gamma, invstd, dgamma, dbeta, beta_acc, coef);
+    launch_bwd_finalize(s, slab, rows, C, npix, gamma, invstd, dgamma, dbeta, beta_acc, coef);
     if (legacy) {
-        if (g_is_f32)
-            hipLaunchKernelGGL(bn_bwd_apply_k<float>, dim3(grid_for(npix * G)), dim3(TPB), 0, s, (const float*)g, (const elem_t*)nullptr, y, dy, (elem_t*)nullptr,
+        with_grad_type(g, g_is_f32, [&](auto d) {
+            hipLaunchKernelGGL(bn_bwd_apply_k<pointee_t<decltype(d)>>, dim3(grid_for(npix * G)), dim3(TPB), 0, s, d, (const elem_t*)nullptr, y, dy, (elem_t*)nullptr,
                                npix * G, C, mean, invstd, coef, 0, gamma, (const float*)nullptr);
-        else
-            hipLaunchKernelGGL(bn_bwd_apply_k<elem_t>, dim3(grid_for(npix * G)), dim3(TPB), 0, s, (const elem_t*)g, (const elem_t*)nullptr, y, dy,
-                               (elem_t*)nullptr, npix * G, C, mean, invstd, coef, 0, gamma, (const float*)nullptr);
+        });
         return udapose_check_launch();
     }
     const int grid = bn_apply_grid(npix * G, C);
     const int ok = xcd_stream && pw_bn_apply_xcd_ok(npix * G, C);
-    if (g_is_f32)
-        hipLaunchKernelGGL(bn_bwd_apply_pre_k<float>, dim3(grid), dim3(TPB), 0, s, (const float*)g, y, dy, npix * G, C, mean, invstd, coef, ok);
-    else
-        hipLaunchKernelGGL(bn_bwd_apply_pre_k<elem_t>, dim3(grid), dim3(TPB), 0, s, (const elem_t*)g, y, dy, npix * G, C, mean, invstd, coef, ok);
+    with_grad_type(g, g_is_f32, [&](auto d) {
+        hipLaunchKernelGGL(bn_bwd_apply_pre_k<pointee_t<decltype(d)>>, dim3(grid), dim3(TPB), 0, s, d, y, dy, npix * G, C, mean, invstd, coef, ok);
+    });
     return udapose_check_launch();
 }
 int pw_maxpool3x3s2_fwd(hipStream_t s, const elem_t* x, elem_t* y, unsigned char* idx, int N, int H, int W, int C) {
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    const int Ho = pool3x3s2_out(H), Wo = pool3x3s2_out(W);
     hipLaunchKernelGGL(maxpool3x3s2_fwd_k<elem_t>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, x, y, idx, N, H, W, C, Ho, Wo);
     return udapose_check_launch();
 }
 int pw_bn_relu_maxpool3x3s2(hipStream_t s, const elem_t* x, elem_t* y, unsigned char* idx, int N, int H, int W, int C, const float* scale,
                             const float* shift) {
     if (C % 8 || !idx) return UDAPOSE_ERR_ARG;
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    const int Ho = pool3x3s2_out(H), Wo = pool3x3s2_out(W);
     hipLaunchKernelGGL(bn_relu_maxpool3x3s2_k, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, x, y, idx, N, H, W, C, Ho, Wo, scale, shift);
     return udapose_check_launch();
 }
@@ -1541,25 +1450,21 @@ int pw_bn_bwd_pooled(hipStream_t s, const elem_t* pool_dy, const unsigned char* 
     const int G = C / 8;
     if (C % 8 || G > 256 || (G & (G - 1)) || !beta || npix % ((size_t)H * W)) return UDAPOSE_ERR_UNSUPPORTED;
     const PoolSrc ps{pool_dy, pool_idx, H, W};
-    const int pstep = TPB / G;
-    size_t want = (npix + pstep - 1) / pstep;
-    if (want > 1024) want = 1024;
-    const int rows = (int)(want < 1 ? 1 : want);
-    const int ppb = (int)((npix + rows - 1) / rows);
-    hipLaunchKernelGGL((bn_bwd_reduce_k<elem_t, true>), dim3(rows), dim3(TPB), 0, s, (const elem_t*)nullptr, (const elem_t*)nullptr, y, npix, C, mean, invstd,
-                       2, slab, ppb, gamma, beta, ps);
-    hipLaunchKernelGGL(bn_bwd_finalize_k, dim3((C + FIN_C - 1) / FIN_C), dim3(FIN_T), 0, s, slab, rows, C, (double)npix, gamma, invstd, dgamma, dbeta, beta_acc, coef);
+    const ReduceGeom rg = stream_reduce_geometry(npix, G);
+    hipLaunchKernelGGL((bn_bwd_reduce_k<elem_t, true>), dim3(rg.rows), dim3(TPB), 0, s, (const elem_t*)nullptr, (const elem_t*)nullptr, y, npix, C, mean, invstd,
+                       2, slab, rg.ppb, gamma, beta, ps);
+    launch_bwd_finalize(s, slab, rg.rows, C, npix, gamma, invstd, dgamma, dbeta, beta_acc, coef);
     hipLaunchKernelGGL((bn_bwd_apply_k<elem_t, true>), dim3(grid_for(npix * G)), dim3(TPB), 0, s, (const elem_t*)nullptr, (const elem_t*)nullptr, y, dy,
                        (elem_t*)nullptr, npix * G, C, mean, invstd, coef, 2, gamma, beta, ps);
     return udapose_check_launch();
 }
 int pw_maxpool3x3s2_fwd_f32(hipStream_t s, const float* x, float* y, unsigned char* idx, int N, int H, int W, int C) {
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    const int Ho = pool3x3s2_out(H), Wo = pool3x3s2_out(W);
     hipLaunchKernelGGL(maxpool3x3s2_fwd_k<float>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, x, y, idx, N, H, W, C, Ho, Wo);
     return udapose_check_launch();
 }
 int pw_maxpool3x3s2_fwd_split(hipStream_t s, const void* x, void* y, unsigned char* idx, int N, int H, int W, int C, void* y16) {
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    const int Ho = pool3x3s2_out(H), Wo = pool3x3s2_out(W);
     if (y16) {      // ('strict' plans: the pooled fp16 map as well)
         hipLaunchKernelGGL((maxpool3x3s2_fwd_k<sp32, true>), dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, (const sp32*)x, (sp32*)y, idx, N, H, W,
                            C, Ho, Wo, (_Float16*)y16);
@@ -1575,8 +1480,7 @@ int pw_maxpool2x2_ceil_split(hipStream_t s, const void* x, void* y, int N, int H
     return udapose_check_launch();
 }
 int pw_maxpool3x3s2_bwd(hipStream_t s, const elem_t* dy, const unsigned char* idx, elem_t* dx, int N, int H, int W, int C) {
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    hipLaunchKernelGGL(maxpool3x3s2_bwd_k, dim3(grid_for((size_t)N * H * W * (C / 8))), dim3(TPB), 0, s, dy, idx, dx, N, H, W, C, Ho, Wo);
+    hipLaunchKernelGGL(maxpool3x3s2_bwd_k, dim3(grid_for((size_t)N * H * W * (C / 8))), dim3(TPB), 0, s, dy, idx, dx, N, H, W, C);
     return udapose_check_launch();
 }
 int pw_maxpool2x2_ceil(hipStream_t s, const elem_t* x, elem_t* y, int N, int H, int W, int C) {
