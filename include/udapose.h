@@ -589,6 +589,34 @@ int udapose_grad_scaler_check2(void* stream, const long long* g, const long long
                                int nblocks, float* dev_state, long long grad2_delta_bytes);
 int udapose_grad_scaler_update(void* stream, float* dev_state, float growth, float backoff, int interval);
 
+/* Gradient clipping by global norm (torch.nn.utils.clip_grad_norm_, norm_type 2) without rewriting a gradient: the norm is formed on the
+ * device and the clip coefficient is multiplied into every group's dev_state[4] (grad_scale), which the sweeps above read at run time.
+ *   x_i   = fl32(g_i + g2_i)                       (g2: the second per-pass buffer grad2_delta_bytes behind g, a multiple of 4; 0: none)
+ *   S_g   = sum_i x_i^2 in double, fixed order     (udapose_grad_sumsq: partials[block], one block per udapose_multi_chunk() elements)
+ *   total = sum_g (double)state_g[4]^2 * S_g       (the UNSCALED gradient: state[4] is 1/S under the loss scaler), groups in order
+ *   norm  = (float)sqrt(total)                     (before clipping, as clip_grad_norm_ returns it; +inf beyond fp32's range)
+ *   coef  = (float)min(1.0, (double)max_norm / ((double)norm + 1e-6))   from the STORED norm; NaN stays NaN; max_norm = +inf gives 1.0f
+ *   state_g[4] *= coef for every group, its old value saved - unless some state_g[5] (found_inf) is up: then nothing is scaled.
+ * sumsq: one launch per table, writing partials[0 .. nblocks); dev_state (optional) also raises dev_state[5] on a non-finite x exactly as
+ * udapose_grad_scaler_check2 does, in the same read.  clip: one work-group; group g owns partials[blk_begin[g] .. blk_end[g]); dev_states is
+ * a HOST array of n_groups (1 .. 8) device pointers, read when the call is made.  restore: dev_state_g[4] = the saved value (issue it behind
+ * the sweeps and in front of udapose_grad_scaler_update, which then refreshes 1/S as before).
+ * clip: UDAPOSE_CLIP_FLOATS device floats owned by the caller: [UDAPOSE_CLIP_MAX_NORM] is READ on the device (a captured call follows a host
+ * change through a 4-byte copy), [UDAPOSE_CLIP_NORM] and [UDAPOSE_CLIP_COEF] are written, [UDAPOSE_CLIP_SAVED + g] holds group g's saved
+ * state[4].  No atomics, no allocation, fixed summation order: capturable, and two calls on the same gradients give the same bits.
+ * UDAPOSE_ERR_ARG: a null table / partials / clip / state pointer, n_groups outside 1 .. 8, a negative or reversed block range, a
+ * grad2_delta_bytes that is no multiple of 4; nothing is launched then. */
+#define UDAPOSE_CLIP_MAX_NORM 0
+#define UDAPOSE_CLIP_NORM 1
+#define UDAPOSE_CLIP_COEF 2
+#define UDAPOSE_CLIP_SAVED 4
+#define UDAPOSE_CLIP_FLOATS 12
+int udapose_grad_sumsq(void* stream, const long long* g, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks,
+                       long long grad2_delta_bytes, float* dev_state, double* partials);
+int udapose_grad_clip(void* stream, const double* partials, const int* blk_begin, const int* blk_end, int n_groups, float* const* dev_states,
+                      float* clip);
+int udapose_grad_clip_restore(void* stream, int n_groups, float* const* dev_states, const float* clip);
+
 /* ---------------------------------------------------------------- gradient all-reduce in bf16 on the wire (data parallel,
  * the 212 MB fp32 student-gradient buffer): pack = one rounding of the fp32 bucket to bf16 (zero padded to n_padded, a
  * multiple of the world size); after an all-to-all every rank holds the W ranks' copies of its shard: shard_mean adds them in fp32

@@ -47,6 +47,9 @@ _SIGS = {
     "udapose_grad_scaler_check": (ci, [vp, vp, vp, vp, vp, ci, vp]),
     "udapose_grad_scaler_check2": (ci, [vp, vp, vp, vp, vp, ci, vp, ll]),
     "udapose_grad_scaler_update": (ci, [vp, vp, cf, cf, ci]),
+    "udapose_grad_sumsq": (ci, [vp, vp, vp, vp, vp, ci, ll, vp, vp]),
+    "udapose_grad_clip": (ci, [vp, vp, vp, vp, ci, vp, vp]),
+    "udapose_grad_clip_restore": (ci, [vp, ci, vp, vp]),
     "udapose_policy_default": (None, [vp]),
     "udapose_conv_prepare": (ci, [vp]),
     "udapose_net_set_policy": (ci, [vp, vp]),

@@ -454,6 +454,17 @@ int udapose_grad_scaler_check2(void* stream, const long long* g, const long long
 int udapose_grad_scaler_update(void* stream, float* dev_state, float growth, float backoff, int interval) {
     return opt_scaler_update(S(stream), dev_state, growth, backoff, interval);
 }
+int udapose_grad_sumsq(void* stream, const long long* g, const long long* sizes, const int* bt, const long long* bo, int nb,
+                       long long grad2_delta_bytes, float* dev_state, double* partials) {
+    return opt_grad_sumsq(S(stream), g, sizes, bt, bo, nb, grad2_delta_bytes, dev_state, partials);
+}
+int udapose_grad_clip(void* stream, const double* partials, const int* blk_begin, const int* blk_end, int n_groups, float* const* dev_states,
+                      float* clip) {
+    return opt_grad_clip(S(stream), partials, blk_begin, blk_end, n_groups, dev_states, clip);
+}
+int udapose_grad_clip_restore(void* stream, int n_groups, float* const* dev_states, const float* clip) {
+    return opt_grad_clip_restore(S(stream), n_groups, dev_states, clip);
+}
 int udapose_comm_pack_bf16(void* stream, const float* src, long long n, void* dst_bf16, long long n_padded) {
     if (!src || !dst_bf16) return UDAPOSE_ERR_ARG;
     return comm_pack_bf16(S(stream), src, n, dst_bf16, n_padded);

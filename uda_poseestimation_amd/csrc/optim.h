@@ -22,6 +22,10 @@ int opt_tail(hipStream_t s, const TailJob* d_jobs, const int* blk_job, const int
 int opt_grad_check(hipStream_t s, const long long* g, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks,
                    float* dev_state, long long grad2_delta);
 int opt_scaler_update(hipStream_t s, float* dev_state, float growth, float backoff, int interval);
+int opt_grad_sumsq(hipStream_t s, const long long* g, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks,
+                   long long grad2_delta, float* dev_state, double* partials);
+int opt_grad_clip(hipStream_t s, const double* partials, const int* blk_begin, const int* blk_end, int ngroups, float* const* states, float* clip);
+int opt_grad_clip_restore(hipStream_t s, int ngroups, float* const* states, const float* clip);
 int opt_ema(hipStream_t s, const long long* tgt, const long long* src, const long long* sizes, const int* blk_tensor, const long long* blk_off,
             int nblocks, float alpha, float one_minus_alpha);
 int opt_adam(hipStream_t s, const long long* p, const long long* g, const long long* m, const long long* v, const long long* sizes,

@@ -161,6 +161,104 @@ __global__ void scaler_update_k(float* __restrict__ state, float growth, float b
     state[6] = scale; state[7] = tr; state[5] = 0.f;
     state[4] = 1.f / scale;
 }
+// ---- gradient clipping by global norm (FusedAdam / FusedSGD max_grad_norm; torch.nn.utils.clip_grad_norm_'s norm and coefficient) ----------
+// No gradient is rewritten: the norm of the UNSCALED gradient is formed from sum(fl32(g + g2)^2) per parameter group and that group's
+// state[4] (grad_scale), and the clip coefficient is multiplied into every group's state[4], which the sweeps read at run time; a restore
+// launch behind the sweep(s) puts the saved values back.  Fixed order, no atomics: grad_sumsq_k writes one double per block (thread-strided
+// double accumulation, a shuffle tree per wave, the four waves in order), grad_clip_k - one work-group - adds each group's partials in index
+// order with the same tree.  The square of an fp32 value is exact in double, so nothing overflows or is lost below 2^-53 of the sum.
+// clip buffer (floats, include/udapose.h UDAPOSE_CLIP_*): [0] max_norm (read), [1] norm, [2] coef, [3] -, [4 .. 11] the saved state[4] per group.
+struct ClipGroups { float* state[TAIL_GROUPS]; int begin[TAIL_GROUPS]; int end[TAIL_GROUPS]; };
+enum { CLIP_MAX_NORM = 0, CLIP_NORM = 1, CLIP_COEF = 2, CLIP_SAVED = 4 };
+
+// the block's sum in a fixed order: lane i += lane i + 32, 16, ... 1 inside each wave, then ((w0 + w1) + w2) + w3
+__device__ __forceinline__ double block_sum(double v, double* lds) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+// partials[block] = sum over the block's chunk of fl32(g + g2)^2; the loads are grad_check_k's.  state != NULL: the loss scaler's found-inf check in
+// the same read (grad_check_k's test on the same values), so that an fp16 step reads its gradients once.
+__global__ __launch_bounds__(TPB) void grad_sumsq_k(MtTable t, float* __restrict__ state, long long g2, double* __restrict__ partials) {
+    __shared__ double lds[TPB / 64];
+    const int ti = t.blk_tensor[blockIdx.x];
+    const long long off = t.blk_off[blockIdx.x];
+    const float* g = (const float*)t.b[ti];
+    const long long n = t.sizes[ti];
+    const long long end = off + CHUNK < n ? off + CHUNK : n;
+    bool bad = false;
+    double acc = 0.0;
+    long long i0 = off;
+    if (((uintptr_t)(g + off) & 15) == 0 && (g2 & 15) == 0) {
+        const long long n4 = (end - off) >> 2;
+        for (long long q = threadIdx.x; q < n4; q += TPB) {
+            f32x4 v = *(const f32x4*)(g + off + q * 4);
+            if (g2) {
+                const f32x4 w = *(const f32x4*)((const char*)(g + off + q * 4) + g2);
+                v[0] += w[0]; v[1] += w[1]; v[2] += w[2]; v[3] += w[3];
+            }
+            bad = bad || !(fabsf(v[0]) <= 3.4028234e38f) || !(fabsf(v[1]) <= 3.4028234e38f) || !(fabsf(v[2]) <= 3.4028234e38f) || !(fabsf(v[3]) <= 3.4028234e38f);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc += (double)v[e] * (double)v[e];
+        }
+        i0 = off + n4 * 4;
+    }
+    for (long long i = i0 + threadIdx.x; i < end; i += TPB) {
+        float v = g[i];
+        if (g2) v += *(const float*)((const char*)(g + i) + g2);
+        bad = bad || !(fabsf(v) <= 3.4028234e38f);        // inf or nan
+        acc += (double)v * (double)v;
+    }
+    if (state && bad) state[5] = 1.f;
+    const double s = block_sum(acc, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// one work-group: S_g = the ordered sum of partials[begin_g .. end_g), total = sum_g (double)state_g[4]^2 * S_g in group order,
+// norm = (float)sqrt(total), coef = (float)min(1, max_norm / (norm + 1e-6)) from the STORED fp32 norm (torch's formula; a NaN stays a NaN),
+// then every group's state[4] is saved and multiplied by coef - unless a found_inf flag is up: the step is skipped and nothing is scaled.
+__global__ __launch_bounds__(TPB) void grad_clip_k(const double* __restrict__ partials, ClipGroups G, int ngroups, float* __restrict__ clip) {
+    __shared__ double lds[TPB / 64];
+    double total = 0.0;
+    bool skip = false;
+    for (int g = 0; g < ngroups; ++g) {
+        double acc = 0.0;
+        int i = G.begin[g] + (int)threadIdx.x;
+        for (; i + 7 * TPB < G.end[g]; i += 8 * TPB) {        // (eight loads in flight, added in index order: the sum's order is the plain loop's)
+            double v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = partials[i + k * TPB];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc += v[k];
+        }
+        for (; i < G.end[g]; i += TPB) acc += partials[i];
+        const double S = block_sum(acc, lds);
+        __syncthreads();
+        if (threadIdx.x == 0) {          // (thread 0 alone reads the states it is about to write)
+            const double gs = (double)G.state[g][4];
+            total += gs * gs * S;
+            skip = skip || G.state[g][5] != 0.f;
+        }
+    }
+    if (threadIdx.x != 0) return;
+    const float norm = (float)sqrt(total);
+    const double c = (double)clip[CLIP_MAX_NORM] / ((double)norm + 1e-6);
+    const float coef = (float)(c > 1.0 ? 1.0 : c);
+    clip[CLIP_NORM] = norm;
+    clip[CLIP_COEF] = coef;
+    for (int g = 0; g < ngroups; ++g) {
+        const float old = G.state[g][4];
+        clip[CLIP_SAVED + g] = old;
+        if (!skip) G.state[g][4] = old * coef;
+    }
+}
+__global__ void grad_clip_restore_k(ClipGroups G, int ngroups, const float* __restrict__ clip) {
+    const int g = threadIdx.x;
+    if (g < ngroups) G.state[g][4] = clip[CLIP_SAVED + g];
+}
 // ---- fused optimizer tail -------------------------------------------------------------------------------------------------
 // After the backward a step has nothing left but sweeps over the 55 M parameters, one after the other on one stream: Adam
 // (28 B / parameter), the EMA teacher update (12 B), and - at the start of the next step - the element-type weight packs of
@@ -358,6 +456,44 @@ int opt_grad_check(hipStream_t s, const long long* g, const long long* sizes, co
 int opt_scaler_update(hipStream_t s, float* dev_state, float growth, float backoff, int interval) {
     if (!dev_state || interval < 1) return UDAPOSE_ERR_ARG;
     hipLaunchKernelGGL(scaler_update_k, dim3(1), dim3(1), 0, s, dev_state, growth, backoff, (float)interval);
+    return udapose_check_launch();
+}
+
+// gradient clipping by global norm: the sum of squares of one table (one launch per parameter group, each writing its own range of `partials`),
+// the finisher over every group's range, and the restore behind the sweep(s)
+int opt_grad_sumsq(hipStream_t s, const long long* g, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks,
+                   long long grad2_delta, float* dev_state, double* partials) {
+    if (!partials || grad2_delta % 4 || nblocks < 0) return UDAPOSE_ERR_ARG;
+    if (nblocks == 0) return UDAPOSE_OK;
+    if (!g || !sizes || !blk_tensor || !blk_off) return UDAPOSE_ERR_ARG;
+    MtTable t{nullptr, g, nullptr, nullptr, sizes, blk_tensor, blk_off};
+    hipLaunchKernelGGL(grad_sumsq_k, dim3(nblocks), dim3(TPB), 0, s, t, dev_state, grad2_delta, partials);
+    return udapose_check_launch();
+}
+static int clip_groups(ClipGroups& G, const int* blk_begin, const int* blk_end, int ngroups, float* const* states) {
+    if (ngroups < 1 || ngroups > TAIL_GROUPS || !states) return UDAPOSE_ERR_ARG;
+    for (int g = 0; g < ngroups; ++g) {
+        if (!states[g]) return UDAPOSE_ERR_ARG;
+        G.state[g] = states[g];
+        if (blk_begin) {
+            if (blk_begin[g] < 0 || blk_end[g] < blk_begin[g]) return UDAPOSE_ERR_ARG;
+            G.begin[g] = blk_begin[g]; G.end[g] = blk_end[g];
+        }
+    }
+    return UDAPOSE_OK;
+}
+int opt_grad_clip(hipStream_t s, const double* partials, const int* blk_begin, const int* blk_end, int ngroups, float* const* states, float* clip) {
+    if (!partials || !blk_begin || !blk_end || !clip) return UDAPOSE_ERR_ARG;
+    ClipGroups G{};
+    if (const int rc = clip_groups(G, blk_begin, blk_end, ngroups, states)) return rc;
+    hipLaunchKernelGGL(grad_clip_k, dim3(1), dim3(TPB), 0, s, partials, G, ngroups, clip);
+    return udapose_check_launch();
+}
+int opt_grad_clip_restore(hipStream_t s, int ngroups, float* const* states, const float* clip) {
+    if (!clip) return UDAPOSE_ERR_ARG;
+    ClipGroups G{};
+    if (const int rc = clip_groups(G, nullptr, nullptr, ngroups, states)) return rc;
+    hipLaunchKernelGGL(grad_clip_restore_k, dim3(1), dim3(TAIL_GROUPS), 0, s, G, ngroups, clip);
     return udapose_check_launch();
 }
 

@@ -306,6 +306,19 @@ class MeanTeacherTrainer:
                                             # sweep's split blocks wait on ks dependent loads per row; profiles/tail_ab_runs.txt), so it stays off
         self.fused_last = False
 
+    @property
+    def max_grad_norm(self):
+        """Clipping of the student's update by the global gradient norm (FusedAdam / FusedSGD.max_grad_norm): None = off, a positive float,
+        or float('inf') to measure only (stu_optimizer.grad_norm() / clip_coef()).  An ATTRIBUTE forwarding to stu_optimizer, set after
+        construction like coral_criterion and before a GraphedTrainStep is built: on / off changes the captured launches, the value does not
+        (it lives on the device).  Data parallel: the norm is taken in _update(), behind GradSync.finish(), on the reduced gradient - every
+        rank forms the same bits and no collective is added."""
+        return getattr(self.stu_optimizer, "max_grad_norm", None)
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v):
+        self.stu_optimizer.max_grad_norm = v
+
     def _check_scaler(self):
         """An fp16 student forward needs the loss scaler the optimizer was built with (or the caller's own GradScaler: then build the
         trainer's optimizer yourself)."""
@@ -578,7 +591,9 @@ class MeanTeacherTrainer:
     def _tail_sums_splits(self):
         # (a loss scaler's inf / nan check reads the gradient tensors between the weight gradients and the sweep: the fp16 step keeps the launch)
         # (the sweep that adds the split sums has an Adam form only: FusedSGD.tail_takes_split_sums is False)
+        # (clipping by global norm reads the gradient tensors in the same place, for the same reason)
         return bool(self.sum_splits_in_tail and self._tail_sums_grads() and getattr(self.stu_optimizer, "_scaler", None) is None
+                    and getattr(self.stu_optimizer, "max_grad_norm", None) is None
                     and getattr(self.stu_optimizer, "tail_takes_split_sums", False))
 
     def _update(self):
@@ -976,7 +991,10 @@ class GraphedTrainStep:
         else:
             acc, avg_cnt, _ = kd.accuracy_device(self.out["y_s"], self.static["label_s"])
         parts = [self.out["loss_all"].reshape(1), self.out["loss_s"].reshape(1), self.out["loss_c"].reshape(1), avg_cnt.reshape(2), acc.reshape(-1)]
-        self._mextra = [k for k in ("loss_ent", "loss_coral") if k in self.out]      # (appended in this order: the layout without them is unchanged)
+        opt = self.t.stu_optimizer
+        if getattr(opt, "max_grad_norm", None) is not None:       # (the captured update has just written it: the norm before clipping)
+            self.out["grad_norm"] = opt.grad_norm()
+        self._mextra = [k for k in ("loss_ent", "loss_coral", "grad_norm") if k in self.out]      # (appended in this order: the layout without them is unchanged)
         parts += [self.out[k].reshape(1) for k in self._mextra]
         self._mk = int(acc.numel())
         self._mvec = torch.cat([p.float() for p in parts])
@@ -1129,9 +1147,12 @@ class GraphedTrainStep:
             st["u"].copy_(self.t.draw_occlusion_uniforms(self.n), non_blocking=True)
 
     def _optimizer_key(self):
-        """Storage the captured optimizer launches point at: the device state of every group and the first moment tensor."""
+        """Storage the captured optimizer launches point at: the device state of every group and the first moment tensor; with clipping by
+        global norm its device buffer and the per-block partial sums."""
         opt = self.t.stu_optimizer
         key = [ent[0].data_ptr() for _, ent in sorted(getattr(opt, "_dev", {}).items())]
+        if getattr(opt, "max_grad_norm", None) is not None:
+            key += [buf.data_ptr() for buf in (opt._clip[0] if opt._clip else None, opt._clip_part) if buf is not None]
         for g in opt.param_groups:
             for p in g["params"]:
                 st = opt.state.get(p)
@@ -1150,6 +1171,8 @@ class GraphedTrainStep:
             for k in ("betas", "eps", "weight_decay", "momentum", "nesterov"):
                 if k in g:
                     frozen.append((f"group{gi}.{k}", g[k]))
+        # clipping by global norm on / off changes the launches; its value lives on the device and may change freely (sync_hyper)
+        frozen.append(("max_grad_norm enabled", getattr(opt, "max_grad_norm", None) is not None))
         return frozen
 
     def prefetch(self, x_s, label_s, weight_s, x_t_stu, x_t_tea):

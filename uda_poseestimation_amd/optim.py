@@ -16,6 +16,13 @@ Loss scaling for the fp16 precision (`dynamic_loss_scale=True`) is torch.cuda.am
 `step()` = found-inf sweep over the gradients -> Adam / SGD sweep that un-scales (and is skipped whole, counter included,
 when an inf / nan was found) -> scale update (x backoff on overflow, x growth after `growth_interval` clean steps).
 No host read-back, so the whole thing is hipGraph-capturable.
+
+Clipping by global norm (`max_grad_norm=M`, off by default; `float("inf")` measures only) is torch.nn.utils.clip_grad_norm_'s norm and
+coefficient over ALL parameter groups without rewriting a gradient: one sum-of-squares sweep per group over g (+ the pending second
+per-pass buffer) in front of the first sweep - which also does the loss scaler's found-inf check, so an fp16 step reads its gradients once
+- a one-work-group finisher that multiplies the coefficient into every group's device grad_scale, and a restore launch behind the sweep(s).
+`grad_norm()` / `clip_coef()` are 0-d device tensors of the last step; `M` lives on the device (`sync_hyper()`), so a captured step follows
+a host change.  Fixed summation order, no atomics: two runs on the same gradients give the same bits.
 """
 import torch
 
@@ -26,6 +33,19 @@ from .utils import _MultiTensorTable, _bump_versions
 
 def _norm(v):
     return tuple(v) if isinstance(v, (list, tuple)) else v
+
+
+CLIP_MAX_NORM, CLIP_NORM, CLIP_COEF, CLIP_SAVED, CLIP_FLOATS = 0, 1, 2, 4, 12       # include/udapose.h UDAPOSE_CLIP_*
+
+
+def _max_norm(v):
+    """None (clipping off) or a positive float, +inf included (measure only)."""
+    if v is None:
+        return None
+    v = float(v)
+    if not v > 0.0:         # (NaN fails this too)
+        raise ValueError(f"max_grad_norm must be None or a positive number (float('inf') measures only), got {v!r}")
+    return v
 
 
 def group_partition(param_groups, params):
@@ -48,6 +68,10 @@ class _FusedBase(torch.optim.Optimizer):
         self._dev = {}           # group index -> (device state tensor [8], uploaded (lr, grad_scale))
         # dynamic loss scaling (GradScaler's defaults: 65536, x2 every 2000 clean steps, x0.5 on overflow), or None
         self._scaler = scaler
+        # clipping by global norm: [UDAPOSE_CLIP_FLOATS device floats (max_norm, norm, coef, -, saved grad_scales), uploaded max_norm], and
+        # one double per table block of every group; both are pointed at by captured launches and never serialised
+        self._clip, self._clip_part = None, None
+        self.max_grad_norm = self.defaults.get("max_grad_norm")        # (validates, and writes the one value into every group)
         if scaler is not None and len(self.param_groups) != 1:
             raise ValueError("dynamic loss scaling needs a single parameter group (one device-resident scaler state)")
 
@@ -96,6 +120,88 @@ class _FusedBase(torch.optim.Optimizer):
             hyper = (hyper[0], 1.0 / scale)
         return [float(group.get("step", 0)), 0.0, 0.0, hyper[0], hyper[1], 0.0, scale, tracker], hyper
 
+    # ------------------------------------------------------------------ clipping by global norm
+    @property
+    def max_grad_norm(self):
+        """None: no clipping (no launch is added).  A positive float M: the update is scaled by min(1, M / (norm + 1e-6)), norm = the global L2
+        norm of the unscaled gradient over every parameter group.  float('inf'): the norm is measured and the update is bit-identical to the
+        unclipped one.  One value for the optimizer, kept in the group dicts (state_dict()); read from device memory by the kernels."""
+        return self.param_groups[0].get("max_grad_norm")
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v):
+        v = _max_norm(v)
+        self.defaults["max_grad_norm"] = v
+        for g in self.param_groups:
+            g["max_grad_norm"] = v
+
+    def _clip_buffer(self, device):
+        if self._clip is None:
+            v = float(self.max_grad_norm)
+            host = [0.0] * CLIP_FLOATS
+            host[CLIP_MAX_NORM], host[CLIP_COEF] = v, 1.0
+            self._clip = [torch.tensor(host, dtype=torch.float32, device=device), v]
+        return self._clip[0]
+
+    def grad_norm(self):
+        """The global gradient norm of the last step, before clipping (clip_grad_norm_'s return value), as a 0-d DEVICE tensor; no host
+        synchronisation.  None while clipping is disabled."""
+        if self.max_grad_norm is None:
+            return None
+        return self._clip_buffer(self.param_groups[0]["params"][0].device)[CLIP_NORM]
+
+    def clip_coef(self):
+        """min(1, max_grad_norm / (norm + 1e-6)) of the last step as a 0-d DEVICE tensor; None while clipping is disabled."""
+        if self.max_grad_norm is None:
+            return None
+        return self._clip_buffer(self.param_groups[0]["params"][0].device)[CLIP_COEF]
+
+    def _clip_begin(self, got, ents, grad2_delta=0):
+        """In front of the first sweep: the sum of squares of every group's g + g2 (with the loss scaler's found-inf check in the same read),
+        then the finisher, which scales every group's device grad_scale.  got: [(params, table)] of the groups that step, ents: their device
+        states.  Returns what _clip_end needs."""
+        import ctypes as C
+        n = len(got)
+        if n > self.MAX_TAIL_GROUPS:
+            raise RuntimeError(f"max_grad_norm serves at most {self.MAX_TAIL_GROUPS} parameter groups, got {n}")
+        dev = ents[0][0].device
+        clip = self._clip_buffer(dev)
+        nblocks = sum(t.nblocks for _, t in got)
+        if self._clip_part is None or self._clip_part.numel() < nblocks or self._clip_part.device != dev:
+            self._clip_part = torch.empty(max(nblocks, 1), dtype=torch.float64, device=dev)
+        part = self._clip_part
+        begin, end, b = [], [], 0
+        for (_, t), ent in zip(got, ents):
+            check(lib().udapose_grad_sumsq(_hip.stream(), ptr(t.ptrs[1]), ptr(t.sizes), ptr(t.blk_t), ptr(t.blk_o), t.nblocks, int(grad2_delta),
+                                           ptr(ent[0]) if self._scaler is not None else None, part.data_ptr() + 8 * b), "grad_sumsq")
+            begin.append(b)
+            b += t.nblocks
+            end.append(b)
+        states = (C.c_void_p * n)(*[e[0].data_ptr() for e in ents])
+        check(lib().udapose_grad_clip(_hip.stream(), ptr(part), (C.c_int * n)(*begin), (C.c_int * n)(*end), n, states, ptr(clip)), "grad_clip")
+        return n, states
+
+    def _clip_end(self, tok):
+        """Behind the last sweep (and in front of the scaler update, which refreshes 1 / S as before): every group's grad_scale back."""
+        check(lib().udapose_grad_clip_restore(_hip.stream(), tok[0], tok[1], ptr(self._clip[0])), "grad_clip_restore")
+
+    def _clip_step(self):
+        """step() with clipping on: the norm over every group that has a gradient, before the first group's sweep.  Returns (token, index of
+        the last such group) or None when no group has a gradient."""
+        got, ents, last = [], [], None
+        for gi, group in enumerate(self.param_groups):
+            g = self._gather(gi, group)
+            if g is not None:
+                got.append(g)
+                ents.append(self._dev_state(gi, group, g[0][0].device))
+                last = gi
+        if not got:
+            return None
+        self._clip_buffer(ents[0][0].device)
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_hyper()
+        return self._clip_begin(got, ents), last
+
     # ------------------------------------------------------------------ loss scaling (fp16)
     def loss_scale(self):
         """The current loss scale as a 0-d DEVICE tensor (1.0 without dynamic scaling); no host synchronisation."""
@@ -112,7 +218,7 @@ class _FusedBase(torch.optim.Optimizer):
     def _pre_sweep(self, t, ent, grad2_delta=0):
         """found-inf sweep of the loss scaler; grad2_delta: byte distance to a second per-pass gradient buffer whose sum is still pending
         (the fused tail adds it itself): the check then looks at g + g2."""
-        if self._scaler is not None:
+        if self._scaler is not None and self.max_grad_norm is None:        # (with clipping the sum-of-squares sweep has checked already)
             check(lib().udapose_grad_scaler_check2(_hip.stream(), ptr(t.ptrs[1]), ptr(t.sizes), ptr(t.blk_t), ptr(t.blk_o), t.nblocks, ptr(ent[0]),
                                                    int(grad2_delta)), "grad_scaler_check")
 
@@ -124,7 +230,11 @@ class _FusedBase(torch.optim.Optimizer):
 
     def sync_hyper(self):
         """Upload lr / grad_scale of every group whose host value changed since the last upload (stream-ordered 8-byte copy;
-        call before replaying a captured step)."""
+        call before replaying a captured step); likewise max_grad_norm."""
+        if self._clip is not None and self.max_grad_norm is not None and float(self.max_grad_norm) != self._clip[1]:
+            v = float(self.max_grad_norm)
+            self._clip[0][CLIP_MAX_NORM:CLIP_MAX_NORM + 1].copy_(torch.tensor([v], dtype=torch.float32), non_blocking=True)
+            self._clip[1] = v
         for gi, group in enumerate(self.param_groups):
             ent = self._dev.get(gi)
             if ent is None:
@@ -214,17 +324,24 @@ class _FusedBase(torch.optim.Optimizer):
         _, pa_s, ga, ma, va, pa_t, _, states = cache
         for group in groups:
             group["step"] = group.get("step", 0) + 1
+        clipping = self.max_grad_norm is not None
+        if clipping:
+            self._clip_buffer(ps[0].device)
         if not torch.cuda.is_current_stream_capturing():
             self.sync_hyper()
         # a pending sum of the two passes' gradient buffers is taken in the sweep itself (no separate axpy over 220 MB) - and by the loss
         # scaler's inf / nan check in front of it, which looks at g + g2 (round 4: the fp16 step used to force the sum first)
         delta = student.pending_grad_sum(take=True) if hasattr(student, "pending_grad_sum") else 0
+        # clipping: the norm of g + g2 over every group (and the found-inf check) in front of the sweep, the grad_scales back behind it
+        clip = self._clip_begin(got, ents, delta) if clipping else None
         self._pre_sweep(got[0][1], ents[0], delta)         # (loss scaling: one group)
         b1, b2, eps, nesterov = self._tail_hyper(groups[0])
         wds = (C.c_float * len(groups))(*[float(g["weight_decay"]) for g in groups])
         check(hd_s.L.udapose_net_fused_update_groups(hd_s.h, hd_t.h, _hip.stream(), self._tail_kind, pa_s, ga, ma, pa_t, ptr(hd_s.wpack),
                                                      ptr(hd_t.wpack), b1, b2, eps, nesterov, len(groups), states, wds, float(ema.alpha),
                                                      float(1.0 - ema.alpha), 1, int(delta)), "net_fused_update_groups")
+        if clip is not None:
+            self._clip_end(clip)
         return self._tail_finish(student, teacher, hd_s, hd_t, ps, tps, t_split, ents[0])
 
     def _tail_finish(self, student, teacher, hd_s, hd_t, ps, tps, t_split, ent):
@@ -255,7 +372,11 @@ class _FusedBase(torch.optim.Optimizer):
         (GraphedTrainStep), which hold raw pointers to them, go on working on the restored state."""
         old_state = {p: dict(st) for p, st in self.state.items()}
         old_dev = dict(self._dev)
+        max_norm = self.max_grad_norm
         super().load_state_dict(state_dict)
+        for group in self.param_groups:             # (a checkpoint from before max_grad_norm existed keeps the current setting)
+            group.setdefault("max_grad_norm", max_norm)
+        self.max_grad_norm = self.param_groups[0]["max_grad_norm"]
         for group in self.param_groups:
             if "step" not in group or group["step"] is None:
                 # torch.optim.Adam / SGD checkpoints keep `step` per parameter (or not at all)
@@ -298,15 +419,17 @@ class FusedAdam(_FusedBase):
         return float(b1), float(b2), float(group["eps"]), 0
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, dynamic_loss_scale=False,
-                 init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+                 init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, max_grad_norm=None):
         scaler = dict(init_scale=init_scale, growth_factor=growth_factor, backoff_factor=backoff_factor,
                       growth_interval=growth_interval) if dynamic_loss_scale else None
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, step=0), scaler)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, step=0,
+                                      max_grad_norm=_max_norm(max_grad_norm)), scaler)
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         capturing = torch.cuda.is_current_stream_capturing()
+        clip = self._clip_step() if self.max_grad_norm is not None else None       # (the norm over every group, before the first sweep)
         for gi, group in enumerate(self.param_groups):
             got = self._gather(gi, group)
             if got is None:
@@ -322,6 +445,8 @@ class FusedAdam(_FusedBase):
                                            ptr(t.blk_o), t.nblocks, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                                            float(group["weight_decay"]), int(group["step"]), float(group.get("grad_scale", 1.0)), ptr(ent[0])),
                   "adam_multi")
+            if clip is not None and gi == clip[1]:
+                self._clip_end(clip[0])
             self._post_sweep(ent)
             _bump_versions(ps)
         return loss
@@ -337,16 +462,17 @@ class FusedSGD(_FusedBase):
         return float(group["momentum"]), 0.0, 0.0, int(bool(group["nesterov"]))
 
     def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, nesterov=False, grad_scale=1.0, dynamic_loss_scale=False,
-                 init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+                 init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, max_grad_norm=None):
         scaler = dict(init_scale=init_scale, growth_factor=growth_factor, backoff_factor=backoff_factor,
                       growth_interval=growth_interval) if dynamic_loss_scale else None
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov, grad_scale=grad_scale, step=0),
-                         scaler)
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov, grad_scale=grad_scale, step=0,
+                                      max_grad_norm=_max_norm(max_grad_norm)), scaler)
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         capturing = torch.cuda.is_current_stream_capturing()
+        clip = self._clip_step() if self.max_grad_norm is not None else None       # (the norm over every group, before the first sweep)
         for gi, group in enumerate(self.param_groups):
             got = self._gather(gi, group)
             if got is None:
@@ -361,6 +487,8 @@ class FusedSGD(_FusedBase):
                                           t.nblocks, float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]),
                                           int(group["nesterov"]), int(group["step"] == 1), float(group.get("grad_scale", 1.0)), ptr(ent[0])),
                   "sgd_multi")
+            if clip is not None and gi == clip[1]:
+                self._clip_end(clip[0])
             self._post_sweep(ent)
             _bump_versions(ps)
         return loss
