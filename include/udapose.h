@@ -643,6 +643,28 @@ int udapose_adain_split(void* stream, const void* content, const void* style, vo
 int udapose_adain_alpha_dev(void* stream, const void* content, const void* style, void* out, int N, int HWc, int HWs, int C, float eps,
                             const float* alpha_dev, float* stats_out, int is_f32);
 
+/* ---------------------------------------------------------------- Fourier-domain style transfer (FDA, Yang & Soatto, CVPR 2020)
+ * A style bridge without weights: the content image keeps its phase and takes the style image's amplitude on the lowest spatial frequencies,
+ * |u|, |v| <= b.  fp32 throughout, identical in both builds.  A plane is one (n, c) channel of a contiguous NCHW fp32 tensor.
+ * udapose_fda_spectrum: spec [planes][2b+1][b+1][2] = (re, im) of G[u, v] = sum_y sum_x x[y, x] exp(-2 pi i (u y / H + v x / W)), row u + b,
+ * u = -b .. b, v = 0 .. b (real input: the other half is the conjugate).  Phases are reduced exactly in integers and looked up in tables that
+ * are rounded once from fp64; sums run in a fixed order without atomics (two runs agree to the bit; a plane's result does not depend on the
+ * other planes of the call).  ws: udapose_fda_ws_bytes(planes, H, W, b) bytes, 8-byte aligned (< 0: these sizes are refused).
+ * udapose_fda_apply: out = content + IDFT2(dF), dF[u, v] = alpha (|Gs| - |Gc|) Gc / |Gc| on the window (Gc = spec_c, Gs = spec_s; Gc == 0: the
+ * phase is 1 + 0i), then the optional per-channel clamp max(min(out, hi[c]), lo[c]) (lo, hi [C]: both or neither), c = plane % C.  alpha_dev
+ * (one float on the device) overrides alpha when non-null.  alpha == 0, or spec_s bit-equal to spec_c: out is the clamped content bit for bit.
+ * mean, std [C] (both or neither): the planes hold (raw - mean[c]) / std[c]; the DC coefficient's amplitude and phase are then those of the raw
+ * image, std[c] G[0, 0] + mean[c] H W, and its dF is divided by std[c] - FDA of the raw images, in normalised units.
+ * Refused before any launch, nothing written: UDAPOSE_ERR_ARG for a null pointer, planes, C, H or W <= 0, planes % C != 0, b < 0 or
+ * 2b + 1 > min(H, W) (the window would reach the Nyquist row); UDAPOSE_ERR_UNSUPPORTED for b > UDAPOSE_FDA_MAX_B or H or W >
+ * UDAPOSE_FDA_MAX_DIM (the window, a work-group's 32 rows of row coefficients and both phase tables live in 150 KiB of LDS). */
+#define UDAPOSE_FDA_MAX_B 63
+#define UDAPOSE_FDA_MAX_DIM 4096
+long long udapose_fda_ws_bytes(int planes, int H, int W, int b);
+int udapose_fda_spectrum(void* stream, const float* x, int planes, int H, int W, int b, void* ws, float* spec);
+int udapose_fda_apply(void* stream, const float* content, const float* spec_c, const float* spec_s, float* out, int planes, int C, int H, int W, int b,
+                      float alpha, const float* alpha_dev, const float* lo, const float* hi, const float* mean, const float* std);
+
 /* ---------------------------------------------------------------- AdaIN decoder training (reference adain/net.py:102-162, adain/train/)
  * The backward of the style network's step on NHWC tensors of the library's element type, fp32 accumulation.  Reflection-padded 3x3
  * stride-1 convolutions (desc: reflect = 1, pad = 1, K = 3, optional upsample; Ci and Co multiples of 64 - zero-pad the 3-channel end

@@ -31,6 +31,7 @@ ALIASES = {
     "lib.models.resnet": _PKG + ".lib.models.resnet",
     "lib.models.loss": _PKG + ".lib.models.loss",
     "lib.models.Style_net": _PKG + ".lib.models.Style_net",
+    "lib.models.fda": _PKG + ".lib.models.fda",
     "lib.keypoint_detection": _PKG + ".lib.keypoint_detection",
     "utils": _PKG + ".utils",
 }

@@ -159,6 +159,9 @@ _SIGS = {
     "udapose_adain": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, vp]),
     "udapose_adain_f32": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, vp]),
     "udapose_adain_alpha_dev": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, ci]),
+    "udapose_fda_ws_bytes": (ll, [ci, ci, ci, ci]),
+    "udapose_fda_spectrum": (ci, [vp, vp, ci, ci, ci, ci, vp, vp]),
+    "udapose_fda_apply": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp]),
     "udapose_patch_paste": (ci, [vp, vp, vp, ci, ci, ci, ci, ci]),
     "udapose_occlusion_pick": (ci, [vp, vp, vp, vp, ci, ci, ci, cd, ci, cf, cf, ci, vp, vp]),
     "udapose_select_rows": (ci, [vp, vp, vp, vp, vp, ci, sz]),

@@ -486,6 +486,14 @@ int udapose_adain_alpha_dev(void* stream, const void* c, const void* s, void* ou
     if (is_f32) return adain_launch_f32(S(stream), (const float*)c, (const float*)s, (float*)out, N, HWc, HWs, C, eps, 1.f, alpha_dev, stats_out);
     return adain_launch(S(stream), CB16(c), CB16(s), B16(out), N, HWc, HWs, C, eps, 1.f, alpha_dev, stats_out);
 }
+long long udapose_fda_ws_bytes(int planes, int H, int W, int b) { return fda_ws_bytes(planes, H, W, b); }
+int udapose_fda_spectrum(void* stream, const float* x, int planes, int H, int W, int b, void* ws, float* spec) {
+    return fda_spectrum(S(stream), x, planes, H, W, b, ws, spec);
+}
+int udapose_fda_apply(void* stream, const float* content, const float* spec_c, const float* spec_s, float* out, int planes, int C, int H, int W, int b,
+                      float alpha, const float* alpha_dev, const float* lo, const float* hi, const float* mean, const float* std) {
+    return fda_apply(S(stream), content, spec_c, spec_s, out, planes, C, H, W, b, alpha, alpha_dev, lo, hi, mean, std);
+}
 int udapose_adain_f32(void* stream, const float* c, const float* s, float* out, int N, int HWc, int HWs, int C, float eps, float alpha,
                       float* stats_out) {
     return adain_launch_f32(S(stream), c, s, out, N, HWc, HWs, C, eps, alpha, nullptr, stats_out);

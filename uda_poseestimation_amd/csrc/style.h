@@ -1,4 +1,4 @@
-// Host launchers of the style network: AdaIN and the decoder's training step.
+// Host launchers of the style bridges: AdaIN, the decoder's training step, and Fourier-domain transfer (FDA).
 #pragma once
 #include "conv_plan.h"
 
@@ -24,3 +24,8 @@ int bias_grad(hipStream_t s, const elem_t* dy, float* db, long long M, int C, in
 size_t feat_mse_ws_bytes();
 int feat_mse_fwd(hipStream_t s, const elem_t* a, const elem_t* b, long long n, float* out, void* ws);
 int style_stat_loss(hipStream_t s, const float* stats, int R, float* out, int accumulate);
+// fda.hip
+long long fda_ws_bytes(int planes, int H, int W, int b);
+int fda_spectrum(hipStream_t s, const float* x, int planes, int H, int W, int b, void* ws, float* spec);
+int fda_apply(hipStream_t s, const float* content, const float* spec_c, const float* spec_s, float* out, int planes, int C, int H, int W, int b, float alpha,
+              const float* alpha_dev, const float* lo, const float* hi, const float* mean, const float* stdv);

@@ -402,6 +402,16 @@ class MeanTeacherTrainer:
         x_s_ori, x_t_teas_ori = x_s, list(x_t_teas)
         net = getattr(self.style_net, "module", self.style_net)          # (a single-device DataParallel wrap, as in the reference)
         with torch.no_grad():
+            if hasattr(net, "spectrum") and hasattr(net, "transfer"):
+                # a Fourier-domain net (lib.models.fda.FDANet): every batch's low-frequency spectrum is taken ONCE, from the original images
+                if a_s2t is not None or a_t2s is not None:
+                    sp_s = net.spectrum(x_s_ori)
+                    sp_ts = [net.spectrum(x_t) for x_t in (x_t_teas_ori if a_t2s is not None else x_t_teas_ori[:1])]
+                if a_s2t is not None:
+                    x_s = net.transfer(x_s_ori, sp_s, sp_ts[0], a_s2t, clamp=self.recover)
+                if a_t2s is not None:
+                    x_t_teas = [net.transfer(x_t, sp_t, sp_s, a_t2s, clamp=self.recover) for x_t, sp_t in zip(x_t_teas_ori, sp_ts)]
+                return x_s, x_t_teas
             if hasattr(net, "encode_features") and not getattr(net, "compute_losses", False):
                 # both directions transfer between the same batches: every image is encoded ONCE (the reference's two
                 # style_net(...) calls encode x_s and x_t twice each; same kernels, same inputs - bit-identical results)
@@ -1107,10 +1117,24 @@ class GraphedTrainStep:
 
     def _style_pass(self, which):
         """"enc": relu4_1 of both ORIGINAL batches into static feature buffers (each image is encoded once per step, whichever
-        directions are drawn); "s2t" / "t2s": AdaIN + decoder of one direction from those features into the main graph's input buffer."""
+        directions are drawn); "s2t" / "t2s": AdaIN + decoder of one direction from those features into the main graph's input buffer.
+        A net with spectrum() / transfer() (FDANet) keeps spectra where the AdaIN net keeps features."""
         st, t = self.static, self.t
         net = getattr(t.style_net, "module", t.style_net)
         with torch.no_grad():
+            if hasattr(net, "spectrum") and hasattr(net, "transfer"):
+                # a Fourier-domain net: "enc" = both batches' spectra into static buffers, a direction = one apply launch into the input buffer
+                if which == "enc":
+                    if "sp_s" not in st:
+                        st["sp_s"], st["sp_t"] = net.spectrum(st["x_s"]), net.spectrum(st["x_t_tea"])
+                    else:
+                        net.spectrum(st["x_s"], out=st["sp_s"])
+                        net.spectrum(st["x_t_tea"], out=st["sp_t"])
+                elif which == "s2t":
+                    net.transfer(st["x_s"], st["sp_s"], st["sp_t"], st["alpha_s2t"], clamp=t.recover, out=st["x_s_in"])
+                else:
+                    net.transfer(st["x_t_tea"], st["sp_t"], st["sp_s"], st["alpha_t2s"], clamp=t.recover, out=st["x_t_tea_in"])
+                return
             if which == "enc":
                 f_s, f_t = net.encode_features(st["x_s"]), net.encode_features(st["x_t_tea"])
                 if "f_s" not in st:
