@@ -515,6 +515,32 @@ int udapose_refine_decode(void* stream, const float* hm, int R, int H, int W, in
 /* confidence mask (train_human.py:427-430): thr = k-th smallest of act[n]; mask[i] = (tea_mask[i]*act_local[i]) > thr */
 int udapose_kth_mask(void* stream, const float* act, const float* tea_mask, int n, int k, float* thr_out, unsigned char* mask,
                      const float* act_local, int n_local);
+/* ---- joint selection by an order statistic over [N,K] rows (csrc/select.hip).  One launch each, sums in double in a fixed order, no
+ * atomics on global memory: capturable, and two calls give the same bits.
+ * udapose_topk_select: top-k mining over the per-(n,k) loss rows of udapose_joints_mse_fwd (null mean_out) or udapose_cons_loss_fwd.
+ *   Per sample, joint j is BETTER than joint i when rows[j] > rows[i] (largest != 0; < otherwise) or the two are equal and j < i; values
+ *   order as torch.kthvalue orders them (NaN is the largest).  rank(i) = the number of candidates better than i, sel[n*K+i] = rank < topk.
+ *   A row whose factor is zero (wfac[r] == 0 or mfac[r] == 0; either table may be null) is no candidate when largest == 0 and always gets
+ *   sel = 0, in either direction: with largest != 0 it keeps its place in the order, so fewer than topk joints may be selected.  The
+ *   divisor stays topk:  sample[n] = (sum of the selected rows, in joint order, in double) / topk;
+ *                        mean_out[0] = (sum_n sample[n], in sample order, in double) / N   (null: not written).
+ *   K > 64: UDAPOSE_ERR_UNSUPPORTED (a wave holds a sample, a lane a joint).  topk outside 1 ... K, N < 1, N*K > 1 << 22 or a null rows /
+ *   sel / sample: UDAPOSE_ERR_ARG.  On any refusal nothing is launched and nothing is written.
+ * udapose_topk_sqdiff_bwd: da = gscale[0] * c * w[r] * (a - b) / (HW * topk * N) on the rows with sel != 0 and 0 elsewhere; c = 1 for the
+ *   0.5 * square rows of JointsMSE (half != 0), 2 for the plain squares of ConsLoss (half == 0); w may be null.  The sweep of
+ *   udapose_joints_mse_bwd with sel as its mask.
+ * udapose_joint_kth_mask: for every joint j, thr_out[j] = the k-th smallest (1-indexed) of the n_pool values pool[i*K + j], and
+ *   mask[i*K + j] = (tea_mask * act_local)[i*K + j] > thr_out[j] for the n_local rows of act_local (tea_mask may be null).  One work-group per
+ *   joint, the radix select of udapose_kth_mask; NaN as there.  k < 1, k > n_pool, K < 1, a null pointer or more than 1 << 22 values:
+ *   UDAPOSE_ERR_ARG.
+ * udapose_thr_mask: mask[i] = (tea_mask[i] * act[i]) > thr_dev[0], i < n; the threshold is read on the device. */
+int udapose_topk_select(void* stream, const float* rows, const float* wfac, const unsigned char* mfac, int N, int K, int topk, int largest,
+                        unsigned char* sel, float* sample, float* mean_out);
+int udapose_topk_sqdiff_bwd(void* stream, const float* a, const float* b, const float* w, const unsigned char* sel, const float* gscale, int N,
+                            int K, int HW, int topk, int half, float* da);
+int udapose_joint_kth_mask(void* stream, const float* pool, int n_pool, int K, int k, const float* tea_mask, const float* act_local,
+                           int n_local, float* thr_out, unsigned char* mask);
+int udapose_thr_mask(void* stream, const float* act, const float* tea_mask, size_t n, const float* thr_dev, unsigned char* mask);
 /* PCK (lib/keypoint_detection.py:40-94) from decoded coordinates [B,K,2]; acc[K], avg_cnt[2] = (avg_acc, cnt) */
 int udapose_pck(void* stream, const float* pred_xy, const float* gt_xy, int B, int K, float norm_x, float norm_y, float thr, float* acc,
                 float* avg_cnt);

@@ -148,6 +148,10 @@ _SIGS = {
     "udapose_flip_merge": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
     "udapose_refine_decode": (ci, [vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, vp]),
     "udapose_kth_mask": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, ci]),
+    "udapose_topk_select": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
+    "udapose_topk_sqdiff_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "udapose_joint_kth_mask": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, vp, vp]),
+    "udapose_thr_mask": (ci, [vp, vp, vp, sz, vp, vp]),
     "udapose_pck": (ci, [vp, vp, vp, ci, ci, cf, cf, cf, vp, vp]),
     "udapose_multi_chunk": (ci, []),
     "udapose_ema_multi": (ci, [vp, vp, vp, vp, vp, vp, ci, cf, cf]),

@@ -427,6 +427,21 @@ int udapose_kth_mask(void* stream, const float* act, const float* tm, int n, int
                      int n_local) {
     return hm_kth_mask(S(stream), act, tm, n, k, thr_out, mask, act_local, n_local);
 }
+int udapose_topk_select(void* stream, const float* rows, const float* wfac, const unsigned char* mfac, int N, int K, int topk, int largest,
+                        unsigned char* sel, float* sample, float* mean_out) {
+    return sel_topk(S(stream), rows, wfac, mfac, N, K, topk, largest, sel, sample, mean_out);
+}
+int udapose_topk_sqdiff_bwd(void* stream, const float* a, const float* b, const float* w, const unsigned char* sel, const float* gscale, int N,
+                            int K, int HW, int topk, int half, float* da) {
+    return sel_topk_sqdiff_bwd(S(stream), a, b, w, sel, gscale, N, K, HW, topk, half, da);
+}
+int udapose_joint_kth_mask(void* stream, const float* pool, int n_pool, int K, int k, const float* tm, const float* act_local, int n_local,
+                           float* thr_out, unsigned char* mask) {
+    return sel_joint_kth_mask(S(stream), pool, n_pool, K, k, tm, act_local, n_local, thr_out, mask);
+}
+int udapose_thr_mask(void* stream, const float* act, const float* tm, size_t n, const float* thr_dev, unsigned char* mask) {
+    return sel_thr_mask(S(stream), act, tm, n, thr_dev, mask);
+}
 int udapose_pck(void* stream, const float* pred, const float* gt, int B, int K, float nx, float ny, float thr, float* acc, float* avg_cnt) {
     return hm_pck(S(stream), pred, gt, B, K, nx, ny, thr, acc, avg_cnt);
 }

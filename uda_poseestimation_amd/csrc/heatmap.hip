@@ -2,6 +2,7 @@
 // "rectify" stamping, k-th value confidence mask, PCK.  Pure HBM sweeps: one pass over each operand, one block per
 // (b,k) row where a per-row result is needed.  Deterministic (no atomics).
 #include "losses.h"
+#include "kth_select.h"
 
 namespace {
 constexpr int TPB = 256;
@@ -104,17 +105,7 @@ __global__ void sqdiff_bwd_scalar_k(const float* __restrict__ a, const float* __
     }
 }
 
-// (hm_better, the arg-max order: common.h)
-// order-preserving float -> uint32 key (NaN -> 0xffffffff, the largest: torch.kthvalue's order)
-__device__ __forceinline__ unsigned int hm_key(float v) {
-    if (v != v) return 0xffffffffu;
-    const unsigned int b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float hm_unkey(unsigned int k) {
-    if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+// (hm_better, the arg-max order: common.h; hm_key / hm_unkey, the k-th value order: kth_select.h)
 
 // per row: max value, first flat arg-max, (x,y) zeroed when max <= 0  (utils.py:54-75 / keypoint_detection.py:9-37);
 // optionally stamps the rectify patch (utils.py:77-109) into out (full row written: zeros elsewhere).
@@ -165,52 +156,14 @@ __global__ void argmax_rectify_k(const float* __restrict__ hm, int H, int W, flo
     }
 }
 
-// k-th smallest (1-indexed) of n values, then mask[i] = (tm[i]*act[i]) > thr  (train_human.py:429-430).
-// MSB-first radix select in ONE work-group: 4 passes of 8 bits, each a 256-bin LDS histogram of the keys that still match
-// the prefix found so far, then a scan of the bins for the one that holds rank k.  O(n) per pass (the previous rank-count
-// form was O(n^2): 23 us at n = 512, ~0.7 ms at the n = 4096 of an 8-rank global batch); n = 4096 costs 16 key loads per
-// thread in all.  Values are read from L2 each pass (n <= 65536 floats = 256 KiB).  NaN orders as the largest value and a
-// NaN threshold gives an all-false mask, exactly like torch.kthvalue + `>`.
+// k-th smallest (1-indexed) of n values, then mask[i] = (tm[i]*act[i]) > thr  (train_human.py:429-430), in ONE work-group:
+// hm_kth_smallest (kth_select.h) over the contiguous vector.  NaN orders as the largest value and a NaN threshold gives an
+// all-false mask, exactly like torch.kthvalue + `>`.
 __global__ void kth_mask_k(const float* __restrict__ act, const float* __restrict__ tm, int n, int k, float* __restrict__ thr_out,
                            unsigned char* __restrict__ mask, const float* __restrict__ act_local, int n_local) {
     __shared__ unsigned int hist[256];
-    __shared__ unsigned int sel_bin, sel_rank;
-    unsigned int prefix = 0, pmask = 0, rank = (unsigned int)(k - 1);     // 0-based rank inside the surviving set
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        for (int i = threadIdx.x; i < 256; i += blockDim.x) hist[i] = 0;
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {
-            const unsigned int key = hm_key(act[i]);
-            if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            // wave 0: each lane owns 4 consecutive bins; exclusive prefix over lanes, then the owner of the rank reports
-            const int b0 = threadIdx.x * 4;
-            const unsigned int c0 = hist[b0], c1 = hist[b0 + 1], c2 = hist[b0 + 2], c3 = hist[b0 + 3];
-            const unsigned int tot = c0 + c1 + c2 + c3;
-            unsigned int incl = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned int up = __shfl_up(incl, o, 64);
-                if ((int)threadIdx.x >= o) incl += up;
-            }
-            const unsigned int excl = incl - tot;
-            if (rank >= excl && rank < incl) {
-                unsigned int r = rank - excl;
-                int b = b0;
-                if (r >= c0) { r -= c0; ++b; if (r >= c1) { r -= c1; ++b; if (r >= c2) { r -= c2; ++b; } } }
-                sel_bin = (unsigned int)b;
-                sel_rank = r;
-            }
-        }
-        __syncthreads();
-        prefix |= sel_bin << shift;
-        pmask |= 255u << shift;
-        rank = sel_rank;
-        __syncthreads();
-    }
-    const float thr = hm_unkey(prefix);
+    __shared__ unsigned int pick[2];
+    const float thr = hm_kth_smallest(act, 1, n, k, hist, pick);
     if (threadIdx.x == 0 && thr_out) thr_out[0] = thr;
     const float* al = act_local ? act_local : act;
     const int nl = act_local ? n_local : n;

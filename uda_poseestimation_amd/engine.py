@@ -233,6 +233,13 @@ class MeanTeacherTrainer:
         # product: the occlusion picks, `activates`, the confidence mask, rectify.  Attributes like the two above, set before a GraphedTrainStep
         # is built.  Data parallel: the tables are the same on every rank; nothing is communicated.
         self.skeleton_prior, self.prior_gamma, self.prior_sigma, self.prior_v3 = None, 2, 2, False
+        # mask_mode: how the teacher's confidences become the consistency mask (utils.confidence_mask) - "global", the reference's single
+        # batch-wide k-th value; "per_joint", a k-th value per joint (the pool is all ranks' samples: the all-gather that exists); "threshold",
+        # confidences above mask_threshold, a fixed or ramped absolute value (no collective).  Attributes like the ones above.  mask_mode is
+        # baked into a captured step; mask_threshold lives in a device scalar that is refreshed outside the graph, beside
+        # stu_optimizer.sync_hyper(), so a captured step follows a host change of it (a curriculum ramp).
+        self.mask_mode, self.mask_threshold = "global", 0.5
+        self._mask_thr = None               # [device scalar, the host value it holds]
         # precision: None keeps what the networks are set to (a new PoseResNet is 'auto': a differentiable forward outside
         # autocast runs bf16, the teacher's no-grad forward the fp32-grade 'f16x2' mode).
         # 'reference' = the reference's own precision mix (train_human.py:346-358,414): the student in fp16 (its autocast dtype)
@@ -318,6 +325,19 @@ class MeanTeacherTrainer:
     @max_grad_norm.setter
     def max_grad_norm(self, v):
         self.stu_optimizer.max_grad_norm = v
+
+    def sync_mask_threshold(self, device=None):
+        """The device scalar that holds mask_threshold, uploaded when the host value changed (a stream-ordered 4-byte copy, like
+        stu_optimizer.sync_hyper()); never inside a capture, whose launches read the scalar."""
+        v = float(self.mask_threshold)
+        if self._mask_thr is None or (device is not None and self._mask_thr[0].device != torch.device(device)):
+            if device is None:
+                device = next(self.student.parameters()).device
+            self._mask_thr = [torch.tensor(v, dtype=torch.float32, device=device), v]
+        elif v != self._mask_thr[1] and not torch.cuda.is_current_stream_capturing():
+            self._mask_thr[0].copy_(torch.tensor(v, dtype=torch.float32), non_blocking=True)
+            self._mask_thr[1] = v
+        return self._mask_thr[0]
 
     def _check_scaler(self):
         """An fp16 student forward needs the loss scaler the optimizer was built with (or the caller's own GradScaler: then build the
@@ -548,7 +568,12 @@ class MeanTeacherTrainer:
         self._check_scaler()
         with torch.no_grad():
             # threshold = k-th value over the GLOBAL batch (all-gather of [N,K] floats when data parallel)
-            tea_mask, _, _ = mt.confidence_mask(st["y_t_tea_recon"], self.mask_ratio, None, gathered_activates, st["activates"])
+            if self.mask_mode == "global":
+                tea_mask, _, mask_thr = mt.confidence_mask(st["y_t_tea_recon"], self.mask_ratio, None, gathered_activates, st["activates"])
+            else:
+                thr_dev = self.sync_mask_threshold(st["activates"].device) if self.mask_mode == "threshold" else None
+                tea_mask, _, mask_thr = mt.confidence_mask(st["y_t_tea_recon"], self.mask_ratio, None, gathered_activates, st["activates"],
+                                                           mode=self.mask_mode, threshold=thr_dev)
             y_t_tea_rect = st["y_t_tea_rect"] if st.get("y_t_tea_rect") is not None else mt.rectify(st["y_t_tea_recon"], sigma=self.sigma)
         loss_c = self.con_criterion(st["y_t_stu_recon"], y_t_tea_rect, tea_mask=tea_mask)
         loss_all = loss_s + self.lambda_c * loss_c
@@ -580,6 +605,8 @@ class MeanTeacherTrainer:
         # (the re-warped heat-maps of both networks are handed out for the parity tests and bench.py's measured parity: references only)
         out = {"loss_all": loss_all.detach(), "loss_s": loss_s.detach(), "loss_c": loss_c.detach(), "y_s": st["y_s"].detach(),
                "tea_mask": tea_mask, "y_t_tea_recon": st["y_t_tea_recon"], "y_t_stu_recon": st["y_t_stu_recon"].detach()}
+        if self.mask_mode != "global":
+            out["mask_thr"] = mask_thr          # ([K] per joint; 0-d, the trainer's device scalar, in "threshold" mode)
         if loss_ent is not None:
             out["loss_ent"] = loss_ent.detach()
         if loss_coral is not None:
@@ -846,6 +873,8 @@ class GraphedTrainStep:
         # hyper-parameters that are kernel ARGUMENTS of the captured launches stay what they were at capture: step() checks
         # them.  (lr / grad_scale are read from device memory and follow the optimizer's param_groups, see optim.py.)
         self._frozen = self._frozen_hyper()
+        if trainer.mask_mode == "threshold":
+            trainer.sync_mask_threshold(dev)        # (the captured mask launch reads this scalar: it exists, and is current, before the capture)
         token = object()
         for m in (trainer.student, trainer.teacher):
             m._capture_token = token            # weight packs: captured once per network, unconditionally (pose_resnet._pack)
@@ -1197,6 +1226,12 @@ class GraphedTrainStep:
                     frozen.append((f"group{gi}.{k}", g[k]))
         # clipping by global norm on / off changes the launches; its value lives on the device and may change freely (sync_hyper)
         frozen.append(("max_grad_norm enabled", getattr(opt, "max_grad_norm", None) is not None))
+        # the mask's mode picks the launch; mask_threshold lives on the device and may change freely (sync_mask_threshold)
+        frozen.append(("mask_mode", str(t.mask_mode)))
+        for name, crit in (("criterion", t.criterion), ("con_criterion", t.con_criterion)):
+            for k in ("topk", "largest"):
+                if hasattr(crit, k):
+                    frozen.append((f"{name}.{k}", getattr(crit, k)))
         return frozen
 
     def prefetch(self, x_s, label_s, weight_s, x_t_stu, x_t_tea):
@@ -1248,6 +1283,8 @@ class GraphedTrainStep:
         self._draw_and_style()
         seg = self._seg_mark            # (profile_segments: an event after each part of the data-parallel step; a no-op otherwise)
         seg("start")
+        if self.t.mask_mode == "threshold":
+            self.t.sync_mask_threshold()         # a curriculum ramp of mask_threshold -> the device scalar the captured mask launch reads
         if self.one_graph:
             self.t.stu_optimizer.sync_hyper()    # lr scheduler / loss scale -> device state read by the captured sweep
         self.g_fb.replay()

@@ -6,6 +6,8 @@ soft-max over the H*W pixels of every (b,k) heat-map fused with the loss, its re
 defined and refuses construction: see its docstring; GramCoralLoss is the same loss through n x n Gram matrices (csrc/coral.hip).
 JointsSoftArgmaxLoss and ConsSoftArgmaxLoss have no counterpart in the reference:
 they are losses on the soft-argmax COORDINATES of the student's heat-maps (csrc/softargmax.hip), a gradient on where the peak is.
+JointsOHKMMSELoss and ConsTopKLoss train only the `topk` joints of every sample that an order statistic over the rows of JointsMSELoss /
+ConsLoss selects (csrc/select.hip: hard key-point mining, small-loss selection).
 Each forward is one sweep over the operands (per-(b,k) row partial + a tiny row reduction), each backward one sweep.
 """
 import warnings
@@ -123,6 +125,117 @@ class ConsLoss(nn.Module):
 
     def forward(self, stu_out, tea_out, valid_mask=None, tea_mask=None):
         return _ConsFn.apply(stu_out, tea_out, tea_mask, valid_mask)
+
+
+# ---------------------------------------------------------------------------------------------- top-k joint mining
+TOPK_MAX_KEYPOINTS = 64     # udapose_topk_select: a wave holds a sample, a lane a joint
+
+
+def _topk_args(x, topk):
+    """(N, K, topk) of a [N,K,...] heat-map batch, or ValueError - before any launch."""
+    if x.dim() < 3:
+        raise ValueError(f"top-k joint mining needs [N, K, ...] heat-maps, got {tuple(x.shape)}")
+    N, K = x.shape[:2]
+    if int(topk) != topk or topk < 1:
+        raise ValueError(f"topk must be an integer >= 1, got {topk!r}")
+    if K > TOPK_MAX_KEYPOINTS:
+        raise ValueError(f"top-k joint mining serves K <= {TOPK_MAX_KEYPOINTS} key points, got {K}")
+    if topk > K:
+        raise ValueError(f"topk = {topk} exceeds the {K} key points of the heat-maps")
+    if N < 1 or x.numel() == 0:
+        raise ValueError(f"top-k joint mining: empty heat-maps {tuple(x.shape)}")
+    return N, K, int(topk)
+
+
+class _TopKSqdiffFn(torch.autograd.Function):
+    """The rows of _JointsMSEFn (cons == False: factor = weight) or _ConsFn (cons == True: factor = mask), then udapose_topk_select over
+    them; backward is the squared-difference sweep with the selection as its mask."""
+
+    @staticmethod
+    def forward(ctx, a, b, factor, topk, largest, cons, reduce_mean, owner):
+        N, K, topk = _topk_args(a, topk)
+        _hip.require_cuda(a, b, factor)
+        R, HW = _rows(a)
+        x, y = _f32c(a), _f32c(b)
+        w = m = None
+        if cons:
+            m = _bytes_mask(factor)
+        elif factor is not None:
+            w = _f32c(factor).reshape(-1)
+        for f, what in ((w, "target_weight"), (m, "tea_mask")):
+            if f is not None and f.numel() != R:
+                raise ValueError(f"{what} must have B*K elements")
+        rows = torch.empty(R, dtype=torch.float32, device=x.device)
+        sel = torch.empty(R, dtype=torch.uint8, device=x.device)
+        sample = torch.empty(N, dtype=torch.float32, device=x.device)
+        mean = torch.empty((), dtype=torch.float32, device=x.device) if reduce_mean else None
+        if cons:
+            check(lib().udapose_cons_loss_fwd(_hip.stream(), ptr(x), ptr(y), ptr(m), R, HW, ptr(rows), None), "cons_loss_fwd")
+        else:
+            check(lib().udapose_joints_mse_fwd(_hip.stream(), ptr(x), ptr(y), ptr(w), R, HW, ptr(rows), None), "joints_mse_fwd")
+        check(lib().udapose_topk_select(_hip.stream(), ptr(rows), ptr(w), ptr(m), N, K, topk, int(bool(largest)), ptr(sel), ptr(sample), ptr(mean)),
+              "topk_select")
+        if owner is not None:
+            owner.last_selection = sel.view(torch.bool).reshape(N, K)       # (the kernel writes 0 / 1: a bool view, not a conversion launch)
+        ctx.save_for_backward(x, y, w if w is not None else torch.empty(0, device=x.device), sel)
+        ctx.has_w, ctx.cons, ctx.topk, ctx.reduce_mean, ctx.shape, ctx.in_dtype = w is not None, cons, topk, reduce_mean, a.shape, a.dtype
+        return mean if reduce_mean else sample
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, w, sel = ctx.saved_tensors
+        if not ctx.reduce_mean:
+            raise NotImplementedError("backward of reduction='none' is not on the hot path")
+        N, K = ctx.shape[:2]
+        R, HW = _rows(x)
+        d = torch.empty_like(x)
+        gs = _gscale(g)
+        check(lib().udapose_topk_sqdiff_bwd(_hip.stream(), ptr(x), ptr(y), ptr(w) if ctx.has_w else None, ptr(sel), ptr(gs), N, K, HW, ctx.topk,
+                                            0 if ctx.cons else 1, ptr(d)), "topk_sqdiff_bwd")
+        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None, None, None, None, None, None
+
+
+class JointsOHKMMSELoss(nn.Module):
+    """Online hard key-point mining over JointsMSELoss's rows (the OHKM loss of the Simple-Baseline code this PoseResNet comes from):
+    mean_n( (1/topk) * sum_{k in top-k of n} 0.5 * w[n,k] * mean_hw((p - g)^2) ), the `topk` joints of every sample with the LARGEST row.
+    The rows are exactly JointsMSELoss(reduction='none')'s, so target_weight enters ONCE, as everywhere in this package; the MSRA code
+    multiplies prediction and target by it before squaring, i.e. squares it - identical for the 0 / 1 weights the data pipeline emits.
+    Ties go to the lower joint index.  A joint of weight 0 keeps its place in the order (its row is 0) and is never selected, so fewer
+    than topk joints may train; the divisor stays topk.  reduction='none' returns the per-sample values [N] (forward only).
+    `last_selection`: the selection of the last forward, a detached bool [N,K] device tensor (for logging; no synchronisation).
+    topk is read at every call and is baked into a captured step's launches: build a new capture to change it."""
+
+    def __init__(self, topk=8, reduction='mean'):
+        super(JointsOHKMMSELoss, self).__init__()
+        if int(topk) != topk or topk < 1:
+            raise ValueError(f"topk must be an integer >= 1, got {topk!r}")
+        self.topk, self.reduction = int(topk), reduction
+        self.last_selection = None
+
+    def forward(self, output, target, target_weight=None):
+        if self.reduction not in ('mean', 'none'):
+            return None         # (as the other classes of this module)
+        return _TopKSqdiffFn.apply(output, target, target_weight, self.topk, True, False, self.reduction == 'mean', self)
+
+
+class ConsTopKLoss(nn.Module):
+    """The same selection over ConsLoss's rows m[n,k] * mean_hw((stu - tea)^2): mean_n( (1/topk) * sum over the selected joints ).
+    largest=True trains the `topk` joints of a sample where student and teacher disagree MOST; largest=False the `topk` where they disagree
+    LEAST among the joints tea_mask admits (small-loss selection for noisy pseudo-labels).  A joint the mask rejects is never selected;
+    fewer than topk joints may train and the divisor stays topk.  Ties go to the lower joint index.  The selection is per (sample, joint):
+    a per-pixel `valid_mask` is refused.  `last_selection` as in JointsOHKMMSELoss; topk and largest are baked into a captured step."""
+
+    def __init__(self, topk=8, largest=True):
+        super(ConsTopKLoss, self).__init__()
+        if int(topk) != topk or topk < 1:
+            raise ValueError(f"topk must be an integer >= 1, got {topk!r}")
+        self.topk, self.largest = int(topk), bool(largest)
+        self.last_selection = None
+
+    def forward(self, stu_out, tea_out, valid_mask=None, tea_mask=None):
+        if valid_mask is not None:
+            raise NotImplementedError("ConsTopKLoss selects (sample, joint) rows: a per-pixel valid_mask is not implemented (use tea_mask)")
+        return _TopKSqdiffFn.apply(stu_out, tea_out, tea_mask, self.topk, self.largest, True, True, self)
 
 
 # ---------------------------------------------------------------------------------------------- the soft-max family

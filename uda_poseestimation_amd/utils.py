@@ -160,10 +160,23 @@ def activations_and_rectify(recon, sigma):
     return act, out.to(recon.dtype)
 
 
-def confidence_mask(recon, mask_ratio, tea_mask=None, gathered_activates=None, activates=None):
+MASK_MODES = ("global", "per_joint", "threshold")
+
+
+def confidence_mask(recon, mask_ratio, tea_mask=None, gathered_activates=None, activates=None, *, mode="global", threshold=None):
     """train_human.py:427-430 without the host round trip: activates = amax_{hw}(recon); thr = k-th smallest with
     k = int(mask_ratio * numel); mask = (tea_mask * activates) > thr.  `gathered_activates` (all ranks' activates,
-    flattened) makes thr the GLOBAL-batch statistic under data parallelism.  Returns (mask bool [B,K], activates [B,K], thr)."""
+    flattened) makes thr the GLOBAL-batch statistic under data parallelism.  Returns (mask bool [B,K], activates [B,K], thr).
+    mode="global" is that, the reference's single batch-wide threshold.  mode="per_joint": one threshold per joint (class-balanced
+    self-training) - thr[j] = the k-th smallest of joint j's confidences over the pool's samples (all ranks' with `gathered_activates`),
+    k = int(mask_ratio * n_pool) >= 1, thr returned as [K].  mode="threshold": mask = (tea_mask * activates) > threshold, a float or a
+    0-d device tensor (read on the device: no synchronisation, and a captured launch follows its value); mask_ratio is ignored."""
+    if mode not in MASK_MODES:
+        raise ValueError(f"confidence_mask: mode {mode!r}: one of {MASK_MODES}")
+    if mode == "threshold" and threshold is None:
+        raise ValueError("confidence_mask: mode='threshold' needs threshold= (a float or a 0-d device tensor)")
+    if mode != "global":
+        return _confidence_mask_select(recon, mask_ratio, tea_mask, gathered_activates, activates, mode, threshold)
     act = heatmap_activations(recon) if activates is None else activates
     B, K = act.shape
     pool = act.reshape(-1) if gathered_activates is None else gathered_activates.detach().float().reshape(-1).contiguous()
@@ -173,6 +186,38 @@ def confidence_mask(recon, mask_ratio, tea_mask=None, gathered_activates=None, a
     tm = None if tea_mask is None else tea_mask.detach().float().contiguous()
     check(lib().udapose_kth_mask(_hip.stream(), ptr(pool), ptr(tm), pool.numel(), k, ptr(thr), ptr(mask), ptr(act), B * K), "kth_mask")
     return mask.view(torch.bool), act, thr        # (the kernel writes 0 / 1: a bool view, not a conversion launch)
+
+
+def _confidence_mask_select(recon, mask_ratio, tea_mask, gathered_activates, activates, mode, threshold):
+    """The per-joint and fixed-threshold forms of confidence_mask (csrc/select.hip): one launch behind the arg-max sweep."""
+    B, K = (activates if activates is not None else recon).shape[:2]
+    if mode == "per_joint":
+        if gathered_activates is not None and gathered_activates.numel() % K:
+            raise ValueError(f"confidence_mask: gathered_activates has {gathered_activates.numel()} elements, no multiple of K = {K}")
+        n_pool = B if gathered_activates is None else gathered_activates.numel() // K
+        k = int(mask_ratio * n_pool)
+        if k < 1 or k > n_pool:
+            raise ValueError(f"confidence_mask(mode='per_joint'): k = int(mask_ratio * n_pool) = int({mask_ratio} * {n_pool}) = {k} is outside "
+                             f"1 ... {n_pool}")
+    elif torch.is_tensor(threshold) and threshold.numel() != 1:
+        raise ValueError(f"confidence_mask: threshold must be a float or a 0-d tensor, got shape {tuple(threshold.shape)}")
+    _hip.require_cuda(recon, tea_mask, gathered_activates, activates, threshold if torch.is_tensor(threshold) else None)
+    act = heatmap_activations(recon) if activates is None else activates.detach().float().contiguous()
+    mask = torch.empty(B, K, dtype=torch.uint8, device=act.device)
+    tm = None if tea_mask is None else tea_mask.detach().float().contiguous()
+    if mode == "per_joint":
+        pool = act if gathered_activates is None else gathered_activates.detach().float().reshape(-1).contiguous()
+        thr = torch.empty(K, dtype=torch.float32, device=act.device)
+        check(lib().udapose_joint_kth_mask(_hip.stream(), ptr(pool), n_pool, K, k, ptr(tm), ptr(act), B, ptr(thr), ptr(mask)), "joint_kth_mask")
+    else:
+        if torch.is_tensor(threshold):
+            thr = threshold.detach().reshape(())
+            if thr.dtype != torch.float32:
+                thr = thr.float()
+        else:
+            thr = torch.full((), float(threshold), dtype=torch.float32, device=act.device)
+        check(lib().udapose_thr_mask(_hip.stream(), ptr(act), ptr(tm), B * K, ptr(thr), ptr(mask)), "thr_mask")
+    return mask.view(torch.bool), act, thr
 
 
 PRIOR_MAX_KEYPOINTS = 64
