@@ -14,7 +14,10 @@ tr = MeanTeacherTrainer(stu, tea, precision="bf16")
 b = synthetic.mean_teacher_batch(32, seed=0)
 g = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in b.items()}
 args = (g["x_s"], g["label_s"], g["weight_s"], g["x_t_stu"], g["x_t_tea"], g["aug_param_stu"], g["aug_param_tea"])
-gs = GraphedTrainStep(tr, *args)
+torch.cuda.synchronize()
+t0 = time.perf_counter()
+gs = GraphedTrainStep(tr, *args)            # (ends in a synchronize of its own)
+print(f"GraphedTrainStep construction (two warm-up steps, capture): {time.perf_counter() - t0:.3f} s")
 for _ in range(20):
     gs.step(*args)
 torch.cuda.synchronize()

@@ -13,6 +13,7 @@ student / teacher replicas; the only collectives are the gradient all-reduce (st
 the per-key-point confidences so that the mask threshold stays the GLOBAL-batch k-th value.  BN statistics stay per
 rank, as with the reference's nn.DataParallel.
 """
+import contextlib
 import numpy as np
 import os
 
@@ -25,6 +26,8 @@ from . import utils as mt
 from . import warp
 from .lib import keypoint_detection as kd
 from .lib.models.loss import ConsLoss, JointsMSELoss
+
+_INPUTS = ("x_s", "label_s", "weight_s", "x_t_stu", "x_t_tea")      # the batch tensors of a step, in call order
 
 
 def _dist_on():
@@ -43,7 +46,7 @@ class GradSync:
 
     def __init__(self, model, comm_dtype="fp32"):
         self.model = model
-        self._work, self._upper, self._cstream = None, None, None
+        self.reset()
         # 'bf16': the buckets travel in bf16 (udapose_comm_*: one rounding per contribution, all-to-all of shards, fp32 accumulation on
         # the shard's owner, the MEAN rounded to bf16 once more for the all-gather of the averaged shards): half the bytes per xGMI
         # link, two bf16 roundings per averaged gradient element.  RCCL backend only.
@@ -52,6 +55,10 @@ class GradSync:
         # timing (bench.py): HIP events around finish() on the current stream = what the step WAITS for communication
         self.profile = False
         self._events = []
+
+    def reset(self):
+        # an exchange in flight: the Work of the suffix's collective, its view, the bf16 exchange's side stream (an aborted capture)
+        self._work, self._upper, self._cstream = None, None, None
 
     def _flat(self):
         flat = getattr(self.model, "_flat_grad", None)
@@ -195,6 +202,50 @@ def gather_activates(act):
     return torch.cat([b.reshape(-1) for b in bufs])
 
 
+class _StyleAdapter:
+    """The three call forms of a style net behind two operations: a batch is SUMMARISED once per step, from its original images, and every
+    transfer is made from two summaries.  FDA (lib.models.fda.FDANet: spectrum / transfer): the low-frequency spectrum.  AdaIN (Style_net.Net:
+    encode_features / transfer_from_features): relu4_1 - the reference's two style_net(...) calls encode each batch twice; same kernels, same
+    inputs, same bits.  Plain (the reference's call, style_net(content, style, alpha, clamp=)[2]): the image itself.
+    ASYMMETRY, kept: the eager step takes the plain call for an AdaIN net whose compute_losses is set; a captured step, whose summaries
+    live in static buffers, ignores that flag and refuses a net that offers neither fast protocol."""
+
+    def __init__(self, style_net, captured=False):
+        self.style_net, self.captured = style_net, captured
+        net = self.net = getattr(style_net, "module", style_net)          # (a single-device DataParallel wrap, as in the reference)
+        self.kind, self.keys = "plain", None           # (keys: the static buffers of a captured step's summaries)
+        if hasattr(net, "spectrum") and hasattr(net, "transfer"):
+            self.kind, self.keys = "fda", ("sp_s", "sp_t")
+        elif hasattr(net, "encode_features") and hasattr(net, "transfer_from_features"):
+            self.kind, self.keys = "adain", ("f_s", "f_t")
+        elif captured:
+            raise TypeError(f"GraphedTrainStep: style_net {type(net).__name__} offers neither spectrum() / transfer() nor encode_features() / "
+                            "transfer_from_features(); a captured style pass needs one of the two protocols")
+
+    @property
+    def form(self):
+        if self.kind == "adain" and not self.captured and getattr(self.net, "compute_losses", False):
+            return "plain"
+        return self.kind
+
+    def summarize(self, img, out=None):
+        if self.form == "fda":
+            return self.net.spectrum(img, out=out)
+        if self.form == "plain":
+            return img
+        f = self.net.encode_features(img)
+        return f if out is None else out.copy_(f)
+
+    def transfer(self, content_img, sum_content, sum_style, alpha, clamp, out=None):
+        if self.form == "fda":
+            return self.net.transfer(content_img, sum_content, sum_style, alpha, clamp=clamp, out=out)
+        if self.form == "plain":
+            g = self.style_net(sum_content, sum_style, alpha, clamp=clamp)[2]
+        else:
+            g = self.net.transfer_from_features(sum_content, sum_style, alpha, clamp=clamp)
+        return g if out is None else out.copy_(g)
+
+
 class MeanTeacherTrainer:
     def __init__(self, student, teacher, lr=1e-4, teacher_alpha=0.999, lambda_c=1.0, mask_ratio=0.5, sigma=2, image_size=256,
                  heatmap_size=64, use_sgd=False, style_net=None, recover=None, s2t_freq=0.5, t2s_freq=0.5, s2t_alpha=(0.0, 1.0),
@@ -249,32 +300,22 @@ class MeanTeacherTrainer:
         #   under the same loss scaling - the gradients are not fp32-grade); teacher and style network as in 'reference'.
         # 'bf16' / 'fp16': student AND teacher in that 16-bit type (BASELINE.json's benched configuration is 'bf16'; the style
         #   network keeps its own setting).
-        # (the networks may arrive wrapped in a single-device nn.DataParallel, as in the reference: attributes go to the modules)
-        stu_m, tea_m = getattr(student, "module", student), getattr(teacher, "module", teacher)
-        if precision in ("reference", "reference_fp32"):
-            # ('reference_fp32': the same mix with the EXACT fp32 MFMA forms for the teacher and the style network - the slow way to the
-            # same numbers, kept for A/B timing of the f16x2 mode)
-            hi = "f16x2" if precision == "reference" else "fp32"
-            stu_m.precision, tea_m.precision = "fp16", hi
-            sn = getattr(style_net, "module", style_net)
-            if sn is not None and hasattr(sn, "precision"):
-                sn.precision = hi
-        elif precision == "strict":
-            stu_m.precision, tea_m.precision = "strict", "f16x2"
-            sn = getattr(style_net, "module", style_net)
-            if sn is not None and hasattr(sn, "precision"):
-                sn.precision = "f16x2"
-        elif precision is not None:
-            stu_m.precision = precision
-            tea_m.precision = precision
+        # ('reference_fp32': the 'reference' mix with the EXACT fp32 MFMA forms for the teacher and the style network - the slow way to the same
+        # numbers, kept for A/B timing of the f16x2 mode)
+        mixes = {"reference": ("fp16", "f16x2", "f16x2"), "reference_fp32": ("fp16", "fp32", "fp32"), "strict": ("strict", "f16x2", "f16x2")}
+        self._style = _StyleAdapter(style_net) if style_net is not None else None       # (unwraps the style net)
+        if precision is not None:
+            student.precision, teacher.precision, style_precision = mixes.get(precision, (precision, precision, None))
+            if style_precision is not None and self._style is not None and hasattr(self._style.net, "precision"):
+                self._style.net.precision = style_precision
         # Loss scaling is decided ONCE, here, from what the student can run: 'fp16', or 'auto' (which resolves to fp16 whenever the step
         # runs under torch.autocast, the reference's call form) get the device-side GradScaler; a scaled bf16 step is exact (powers of
         # two), an unscaled fp16 step underflows silently - _check_scaler() refuses that combination at step time
-        sp = getattr(stu_m, "precision", "bf16")
+        sp = getattr(student, "precision", "bf16")
         scaled = sp in ("fp16", "auto", "strict")       # ('strict': the fp16 backward)
         # the teacher's fp32-grade plans live in the student's library build, so the fused optimizer tail hands both plans to one .so
-        if hasattr(tea_m, "aux_lib_kind"):
-            tea_m.aux_lib_kind = "fp16" if sp in ("fp16", "strict") else "bf16"
+        if hasattr(teacher, "aux_lib_kind"):
+            teacher.aux_lib_kind = "fp16" if sp in ("fp16", "strict") else "bf16"
         sc = dict(dynamic_loss_scale=True, init_scale=loss_scale_init, growth_interval=loss_scale_interval) if scaled else {}
         opt_params = params if params is not None else student.parameters()
         if use_sgd:
@@ -417,37 +458,20 @@ class MeanTeacherTrainer:
         return u.to(device, non_blocking=True) if device is not None else u
 
     def _style_part(self, x_s, x_t_teas):
-        """Bidirectional style transfer of the step's inputs (train_human.py:345-358), both from the ORIGINAL images."""
+        """Bidirectional style transfer of the step's inputs (train_human.py:345-358), both from the ORIGINAL images: each batch is
+        summarised once (_StyleAdapter), and only the first teacher view when t2s was not drawn."""
         a_s2t, a_t2s = self.draw_style_decisions()
-        x_s_ori, x_t_teas_ori = x_s, list(x_t_teas)
-        net = getattr(self.style_net, "module", self.style_net)          # (a single-device DataParallel wrap, as in the reference)
+        if a_s2t is None and a_t2s is None:
+            return x_s, x_t_teas
+        style, out_s, out_ts = self._style, x_s, x_t_teas
         with torch.no_grad():
-            if hasattr(net, "spectrum") and hasattr(net, "transfer"):
-                # a Fourier-domain net (lib.models.fda.FDANet): every batch's low-frequency spectrum is taken ONCE, from the original images
-                if a_s2t is not None or a_t2s is not None:
-                    sp_s = net.spectrum(x_s_ori)
-                    sp_ts = [net.spectrum(x_t) for x_t in (x_t_teas_ori if a_t2s is not None else x_t_teas_ori[:1])]
-                if a_s2t is not None:
-                    x_s = net.transfer(x_s_ori, sp_s, sp_ts[0], a_s2t, clamp=self.recover)
-                if a_t2s is not None:
-                    x_t_teas = [net.transfer(x_t, sp_t, sp_s, a_t2s, clamp=self.recover) for x_t, sp_t in zip(x_t_teas_ori, sp_ts)]
-                return x_s, x_t_teas
-            if hasattr(net, "encode_features") and not getattr(net, "compute_losses", False):
-                # both directions transfer between the same batches: every image is encoded ONCE (the reference's two
-                # style_net(...) calls encode x_s and x_t twice each; same kernels, same inputs - bit-identical results)
-                if a_s2t is not None or a_t2s is not None:
-                    f_s = net.encode_features(x_s_ori)
-                    f_ts = [net.encode_features(x_t) for x_t in (x_t_teas_ori if a_t2s is not None else x_t_teas_ori[:1])]
-                if a_s2t is not None:
-                    x_s = net.transfer_from_features(f_s, f_ts[0], a_s2t, clamp=self.recover)
-                if a_t2s is not None:
-                    x_t_teas = [net.transfer_from_features(f_t, f_s, a_t2s, clamp=self.recover) for f_t in f_ts]
-                return x_s, x_t_teas
+            sum_s = style.summarize(x_s)
+            sum_ts = [style.summarize(x_t) for x_t in (x_t_teas if a_t2s is not None else x_t_teas[:1])]
             if a_s2t is not None:
-                x_s = self.style_net(x_s_ori, x_t_teas_ori[0], a_s2t, clamp=self.recover)[2]
+                out_s = style.transfer(x_s, sum_s, sum_ts[0], a_s2t, self.recover)
             if a_t2s is not None:
-                x_t_teas = [self.style_net(x_t, x_s_ori, a_t2s, clamp=self.recover)[2] for x_t in x_t_teas_ori]
-        return x_s, x_t_teas
+                out_ts = [style.transfer(x_t, sum_t, sum_s, a_t2s, self.recover) for x_t, sum_t in zip(x_t_teas, sum_ts)]
+        return out_s, out_ts
 
     def _forward_part(self, x_s, label_s, weight_s, x_t_stu, x_t_teas, theta_stu, thetas_tea):
         """All forwards of the step after the style pass (no host reads unless the occlusion draws on the host: capturable
@@ -568,12 +592,9 @@ class MeanTeacherTrainer:
         self._check_scaler()
         with torch.no_grad():
             # threshold = k-th value over the GLOBAL batch (all-gather of [N,K] floats when data parallel)
-            if self.mask_mode == "global":
-                tea_mask, _, mask_thr = mt.confidence_mask(st["y_t_tea_recon"], self.mask_ratio, None, gathered_activates, st["activates"])
-            else:
-                thr_dev = self.sync_mask_threshold(st["activates"].device) if self.mask_mode == "threshold" else None
-                tea_mask, _, mask_thr = mt.confidence_mask(st["y_t_tea_recon"], self.mask_ratio, None, gathered_activates, st["activates"],
-                                                           mode=self.mask_mode, threshold=thr_dev)
+            thr_dev = self.sync_mask_threshold(st["activates"].device) if self.mask_mode == "threshold" else None
+            tea_mask, _, mask_thr = mt.confidence_mask(st["y_t_tea_recon"], self.mask_ratio, None, gathered_activates, st["activates"],
+                                                       mode=self.mask_mode, threshold=thr_dev)
             y_t_tea_rect = st["y_t_tea_rect"] if st.get("y_t_tea_rect") is not None else mt.rectify(st["y_t_tea_recon"], sigma=self.sigma)
         loss_c = self.con_criterion(st["y_t_stu_recon"], y_t_tea_rect, tea_mask=tea_mask)
         loss_all = loss_s + self.lambda_c * loss_c
@@ -770,37 +791,47 @@ class GraphedTrainStep:
         # metrics: the captured step also decodes y_s and computes PCK@0.05 against label_s on the device (the reference's per-iteration
         # `accuracy(y_s, label_s)`, train_human.py:443) and gathers the losses + PCK into ONE small device vector: step_async() reads
         # it back one step late through a pinned double buffer, so a loop that logs every iteration never drains the device
+        self.t = trainer
         self.metrics = bool(metrics)
-        self._mvec, self._mpin, self._mev, self._mi, self._mk, self._macc = None, None, [None, None], 0, 0, None
-        self._mextra = []
-        self.styled = trainer.style_net is not None
-        self.occl = trainer.occlude_rate > -1
-        if self.occl and not trainer.device_occlusion:
+        self._mvec, self._mpin, self._mev, self._mi, self._mk, self._macc, self._mextra = None, None, [None, None], 0, 0, None, []
+        # other threads (the RCCL watchdog of torch.distributed) may touch the runtime while this thread captures
+        self._mode = "thread_local" if _dist_on() else "global"
+        self._refuse_uncapturable(x_t_stu)
+        self._allocate_static(x_s, label_s, weight_s, x_t_stu, x_t_tea, aug_param_stu, aug_param_tea)
+        self._warm_up(warmup)
+        self._settle_watchdog(capture_comm)
+        self._capture_style()
+        self._decide_form(split, capture_comm)
+        if self.split or not self._capture_whole():
+            self._capture_split()
+        self._capture_update()
+        self._after_capture()
+
+    def _refuse_uncapturable(self, x_t_stu):
+        t = self.t
+        self._style = _StyleAdapter(t.style_net, captured=True) if t.style_net is not None else None     # (TypeError: a net with the plain call only)
+        self.styled, self.occl = self._style is not None, t.occlude_rate > -1
+        if self.occl and not t.device_occlusion:
             raise RuntimeError("GraphedTrainStep with occlusion needs trainer.device_occlusion = True (the reference's host draws read "
                                "the confidences back every step, which a captured step cannot do)")
-        if trainer.warp_mode == "bilinear":
-            hm = [int(round(v / trainer.ratio)) for v in x_t_stu.shape[-2:]]
+        if t.warp_mode == "bilinear":
+            hm = [int(round(v / t.ratio)) for v in x_t_stu.shape[-2:]]
             if not warp.bilinear_fits_lds(*hm):
                 raise RuntimeError(f"GraphedTrainStep with warp_mode='bilinear': {hm[0]}x{hm[1]} heat-map planes exceed the re-warp's "
                                    f"{warp.BILINEAR_LDS_BYTES // 1024} KB LDS budget; the stage-by-stage form allocates scratch memory, which a "
                                    "captured step must not do - use the eager train_step for heat-maps this large")
-        self.t = trainer
+
+    def _allocate_static(self, x_s, label_s, weight_s, x_t_stu, x_t_tea, aug_param_stu, aug_param_tea):
         self._stage, self._have_staged = None, False
-        dev = x_s.device
-        n = x_s.shape[0]
+        dev, n = x_s.device, x_s.shape[0]
         self.n = n
         # The re-warp matrices are computed INSIDE the captured step (udapose_recon_thetas, double precision) from the batch's raw
         # aug_param values: per step the host packs 2 x N x 6 doubles into a pinned buffer and issues one asynchronous copy.
-        self.static = {"x_s": x_s.clone(), "label_s": label_s.clone(), "weight_s": weight_s.clone(), "x_t_stu": x_t_stu.clone(),
-                       "x_t_tea": x_t_tea.clone(),
-                       "aug": torch.empty(2, n, 6, dtype=torch.float64, device=dev),
-                       "theta_stu": torch.empty(n, 3, 6, dtype=torch.float32, device=dev),
-                       "theta_tea": torch.empty(n, 3, 6, dtype=torch.float32, device=dev)}
-        st = self.static
+        st = self.static = {k: v.clone() for k, v in zip(_INPUTS, (x_s, label_s, weight_s, x_t_stu, x_t_tea))}
+        st.update(aug=torch.empty(2, n, 6, dtype=torch.float64, device=dev), theta_stu=torch.empty(n, 3, 6, dtype=torch.float32, device=dev),
+                  theta_tea=torch.empty(n, 3, 6, dtype=torch.float32, device=dev))
         self._aug_pin = [torch.empty(2, n, 6, dtype=torch.float64).pin_memory() for _ in range(4)]
-        self._aug_ev = [None] * 4
-        self._aug_i = 0
-        self._aug_last = None
+        self._aug_ev, self._aug_i, self._aug_last = [None] * 4, 0, None
         self._stage_aug(aug_param_stu, aug_param_tea)
         # the main graph reads the step's EFFECTIVE inputs: the originals, or what the style graphs wrote
         st["x_s_in"] = st["x_s"].clone() if self.styled else st["x_s"]
@@ -811,180 +842,198 @@ class GraphedTrainStep:
         if self.occl:
             st["theta_back"] = torch.empty(n, 1, 6, dtype=torch.float32, device=dev)
             st["u"] = torch.zeros(n, 4, dtype=torch.float32, device=dev)
-            trainer._occl = ("device", st["theta_back"], st["u"])
-        else:
-            trainer._occl = None
+        self.t._occl = ("device", st["theta_back"], st["u"]) if self.occl else None
+
+    def _step_args(self):
+        """What the trainer's _forward_backward / _forward_part are called with, in the warm-up steps and in every capture."""
+        st = self.static
+        return st["x_s_in"], st["label_s"], st["weight_s"], st["x_t_stu"], [st["x_t_tea_in"]], st["theta_stu"], [st["theta_tea"]]
+
+    def _warm_up(self, warmup):
+        t, dev = self.t, self.static["x_s"].device
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
         self.g_style = {}
-        self._cap = {"stream": torch.cuda.Stream(device=dev, priority=trainer.stream_priority)} if trainer.stream_priority else {}
+        self._cap = {"stream": torch.cuda.Stream(device=dev, priority=t.stream_priority)} if t.stream_priority else {}
         with torch.cuda.stream(side):
-            if self.styled:             # (the style net's plans and packs; no model state involved)
-                self._style_pass("enc")
-                self._style_pass("s2t")
-                self._style_pass("t2s")
+            for which in ("enc", "s2t", "t2s") if self.styled else ():      # (the style net's plans and packs; no model state involved)
+                self._style_pass(which)
             for _ in range(warmup):     # REAL steps (same host draws as step()): fill the plan / table caches, allocator steady state
                 self._thetas()
                 self._draw_and_style()
-                trainer._forward_backward(st["x_s_in"], st["label_s"], st["weight_s"], st["x_t_stu"], [st["x_t_tea_in"]], st["theta_stu"],
-                                          [st["theta_tea"]])
-                trainer._sync_grads()
-                trainer._update()
+                t._forward_backward(*self._step_args())
+                t._sync_grads()
+                t._update()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        if _dist_on() and dist.get_backend() == "nccl":
-            # RCCL's watchdog thread polls the end events of the EAGER collectives issued so far (the warm-up steps'); on this HIP an
-            # event query fails with hipErrorCapturedEvent once the communicator's stream has joined a capture, even for an event that
-            # was recorded before it - and the watchdog then takes the process down.  Everything is complete here (synchronize above):
-            # give the watchdog (100 ms poll) time to retire those works before any collective is captured.  torch exposes no call that
-            # waits for the watchdog's list to drain, so this IS a timed wait (ten polls) - which is why capturing the
-            # collectives is opt-in (capture_comm below) and why the capture's failure path falls back to eager collectives.
-            if capture_comm or (capture_comm is None and os.environ.get("UDAPOSE_CAPTURE_COMM", "0") == "1"):
-                import time
-                dist.barrier()
-                torch.cuda.synchronize()
-                time.sleep(1.0)
-        style_mode = "thread_local" if _dist_on() else "global"
-        if self.styled:
-            for which in ("enc", "s2t", "t2s"):
-                g = torch.cuda.CUDAGraph()
-                pool = {} if not self.g_style else {"pool": self.g_style["enc"].pool()}
-                with torch.cuda.graph(g, capture_error_mode=style_mode, **pool):
-                    self._style_pass(which)
-                self.g_style[which] = g
-        # Data parallel: the confidence all-gather sits between the forwards and the losses, the gradient all-reduce between
-        # backward and the optimizer; both stay eager, so the step is cut into three graphs around them.
+
+    def _settle_watchdog(self, capture_comm):
+        # RCCL's watchdog thread polls the end events of the EAGER collectives issued so far (the warm-up steps'); on this HIP an
+        # event query fails with hipErrorCapturedEvent once the communicator's stream has joined a capture, even for an event that
+        # was recorded before it - and the watchdog then takes the process down.  Everything is complete here (synchronize above):
+        # give the watchdog (100 ms poll) time to retire those works before any collective is captured.  torch exposes no call that
+        # waits for the watchdog's list to drain, so this IS a timed wait (ten polls; ADVICE r5) - which is why capturing the
+        # collectives is opt-in (capture_comm below) and why the capture's failure path falls back to eager collectives.
+        if _dist_on() and dist.get_backend() == "nccl" and (
+                capture_comm or (capture_comm is None and os.environ.get("UDAPOSE_CAPTURE_COMM", "0") == "1")):
+            import time
+            dist.barrier()
+            torch.cuda.synchronize()
+            time.sleep(1.0)
+
+    @contextlib.contextmanager
+    def _capturing(self, g, pool=None, whole=False, origin=True):
+        """`with` this: the body is captured into the graph g.  whole: g holds the losses of a one-graph step, whose metrics are computed on a
+        side stream under the backward (_metrics_side).  origin=False: the style graphs, captured on torch's own capture stream."""
+        if whole and self.one_graph and self.metrics:
+            self.t._metrics_cb = self._metrics_side
+        try:
+            with torch.cuda.graph(g, capture_error_mode=self._mode, pool=pool, **(self._cap if origin else {})):
+                yield
+        finally:
+            self.t._metrics_cb = None
+
+    def _capture_style(self):
+        for which in ("enc", "s2t", "t2s") if self.styled else ():
+            g = torch.cuda.CUDAGraph()
+            with self._capturing(g, pool=self.g_style["enc"].pool() if self.g_style else None, origin=False):
+                self._style_pass(which)
+            self.g_style[which] = g
+
+    def _decide_form(self, split, capture_comm):
+        t = self.t
         # capture_comm (round 5): the step's collectives - confidence all-gather, gradient all-reduce buckets - are captured INTO the step's
         # graph (RCCL launches are stream-ordered kernels: capturable), so the data-parallel step is ONE graph launch like the one-rank step
         # instead of four graphs with eager collectives between them.  OPT-IN (round 6, ADVICE r5: the argument, or UDAPOSE_CAPTURE_COMM=1):
         # it rests on a timed wait for RCCL's watchdog (above), replayed collectives are invisible to torch.distributed's timeout, and no
         # multi-GPU node has run it yet; bench.py --gpus N asks for it explicitly (with its own hang guard) and lets the ranks fall back
-        # together.  If the capture raises (a collective backend that cannot be captured), the four-graph form below is built instead.
+        # together.  If the capture raises (a collective backend that cannot be captured), the four-graph form is built instead.
         if capture_comm is None:
             capture_comm = (_dist_on() and dist.get_backend() == "nccl" and split is None
                             and os.environ.get("UDAPOSE_CAPTURE_COMM", "0") == "1")
         self.capture_comm = bool(capture_comm) and _dist_on()
-        if self.capture_comm and trainer.sync.comm_dtype == "bf16" and trainer._overlap():
+        if self.capture_comm and t.sync.comm_dtype == "bf16" and t._overlap():
             # the bf16 exchange of the suffix runs on a side stream that hands over to the communicator's stream and waits for it again:
             # a fork that waits back on a non-origin stream brings hipStreamEndCapture down on this ROCm (tools/capture_fork_patterns.py)
             self.capture_comm = False
-        trainer.capture_comm = self.capture_comm
+        t.capture_comm = self.capture_comm
         self.split = (_dist_on() and not self.capture_comm) if split is None else bool(split)
         # hyper-parameters that are kernel ARGUMENTS of the captured launches stay what they were at capture: step() checks
         # them.  (lr / grad_scale are read from device memory and follow the optimizer's param_groups, see optim.py.)
         self._frozen = self._frozen_hyper()
-        if trainer.mask_mode == "threshold":
-            trainer.sync_mask_threshold(dev)        # (the captured mask launch reads this scalar: it exists, and is current, before the capture)
-        token = object()
-        for m in (trainer.student, trainer.teacher):
-            m._capture_token = token            # weight packs: captured once per network, unconditionally (pose_resnet._pack)
-        self.g_fb, self.g_up = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        # other threads (the RCCL watchdog of torch.distributed) may touch the runtime while this thread captures
-        mode = "thread_local" if _dist_on() else "global"
+        if t.mask_mode == "threshold":
+            t.sync_mask_threshold(self.static["x_s"].device)    # (the captured mask launch reads this scalar: it exists, and is current, before the capture)
+        t.student._capture_token = t.teacher._capture_token = object()      # weight packs: captured once per network, unconditionally (pose_resnet._pack)
+        self.g_fb, self.g_lb, self.g_lb2, self.g_up = torch.cuda.CUDAGraph(), None, None, None
         # overlap: the backward is cut after layer3 (two graph segments) and the finished gradient suffix is all-reduced on
         # the communicator's stream while the second segment replays
-        self.overlap = trainer._overlap()
-        self.g_lb2 = None
+        self.overlap = t._overlap()
         # one rank, nothing eager between backward and the optimizer: the update is captured into the same graph (one launch per step)
-        self.one_graph = (not self.split) and (self.capture_comm or not _dist_on()) and trainer.single_graph
+        self.one_graph = (not self.split) and (self.capture_comm or not _dist_on()) and t.single_graph
         self.capture_fallback = None        # why the captured-collectives form was given up (None: it was not, or was never asked for)
-        if not self.split and self.capture_comm:
-            e = None
-            try:
-                self._capture_one(trainer, st, mode)
-            except Exception as e_:      # (the backend refused the capture: fall back to eager collectives between four graphs)
-                e = e_
-            # The fallback is a COLLECTIVE decision: a rank that kept its captured graph while another replays eager collectives would pair
-            # them wrongly and hang.  Every rank reports, the minimum decides (one eager all-reduce, outside any capture).
-            ok_here = e is None
-            if dist.is_available() and dist.is_initialized() and not torch.cuda.is_current_stream_capturing():
-                flag = torch.tensor([1.0 if ok_here else 0.0], device=dev)
-                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-                ok_all = bool(flag.item() >= 1.0)
-            else:
-                ok_all = ok_here
-            if not ok_all:
-                import warnings
-                why = f"{type(e).__name__}: {e}" if e is not None else "another rank could not capture the collectives"
-                self.capture_fallback = why
-                warnings.warn(f"GraphedTrainStep: capturing the collectives into the step's graph failed ({why}); "
-                              "every rank uses the four-graph form with eager collectives")
-                trainer.capture_comm = False
-                self.capture_comm = False
-                trainer._metrics_cb = None
-                self._macc = None
-                trainer.student._pending_lower, trainer.student._pending_wg = [], []
-                # (whatever the aborted capture left half-done in the gradient exchange: the Work of the suffix's collective, its view,
-                # the bf16 exchange's side stream - the four-graph form starts from a clean GradSync)
-                trainer.sync._work, trainer.sync._upper, trainer.sync._cstream = None, None, None
-                trainer.student._grad_state = None
-                if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("GraphedTrainStep: the failed capture of the collectives left the stream capturing; cannot fall back")
-                torch.cuda.synchronize()
-                self.g_fb = torch.cuda.CUDAGraph()
-                self.split = True
-                self.one_graph = False
-        if not self.split and self.capture_comm:
-            pass
-        elif not self.split:
-            if self.one_graph and self.metrics:
-                trainer._metrics_cb = self._metrics_side
-            try:
-                with torch.cuda.graph(self.g_fb, capture_error_mode=mode, **self._cap):
-                    self._thetas()
-                    self.out = trainer._forward_backward(st["x_s_in"], st["label_s"], st["weight_s"], st["x_t_stu"], [st["x_t_tea_in"]],
-                                                         st["theta_stu"], [st["theta_tea"]])
-                    if trainer.student._pending_lower:      # (overlap forced on one rank: both backward parts in the one graph)
-                        trainer._backward_lower()
-                    if self.one_graph:
-                        trainer._sync_grads()
-                        trainer._update()
-                        self._capture_metrics()
-            finally:
-                trainer._metrics_cb = None
-        else:
-            self.g_lb = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_fb, capture_error_mode=mode, **self._cap):
+
+    def _capture_whole(self):
+        """The unsplit step in self.g_fb: forwards, losses, backward; with capture_comm its collectives too; with one_graph also Adam + EMA + packs and
+        the metrics.  False: some rank could not capture the collectives - all is cleaned up here and every rank builds the split form instead."""
+        t, e = self.t, None
+        try:
+            if self.capture_comm and os.environ.get("UDAPOSE_TEST_FAIL_CAPTURE", "0") == "1":     # test hook (tests/test_gpu_hotpath.py): the collective fallback
+                raise RuntimeError("injected capture failure (UDAPOSE_TEST_FAIL_CAPTURE=1)")
+            with self._capturing(self.g_fb, whole=True):
                 self._thetas()
-                self.fwd_state = trainer._forward_part(st["x_s_in"], st["label_s"], st["weight_s"], st["x_t_stu"], [st["x_t_tea_in"]],
-                                                       st["theta_stu"], [st["theta_tea"]])
-            g0 = gather_activates(self.fwd_state["activates"])
-            self.gathered = g0.clone() if g0 is not None else self.fwd_state["activates"].reshape(-1).clone()
-            with torch.cuda.graph(self.g_lb, pool=self.g_fb.pool(), capture_error_mode=mode, **self._cap):
-                self.out = trainer._loss_backward_part(self.fwd_state, self.gathered)
-            if self.overlap:
-                trainer.sync.start_upper()
-                self.g_lb2 = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.g_lb2, pool=self.g_fb.pool(), capture_error_mode=mode, **self._cap):
-                    trainer._backward_lower()
-        if self.one_graph:
-            self.g_up = None
-        else:
-            if self.capture_comm:
-                pass                        # (the collectives are inside g_fb)
-            elif self.g_lb2 is not None:
-                trainer.sync.finish()
-            else:
-                trainer.sync()
-            with torch.cuda.graph(self.g_up, pool=self.g_fb.pool(), capture_error_mode=mode, **self._cap):
-                trainer._update()
-                self._capture_metrics()
-        for m in (trainer.student, trainer.teacher):
-            m._capture_token = None
-            m.weights_changed()
-        self._opt_key = self._optimizer_key()
-        self._fused_tail = bool(trainer.fused_last)
-        self._maintained = [(trainer.student, trainer.student._last_hd, True), (trainer.teacher, trainer.teacher._last_hd, False)]
-        if self._fused_tail:
-            for m, hd, bwd in self._maintained:
-                m.packs_refreshed(hd, bwd)
+                self.out = t._forward_backward(*self._step_args())
+                if self.capture_comm or self.one_graph:
+                    # captured collectives: backward part 2 under the suffix's all-reduce, then the prefix's.  One rank: the collectives are
+                    # no-ops, what is left is _backward_lower() where part 2 is pending (overlap forced: both parts in the one graph)
+                    t._sync_grads()
+                elif t.student._pending_lower:      # (part 2 of a forced overlap; what follows it stays eager: _capture_update)
+                    t._backward_lower()
+                if self.one_graph:
+                    t._update()
+                    self._capture_metrics()
+        except Exception as e_:      # (the backend refused the capture: fall back to eager collectives between four graphs)
+            if not self.capture_comm:
+                raise
+            e = e_
+        if not self.capture_comm:
+            return True
+        # The fallback is a COLLECTIVE decision: a rank that kept its captured graph while another replays eager collectives would pair
+        # them wrongly and hang.  Every rank reports, the minimum decides (one eager all-reduce, outside any capture).
+        ok_all = e is None
+        if dist.is_available() and dist.is_initialized() and not torch.cuda.is_current_stream_capturing():
+            flag = torch.tensor([1.0 if ok_all else 0.0], device=self.static["x_s"].device)
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            ok_all = bool(flag.item() >= 1.0)
+        if ok_all:
+            return True
+        import warnings
+        why = f"{type(e).__name__}: {e}" if e is not None else "another rank could not capture the collectives"
+        self.capture_fallback = why
+        warnings.warn(f"GraphedTrainStep: capturing the collectives into the step's graph failed ({why}); "
+                      "every rank uses the four-graph form with eager collectives")
+        t.capture_comm = self.capture_comm = False
+        self._macc = None
+        # whatever the aborted capture left half-done: the four-graph form starts from a clean executor and a clean GradSync
+        t.student._drop_pending_step()
+        t.sync.reset()
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("GraphedTrainStep: the failed capture of the collectives left the stream capturing; cannot fall back")
         torch.cuda.synchronize()
+        self.g_fb = torch.cuda.CUDAGraph()
+        self.split, self.one_graph = True, False
+        return False
+
+    def _capture_split(self):
+        """g_fb | eager all-gather | g_lb | [eager start of the suffix's all-reduce | g_lb2]; the other collectives and g_up: _capture_update."""
+        self.g_lb = torch.cuda.CUDAGraph()
+        with self._capturing(self.g_fb):
+            self._thetas()
+            self.fwd_state = self.t._forward_part(*self._step_args())
+        g0 = gather_activates(self.fwd_state["activates"])
+        self.gathered = g0.clone() if g0 is not None else self.fwd_state["activates"].reshape(-1).clone()
+        with self._capturing(self.g_lb, pool=self.g_fb.pool()):
+            self.out = self.t._loss_backward_part(self.fwd_state, self.gathered)
+        if self.overlap:
+            self.t.sync.start_upper()
+            self.g_lb2 = torch.cuda.CUDAGraph()
+            with self._capturing(self.g_lb2, pool=self.g_fb.pool()):
+                self.t._backward_lower()
+
+    def _capture_update(self):
+        if self.one_graph:
+            return
+        self.g_up = torch.cuda.CUDAGraph()
+        if not self.capture_comm:           # (captured collectives are inside g_fb)
+            (self.t.sync.finish if self.g_lb2 is not None else self.t.sync)()
+        with self._capturing(self.g_up, pool=self.g_fb.pool()):
+            self.t._update()
+            self._capture_metrics()
+
+    def _after_capture(self):
+        t = self.t
+        t.student._capture_token = t.teacher._capture_token = None
+        self._opt_key = self._optimizer_key()
+        self._fused_tail = bool(t.fused_last)
+        self._maintained = [(t.student, t.student._last_hd, True), (t.teacher, t.teacher._last_hd, False)]
+        self._weights_moved()
+        torch.cuda.synchronize()
+
+    def _weights_moved(self):
+        # the captured Adam / EMA kernels changed both networks' parameters behind torch's back: every executor plan (other batch sizes,
+        # validate(), fp32 mode) must re-pack its bf16 weights before its next forward ...
+        for m, hd, bwd in self._maintained:
+            m.weights_changed()
+            if self._fused_tail:          # ... but the step's own plans, whose packs the captured update has just rewritten
+                m.packs_refreshed(hd, bwd)
+
+    def _drop_graphs(self):
+        self.g_fb = self.g_lb = self.g_lb2 = self.g_up = None
 
     def release(self):
         """Destroy the captured graphs.  With capture_comm the graphs hold RCCL launches, and RCCL's communicator teardown waits for every
         such graph to be gone: call this (or drop every reference to the object) BEFORE torch.distributed.destroy_process_group(), which
         otherwise never returns (measured on RCCL 2.26 / ROCm 7.0)."""
-        self.g_fb = self.g_lb = self.g_lb2 = self.g_up = None
+        self._drop_graphs()
         self.g_style = {}
         import gc
         gc.collect()
@@ -994,28 +1043,9 @@ class GraphedTrainStep:
         # (graphs that captured RCCL launches must be gone before destroy_process_group(): dropping the last reference does what release() does)
         try:
             if getattr(self, "capture_comm", False):
-                self.g_fb = self.g_lb = self.g_lb2 = self.g_up = None
+                self._drop_graphs()
         except Exception:
             pass
-
-    def _capture_one(self, trainer, st, mode):
-        """The whole data-parallel step - forwards, all-gather, losses, backward part 1, the suffix's all-reduce under backward part 2, the
-        prefix's all-reduce, Adam + EMA + packs - captured into self.g_fb."""
-        if os.environ.get("UDAPOSE_TEST_FAIL_CAPTURE", "0") == "1":       # test hook (tests/test_gpu_hotpath.py): exercises the collective fallback
-            raise RuntimeError("injected capture failure (UDAPOSE_TEST_FAIL_CAPTURE=1)")
-        if self.one_graph and self.metrics:
-            trainer._metrics_cb = self._metrics_side
-        try:
-            with torch.cuda.graph(self.g_fb, capture_error_mode=mode, **self._cap):
-                self._thetas()
-                self.out = trainer._forward_backward(st["x_s_in"], st["label_s"], st["weight_s"], st["x_t_stu"], [st["x_t_tea_in"]],
-                                                     st["theta_stu"], [st["theta_tea"]])
-                trainer._sync_grads()
-                if self.one_graph:
-                    trainer._update()
-                    self._capture_metrics()
-        finally:
-            trainer._metrics_cb = None
 
     def _capture_metrics(self):
         """(inside the capture of the step's last graph) losses + device PCK of the source batch -> self._mvec = [loss_all, loss_s, loss_c,
@@ -1074,26 +1104,22 @@ class GraphedTrainStep:
         self.step(*args, **kw)
         i = self._mi
         self._mpin[i].copy_(self._mvec, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._mev[i] = ev
+        self._mev[i] = torch.cuda.Event()
+        self._mev[i].record()
         self._mi = 1 - i
-        prev = self._mev[1 - i]
-        if prev is None:
-            return None
-        prev.synchronize()
-        self._mev[1 - i] = None
-        return self._metrics_dict(self._mpin[1 - i])
+        return self._read_slot(1 - i)
 
-    def flush_metrics(self):
-        """Metrics of the most recent step_async() (waits for it)."""
-        last = 1 - self._mi
-        ev = self._mev[last]
+    def _read_slot(self, i):
+        """Wait for metric slot i, clear it and decode it (None: nothing is queued in it)."""
+        ev, self._mev[i] = self._mev[i], None
         if ev is None:
             return None
         ev.synchronize()
-        self._mev[last] = None
-        return self._metrics_dict(self._mpin[last])
+        return self._metrics_dict(self._mpin[i])
+
+    def flush_metrics(self):
+        """Metrics of the most recent step_async() (waits for it)."""
+        return self._read_slot(1 - self._mi)
 
     profile_segments = False        # bench.py --dp-segments: HIP events between the parts of a step (device time per part, after a synchronize)
 
@@ -1145,55 +1171,35 @@ class GraphedTrainStep:
         warp.thetas_from_packed(st["aug"][1], r, fwd=st["theta_tea"])
 
     def _style_pass(self, which):
-        """"enc": relu4_1 of both ORIGINAL batches into static feature buffers (each image is encoded once per step, whichever
-        directions are drawn); "s2t" / "t2s": AdaIN + decoder of one direction from those features into the main graph's input buffer.
-        A net with spectrum() / transfer() (FDANet) keeps spectra where the AdaIN net keeps features."""
-        st, t = self.static, self.t
-        net = getattr(t.style_net, "module", t.style_net)
+        """"enc": the summaries (_StyleAdapter: relu4_1 features, or low-frequency spectra) of both ORIGINAL batches into static buffers, once per
+        step whichever directions are drawn; "s2t" / "t2s": one direction's transfer from those summaries into the main graph's input buffer."""
+        if which in self.g_style:       # (captured by now: replay it)
+            return self.g_style[which].replay()
+        st, style, (k_s, k_t) = self.static, self._style, self._style.keys
         with torch.no_grad():
-            if hasattr(net, "spectrum") and hasattr(net, "transfer"):
-                # a Fourier-domain net: "enc" = both batches' spectra into static buffers, a direction = one apply launch into the input buffer
-                if which == "enc":
-                    if "sp_s" not in st:
-                        st["sp_s"], st["sp_t"] = net.spectrum(st["x_s"]), net.spectrum(st["x_t_tea"])
-                    else:
-                        net.spectrum(st["x_s"], out=st["sp_s"])
-                        net.spectrum(st["x_t_tea"], out=st["sp_t"])
-                elif which == "s2t":
-                    net.transfer(st["x_s"], st["sp_s"], st["sp_t"], st["alpha_s2t"], clamp=t.recover, out=st["x_s_in"])
-                else:
-                    net.transfer(st["x_t_tea"], st["sp_t"], st["sp_s"], st["alpha_t2s"], clamp=t.recover, out=st["x_t_tea_in"])
-                return
             if which == "enc":
-                f_s, f_t = net.encode_features(st["x_s"]), net.encode_features(st["x_t_tea"])
-                if "f_s" not in st:
-                    st["f_s"], st["f_t"] = torch.empty_like(f_s), torch.empty_like(f_t)
-                st["f_s"].copy_(f_s)
-                st["f_t"].copy_(f_t)
+                for img, key in (("x_s", k_s), ("x_t_tea", k_t)):
+                    if key in st:
+                        style.summarize(st[img], out=st[key])
+                    else:       # (the first, uncaptured pass: a buffer of its own, not the net's arena)
+                        st[key] = style.summarize(st[img]).clone()
             elif which == "s2t":
-                st["x_s_in"].copy_(net.transfer_from_features(st["f_s"], st["f_t"], st["alpha_s2t"], clamp=t.recover))
+                style.transfer(st["x_s"], st[k_s], st[k_t], st["alpha_s2t"], self.t.recover, out=st["x_s_in"])
             else:
-                st["x_t_tea_in"].copy_(net.transfer_from_features(st["f_t"], st["f_s"], st["alpha_t2s"], clamp=t.recover))
+                style.transfer(st["x_t_tea"], st[k_t], st[k_s], st["alpha_t2s"], self.t.recover, out=st["x_t_tea_in"])
 
     def _draw_and_style(self):
-        """The step's host draws, in the eager step's (= the reference's) order, and what follows from them: each style
-        direction drawn runs (its graph once captured) into the main graph's input buffer, the other keeps the original
-        images; the occlusion's uniform numbers go to the device."""
+        """The step's host draws, in the eager step's (= the reference's) order, and what follows from them: each style direction drawn runs (its
+        graph once captured) into the main graph's input buffer, the other keeps the original images; the occlusion's uniform numbers go to the device."""
         st = self.static
         if self.styled:
             decisions = self.t.draw_style_decisions()
             if any(a is not None for a in decisions):
-                if "enc" in self.g_style:
-                    self.g_style["enc"].replay()
-                else:
-                    self._style_pass("enc")
+                self._style_pass("enc")
             for which, a, src in zip(("s2t", "t2s"), decisions, (("x_s_in", "x_s"), ("x_t_tea_in", "x_t_tea"))):
                 if a is not None:
                     st["alpha_" + which].fill_(float(a))
-                    if which in self.g_style:
-                        self.g_style[which].replay()
-                    else:
-                        self._style_pass(which)
+                    self._style_pass(which)
                 else:
                     st[src[0]].copy_(st[src[1]], non_blocking=True)
         if self.occl:
@@ -1215,8 +1221,7 @@ class GraphedTrainStep:
         return key
 
     def _frozen_hyper(self):
-        t = self.t
-        opt = t.stu_optimizer
+        t, opt = self.t, self.t.stu_optimizer
         frozen = [("teacher_alpha", float(t.tea_optimizer.alpha)), ("lambda_c", float(t.lambda_c)), ("mask_ratio", float(t.mask_ratio)),
                   ("sigma", float(t.sigma)), ("bn_momentum", float(t.student.bn_momentum)), ("occlude_rate", float(t.occlude_rate)),
                   ("occlude_thresh", float(t.occlude_thresh)), ("occlude_size", int(t.occlude_size)), ("warp_mode", str(t.warp_mode))]
@@ -1239,13 +1244,13 @@ class GraphedTrainStep:
         replay of the current step.  The following step() call (with no tensors given) takes the staged batch with five
         device-to-device copies (92 MB, ~30 us) instead of waiting for PCIe on the compute stream."""
         if self._stage is None:
-            self._stage = {k: torch.empty_like(self.static[k]) for k in ("x_s", "label_s", "weight_s", "x_t_stu", "x_t_tea")}
+            self._stage = {k: torch.empty_like(self.static[k]) for k in _INPUTS}
             self._copy_stream = torch.cuda.Stream(device=self.static["x_s"].device)
             self._staged, self._consumed = torch.cuda.Event(), None
         if self._consumed is not None:
             self._copy_stream.wait_event(self._consumed)     # the previous step's D2D reads of the staging buffers come first
         with torch.cuda.stream(self._copy_stream):
-            for k, v in (("x_s", x_s), ("label_s", label_s), ("weight_s", weight_s), ("x_t_stu", x_t_stu), ("x_t_tea", x_t_tea)):
+            for k, v in zip(_INPUTS, (x_s, label_s, weight_s, x_t_stu, x_t_tea)):
                 self._stage[k].copy_(v, non_blocking=True)
             self._staged.record(self._copy_stream)
         self._have_staged = True
@@ -1259,7 +1264,7 @@ class GraphedTrainStep:
             self._consumed = torch.cuda.Event()
             self._consumed.record()
             self._have_staged = False
-        for k, v in (("x_s", x_s), ("label_s", label_s), ("weight_s", weight_s), ("x_t_stu", x_t_stu), ("x_t_tea", x_t_tea)):
+        for k, v in zip(_INPUTS, (x_s, label_s, weight_s, x_t_stu, x_t_tea)):
             if v is not None and v.data_ptr() != st[k].data_ptr():
                 st[k].copy_(v, non_blocking=True)
         self._stage_aug(aug_param_stu, aug_param_tea)
@@ -1308,11 +1313,5 @@ class GraphedTrainStep:
             self.t.stu_optimizer.sync_hyper()    # lr scheduler / loss scale -> device state read by the captured sweep
             self.g_up.replay()
             seg("update")
-        # the replayed Adam / EMA kernels changed both networks' parameters behind torch's back: every executor plan (other
-        # batch sizes, validate(), fp32 mode) must re-pack its bf16 weights before its next forward
-        self.t.student.weights_changed()
-        self.t.teacher.weights_changed()
-        if self._fused_tail:
-            for m, hd, bwd in self._maintained:          # ... whose own packs the captured update has just rewritten
-                m.packs_refreshed(hd, bwd)
+        self._weights_moved()
         return self.out

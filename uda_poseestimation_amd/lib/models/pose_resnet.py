@@ -195,14 +195,17 @@ class PoseResNet(nn.Module):
         self._ptr_cache = None
         self._flat_grad = None
         self._flat_grad2 = None
-        self._grad_state = None
         self._deferred_bn = []
         self._handles = {}
-        self._pending_lower = []
-        self._pending_wg = []
+        self._drop_pending_step()
         self._split_sum_hd = None
         self._split_off = None
         return r
+
+    def _drop_pending_step(self):
+        """Forget the per-step work a backward left for later calls: part 2 of a split backward, merged weight gradients, the pending sum
+        of the second gradient buffer.  (_apply: the tensors moved; the engine: a capture of the step was abandoned half-way.)"""
+        self._pending_lower, self._pending_wg, self._grad_state = [], [], None
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         # accept checkpoints saved from DataParallel wrappers ('module.' prefix, train_human.py:229-230)
