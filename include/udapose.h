@@ -342,6 +342,23 @@ int udapose_net_wgrad_pair(udapose_net_t net, void* stream, const void* act_a, v
 int udapose_net_wgrad_pair_defer(udapose_net_t net, void* stream, const void* act_a, void* ws_a, void* const* h_grads_a, float beta_a,
                                  const void* act_b, void* ws_b, void* const* h_grads_b, float beta_b, int part, int* deferred);
 int udapose_net_split_sum_flush(udapose_net_t net, void* stream);
+/* Data gradient of the stem convolution (Conv2d(3, 64, 7, stride 2, pad 3, bias=False), resnet.py's conv1): the gradient of a loss with
+ * respect to the network's INPUT.
+ *   dx[n][c][iy][ix] = sum over co, ky, kx with 2*oy + ky - 3 == iy and 2*ox + kx - 3 == ix of dy[n][oy][ox][co] * w[co][c][ky][kx]
+ * dy: NHWC [N][H/2][W/2][64] in the element type (16-byte aligned); w: the fp32 master weight in its channels-last memory layout
+ * [64][7][7][3], rounded to the element type by the kernel (every data gradient of a plan reads element-type weights); dx: fp32 NCHW
+ * [N][3][H][W], every element written (no prior clear), fp32 accumulation in one fixed order: no atomics, no workspace, no allocation,
+ * capturable, and two calls give the same bits.  UDAPOSE_ERR_ARG: a null pointer, N < 1, H or W odd or below 8, dy not 16-byte aligned, dx
+ * overlapping dy; nothing is launched then. */
+int udapose_stem_dgrad(void* stream, const void* dy, const float* w, int N, int H, int W, float* dx);
+/* The same launch on a plan's own tensors: dy = the stem's output gradient of the pass whose workspace is `ws`, w = h_params[stem weight].
+ * Contract: valid once the gradient chain that holds the stem has been enqueued on `stream` (or on a stream `stream` waits for) with this
+ * `ws` - udapose_net_backward, udapose_net_backward_part(part 2), or phase 0 / phase 1 of either through udapose_net_backward_phase - and
+ * before `ws` is given to another pass; the stem's dy stays in `ws` for the grouped weight-gradient launch, so the call may come before or
+ * after phase 2.  Stateless: the pass is named by `ws` alone, so two passes of one plan on two streams each hand in their own workspace.  dx
+ * (fp32 NCHW [N][3][H][W] of the plan) carries the loss scale the backward's dout carried.  UDAPOSE_ERR_UNSUPPORTED: forward-only plans and
+ * the fp32 / f16x2 modes (they keep nothing for a backward); 'strict' plans are supported (their backward is the fp16 one). */
+int udapose_net_input_grad(udapose_net_t net, void* stream, const void* const* h_params, void* ws, float* dx);
 /* The deal of a grouped weight-gradient launch, as a pure host function (no device): unit i = nblk[i] work-groups of stages[i] 64-pixel stages.
  * Writes the runs of the eight XCD lists, XCD by XCD in list order, as entries (ent_xcd, ent_unit, ent_first = first work-group of the unit,
  * ent_count), at most `cap` of them, and returns how many entries there are (< 0: an error code); finish_out[8]: modelled finish time of each

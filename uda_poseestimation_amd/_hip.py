@@ -111,6 +111,8 @@ _SIGS = {
     "udapose_net_wgrad_pair": (ci, [vp, vp, vp, vp, vp, cf, vp, vp, vp, cf, ci]),
     "udapose_net_wgrad_pair_defer": (ci, [vp, vp, vp, vp, vp, cf, vp, vp, vp, cf, ci, vp]),
     "udapose_net_split_sum_flush": (ci, [vp, vp]),
+    "udapose_stem_dgrad": (ci, [vp, vp, vp, ci, ci, ci, vp]),
+    "udapose_net_input_grad": (ci, [vp, vp, vp, vp, vp]),
     "udapose_wgrad_deal": (ci, [vp, vp, ci, ci, vp, vp, vp, vp, ci, vp]),
     "udapose_net_grad_split_param": (ll, [vp]),
     "udapose_net_bind_update": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -282,6 +282,13 @@ int udapose_net_backward_phase(udapose_net_t n, void* stream, const float* dout,
     if (!n) return UDAPOSE_ERR_ARG;
     return net_backward(n, S(stream), dout, params, wpack, act, ws, grads, beta, part, phase);
 }
+int udapose_stem_dgrad(void* stream, const void* dy, const float* w, int N, int H, int W, float* dx) {
+    return stem_dgrad(S(stream), (const elem_t*)dy, w, N, H, W, dx);
+}
+int udapose_net_input_grad(udapose_net_t n, void* stream, const void* const* params, void* ws, float* dx) {
+    if (!n || !params || !ws || !dx) return UDAPOSE_ERR_ARG;
+    return net_input_grad(n, S(stream), params, ws, dx);
+}
 long long udapose_net_grad_split_param(udapose_net_t n) { return net_grad_split_param(n); }
 int udapose_net_bind_update(udapose_net_t student, udapose_net_t teacher, void* const* params_s, void* const* grads, void* const* exp_avg,
                             void* const* exp_avg_sq, void* const* params_t, void* wpack_s, void* wpack_t) {

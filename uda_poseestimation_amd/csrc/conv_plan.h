@@ -112,6 +112,8 @@ struct DgradBnStat {
 // dx = conv^T(dy, w_bwd[Ci][wtaps][Co]) (+ res)
 int conv_dgrad(hipStream_t s, const ConvGeom& g, const elem_t* dy, const elem_t* w_bwd, void* dx, const elem_t* res, int out_f32,
                DgradBnStat* bs = nullptr);
+// the stem's data gradient (stem_dgrad.hip): dx fp32 NCHW [N][3][H][W] = conv^T(dy NHWC [N][H/2][W/2][64], fp32 w [64][7][7][3] rounded to elem_t)
+int stem_dgrad(hipStream_t s, const elem_t* dy, const float* w, int N, int H, int W, float* dx);
 // dw (fp32, [Co][wtaps][Ci]; transposed: [Ci][wtaps][Co]) (+)= ...;  rows_valid < 0 -> all rows
 int conv_wgrad(hipStream_t s, const ConvGeom& g, const elem_t* dy, const elem_t* x, float* dw, int accumulate, int rows_valid);
 // the same problem as a parameter block (for the grouped launch); returns the layer's algorithmic FLOPs in *flops

@@ -27,6 +27,7 @@ int net_wgrad_deal(const int* nblk, const int* stages, int n_units, int order, i
                    double* finish_out);
 int net_backward(void* h, hipStream_t s, const float* dout_nchw, const void* const* params, const void* wpack_, void* act_, void* ws_,
                  void* const* grads, float beta, int part, int phase);
+int net_input_grad(void* h, hipStream_t s, const void* const* params, void* ws_, float* dx);
 int net_apply_running(void* h, hipStream_t s, const void* act_, void* const* buffers, float momentum);
 int net_bind_grads(void* h, void* const* grads);
 long long net_grad_split_param(void* h);

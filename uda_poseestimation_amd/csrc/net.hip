@@ -1216,7 +1216,7 @@ int net_backward(void* h, hipStream_t s, const float* dout_nchw, const void* con
         }
         return UDAPOSE_OK;
     }
-    // stem: maxpool -> bn/relu -> conv (no input gradient)
+    // stem: maxpool -> bn/relu -> conv (its dy stays at ws + stem.dy_off: the weight gradient's operand and net_input_grad's)
     if (n.policy.stem_fused >= 2 && grouped && n.policy.wgrad_group_stem) {
         // the max-pool backward is gathered inside the BN backward's two sweeps: the full-resolution gradient is never stored
         const BnL& sb = n.stem_bn;
@@ -1239,6 +1239,16 @@ int net_backward(void* h, hipStream_t s, const float* dout_nchw, const void* con
         if (pw_zero(s, grads[n.fc_w_idx], (size_t)1000 * 2048 * 4) != UDAPOSE_OK) return UDAPOSE_ERR_LAUNCH;
         if (pw_zero(s, grads[n.fc_b_idx], (size_t)1000 * 4) != UDAPOSE_OK) return UDAPOSE_ERR_LAUNCH;
     }
+    return UDAPOSE_OK;
+}
+
+// d loss / d x (fp32 NCHW) from the stem's dy, which the stem's BatchNorm backward of a pass left at ws + stem.dy_off (both stem paths of
+// net_backward; the grouped weight-gradient launch only reads it).  Stateless: the pass is named by its workspace.
+int net_input_grad(void* h, hipStream_t s, const void* const* params, void* ws_, float* dx) {
+    Net& n = *(Net*)h;
+    if ((n.f32 && !n.strict) || n.fwd_only) return UDAPOSE_ERR_UNSUPPORTED;
+    DbgSyncScope dbg(n.policy.debug_sync);
+    CK(stem_dgrad(s, (const elem_t*)((const char*)ws_ + n.stem.dy_off), (const float*)params[n.stem.w_idx], n.N, n.H, n.W, dx));
     return UDAPOSE_OK;
 }
 

@@ -98,6 +98,7 @@ class _PoseNetFn(torch.autograd.Function):
         out, act, hd, ws = net._run_forward(x, save=need_grad, defer_bn=defer_bn)
         ctx.net, ctx.act, ctx.hd, ctx.ws = net, act, hd, ws
         ctx.nparams = len(params)
+        ctx.x_shape = tuple(x.shape)
         return out
 
     @staticmethod
@@ -105,10 +106,11 @@ class _PoseNetFn(torch.autograd.Function):
         net = ctx.net
         if ctx.act is None:
             raise RuntimeError("PoseResNet backward without saved activations (forward ran without grad, or backward ran twice)")
-        net._run_backward(dout, ctx.act, ctx.hd, ctx.ws)
+        # an input that requires grad gets d loss / d x (fp32, x's shape) from the stem's data-gradient kernel, behind the gradient chain
+        dx = net._run_backward(dout, ctx.act, ctx.hd, ctx.ws, x_shape=ctx.x_shape if ctx.needs_input_grad[0] else None)
         ctx.act = ctx.ws = None
         # parameter gradients are accumulated straight into p.grad (views of the module's flat gradient buffer)
-        return (None, None, None, None) + (None,) * ctx.nparams
+        return (dx, None, None, None) + (None,) * ctx.nparams
 
 
 class PoseResNet(nn.Module):
@@ -270,7 +272,7 @@ class PoseResNet(nn.Module):
         if Cc != 3:
             raise ValueError("PoseResNet expects [N,3,H,W] input")
         if differentiable is None:
-            differentiable = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+            differentiable = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         prec = self.resolved_precision(differentiable)
         aux = self.aux_lib_kind if prec in ('fp32', 'f16x2') else None
         fo = bool(PoseResNet.fwd_only_plans) and not differentiable
@@ -292,7 +294,7 @@ class PoseResNet(nn.Module):
         launched afterwards on OTHER streams only need to wait for this point)."""
         hd = self._handle(x)
         pa, ba, params = self._pointers()
-        self._pack(hd, pa, params, need_bwd=torch.is_grad_enabled() and any(p.requires_grad for p in params))
+        self._pack(hd, pa, params, need_bwd=torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)))
         return hd
 
     def weights_changed(self):
@@ -454,7 +456,12 @@ class PoseResNet(nn.Module):
                 act.record_stream(stream)
                 ws.record_stream(stream)
 
-    def _run_backward(self, dout, act, hd, ws):
+    def _run_backward(self, dout, act, hd, ws, x_shape=None):
+        """Enqueue the backward of one pass.  x_shape: the input requires grad - returns d loss / d x (fp32 NCHW), None otherwise."""
+        if x_shape is not None and self.split_backward:
+            # (the stem's gradient chain is part 2: it runs later, in finish_backward(), outside this autograd node)
+            raise RuntimeError("PoseResNet: an input that requires grad is not supported with split_backward = True (the stem's gradient chain runs "
+                               "later, in finish_backward()); detach the input or clear split_backward")
         pa, ba, params = self._pointers()
         views = self._grad_views(params)
         cur = torch.cuda.current_stream()
@@ -505,12 +512,19 @@ class PoseResNet(nn.Module):
             self._pending_wg.append((hd, act, ws, gptrs, beta, cur))      # (keeps the arenas alive until the weight gradients have run)
         else:
             check(hd.L.udapose_net_backward(hd.h, _hip.stream(), ptr(dout), pa, ptr(hd.wpack), ptr(act), ptr(ws), gptrs, beta), "net_backward")
+        dx = None
+        if x_shape is not None:
+            # the chain that holds the stem is enqueued (with merge_wgrad, ws stays alive in _pending_wg for the weight gradients):
+            # one more launch on the same stream reads the stem's dy in ws
+            dx = torch.empty(x_shape, dtype=torch.float32, device=dout.device)
+            check(hd.L.udapose_net_input_grad(hd.h, _hip.stream(), pa, ptr(ws), ptr(dx)), "net_input_grad")
         # backbone.fc is not part of forward (resnet.py:21-40): like autograd in the reference, it gets NO gradient (None, not
         # zeros: SGD's weight decay and Adam must skip it exactly as torch.optim skips parameters without .grad)
         nograd = self._no_grad_ids()
         for p, v in zip(params, views):
             if p.requires_grad and id(p) not in nograd:
                 p.grad = v
+        return dx
 
     def finish_wgrad(self, defer_sum=False):
         """Launch the grouped weight gradients of the backward passes that ran with merge_wgrad, on the current stream (the caller
@@ -548,8 +562,13 @@ class PoseResNet(nn.Module):
     _warned_eval_grad = False
 
     def forward(self, x):
+        """head(upsampling(backbone(x))).  A training-mode call with grad enabled is differentiable when any parameter OR the input x requires
+        grad: x.grad is fp32, of x's shape (d loss / d x through the stem convolution, csrc/stem_dgrad.hip).  Like every p.grad it is the
+        gradient of whatever was backpropagated: in the 'fp16' / 'strict' precisions x.grad carries the loss scale - divide it out (a
+        GradScaler's unscale_ only sees the optimizer's parameters).  Parameters that do not require grad keep .grad = None.  Not available with
+        split_backward (the backward raises): the stem's gradient chain runs later there, in finish_backward()."""
         params = list(self.parameters())
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
         if need_grad and not self.training:
             # eval-mode BatchNorm is folded into the convolutions' epilogues (policy eval_fold) and this path has no eval-mode BN backward: such a
             # forward keeps no backward state.  Say so HERE - the output carries no grad_fn, so a later .backward() fails at once with torch's own
@@ -569,7 +588,7 @@ class PoseResNet(nn.Module):
         order, by apply_deferred_bn().  For forwards of one module that run concurrently on different streams (the batch
         statistics used for normalisation are per call either way)."""
         params = list(self.parameters())
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
         return _PoseNetFn.apply(x, self, need_grad, True, *params)
 
     def get_parameters(self, lr=1.):

@@ -102,6 +102,21 @@ def conv2d_bwd_data_bn(dy, w_bwd, d, bn_y, bn_mean, bn_invstd, bn_z=None, bn_gam
     return dx, slab
 
 
+def stem_dgrad(dy, w, dx=None):
+    """Data gradient of the stem convolution Conv2d(3, 64, 7, stride 2, pad 3) (udapose_stem_dgrad): dy NHWC [N, H/2, W/2, 64] bf16 / fp16,
+    w the fp32 weight [64, 3, 7, 7] (rounded to dy's type by the kernel) -> dx fp32 NCHW [N, 3, H, W], every element written."""
+    require_cuda(dy, w)
+    assert dy.dtype in (torch.bfloat16, torch.float16) and dy.is_contiguous() and dy.dim() == 4 and dy.shape[3] == 64
+    assert w.dtype == torch.float32 and tuple(w.shape) == (64, 3, 7, 7)
+    wc = w.detach().contiguous(memory_format=torch.channels_last)            # physical [64][7][7][3]
+    N, Ho, Wo, _ = dy.shape
+    if dx is None:
+        dx = torch.empty(N, 3, 2 * Ho, 2 * Wo, dtype=torch.float32, device=dy.device)
+    assert dx.dtype == torch.float32 and dx.is_contiguous() and tuple(dx.shape) == (N, 3, 2 * Ho, 2 * Wo)
+    check(lib_for(dy).udapose_stem_dgrad(stream(), ptr(dy), ptr(wc), N, 2 * Ho, 2 * Wo, ptr(dx)), "stem_dgrad")
+    return dx
+
+
 def conv2d_bwd_weight(dy, x, d, dw=None):
     require_cuda(dy, x)
     T = d.KH * kwp(d)
