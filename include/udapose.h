@@ -359,6 +359,26 @@ int udapose_stem_dgrad(void* stream, const void* dy, const float* w, int N, int 
  * (fp32 NCHW [N][3][H][W] of the plan) carries the loss scale the backward's dout carried.  UDAPOSE_ERR_UNSUPPORTED: forward-only plans and
  * the fp32 / f16x2 modes (they keep nothing for a backward); 'strict' plans are supported (their backward is the fp16 one). */
 int udapose_net_input_grad(udapose_net_t net, void* stream, const void* const* h_params, void* ws, float* dx);
+/* Gradient-direction perturbation of an image batch inside a norm ball (csrc/perturb.hip).  x, g, out (and x0, the centre of
+ * the ball; NULL: x0 = x): fp32 [N][C][HW] contiguous.  eps_dev, step_dev: DEVICE fp32 scalars, read by the launches (a captured launch follows
+ * a host change of them); step_dev NULL: step = eps.  lo, hi: per-channel fp32 [C] clamp of the result (both or neither).
+ *   mode UDAPOSE_PERTURB_L2, per sample:    u = g / ||g||_2; d = (x - x0) + step * u; if ||d||_2 > eps: d *= eps / ||d||_2; out = clamp(x0 + d)
+ *                                          (x0 NULL and step_dev NULL: the one-step form x + eps * u, which runs no second norm)
+ *   mode UDAPOSE_PERTURB_LINF, per element: d = clip((x - x0) + step * sign(g), -eps, eps); out = clamp(x0 + d); sign(0) = sign(NaN) = 0
+ * A sample whose sum of squares of g is zero, infinite or NaN (g == 0, a non-finite element, or squares that overflow) gets
+ * out = clamp(x) - x bit for bit without a clamp - and gnorm 0; the other samples are unaffected.  The sum of squares is formed in l2 always
+ * and in linf when gnorm is given; linf without gnorm is ONE launch with no reduction and handles a non-finite g per element (sign).
+ * gnorm [N] (may be NULL): ||g[n]||_2.  ws: udapose_perturb_ws_bytes(N, C, HW) bytes (4-byte aligned; may be NULL in linf without gnorm),
+ * per-(sample, work-group) partial sums that every consumer adds in index order: no atomics, no allocation, capturable, two calls give the
+ * same bits, and g scaled by 2^k gives the same out bits (range of k: perturb.hip).  16-byte accesses where HW % 4 == 0 and x, g, x0, out are
+ * 16-byte aligned, 4-byte accesses otherwise.  out == x (in place) is allowed.  UDAPOSE_ERR_ARG, nothing launched: a null x, g, eps_dev or
+ * out; a null ws where it is needed; N < 1; C * HW < 1; an unknown mode; one of lo / hi alone; out overlapping g.  UDAPOSE_ERR_UNSUPPORTED:
+ * C * HW >= 2^31 - 1024. */
+#define UDAPOSE_PERTURB_L2 0
+#define UDAPOSE_PERTURB_LINF 1
+long long udapose_perturb_ws_bytes(int N, int C, int HW);
+int udapose_perturb(void* stream, const float* x, const float* g, const float* x0, int N, int C, int HW, int mode, const float* eps_dev,
+                    const float* step_dev, const float* lo, const float* hi, void* ws, float* out, float* gnorm);
 /* The deal of a grouped weight-gradient launch, as a pure host function (no device): unit i = nblk[i] work-groups of stages[i] 64-pixel stages.
  * Writes the runs of the eight XCD lists, XCD by XCD in list order, as entries (ent_xcd, ent_unit, ent_first = first work-group of the unit,
  * ent_count), at most `cap` of them, and returns how many entries there are (< 0: an error code); finish_out[8]: modelled finish time of each

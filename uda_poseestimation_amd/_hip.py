@@ -113,6 +113,8 @@ _SIGS = {
     "udapose_net_split_sum_flush": (ci, [vp, vp]),
     "udapose_stem_dgrad": (ci, [vp, vp, vp, ci, ci, ci, vp]),
     "udapose_net_input_grad": (ci, [vp, vp, vp, vp, vp]),
+    "udapose_perturb_ws_bytes": (ll, [ci, ci, ci]),
+    "udapose_perturb": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
     "udapose_wgrad_deal": (ci, [vp, vp, ci, ci, vp, vp, vp, vp, ci, vp]),
     "udapose_net_grad_split_param": (ll, [vp]),
     "udapose_net_bind_update": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -289,6 +289,11 @@ int udapose_net_input_grad(udapose_net_t n, void* stream, const void* const* par
     if (!n || !params || !ws || !dx) return UDAPOSE_ERR_ARG;
     return net_input_grad(n, S(stream), params, ws, dx);
 }
+long long udapose_perturb_ws_bytes(int N, int C, int HW) { return perturb_ws_bytes(N, C, HW); }
+int udapose_perturb(void* stream, const float* x, const float* g, const float* x0, int N, int C, int HW, int mode, const float* eps_dev,
+                    const float* step_dev, const float* lo, const float* hi, void* ws, float* out, float* gnorm) {
+    return perturb(S(stream), x, g, x0, N, C, HW, mode, eps_dev, step_dev, lo, hi, ws, out, gnorm);
+}
 long long udapose_net_grad_split_param(udapose_net_t n) { return net_grad_split_param(n); }
 int udapose_net_bind_update(udapose_net_t student, udapose_net_t teacher, void* const* params_s, void* const* grads, void* const* exp_avg,
                             void* const* exp_avg_sq, void* const* params_t, void* wpack_s, void* wpack_t) {

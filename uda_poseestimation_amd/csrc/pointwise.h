@@ -75,3 +75,7 @@ int pw_maxpool2x2_ceil(hipStream_t s, const elem_t* x, elem_t* y, int N, int H, 
 int pw_maxpool2x2_ceil_f32(hipStream_t s, const float* x, float* y, int N, int H, int W, int C);
 int pw_plane_sum(hipStream_t s, const float* x, float* out, int N, int C, int HW, float beta);
 unsigned long long sp_sat_read_pointwise(int reset);
+// gradient-direction perturbation inside an l2 / linf ball (perturb.hip): fp32 [N][C][HW]; eps / step device scalars; ws of perturb_ws_bytes
+long long perturb_ws_bytes(int N, int C, int HW);
+int perturb(hipStream_t s, const float* x, const float* g, const float* x0, int N, int C, int HW, int mode, const float* eps, const float* step,
+            const float* lo, const float* hi, void* ws, float* out, float* gnorm);

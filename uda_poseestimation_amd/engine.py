@@ -20,6 +20,7 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import adversarial
 from . import ops
 from . import optim as fused_optim
 from . import utils as mt
@@ -291,6 +292,16 @@ class MeanTeacherTrainer:
         # stu_optimizer.sync_hyper(), so a captured step follows a host change of it (a curriculum ramp).
         self.mask_mode, self.mask_threshold = "global", 0.5
         self._mask_thr = None               # [device scalar, the host value it holds]
+        # adv_eps (None: off): the student's target view is replaced by its adversarial view (adversarial.adversarial_view) -
+        # the view moved inside the adv_norm ("l2" / "linf") ball of radius adv_eps in the direction that increases the plain mean-squared
+        # distance between the student's re-warped heat-maps and the teacher's re-warped mean map (times the skeleton prior where one is
+        # set): the "strong view" of consistency training picked by gradient.  adv_steps (1 .. 4) probe passes of the student, none of which
+        # leaves a trace on it; adv_step: the step of an iteration (None: adv_eps for one step, 2.5 * adv_eps / adv_steps otherwise).  It
+        # runs after the occlusion, clamps to `recover`, and the rest of the step sees the perturbed view.  Attributes like the ones above;
+        # on / off, adv_norm and adv_steps are baked into a captured step, adv_eps / adv_step live in device scalars refreshed outside the
+        # graph (sync_adv).  Data parallel: the probes are per rank, before the split backward; nothing is communicated.
+        self.adv_eps, self.adv_norm, self.adv_steps, self.adv_step = None, "l2", 1, None
+        self._adv_dev = None                # [device scalars (eps, step), the host values they hold, the clamp on the device]
         # precision: None keeps what the networks are set to (a new PoseResNet is 'auto': a differentiable forward outside
         # autocast runs bf16, the teacher's no-grad forward the fp32-grade 'f16x2' mode).
         # 'reference' = the reference's own precision mix (train_human.py:346-358,414): the student in fp16 (its autocast dtype)
@@ -379,6 +390,35 @@ class MeanTeacherTrainer:
             self._mask_thr[0].copy_(torch.tensor(v, dtype=torch.float32), non_blocking=True)
             self._mask_thr[1] = v
         return self._mask_thr[0]
+
+    def sync_adv(self, device=None):
+        """The device scalars that hold adv_eps and the iterations' step, uploaded when a host value changed (stream-ordered 8-byte copy, like
+        sync_mask_threshold()); never inside a capture, whose launches read them.  -> (eps, step or None: the kernel's one-step form)."""
+        eps = float(self.adv_eps)
+        steps = int(self.adv_steps)
+        step = float(self.adv_step) if self.adv_step is not None else (eps if steps == 1 else 2.5 * eps / steps)
+        if self._adv_dev is None or (device is not None and self._adv_dev[0].device != torch.device(device)):
+            if device is None:
+                device = next(self.student.parameters()).device
+            clamp = None        # (`recover` on the device, made once: the view's clamp must not copy from the host inside a capture)
+            if self.recover is not None:
+                clamp = tuple(torch.as_tensor(v, dtype=torch.float32).detach().reshape(-1).to(device) for v in self.recover)
+            self._adv_dev = [torch.tensor([eps, step], dtype=torch.float32, device=device), (eps, step), clamp]
+        elif (eps, step) != self._adv_dev[1] and not torch.cuda.is_current_stream_capturing():
+            self._adv_dev[0].copy_(torch.tensor([eps, step], dtype=torch.float32), non_blocking=True)
+            self._adv_dev[1] = (eps, step)
+        d = self._adv_dev[0]
+        return d[0], (None if (steps == 1 and self.adv_step is None) else d[1])
+
+    def _adversarial_part(self, x_t_stu, theta_stu, target):
+        """(on the student's target stream, behind the teacher branch) the adversarial view of x_t_stu against the teacher's pseudo-labels."""
+        eps, step = self.sync_adv(x_t_stu.device)
+        cons = ConsLoss()
+
+        def probe_loss(y):      # no mask, no rectify: nothing is communicated, nothing moves out of _loss_backward_part
+            return cons(warp.warp_chain(y, theta_stu, self.warp_mode), target)
+        return adversarial.adversarial_view(self.student, x_t_stu, probe_loss, eps, norm=self.adv_norm, steps=self.adv_steps, step=step,
+                                            clamp=self._adv_dev[2], grad_scale=self.stu_optimizer.loss_scale())
 
     def _check_scaler(self):
         """An fp16 student forward needs the loss scaler the optimizer was built with (or the caller's own GradScaler: then build the
@@ -492,6 +532,7 @@ class MeanTeacherTrainer:
             self._side = (torch.cuda.Stream(device=x_s.device, priority=pr), torch.cuda.Stream(device=x_s.device, priority=pr))
         s_tea, s_stu = self._side if self.concurrent else (main, main)
         occl = self._occl if self.occlude_rate > -1 else None
+        adv, adv_gnorm = self.adv_eps is not None, None
         student.prepare(x_s)                # bf16 weight packs refreshed on `main` before the branches fork
         with torch.no_grad():
             teacher.prepare(x_t_teas[0])
@@ -507,9 +548,9 @@ class MeanTeacherTrainer:
                 y_t_tea_recon = mt.generate_prior_map(self.skeleton_prior, y_t_tea_raw, self.prior_gamma, self.prior_sigma, v3=self.prior_v3,
                                                       multiply=True)
                 tea_out = [y_t_tea_raw, y_t_tea_recon]
-        if occl is not None:
-            # the occlusion needs the teacher's re-warped heat-maps: the source-domain forward is issued first (it runs under
-            # the teacher's), the target-domain branch waits for the teacher
+        if occl is not None or adv:
+            # the occlusion (and the adversarial view) needs the teacher's re-warped heat-maps: the source-domain forward is issued first
+            # (it runs under the teacher's), the target-domain branch waits for the teacher
             y_s = student(x_s)
             s_stu.wait_stream(s_tea)
             for t in y_t_teas + recons + tea_out:
@@ -524,9 +565,11 @@ class MeanTeacherTrainer:
                     else:   # (one small D2H of confidences, as in the reference)
                         x_t_stu, self.occluded = warp.occlude_keypoints(x_t_stu, y_t_tea_recon, occl[1], self.ratio, self.image_px,
                                                                         self.occlude_rate, self.occlude_thresh, self.occlude_size, self.occl_rng)
+            if adv:
+                x_t_stu, adv_gnorm = self._adversarial_part(x_t_stu, theta_stu, y_t_tea_recon)
             y_t_stu = student.forward_deferred_bn(x_t_stu)     # separate forwards: separate BN statistics per domain
             y_t_stu_recon = warp.warp_chain(y_t_stu, theta_stu, self.warp_mode)
-        if occl is None:
+        if occl is None and not adv:
             y_s = student(x_s)
         main.wait_stream(s_stu)
         student.apply_deferred_bn()         # (x_s first, then x_t_stu: the reference's call order, train_human.py:414-417)
@@ -545,6 +588,9 @@ class MeanTeacherTrainer:
               "label_s": label_s, "weight_s": weight_s, "main": main, "s_stu": s_stu}
         if self.skeleton_prior is not None:
             st["y_t_tea_raw"] = y_t_tea_raw
+        if adv:
+            adv_gnorm.record_stream(main)
+            st["x_t_stu_adv"], st["adv_gnorm"] = x_t_stu, adv_gnorm
         return st
 
     def _overlap(self):
@@ -633,6 +679,8 @@ class MeanTeacherTrainer:
         if loss_coral is not None:
             out["loss_coral"] = loss_coral.detach()
             out["y_t_stu"] = st["y_t_stu"].detach()      # (what the criterion saw beside y_s: the target heat-maps before the re-warp)
+        if "x_t_stu_adv" in st:
+            out["x_t_stu_adv"], out["adv_gnorm"] = st["x_t_stu_adv"], st["adv_gnorm"]      # (the view the student saw; ||d probe loss / d x|| per sample)
         if "y_t_tea_raw" in st:
             # (y_t_tea_recon above IS the product: the teacher's map as the rest of the step saw it)
             out["prior_map"], out["y_t_tea_raw"] = st["y_t_tea_recon"], st["y_t_tea_raw"]
@@ -923,6 +971,8 @@ class GraphedTrainStep:
         self._frozen = self._frozen_hyper()
         if t.mask_mode == "threshold":
             t.sync_mask_threshold(self.static["x_s"].device)    # (the captured mask launch reads this scalar: it exists, and is current, before the capture)
+        if t.adv_eps is not None:
+            t.sync_adv(self.static["x_s"].device)               # (likewise the perturbation's eps / step)
         t.student._capture_token = t.teacher._capture_token = object()      # weight packs: captured once per network, unconditionally (pose_resnet._pack)
         self.g_fb, self.g_lb, self.g_lb2, self.g_up = torch.cuda.CUDAGraph(), None, None, None
         # overlap: the backward is cut after layer3 (two graph segments) and the finished gradient suffix is all-reduced on
@@ -1233,6 +1283,10 @@ class GraphedTrainStep:
         frozen.append(("max_grad_norm enabled", getattr(opt, "max_grad_norm", None) is not None))
         # the mask's mode picks the launch; mask_threshold lives on the device and may change freely (sync_mask_threshold)
         frozen.append(("mask_mode", str(t.mask_mode)))
+        # the adversarial view: on / off, the norm, the number of probes and whether a step is given pick the launches; adv_eps / adv_step
+        # live on the device and may change freely (sync_adv)
+        frozen += [("adv_eps enabled", t.adv_eps is not None), ("adv_norm", str(t.adv_norm)), ("adv_steps", int(t.adv_steps)),
+                   ("adv_step given", t.adv_step is not None)]
         for name, crit in (("criterion", t.criterion), ("con_criterion", t.con_criterion)):
             for k in ("topk", "largest"):
                 if hasattr(crit, k):
@@ -1290,6 +1344,8 @@ class GraphedTrainStep:
         seg("start")
         if self.t.mask_mode == "threshold":
             self.t.sync_mask_threshold()         # a curriculum ramp of mask_threshold -> the device scalar the captured mask launch reads
+        if self.t.adv_eps is not None:
+            self.t.sync_adv()                    # adv_eps / adv_step -> the device scalars the captured perturb launches read
         if self.one_graph:
             self.t.stu_optimizer.sync_hyper()    # lr scheduler / loss scale -> device state read by the captured sweep
         self.g_fb.replay()

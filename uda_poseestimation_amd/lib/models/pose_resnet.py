@@ -179,6 +179,8 @@ class PoseResNet(nn.Module):
         # (udapose_net_wgrad_pair): the passes end together and their weight-gradient launches are exposed at the step's end
         self.merge_wgrad = False
         self._pending_wg = []
+        self._probe = False           # inside input_grad_only(): forwards and backwards leave no trace (see there)
+        self._probe_grad = None       # (scratch gradient buffer of the probes' gradient chain, its pointer table)
         self._split_sum_hd = None     # the plan whose split sums finish_wgrad(defer_sum=True) left to the optimizer sweep (None: nothing pending)
         self.split_sums_deferred = 0  # how often that happened (tests)
         self._to_channels_last()
@@ -197,6 +199,7 @@ class PoseResNet(nn.Module):
         self._ptr_cache = None
         self._flat_grad = None
         self._flat_grad2 = None
+        self._probe_grad = None
         self._deferred_bn = []
         self._handles = {}
         self._drop_pending_step()
@@ -380,10 +383,10 @@ class PoseResNet(nn.Module):
                 hd.act_nograd = torch.empty(hd.act_bytes, dtype=torch.uint8, device=x.device)
             act, ws = hd.act_nograd, hd.ws
         out = torch.empty(hd.out_shape, dtype=torch.float32, device=x.device)
-        defer = bool(defer_bn) and self.training
+        defer = (bool(defer_bn) or self._probe) and self.training
         check(hd.L.udapose_net_forward(hd.h, s, ptr(x), pa, ba, ptr(hd.wpack), ptr(act), ptr(ws), ptr(out),
                                         int(self.training) | (2 if defer else 0), float(self.bn_momentum)), "net_forward")
-        if defer:
+        if defer and not self._probe:      # (a probe's batch statistics are dropped with its arena: the running statistics never see them)
             self._deferred_bn.append((hd, act))
         return out, (act if save else None), hd, (ws if save else None)
 
@@ -462,6 +465,8 @@ class PoseResNet(nn.Module):
             # (the stem's gradient chain is part 2: it runs later, in finish_backward(), outside this autograd node)
             raise RuntimeError("PoseResNet: an input that requires grad is not supported with split_backward = True (the stem's gradient chain runs "
                                "later, in finish_backward()); detach the input or clear split_backward")
+        if self._probe:
+            return self._run_probe_backward(dout, act, hd, ws, x_shape)
         pa, ba, params = self._pointers()
         views = self._grad_views(params)
         cur = torch.cuda.current_stream()
@@ -525,6 +530,58 @@ class PoseResNet(nn.Module):
             if p.requires_grad and id(p) not in nograd:
                 p.grad = v
         return dx
+
+    def _run_probe_backward(self, dout, act, hd, ws, x_shape):
+        """The backward of a probe (input_grad_only): the gradient chain alone where the plan's weight gradients are grouped launches
+        (udapose_net_backward_phase, phase 1: no weight-gradient launch at all), the whole backward otherwise (ungrouped plans are tiny test
+        plans) - either way into a scratch gradient buffer of the probes' own, laid out like the flat gradient buffer (so the plan's bound
+        tables serve it) and overwritten (beta 0) by every probe: the chain's BatchNorm dgamma / dbeta and the head's bias gradient land
+        there.  p.grad, _grad_state, _pending_wg, _pending_lower and the split-sum mark are not touched."""
+        pa, ba, params = self._pointers()
+        pg = self._probe_grad
+        if pg is None or pg[0].device != dout.device:
+            buf = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dout.device)
+            off, arr = 0, []
+            for p in params:
+                arr.append(buf.data_ptr() + 4 * off)
+                off += p.numel()
+            pg = self._probe_grad = (buf, (C.c_void_p * len(arr))(*arr))
+        gptrs = pg[1]
+        if gptrs[0] not in hd.bound_grads:
+            check(hd.L.udapose_net_bind_grads(hd.h, gptrs), "net_bind_grads")
+            hd.bound_grads.add(gptrs[0])
+        dout = dout.contiguous().float()
+        if hd.grouped:
+            check(hd.L.udapose_net_backward_phase(hd.h, _hip.stream(), ptr(dout), pa, ptr(hd.wpack), ptr(act), ptr(ws), gptrs, 0.0, 0, 1),
+                  "net_backward gradient chain (probe)")
+        else:
+            check(hd.L.udapose_net_backward(hd.h, _hip.stream(), ptr(dout), pa, ptr(hd.wpack), ptr(act), ptr(ws), gptrs, 0.0), "net_backward (probe)")
+        dx = torch.empty(x_shape, dtype=torch.float32, device=dout.device)
+        check(hd.L.udapose_net_input_grad(hd.h, _hip.stream(), pa, ptr(ws), ptr(dx)), "net_input_grad")
+        return dx
+
+    def input_grad_only(self, x, loss_fn):
+        """A probe: the training-mode forward of x, loss = loss_fn(y) (a scalar, built from differentiable torch / package ops), and the
+        backward to the INPUT only -> (d loss / d x [fp32, x's shape], loss.detach()).  It leaves no trace on the module: the BatchNorm
+        running statistics and num_batches_tracked are not updated (the forward runs with the update deferred and the deferred entry is
+        never queued), every p.grad is what it was (None stays None, gradient tensors keep their bits: the chain writes into a scratch
+        buffer, _run_probe_backward), and _grad_state / _pending_wg / _pending_lower / the split-sum mark are untouched.  The module must be
+        in training mode; not available with split_backward (as for any input that requires grad).  Like x.grad of forward(), the result
+        carries whatever scale loss_fn put on the loss."""
+        if not self.training:
+            raise RuntimeError("PoseResNet.input_grad_only: the module must be in training mode (an eval-mode forward keeps no backward state)")
+        if self.split_backward:
+            raise RuntimeError("PoseResNet.input_grad_only is not supported with split_backward = True")
+        params = list(self.parameters())
+        xi = x.detach().requires_grad_(True)
+        self._probe = True
+        try:
+            with torch.enable_grad():
+                loss = loss_fn(_PoseNetFn.apply(xi, self, True, True, *params))
+            dx, = torch.autograd.grad(loss, xi)
+        finally:
+            self._probe = False
+        return dx, loss.detach()
 
     def finish_wgrad(self, defer_sum=False):
         """Launch the grouped weight gradients of the backward passes that ran with merge_wgrad, on the current stream (the caller
