@@ -787,6 +787,27 @@ int udapose_split_saturations(int reset, unsigned long long* count);
 /* mean of k re-warped teacher heat-map tensors (train_human.py:361-372 with `--k` > 1: `torch.mean(recons, dim=0)` per sample): h_views = HOST
  * array of k (1..8) device pointers to fp32 tensors of n elements; dst[i] = (v0[i] + v1[i] + ...) / k, added in view order in fp32. */
 int udapose_mean_views(void* stream, const float* const* h_views, int k, float* dst, size_t n);
+/* Merge of the k re-warped teacher views BY AGREEMENT, one launch in place of udapose_mean_views.  h_views = HOST array of
+ * k (1..8) device pointers to contiguous fp32 tensors of R = B*K planes of H x W.  Per plane r and view v:
+ *   peak p_v = (idx % W, idx / W), idx = the first flat index of the plane's maximum (udapose_heatmap_argmax's order), maxval_v = that
+ *     maximum; view v is VALID on the plane iff maxval_v > 0.  d2(u, v) = the integer squared distance of p_u and p_v.
+ *   medoid = the valid view with the smallest sum of d2 to the other valid views, the lowest view index on a tie; none without a valid view.
+ *   inliers = the valid views with (float)d2(v, medoid) <= r * r, r = radius_dev[0] read on the device (fp32 product; inf admits every valid
+ *     view): inliers[r] holds bit v, n_inliers[r] their number - both 0 without a valid view.
+ *   spread2[r] = the largest d2 over pairs of valid views (0 with fewer than two).  agree[r] = 1.f iff n_inliers >= min_views (1..k), else 0.f.
+ *   mean, mode UDAPOSE_MERGE_MEAN: ((v0 + v1) + ...) / (float)k per pixel in fp32, in view order - the bits of udapose_mean_views;
+ *     mode UDAPOSE_MERGE_TRIMMED: the same over the inlier views only, in view order, divided by (float)n_inliers; a plane without an inlier
+ *     gets the MEAN value (its agree is 0).
+ *   energy[r] (optional) = the mean over pixels of sum_v (v - m)^2 / k, m = the MEAN value of the pixel, over ALL views in either mode;
+ *     the pixels are added in a fixed order (double precision): the same bits on every run.
+ * peaks [k][R][2] int (x, y), maxvals [k][R], inliers / n_inliers / spread2 [R] int, agree / energy [R] float: every output but mean may be NULL.
+ * No atomics.  16-byte accesses when H * W % 4 == 0 and every tensor is 16-byte aligned, element by element otherwise (the same bits).
+ * UDAPOSE_ERR_ARG, before any launch and with nothing written: k outside 1..8, a NULL view / mean / radius_dev, min_views outside 1..k,
+ * R, H or W < 1, H or W > 2048, an unknown mode. */
+#define UDAPOSE_MERGE_MEAN 0
+#define UDAPOSE_MERGE_TRIMMED 1
+int udapose_view_merge(void* stream, const float* const* h_views, int k, int R, int H, int W, int mode, const float* radius_dev, int min_views,
+                       float* mean, int* peaks, float* maxvals, int* inliers, int* n_inliers, int* spread2, float* agree, float* energy);
 /* the loop's matrices on the device, in double precision, from the collated aug_param of lib/transforms/keypoint_detection.py:139:
  * params[n] = (angle, tx, ty, shear_x, shear_y, scale), angles in degrees (6 doubles per sample).  theta_fwd [N][3][6] (may be NULL):
  * translate by (tx, ty) / ratio | rotate by angle and scale | shear - the three warps of train_human.py:366-368,421-423;

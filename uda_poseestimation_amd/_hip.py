@@ -182,6 +182,7 @@ _SIGS = {
     "udapose_gaussian_labels_subpixel": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, cd, cd, cd, ci]),
     "udapose_split_saturations": (ci, [ci, vp]),
     "udapose_mean_views": (ci, [vp, vp, ci, vp, sz]),
+    "udapose_view_merge": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
     "udapose_draw_labelmap_ori": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, cf, vp, ci]),
     "udapose_prof_begin": (None, []),
     "udapose_prof_end": (ci, [vp]),

@@ -560,6 +560,11 @@ int udapose_split_saturations(int reset, unsigned long long* count) {
 int udapose_mean_views(void* stream, const float* const* h_views, int k, float* dst, size_t n) {
     return affine_mean_views(S(stream), h_views, k, dst, n);
 }
+int udapose_view_merge(void* stream, const float* const* h_views, int k, int R, int H, int W, int mode, const float* radius_dev, int min_views,
+                       float* mean, int* peaks, float* maxvals, int* inliers, int* n_inliers, int* spread2, float* agree, float* energy) {
+    return affine_view_merge(S(stream), h_views, k, R, H, W, mode, radius_dev, min_views, mean, peaks, maxvals, inliers, n_inliers, spread2, agree,
+                             energy);
+}
 int udapose_affine_nearest(void* stream, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward) {
     return affine_warp_chain(S(stream), src, dst, theta, N, C, H, W, nstage, backward);
 }

@@ -1,4 +1,4 @@
-// Host launchers of the data pipeline: warps, occlusion and patches (affine.hip), image augmentation and label maps (augment.hip).
+// Host launchers of the data pipeline: warps, occlusion and patches (affine.hip), the merge of the teacher's views (view_merge.hip), image augmentation and label maps (augment.hip).
 #pragma once
 #include "common.h"
 
@@ -11,6 +11,9 @@ int affine_recon_thetas(hipStream_t s, const double* params, int N, double ratio
 int affine_warp_chain(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward);
 int affine_warp_chain_bilinear(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward);
 int affine_mean_views(hipStream_t s, const float* const* srcs, int k, float* dst, size_t n);
+// view_merge.hip
+int affine_view_merge(hipStream_t s, const float* const* srcs, int k, int R, int H, int W, int mode, const float* radius_dev, int min_views,
+                      float* mean, int* peaks, float* maxvals, int* inliers, int* n_inliers, int* spread2, float* agree, float* energy);
 // augment.hip
 int aug_resized_crop_u8(hipStream_t s, const unsigned char* src, unsigned char* dst, unsigned char* tmp, const int* box, const int* bounds,
                         const int* coef, int N, int Hs, int Ws, int S, int ksize);

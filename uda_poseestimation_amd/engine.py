@@ -302,6 +302,16 @@ class MeanTeacherTrainer:
         # graph (sync_adv).  Data parallel: the probes are per rank, before the split backward; nothing is communicated.
         self.adv_eps, self.adv_norm, self.adv_steps, self.adv_step = None, "l2", 1, None
         self._adv_dev = None                # [device scalars (eps, step), the host values they hold, the clamp on the device]
+        # view_merge (None: off, the plain warp.mean_views): "mean" or "trimmed" - the k >= 2 re-warped teacher views are merged by agreement
+        # (warp.merge_views): per (sample, joint) the views whose peak lies within view_radius heat-map pixels of the medoid
+        # peak are the inliers; "trimmed" averages the inliers only, "mean" keeps the plain mean; either way a joint on which fewer than
+        # view_min views (None: all k) are inliers is taken out of the consistency mask, in every mask_mode (the gate is confidence_mask's
+        # tea_mask=).  The skeleton prior, the occlusion picks, `activates`, rectify and the adversarial probe see the merged map as they see
+        # the mean.  The step's dict gains view_agree, view_n_inliers, view_spread2.  Attributes like the ones above; view_radius lives in a
+        # device scalar refreshed outside any graph (sync_view_radius).  GraphedTrainStep stages one teacher view and refuses a trainer with
+        # view_merge set.  Data parallel: the views, their peaks and the gate are per rank and per sample; nothing is communicated.
+        self.view_merge, self.view_radius, self.view_min = None, 2.0, None
+        self._view_rad = None               # [device scalar, the host value it holds]
         # precision: None keeps what the networks are set to (a new PoseResNet is 'auto': a differentiable forward outside
         # autocast runs bf16, the teacher's no-grad forward the fp32-grade 'f16x2' mode).
         # 'reference' = the reference's own precision mix (train_human.py:346-358,414): the student in fp16 (its autocast dtype)
@@ -391,6 +401,29 @@ class MeanTeacherTrainer:
             self._mask_thr[1] = v
         return self._mask_thr[0]
 
+    def sync_view_radius(self, device=None):
+        """The device scalar that holds view_radius, uploaded when the host value changed (a stream-ordered 4-byte copy, like
+        sync_mask_threshold()); never inside a capture, whose launch reads the scalar."""
+        v = float(self.view_radius)
+        if self._view_rad is None or (device is not None and self._view_rad[0].device != torch.device(device)):
+            if device is None:
+                device = next(self.student.parameters()).device
+            self._view_rad = [torch.tensor(v, dtype=torch.float32, device=device), v]
+        elif v != self._view_rad[1] and not torch.cuda.is_current_stream_capturing():
+            self._view_rad[0].copy_(torch.tensor(v, dtype=torch.float32), non_blocking=True)
+            self._view_rad[1] = v
+        return self._view_rad[0]
+
+    def _check_view_merge(self, k):
+        """view_merge set: a mode warp.merge_views knows, and at least two teacher views to merge."""
+        if self.view_merge is None:
+            return
+        if self.view_merge not in warp.MERGE_MODES:
+            raise ValueError(f"trainer.view_merge = {self.view_merge!r}: None or one of {tuple(warp.MERGE_MODES)}")
+        if k < 2:
+            raise ValueError(f"trainer.view_merge = {self.view_merge!r} merges the teacher's views by their agreement and needs at least two "
+                             f"of them per step, got {k} (pass a list of k >= 2 target views, or set trainer.view_merge = None)")
+
     def sync_adv(self, device=None):
         """The device scalars that hold adv_eps and the iterations' step, uploaded when a host value changed (stream-ordered 8-byte copy, like
         sync_mask_threshold()); never inside a capture, whose launches read them.  -> (eps, step or None: the kernel's one-step form)."""
@@ -454,6 +487,7 @@ class MeanTeacherTrainer:
         """Eager step from the loader's collated batch (aug_param tuples as produced by the reference's transforms)."""
         if not isinstance(x_t_teas, (list, tuple)):
             x_t_teas, aug_params_tea = [x_t_teas], [aug_params_tea]
+        self._check_view_merge(len(x_t_teas))
         n, dev = x_t_stu.shape[0], x_t_stu.device
         theta_stu = warp.recon_thetas(aug_param_stu, n, self.ratio, dev)
         thetas_tea = [warp.recon_thetas(ap, n, self.ratio, dev) for ap in aug_params_tea]
@@ -533,7 +567,10 @@ class MeanTeacherTrainer:
         s_tea, s_stu = self._side if self.concurrent else (main, main)
         occl = self._occl if self.occlude_rate > -1 else None
         adv, adv_gnorm = self.adv_eps is not None, None
-        student.prepare(x_s)                # bf16 weight packs refreshed on `main` before the branches fork
+        self._check_view_merge(len(x_t_teas))
+        view_rad = self.sync_view_radius(x_s.device) if self.view_merge is not None else None      # (on `main`, before the branches fork)
+        merged = None
+        student.prepare(x_s)               # bf16 weight packs refreshed on `main` before the branches fork
         with torch.no_grad():
             teacher.prepare(x_t_teas[0])
         s_tea.wait_stream(main)
@@ -541,13 +578,19 @@ class MeanTeacherTrainer:
         with torch.cuda.stream(s_tea), torch.no_grad():
             y_t_teas = [teacher(x_t) for x_t in x_t_teas]
             recons = [warp.warp_chain(y, th, self.warp_mode) for y, th in zip(y_t_teas, thetas_tea)]
-            y_t_tea_recon = warp.mean_views(recons)          # (k teacher views, train_human.py:361-372: one launch; k = 1: the view itself)
-            tea_out = [y_t_tea_recon]
+            if self.view_merge is None:
+                y_t_tea_recon = warp.mean_views(recons)      # (k teacher views, train_human.py:361-372: one launch; k = 1: the view itself)
+                tea_out = [y_t_tea_recon]
+            else:
+                # the same launch slot: the views' mean (of the inliers in "trimmed" mode) plus the per-joint agreement gate of the mask
+                merged = warp.merge_views(recons, view_rad, self.view_merge, self.view_min)
+                y_t_tea_recon = merged.mean
+                tea_out = [t for t in merged if t is not None]
             if self.skeleton_prior is not None:
                 y_t_tea_raw = y_t_tea_recon
                 y_t_tea_recon = mt.generate_prior_map(self.skeleton_prior, y_t_tea_raw, self.prior_gamma, self.prior_sigma, v3=self.prior_v3,
                                                       multiply=True)
-                tea_out = [y_t_tea_raw, y_t_tea_recon]
+                tea_out = tea_out + [y_t_tea_recon]
         if occl is not None or adv:
             # the occlusion (and the adversarial view) needs the teacher's re-warped heat-maps: the source-domain forward is issued first
             # (it runs under the teacher's), the target-domain branch waits for the teacher
@@ -588,6 +631,8 @@ class MeanTeacherTrainer:
               "label_s": label_s, "weight_s": weight_s, "main": main, "s_stu": s_stu}
         if self.skeleton_prior is not None:
             st["y_t_tea_raw"] = y_t_tea_raw
+        if merged is not None:
+            st["view_agree"], st["view_n_inliers"], st["view_spread2"] = merged.agree, merged.n_inliers, merged.spread2
         if adv:
             adv_gnorm.record_stream(main)
             st["x_t_stu_adv"], st["adv_gnorm"] = x_t_stu, adv_gnorm
@@ -639,8 +684,9 @@ class MeanTeacherTrainer:
         with torch.no_grad():
             # threshold = k-th value over the GLOBAL batch (all-gather of [N,K] floats when data parallel)
             thr_dev = self.sync_mask_threshold(st["activates"].device) if self.mask_mode == "threshold" else None
-            tea_mask, _, mask_thr = mt.confidence_mask(st["y_t_tea_recon"], self.mask_ratio, None, gathered_activates, st["activates"],
-                                                       mode=self.mask_mode, threshold=thr_dev)
+            # (view_agree: the 0 / 1 agreement gate of the merged teacher views, absent with view_merge off)
+            tea_mask, _, mask_thr = mt.confidence_mask(st["y_t_tea_recon"], self.mask_ratio, st.get("view_agree"), gathered_activates,
+                                                       st["activates"], mode=self.mask_mode, threshold=thr_dev)
             y_t_tea_rect = st["y_t_tea_rect"] if st.get("y_t_tea_rect") is not None else mt.rectify(st["y_t_tea_recon"], sigma=self.sigma)
         loss_c = self.con_criterion(st["y_t_stu_recon"], y_t_tea_rect, tea_mask=tea_mask)
         loss_all = loss_s + self.lambda_c * loss_c
@@ -679,6 +725,8 @@ class MeanTeacherTrainer:
         if loss_coral is not None:
             out["loss_coral"] = loss_coral.detach()
             out["y_t_stu"] = st["y_t_stu"].detach()      # (what the criterion saw beside y_s: the target heat-maps before the re-warp)
+        if "view_agree" in st:
+            out["view_agree"], out["view_n_inliers"], out["view_spread2"] = st["view_agree"], st["view_n_inliers"], st["view_spread2"]
         if "x_t_stu_adv" in st:
             out["x_t_stu_adv"], out["adv_gnorm"] = st["x_t_stu_adv"], st["adv_gnorm"]      # (the view the student saw; ||d probe loss / d x|| per sample)
         if "y_t_tea_raw" in st:
@@ -858,6 +906,10 @@ class GraphedTrainStep:
     def _refuse_uncapturable(self, x_t_stu):
         t = self.t
         self._style = _StyleAdapter(t.style_net, captured=True) if t.style_net is not None else None     # (TypeError: a net with the plain call only)
+        if t.view_merge is not None:
+            raise ValueError(f"GraphedTrainStep stages a single teacher view per step, and trainer.view_merge = {t.view_merge!r} merges k >= 2 "
+                             "of them: use the eager train_step (the merge launch itself is capturable: warp.merge_views), or set "
+                             "trainer.view_merge = None before building the captured step")
         self.styled, self.occl = self._style is not None, t.occlude_rate > -1
         if self.occl and not t.device_occlusion:
             raise RuntimeError("GraphedTrainStep with occlusion needs trainer.device_occlusion = True (the reference's host draws read "
@@ -1287,6 +1339,8 @@ class GraphedTrainStep:
         # live on the device and may change freely (sync_adv)
         frozen += [("adv_eps enabled", t.adv_eps is not None), ("adv_norm", str(t.adv_norm)), ("adv_steps", int(t.adv_steps)),
                    ("adv_step given", t.adv_step is not None)]
+        # the merge of k teacher views is refused at construction (_refuse_uncapturable): it cannot be switched on afterwards either
+        frozen.append(("view_merge", t.view_merge))
         for name, crit in (("criterion", t.criterion), ("con_criterion", t.con_criterion)):
             for k in ("topk", "largest"):
                 if hasattr(crit, k):

@@ -9,6 +9,7 @@ affine matrices are built on the host in double precision exactly like torchvisi
 (torchvision itself is not a dependency); parameters arrive as the collated `aug_param` structure of
 lib/transforms/keypoint_detection.py:139: [angle[N], [tx[N], ty[N]], [sx[N], sy[N]], scale[N]].
 """
+import collections
 import math
 
 import torch
@@ -183,6 +184,55 @@ def mean_views(views):
     out = torch.empty_like(vs[0])
     arr = (C.c_void_p * len(vs))(*[v.data_ptr() for v in vs])
     check(lib().udapose_mean_views(_hip.stream(), arr, len(vs), ptr(out), out.numel()), "mean_views")
+    return out
+
+
+MERGE_MODES = {"mean": 0, "trimmed": 1}          # UDAPOSE_MERGE_MEAN / UDAPOSE_MERGE_TRIMMED
+MergedViews = collections.namedtuple("MergedViews", "mean peaks maxvals inliers n_inliers spread2 agree energy")
+
+
+def merge_views(views, radius=2.0, mode="mean", min_views=None, want_energy=False):
+    """The k re-warped teacher heat-map tensors [B,K,H,W] merged BY AGREEMENT (udapose_view_merge), one launch in place of
+    mean_views.  Per (sample, joint): every view's peak (first flat arg-max, the order of get_max_preds_torch_raw) and maximum; a view is
+    valid where its maximum is > 0; the medoid is the valid view with the smallest sum of squared peak distances to the other valid views
+    (lowest view on a tie); the inliers are the valid views within `radius` heat-map pixels of the medoid ((float)d2 <= radius * radius).
+    mode "mean": the plain mean, the bits of mean_views; "trimmed": the mean of the inliers only, in view order (the plain mean where there
+    is none).  agree = 1.0 where at least `min_views` (1..k, default k: every view) are inliers, else 0.0 - the per-joint gate that
+    utils.confidence_mask takes as tea_mask=.  `radius`: a float, or a 0-d fp32 device tensor that is read on the device (no
+    synchronisation; a captured launch follows its value).  want_energy: also the mean over pixels of the k views' variance.
+    -> MergedViews(mean [B,K,H,W], peaks [k,B,K,2] int32 (x, y), maxvals [k,B,K], inliers [B,K] int32 (bit v = view v), n_inliers [B,K]
+    int32, spread2 [B,K] int32 (largest squared distance between valid peaks), agree [B,K] fp32, energy [B,K] fp32 | None)."""
+    import ctypes as C
+    k = len(views)
+    if k < 1:
+        raise ValueError("merge_views: no views")
+    if k > 8:
+        raise NotImplementedError("at most 8 teacher views per step (the reference's --k defaults to 1)")
+    if mode not in MERGE_MODES:
+        raise ValueError(f"merge_views: mode {mode!r}: one of {tuple(MERGE_MODES)}")
+    min_views = k if min_views is None else int(min_views)
+    if not 1 <= min_views <= k:
+        raise ValueError(f"merge_views: min_views = {min_views} is outside 1 ... {k} (the number of views)")
+    _hip.require_cuda(*views, radius if torch.is_tensor(radius) else None)
+    vs = [v.detach().float().contiguous() for v in views]
+    if vs[0].dim() != 4 or any(v.shape != vs[0].shape for v in vs):
+        raise ValueError(f"merge_views: the views must share one [B,K,H,W] shape, got {[tuple(v.shape) for v in vs]}")
+    B, K, H, W = vs[0].shape
+    dev = vs[0].device
+    if torch.is_tensor(radius):
+        if radius.numel() != 1:
+            raise ValueError(f"merge_views: radius must be a float or a 0-d tensor, got shape {tuple(radius.shape)}")
+        rad = radius.detach().reshape(())
+        if rad.dtype != torch.float32:
+            rad = rad.float()
+    else:
+        rad = torch.full((), float(radius), dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = MergedViews(torch.empty_like(vs[0]), torch.empty(k, B, K, 2, **i32), torch.empty(k, B, K, dtype=torch.float32, device=dev),
+                      torch.empty(B, K, **i32), torch.empty(B, K, **i32), torch.empty(B, K, **i32),
+                      torch.empty(B, K, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.float32, device=dev) if want_energy else None)
+    arr = (C.c_void_p * k)(*[v.data_ptr() for v in vs])
+    check(lib().udapose_view_merge(_hip.stream(), arr, k, B * K, H, W, MERGE_MODES[mode], ptr(rad), min_views, *[ptr(t) for t in out]), "view_merge")
     return out
 
 
