@@ -581,6 +581,38 @@ int udapose_thr_mask(void* stream, const float* act, const float* tea_mask, size
 /* PCK (lib/keypoint_detection.py:40-94) from decoded coordinates [B,K,2]; acc[K], avg_cnt[2] = (avg_acc, cnt) */
 int udapose_pck(void* stream, const float* pred_xy, const float* gt_xy, int B, int K, float norm_x, float norm_y, float thr, float* acc,
                 float* avg_cnt);
+/* ---- evaluation meter (csrc/pck_curve.hip): a PCK curve, the visible count and the end-point error of a whole set, kept on the device as
+ * integers.  state is an int64 array [K][T + 3]; row k belongs to joint k and its columns are
+ *     0 .. T-1 : hits[j], the visible (sample, joint) pairs with d < thr[j]
+ *     T        : count, the visible pairs
+ *     T + 1    : epe_q, the sum over the visible pairs with a finite error of llrintf(e * UDAPOSE_PCK_EPE_SCALE)
+ *     T + 2    : nonfinite, the visible pairs whose e is NaN, infinite or >= 2^46 px (they add nothing to epe_q)
+ * The caller zeroes state once; a call only ADDS, with integer adds alone (registers, wave shuffles, LDS integer atomics, one 64-bit
+ * integer atomic per touched column), so the state after a set is the same bits whatever the batch split, the grid or the order of
+ * arrival; no floating-point atomics, no scratch, no host synchronisation: capturable.
+ * Per visible pair (b, k), prediction (px, py), target (tx, ty), every operation one correctly rounded fp32 operation (no FMA):
+ *     e = sqrtf((px-tx)*(px-tx) + (py-ty)*(py-ty))                                    heat-map pixels
+ *     norm == NULL: dx = px / nh - tx / nh, dy = py / nw - ty / nw, d = sqrtf(dx*dx + dy*dy)   (udapose_pck's expression: x over the
+ *                   HEIGHT term nh = H / 10, y over nw = W / 10, the reference's pairing)
+ *     norm [B]    : d = e / norm[b]; a norm[b] that is not finite and > 0 makes the sample's joints count as not visible
+ *     threshold j is hit iff d < thr[j] (strict; a NaN d hits nothing and is still counted)
+ * thr [T] fp32 on the device, strictly ascending (the CALLER's duty: it lives on the device, the first hit is found by bisection and the
+ * columns equal the T independent compares only for an ascending table), 1 <= T <= UDAPOSE_PCK_MAX_THRESHOLDS.
+ * udapose_pck_accumulate: pred_xy, gt_xy [B][K][2].  Visible: visible[b*K + k] != 0, or with a NULL visible the reference's rule on the
+ *   target, tx > 1 && ty > 1.  One work-group per (joint, 256 samples), a lane per sample.
+ * udapose_pck_accumulate_heatmaps: out, target [B][K][H][W]; one work-group per (b, k) reduces both planes (16-byte loads when H*W % 4 == 0
+ *   and both pointers are 16-byte aligned) in udapose_heatmap_argmax's order, bit for bit: first flat index on ties, NaN as the largest
+ *   value, (0, 0) where the maximum is <= 0.  nh = H / 10, nw = W / 10; visible by tx > 1 && ty > 1 on the target's arg-max.  preds_xy
+ *   [B][K][2] (may be NULL) receives exactly what udapose_heatmap_argmax returns for out.  H * W <= 1 << 30.
+ * UDAPOSE_ERR_ARG: a null required pointer (everything but visible, norm, preds_xy), B, K, T (H, W) < 1, T > UDAPOSE_PCK_MAX_THRESHOLDS,
+ * B * K > INT_MAX.  UDAPOSE_ERR_UNSUPPORTED: K > UDAPOSE_PCK_MAX_KEYPOINTS.  On a refusal nothing is launched. */
+#define UDAPOSE_PCK_MAX_THRESHOLDS 64
+#define UDAPOSE_PCK_MAX_KEYPOINTS 256
+#define UDAPOSE_PCK_EPE_SCALE 65536
+int udapose_pck_accumulate(void* stream, const float* pred_xy, const float* gt_xy, const unsigned char* visible, const float* norm, int B, int K,
+                           float nh, float nw, const float* thr, int T, long long* state);
+int udapose_pck_accumulate_heatmaps(void* stream, const float* out, const float* target, const float* norm, int B, int K, int H, int W,
+                                    const float* thr, int T, long long* state, float* preds_xy);
 
 /* ---------------------------------------------------------------- optimizer sweeps over many tensors (device tables) */
 int udapose_multi_chunk(void);

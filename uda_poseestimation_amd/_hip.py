@@ -157,6 +157,8 @@ _SIGS = {
     "udapose_joint_kth_mask": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, vp, vp]),
     "udapose_thr_mask": (ci, [vp, vp, vp, sz, vp, vp]),
     "udapose_pck": (ci, [vp, vp, vp, ci, ci, cf, cf, cf, vp, vp]),
+    "udapose_pck_accumulate": (ci, [vp, vp, vp, vp, vp, ci, ci, cf, cf, vp, ci, vp]),
+    "udapose_pck_accumulate_heatmaps": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, vp]),
     "udapose_multi_chunk": (ci, []),
     "udapose_ema_multi": (ci, [vp, vp, vp, vp, vp, vp, ci, cf, cf]),
     "udapose_adam_multi": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, cf, cf, cf, cf, cf, ci, cf, vp]),

@@ -457,6 +457,14 @@ int udapose_thr_mask(void* stream, const float* act, const float* tm, size_t n, 
 int udapose_pck(void* stream, const float* pred, const float* gt, int B, int K, float nx, float ny, float thr, float* acc, float* avg_cnt) {
     return hm_pck(S(stream), pred, gt, B, K, nx, ny, thr, acc, avg_cnt);
 }
+int udapose_pck_accumulate(void* stream, const float* pred_xy, const float* gt_xy, const unsigned char* visible, const float* norm, int B, int K,
+                           float nh, float nw, const float* thr, int T, long long* state) {
+    return pck_accumulate(S(stream), pred_xy, gt_xy, visible, norm, B, K, nh, nw, thr, T, state);
+}
+int udapose_pck_accumulate_heatmaps(void* stream, const float* out, const float* target, const float* norm, int B, int K, int H, int W,
+                                    const float* thr, int T, long long* state, float* preds_xy) {
+    return pck_accumulate_heatmaps(S(stream), out, target, norm, B, K, H, W, thr, T, state, preds_xy);
+}
 int udapose_multi_chunk(void) { return opt_chunk(); }
 int udapose_ema_multi(void* stream, const long long* t, const long long* s, const long long* sizes, const int* bt, const long long* bo, int nb,
                       float alpha, float oma) {

@@ -141,6 +141,23 @@ __device__ __forceinline__ bool hm_better(float v, int i, float bv, int bi) {
     if (vn) return i < bi;
     return v > bv || (v == bv && i < bi);
 }
+// The block arg-max of refine.hip and pck_curve.hip: every thread of a block of WAVES waves brings its own best (value, flat index) and
+// returns the block's, under hm_better (a total order: the winner does not depend on the reduction tree).  sv, si: WAVES entries of LDS.
+template <int WAVES>
+__device__ __forceinline__ void hm_block_best(float& bv, int& bi, float* sv, int* si) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (hm_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    __syncthreads();      // (sv, si may still be read from the previous reduction)
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    bv = sv[0]; bi = si[0];
+    for (int w = 1; w < WAVES; ++w)
+        if (hm_better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -13,6 +13,11 @@ int hm_argmax_rectify(hipStream_t s, const float* hm, int R, int H, int W, float
 int hm_kth_mask(hipStream_t s, const float* act, const float* tm, int n, int k, float* thr_out, unsigned char* mask, const float* act_local,
                 int n_local);
 int hm_pck(hipStream_t s, const float* pred, const float* gt, int B, int K, float nh, float nw, float thr, float* acc, float* avg_cnt);
+// pck_curve.hip
+int pck_accumulate(hipStream_t s, const float* pred, const float* gt, const unsigned char* visible, const float* norm, int B, int K, float nh,
+                   float nw, const float* thr, int T, long long* state);
+int pck_accumulate_heatmaps(hipStream_t s, const float* out, const float* target, const float* norm, int B, int K, int H, int W,
+                            const float* thr, int T, long long* state, float* preds);
 // select.hip
 int sel_topk(hipStream_t s, const float* rows, const float* wfac, const unsigned char* mfac, int N, int K, int topk, int largest,
              unsigned char* sel, float* sample, float* mean_out);

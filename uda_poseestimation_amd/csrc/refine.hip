@@ -17,21 +17,8 @@ constexpr int MAX_TAPS = 31;
 constexpr size_t LDS_BUDGET = (size_t)UDAPOSE_REFINE_MAX_PIXELS * 2 * sizeof(float);      // 150 KiB of the CU's 160
 struct Taps { float t[MAX_TAPS]; };
 
-// every thread returns the block's best (value, flat index) under hm_better
-__device__ __forceinline__ void block_best(float& bv, int& bi, float* sv, int* si) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (hm_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    __syncthreads();      // (sv, si may still be read from the previous reduction)
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    bv = sv[0]; bi = si[0];
-    for (int w = 1; w < TPB / 64; ++w)
-        if (hm_better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
-}
+// every thread returns the block's best (value, flat index) under hm_better: common.h's block arg-max
+__device__ __forceinline__ void block_best(float& bv, int& bi, float* sv, int* si) { hm_block_best<TPB / 64>(bv, bi, sv, si); }
 __device__ __forceinline__ float sign_or_0(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }      // (NaN: 0)
 
 template <int MODE>

@@ -868,6 +868,66 @@ def validate_flip(batches, model, flip_pairs, criterion=None, decode="argmax", s
     return validate(batches, flipped, criterion, decode=flipped.decoded if fused else decode)
 
 
+def evaluate(batches, model, thresholds=kd.PCK_THRESHOLDS, groups=None, criterion=None, decode="argmax", flip_pairs=None, shift_heatmap=False,
+             norm=None, pixel_scale=1.0):
+    """validate()'s loop (eval mode, no grad, the mode restored, the saturation warning) with a lib.keypoint_detection.PCKMeter in place of
+    the per-batch PCK: the report of the whole set - PCK at every threshold of a curve, its AUC, the end-point error, joint groups - from
+    integer counts kept on the device, so the numbers do not depend on how the set is cut into batches (validate()'s batch-weighted mean of
+    per-batch fractions does: DESIGN.md 4.18) and nothing is read back before the end.  `batches` yields (x, label, weight[, meta]); a meta
+    that is a dict with "target_coords" ([B,K,2] in heat-map pixels; optionally "visible" [B,K]) is scored against those instead of the
+    label's arg-max.  thresholds: in the unit of `accuracy`'s thr (0.5 is PCK@0.05).  groups: a key of JOINT_GROUPS or a mapping, what the
+    reference's dataset.group_accuracy(acc.average()) prints.  decode: as in validate().  flip_pairs: given, the forward is
+    flip_forward's (shift_heatmap as there), and with decode="argmax" the merge launch's own decode is scored.  norm: None or a callable
+    batch -> [B] device tensor of per-sample lengths in heat-map pixels.  Returns PCKMeter.report()'s dict plus "loss" (the batch-size
+    weighted mean, as validate()) and "n" (the samples seen)."""
+    criterion = criterion or JointsMSELoss()
+    dev = next(model.parameters()).device
+    meter = kd.PCKMeter(model.num_keypoints, thresholds, device=dev)      # (bad thresholds fail here, before any forward)
+    if groups is not None:
+        kd._joint_groups(groups)
+    run = model
+    if flip_pairs is not None:
+        kd.flip_perm(flip_pairs, model.num_keypoints)
+        fused = isinstance(decode, str) and decode == "argmax"
+        run = _FlipTestModel(model, flip_pairs, shift_heatmap, fused)
+        if fused:
+            decode = run.decoded
+    was_training = run.training
+    run.eval()
+    loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
+    n_seen = 0
+    with torch.no_grad():
+        for batch in batches:
+            x, label, weight = batch[0], batch[1], batch[2]
+            x, label, weight = x.to(dev, non_blocking=True), label.to(dev, non_blocking=True), weight.to(dev, non_blocking=True)
+            meta = batch[3] if len(batch) > 3 and isinstance(batch[3], dict) and "target_coords" in batch[3] else None
+            y = run(x)
+            loss = criterion(y, label, weight)
+            length = norm(batch) if norm is not None else None
+            if meta is not None:
+                vis = meta.get("visible")
+                meter.update(y, decode=decode, target_coords=meta["target_coords"].to(dev), visible=None if vis is None else vis.to(dev),
+                             norm=length)
+            else:
+                meter.update(y, label, decode=decode, norm=length)
+            n = x.shape[0]
+            loss_sum += loss.detach().double() * n
+            n_seen += n
+    if was_training:
+        run.train()
+    # the one read-back: the counts and the mean loss's bits in one int64 copy
+    mean_loss = (loss_sum / max(n_seen, 1)) if n_seen else torch.full_like(loss_sum, float("nan"))
+    packed = torch.cat([meter.state().reshape(-1), mean_loss.reshape(1).view(torch.int64)]).cpu()
+    rep = kd.PCKMeter.report(packed[:-1].reshape(meter.state().shape), meter.thresholds, groups, pixel_scale)
+    rep["loss"], rep["n"] = float(packed[-1:].view(torch.float64)), n_seen
+    sat = mt.split_saturations(reset=True)          # (as validate(): the evaluation forward runs the f16x2 mode under 'auto')
+    if sat:
+        import warnings
+        warnings.warn(f"evaluate(): {sat} f16x2 stores saturated at |x| = 65504 (or were NaN) since the last check - activations outside fp16's "
+                      "range; run the model with precision='fp32' (exact, slower) to rule the format out")
+    return rep
+
+
 class GraphedTrainStep:
     """The mean-teacher step captured into hipGraphs: ~1300 kernel launches per step are replayed by ONE graph launch on one
     rank (forwards, losses, backward, Adam + EMA + packs), which removes the host launch gaps.

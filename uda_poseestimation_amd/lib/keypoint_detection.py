@@ -1,7 +1,9 @@
 """Arg-max decode and PCK (API mirror of the reference's lib/keypoint_detection.py:9-94) on MI355X kernels, and the soft-argmax
 decode the reference lacks (`soft_argmax`, csrc/softargmax.hip: sub-pixel coordinates, differentiable), the two published sub-pixel
 decodes (`quarter_decode`, `dark_decode`, csrc/refine.hip: one launch, not differentiable), and the flip test's heat-map side
-(`flip_perm`, `flip_back`, `flip_merge`, csrc/flip.hip: flip back, swap left / right joints, average, decode - one launch).
+(`flip_perm`, `flip_back`, `flip_merge`, csrc/flip.hip: flip back, swap left / right joints, average, decode - one launch), and the
+evaluation report of a whole set (`PCKMeter`, `PCK_THRESHOLDS`, `JOINT_GROUPS`, `group_accuracy`, csrc/pck_curve.hip: a PCK curve, its
+AUC, the end-point error and the reference's joint groups from integer counts kept on the device).
 
 The reference takes numpy arrays (it is called on `.cpu().numpy()` copies, train_human.py:289,443).  The same calls work
 here; torch CUDA tensors are accepted as well and avoid the 2 x 8.4 MB device->host copy per iteration: decode and PCK
@@ -296,3 +298,216 @@ def flip_merge(output, output_flipped, flip_pairs, shift=False, decode=False):
         return (out, preds.cpu().numpy(), maxv.cpu().numpy().astype(output.dtype, copy=False)) if decode else out
     return (out, preds, maxv) if decode else out
 
+
+
+# ---------------------------------------------------------------------------------------------------------------- evaluation report
+# The default PCK curve, in the unit of `accuracy`'s thr (tenths of the heat-map size): 0.5 is the reference's PCK@0.05.
+PCK_THRESHOLDS = tuple(0.05 * j for j in range(1, 21))
+PCK_MAX_THRESHOLDS = 64      # UDAPOSE_PCK_MAX_THRESHOLDS (include/udapose.h)
+PCK_EPE_SCALE = 65536        # UDAPOSE_PCK_EPE_SCALE: epe_q counts 2^-16 px
+# The joint groups the reference's tables are printed from, per key-point layout, in the reference's order of names (the `keypoints_group`
+# dicts of lib/datasets/keypoint_dataset.py:107-116,145-151,190-199,228-234 over the class attributes :85-92,126-130,161-168,208-212).
+JOINT_GROUPS = {
+    "body16": {"head": (9,), "shoulder": (12, 13), "elbow": (11, 14), "wrist": (10, 15), "hip": (2, 3), "knee": (1, 4), "ankle": (0, 5),
+               "all": (12, 13, 11, 14, 10, 15, 2, 3, 1, 4, 0, 5)},
+    "hand21": {"MCP": (1, 5, 9, 13, 17), "PIP": (2, 6, 10, 14, 18), "DIP": (3, 7, 11, 15, 19), "fingertip": (4, 8, 12, 16, 20),
+               "all": tuple(range(21))},
+    "animal18": {"eye": (0, 1), "chin": (2,), "hoof": (3, 4, 5, 6), "hip": (7,), "knee": (8, 9, 10, 11), "shoulder": (12, 13),
+                 "elbow": (14, 15, 16, 17), "all": tuple(range(18))},
+    "animal14": {"eye": (0, 1), "hoof": (2, 3, 4, 5), "knee": (6, 7, 8, 9), "elbow": (10, 11, 12, 13), "all": tuple(range(14))},
+}
+
+
+def _joint_groups(groups):
+    """A key of JOINT_GROUPS or a mapping name -> joint indices, as {name: tuple of ints}.  ValueError for an unknown key or an empty group."""
+    if isinstance(groups, str):
+        if groups not in JOINT_GROUPS:
+            raise ValueError(f"unknown joint-group table {groups!r}: one of {sorted(JOINT_GROUPS)} or a mapping name -> joint indices")
+        return JOINT_GROUPS[groups]
+    out = {name: tuple(int(i) for i in idx) for name, idx in dict(groups).items()}
+    for name, idx in out.items():
+        if not idx:
+            raise ValueError(f"joint group {name!r} is empty")
+    return out
+
+
+def group_accuracy(acc, groups):
+    """The reference's KeypointDataset.group_accuracy (lib/datasets/keypoint_dataset.py:64-77): for every group the plain mean of the
+    listed joints' values, {name: sum(acc[i] for i in joints) / len(joints)}.  groups: a key of JOINT_GROUPS or a mapping."""
+    return {name: sum(acc[i] for i in idx) / len(idx) for name, idx in _joint_groups(groups).items()}
+
+
+def _check_thresholds(thresholds):
+    """The thresholds as the kernels take them, a float32 array [T]: 1 .. PCK_MAX_THRESHOLDS of them, finite, > 0 and strictly ascending
+    AS fp32 (the device compares in fp32 and finds the first hit by bisection).  ValueError otherwise."""
+    try:
+        t64 = np.asarray([float(t) for t in thresholds], dtype=np.float64)
+    except TypeError:
+        raise ValueError(f"thresholds must be a sequence of numbers, got {thresholds!r}") from None
+    if not 1 <= t64.size <= PCK_MAX_THRESHOLDS:
+        raise ValueError(f"a PCK curve takes 1 to {PCK_MAX_THRESHOLDS} thresholds, got {t64.size}")
+    with np.errstate(over="ignore"):
+        t32 = t64.astype(np.float32)
+    if not (np.isfinite(t32).all() and (t32 > 0).all()):
+        raise ValueError(f"thresholds must be finite and > 0 as fp32, got {list(thresholds)!r}")
+    if not (t32[1:] > t32[:-1]).all():
+        raise ValueError(f"thresholds must be strictly ascending as fp32, got {list(thresholds)!r}")
+    return t32
+
+
+def _nan_div(a, b):
+    """a / b in fp64, NaN where b == 0."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.divide(a, b, out=np.full(np.broadcast(a, b).shape, np.nan), where=b != 0)
+
+
+def _trapezoid(y, x):
+    """The trapezoid area under y (last axis) over x, divided by x's range."""
+    return ((y[..., 1:] + y[..., :-1]) * 0.5 * np.diff(x)).sum(-1) / (x[-1] - x[0])
+
+
+class PCKMeter:
+    """The evaluation report of a whole set, accumulated on the device (csrc/pck_curve.hip): per joint the hits at every threshold of a PCK
+    curve, the visible count and the end-point error, kept as int64 counts (`state()`: [K, T + 3], columns hits[0..T-1], count, epe_q,
+    nonfinite - include/udapose.h).  An update only adds integers, so the state after a set is the same bits whatever the batch size, and
+    nothing is read back before `compute()`.
+
+    thresholds: in the unit of `accuracy`'s thr, 1 to 64 of them, finite, > 0, strictly ascending as fp32 (ValueError otherwise); they are
+    uploaded once.  The state and the thresholds live on `device` (default: the current CUDA device; without a GPU the meter can be made
+    and refuses every update)."""
+
+    def __init__(self, num_keypoints, thresholds=PCK_THRESHOLDS, device=None):
+        self.num_keypoints = int(num_keypoints)
+        if not 1 <= self.num_keypoints <= 256:
+            raise ValueError(f"PCKMeter takes 1 to 256 key points (UDAPOSE_PCK_MAX_KEYPOINTS), got {num_keypoints}")
+        self._thr32 = _check_thresholds(thresholds)
+        self.thresholds = tuple(float(t) for t in thresholds)
+        self._state = self._thr = None
+        if device is not None or torch.cuda.is_available():
+            self._allocate(torch.device("cuda" if device is None else device))
+
+    def _allocate(self, device):
+        if device.type != "cuda":
+            raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
+        self._thr = torch.from_numpy(self._thr32).to(device)
+        self._state = torch.zeros(self.num_keypoints, len(self._thr32) + 3, dtype=torch.int64, device=device)
+
+    def _on_device(self, like=None):
+        if self._state is None:
+            if like is None or not like.is_cuda:
+                raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
+            self._allocate(like.device)
+        return self._state
+
+    def reset(self):
+        """Zero the state (in place: a captured update keeps adding to the same memory)."""
+        self._on_device().zero_()
+
+    def state(self):
+        """The raw int64 state [K, T + 3] on the device (the meter's own tensor, not a copy)."""
+        return self._on_device()
+
+    def merge(self, other_state):
+        """Add another meter's state (a PCKMeter or its int64 `state()` tensor, from any device): ranks or shards of one set."""
+        s = self._on_device()
+        o = other_state.state() if isinstance(other_state, PCKMeter) else other_state
+        if not torch.is_tensor(o) or o.dtype != torch.int64 or o.shape != s.shape:
+            raise ValueError(f"merge() takes an int64 state of shape {tuple(s.shape)}")
+        s += o.to(s.device)
+
+    def _coords(self, pred, gt, visible, norm, nh, nw):
+        """udapose_pck_accumulate on fp32 contiguous CUDA coordinates [B,K,2]."""
+        B, K = pred.shape[:2]
+        check(lib().udapose_pck_accumulate(_hip.stream(), ptr(pred), ptr(gt), ptr(visible), ptr(norm), B, K, nh, nw, ptr(self._thr),
+                                           len(self._thr32), ptr(self._state)), "pck_accumulate")
+
+    def update(self, output, target=None, *, decode="argmax", target_coords=None, visible=None, norm=None):
+        """Add a batch.  output: the network's heat-maps [B,K,H,W]; exactly one of target (heat-maps [B,K,H,W], scored against their
+        arg-max with the reference's `> 1` visibility rule) and target_coords ([B,K,2], (x, y) in heat-map pixels; visible [B,K], where
+        given, says which count - otherwise the same `> 1` rule applies to the coordinates).  decode: as in `accuracy`.  norm [B]: a
+        per-sample length in heat-map pixels (head size, box diagonal) to divide the pixel distance by instead of the heat-map size; a
+        sample whose length is not finite and > 0 drops out.  "argmax" against heat-map targets is ONE launch that reduces both tensors
+        (udapose_pck_accumulate_heatmaps); everything else decodes first and takes udapose_pck_accumulate.  Returns the prediction
+        [B,K,2] on the device; nothing is read back.  CPU tensors are refused, shape mismatches raise ValueError, before any launch."""
+        if (target is None) == (target_coords is None):
+            raise ValueError("update() takes exactly one of target (heat-maps) and target_coords ([B,K,2])")
+        if visible is not None and target_coords is None:
+            raise ValueError("visible goes with target_coords (heat-map targets carry their own visibility)")
+        given = [a for a in (output, target, target_coords, visible, norm) if a is not None]
+        if not all(torch.is_tensor(a) for a in given):
+            raise ValueError("update() takes torch tensors")
+        _hip.require_cuda(*given)
+        if output.dim() != 4 or output.shape[1] != self.num_keypoints or output.shape[0] < 1:
+            raise ValueError(f"output must be heat-maps [B,{self.num_keypoints},H,W], got {tuple(output.shape)}")
+        B, K, H, W = output.shape
+        if target is not None and target.shape != output.shape:
+            raise ValueError(f"output {tuple(output.shape)} and target {tuple(target.shape)} differ in shape")
+        if target_coords is not None and tuple(target_coords.shape) != (B, K, 2):
+            raise ValueError(f"target_coords must be [{B},{K},2], got {tuple(target_coords.shape)}")
+        if visible is not None and tuple(visible.shape) != (B, K):
+            raise ValueError(f"visible must be [{B},{K}], got {tuple(visible.shape)}")
+        if norm is not None and tuple(norm.shape) != (B,):
+            raise ValueError(f"norm must be [{B}], got {tuple(norm.shape)}")
+        self._on_device(output)
+        if any(a.device != self._state.device for a in given):
+            raise ValueError(f"the meter's state lives on {self._state.device}: every tensor of an update must")
+        o = output.detach().float().contiguous()
+        if norm is not None:
+            norm = norm.detach().float().contiguous()
+        if target is not None and isinstance(decode, str) and decode == "argmax":
+            pred = torch.empty(B, K, 2, dtype=torch.float32, device=o.device)
+            t = target.detach().float().contiguous()
+            check(lib().udapose_pck_accumulate_heatmaps(_hip.stream(), ptr(o), ptr(t), ptr(norm), B, K, H, W, ptr(self._thr),
+                                                        len(self._thr32), ptr(self._state), ptr(pred)), "pck_accumulate_heatmaps")
+            return pred
+        pred = _decode_pred(o, decode)
+        if target is not None:
+            gt = _decode(target.detach().float().contiguous())[0]
+        else:
+            gt = target_coords.detach().float().contiguous()
+            if visible is not None:
+                visible = (visible if visible.dtype in (torch.uint8, torch.bool) else visible != 0).contiguous().view(torch.uint8)
+        self._coords(pred, gt, visible, norm, H / 10.0, W / 10.0)
+        return pred
+
+    def compute(self, groups=None, pixel_scale=1.0):
+        """The one read-back: `report()` of the state."""
+        return PCKMeter.report(self._on_device().cpu(), self.thresholds, groups, pixel_scale)
+
+    @staticmethod
+    def report(state, thresholds, groups=None, pixel_scale=1.0):
+        """The report of a CPU int64 state [K, T + 3], in fp64 on the host (pure: no device, no side effect).  Arrays are numpy float64.
+          thresholds     as given
+          count [K]      visible (sample, joint) pairs (int64); nonfinite [K]: those whose error was not finite (int64)
+          pck [K][T]     hits / count, NaN where count == 0
+          pck_mean [T]   the mean over the joints with count > 0 (the reference's avg_acc: 0 where no joint was seen)
+          pck_micro [T]  total hits / total count (NaN without a visible pair)
+          auc            the trapezoid area under pck_mean over [thr[0], thr[-1]] divided by that range; None for T == 1
+          auc_per_joint [K]   the same under pck[k] (NaN where count == 0); None for T == 1
+          epe [K]        epe_q / 65536 / (count - nonfinite) * pixel_scale: the mean end-point error in heat-map pixels times pixel_scale
+                         (NaN without a finite pair); epe_mean: the mean of epe over the joints that have one (NaN without any)
+          groups         given `groups` (a key of JOINT_GROUPS or a mapping): per group {"pck" [T], "auc", "epe"}, each the plain mean
+                         over the group's joints as group_accuracy takes it (a joint without a value makes its groups' NaN)"""
+        thr = np.asarray([float(t) for t in thresholds], dtype=np.float64)
+        T = thr.size
+        s = state.numpy() if torch.is_tensor(state) else np.asarray(state)
+        if s.dtype != np.int64 or s.ndim != 2 or s.shape[1] != T + 3:
+            raise ValueError(f"report() takes an int64 state [K, {T + 3}] for {T} thresholds, got {s.dtype} {s.shape}")
+        hits, count, q, nonfinite = s[:, :T], s[:, T], s[:, T + 1], s[:, T + 2]
+        seen = count > 0
+        pck = _nan_div(hits, count[:, None])
+        pck_mean = pck[seen].mean(0) if seen.any() else np.zeros(T)
+        epe = _nan_div(q / float(PCK_EPE_SCALE), count - nonfinite) * float(pixel_scale)
+        rep = {"thresholds": tuple(float(t) for t in thresholds), "count": count.copy(), "nonfinite": nonfinite.copy(), "pck": pck,
+               "pck_mean": pck_mean, "pck_micro": _nan_div(hits.sum(0), count.sum()),
+               "auc": float(_trapezoid(pck_mean, thr)) if T > 1 else None, "auc_per_joint": _trapezoid(pck, thr) if T > 1 else None,
+               "epe": epe, "epe_mean": float(epe[~np.isnan(epe)].mean()) if (~np.isnan(epe)).any() else float("nan")}
+        if groups is not None:
+            rep["groups"] = {}
+            for name, idx in _joint_groups(groups).items():
+                if min(idx) < 0 or max(idx) >= s.shape[0]:
+                    raise ValueError(f"joint group {name!r} {idx} is out of range for {s.shape[0]} key points")
+                ix = list(idx)
+                rep["groups"][name] = {"pck": pck[ix].sum(0) / len(ix), "auc": float(rep["auc_per_joint"][ix].sum() / len(ix)) if T > 1 else None,
+                                       "epe": float(epe[ix].sum() / len(ix))}
+        return rep
