@@ -162,6 +162,49 @@ def test_decode_equals_heatmap_argmax_of_the_merged_map(shape):
                         assert bool(torch.isinf(maxv.flatten()).any()), tag
 
 
+@pytest.mark.parametrize("H,W", [(5, 7), (8, 8), (72, 72)], ids=["5x7_scalar_loads", "8x8_vector_loads", "72x72_rows_past_4096"])
+def test_every_user_of_the_block_argmax_gives_the_same_index_and_maximum_bits(H, W):
+    """udapose_heatmap_argmax, the decode of flip_merge, udapose_soft_argmax_fwd's saved index and udapose_refine_decode (quarter mode) reduce
+    with one block arg-max (csrc/common.h): the same first flat index and the same bits of the maximum on a row with one NaN, a row of
+    -inf, a constant row (first index wins), an all-negative row and two ordinary ones.  72x72 rows are longer than the 4096 floats the
+    soft-argmax keeps in registers; that size runs the first and the third only."""
+    from uda_poseestimation_amd import _hip
+    g = torch.Generator().manual_seed(H * 100 + W)
+    x = torch.randn(1, 6, H, W, generator=g)
+    x[0, 0, H // 2, W // 3] = float("nan")
+    x[0, 1] = float("-inf")
+    x[0, 2] = 0.375
+    x[0, 3] = -x[0, 3].abs() - 0.125
+    xd = x.cuda()
+    R = 6
+    want_idx = [H // 2 * W + W // 3, 0, 0] + [int(x[0, r].argmax()) for r in (3, 4, 5)]
+    maxv, idx, _ = argmax_of(xd)
+    assert idx.tolist() == want_idx
+    assert torch.equal(_bits(maxv).flatten()[1:].cpu(), _bits(x.reshape(R, -1).amax(1))[1:]) and bool(torch.isnan(maxv.flatten()[0]))
+
+    def new():
+        return torch.full((R,), -1, dtype=torch.int32, device="cuda"), torch.full((R,), 7.0, device="cuda")
+
+    got = {}
+    i2, m2 = new()
+    coords, stats = torch.empty(R, 2, device="cuda"), torch.empty(4 * R, device="cuda")
+    _hip.check(_hip.lib().udapose_soft_argmax_fwd(_hip.stream(), _hip.ptr(xd), R, H, W, 10.0, 2, _hip.ptr(coords), _hip.ptr(m2), _hip.ptr(i2),
+                                                  _hip.ptr(stats)), "soft_argmax_fwd")
+    got["soft_argmax_fwd"] = (i2, m2)
+    if H * W <= 4096:
+        # (x + flip_back(flip(x))) * 0.5 is x, bit for bit: the merge decodes the map itself
+        code, out, mf, i_f, _ = merge_raw(xd, torch.flip(xd, [3]).contiguous(), torch.arange(6, dtype=torch.int32, device="cuda"), 0, 1)
+        assert code == 0 and torch.equal(_bits(out), _bits(xd))
+        got["flip_merge"] = (i_f, mf.flatten())
+        i3, m3 = new()
+        _hip.check(_hip.lib().udapose_refine_decode(_hip.stream(), _hip.ptr(xd), R, H, W, 0, 0, 0.0, _hip.ptr(coords), _hip.ptr(m3), _hip.ptr(i3)),
+                   "refine_decode")
+        got["refine_decode"] = (i3, m3)
+    for name, (i, m) in got.items():
+        assert torch.equal(i, idx), (name, i.tolist(), idx.tolist())
+        assert torch.equal(_bits(m), _bits(maxv.flatten())), name
+
+
 # ---------------------------------------------------------------------------------------------- table guard and argument checks
 def test_table_entries_out_of_range_are_the_identity():
     """An argument check, not a fault: the kernel clamps, so nothing outside f is read whatever the table holds."""

@@ -408,6 +408,63 @@ def test_cons_loss_valid_mask_matches_reference_golden(golden_dir):
         ConsLoss()(pred.cuda(), gt.cuda(), valid_mask=valid[:, :10].cuda())
 
 
+def _optional_cases():
+    """name -> (device loss, restatement, fp64?): every optional tensor of JointsMSELoss, ConsLoss and the two top-k losses absent, and every
+    one present.  (The soft-max and coordinate families run both in tests/test_gpu_softmax_losses.py and tests/test_gpu_soft_argmax.py.)"""
+    from helpers import joint_selection_fp64 as R64
+    from oracle.losses_ref import cons_loss_ref, joints_mse_ref
+    from uda_poseestimation_amd.lib.models import loss as L
+    return {
+        "mse": (lambda x, d: L.JointsMSELoss()(x, d["label"]), lambda x, d: joints_mse_ref(x, d["label"]), False),
+        "mse_w": (lambda x, d: L.JointsMSELoss()(x, d["label"], d["weight"]), lambda x, d: joints_mse_ref(x, d["label"], d["weight"]), False),
+        "cons": (lambda x, d: L.ConsLoss()(x, d["tea"]), lambda x, d: cons_loss_ref(x, d["tea"]), False),
+        "cons_valid_mask": (lambda x, d: L.ConsLoss()(x, d["tea"], d["valid"], d["tea_mask"]),
+                            lambda x, d: cons_loss_ref(x, d["tea"], d["valid"], d["tea_mask"]), False),
+        "ohkm": (lambda x, d: L.JointsOHKMMSELoss(2)(x, d["label"]), lambda x, d: R64.joints_ohkm(x, d["label"], None, 2)[0], True),
+        "ohkm_w": (lambda x, d: L.JointsOHKMMSELoss(2)(x, d["label"], d["weight"]), lambda x, d: R64.joints_ohkm(x, d["label"], d["weight"], 2)[0], True),
+        "cons_topk": (lambda x, d: L.ConsTopKLoss(2)(x, d["tea"]), lambda x, d: R64.cons_topk(x, d["tea"], None, 2)[0], True),
+        "cons_topk_mask": (lambda x, d: L.ConsTopKLoss(2)(x, d["tea"], tea_mask=d["tea_mask"]),
+                           lambda x, d: R64.cons_topk(x, d["tea"], d["tea_mask"], 2)[0], True),
+    }
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("name", ["mse", "mse_w", "cons", "cons_valid_mask", "ohkm", "ohkm_w", "cons_topk", "cons_topk_mask"])
+def test_losses_with_every_optional_tensor_absent_and_present(name, dtype):
+    """B=2, K=3, 4x4: one forward and backward; the gradient has the input's shape and dtype and is the restatement's.  The tolerances are
+    those of the tests that own the losses: rtol 1e-5 against autograd of the CPU oracle (this module), 6 units of 2^-24 per element against
+    the fp64 restatement for the top-k losses (GRAD_BAR of tests/test_gpu_joint_selection.py); a bf16 input is taken as fp32 rows, so its
+    gradient is the widened input's gradient rounded once (the 16-bit tests of the loss families)."""
+    g = torch.Generator().manual_seed(17)
+    d = {"stu": torch.randn(2, 3, 4, 4, generator=g), "tea": torch.randn(2, 3, 4, 4, generator=g), "label": torch.rand(2, 3, 4, 4, generator=g),
+         "weight": torch.tensor([[[1.0], [0.0], [0.5]], [[0.75], [1.0], [1.25]]]), "tea_mask": torch.tensor([[True, False, True], [True, True, True]]),
+         "valid": torch.rand(2, 4, 4, generator=g) > 0.35}
+    for k in ("stu", "tea", "label"):
+        d[k] = d[k].to(dtype).float()                  # values every dtype of this test holds exactly
+    dev_fn, ref_fn, fp64 = _optional_cases()[name]
+    dd = {k: v.cuda() for k, v in d.items()}
+    wide = dd["stu"].clone().requires_grad_(True)
+    dev_fn(wide, dd).backward()
+    x = dd["stu"].to(dtype).requires_grad_(True)
+    loss = dev_fn(x, {k: (v.to(dtype) if k in ("tea", "label") else v) for k, v in dd.items()})
+    loss.backward()
+    assert loss.dtype == torch.float32 and x.grad.dtype == dtype and x.grad.shape == x.shape
+    assert torch.equal(x.grad, wide.grad.to(dtype))
+    dr = {k: (v.double() if fp64 and v.dtype == torch.float32 else v) for k, v in d.items()}
+    xr = dr["stu"].clone().requires_grad_(True)
+    ref_fn(xr, dr).backward()
+    got, want = wide.grad.cpu().double(), xr.grad.double()
+    assert want.abs().max() > 0
+    if fp64:
+        zero = want == 0
+        assert bool((got[zero] == 0).all())
+        rel = float(((got[~zero] - want[~zero]).abs() / want[~zero].abs()).max())
+        print(f"\n{name}: gradient element {rel * 2.0 ** 24:.2f}u against fp64 (bar 6u)")
+        assert rel <= 6 * 2.0 ** -24
+    else:
+        np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=1e-5, atol=1e-10)
+
+
 def test_mean_teacher_step_matches_cpu_oracle():
     """One whole step (train_human.py:326-440 order) on a small PoseResNet: losses, mask, EMA and Adam vs oracle/step_ref."""
     from oracle.pose_resnet_ref import PoseResNetRef

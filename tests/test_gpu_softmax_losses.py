@@ -179,6 +179,27 @@ def test_forward_of_every_class_matches_what_the_reference_returned(golden_dir):
             assert e <= bar, (pre, name, e, bar)
 
 
+@pytest.mark.parametrize("n", [2, 7])
+def test_a_tea_mask_that_does_not_have_one_entry_per_heatmap_is_refused_before_any_launch(n, monkeypatch):
+    """The kernels index tea_mask by (b,k) row: a mask of another size (here 2 and 7 entries for B*K = 6) would be read out of bounds, so
+    ConsLoss, ConsSoftmaxLoss and ConsKLLoss raise ValueError - and reach no library call on the way."""
+    from uda_poseestimation_amd import heatmap_args
+    L = _losses()
+    stu, tea = torch.randn(2, 3, 4, 4, device="cuda"), torch.randn(2, 3, 4, 4, device="cuda")
+    mask = torch.ones(n, dtype=torch.bool, device="cuda")
+
+    def no_launch(*a, **k):
+        raise AssertionError("a library call was reached")
+
+    monkeypatch.setattr(L, "lib", no_launch)
+    monkeypatch.setattr(heatmap_args, "lib", no_launch)
+    for crit in (L.ConsLoss(), L.ConsSoftmaxLoss(), L.ConsKLLoss(log_target=True)):
+        with pytest.raises(ValueError, match="tea_mask must have B\\*K elements"):
+            crit(stu, tea, tea_mask=mask)
+        with pytest.raises(ValueError, match="tea_mask must have B\\*K elements"):
+            crit(stu, tea, valid_mask=torch.ones(2, 4, 4, dtype=torch.bool, device="cuda"), tea_mask=mask)
+
+
 class _nullcontext:
     def __enter__(self):
         return None
@@ -188,7 +209,7 @@ class _nullcontext:
 
 
 def test_gradients_on_the_golden_shapes_match_fp64_autograd():
-    check_against_fp32_arithmetic([(3, 5, 16, 16), (3, 5, 7, 9)], "golden shapes")
+    check_against_fp32_arithmetic([(3, 5, 16, 16), (3, 5, 7, 9), (2, 3, 4, 4)], "golden shapes and B=2 K=3 4x4")
 
 
 def test_gradients_on_ragged_shapes_match_fp64_autograd():

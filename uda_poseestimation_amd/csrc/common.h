@@ -134,29 +134,42 @@ __device__ __forceinline__ void bn_scale_shift8(const float (&gamma)[8], const f
 }
 
 // torch's total order on floats for max / kthvalue: NaN is the LARGEST value (and all NaNs are equal); the first index wins a tie.
-// The one arg-max order of heatmap.hip (argmax_rectify_k) and softargmax.hip.
+// The one arg-max order of every heat-map decode (heatmap.hip, softargmax.hip, flip.hip, refine.hip, pck_curve.hip, view_merge.hip).
 __device__ __forceinline__ bool hm_better(float v, int i, float bv, int bi) {
     const bool vn = v != v, bn = bv != bv;
     if (vn != bn) return vn;
     if (vn) return i < bi;
     return v > bv || (v == bv && i < bi);
 }
-// The block arg-max of refine.hip and pck_curve.hip: every thread of a block of WAVES waves brings its own best (value, flat index) and
-// returns the block's, under hm_better (a total order: the winner does not depend on the reduction tree).  sv, si: WAVES entries of LDS.
-template <int WAVES>
-__device__ __forceinline__ void hm_block_best(float& bv, int& bi, float* sv, int* si) {
+// The wave arg-max: every lane brings its own best (value, flat index) and returns the wave's, under hm_better (a total order: the winner
+// does not depend on the reduction tree).  view_merge_k runs it once per view and combines the waves in LDS tables of its own.
+// (Both helpers reduce in locals and write the references once: updated through the references, the compiler keeps hm_better's branches
+// where it otherwise selects - view_merge_k measured 0.9 us slower that way.)
+__device__ __forceinline__ void hm_wave_best(float& bv, int& bi) {
+    float v = bv;
+    int i = bi;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (hm_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+        const float ov = __shfl_xor(v, o, 64);
+        const int oi = __shfl_xor(i, o, 64);
+        if (hm_better(ov, oi, v, i)) { v = ov; i = oi; }
     }
+    bv = v; bi = i;
+}
+// The block arg-max of argmax_rectify_k, sa_row, flip_merge_k, refine.hip and pck_curve.hip: hm_wave_best, then the WAVES waves' results
+// combined through LDS; every thread returns the block's.  sv, si: WAVES entries of LDS.  Opens with a barrier: every thread of the
+// block must reach the call.
+template <int WAVES>
+__device__ __forceinline__ void hm_block_best(float& bv, int& bi, float* sv, int* si) {
+    hm_wave_best(bv, bi);
     __syncthreads();      // (sv, si may still be read from the previous reduction)
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
     __syncthreads();
-    bv = sv[0]; bi = si[0];
+    float v = sv[0];
+    int i = si[0];
     for (int w = 1; w < WAVES; ++w)
-        if (hm_better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
+        if (hm_better(sv[w], si[w], v, i)) { v = sv[w]; i = si[w]; }
+    bv = v; bi = i;
 }
 
 __device__ __forceinline__ float wave_sum(float v) {

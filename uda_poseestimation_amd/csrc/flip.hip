@@ -60,18 +60,8 @@ __global__ void flip_merge_k(const float* a, const float* __restrict__ f, const 
         if (hm_better(v, i, bv, bi)) { bv = v; bi = i; }
     }
     if (!maxv && !idx_out && !preds) return;      // (uniform over the grid)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (hm_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
+    hm_block_best<TPB / 64>(bv, bi, sv, si);
     if (threadIdx.x == 0) {
-        bv = sv[0]; bi = si[0];
-        for (int w = 1; w < TPB / 64; ++w)
-            if (hm_better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
         const bool pos = bv > 0.f;
         if (maxv) maxv[r] = bv;
         if (idx_out) idx_out[r] = bi;

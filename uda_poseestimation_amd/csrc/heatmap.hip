@@ -66,42 +66,30 @@ __global__ void mask_count_k(const unsigned char* __restrict__ m, size_t n, floa
     const double t = block_sum_d(s, red);
     if (threadIdx.x == 0) count[0] = (float)t;
 }
-// da = gscale[0] * coef * f[r] * (a-b), f = w or mask (or 1)
+// da = gscale[0] * coef * f[r] * (a-b), f = w or mask (or 1).  E elements per thread and step: 4 (16-byte loads; the launcher sees to
+// HW % 4 == 0, so a quad lies in one row) or 1, for maps whose pixel count is no multiple of 4 (rows are then not 16-byte aligned).
+template <int E>
 __global__ void sqdiff_bwd_k(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ w,
                              const unsigned char* __restrict__ mask, const float* __restrict__ gscale, float coef, int HW,
                              size_t total, float* __restrict__ da, const unsigned char* __restrict__ valid, const float* __restrict__ count, int Kc) {
+    typedef float vec __attribute__((ext_vector_type(E)));
     float gs = gscale ? gscale[0] : 1.f;
     if (count) gs *= (float)(((double)(total / HW) / Kc) * HW / (double)count[0]);     // B*HW / count: the mean runs over the selected pixels
-    for (size_t i = ((size_t)blockIdx.x * TPB + threadIdx.x) * 4; i < total; i += (size_t)gridDim.x * TPB * 4) {
-        const size_t r = i / HW;     // HW % 4 == 0 enforced by the launcher
-        float f = gs * coef;
-        if (w) f *= w[r];
-        if (mask) f *= mask[r] ? 1.f : 0.f;
-        const f32x4 x = *(const f32x4*)(a + i), y = *(const f32x4*)(b + i);
-        f32x4 o = (f32x4){f * (x[0] - y[0]), f * (x[1] - y[1]), f * (x[2] - y[2]), f * (x[3] - y[3])};
-        if (valid) {
-            const unsigned char* pv = valid + (r / Kc) * HW + (i - r * HW);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) if (!pv[e]) o[e] = 0.f;
-        }
-        *(f32x4*)(da + i) = o;
-    }
-}
-
-// the same element by element, for maps whose pixel count is not a multiple of 4 (rows are then not 16-byte aligned)
-__global__ void sqdiff_bwd_scalar_k(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ w,
-                                    const unsigned char* __restrict__ mask, const float* __restrict__ gscale, float coef, int HW,
-                                    size_t total, float* __restrict__ da, const unsigned char* __restrict__ valid, const float* __restrict__ count, int Kc) {
-    float gs = gscale ? gscale[0] : 1.f;
-    if (count) gs *= (float)(((double)(total / HW) / Kc) * HW / (double)count[0]);
-    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
+    for (size_t i = ((size_t)blockIdx.x * TPB + threadIdx.x) * E; i < total; i += (size_t)gridDim.x * TPB * E) {
         const size_t r = i / HW;
         float f = gs * coef;
         if (w) f *= w[r];
         if (mask) f *= mask[r] ? 1.f : 0.f;
-        float o = f * (a[i] - b[i]);
-        if (valid && !valid[(r / Kc) * HW + (i - r * HW)]) o = 0.f;
-        da[i] = o;
+        const vec x = *(const vec*)(a + i), y = *(const vec*)(b + i);
+        vec o;
+#pragma unroll
+        for (int e = 0; e < E; ++e) o[e] = f * (x[e] - y[e]);
+        if (valid) {
+            const unsigned char* pv = valid + (r / Kc) * HW + (i - r * HW);
+#pragma unroll
+            for (int e = 0; e < E; ++e) if (!pv[e]) o[e] = 0.f;
+        }
+        *(vec*)(da + i) = o;
     }
 }
 
@@ -122,17 +110,7 @@ __global__ void argmax_rectify_k(const float* __restrict__ hm, int H, int W, flo
         const float v = p[i];
         if (hm_better(v, i, bv, bi)) { bv = v; bi = i; }      // (NaN counts as the maximum, first index on ties: torch / numpy)
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (hm_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    bv = sv[0]; bi = si[0];
-    for (int k = 1; k < TPB / 64; ++k)
-        if (hm_better(sv[k], si[k], bv, bi)) { bv = sv[k]; bi = si[k]; }
+    hm_block_best<TPB / 64>(bv, bi, sv, si);
     const bool pos = bv > 0.f;
     const int mx = pos ? bi % W : 0, my = pos ? bi / W : 0;
     if (threadIdx.x == 0) {
@@ -213,18 +191,12 @@ int hm_sqdiff_bwd(hipStream_t s, const float* a, const float* b, const float* w,
                   int R, int HW, float* da, const unsigned char* valid, const float* count, int Kc) {
     if (valid && (!count || Kc < 1 || R % Kc)) return UDAPOSE_ERR_ARG;
     const size_t total = (size_t)R * HW;
-    if (HW % 4) {
-        size_t blocks = (total + TPB - 1) / TPB;
-        if (blocks > 4096) blocks = 4096;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(sqdiff_bwd_scalar_k, dim3((int)blocks), dim3(TPB), 0, s, a, b, w, mask, gscale, coef, HW, total, da, valid,
-                           valid ? count : nullptr, Kc);
-        return udapose_check_launch();
-    }
-    size_t blocks = (total / 4 + TPB - 1) / TPB;
+    const int E = HW % 4 ? 1 : 4;
+    size_t blocks = (total / E + TPB - 1) / TPB;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(sqdiff_bwd_k, dim3((int)blocks), dim3(TPB), 0, s, a, b, w, mask, gscale, coef, HW, total, da, valid, valid ? count : nullptr,
-                       Kc);
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(E == 4 ? sqdiff_bwd_k<4> : sqdiff_bwd_k<1>, dim3((int)blocks), dim3(TPB), 0, s, a, b, w, mask, gscale, coef, HW, total, da,
+                       valid, valid ? count : nullptr, Kc);
     return udapose_check_launch();
 }
 int hm_mask_count(hipStream_t s, const unsigned char* m, size_t n, float* count) {

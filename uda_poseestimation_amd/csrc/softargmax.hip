@@ -46,17 +46,7 @@ __device__ __forceinline__ SaRow sa_row(const Row& S, int H, int W, float beta, 
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     each2(S, S, [&](int i, float v, float) { if (hm_better(v, i, bv, bi)) { bv = v; bi = i; } });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (hm_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    bv = sv[0]; bi = si[0];
-    for (int k = 1; k < TPB / 64; ++k)
-        if (hm_better(sv[k], si[k], bv, bi)) { bv = sv[k]; bi = si[k]; }
+    hm_block_best<TPB / 64>(bv, bi, sv, si);
     const Win w(bi, H, W, window);
     double z = 0.0, sx = 0.0, sy = 0.0, unused = 0.0;
     each2(S, S, [&](int i, float v, float) {

@@ -129,12 +129,7 @@ __global__ __launch_bounds__(TPB) void view_merge_k(MergeViews v, int k, int H, 
         if (j < k) {
             // (a thread whose pixels are all -inf has replaced nothing: its first pixel is its first maximum)
             if (bi[j] == 0x7fffffff && (int)threadIdx.x * 4 < HW) bi[j] = threadIdx.x * 4;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv[j], o, 64);
-                const int oi = __shfl_xor(bi[j], o, 64);
-                if (hm_better(ov, oi, bv[j], bi[j])) { bv[j] = ov; bi[j] = oi; }
-            }
+            hm_wave_best(bv[j], bi[j]);
             if (lane == 0) { sv[wave][j] = bv[j]; si[wave][j] = bi[j]; }
         }
     }

@@ -13,7 +13,24 @@ import numpy as np
 import torch
 
 from .. import _hip
+from .. import heatmap_args as ha
 from .._hip import check, lib, ptr
+
+
+def _is_numpy(a, what='batch_heatmaps should be numpy.ndarray or a 4-d tensor'):
+    """True for a numpy array, False for a tensor; anything else is refused."""
+    if not isinstance(a, np.ndarray) and not torch.is_tensor(a):
+        raise AssertionError(what)
+    return isinstance(a, np.ndarray)
+
+
+def _like_input(src, t, in_dtype=False):
+    """numpy in -> numpy out, tensor in -> tensor out: the device result `t` as the caller of `src` gets it - a numpy array for a numpy
+    `src` (in src's dtype with in_dtype=True: heat-maps and maxvals; coordinates stay float32), `t` itself for a tensor."""
+    if not isinstance(src, np.ndarray):
+        return t
+    a = t.cpu().numpy()
+    return a.astype(src.dtype, copy=False) if in_dtype else a
 
 
 def _dev_f32(a):
@@ -24,33 +41,27 @@ def _dev_f32(a):
         return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
     assert torch.is_tensor(a) and a.dim() == 4, 'batch_heatmaps should be numpy.ndarray or a 4-d tensor'
     _hip.require_cuda(a)
-    return a.detach().float().contiguous()
+    return ha.f32c(a)
 
 
 def _decode(hm):
-    B, K, H, W = hm.shape
-    preds = torch.empty(B, K, 2, dtype=torch.float32, device=hm.device)
-    maxv = torch.empty(B, K, 1, dtype=torch.float32, device=hm.device)
-    check(lib().udapose_heatmap_argmax(_hip.stream(), ptr(hm), B * K, H, W, ptr(maxv), None, ptr(preds), None, None, 0), "heatmap_argmax")
-    return preds, maxv
+    """The arg-max decode of an fp32 contiguous CUDA batch: (preds [B,K,2], (0, 0) where the maximum is <= 0; maxvals [B,K,1])."""
+    r = ha.heatmap_argmax(hm, maxv=True, xy=True)
+    return r.xy, r.maxv.unsqueeze(-1)
 
 
 def get_max_preds(batch_heatmaps):
     """[B,K,H,W] -> (preds [B,K,2] float32 (x,y), maxvals [B,K,1]); numpy in -> numpy out, tensor in -> tensor out."""
-    is_np = isinstance(batch_heatmaps, np.ndarray)
-    if not is_np and not torch.is_tensor(batch_heatmaps):
-        raise AssertionError('batch_heatmaps should be numpy.ndarray')
+    _is_numpy(batch_heatmaps, 'batch_heatmaps should be numpy.ndarray')
     preds, maxv = _decode(_dev_f32(batch_heatmaps))
-    if is_np:
-        return preds.cpu().numpy(), maxv.cpu().numpy().astype(batch_heatmaps.dtype, copy=False)
-    return preds, maxv
+    return _like_input(batch_heatmaps, preds), _like_input(batch_heatmaps, maxv, True)
 
 
 class _SoftArgmaxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hm, beta, window):
         B, K, H, W = hm.shape
-        h = hm.detach().float().contiguous()
+        h = ha.f32c(hm)
         coords = torch.empty(B, K, 2, dtype=torch.float32, device=h.device)
         maxv = torch.empty(B, K, 1, dtype=torch.float32, device=h.device)
         idx = torch.empty(B * K, dtype=torch.int32, device=h.device)
@@ -67,10 +78,10 @@ class _SoftArgmaxFn(torch.autograd.Function):
         h, idx, stats = ctx.saved_tensors
         B, K, H, W = ctx.shape
         d = torch.empty_like(h)
-        gc = g.detach().float().contiguous()
+        gc = ha.f32c(g)
         check(lib().udapose_soft_argmax_bwd(_hip.stream(), ptr(h), ptr(gc), ptr(idx), ptr(stats), B * K, H, W, ctx.beta, ctx.window, ptr(d)),
               "soft_argmax_bwd")
-        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None
+        return ha.grad_like_input(ctx, d), None, None
 
 
 def _soft_args(beta, window):
@@ -91,16 +102,14 @@ def soft_argmax(batch_heatmaps, beta=10.0, window=None):
     the whole map for window=None.  MSE-trained maps have a flat background of thousands of pixels: decode them with a window
     (beta=10, window=5 is what accuracy(decode="soft") uses).  Differentiable for a tensor that requires grad (the arg-max that places
     the window is a constant; the gradient comes back in the input's dtype).  Coordinates are NOT zeroed where maxvals <= 0."""
-    is_np = isinstance(batch_heatmaps, np.ndarray)
-    if not is_np and not torch.is_tensor(batch_heatmaps):
-        raise AssertionError('batch_heatmaps should be numpy.ndarray or a 4-d tensor')
+    is_np = _is_numpy(batch_heatmaps)
     beta, window = _soft_args(beta, window)
     if is_np:
         coords, maxv = _SoftArgmaxFn.apply(_dev_f32(batch_heatmaps), beta, window)
-        return coords.cpu().numpy(), maxv.cpu().numpy().astype(batch_heatmaps.dtype, copy=False)
+        return _like_input(batch_heatmaps, coords), _like_input(batch_heatmaps, maxv, True)
     assert batch_heatmaps.dim() == 4, 'batch_heatmaps should be numpy.ndarray or a 4-d tensor'
     _hip.require_cuda(batch_heatmaps)
-    return _SoftArgmaxFn.apply(batch_heatmaps, beta, window)
+    return _SoftArgmaxFn.apply(batch_heatmaps, beta, window)      # (the tensor itself: the gradient flows to it)
 
 
 DARK_MAX_PIXELS = 19200      # UDAPOSE_REFINE_MAX_PIXELS (include/udapose.h): the map and its row-blurred copy share one CU's LDS
@@ -129,15 +138,11 @@ def _dark_args(kernel, sigma, H, W):
 
 def _refine_public(batch_heatmaps, mode, kernel=0, sigma=None):
     """numpy in -> numpy out, tensor in -> tensor out; the arguments are checked before anything is copied or launched."""
-    is_np = isinstance(batch_heatmaps, np.ndarray)
-    if not is_np and not torch.is_tensor(batch_heatmaps):
-        raise AssertionError('batch_heatmaps should be numpy.ndarray or a 4-d tensor')
+    _is_numpy(batch_heatmaps)
     assert batch_heatmaps.ndim == 4, 'batch_heatmaps should be numpy.ndarray or a 4-d tensor'
     kernel, sigma = _dark_args(kernel, sigma, *batch_heatmaps.shape[2:]) if mode == 1 else (0, 0.0)
     coords, maxv = _refine(_dev_f32(batch_heatmaps), mode, kernel, sigma)
-    if is_np:
-        return coords.cpu().numpy(), maxv.cpu().numpy().astype(batch_heatmaps.dtype, copy=False)
-    return coords, maxv
+    return _like_input(batch_heatmaps, coords), _like_input(batch_heatmaps, maxv, True)
 
 
 def quarter_decode(batch_heatmaps):
@@ -209,11 +214,10 @@ def accuracy(output, target, hm_type='gaussian', thr=0.5, decode="argmax"):
     sub-pixel coordinates are zeroed where maxvals <= 0, as the arg-max's are."""
     if hm_type != 'gaussian':
         raise NotImplementedError("only hm_type='gaussian' is used by the reference scripts")
-    is_np = isinstance(output, np.ndarray)
     acc, avg_cnt, pred = accuracy_device(output, target, thr, decode)
     ac = avg_cnt.cpu()
     acc_np = acc.cpu().numpy().astype(np.float64)
-    return acc_np, float(ac[0]), int(ac[1]), (pred.cpu().numpy() if is_np else pred)
+    return acc_np, float(ac[0]), int(ac[1]), _like_input(output, pred)
 
 
 # ---------------------------------------------------------------------------------------------------------------- flip test
@@ -278,26 +282,21 @@ def flip_back(output_flipped, flip_pairs, shift=False):
     """The network's heat-maps [B,K,H,W] of a mirrored batch, flipped back: columns reversed and left / right channels swapped
     (`flip_pairs`: a sequence of pairs or a key of FLIP_PAIRS); shift=True moves the result one pixel to the right (column 0 is kept), as
     Simple Baselines does before averaging.  numpy in -> numpy out, tensor in -> tensor out."""
-    is_np = isinstance(output_flipped, np.ndarray)
     f = _dev_f32(output_flipped)
     out, _, _ = _flip_merge(None, f, _perm_device(flip_pairs, f.shape[1], f.device), shift, False)
-    return out.cpu().numpy().astype(output_flipped.dtype, copy=False) if is_np else out
+    return _like_input(output_flipped, out, True)
 
 
 def flip_merge(output, output_flipped, flip_pairs, shift=False, decode=False):
     """The flip test's average: (output + flip_back(output_flipped, flip_pairs, shift)) * 0.5 as [B,K,H,W] fp32.  decode=True returns
     (merged, preds [B,K,2], maxvals [B,K,1]) with the arg-max decode of `merged` (what get_max_preds gives for it) out of the same
     launch.  numpy in -> numpy out, tensor in -> tensor out."""
-    is_np = isinstance(output, np.ndarray)
     a, f = _dev_f32(output), _dev_f32(output_flipped)
     if a.shape != f.shape:
         raise ValueError(f"output {tuple(a.shape)} and output_flipped {tuple(f.shape)} differ in shape")
     out, preds, maxv = _flip_merge(a, f, _perm_device(flip_pairs, f.shape[1], f.device), shift, decode)
-    if is_np:
-        out = out.cpu().numpy().astype(output.dtype, copy=False)
-        return (out, preds.cpu().numpy(), maxv.cpu().numpy().astype(output.dtype, copy=False)) if decode else out
-    return (out, preds, maxv) if decode else out
-
+    out = _like_input(output, out, True)
+    return (out, _like_input(output, preds), _like_input(output, maxv, True)) if decode else out
 
 
 # ---------------------------------------------------------------------------------------------------------------- evaluation report

@@ -24,7 +24,8 @@ import torch
 import torch.nn as nn
 
 from ... import _hip, ops
-from ..._hip import check, lib, ptr
+from ... import heatmap_args as ha
+from .loss import _cons_fwd
 
 
 def _nchw_feat(feat):
@@ -70,14 +71,8 @@ def gram_matrix(y):
 
 def _mse(a, b):
     """nn.MSELoss() of two equally shaped fp32 tensors on the device (one sweep)."""
-    a, b = a.detach().float().contiguous(), b.detach().float().contiguous()
     assert a.shape == b.shape
-    R = a.shape[0] * a.shape[1]
-    HW = a.numel() // R
-    rows = torch.empty(R, dtype=torch.float32, device=a.device)
-    mean = torch.empty((), dtype=torch.float32, device=a.device)
-    check(lib().udapose_cons_loss_fwd(_hip.stream(), ptr(a), ptr(b), None, R, HW, ptr(rows), ptr(mean)), "mse")
-    return mean
+    return _cons_fwd(ha.f32c(a), ha.f32c(b))[1]      # (ConsLoss's forward without a mask: the mean of (a - b)^2 over everything)
 
 
 # decoder (Style_net.py:32-62): mirror of the encoder; 'U' = nearest x2 upsample; the last conv has no ReLU

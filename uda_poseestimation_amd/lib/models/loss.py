@@ -16,44 +16,59 @@ import torch
 import torch.nn as nn
 
 from ... import _hip
+from ... import heatmap_args as ha
 from ..._hip import check, lib, ptr
+from ..keypoint_detection import _decode, _soft_args, soft_argmax
 
 
-def _rows(t):
-    B, K = t.shape[:2]
-    return B * K, t.numel() // (B * K)
+def _reduce_mean(reduction):
+    """True for 'mean', False for 'none'.  Any other string: None, and the module's forward returns None - as the reference silently does
+    (loss.py:46-49, 92-95)."""
+    return True if reduction == 'mean' else False if reduction == 'none' else None
 
 
-def _f32c(t):
-    return t.detach().float().contiguous()
+def _mean_only(ctx):
+    if not ctx.reduce_mean:
+        raise NotImplementedError("backward of reduction='none' is not on the hot path")
+
+
+def _joints_mse_fwd(o, t, w, want_mean=True):
+    """udapose_joints_mse_fwd on fp32 contiguous operands: (rows [R], their mean or None)."""
+    R, HW = ha.rows(o)
+    rows = torch.empty(R, dtype=torch.float32, device=o.device)
+    mean = torch.empty((), dtype=torch.float32, device=o.device) if want_mean else None
+    check(lib().udapose_joints_mse_fwd(_hip.stream(), ptr(o), ptr(t), ptr(w), R, HW, ptr(rows), ptr(mean)), "joints_mse_fwd")
+    return rows, mean
+
+
+def _cons_fwd(s, t, m=None, want_mean=True):
+    """udapose_cons_loss_fwd on fp32 contiguous operands: (rows [R], their mean or None).  (Style_net's nn.MSELoss is this without a mask.)"""
+    R, HW = ha.rows(s)
+    rows = torch.empty(R, dtype=torch.float32, device=s.device)
+    mean = torch.empty((), dtype=torch.float32, device=s.device) if want_mean else None
+    check(lib().udapose_cons_loss_fwd(_hip.stream(), ptr(s), ptr(t), ptr(m), R, HW, ptr(rows), ptr(mean)), "cons_loss_fwd")
+    return rows, mean
 
 
 class _JointsMSEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, output, target, weight, reduce_mean):
         _hip.require_cuda(output, target, weight)
-        R, HW = _rows(output)
-        o, t = _f32c(output), _f32c(target)
-        w = None if weight is None else _f32c(weight).reshape(-1)
-        if w is not None and w.numel() != R:
-            raise ValueError("target_weight must have B*K elements")
-        rows = torch.empty(R, dtype=torch.float32, device=o.device)
-        mean = torch.empty((), dtype=torch.float32, device=o.device)
-        check(lib().udapose_joints_mse_fwd(_hip.stream(), ptr(o), ptr(t), ptr(w), R, HW, ptr(rows), ptr(mean)), "joints_mse_fwd")
-        ctx.save_for_backward(o, t, w if w is not None else torch.empty(0, device=o.device))
-        ctx.has_w, ctx.reduce_mean, ctx.shape, ctx.in_dtype = w is not None, reduce_mean, output.shape, output.dtype
+        w = ha.bk_factor(weight, ha.rows(output)[0])
+        o, t = ha.f32c(output), ha.f32c(target)
+        rows, mean = _joints_mse_fwd(o, t, w)
+        ctx.save_for_backward(o, t, w)
+        ctx.reduce_mean, ctx.shape, ctx.in_dtype = reduce_mean, output.shape, output.dtype
         return mean if reduce_mean else rows.reshape(output.shape[0], output.shape[1])
 
     @staticmethod
     def backward(ctx, g):
         o, t, w = ctx.saved_tensors
-        if not ctx.reduce_mean:
-            raise NotImplementedError("backward of reduction='none' is not on the hot path")
-        R, HW = _rows(o)
+        _mean_only(ctx)
+        R, HW = ha.rows(o)
         d = torch.empty_like(o)
-        gs = g.detach().float().reshape(1).contiguous()
-        check(lib().udapose_joints_mse_bwd(_hip.stream(), ptr(o), ptr(t), ptr(w) if ctx.has_w else None, ptr(gs), R, HW, ptr(d)), "joints_mse_bwd")
-        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None, None
+        check(lib().udapose_joints_mse_bwd(_hip.stream(), ptr(o), ptr(t), ptr(w), ptr(ha.gscale(g)), R, HW, ptr(d)), "joints_mse_bwd")
+        return ha.grad_like_input(ctx, d), None, None, None
 
 
 class JointsMSELoss(nn.Module):
@@ -64,56 +79,41 @@ class JointsMSELoss(nn.Module):
         self.reduction = reduction
 
     def forward(self, output, target, target_weight=None):
-        if self.reduction == 'mean':
-            return _JointsMSEFn.apply(output, target, target_weight, True)
-        elif self.reduction == 'none':
-            return _JointsMSEFn.apply(output, target, target_weight, False)
-        # the reference silently returns None for any other string (loss.py:46-49)
+        mean = _reduce_mean(self.reduction)
+        return None if mean is None else _JointsMSEFn.apply(output, target, target_weight, mean)
 
 
 class _ConsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, stu, tea, mask, valid):
         _hip.require_cuda(stu, tea, mask, valid)
-        R, HW = _rows(stu)
-        K = stu.shape[1]
-        s, t = _f32c(stu), _f32c(tea)
-        if mask is not None and mask.dtype == torch.bool and mask.is_contiguous():
-            m = mask.detach().view(torch.uint8).reshape(-1)        # (bool storage is 0 / 1: no conversion launches)
+        R, HW = ha.rows(stu)
+        m = ha.bk_mask(mask, R)
+        s, t = ha.f32c(stu), ha.f32c(tea)
+        v, cnt = ha.valid_selection(valid, stu)
+        if v is None:
+            mean = _cons_fwd(s, t, m)[1]
         else:
-            m = None if mask is None else (mask.detach() != 0).to(torch.uint8).reshape(-1).contiguous()
-        rows = torch.empty(R, dtype=torch.float32, device=s.device)
-        mean = torch.empty((), dtype=torch.float32, device=s.device)
-        v = cnt = None
-        if valid is None:
-            check(lib().udapose_cons_loss_fwd(_hip.stream(), ptr(s), ptr(t), ptr(m), R, HW, ptr(rows), ptr(mean)), "cons_loss_fwd")
-        else:
-            # loss_map[valid_mask].mean() (loss.py:129-130): boolean selection over (b, h, w)
-            if tuple(valid.shape) != (stu.shape[0],) + tuple(stu.shape[2:]):
-                raise IndexError(f"valid_mask shape {tuple(valid.shape)} does not index loss_map {(stu.shape[0],) + tuple(stu.shape[2:])}")
-            v = (valid.detach() != 0).to(torch.uint8).reshape(-1).contiguous()
-            cnt = torch.empty((), dtype=torch.float32, device=s.device)
-            check(lib().udapose_mask_count(_hip.stream(), ptr(v), v.numel(), ptr(cnt)), "mask_count")
-            check(lib().udapose_cons_loss_valid_fwd(_hip.stream(), ptr(s), ptr(t), ptr(m), ptr(v), ptr(cnt), R, K, HW, ptr(rows), ptr(mean)),
-                  "cons_loss_valid_fwd")
-        empty = torch.empty(0, dtype=torch.uint8, device=s.device)
-        ctx.save_for_backward(s, t, m if m is not None else empty, v if v is not None else empty,
-                              cnt if cnt is not None else torch.empty(0, device=s.device))
-        ctx.has_m, ctx.has_v, ctx.shape, ctx.in_dtype = m is not None, v is not None, stu.shape, stu.dtype
+            rows = torch.empty(R, dtype=torch.float32, device=s.device)
+            mean = torch.empty((), dtype=torch.float32, device=s.device)
+            check(lib().udapose_cons_loss_valid_fwd(_hip.stream(), ptr(s), ptr(t), ptr(m), ptr(v), ptr(cnt), R, stu.shape[1], HW, ptr(rows),
+                                                    ptr(mean)), "cons_loss_valid_fwd")
+        ctx.save_for_backward(s, t, m, v, cnt)
+        ctx.shape, ctx.in_dtype = stu.shape, stu.dtype
         return mean
 
     @staticmethod
     def backward(ctx, g):
         s, t, m, v, cnt = ctx.saved_tensors
-        R, HW = _rows(s)
+        R, HW = ha.rows(s)
         d = torch.empty_like(s)
-        gs = g.detach().float().reshape(1).contiguous()
-        if ctx.has_v:
-            check(lib().udapose_cons_loss_valid_bwd(_hip.stream(), ptr(s), ptr(t), ptr(m) if ctx.has_m else None, ptr(v), ptr(cnt), ptr(gs), R,
-                                                    ctx.shape[1], HW, ptr(d)), "cons_loss_valid_bwd")
+        gs = ha.gscale(g)
+        if v is not None:
+            check(lib().udapose_cons_loss_valid_bwd(_hip.stream(), ptr(s), ptr(t), ptr(m), ptr(v), ptr(cnt), ptr(gs), R, ctx.shape[1], HW, ptr(d)),
+                  "cons_loss_valid_bwd")
         else:
-            check(lib().udapose_cons_loss_bwd(_hip.stream(), ptr(s), ptr(t), ptr(m) if ctx.has_m else None, ptr(gs), R, HW, ptr(d)), "cons_loss_bwd")
-        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None, None
+            check(lib().udapose_cons_loss_bwd(_hip.stream(), ptr(s), ptr(t), ptr(m), ptr(gs), R, HW, ptr(d)), "cons_loss_bwd")
+        return ha.grad_like_input(ctx, d), None, None, None
 
 
 class ConsLoss(nn.Module):
@@ -155,44 +155,31 @@ class _TopKSqdiffFn(torch.autograd.Function):
     def forward(ctx, a, b, factor, topk, largest, cons, reduce_mean, owner):
         N, K, topk = _topk_args(a, topk)
         _hip.require_cuda(a, b, factor)
-        R, HW = _rows(a)
-        x, y = _f32c(a), _f32c(b)
-        w = m = None
-        if cons:
-            m = _bytes_mask(factor)
-        elif factor is not None:
-            w = _f32c(factor).reshape(-1)
-        for f, what in ((w, "target_weight"), (m, "tea_mask")):
-            if f is not None and f.numel() != R:
-                raise ValueError(f"{what} must have B*K elements")
-        rows = torch.empty(R, dtype=torch.float32, device=x.device)
+        R = N * K
+        w = None if cons else ha.bk_factor(factor, R)
+        m = ha.bk_mask(factor, R) if cons else None
+        x, y = ha.f32c(a), ha.f32c(b)
+        rows = (_cons_fwd(x, y, m, want_mean=False) if cons else _joints_mse_fwd(x, y, w, want_mean=False))[0]
         sel = torch.empty(R, dtype=torch.uint8, device=x.device)
         sample = torch.empty(N, dtype=torch.float32, device=x.device)
         mean = torch.empty((), dtype=torch.float32, device=x.device) if reduce_mean else None
-        if cons:
-            check(lib().udapose_cons_loss_fwd(_hip.stream(), ptr(x), ptr(y), ptr(m), R, HW, ptr(rows), None), "cons_loss_fwd")
-        else:
-            check(lib().udapose_joints_mse_fwd(_hip.stream(), ptr(x), ptr(y), ptr(w), R, HW, ptr(rows), None), "joints_mse_fwd")
         check(lib().udapose_topk_select(_hip.stream(), ptr(rows), ptr(w), ptr(m), N, K, topk, int(bool(largest)), ptr(sel), ptr(sample), ptr(mean)),
               "topk_select")
         if owner is not None:
             owner.last_selection = sel.view(torch.bool).reshape(N, K)       # (the kernel writes 0 / 1: a bool view, not a conversion launch)
-        ctx.save_for_backward(x, y, w if w is not None else torch.empty(0, device=x.device), sel)
-        ctx.has_w, ctx.cons, ctx.topk, ctx.reduce_mean, ctx.shape, ctx.in_dtype = w is not None, cons, topk, reduce_mean, a.shape, a.dtype
+        ctx.save_for_backward(x, y, w, sel)
+        ctx.cons, ctx.topk, ctx.reduce_mean, ctx.shape, ctx.in_dtype = cons, topk, reduce_mean, a.shape, a.dtype
         return mean if reduce_mean else sample
 
     @staticmethod
     def backward(ctx, g):
         x, y, w, sel = ctx.saved_tensors
-        if not ctx.reduce_mean:
-            raise NotImplementedError("backward of reduction='none' is not on the hot path")
+        _mean_only(ctx)
         N, K = ctx.shape[:2]
-        R, HW = _rows(x)
         d = torch.empty_like(x)
-        gs = _gscale(g)
-        check(lib().udapose_topk_sqdiff_bwd(_hip.stream(), ptr(x), ptr(y), ptr(w) if ctx.has_w else None, ptr(sel), ptr(gs), N, K, HW, ctx.topk,
+        check(lib().udapose_topk_sqdiff_bwd(_hip.stream(), ptr(x), ptr(y), ptr(w), ptr(sel), ptr(ha.gscale(g)), N, K, ha.rows(x)[1], ctx.topk,
                                             0 if ctx.cons else 1, ptr(d)), "topk_sqdiff_bwd")
-        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None, None, None, None, None, None
+        return ha.grad_like_input(ctx, d), None, None, None, None, None, None, None
 
 
 class JointsOHKMMSELoss(nn.Module):
@@ -213,9 +200,8 @@ class JointsOHKMMSELoss(nn.Module):
         self.last_selection = None
 
     def forward(self, output, target, target_weight=None):
-        if self.reduction not in ('mean', 'none'):
-            return None         # (as the other classes of this module)
-        return _TopKSqdiffFn.apply(output, target, target_weight, self.topk, True, False, self.reduction == 'mean', self)
+        mean = _reduce_mean(self.reduction)
+        return None if mean is None else _TopKSqdiffFn.apply(output, target, target_weight, self.topk, True, False, mean, self)
 
 
 class ConsTopKLoss(nn.Module):
@@ -239,49 +225,32 @@ class ConsTopKLoss(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------- the soft-max family
-def _bytes_mask(mask):
-    """(b,k) mask as bytes, _ConsFn's conventions: bool storage is read as it is, anything else is `!= 0`."""
-    if mask is None:
-        return None
-    if mask.dtype == torch.bool and mask.is_contiguous():
-        return mask.detach().view(torch.uint8).reshape(-1)
-    return (mask.detach() != 0).to(torch.uint8).reshape(-1).contiguous()
-
-
-def _gscale(g):
-    return g.detach().float().reshape(1).contiguous()
-
-
 class _JointsKLFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, output, target, weight, reduce_mean, eps):
         _hip.require_cuda(output, target, weight)
-        R, HW = _rows(output)
+        R, HW = ha.rows(output)
         B, K = output.shape[:2]
-        o, t = _f32c(output), _f32c(target)
-        w = None if weight is None else _f32c(weight).reshape(-1)
-        if w is not None and w.numel() != R:
-            raise ValueError("target_weight must have B*K elements")
+        w = ha.bk_factor(weight, R)
+        o, t = ha.f32c(output), ha.f32c(target)
         rows = torch.empty(R, dtype=torch.float32, device=o.device)
         stats = torch.empty(5 * R, dtype=torch.float32, device=o.device)
         out = torch.empty(() if reduce_mean else (B,), dtype=torch.float32, device=o.device)
         check(lib().udapose_joints_kl_fwd(_hip.stream(), ptr(o), ptr(t), ptr(w), eps, R, R if reduce_mean else K, HW, ptr(rows), ptr(stats),
                                           ptr(out)), "joints_kl_fwd")
-        ctx.save_for_backward(o, t, w if w is not None else torch.empty(0, device=o.device), stats)
-        ctx.has_w, ctx.reduce_mean, ctx.eps, ctx.shape, ctx.in_dtype = w is not None, reduce_mean, eps, output.shape, output.dtype
+        ctx.save_for_backward(o, t, w, stats)
+        ctx.reduce_mean, ctx.eps, ctx.shape, ctx.in_dtype = reduce_mean, eps, output.shape, output.dtype
         return out
 
     @staticmethod
     def backward(ctx, g):
         o, t, w, stats = ctx.saved_tensors
-        if not ctx.reduce_mean:
-            raise NotImplementedError("backward of reduction='none' is not on the hot path")
-        R, HW = _rows(o)
+        _mean_only(ctx)
+        R, HW = ha.rows(o)
         d = torch.empty_like(o)
-        gs = _gscale(g)
-        check(lib().udapose_joints_kl_bwd(_hip.stream(), ptr(o), ptr(t), ptr(w) if ctx.has_w else None, ctx.eps, ptr(stats), ptr(gs), R, HW,
-                                          ptr(d)), "joints_kl_bwd")
-        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None, None, None
+        check(lib().udapose_joints_kl_bwd(_hip.stream(), ptr(o), ptr(t), ptr(w), ctx.eps, ptr(stats), ptr(ha.gscale(g)), R, HW, ptr(d)),
+              "joints_kl_bwd")
+        return ha.grad_like_input(ctx, d), None, None, None, None
 
 
 class JointsKLLoss(nn.Module):
@@ -294,20 +263,17 @@ class JointsKLLoss(nn.Module):
         self.epsilon = epsilon
 
     def forward(self, output, target, target_weight=None):
-        if self.reduction == 'mean':
-            return _JointsKLFn.apply(output, target, target_weight, True, float(self.epsilon))
-        elif self.reduction == 'none':
-            return _JointsKLFn.apply(output, target, target_weight, False, float(self.epsilon))
-        # any other string: None, as the reference (loss.py:92-95)
+        mean = _reduce_mean(self.reduction)
+        return None if mean is None else _JointsKLFn.apply(output, target, target_weight, mean, float(self.epsilon))
 
 
 class _EntFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, threshold, reduce_mean):
         _hip.require_cuda(x)
-        R, HW = _rows(x)
+        R, HW = ha.rows(x)
         B, K = x.shape[:2]
-        s = _f32c(x)
+        s = ha.f32c(x)
         thr = float(threshold) if threshold > 0 else 0.0
         scalar = reduce_mean or thr > 0        # (a threshold makes the selection 1-D: its mean(dim=-1) is a scalar too, loss.py:111-117)
         rows = torch.empty(R, dtype=torch.float32, device=s.device)
@@ -325,12 +291,11 @@ class _EntFn(torch.autograd.Function):
         s, rows, stats, cnt = ctx.saved_tensors
         if not ctx.scalar:
             raise NotImplementedError("backward of reduction='none' is not on the hot path")
-        R, HW = _rows(s)
+        R, HW = ha.rows(s)
         d = torch.empty_like(s)
-        gs = _gscale(g)
-        check(lib().udapose_entropy_loss_bwd(_hip.stream(), ptr(s), ptr(rows), ptr(stats), ptr(cnt), ptr(gs), ctx.thr, R, HW, ptr(d)),
+        check(lib().udapose_entropy_loss_bwd(_hip.stream(), ptr(s), ptr(rows), ptr(stats), ptr(cnt), ptr(ha.gscale(g)), ctx.thr, R, HW, ptr(d)),
               "entropy_loss_bwd")
-        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None
+        return ha.grad_like_input(ctx, d), None, None
 
 
 class EntLoss(nn.Module):
@@ -342,10 +307,8 @@ class EntLoss(nn.Module):
         self.reduction = reduction
 
     def forward(self, x, threshold=-1):
-        if self.reduction == 'mean':
-            return _EntFn.apply(x, threshold, True)
-        elif self.reduction == 'none':
-            return _EntFn.apply(x, threshold, False)
+        mean = _reduce_mean(self.reduction)
+        return None if mean is None else _EntFn.apply(x, threshold, mean)
 
 
 class _ConsProbFn(torch.autograd.Function):
@@ -354,48 +317,38 @@ class _ConsProbFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, stu, tea, mask, valid, mode):
         _hip.require_cuda(stu, tea, mask, valid)
-        R, HW = _rows(stu)
+        R, HW = ha.rows(stu)
         K = stu.shape[1]
-        s, t = _f32c(stu), _f32c(tea)
-        m = _bytes_mask(mask)
+        m = ha.bk_mask(mask, R)
+        s, t = ha.f32c(stu), ha.f32c(tea)
+        v, cnt = ha.valid_selection(valid, stu)
         rows = torch.empty(R, dtype=torch.float32, device=s.device)
         stats = torch.empty(7 * R, dtype=torch.float32, device=s.device)
         out = torch.empty((), dtype=torch.float32, device=s.device)
-        v = cnt = None
-        if valid is not None:
-            # loss_map[valid_mask].mean() (loss.py:149-150, 170-171): boolean selection over (b, h, w)
-            if tuple(valid.shape) != (stu.shape[0],) + tuple(stu.shape[2:]):
-                raise IndexError(f"valid_mask shape {tuple(valid.shape)} does not index loss_map {(stu.shape[0],) + tuple(stu.shape[2:])}")
-            v = (valid.detach() != 0).to(torch.uint8).reshape(-1).contiguous()
-            cnt = torch.empty((), dtype=torch.float32, device=s.device)
-            check(lib().udapose_mask_count(_hip.stream(), ptr(v), v.numel(), ptr(cnt)), "mask_count")
         if mode == 0:
             check(lib().udapose_cons_softmax_fwd(_hip.stream(), ptr(s), ptr(t), ptr(m), ptr(v), ptr(cnt), R, K, HW, ptr(rows), ptr(stats),
                                                  ptr(out)), "cons_softmax_fwd")
         else:
             check(lib().udapose_cons_kl_fwd(_hip.stream(), ptr(s), ptr(t), ptr(m), ptr(v), ptr(cnt), int(mode == 1), R, K, HW, ptr(rows),
                                             ptr(stats), ptr(out)), "cons_kl_fwd")
-        empty = torch.empty(0, dtype=torch.uint8, device=s.device)
-        ctx.save_for_backward(s, t, m if m is not None else empty, v if v is not None else empty,
-                              cnt if cnt is not None else torch.empty(0, device=s.device), stats)
-        ctx.has_m, ctx.has_v, ctx.mode, ctx.shape, ctx.in_dtype = m is not None, v is not None, mode, stu.shape, stu.dtype
+        ctx.save_for_backward(s, t, m, v, cnt, stats)
+        ctx.mode, ctx.shape, ctx.in_dtype = mode, stu.shape, stu.dtype
         return out
 
     @staticmethod
     def backward(ctx, g):
         s, t, m, v, cnt, stats = ctx.saved_tensors
-        R, HW = _rows(s)
+        R, HW = ha.rows(s)
         K = ctx.shape[1]
         d = torch.empty_like(s)
-        gs = _gscale(g)
-        pm, pv, pc = (ptr(m) if ctx.has_m else None), (ptr(v) if ctx.has_v else None), (ptr(cnt) if ctx.has_v else None)
+        gs = ha.gscale(g)
         if ctx.mode == 0:
-            check(lib().udapose_cons_softmax_bwd(_hip.stream(), ptr(s), ptr(t), pm, pv, pc, ptr(stats), ptr(gs), R, K, HW, ptr(d)),
+            check(lib().udapose_cons_softmax_bwd(_hip.stream(), ptr(s), ptr(t), ptr(m), ptr(v), ptr(cnt), ptr(stats), ptr(gs), R, K, HW, ptr(d)),
                   "cons_softmax_bwd")
         else:
-            check(lib().udapose_cons_kl_bwd(_hip.stream(), ptr(s), ptr(t), pm, pv, pc, int(ctx.mode == 1), ptr(stats), ptr(gs), R, K, HW,
-                                            ptr(d)), "cons_kl_bwd")
-        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None, None, None
+            check(lib().udapose_cons_kl_bwd(_hip.stream(), ptr(s), ptr(t), ptr(m), ptr(v), ptr(cnt), int(ctx.mode == 1), ptr(stats), ptr(gs), R, K,
+                                            HW, ptr(d)), "cons_kl_bwd")
+        return ha.grad_like_input(ctx, d), None, None, None, None
 
 
 class ConsSoftmaxLoss(nn.Module):
@@ -442,42 +395,34 @@ class _CoordLossFn(torch.autograd.Function):
         _hip.require_cuda(output, coords, weight, mask)
         B, K, H, W = output.shape
         R = B * K
-        o, t = _f32c(output), _f32c(coords)
-        if t.numel() != 2 * R:
+        if coords.numel() != 2 * R:
             raise ValueError("target coordinates must be [B,K,2]")
-        w = None if weight is None else _f32c(weight).reshape(-1)
-        if w is not None and w.numel() != R:
-            raise ValueError("target_weight must have B*K elements")
-        m = _bytes_mask(mask)
-        if m is not None and m.numel() != R:
-            raise ValueError("the (b,k) mask must have B*K elements")
+        w = ha.bk_factor(weight, R)
+        m = ha.bk_mask(mask, R, "the (b,k) mask")
+        o, t = ha.f32c(output), ha.f32c(coords)
         rows = torch.empty(R, dtype=torch.float32, device=o.device)
         idx = torch.empty(R, dtype=torch.int32, device=o.device)
         stats = torch.empty(4 * R, dtype=torch.float32, device=o.device)
         out = torch.empty(() if reduce_mean else (B,), dtype=torch.float32, device=o.device)
         check(lib().udapose_coord_loss_fwd(_hip.stream(), ptr(o), ptr(t), ptr(w), ptr(m), R, R if reduce_mean else K, H, W, beta, window, norm,
                                            ptr(rows), ptr(idx), ptr(stats), ptr(out)), "coord_loss_fwd")
-        ctx.save_for_backward(o, t, w if w is not None else torch.empty(0, device=o.device),
-                              m if m is not None else torch.empty(0, dtype=torch.uint8, device=o.device), idx, stats)
-        ctx.has_w, ctx.has_m, ctx.reduce_mean, ctx.shape, ctx.in_dtype = w is not None, m is not None, reduce_mean, output.shape, output.dtype
+        ctx.save_for_backward(o, t, w, m, idx, stats)
+        ctx.reduce_mean, ctx.shape, ctx.in_dtype = reduce_mean, output.shape, output.dtype
         ctx.beta, ctx.window, ctx.norm = beta, window, norm
         return out
 
     @staticmethod
     def backward(ctx, g):
         o, t, w, m, idx, stats = ctx.saved_tensors
-        if not ctx.reduce_mean:
-            raise NotImplementedError("backward of reduction='none' is not on the hot path")
+        _mean_only(ctx)
         B, K, H, W = ctx.shape
         d = torch.empty_like(o)
-        gs = _gscale(g)
-        check(lib().udapose_coord_loss_bwd(_hip.stream(), ptr(o), ptr(t), ptr(w) if ctx.has_w else None, ptr(m) if ctx.has_m else None, ptr(idx),
-                                           ptr(stats), ptr(gs), B * K, H, W, ctx.beta, ctx.window, ctx.norm, ptr(d)), "coord_loss_bwd")
-        return d.reshape(ctx.shape).to(ctx.in_dtype), None, None, None, None, None, None, None
+        check(lib().udapose_coord_loss_bwd(_hip.stream(), ptr(o), ptr(t), ptr(w), ptr(m), ptr(idx), ptr(stats), ptr(ha.gscale(g)), B * K, H, W,
+                                           ctx.beta, ctx.window, ctx.norm, ptr(d)), "coord_loss_bwd")
+        return ha.grad_like_input(ctx, d), None, None, None, None, None, None, None
 
 
 def _coord_args(beta, window, norm):
-    from ..keypoint_detection import _soft_args
     if norm not in _NORMS:
         raise ValueError(f"norm must be 'l1' or 'l2', got {norm!r}")
     return _soft_args(beta, window) + (_NORMS[norm],)
@@ -485,10 +430,9 @@ def _coord_args(beta, window, norm):
 
 def _argmax_decode(hm):
     """(coords [B,K,2], maxvals [B,K,1]) of get_max_preds, on fp32 rows and without a graph."""
-    from ..keypoint_detection import _decode
     _hip.require_cuda(hm)
     with torch.no_grad():
-        return _decode(_f32c(hm))
+        return _decode(ha.f32c(hm))
 
 
 class JointsSoftArgmaxLoss(nn.Module):
@@ -505,14 +449,15 @@ class JointsSoftArgmaxLoss(nn.Module):
         self.beta, self.window, self.norm, self.reduction = beta, window, norm, reduction
 
     def forward(self, output, target, target_weight=None):
-        if self.reduction not in ('mean', 'none'):
-            return None         # (as the other classes of this module)
+        mean = _reduce_mean(self.reduction)
+        if mean is None:
+            return None
         beta, window, norm = _coord_args(self.beta, self.window, self.norm)
         present = None
         if target.dim() == 4:
             target, maxv = _argmax_decode(target)
             present = maxv > 0
-        return _CoordLossFn.apply(output, target, target_weight, present, self.reduction == 'mean', beta, window, norm)
+        return _CoordLossFn.apply(output, target, target_weight, present, mean, beta, window, norm)
 
 
 class ConsSoftArgmaxLoss(nn.Module):
@@ -536,7 +481,6 @@ class ConsSoftArgmaxLoss(nn.Module):
         if self.tea_decode == "argmax":
             tea_xy, _ = _argmax_decode(tea_out)
         else:
-            from ..keypoint_detection import soft_argmax
             with torch.no_grad():
                 tea_xy, _ = soft_argmax(tea_out.detach(), beta, None if window < 0 else window)
         return _CoordLossFn.apply(stu_out, tea_xy, None, tea_mask, True, beta, window, norm)
@@ -567,7 +511,7 @@ class _GramCoralFn(torch.autograd.Function):
             raise ValueError(f"GramCoralLoss: the batch size must be 2 ... 64 (a covariance needs two samples; the kernels hold 2N <= 128 rows), got {N}")
         if H // down < 1 or W // down < 1:
             raise ValueError(f"GramCoralLoss: coral_downsample {down} leaves no pixel of a {H}x{W} map")
-        s, t = _f32c(src), _f32c(tgt)
+        s, t = ha.f32c(src), ha.f32c(tgt)
         mp = (2 * N + 31) // 32 * 32
         ws = torch.empty(int(lib().udapose_coral_ws_bytes(N, K, H, W, down)) // 8, dtype=torch.float64, device=s.device)
         coef = torch.empty(mp * mp, dtype=torch.float32, device=s.device)
@@ -582,7 +526,7 @@ class _GramCoralFn(torch.autograd.Function):
         s, t, coef = ctx.saved_tensors
         N, K, H, W = ctx.shape
         ds, dt = torch.empty_like(s), torch.empty_like(t)
-        gs = _gscale(g)
+        gs = ha.gscale(g)
         check(lib().udapose_coral_bwd(_hip.stream(), ptr(s), ptr(t), ptr(coef), ptr(gs), N, K, H, W, ctx.down, ptr(ds), ptr(dt)), "coral_bwd")
         return ds.to(ctx.dtypes[0]), dt.to(ctx.dtypes[1]), None
 

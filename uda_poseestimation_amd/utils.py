@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _hip
+from . import heatmap_args as ha
 from ._hip import check, lib, ptr
 
 
@@ -87,77 +88,36 @@ def get_max_preds_torch_raw(batch_heatmaps):
     """(x = idx % W, y = idx // W) [B,K,2] and the maxima [B,K,1] WITHOUT the max>0 masking: what the occlusion code
     computes inline with amax / view().argmax(-1) (train_human.py:378-381)."""
     _hip.require_cuda(batch_heatmaps)
-    hm = batch_heatmaps.detach().float().contiguous()
-    B, K, H, W = hm.shape
-    idx = torch.empty(B, K, dtype=torch.int32, device=hm.device)
-    maxv = torch.empty(B, K, 1, dtype=torch.float32, device=hm.device)
-    check(lib().udapose_heatmap_argmax(_hip.stream(), ptr(hm), B * K, H, W, ptr(maxv), ptr(idx), None, None, None, 0), "heatmap_argmax")
-    idx = idx.long()
-    return torch.stack([idx % W, idx // W], -1), maxv
+    r = ha.heatmap_argmax(ha.f32c(batch_heatmaps), maxv=True, idx=True)
+    idx, W = r.idx.long(), batch_heatmaps.shape[3]
+    return torch.stack([idx % W, idx // W], -1), r.maxv.unsqueeze(-1)
 
 
 def get_max_preds_torch(batch_heatmaps):
     """utils.py:54-75: (preds [B,K,2] float (x,y) zeroed where max<=0, maxvals [B,K,1])."""
     _hip.require_cuda(batch_heatmaps)
-    hm = batch_heatmaps.detach().float().contiguous()
-    B, K, H, W = hm.shape
-    preds = torch.empty(B, K, 2, dtype=torch.float32, device=hm.device)
-    maxv = torch.empty(B, K, 1, dtype=torch.float32, device=hm.device)
-    check(lib().udapose_heatmap_argmax(_hip.stream(), ptr(hm), B * K, H, W, ptr(maxv), None, ptr(preds), None, None, 0), "heatmap_argmax")
-    return preds, maxv.to(batch_heatmaps.dtype)
-
-
-_PATCH_CACHE = {}
-
-
-def _gauss_patch(sigma, device):
-    """The (6*sigma+1)^2 un-normalised Gaussian exactly as utils.py:93-98 builds it (host, once per sigma)."""
-    key = (float(sigma), type(sigma) is int, str(device))
-    if key not in _PATCH_CACHE:
-        tmp_size = 3 * sigma
-        if float(tmp_size) != int(tmp_size):
-            raise NotImplementedError("rectify on the device needs 3*sigma to be an integer (reference uses sigma=2 or 1.0)")
-        size = 2 * tmp_size + 1
-        x = torch.arange(0, size, 1).float()
-        y = x.unsqueeze(1)
-        x0 = y0 = size // 2
-        g = torch.exp(- ((x - x0) ** 2 + (y - y0) ** 2) / (2 * sigma ** 2))
-        _PATCH_CACHE[key] = (g.contiguous().to(device), int(tmp_size))
-    return _PATCH_CACHE[key]
+    r = ha.heatmap_argmax(ha.f32c(batch_heatmaps), maxv=True, xy=True)
+    return r.xy, r.maxv.unsqueeze(-1).to(batch_heatmaps.dtype)
 
 
 def rectify(hm, sigma):  # b, c, h, w -> b, c, h, w
     """utils.py:77-109 as ONE kernel: arg-max per (b,c) then the Gaussian patch stamped into a zero map (clipped)."""
     _hip.require_cuda(hm)
-    src = hm.detach().float().contiguous()
-    B, K, H, W = src.shape
-    patch, rad = _gauss_patch(sigma, src.device)
-    out = torch.empty_like(src)
-    check(lib().udapose_heatmap_argmax(_hip.stream(), ptr(src), B * K, H, W, None, None, None, ptr(out), ptr(patch), rad), "rectify")
-    return out.to(hm.dtype)
+    return ha.heatmap_argmax(ha.f32c(hm), rectify_sigma=sigma).rect.to(hm.dtype)
 
 
 def heatmap_activations(recon):
     """activates = amax over (h,w) per (b,k)  (train_human.py:427), one sweep."""
     _hip.require_cuda(recon)
-    src = recon.detach().float().contiguous()
-    B, K, H, W = src.shape
-    act = torch.empty(B, K, dtype=torch.float32, device=src.device)
-    check(lib().udapose_heatmap_argmax(_hip.stream(), ptr(src), B * K, H, W, ptr(act), None, None, None, None, 0), "amax")
-    return act
+    return ha.heatmap_argmax(ha.f32c(recon), maxv=True).maxv
 
 
 def activations_and_rectify(recon, sigma):
     """heatmap_activations(recon) and rectify(recon, sigma) from ONE sweep (the arg-max of a (b,k) plane gives both; the mean-teacher step
     needs both from the teacher's re-warped heat-maps, train_human.py:427 and :431).  Returns (activates [B,K], rectified [B,K,H,W])."""
     _hip.require_cuda(recon)
-    src = recon.detach().float().contiguous()
-    B, K, H, W = src.shape
-    patch, rad = _gauss_patch(sigma, src.device)
-    act = torch.empty(B, K, dtype=torch.float32, device=src.device)
-    out = torch.empty_like(src)
-    check(lib().udapose_heatmap_argmax(_hip.stream(), ptr(src), B * K, H, W, ptr(act), None, None, ptr(out), ptr(patch), rad), "amax + rectify")
-    return act, out.to(recon.dtype)
+    r = ha.heatmap_argmax(ha.f32c(recon), maxv=True, rectify_sigma=sigma)
+    return r.maxv, r.rect.to(recon.dtype)
 
 
 MASK_MODES = ("global", "per_joint", "threshold")
@@ -266,12 +226,10 @@ def generate_prior_map(prior, preds, gamma=2, sigma=2, epsilon=-10e10, v3=False,
     if not v3 and not (np.isfinite(float(gamma)) and float(gamma) != 0):
         raise ValueError(f"generate_prior_map: gamma must be finite and non-zero, got {gamma}")
     mean_d, w = _prior_tables(prior, K, gamma, epsilon, v3, preds.device)
-    hm = preds.detach().float().contiguous()
-    coords = torch.empty(B, K, 2, dtype=torch.float32, device=hm.device)
-    conf = torch.empty(B, K, dtype=torch.float32, device=hm.device)
-    check(lib().udapose_heatmap_argmax(_hip.stream(), ptr(hm), B * K, H, W, ptr(conf), None, ptr(coords), None, None, 0), "heatmap_argmax")
+    hm = ha.f32c(preds)
+    peak = ha.heatmap_argmax(hm, maxv=True, xy=True)
     out = torch.empty_like(hm)
-    check(lib().udapose_prior_map(_hip.stream(), ptr(coords), ptr(conf), ptr(mean_d), ptr(w), ptr(hm) if multiply else None, B, K, H, W, float(sigma),
+    check(lib().udapose_prior_map(_hip.stream(), ptr(peak.xy), ptr(peak.maxv), ptr(mean_d), ptr(w), ptr(hm) if multiply else None, B, K, H, W, float(sigma),
                                   int(bool(v3)), ptr(out)), "prior_map")
     return out.to(preds.dtype)
 

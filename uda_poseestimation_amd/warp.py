@@ -15,6 +15,7 @@ import math
 import torch
 
 from . import _hip
+from . import heatmap_args as ha
 from ._hip import check, lib, ptr
 
 
@@ -326,15 +327,13 @@ def occlude_keypoints_device(x_t_stu, y_t_tea_recon, theta_fwd, theta_back, u, r
     selected samples keep the result (the others are returned bit-identical).  Returns (images, apply [N] uint8)."""
     _hip.require_cuda(x_t_stu, y_t_tea_recon, theta_fwd, theta_back, u)
     B, K, h, w = y_t_tea_recon.shape
-    hm = y_t_tea_recon.detach().float().contiguous()
-    conf = torch.empty(B, K, dtype=torch.float32, device=hm.device)
-    idx = torch.empty(B, K, dtype=torch.int32, device=hm.device)
-    check(lib().udapose_heatmap_argmax(_hip.stream(), ptr(hm), B * K, h, w, ptr(conf), ptr(idx), None, None, None, 0), "heatmap_argmax")
+    hm = ha.f32c(y_t_tea_recon)
+    peak = ha.heatmap_argmax(hm, maxv=True, idx=True)
     boxes = torch.empty(B, 6, dtype=torch.int32, device=hm.device)
     apply = torch.empty(B, dtype=torch.uint8, device=hm.device)
     uu = u.detach().float().contiguous()
     assert tuple(uu.shape) == (B, 4)
-    check(lib().udapose_occlusion_pick(_hip.stream(), ptr(conf), ptr(idx), ptr(uu), B, K, w, float(ratio), int(image_size), float(occlude_rate),
+    check(lib().udapose_occlusion_pick(_hip.stream(), ptr(peak.maxv), ptr(peak.idx), ptr(uu), B, K, w, float(ratio), int(image_size), float(occlude_rate),
                                        float(occlude_thresh), int(occlude_size), ptr(boxes), ptr(apply)), "occlusion_pick")
     x = x_t_stu.detach().float().contiguous()
     temp = warp_chain(x, theta_fwd).contiguous()
