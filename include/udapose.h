@@ -878,6 +878,30 @@ int udapose_aug_color_op(void* stream, unsigned char* img, const int* op, const 
  * the scratch buffer tmp (same size): three box-blur passes per direction in PIL's 8.24 fixed point, bit-exact.  prm[n] = (r, ww, fw)
  * as uint32 (box radius integer part, centre and far weights: data_gpu.pil_box_blur_params), r = 0xffffffff: sample n is left as is. */
 int udapose_aug_gaussian_blur_u8(void* stream, unsigned char* img, unsigned char* tmp, const unsigned int* prm, int N, int H, int W);
+/* The strong student view (FixMatch / RandAugment colour ops; no counterpart in the reference, whose student view is ColorJitter), in place
+ * on img [N][HW][3] uint8, byte for byte PIL's results.  op [N] continues aug_color_op's codes, one per image: 4 ImageOps.autocontrast
+ * (cutoff 0), 5 ImageOps.equalize, 6 ImageOps.posterize(bits = param[n], 1..8), 7 ImageOps.solarize (param[n] = the integer cut
+ * ceil(threshold) in [0, 256]: a pixel below it is kept, any other becomes 255 - i); an image with any other code is left alone.
+ * Two launches, no read-back: a per-image, per-channel 256-entry table into lut_scratch [N][768] bytes (ops 4 and 5 from the image's own
+ * histograms, counted on the device), then the look-up.  inv_scale [255] double on the device, inv_scale[d - 1] = 255.0 / d computed by
+ * the host (autocontrast's scale: the table is formed in fp64 with separately rounded product and sum, no fp64 divide on the device).
+ * param [N] int is read for ops 6 and 7 only.  The histograms count in 32 bits: UDAPOSE_ERR_UNSUPPORTED above HW = UDAPOSE_AUG_MAX_HW
+ * (2^30: equalize's running sum step / 2 + HW stays below 2^31).  UDAPOSE_ERR_ARG: a null pointer, N or HW < 1. */
+#define UDAPOSE_AUG_MAX_HW (1 << 30)
+int udapose_aug_point_op(void* stream, unsigned char* img, const int* op, const int* param, const double* inv_scale, unsigned char* lut_scratch,
+                         int N, int HW);
+/* op code 8, ImageEnhance.Sharpness(img).enhance(factor[n]) = Image.blend(img.filter(SMOOTH), img, factor), in place on img [N][H][W][3]
+ * uint8 through the scratch buffer tmp (same size; the images with op[n] == 8 are copied there and the stencil reads the copy).  SMOOTH is
+ * the 3x3 kernel (1,1,1,1,5,1,1,1,1) / 13 in float32 exactly as libImaging sums it (coefficients float32(k / 13), start 0.5f, rows top
+ * down, no fused multiply-add), the one-pixel border keeps its bytes; the blend is aug_color_op's.  H < 3 or W < 3: nothing is launched
+ * (PIL returns the image).  An image with any other code is left alone.  UDAPOSE_ERR_ARG: a null pointer, N, H or W < 1;
+ * UDAPOSE_ERR_UNSUPPORTED: H * W above UDAPOSE_AUG_MAX_HW. */
+int udapose_aug_sharpness_u8(void* stream, unsigned char* img, unsigned char* tmp, const int* op, const float* factor, int N, int H, int W);
+/* RandomErasing's write (lib/transforms/__init__.py:171-174) on x [N][3][H][W] fp32, in place: x[n][c][top : top + h, left : left + w] = v_c
+ * with boxes[n] = (top, left, h, w) int32 on the device.  A box with h or w < 1 erases nothing; so does one that leaves the image.
+ * Everything outside the box keeps its bits.  UDAPOSE_ERR_ARG: a null pointer, N, H or W < 1; UDAPOSE_ERR_UNSUPPORTED: H * W above
+ * UDAPOSE_AUG_MAX_HW. */
+int udapose_aug_erase_f32(void* stream, float* x, const int* boxes, float v0, float v1, float v2, int N, int H, int W);
 /* T.RandomResizedCrop's image side (lib/transforms/keypoint_detection.py:456-521 -> resized_crop :66-88 = F.crop + F.resize(BILINEAR) on a
  * PIL image): src [N][Hs][Ws][3] uint8 -> dst [N][S][S][3] uint8, sample n's crop box[n] = (top, left, h, w) resampled to S x S with PIL's
  * two-pass 8-bit resampler (libImaging Resample.c: horizontal pass into the uint8 intermediate tmp [N][Hs][S][3], then vertical; 22-bit

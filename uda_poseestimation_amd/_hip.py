@@ -180,6 +180,9 @@ _SIGS = {
     "udapose_aug_to_tensor": (ci, [vp, vp, vp, ci, ci, vp, vp]),
     "udapose_aug_gaussian_blur_u8": (ci, [vp, vp, vp, vp, ci, ci, ci]),
     "udapose_aug_resized_crop_u8": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci]),
+    "udapose_aug_point_op": (ci, [vp, vp, vp, vp, vp, vp, ci, ci]),
+    "udapose_aug_sharpness_u8": (ci, [vp, vp, vp, vp, vp, ci, ci, ci]),
+    "udapose_aug_erase_f32": (ci, [vp, vp, vp, cf, cf, cf, ci, ci, ci]),
     "udapose_gaussian_labels": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, cd, cd, vp, ci]),
     "udapose_gaussian_labels_subpixel": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, cd, cd, cd, ci]),
     "udapose_split_saturations": (ci, [ci, vp]),

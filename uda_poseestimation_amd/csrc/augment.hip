@@ -9,6 +9,7 @@
 //     L = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16.
 // All kernels are byte / float sweeps (HBM-bound, 196 KB per 256x256 image); images are uint8 NHWC as PIL arrays are.
 #include "data.h"
+#include "blend.h"      // blend1: Image.blend on one byte
 
 // no FMA contraction: PIL's blend rounds the product and the sum separately (d + f * (v - d) in C float); a fused
 // multiply-add lands on the other side of an integer for ~1 % of the bytes and the truncation to uint8 then differs
@@ -58,13 +59,6 @@ __global__ void aug_gray_mean_k(const unsigned char* __restrict__ img, const int
         // int(t / HW + 0.5) with t / HW in double exactly as ImageStat computes it (sum / count), then truncation
         mean[n] = (int)((double)t / (double)HW + 0.5);
     }
-}
-
-__device__ __forceinline__ unsigned char blend1(float d, float v, float f) {
-    float prod = f * (v - d);
-    asm volatile("" : "+v"(prod));        // (belt and braces: the product is pinned in a register, no contraction can cross this)
-    const float t = d + prod;
-    return t <= 0.f ? 0 : (t >= 255.f ? 255 : (unsigned char)t);
 }
 
 // one ImageEnhance step per image, in place: op 0 none, 1 brightness, 2 contrast, 3 saturation (Color)

@@ -592,6 +592,19 @@ int udapose_aug_gaussian_blur_u8(void* stream, unsigned char* img, unsigned char
     if (!img || !tmp || !prm) return UDAPOSE_ERR_ARG;
     return aug_gaussian_blur_u8(S(stream), img, tmp, prm, N, H, W);
 }
+int udapose_aug_point_op(void* stream, unsigned char* img, const int* op, const int* param, const double* inv_scale, unsigned char* lut_scratch,
+                         int N, int HW) {
+    if (!img || !op || !param || !inv_scale || !lut_scratch) return UDAPOSE_ERR_ARG;
+    return aug_point_op(S(stream), img, op, param, inv_scale, lut_scratch, N, HW);
+}
+int udapose_aug_sharpness_u8(void* stream, unsigned char* img, unsigned char* tmp, const int* op, const float* factor, int N, int H, int W) {
+    if (!img || !tmp || !op || !factor) return UDAPOSE_ERR_ARG;
+    return aug_sharpness_u8(S(stream), img, tmp, op, factor, N, H, W);
+}
+int udapose_aug_erase_f32(void* stream, float* x, const int* boxes, float v0, float v1, float v2, int N, int H, int W) {
+    if (!x || !boxes) return UDAPOSE_ERR_ARG;
+    return aug_erase_f32(S(stream), x, boxes, v0, v1, v2, N, H, W);
+}
 int udapose_aug_resized_crop_u8(void* stream, const unsigned char* src, unsigned char* dst, unsigned char* tmp, const int* box, const int* bounds,
                                 const int* coef, int N, int Hs, int Ws, int S, int ksize) {
     if (!src || !dst || !tmp || !box || !bounds || !coef) return UDAPOSE_ERR_ARG;

@@ -1,4 +1,4 @@
-// Host launchers of the data pipeline: warps, occlusion and patches (affine.hip), the merge of the teacher's views (view_merge.hip), image augmentation and label maps (augment.hip).
+// Host launchers of the data pipeline: warps, occlusion and patches (affine.hip), the merge of the teacher's views (view_merge.hip), image augmentation and label maps (augment.hip), the strong view's colour ops and erase (strong_aug.hip).
 #pragma once
 #include "common.h"
 
@@ -27,3 +27,7 @@ int aug_gaussian_labels_subpixel(hipStream_t s, const double* kp, const float* v
                                  double stride_x, double stride_y, double sigma, int rad);
 int aug_draw_labelmap_ori(hipStream_t s, const float* pt, const float* vis, const unsigned char* gate, float* target, float* weight, int R, int Hh,
                           int Wh, float r3, const float* patch, int psize);
+// strong_aug.hip
+int aug_point_op(hipStream_t s, unsigned char* img, const int* op, const int* param, const double* inv_scale, unsigned char* lut, int N, int HW);
+int aug_sharpness_u8(hipStream_t s, unsigned char* img, unsigned char* tmp, const int* op, const float* factor, int N, int H, int W);
+int aug_erase_f32(hipStream_t s, float* x, const int* box, float v0, float v1, float v2, int N, int H, int W);

@@ -16,6 +16,12 @@ does, including the `aug_param` tuple that the loop consumes (inverse augmentati
 
 GaussianBlur (`--blur_stu / --blur_tea`, radius U(0, high) per sample; 0 by default = a copy) is PIL's three-pass box blur in
 8.24 fixed point, reproduced bit for bit on the device (udapose_aug_gaussian_blur_u8).
+
+The strong student view of weak-teacher / strong-student consistency training (FixMatch / RandAugment; the reference's student view stops at
+ColorJitter + blur): `ViewConfig(strong_ops=k, strong_magnitude=m)` appends k ops drawn from STRONG_OPS - the three ImageEnhance steps above,
+ImageOps.autocontrast / equalize / posterize / solarize and ImageEnhance.Sharpness, byte for byte PIL's results (csrc/strong_aug.hip) -
+between the colour jitter and the blur, and `ViewConfig(erase=p)` the reference's RandomErasing (lib/transforms/__init__.py:134-179) on the
+normalised tensor.  Both are off by default: nothing more is drawn or launched then.
 """
 import math
 import random
@@ -27,6 +33,12 @@ from . import _hip
 from ._hip import check, lib, ptr
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+# op codes of the strong view, one per image and step: 0 none; 1 brightness, 2 contrast, 3 colour (udapose_aug_color_op's codes);
+# 4 autocontrast, 5 equalize, 6 posterize, 7 solarize (udapose_aug_point_op); 8 sharpness (udapose_aug_sharpness_u8)
+STRONG_OPS = (0, 1, 2, 3, 4, 5, 6, 7, 8)
+STRONG_BINS = 31          # RandAugment's magnitude scale: integers 0 .. 30
+# ImageOps.autocontrast's `scale = 255.0 / (hi - lo)` for hi - lo = 1 .. 255, divided by Python as PIL divides it: the device looks it up
+AUTOCONTRAST_SCALES = tuple(255.0 / d for d in range(1, 256))
 
 
 def inverse_affine_matrix_pil(center, angle, translate, scale, shear):
@@ -145,17 +157,63 @@ def transform_keypoints(kp, angle, shear_x, shear_y, trans_x, trans_y, scale, wi
     return kp
 
 
+def strong_op_arrays(ops, params, N):
+    """The host side of `TargetViewPipeline.strong_`: per-sample op / parameter lists, checked, -> four [L][N] arrays, one row per list
+    position: the codes, the codes as udapose_aug_color_op reads them (everything but 1..3 is "none" there), the float parameters (factors
+    of 1 / 2 / 3 / 8) and the integer ones (posterize's bits, solarize's cut = ceil(threshold) clipped to [0, 256]: for an integer i,
+    PIL's `i < threshold` is `i < ceil(threshold)`).  ValueError: list lengths that do not match N or each other, a code outside
+    STRONG_OPS, bits outside 1..8, a factor or threshold that is not finite."""
+    if len(ops) != N or len(params) != N:
+        raise ValueError(f"strong_: {len(ops)} op lists and {len(params)} parameter lists for a batch of {N}")
+    L = len(ops[0]) if N else 0
+    color = np.zeros((L, N), np.int32)
+    code = np.zeros((L, N), np.int32)
+    fpar = np.zeros((L, N), np.float32)
+    ipar = np.zeros((L, N), np.int32)
+    for n in range(N):
+        if len(ops[n]) != L or len(params[n]) != L:
+            raise ValueError(f"strong_: sample {n} has {len(ops[n])} ops and {len(params[n])} parameters, sample 0 has {L} ops")
+        for j, (o, p) in enumerate(zip(ops[n], params[n])):
+            if o not in STRONG_OPS:
+                raise ValueError(f"strong_: op code {o!r} is not one of {STRONG_OPS}")
+            code[j, n] = o
+            if o in (1, 2, 3, 8):
+                if not math.isfinite(p):
+                    raise ValueError(f"strong_: factor {p!r} of op {o} is not finite")
+                fpar[j, n] = p
+                if o != 8:
+                    color[j, n] = o
+            elif o == 6:
+                if not (math.isfinite(p) and p == int(p) and 1 <= p <= 8):
+                    raise ValueError(f"strong_: posterize keeps 1..8 bits, got {p!r}")
+                ipar[j, n] = int(p)
+            elif o == 7:
+                if not math.isfinite(p):
+                    raise ValueError(f"strong_: solarize threshold {p!r} is not finite")
+                ipar[j, n] = min(256, max(0, math.ceil(p)))
+    return code, color, fpar, ipar
+
+
 class ViewConfig:
     """Ranges of one view's augmentation = the reference's `--rotation_* --shear_* --translate_* --scale_* --color_*` flags
     (train_human.py:535-557)."""
 
-    def __init__(self, rotation=180, shear=(-30, 30), translate=(0.05, 0.05), scale=(0.6, 1.3), color=0.25, blur=0.0):
+    def __init__(self, rotation=180, shear=(-30, 30), translate=(0.05, 0.05), scale=(0.6, 1.3), color=0.25, blur=0.0, strong_ops=0,
+                 strong_magnitude=9, erase=0.0, erase_value=(0.4914, 0.4822, 0.4465)):
         self.degrees = (-rotation, rotation) if isinstance(rotation, (int, float)) else tuple(rotation)
         self.shear = (-shear, shear) if isinstance(shear, (int, float)) else tuple(shear)
         self.translate = (translate, translate) if isinstance(translate, (int, float)) else tuple(translate)
         self.scale = (scale, scale) if isinstance(scale, (int, float)) else tuple(scale)
         self.color = float(color)
         self.blur = float(blur)          # T.GaussianBlur(high=blur): radius ~ U(0, blur) per sample (`--blur_stu / --blur_tea`)
+        # the strong view (no flag of the reference): strong_ops ops per sample from STRONG_OPS at RandAugment magnitude strong_magnitude of
+        # STRONG_BINS bins; erase = RandomErasing's probability, erase_value its fill (the class's default `mean`, written as is)
+        self.strong_ops, self.strong_magnitude = int(strong_ops), int(strong_magnitude)
+        self.erase, self.erase_value = float(erase), tuple(float(v) for v in erase_value)
+        if self.strong_ops < 0 or not 0 <= self.strong_magnitude < STRONG_BINS:
+            raise ValueError(f"strong_ops must be >= 0 and strong_magnitude in 0..{STRONG_BINS - 1}")
+        if not 0.0 <= self.erase <= 1.0 or len(self.erase_value) != 3:
+            raise ValueError("erase is a probability and erase_value has one value per channel")
 
     def draw_blur(self, rng):
         """GaussianBlur.__call__ (keypoint_detection.py:221-223): one uniform radius per sample (the reference draws from np.random)."""
@@ -183,6 +241,48 @@ class ViewConfig:
         c = self.color
         return ops, [rng.uniform(max(0.0, 1 - c), 1 + c) for _ in ops]
 
+    def draw_strong(self, rng):
+        """RandAugment: strong_ops ops, each uniform over STRONG_OPS, all at magnitude m = strong_magnitude of the published table
+        (Cubuk et al. 2020, 31 bins).  Draw order, per op: one `rng.randrange(9)` for the code; then, for codes 1 / 2 / 3 / 8 only, one
+        `rng.random()` whose value below 0.5 turns the factor 1 + 0.9 m / 30 into 1 - 0.9 m / 30.  Posterize keeps
+        bits = 8 - round(m / 7.5), solarize the threshold 255 - 255 m / 30; codes 0, 4, 5 have no parameter (0.0 stands in) and, like 6 and 7,
+        draw nothing further.  -> ([codes], [parameters])"""
+        m = self.strong_magnitude
+        codes, params = [], []
+        for _ in range(self.strong_ops):
+            code = STRONG_OPS[rng.randrange(len(STRONG_OPS))]
+            if code in (1, 2, 3, 8):
+                d = 0.9 * m / (STRONG_BINS - 1)
+                p = 1.0 - d if rng.random() < 0.5 else 1.0 + d
+            elif code == 6:
+                p = 8 - int(round(m / 7.5))
+            elif code == 7:
+                p = 255.0 - 255.0 * m / (STRONG_BINS - 1)
+            else:
+                p = 0.0
+            codes.append(code)
+            params.append(p)
+        return codes, params
+
+    def draw_erase(self, rng, H, W, sl=0.02, sh=0.4, r1=0.3):
+        """RandomErasing.__call__ (lib/transforms/__init__.py:156-177), same draws in the same order from `rng` (the reference uses the global
+        `random` module): one uniform against the probability `erase`; then up to 100 attempts of an area U(sl, sh) x H W and an aspect
+        ratio U(r1, 1 / r1), the first box that is smaller than the image on both sides is placed by two `randint`s (row, then column: the
+        reference's x1 is the row).  -> (top, left, h, w); (0, 0, 0, 0) when nothing is erased."""
+        if rng.uniform(0, 1) >= self.erase:
+            return 0, 0, 0, 0
+        for _ in range(100):
+            area = H * W
+            target_area = rng.uniform(sl, sh) * area
+            aspect_ratio = rng.uniform(r1, 1 / r1)
+            h = int(round(math.sqrt(target_area * aspect_ratio)))
+            w = int(round(math.sqrt(target_area / aspect_ratio)))
+            if w < W and h < H:
+                top = rng.randint(0, H - h)
+                left = rng.randint(0, W - w)
+                return top, left, h, w
+        return 0, 0, 0, 0
+
 
 class TargetViewPipeline:
     """Batched device pipeline for the `_mt` datasets' student / teacher views."""
@@ -202,6 +302,7 @@ class TargetViewPipeline:
         self.resize_scale = tuple(resize_scale)          # `--resize-scale` (train_human.py:523)
         self._dev = {}
         self._coef_cache = {}
+        self._inv_scale = {}          # per device: autocontrast's 255.0 / d, d = 1 .. 255, divided here (strong_)
 
     # ------------------------------------------------------------------ device constants
     def _consts(self, device):
@@ -297,6 +398,60 @@ class TargetViewPipeline:
         check(lib().udapose_aug_gaussian_blur_u8(_hip.stream(), ptr(img_u8), ptr(tmp), ptr(pdev), N, H, W), "aug_gaussian_blur_u8")
         return img_u8
 
+    def strong_(self, img_u8, ops, params):
+        """The strong view's ops in place: ops / params = per-sample lists of equally many codes of STRONG_OPS / their parameters (applied
+        in list order): the factor for 1 brightness, 2 contrast, 3 colour and 8 sharpness, `bits` (1..8) for 6 posterize, the threshold for
+        7 solarize (PIL compares `i < threshold`; the device gets the integer cut ceil(threshold) clipped to [0, 256]); ignored for 0, 4
+        autocontrast and 5 equalize.  Per list position only the launches whose codes occur in the batch are issued; nothing is read back."""
+        _hip.require_cuda(img_u8)
+        N, H, W, C3 = img_u8.shape
+        assert C3 == 3 and img_u8.dtype == torch.uint8 and img_u8.is_contiguous()
+        code, color, fpar, ipar = strong_op_arrays(ops, params, N)
+        L = code.shape[0]
+        if L == 0 or not code.any():
+            return img_u8
+        dev = img_u8.device
+        up = lambda a: torch.from_numpy(a).to(dev, non_blocking=True)
+        code_d, fpar_d = up(code), up(fpar)
+        has = lambda j, lo, hi: bool(((code[j] >= lo) & (code[j] <= hi)).any())
+        if color.any():
+            color_d, mean_scratch = up(color), torch.empty(N, dtype=torch.int32, device=dev)
+        if any(has(j, 4, 7) for j in range(L)):
+            ipar_d, lut = up(ipar), torch.empty(N, 768, dtype=torch.uint8, device=dev)
+            inv = self._inv_scale.get(dev)
+            if inv is None:
+                inv = self._inv_scale[dev] = torch.tensor(AUTOCONTRAST_SCALES, dtype=torch.float64).to(dev)
+        tmp = torch.empty_like(img_u8) if any(has(j, 8, 8) for j in range(L)) else None
+        for j in range(L):
+            if has(j, 1, 3):
+                check(lib().udapose_aug_color_op(_hip.stream(), ptr(img_u8), ptr(color_d[j]), ptr(fpar_d[j]), ptr(mean_scratch), N, H * W),
+                      "aug_color_op")
+            if has(j, 4, 7):
+                check(lib().udapose_aug_point_op(_hip.stream(), ptr(img_u8), ptr(code_d[j]), ptr(ipar_d[j]), ptr(inv), ptr(lut), N, H * W),
+                      "aug_point_op")
+            if has(j, 8, 8):
+                check(lib().udapose_aug_sharpness_u8(_hip.stream(), ptr(img_u8), ptr(tmp), ptr(code_d[j]), ptr(fpar_d[j]), N, H, W),
+                      "aug_sharpness_u8")
+        return img_u8
+
+    def erase_(self, x, boxes, value):
+        """RandomErasing's write in place on the normalised tensor x [N,3,H,W] fp32 (the reference applies it after ToTensor and writes
+        `mean` as it is): boxes = one (top, left, h, w) per sample, an empty box (h or w 0) leaves its sample alone; value = the three fills."""
+        _hip.require_cuda(x)
+        N, C3, H, W = x.shape
+        assert C3 == 3 and x.dtype == torch.float32 and x.is_contiguous()
+        if len(boxes) != N or len(value) != 3:
+            raise ValueError(f"erase_: {len(boxes)} boxes for a batch of {N}, {len(value)} fill values for 3 channels")
+        for (top, left, h, w) in boxes:
+            if h < 0 or w < 0 or (h > 0 and w > 0 and not (0 <= top and 0 <= left and top + h <= H and left + w <= W)):
+                raise ValueError(f"erase box {(top, left, h, w)} outside a {H}x{W} image")
+        if not any(h > 0 and w > 0 for (_, _, h, w) in boxes):
+            return x
+        box_d = torch.tensor(boxes, dtype=torch.int32).to(x.device, non_blocking=True)
+        check(lib().udapose_aug_erase_f32(_hip.stream(), ptr(x), ptr(box_d), float(value[0]), float(value[1]), float(value[2]), N, H, W),
+              "aug_erase_f32")
+        return x
+
     def to_tensor(self, img_u8):
         N, H, W, _ = img_u8.shape
         c = self._consts(img_u8.device)
@@ -354,20 +509,32 @@ class TargetViewPipeline:
         return target, weight
 
     # ------------------------------------------------------------------ one view of the whole batch
-    def view(self, base_u8, keypoints, cfg, params=None, jitter=None, blur=None):
-        """-> (image [N,3,H,W] fp32 normalised, key points [N,K,2], aug_param collated, target, weight)"""
+    def view(self, base_u8, keypoints, cfg, params=None, jitter=None, blur=None, strong=None, erase=None):
+        """-> (image [N,3,H,W] fp32 normalised, key points [N,K,2], aug_param collated, target, weight)
+        strong = per-sample (codes, parameters) as `draw_strong` returns them, erase = per-sample boxes as `draw_erase` does; both are drawn
+        when None and the configuration has them on - after every other draw of the view (affine for every sample, jitter for every
+        sample, blur), strong for every sample first, then erase: a seeded pipeline draws the same affine / jitter / blur values with the
+        strong view on as with it off.  Neither touches key points, aug_param, labels or weights (an erased key point stays labelled)."""
         N, H, W, _ = base_u8.shape
         if params is None:
             params = [cfg.draw_affine(self.rng, (W, H)) for _ in range(N)]
         if jitter is None:
             jitter = [cfg.draw_jitter(self.rng) for _ in range(N)]
-        img = self.warp_images(base_u8, params)
-        self.jitter_(img, [j[0] for j in jitter], [j[1] for j in jitter])
         if blur is None and cfg.blur > 0:
             blur = [cfg.draw_blur(self.np_rng) for _ in range(N)]
+        if strong is None and cfg.strong_ops > 0:
+            strong = [cfg.draw_strong(self.rng) for _ in range(N)]
+        if erase is None and cfg.erase > 0:
+            erase = [cfg.draw_erase(self.rng, H, W) for _ in range(N)]
+        img = self.warp_images(base_u8, params)
+        self.jitter_(img, [j[0] for j in jitter], [j[1] for j in jitter])
+        if strong is not None:
+            self.strong_(img, [s[0] for s in strong], [s[1] for s in strong])
         if blur is not None:
             self.blur_(img, blur)                     # (after the colour jitter, before ToTensor: train_human.py:67-71)
         x = self.to_tensor(img)
+        if erase is not None:
+            self.erase_(x, erase, cfg.erase_value)    # (RandomErasing works on the tensor: lib/transforms/__init__.py:154-177)
         kp = np.stack([transform_keypoints(keypoints[i], *params[i], W, H) for i in range(N)])
         # aug_param = the INVERSE augmentation (keypoint_detection.py:139), collated like default_collate does
         aug = [torch.tensor([-p[0] for p in params], dtype=torch.float64),
