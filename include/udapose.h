@@ -760,6 +760,41 @@ int udapose_fda_spectrum(void* stream, const float* x, int planes, int H, int W,
 int udapose_fda_apply(void* stream, const float* content, const float* spec_c, const float* spec_s, float* out, int planes, int C, int H, int W, int b,
                       float alpha, const float* alpha_dev, const float* lo, const float* hi, const float* mean, const float* std);
 
+/* ---------------------------------------------------------------- Histogram matching and colour-statistics style transfer
+ * Two more style bridges without weights (with FDA, the classical pixel-level three).  fp32 NCHW throughout, identical in both builds.
+ * LEVEL of a pixel of channel c: l = (int) min(max(rint(fmaf(x, std[c], mean[c]) * 255), 0), 255), in fp32 as written (mean, std [C], both or
+ * neither; without them std = 1, mean = 0: raw images in [0, 1]).  The clamp comes before the cast: out-of-range, infinite and NaN pixels
+ * land on a bound.  For images that came from bytes through that normalisation the level is the byte; for other floats it is a quantisation.
+ * SUMMARY: udapose_pixel_summary_bytes(N, C) bytes (< 0: refused), 8-byte aligned, int32 words; sample n owns the row of
+ * R = C * 256 + (C == 3 ? 8 : 0) words at n * R:
+ *   word c * 256 + k             uint32, the number of pixels of channel c at level k
+ *   words 768 .. 773 (C == 3)    three uint64, low word first: sum l_0 l_1, sum l_0 l_2, sum l_1 l_2 over the pixels; words 774, 775 are zero
+ * Exact integers (a kernel clears the buffer, integer atomics add): two runs agree to the bit, a sample's row does not depend on the batch.
+ * TRANSFER: out = x + alpha (T - l) / (255 std[c]), then the optional clamp max(min(out, hi[c]), lo[c]) (lo, hi [C]: both or neither); T is
+ * the target level from the content's and the style's summary (same N, C, H, W; sample n pairs with sample n).  alpha_dev (one float on the
+ * device) overrides alpha when non-null.  alpha == 0 returns the (clamped) content bit for bit.  Per plane or sample everything is derived
+ * in fp64 from the integers and rounded once to fp32; the per-pixel work is fp32.
+ *   UDAPOSE_PIXEL_HIST      per channel, scikit-image's match_histograms on integer cumulative counts Cc, Cs: q = Cc[l]; v_0 < v_1 < .. the
+ *                           occupied style levels; T = v_0 for q < Cs[v_0], v_last for q >= Cs[v_last], else with j the last index such that
+ *                           Cs[v_j] <= q:  T = v_j + (q - Cs[v_j]) / (Cs[v_j+1] - Cs[v_j]) (v_j+1 - v_j).  sum_s bit-equal to sum_c: out == content.
+ *   UDAPOSE_PIXEL_MEANSTD   per channel, AdaIN on pixels: T / 255 = (l / 255 - mu_c) sqrt(var_s + eps) / sqrt(var_c + eps) + mu_s, unbiased
+ *                           variances of l / 255.  H W >= 2.
+ *   UDAPOSE_PIXEL_CHOLESKY  C == 3: T / 255 = L_s L_c^-1 (l / 255 - mu_c) + mu_s, L = chol(Sigma + eps I), Sigma the unbiased 3 x 3
+ *                           covariance of l / 255 (closed-form Cholesky and triangular inverse).  H W >= 2.
+ * Refused before any launch, nothing written: UDAPOSE_ERR_ARG for a null or misaligned pointer, N, C, H or W <= 0, an unknown mode, CHOLESKY
+ * with C != 3, H W < 2 or eps <= 0 in the two variance modes, one of lo / hi or of mean / std alone; UDAPOSE_ERR_UNSUPPORTED for
+ * H W > UDAPOSE_PIXEL_MAX_HW (the counts are uint32 and the exact variance numerator n sum l^2 - (sum l)^2 stays below 2^64).
+ * A work-group of either kernel covers UDAPOSE_PIXEL_SHARE pixels of a plane. */
+#define UDAPOSE_PIXEL_HIST 0
+#define UDAPOSE_PIXEL_MEANSTD 1
+#define UDAPOSE_PIXEL_CHOLESKY 2
+#define UDAPOSE_PIXEL_MAX_HW 16777216
+#define UDAPOSE_PIXEL_SHARE 4096
+long long udapose_pixel_summary_bytes(int N, int C);
+int udapose_pixel_summary(void* stream, const float* x, int N, int C, int H, int W, const float* mean, const float* std, void* summary);
+int udapose_pixel_transfer(void* stream, const float* content, const void* sum_c, const void* sum_s, float* out, int N, int C, int H, int W, int mode,
+                           double eps, float alpha, const float* alpha_dev, const float* lo, const float* hi, const float* mean, const float* std);
+
 /* ---------------------------------------------------------------- AdaIN decoder training (reference adain/net.py:102-162, adain/train/)
  * The backward of the style network's step on NHWC tensors of the library's element type, fp32 accumulation.  Reflection-padded 3x3
  * stride-1 convolutions (desc: reflect = 1, pad = 1, K = 3, optional upsample; Ci and Co multiples of 64 - zero-pad the 3-channel end

@@ -32,6 +32,7 @@ ALIASES = {
     "lib.models.loss": _PKG + ".lib.models.loss",
     "lib.models.Style_net": _PKG + ".lib.models.Style_net",
     "lib.models.fda": _PKG + ".lib.models.fda",
+    "lib.models.pixel_style": _PKG + ".lib.models.pixel_style",
     "lib.keypoint_detection": _PKG + ".lib.keypoint_detection",
     "utils": _PKG + ".utils",
 }

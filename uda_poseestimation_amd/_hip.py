@@ -172,6 +172,9 @@ _SIGS = {
     "udapose_fda_ws_bytes": (ll, [ci, ci, ci, ci]),
     "udapose_fda_spectrum": (ci, [vp, vp, ci, ci, ci, ci, vp, vp]),
     "udapose_fda_apply": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp]),
+    "udapose_pixel_summary_bytes": (ll, [ci, ci]),
+    "udapose_pixel_summary": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp]),
+    "udapose_pixel_transfer": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cd, cf, vp, vp, vp, vp, vp]),
     "udapose_patch_paste": (ci, [vp, vp, vp, ci, ci, ci, ci, ci]),
     "udapose_occlusion_pick": (ci, [vp, vp, vp, vp, ci, ci, ci, cd, ci, cf, cf, ci, vp, vp]),
     "udapose_select_rows": (ci, [vp, vp, vp, vp, vp, ci, sz]),

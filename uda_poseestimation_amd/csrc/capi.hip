@@ -529,6 +529,14 @@ int udapose_fda_apply(void* stream, const float* content, const float* spec_c, c
                       float alpha, const float* alpha_dev, const float* lo, const float* hi, const float* mean, const float* std) {
     return fda_apply(S(stream), content, spec_c, spec_s, out, planes, C, H, W, b, alpha, alpha_dev, lo, hi, mean, std);
 }
+long long udapose_pixel_summary_bytes(int N, int C) { return pixel_summary_bytes(N, C); }
+int udapose_pixel_summary(void* stream, const float* x, int N, int C, int H, int W, const float* mean, const float* std, void* summary) {
+    return pixel_summary(S(stream), x, N, C, H, W, mean, std, summary);
+}
+int udapose_pixel_transfer(void* stream, const float* content, const void* sum_c, const void* sum_s, float* out, int N, int C, int H, int W, int mode,
+                           double eps, float alpha, const float* alpha_dev, const float* lo, const float* hi, const float* mean, const float* std) {
+    return pixel_transfer(S(stream), content, sum_c, sum_s, out, N, C, H, W, mode, eps, alpha, alpha_dev, lo, hi, mean, std);
+}
 int udapose_adain_f32(void* stream, const float* c, const float* s, float* out, int N, int HWc, int HWs, int C, float eps, float alpha,
                       float* stats_out) {
     return adain_launch_f32(S(stream), c, s, out, N, HWc, HWs, C, eps, alpha, nullptr, stats_out);

@@ -8,6 +8,7 @@
 // An image whose code belongs to another kernel is left alone.  RandomErasing (lib/transforms/__init__.py:134-179) fills a box of the
 // normalised fp32 NCHW tensor.
 #include "data.h"
+#include "lds_hist.h"   // hist_add
 #include "blend.h"      // blend1; and NO FMA contraction in this file: the stencil and the blend round every product and every sum separately
 
 namespace {
@@ -16,18 +17,6 @@ constexpr int TAB_TPB = 1024;      // point_table_k: one work-group per image
 constexpr int LUT = 768;           // 3 channels x 256 entries, bytes
 
 __device__ __forceinline__ bool is_point_op(int o) { return o >= 4 && o <= 7; }
-
-// ++h[v] for every active lane.  A wave whose lanes all bring one value - the black border a warp leaves, a flat background - adds its
-// lane count once: 64 atomics on one LDS address would be served one after the other.
-__device__ __forceinline__ void hist_add(unsigned int* h, unsigned int v) {
-    const unsigned int first = __builtin_amdgcn_readfirstlane(v);
-    if (__all(v == first)) {
-        const unsigned long long m = __ballot(1);
-        if ((int)__lane_id() == __ffsll((long long)m) - 1) atomicAdd(&h[first], (unsigned int)__popcll(m));
-    } else {
-        atomicAdd(&h[v], 1u);
-    }
-}
 
 // lut[n][c][i] of every image whose op is 4..7.  Ops 4 and 5 first count the image's three 256-bin histograms in LDS (integer atomics:
 // exact, whatever the order); the table is then one entry per thread.

@@ -1,4 +1,5 @@
-// Host launchers of the style bridges: AdaIN, the decoder's training step, and Fourier-domain transfer (FDA).
+// Host launchers of the style bridges: AdaIN, the decoder's training step, Fourier-domain transfer (FDA), and the histogram / colour-statistics
+// transfers.
 #pragma once
 #include "conv_plan.h"
 
@@ -29,3 +30,8 @@ long long fda_ws_bytes(int planes, int H, int W, int b);
 int fda_spectrum(hipStream_t s, const float* x, int planes, int H, int W, int b, void* ws, float* spec);
 int fda_apply(hipStream_t s, const float* content, const float* spec_c, const float* spec_s, float* out, int planes, int C, int H, int W, int b, float alpha,
               const float* alpha_dev, const float* lo, const float* hi, const float* mean, const float* stdv);
+// pixel_style.hip
+long long pixel_summary_bytes(int N, int C);
+int pixel_summary(hipStream_t s, const float* x, int N, int C, int H, int W, const float* mean, const float* stdv, void* summary);
+int pixel_transfer(hipStream_t s, const float* content, const void* sum_c, const void* sum_s, float* out, int N, int C, int H, int W, int mode, double eps,
+                   float alpha, const float* alpha_dev, const float* lo, const float* hi, const float* mean, const float* stdv);

@@ -131,14 +131,14 @@ def fda_transfer(content, style, beta=0.01, alpha=1.0, clamp=None, mean=None, st
     return FDANet(beta, mean, std)(content, style, alpha, clamp)[2]
 
 
-class FDANet(nn.Module):
-    """`Style_net.Net`'s call form without weights: forward(content, style, alpha, clamp) -> (None, None, g_t).  No parameters, no buffers."""
+class NormalisedStyleNet(nn.Module):
+    """What the style nets without weights share: the optional per-channel mean / std of normalised images, kept as host values and uploaded once
+    per device.  No parameters, no buffers."""
 
-    def __init__(self, beta=0.01, mean=None, std=None):
+    def __init__(self, mean=None, std=None):
         super().__init__()
         if (mean is None) != (std is None):
             raise ValueError("mean and std go together")
-        self.beta = float(beta)
         self.mean = None if mean is None else [float(v) for v in torch.as_tensor(mean).reshape(-1).tolist()]
         self.std = None if std is None else [float(v) for v in torch.as_tensor(std).reshape(-1).tolist()]
         if self.std is not None and not all(s > 0 and math.isfinite(s) for s in self.std):
@@ -154,6 +154,14 @@ class FDANet(nn.Module):
         if hit is None:
             hit = self._norm[dev] = (torch.tensor(self.mean, dtype=torch.float32, device=dev), torch.tensor(self.std, dtype=torch.float32, device=dev))
         return hit
+
+
+class FDANet(NormalisedStyleNet):
+    """`Style_net.Net`'s call form without weights: forward(content, style, alpha, clamp) -> (None, None, g_t).  No parameters, no buffers."""
+
+    def __init__(self, beta=0.01, mean=None, std=None):
+        super().__init__(mean, std)
+        self.beta = float(beta)
 
     def window_of(self, img):
         return window(img.shape[-2], img.shape[-1], self.beta)
