@@ -1,7 +1,9 @@
 """The fp64 convolution reference and its checker (tests/helpers/fp64_conv.py) on the CPU: the reference agrees with torch's own
 float64 convolutions in every geometry the library runs, a correct fp32-accumulated result passes check() at the bars the GPU tests use
 (helpers.fp64_conv.BOUNDS), and each planted fault of the kind a wrong kernel form makes fails it - at small shapes and at bench-like
-reduction lengths (K = 2304 for a forward, M = 131072 pixels for a weight gradient)."""
+reduction lengths (K = 2304 for a forward, M = 131072 pixels for a weight gradient); the faults of the patch-staged kernels (a wrong
+padding index, a shifted pixel block, a swapped 16-byte chunk, a dropped l part, another image's tile) at the bars of
+tests/test_gpu_patchconv_forms.py."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -200,3 +202,96 @@ def test_weight_gradient_stage_faults_fail_the_check(shape):
         # the whole-tensor condition alone catches it as well
         with pytest.raises(AssertionError, match="rho"):
             fc.check(f, ref, absref, torch.float32, 1.0, RHO_W, name + " (element bar disabled)")
+
+
+# ---- planted faults of the patch-staged kernels (csrc/patchconv.hip; the GPU module is tests/test_gpu_patchconv_forms.py) ----------------
+
+TAU_S, RHO_S = fc.BOUNDS[("split", "fprop")]
+PATCH_GEOMS = [
+    # N, Hi, Wi, Ci, Co, upsample: reflection-padded 3x3, two tile rows and two 32-wide (one 64-wide) tile columns per image
+    pytest.param((2, 8, 64, 64, 64, False), id="reflect"),
+    pytest.param((2, 4, 32, 64, 64, True), id="upsample_reflect"),
+]
+
+
+def _split_parts(v):
+    """(h, l) of the f16x2 storage h + l * 2^-11 of fp32 values, as float64."""
+    h = v.half().double()
+    return h, ((v.double() - h) * 2048.0).half().double()
+
+
+def _round_out(ref, kind):
+    """The float64 reference as the kernel would store it: one rounding to the output type (split: the (h, l) pair read back as fp32)."""
+    if kind == "split":
+        h, l = _split_parts(ref.float())
+        return (h + l / 2048.0).float()
+    return ref.to(kind)
+
+
+def _padded_conv(g, x, w, left):
+    """The reflect (+ upsample) convolution in float64 with the LEFT padding column replaced: left(xu) -> [N, C, H] column of the upsampled
+    input that output column 0 reads at tap kw = 0."""
+    xu = _nchw(x).double()
+    if g.upsample:
+        xu = F.interpolate(xu, scale_factor=2, mode="nearest")
+    xp = F.pad(xu, (1, 1, 0, 0), mode="reflect")
+    xp[..., 0] = left(xu)
+    return _nhwc(F.conv2d(F.pad(xp, (0, 0, 1, 1), mode="reflect"), w.double()))
+
+
+def _patch_faults(y, y_border, y_h):
+    """{name: corrupted stored result}.  y: the clean stored result [N, Ho, Wo, Co]; y_border: computed with the wrong left padding index;
+    y_h: computed from the h parts alone (split form) or None.  A tile is 4 x 32 output pixels."""
+    out = {}
+    f = y.clone()
+    f[:, :, 0] = y_border[:, :, 0]                                   # column 0 of every row from the wrong padding index
+    out["border_column_clamped"] = f
+    f = y.clone()
+    f[1, 5, 32:48] = y[1, 5, 33:49]                                  # one 16-pixel block of tile (row 1, column 1) one column off
+    out["pixel_block_shifted"] = f
+    f = y.clone()
+    f[0, 2, 37, 8:16], f[0, 2, 37, 16:24] = y[0, 2, 37, 16:24], y[0, 2, 37, 8:16]      # one 16-byte chunk swapped with its neighbour
+    out["channel_chunk_swapped"] = f
+    f = y.clone()
+    f[1, 4:8, 0:32] = y[0, 4:8, 0:32]                # a tile of image 1 computed from image 0's patch
+    out["previous_images_tile"] = f
+    if y_h is not None:
+        f = y.clone()
+        f[0, 0:4, 32:64] = y_h[0, 0:4, 32:64]                        # acc2 * 2^-11 never added in one tile
+        out["l_part_dropped"] = f
+    return out
+
+
+@pytest.mark.parametrize("kind", [torch.float32, torch.bfloat16, torch.float16, "split"], ids=["f32", "bf16", "fp16", "split"])
+@pytest.mark.parametrize("geom", PATCH_GEOMS)
+def test_patch_kernel_faults_fail_the_check(geom, kind):
+    """The float64 reference of a small reflect (+ upsample) convolution, rounded to the output type, passes check() at the bars
+    tests/test_gpu_patchconv_forms.py uses; corrupted the way a patch-staged kernel can go wrong, it does not.  With the folded upsample
+    the clamped padding index and the reflected one name the same input column (-1 -> 1 -> 0 and -1 -> 0 -> 0), so the border fault
+    there is the reflection applied at the input's resolution (-1 >> 1 = -1 -> input column 1)."""
+    N, Hi, Wi, Ci, Co, up = geom
+    g = fc.Geom(N, Hi, Wi, Ci, Co, 3, 3, 1, 1, False, True, up)
+    split = kind == "split"
+    gen = torch.Generator().manual_seed(21)
+    x = torch.randn(N, Ci, Hi, Wi, generator=gen)
+    w = torch.randn(Co, Ci, 3, 3, generator=gen) * (Ci * 9) ** -0.5
+    if not split:                                                    # 16-bit operands; the split form takes the fp32 operands as they are
+        x, w = x.bfloat16().float(), w.bfloat16().float()
+    tau, rho = (TAU_S, RHO_S) if split else (TAU_F, RHO_F)
+    out_dtype = torch.float32 if split else kind
+    ref, absref = fc.fprop(g, _nhwc(x), fc.phys_weight(w, g))
+    y = _round_out(ref, kind)
+    t, r = fc.check(y, ref, absref, out_dtype, tau, rho, "rounded reference")
+    print(f"{geom} {kind}: rounded reference, measured tau {t:.3g}, rho {r:.3g} (bars {tau:g}, {rho:g})")
+    border = _padded_conv(g, _nhwc(x), w, (lambda xu: xu[..., 2]) if up else (lambda xu: xu[..., 0]))
+    assert float((border[:, :, 1:] - ref[:, :, 1:]).abs().max()) < 1e-12 and float((border[:, :, 0] - ref[:, :, 0]).abs().max()) > 1e-3
+    y_h = None
+    if split:
+        y_h = fc.fprop(g, _split_parts(_nhwc(x))[0], fc.phys_weight(_split_parts(w)[0], g))[0]
+    faults = _patch_faults(y, _round_out(border, kind), None if y_h is None else _round_out(y_h, kind))
+    assert len(faults) == (5 if split else 4)
+    for name, f in faults.items():
+        assert not torch.equal(f, y), name
+        with pytest.raises(AssertionError, match="m-tile") as e:
+            fc.check(f, ref, absref, out_dtype, tau, rho, name)
+        print(f"  {name}: {str(e.value)[:160]}")
