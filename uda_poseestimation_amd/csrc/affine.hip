@@ -236,11 +236,7 @@ int affine_warp_chain(hipStream_t s, const float* src, float* dst, const float* 
         // atomic form
         const size_t lds = (size_t)H * W * 13 + 16;
         if (lds <= 150 * 1024 && (long long)N * C < (1ll << 31)) {
-            static std::atomic<unsigned long long> attr_done{0};
-            static std::mutex attr_mu;
-            once_per_device(attr_done, attr_mu, [] {
-                (void)hipFuncSetAttribute((const void*)warp_chain_bwd_det_k, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            });
+            max_dynamic_lds<warp_chain_bwd_det_k>(150 * 1024);
             hipLaunchKernelGGL(warp_chain_bwd_det_k, dim3(N * C), dim3(TPB), (unsigned)((lds + 15) & ~(size_t)15), s, src, dst, theta, C, H, W, nstage);
             return udapose_check_launch();
         }
@@ -399,12 +395,8 @@ int affine_warp_chain_bilinear(hipStream_t s, const float* src, float* dst, cons
     const int HW = H * W;
     const size_t lds = (size_t)HW * 2 * sizeof(float);
     if (lds <= 150 * 1024) {
-        static std::atomic<unsigned long long> attr_done{0};
-        static std::mutex attr_mu;
-        once_per_device(attr_done, attr_mu, [] {
-            (void)hipFuncSetAttribute((const void*)bilin_chain_lds_k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            (void)hipFuncSetAttribute((const void*)bilin_chain_lds_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        });
+        max_dynamic_lds<bilin_chain_lds_k<false>>(150 * 1024);
+        max_dynamic_lds<bilin_chain_lds_k<true>>(150 * 1024);
         const unsigned bytes = (unsigned)((lds + 15) & ~(size_t)15);
         if (backward) hipLaunchKernelGGL(bilin_chain_lds_k<true>, dim3(N * C), dim3(TPB), bytes, s, src, dst, theta, C, H, W, nstage);
         else hipLaunchKernelGGL(bilin_chain_lds_k<false>, dim3(N * C), dim3(TPB), bytes, s, src, dst, theta, C, H, W, nstage);

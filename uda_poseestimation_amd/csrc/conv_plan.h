@@ -20,16 +20,18 @@ struct Policy : udapose_policy {
 };
 inline const Policy& default_policy() { static const Policy p; return p; }
 
-// hipFuncSetAttribute (dynamic LDS size) is a per-DEVICE property of a kernel: run `f` once per (call site, device ordinal).
-template <typename F>
-inline void once_per_device(std::atomic<unsigned long long>& done, std::mutex& mu, F&& f) {
+// Allow `Kernel` `bytes` of dynamic LDS.  hipFuncSetAttribute is a per-DEVICE property of a kernel: set once per (kernel, device ordinal).
+template <auto Kernel>
+inline void max_dynamic_lds(int bytes) {
+    static std::atomic<unsigned long long> done{0};
+    static std::mutex mu;
     int dev = 0;
     (void)hipGetDevice(&dev);
     const unsigned long long bit = 1ull << (dev & 63);
     if (done.load(std::memory_order_acquire) & bit) return;
     std::lock_guard<std::mutex> lk(mu);
     if (done.load(std::memory_order_relaxed) & bit) return;
-    f();
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     done.fetch_or(bit, std::memory_order_release);
 }
 

@@ -241,18 +241,11 @@ long long fda_ws_bytes(int planes, int H, int W, int b) {
     return (long long)planes * ((H + FDA_ROWS - 1) / FDA_ROWS) * (2 * b + 1) * (b + 1) * (long long)sizeof(float2);
 }
 
-template <typename K>
-static void fda_allow_lds(K kernel, std::atomic<unsigned long long>& done, std::mutex& mu) {
-    once_per_device(done, mu, [kernel] { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); });
-}
-
 int fda_spectrum(hipStream_t s, const float* x, int planes, int H, int W, int b, void* ws, float* spec) {
     const int e = fda_check(planes, H, W, b);
     if (e != UDAPOSE_OK) return e;
     if (!x || !ws || !spec || ((uintptr_t)ws & 7) || ((uintptr_t)spec & 7)) return UDAPOSE_ERR_ARG;
-    static std::atomic<unsigned long long> done{0};
-    static std::mutex mu;
-    fda_allow_lds(fda_spectrum_part_k, done, mu);
+    max_dynamic_lds<fda_spectrum_part_k>(150 * 1024);
     const int nblk = (H + FDA_ROWS - 1) / FDA_ROWS, nc = (2 * b + 1) * (b + 1);
     const unsigned lds = (unsigned)((W + H + FDA_ROWS * (b + 1)) * sizeof(float2));
     hipLaunchKernelGGL(fda_spectrum_part_k, dim3(planes * nblk), dim3(FDA_TPB), lds, s, x, (float2*)ws, H, W, b, nblk);
@@ -268,9 +261,7 @@ int fda_apply(hipStream_t s, const float* content, const float* spec_c, const fl
     if (e != UDAPOSE_OK) return e;
     if (!content || !spec_c || !spec_s || !out || ((uintptr_t)spec_c & 7) || ((uintptr_t)spec_s & 7)) return UDAPOSE_ERR_ARG;
     if (C <= 0 || planes % C || !lo != !hi || !mean != !stdv) return UDAPOSE_ERR_ARG;
-    static std::atomic<unsigned long long> done{0};
-    static std::mutex mu;
-    fda_allow_lds(fda_apply_k, done, mu);
+    max_dynamic_lds<fda_apply_k>(150 * 1024);
     const int nblk = (H + FDA_ROWS - 1) / FDA_ROWS, nv = b + 1;
     const unsigned lds = (unsigned)((W + H + (2 * b + 1) * nv + FDA_ROWS * nv) * sizeof(float2));
     hipLaunchKernelGGL(fda_apply_k, dim3(planes * nblk), dim3(FDA_TPB), lds, s, content, (const float2*)spec_c, (const float2*)spec_s, out, C, H, W, b, nblk,

@@ -18,21 +18,13 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "conv_plan.h"
+#include "mma_tile.h"
 
 namespace {
 
 // 8 KiB of zeros: the source of every padded / out-of-range lane of the LDS-DMA loads (large enough that a padded lane
 // may add the per-stage channel offset, < Ci * sizeof(T) <= 8 KiB, and still read zeros)
 __device__ u32x4 g_zero16[512];
-
-template <int U> struct IC { static constexpr int value = U; };
-template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) { static_for<N - 1>(f); f(IC<N - 1>{}); }
-}
-
-// XOR swizzle of the 16-byte chunk index inside a 128-byte LDS row: makes the ds_read_b128 fragment reads (lane l ->
-// row l&15, chunk l>>4) conflict-free (2 rows per 256-byte bank row; derivation in DESIGN.md)
-__device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
 
 template <int BM, int BN, int WM, int WN, int NS>
 struct IgCfg {
@@ -51,21 +43,17 @@ struct IgCfg {
     static_assert(EPI_BYTES + WM * 2 * BN * 4 <= STAGE_BYTES, "the wave-row exchange of the BN statistics sits behind the epilogue regions");
 };
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N <= 24, "vmcnt range");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if constexpr (N == 18) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-    else if constexpr (N == 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else static_assert(N < 0, "add the vmcnt literal");
+// the wave-row exchange xch[WM][2][BN] is complete: add the WM wave rows and store ONE slab row `srow` of the two statistics
+template <int WM, int BN>
+__device__ __forceinline__ void store_slab_row(const float* xch, int tid, int n0, size_t srow, int Co, float* stats) {
+    __syncthreads();
+    if (tid < 2 * BN) {
+        const int st = tid / BN, cl = tid % BN, col = n0 + cl;
+        float t = 0.f;
+#pragma unroll
+        for (int w = 0; w < WM; ++w) t += xch[(w * 2 + st) * BN + cl];
+        if (col < Co) stats[(srow * 2 + st) * Co + col] = t;
+    }
 }
 
 // Main loop: NS-deep LDS ring filled by LDS-DMA (global_load_lds_dwordx4: no staging registers), counted vmcnt waits and
@@ -133,14 +121,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
         const int m = m0 + r;
         a_ok[i] = m < p.M;
         a_lc[i] = pchunk ^ swz(r);                     // logical chunk this lane fetches (swizzle on the SOURCE side)
-        const uint32_t mm = a_ok[i] ? (uint32_t)m : 0u;
-        const uint32_t n = fdiv(mm, p.div_hw);
-        const uint32_t rem = mm - n * (uint32_t)(p.Hg * p.Wg);
-        const uint32_t ii = fdiv(rem, p.div_w);
-        const uint32_t jj = rem - ii * (uint32_t)p.Wg;
-        a_hi0[i] = (int)ii * p.s;
-        a_wi0[i] = (int)jj * p.s;
-        a_nb[i] = (int)n * p.Hi * p.Wi;
+        const RowNIJ rn = row_nij(a_ok[i] ? (uint32_t)m : 0u, p.div_hw, p.div_w, p.Hg, p.Wg);
+        a_hi0[i] = (int)rn.i * p.s;
+        a_wi0[i] = (int)rn.j * p.s;
+        a_nb[i] = (int)rn.n * p.Hi * p.Wi;
     }
     bool b_ok[B_PW];
     int b_lc[B_PW];
@@ -220,7 +204,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
     };
 
     // issue the LDS-DMA loads of the next K stage into ring buffer UB (compile-time: LDS addresses fold to constants)
-    auto issue_stage = [&](auto ub) __attribute__((always_inline)) {
+    auto issue_stage = [&](int, auto ub) __attribute__((always_inline)) {       // (the K cursor below knows the stage)
         constexpr int UB = decltype(ub)::value;
         char* A = stage + UB * C::STAGE1;
         char* B = A + BM * 128;
@@ -228,14 +212,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
             // (scalar base = the kernel argument itself, 32-bit lane offsets advanced by one add each: the saddr form of the load)
 #pragma unroll
             for (int i = 0; i < A_PW; ++i) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)px + a_off3[i]),
-                                                 (__attribute__((address_space(3))) void*)(A + (i * 4 + wid) * 1024), 16, 0, 0);
+                lds_dma16((const char*)px + a_off3[i], A + (i * 4 + wid) * 1024);
                 a_off3[i] += 128u;
             }
 #pragma unroll
             for (int i = 0; i < B_PW; ++i) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const char*)pw + b_off3[i]),
-                                                 (__attribute__((address_space(3))) void*)(B + (i * 4 + wid) * 1024), 16, 0, 0);
+                lds_dma16((const char*)pw + b_off3[i], B + (i * 4 + wid) * 1024);
                 b_off3[i] += 128u;
             }
             return;
@@ -245,12 +227,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
             const long long cb = (long long)c0_cur * (long long)sizeof(T);
 #pragma unroll
             for (int i = 0; i < A_PW; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_cur[i] + cb),
-                                                 (__attribute__((address_space(3))) void*)(A + (i * 4 + wid) * 1024), 16, 0, 0);
+                lds_dma16(a_cur[i] + cb, A + (i * 4 + wid) * 1024);
 #pragma unroll
             for (int i = 0; i < B_PW; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_cur[i] + cb),
-                                                 (__attribute__((address_space(3))) void*)(B + (i * 4 + wid) * 1024), 16, 0, 0);
+                lds_dma16(b_cur[i] + cb, B + (i * 4 + wid) * 1024);
             c0_cur += BKE;
             if (c0_cur >= p.Ci) { c0_cur = 0; ++tap_cur; }
             return;
@@ -261,22 +241,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
             const int coff = smallc ? (a_lc[i] * EPC) & 7 : c0_cur + a_lc[i] * EPC;
             int hi = a_hi0[i] + t.dy, wi = a_wi0[i] + t.dx;
             if (reflect) {
-                hi = hi < 0 ? -hi : (hi >= Hl ? 2 * Hl - 2 - hi : hi);
-                wi = wi < 0 ? -wi : (wi >= Wl ? 2 * Wl - 2 - wi : wi);
+                hi = reflect1(hi, Hl);
+                wi = reflect1(wi, Wl);
             }
             const bool ok = a_ok[i] && (unsigned)hi < (unsigned)Hl && (unsigned)wi < (unsigned)Wl;
             hi >>= up; wi >>= up;
             const char* src = ok ? (const char*)(px + ((size_t)(a_nb[i] + hi * p.Wi + wi) * p.Ci + coff)) : zsrc;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(A + (i * 4 + wid) * 1024), 16, 0, 0);
+            lds_dma16(src, A + (i * 4 + wid) * 1024);
         }
 #pragma unroll
         for (int i = 0; i < B_PW; ++i) {
             const IgTap t = taps_l[smallc ? tap_cur + b_lc[i] * EPC / 8 : tap_cur];
             const int coff = smallc ? (b_lc[i] * EPC) & 7 : c0_cur + b_lc[i] * EPC;
             const char* src = b_ok[i] ? (const char*)(pw + (b_row[i] + (size_t)t.widx * p.Ci + coff)) : zsrc;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(B + (i * 4 + wid) * 1024), 16, 0, 0);
+            lds_dma16(src, B + (i * 4 + wid) * 1024);
         }
         if (smallc) tap_cur += TPS;
         else { c0_cur += BKE; if (c0_cur >= p.Ci) { c0_cur = 0; ++tap_cur; } }
@@ -322,11 +300,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
-                for (int j = 0; j < NT; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                    acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc2[i][j], 0, 0, 0);
-                    acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc2[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < NT; ++j) sp_mfma3(ah[i], al[i], bh[j], bl[j], acc[i][j], acc2[i][j]);
         } else if constexpr (!F32) {
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
@@ -402,15 +376,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
             const int idx = idx0 + 8 * k;
             const char* src = (real && (unsigned)idx < (unsigned)p.M) ? a_p0 + ((long long)k * rb8 + (long long)chunk * 128) : zsrc;
             char* dst = real ? Ab + k * 1024 : dump;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            lds_dma16(src, dst);
         };
         auto issue_b = [&](int tapi, int chunk, int slot) __attribute__((always_inline)) {
             const long long bb = ((long long)tapi * p.Ci + (long long)chunk * BKE) * (long long)sizeof(T);
             char* Bs = Bq + slot * (BNL * 128);
 #pragma unroll
             for (int i = 0; i < B_PW; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_ok[i] ? b_ptr0[i] + bb : zsrc),
-                                                 (__attribute__((address_space(3))) void*)(Bs + (i * 4 + wid) * 1024), 16, 0, 0);
+                lds_dma16(b_ok[i] ? b_ptr0[i] + bb : zsrc, Bs + (i * 4 + wid) * 1024);
         };
         // prologue, FIRST (the loads fly while the fragment offsets below are computed): the whole A stage of chunk 0 (the pieces
         // beyond NPc go to the dump), and the first weight tiles
@@ -438,10 +411,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
             const int r = wm * TM + i * 16 + frow, m = m0 + r;
             int ii = -4, jj = -4;                                   // rows beyond M: every tap reads zeros
             if (m < p.M) {
-                const uint32_t n = fdiv((uint32_t)m, p.div_hw);
-                const uint32_t rem = (uint32_t)m - n * (uint32_t)(p.Hg * p.Wg);
-                ii = (int)fdiv(rem, p.div_w);
-                jj = (int)rem - ii * p.Wg;
+                const RowNIJ rn = row_nij((uint32_t)m, p.div_hw, p.div_w, p.Hg, p.Wg);
+                ii = (int)rn.i;
+                jj = (int)rn.j;
             }
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
@@ -503,26 +475,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
     } else {
     // prologue: NS-1 stages in flight
     if (dbg && tid == 0) dbg[1] = __builtin_amdgcn_s_memrealtime();
-    int issued = 0;
-    static_for<NS - 1>([&](auto u) __attribute__((always_inline)) {
-        if (decltype(u)::value < nsteps) { issue_stage(u); ++issued; }
+    Ring<NS, LPS> ring;
+    ring.prologue(nsteps, issue_stage);
+    ring.run_unrolled(nsteps, issue_stage, compute, [&](int st) __attribute__((always_inline)) {
+        if (dbg && tid == 0 && st == 0) dbg[2] = __builtin_amdgcn_s_memrealtime();
     });
-
-    for (int st0 = 0; st0 < nsteps; st0 += NS) {
-        static_for<NS>([&](auto u) __attribute__((always_inline)) {
-            constexpr int U = decltype(u)::value;
-            const int st = st0 + U;
-            if (st < nsteps) {
-                // stage st must have landed: at most (issued - st - 1) younger stages may still be in flight
-                if (issued - st - 1 >= NS - 2) wait_vmcnt<LPS*(NS - 2)>();
-                else wait_vmcnt<0>();
-                __builtin_amdgcn_s_barrier();          // every wave's share of stage st is in LDS; buffer (st-1)%NS is free
-                if (dbg && tid == 0 && st == 0) dbg[2] = __builtin_amdgcn_s_memrealtime();
-                if (issued < nsteps) { issue_stage(IC<(U + NS - 1) % NS>{}); ++issued; }
-                compute(u);
-            }
-        });
-    }
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();   // all LDS reads of the ring are done before the epilogue reuses it
@@ -537,6 +494,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
     if (dbg && tid == 0) dbg[3] = __builtin_amdgcn_s_memrealtime();
 
     // ---- epilogue: accumulators -> LDS (per-wave region) -> 8-channel vectors -> global
+    // (the two epilogues below spell their accumulators -> staging tile loop, their row -> output pixel map and their 8-value stores out, twice: as shared
+    // functions or lambdas each of the three changes the code of every instantiation - the staging loop loses its paired LDS writes -
+    // profiles/conv_once.txt section 1)
     constexpr int ER = C::ER, ELD = C::ELD, LPR = TN / 8 /*lanes per row*/, RPP = 64 / LPR /*rows per pass*/;
     float* est = (float*)stage + wid * ER * ELD;
     const int cg = lane % LPR, rsub = lane / LPR;
@@ -562,15 +522,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
             const int cl = wn * TN + j * 16 + lane;
             if (lane < 16) { xch[(wm * 2 + 0) * BN + cl] = a; xch[(wm * 2 + 1) * BN + cl] = b; }
         }
-        __syncthreads();
-        if (tid < 2 * BN) {
-            const int st = tid / BN, cl = tid % BN, col = n0 + cl;
-            float t = 0.f;
-#pragma unroll
-            for (int w = 0; w < WM; ++w) t += xch[(w * 2 + st) * BN + cl];
-            const size_t srow = (size_t)cls_id * p.m_tiles + m_tile;
-            if (col < p.Co) p.stats[(srow * 2 + st) * p.Co + col] = t;
-        }
+        store_slab_row<WM, BN>(xch, tid, n0, (size_t)cls_id * p.m_tiles + m_tile, p.Co, p.stats);
     }
     float bias[8], scl[8];
 #pragma unroll
@@ -783,15 +735,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM * BN >= 
             const int e = col & 15, cl = wn * TN + (col >> 4) * 8 + (e & 7);
             xch[(wm * 2 + (e >> 3)) * BN + cl] = t;
         }
-        __syncthreads();
-        if (tid < 2 * BN) {
-            const int st = tid / BN, cl = tid % BN, col = n0 + cl;
-            float t = 0.f;
-#pragma unroll
-            for (int w = 0; w < WM; ++w) t += xch[(w * 2 + st) * BN + cl];
-            const size_t srow = (size_t)cls_id * p.m_tiles + m_tile;
-            if (col < p.Co) p.stats[(srow * 2 + st) * p.Co + col] = t;
-        }
+        store_slab_row<WM, BN>(xch, tid, n0, (size_t)cls_id * p.m_tiles + m_tile, p.Co, p.stats);
     }
     if (dbg && tid == 0) {
         dbg[4] = __builtin_amdgcn_s_memrealtime();
@@ -805,11 +749,7 @@ int launch_cfg_t(IgParams& p, hipStream_t stream, const Policy& pol) {
     using C = IgCfg<BM, BN, WM, WN, NS>;
     p.m_tiles = (p.M + BM - 1) / BM;
     p.n_tiles = (p.Co + BN - 1) / BN;
-    static std::atomic<unsigned long long> attr_done{0};
-    static std::mutex attr_mu;
-    once_per_device(attr_done, attr_mu, [] {
-        (void)hipFuncSetAttribute((const void*)igemm_kernel<T, BM, BN, WM, WN, NS, BS, H3, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, H3 == 1 ? 112 * 1024 : C::LDS_BYTES);
-    });
+    max_dynamic_lds<igemm_kernel<T, BM, BN, WM, WN, NS, BS, H3, SP>>(H3 == 1 ? 112 * 1024 : C::LDS_BYTES);
     dim3 grid(p.m_tiles * p.n_tiles, 1, p.nclass);
     // A launch whose K loop is ONE stage (K <= 128 bytes per row: layer1's 64-channel 1x1 convs and their data gradients, the
     // head's data gradient) only ever touches ring buffer 0: it asks for one stage of LDS instead of NS, so four instead of

@@ -12,6 +12,7 @@
 // Both in the 16-bit element type (one v_mfma_f32_16x16x32 per fragment pair) and in the f16x2 split form (common.h: three fp16 MFMAs per
 // fragment pair into two accumulators, combined as in igemm.hip).  HBM-bound by construction: algorithmic bytes = input + output once.
 #include "conv_plan.h"
+#include "mma_tile.h"
 
 namespace {
 
@@ -22,10 +23,6 @@ struct PcParams {
     void* y;
     int N, H, W, Co, relu, out_f32;
 };
-
-template <int U> struct IC { static constexpr int value = U; };
-
-__device__ __forceinline__ int reflect1(int v, int n) { return v < 0 ? -v : (v >= n ? 2 * n - 2 - v : v); }
 
 // ---------------------------------------------------------------------------------------------------------------- Ci = 64, Co <= 16
 // LDS patch: pixel p = r * 66 + c at byte p * 128 (16-bit: its 64 channels; split: 32 channels as [8 h][8 l] x 4 - the split form stages and
@@ -81,7 +78,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 2 : 3)
                 const int e = tid + (bt * IB + i) * 256;
                 if (e < NCH) {
                     const int px = e >> 3, ch = e & 7;
-                    *(u32x4*)(smem + px * 128 + ((ch ^ ((px >> 1) & 7)) << 4)) = regs[i];
+                    *(u32x4*)(smem + px * 128 + ((ch ^ swz(px)) << 4)) = regs[i];
                 }
             }
         }
@@ -110,14 +107,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 2 : 3)
                 const int mb = wid * TH + i;
                 const int px = ((mb >> 2) + dy) * PW + (mb & 3) * 16 + dx + (lane & 15);
                 const char* prow = smem + px * 128;
-                const int sw = (px >> 1) & 7;
+                const int sw = swz(px);
                 if constexpr (SP) {
                     const half8 ah = *(const half8*)(prow + (((2 * q) ^ sw) << 4));
                     const half8 al = *(const half8*)(prow + (((2 * q + 1) ^ sw) << 4));
                     const half8 bh = __builtin_bit_cast(half8, b0[tp]), bl = __builtin_bit_cast(half8, b1[tp]);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[i], 0, 0, 0);
-                    acc2[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc2[i], 0, 0, 0);
-                    acc2[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc2[i], 0, 0, 0);
+                    sp_mfma3(ah, al, bh, bl, acc[i], acc2[i]);
                 } else {
                     const elem8 a0 = *(const elem8*)(prow + ((q ^ sw) << 4));
                     const elem8 a1 = *(const elem8*)(prow + (((4 + q) ^ sw) << 4));
@@ -150,11 +145,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 2 : 3)
 template <bool SP, int TH>
 int launch_co16(const PcParams& p, hipStream_t s) {
     constexpr int LDS = (TH + 2) * 66 * 128;
-    static std::atomic<unsigned long long> attr_done{0};
-    static std::mutex attr_mu;
-    once_per_device(attr_done, attr_mu, [] {
-        (void)hipFuncSetAttribute((const void*)patch3x3_co16_kernel<SP, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    });
+    max_dynamic_lds<patch3x3_co16_kernel<SP, TH>>(LDS);
     const long long total = (long long)(p.W / 64) * (p.H / TH) * p.N;
     if (total <= 0 || total > 0x7fffffffll) return UDAPOSE_ERR_ARG;
     hipLaunchKernelGGL((patch3x3_co16_kernel<SP, TH>), dim3((unsigned)total), dim3(256), LDS, s, p);
@@ -284,9 +275,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SP ? 2 : 3)
 #pragma unroll
                             for (int jb = 0; jb < 2; ++jb) {
                                 const half8 ah = __builtin_bit_cast(half8, wh[half][jb][s3]), al = __builtin_bit_cast(half8, wl[half][jb][s3]);
-                                acc[jb][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[jb][mi], 0, 0, 0);
-                                acc2[jb][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc2[jb][mi], 0, 0, 0);
-                                acc2[jb][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc2[jb][mi], 0, 0, 0);
+                                sp_mfma3(ah, al, bh, bl, acc[jb][mi], acc2[jb][mi]);
                             }
                         } else {
 #pragma unroll
@@ -346,11 +335,7 @@ int launch_ci8(const PcParams& p, hipStream_t s) {
     constexpr int TH = 4, LDS = (TH + 2) * 66 * 16 * (SP ? 2 : 1) + 4 * 64 * (SP ? 256 : 128) + 256;       // patch + the waves' output rows + bias
     const long long total = (long long)(p.W / 64) * (p.H / TH) * p.N;
     if (total <= 0 || total > 0x7fffffffll) return UDAPOSE_ERR_ARG;
-    static std::atomic<unsigned long long> attr_done{0};
-    static std::mutex attr_mu;
-    once_per_device(attr_done, attr_mu, [] {
-        (void)hipFuncSetAttribute((const void*)patch3x3_ci8_kernel<SP, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    });
+    max_dynamic_lds<patch3x3_ci8_kernel<SP, TH>>(LDS);
     // one round of resident work-groups (256 CUs x 3 / 2 by registers), a multiple of 8 so that a work-group's tiles share its XCD
     const long long slots = 256 * (SP ? 2 : 3);
     const unsigned grid = (unsigned)(total < slots ? total : slots);
@@ -527,9 +512,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(JB > 2 ? 2 
 #pragma unroll
                     for (int jb = 0; jb < JB; ++jb) {
                         const half8 ah = __builtin_bit_cast(half8, wa[jb]), al = __builtin_bit_cast(half8, wb[jb]);
-                        acc[jb][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xh, acc[jb][mb], 0, 0, 0);
-                        acc2[jb][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xl, acc2[jb][mb], 0, 0, 0);
-                        acc2[jb][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, xh, acc2[jb][mb], 0, 0, 0);
+                        sp_mfma3(ah, al, xh, xl, acc[jb][mb], acc2[jb][mb]);
                     }
                 } else {
                     const elem8 xf = *(const elem8*)(prow + csel);
@@ -601,11 +584,7 @@ template <bool SP, int TW, int JB>
 int launch_pg(const PgParams& p, hipStream_t s) {
     constexpr int TH = 128 / TW, BN = 32 * JB, LDS = (TH + 2) * (TW + 2) * 128 + 2 * BN * 128;       // (the output rows reuse it)
     static_assert(LDS >= 128 * BN * (SP ? 4 : 2), "epilogue rows fit the staging buffers");
-    static std::atomic<unsigned long long> attr_done{0};
-    static std::mutex attr_mu;
-    once_per_device(attr_done, attr_mu, [] {
-        (void)hipFuncSetAttribute((const void*)patch3x3_kernel<SP, TW, JB>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    });
+    max_dynamic_lds<patch3x3_kernel<SP, TW, JB>>(LDS);
     const long long total = (long long)(p.Wo / TW) * (p.Ho / TH) * p.N * (p.Co / BN);
     if (total <= 0 || total > 0x7fffffffll) return UDAPOSE_ERR_ARG;
     hipLaunchKernelGGL((patch3x3_kernel<SP, TW, JB>), dim3((unsigned)total), dim3(256), LDS, s, p);

@@ -8,7 +8,7 @@
 // no padding.  Taps are added in ascending order by the pixel's one owner thread, max(g) is reduced under hm_better's order again: no
 // atomics, no scratch, and two calls give the same bits.
 #include <math.h>
-#include "conv_plan.h"      // once_per_device
+#include "conv_plan.h"      // max_dynamic_lds
 #include "losses.h"
 
 namespace {
@@ -121,11 +121,7 @@ int refine_decode(hipStream_t s, const float* hm, int R, int H, int W, int mode,
     double e[MAX_TAPS], sum = 0.0;
     for (int i = 0; i < kernel; ++i) { e[i] = exp(-(double)((i - c) * (i - c)) / (2.0 * sg * sg)); sum += e[i]; }
     for (int i = 0; i < kernel; ++i) taps.t[i] = (float)(e[i] / sum);
-    static std::atomic<unsigned long long> attr_done{0};
-    static std::mutex attr_mu;
-    once_per_device(attr_done, attr_mu, [] {
-        (void)hipFuncSetAttribute((const void*)refine_decode_k<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BUDGET);
-    });
+    max_dynamic_lds<refine_decode_k<1>>((int)LDS_BUDGET);
     const unsigned bytes = (unsigned)((size_t)H * W * 2 * sizeof(float) + 15) & ~15u;
     hipLaunchKernelGGL(refine_decode_k<1>, dim3(R), dim3(TPB), bytes, s, hm, H, W, kernel, taps, coords, maxv, idx);
     return udapose_check_launch();

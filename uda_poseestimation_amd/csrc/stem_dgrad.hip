@@ -117,11 +117,7 @@ __global__ __launch_bounds__(SD_THREADS) void stem_dgrad_k(const elem_t* __restr
 
 template <int VEC>
 void sd_launch(hipStream_t s, int grid, const elem_t* dy, const float* w, float* dx, int QH, int QW, int tiles_x, int tiles_y, int ntiles) {
-    static std::atomic<unsigned long long> done{0};
-    static std::mutex mu;
-    once_per_device(done, mu, [] {
-        (void)hipFuncSetAttribute((const void*)stem_dgrad_k<VEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_A_BYTES + SD_B_BYTES);
-    });
+    max_dynamic_lds<stem_dgrad_k<VEC>>(SD_A_BYTES + SD_B_BYTES);
     hipLaunchKernelGGL(stem_dgrad_k<VEC>, dim3(grid), dim3(SD_THREADS), SD_A_BYTES + SD_B_BYTES, s, dy, w, dx, QH, QW, tiles_x, tiles_y, ntiles);
 }
 }  // namespace

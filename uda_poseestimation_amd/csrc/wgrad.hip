@@ -10,6 +10,7 @@
 // grid = (r_tiles*c_tiles, taps (or tap groups of 4 when Ci==8), ksplit).  ksplit>1 or accumulate -> fp32 atomics.
 #include <stdlib.h>
 #include "conv_plan.h"
+#include "mma_tile.h"
 #include "pointwise.h"      // pw_zero
 
 namespace {
@@ -23,6 +24,27 @@ struct WgCfg {
     static constexpr int P_CH = (32 * RT / 8 + 255) / 256, Q_CH = (32 * CT / 8 + 255) / 256;
     static constexpr int LDS_BYTES = 2 * (P_BYTES + Q_BYTES);
 };
+
+// dW store of one wave's MT x NT accumulator blocks, block (0, 0) at (row0, col0) of the Rdim x Cdim slab `widx`: D[row][col], a lane holds
+// col = lane & 15, rows (lane >> 4) * 4 + reg.  Atomic adds (split or accumulating launches) or plain stores.
+template <int MT, int NT>
+__device__ __forceinline__ void wg_store_tile(const f32x4 (&acc)[MT][NT], int lane, int row0, int col0, int Rdim, int rows_valid, int Cdim, int wtaps, int widx,
+                                              float* dw, size_t part_off, bool atomic) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int rr = row0 + i * 16 + (lane >> 4) * 4 + r;
+                const int cc = col0 + j * 16 + (lane & 15);
+                if (rr >= Rdim || rr >= rows_valid || cc >= Cdim) continue;
+                const size_t off = ((size_t)rr * wtaps + widx) * Cdim + cc + part_off;
+                const float v = acc[i][j][r];
+                if (atomic) atomicAdd(dw + off, v);
+                else dw[off] = v;
+            }
+}
 
 template <int RT, int CT, int WR, int WC>
 __global__ __launch_bounds__(256) void wgrad_kernel(const WgParams p) {
@@ -58,16 +80,13 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgParams p) {
     auto load_op = [&](bool is_x, int row, int chn, int m, const IgTap& t, int dim_base, int dim_lim) -> u32x4 {
         u32x4 v = {0u, 0u, 0u, 0u};
         if (m >= p.M || chn >= dim_lim) return v;
-        const uint32_t n = fdiv((uint32_t)m, p.div_hw);
-        const uint32_t rem = (uint32_t)m - n * (uint32_t)(p.Hg * p.Wg);
-        const uint32_t ii = fdiv(rem, p.div_w);
-        const uint32_t jj = rem - ii * (uint32_t)p.Wg;
+        const RowNIJ r = row_nij((uint32_t)m, p.div_hw, p.div_w, p.Hg, p.Wg);
         if (is_x) {
-            const int hi = (int)ii * p.s + t.dy, wi = (int)jj * p.s + t.dx;
+            const int hi = (int)r.i * p.s + t.dy, wi = (int)r.j * p.s + t.dx;
             if ((unsigned)hi < (unsigned)p.Hi && (unsigned)wi < (unsigned)p.Wi)
-                v = *(const u32x4*)(p.x + (((size_t)n * p.Hi + hi) * p.Wi + wi) * p.Ci + chn);
+                v = *(const u32x4*)(p.x + (((size_t)r.n * p.Hi + hi) * p.Wi + wi) * p.Ci + chn);
         } else {
-            const size_t opix = ((size_t)n * p.Ho + (ii * p.os + cls.oa)) * p.Wo + (jj * p.os + cls.ob);
+            const size_t opix = ((size_t)r.n * p.Ho + (r.i * p.os + cls.oa)) * p.Wo + (r.j * p.os + cls.ob);     // (inside the map: the plain layers' classes)
             v = *(const u32x4*)(p.dy + opix * p.Co + chn);
         }
         return v;
@@ -140,20 +159,12 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgParams p) {
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const int colb = (wr * TR + i * 16 + 4 * pp) * 2;
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, P + trow * C::PSTR + colb));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, P + (16 + trow) * C::PSTR + colb));
-            union { struct { s16x4 a, b; } s; elem8 v; } u;
-            u.s.a = lo; u.s.b = hi;
-            af[i] = u.v;
+            af[i] = tr_frag(P + trow * C::PSTR + colb, P + (16 + trow) * C::PSTR + colb);
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int colb = (wc * TC + j * 16 + 4 * pp) * 2;
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, Q + trow * C::QSTR + colb));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, Q + (16 + trow) * C::QSTR + colb));
-            union { struct { s16x4 a, b; } s; elem8 v; } u;
-            u.s.a = lo; u.s.b = hi;
-            bfr[j] = u.v;
+            bfr[j] = tr_frag(Q + trow * C::QSTR + colb, Q + (16 + trow) * C::QSTR + colb);
         }
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -166,6 +177,12 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgParams p) {
 
     // ---- epilogue: D[row = r][col = c]; lane holds col = lane&15, rows (lane>>4)*4 + reg
     const bool atomic = (p.flags & WG_FLAG_ATOMIC) != 0;
+    if (!smallc) {
+        wg_store_tile(acc, lane, r0 + wr * TR, c0 + wc * TC, Rdim, p.rows_valid, Cdim, p.wtaps, tp[0].widx, p.dw, 0, atomic);
+        return;
+    }
+    if (swap) return;       // (not used: no transposed conv with 8 input channels)
+    // the columns of the Ci == 8 operand enumerate 4 taps x 8 channels
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -174,22 +191,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgParams p) {
             for (int r = 0; r < 4; ++r) {
                 const int rr = r0 + wr * TR + i * 16 + (lane >> 4) * 4 + r;
                 const int ccl = wc * TC + j * 16 + (lane & 15);      // column inside the tile
-                if (rr >= Rdim || rr >= p.rows_valid) continue;
-                size_t off;
-                if (smallc) {
-                    // columns (or rows) of the Ci==8 operand enumerate 4 taps x 8 channels
-                    if (!swap) {
-                        const IgTap& t = tp[(ccl >> 3) & 3];
-                        if (ccl >= 32) continue;
-                        off = ((size_t)rr * p.wtaps + t.widx) * 8 + (ccl & 7);
-                    } else {
-                        continue;   // not used: no transposed conv with 8 input channels
-                    }
-                } else {
-                    const int cc = c0 + ccl;
-                    if (cc >= Cdim) continue;
-                    off = ((size_t)rr * p.wtaps + tp[0].widx) * Cdim + cc;
-                }
+                if (rr >= Rdim || rr >= p.rows_valid || ccl >= 32) continue;
+                const size_t off = ((size_t)rr * p.wtaps + tp[(ccl >> 3) & 3].widx) * 8 + (ccl & 7);
                 const float v = acc[i][j][r];
                 if (atomic) atomicAdd(p.dw + off, v);
                 else p.dw[off] = v;
@@ -204,20 +207,24 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgParams p) {
 // of one 32-lane half (8 pixel rows x 32 bytes) hit 16 distinct 16-byte bank slots.
 __device__ u32x4 g_wzero16[2];
 
-template <int N> __device__ __forceinline__ void wg_wait_vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else static_assert(N < 0, "add the vmcnt literal");
-}
-
 template <int CH> __device__ __forceinline__ int wswz(int row) {   // CH = channels per LDS row (64 or 128)
     return CH == 64 ? (((row >> 1) & 3) << 1) : ((row & 7) << 1);
+}
+
+// byte offset inside a stage's [pixels][CH channels] tile of the transposing read of pixel `row`, channels col .. col + 3 (col % 4 == 0)
+template <int CH> __device__ __forceinline__ int wfrag_off(int row, int col) {
+    return row * (CH * 2) + ((((col >> 3) ^ wswz<CH>(row)) << 4) | ((col & 4) << 1));
+}
+
+// The pixel range of split bz of ksplit: nsteps PX-pixel stages from stage ms0; part_off = where a partial-tile split stores (elements)
+struct WgSplit { int ms0, nsteps; size_t part_off; };
+template <int PX> __device__ __forceinline__ WgSplit wg_split(int M, int ksplit, uint32_t bz, unsigned part_stride) {
+    const int ms_total = (M + PX - 1) / PX;
+    const int per = (ms_total + ksplit - 1) / ksplit;
+    const int ms0 = bz * per;
+    int ms1 = ms0 + per;
+    if (ms1 > ms_total) ms1 = ms_total;
+    return {ms0, ms1 > ms0 ? ms1 - ms0 : 0, (size_t)bz * part_stride};
 }
 
 template <int RT, int CT, int WR, int WC, int NS, int PX = 64>   // PX = pixels (K rows) per LDS stage: 64 or 32
@@ -240,7 +247,7 @@ struct WdCfg {
 // stride-1 same-size layers (WG_FLAG_FASTGEO), 2 the bit-field one of strided, transposed and stem row-tap layers (WG_FLAG_FASTGEO_S).
 template <int RT, int CT, int WR, int WC, int NS, int PX = 64, int GEO = 0>
 __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_t bx, const uint32_t by, const uint32_t bz, char* smem,
-                                               const uintptr_t x_base = 0, const uintptr_t dy_base = 0, const uintptr_t dw_base = 0) {
+                                               const uintptr_t x_base, const uintptr_t dy_base, const uintptr_t dw_base) {
     // scalar copies of the fields used below (gp may live in global memory: read it once, up front, into SGPRs)
     struct {
         const elem_t* dy; const elem_t* x; float* dw; const IgTap* taps;
@@ -268,13 +275,9 @@ __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_
     if (tp.cls == 1) { cls.oa = gp.cls[1].oa; cls.ob = gp.cls[1].ob; }
     if (tp.cls == 2) { cls.oa = gp.cls[2].oa; cls.ob = gp.cls[2].ob; }
     if (tp.cls == 3) { cls.oa = gp.cls[3].oa; cls.ob = gp.cls[3].ob; }
-    const int ms_total = (p.M + PX - 1) / PX;                        // PX-pixel stages
-    const int per = (ms_total + p.ksplit - 1) / p.ksplit;
-    const int ms0 = bz * per;
-    int ms1 = ms0 + per;
-    if (ms1 > ms_total) ms1 = ms_total;
-    const int nsteps = ms1 > ms0 ? ms1 - ms0 : 0;
-    const size_t part_off = (size_t)bz * gp.part_stride;
+    const WgSplit split = wg_split<PX>(p.M, p.ksplit, bz, gp.part_stride);
+    const int ms0 = split.ms0, nsteps = split.nsteps;
+    const size_t part_off = split.part_off;
     const char* zsrc = (const char*)g_wzero16;
 
     // Address generation is the issue-slot hog of this loop (measured 24 VALU instructions per MFMA when every row was
@@ -303,7 +306,7 @@ __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_
     const auto lg2 = [](int v) { return 31 - __builtin_clz((unsigned)(v > 0 ? v : 1)); };
     const int lg_wg = lg2(p.Wg), lg_hwg = lg_wg + lg2(p.Hg), lg_hwi = lgw + lg2(p.Hi), lg_wo = lg2(p.Wo), lg_hwo = lg_wo + lg2(p.Ho);
     const int lgs = p.s >> 1, lgos = p.os >> 1;                       // (strides 1 or 2)
-    auto issue_stage = [&](int st, int buf) {
+    auto issue_stage = [&](int st, int buf) __attribute__((always_inline)) {
         const int mb = (ms0 + st) * PX;
         char* P = smem + buf * C::STAGE1;
         char* Q = P + C::P_BYTES;
@@ -328,10 +331,8 @@ __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_
                 const unsigned ox = __umul24(xpix, (unsigned)p.Ci) + (unsigned)xch;
                 const char* sd = (okm && dch < p.Co) ? (const char*)p.dy + (size_t)od * 2 : zsrc;
                 const char* sx = (okx && xch < p.Ci) ? (const char*)p.x + (size_t)ox * 2 : zsrc;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(swap ? sx : sd),
-                                                 (__attribute__((address_space(3))) void*)(P + (i * 4 + wid) * 1024), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(swap ? sd : sx),
-                                                 (__attribute__((address_space(3))) void*)(Q + (i * 4 + wid) * 1024), 16, 0, 0);
+                lds_dma16(swap ? sx : sd, P + (i * 4 + wid) * 1024);
+                lds_dma16(swap ? sd : sx, Q + (i * 4 + wid) * 1024);
             }
         } else if constexpr (GEO == 1) {
 #pragma unroll
@@ -351,10 +352,8 @@ __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_
                 const unsigned ox = __umul24((unsigned)(m + toff), (unsigned)p.Ci) + (unsigned)qc;   // Q rows from x
                 const char* sp = (okd && pc < Rdim) ? (const char*)p.dy + (size_t)od * 2 : zsrc;
                 const char* sq = (okx && qc < Cdim) ? (const char*)p.x + (size_t)ox * 2 : zsrc;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sp,
-                                                 (__attribute__((address_space(3))) void*)(P + (i * 4 + wid) * 1024), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sq,
-                                                 (__attribute__((address_space(3))) void*)(Q + (i * 4 + wid) * 1024), 16, 0, 0);
+                lds_dma16(sp, P + (i * 4 + wid) * 1024);
+                lds_dma16(sq, Q + (i * 4 + wid) * 1024);
             }
         } else {
 #pragma unroll
@@ -366,24 +365,19 @@ __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_
             const char* sx = zsrc;
             const char* sd = zsrc;
             if (mok) {
-                uint32_t n = 0, ii = 0, jj = 0;
-                if (!(dy_lin && x_lin)) {
-                    n = fdiv((uint32_t)m, p.div_hw);
-                    const uint32_t rem = (uint32_t)m - n * (uint32_t)(p.Hg * p.Wg);
-                    ii = fdiv(rem, p.div_w);
-                    jj = rem - ii * (uint32_t)p.Wg;
-                }
+                RowNIJ r = {0, 0, 0};
+                if (!(dy_lin && x_lin)) r = row_nij((uint32_t)m, p.div_hw, p.div_w, p.Hg, p.Wg);
                 if (x_lin) sx = (const char*)(p.x + (size_t)m * p.Ci);
                 else {
-                    const int hi = (int)ii * p.s + tp.dy, wi = (int)jj * p.s + tp.dx;
+                    const int hi = (int)r.i * p.s + tp.dy, wi = (int)r.j * p.s + tp.dx;
                     const int wl = rowtap ? wi + lc : wi;            // this lane's chunk is column tap lc
                     if ((unsigned)hi < (unsigned)p.Hi && (unsigned)wl < (unsigned)p.Wi && (!rowtap || lc < p.kw))
-                        sx = (const char*)(p.x + (((long long)n * p.Hi + hi) * p.Wi + wi) * p.Ci);   // (+ lc * 16 bytes below)
+                        sx = (const char*)(p.x + (((long long)r.n * p.Hi + hi) * p.Wi + wi) * p.Ci);   // (+ lc * 16 bytes below)
                 }
                 if (dy_lin) sd = (const char*)(p.dy + (size_t)m * p.Co);
                 else {
-                    const uint32_t oh = ii * p.os + cls.oa, ow = jj * p.os + cls.ob;
-                    if (oh < (uint32_t)p.Ho && ow < (uint32_t)p.Wo) sd = (const char*)(p.dy + (((size_t)n * p.Ho + oh) * p.Wo + ow) * p.Co);
+                    size_t opix;
+                    if (out_pixel(r, p.os, cls.oa, cls.ob, p.Ho, p.Wo, opix)) sd = (const char*)(p.dy + opix * p.Co);
                 }
             }
             const char* sp = p_is_x ? sx : sd;
@@ -391,10 +385,8 @@ __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_
             const int pc = r0 + lc * 8, qc = c0 + lc * 8;
             sp = (sp != zsrc && pc < Rdim) ? sp + (size_t)pc * 2 : zsrc;
             sq = (sq != zsrc && qc < Cdim) ? sq + (size_t)qc * 2 : zsrc;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sp,
-                                             (__attribute__((address_space(3))) void*)(P + (i * 4 + wid) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sq,
-                                             (__attribute__((address_space(3))) void*)(Q + (i * 4 + wid) * 1024), 16, 0, 0);
+            lds_dma16(sp, P + (i * 4 + wid) * 1024);
+            lds_dma16(sq, Q + (i * 4 + wid) * 1024);
         }
         }
     };
@@ -405,48 +397,26 @@ __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    int issued = 0;
-#pragma unroll
-    for (int st = 0; st < NS - 1; ++st)
-        if (st < nsteps) { issue_stage(st, st); ++issued; }
+    Ring<NS, LPS> ring;
+    ring.prologue(nsteps, issue_stage);
 
     const int g = lane >> 4, li = lane & 15, qq = li >> 2, pp = li & 3;
-    for (int st = 0; st < nsteps; ++st) {
-        const int buf = st % NS;
-        if (issued - st - 1 >= NS - 2) wg_wait_vmcnt<LPS*(NS - 2)>();
-        else wg_wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        if (issued < nsteps) { issue_stage(issued, issued % NS); ++issued; }
+    ring.run(nsteps, issue_stage, [&](int buf) __attribute__((always_inline)) {
         const char* P = smem + buf * C::STAGE1;
         const char* Q = P + C::P_BYTES;
 #pragma unroll
         for (int kk = 0; kk < PX / 32; ++kk) {
+            const int row = 32 * kk + 4 * g + qq;
             elem8 af[MT], bfr[NT];
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int col = wr * TR + i * 16 + 4 * pp;           // first of this lane's 4 columns
-                union { struct { s16x4 a, b; } s; elem8 v; } u;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int row = 32 * kk + 16 * h + 4 * g + qq;
-                    const int off = row * C::PROW + ((((col >> 3) ^ wswz<RT>(row)) << 4) | ((col & 4) << 1));
-                    const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, P + off));
-                    if (h == 0) u.s.a = v; else u.s.b = v;
-                }
-                af[i] = u.v;
+                af[i] = tr_frag(P + wfrag_off<RT>(row, col), P + wfrag_off<RT>(row + 16, col));
             }
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const int col = wc * TC + j * 16 + 4 * pp;
-                union { struct { s16x4 a, b; } s; elem8 v; } u;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int row = 32 * kk + 16 * h + 4 * g + qq;
-                    const int off = row * C::QROW + ((((col >> 3) ^ wswz<CT>(row)) << 4) | ((col & 4) << 1));
-                    const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, Q + off));
-                    if (h == 0) u.s.a = v; else u.s.b = v;
-                }
-                bfr[j] = u.v;
+                bfr[j] = tr_frag(Q + wfrag_off<CT>(row, col), Q + wfrag_off<CT>(row + 16, col));
             }
 #pragma unroll
             for (int i = 0; i < MT; ++i)
@@ -454,23 +424,9 @@ __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_
                 for (int j = 0; j < NT; ++j)
                     acc[i][j] = UDAPOSE_MFMA_16x16x32(af[i], bfr[j], acc[i][j]);
         }
-    }
+    });
 
-    const bool atomic = (p.flags & WG_FLAG_ATOMIC) != 0;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int rr = r0 + wr * TR + i * 16 + (lane >> 4) * 4 + r;
-                const int cc = c0 + wc * TC + j * 16 + (lane & 15);
-                if (rr >= Rdim || rr >= p.rows_valid || cc >= Cdim) continue;
-                const size_t off = ((size_t)rr * p.wtaps + tp.widx) * Cdim + cc + part_off;
-                const float v = acc[i][j][r];
-                if (atomic) atomicAdd(p.dw + off, v);
-                else p.dw[off] = v;
-            }
+    wg_store_tile(acc, lane, r0 + wr * TR, c0 + wc * TC, Rdim, p.rows_valid, Cdim, p.wtaps, tp.widx, p.dw, part_off, (p.flags & WG_FLAG_ATOMIC) != 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -482,13 +438,9 @@ __device__ __forceinline__ void wgrad_dma_body(const WgParams& gp, const uint32_
 //     hardware writes zeros into LDS (tools/probe/buf_lds.hip) - no 64-bit address arithmetic, no pointer selects, no zero page;
 //   * the ring is unrolled over its NS buffers, so LDS destinations (M0) and fragment read offsets are compile-time constants;
 //   * pixel counts are multiples of the stage (power-of-two maps), so there is no row-validity test at all for centre taps.
-template <int U> struct WIC { static constexpr int value = U; };
-template <int N, typename F> __device__ __forceinline__ void w_static_for(F&& f) {
-    if constexpr (N > 0) { w_static_for<N - 1>(f); f(WIC<N - 1>{}); }
-}
 template <int RT, int CT, int WR, int WC, int NS, int PX>
 __device__ __forceinline__ void wgrad_fast2_body(const WgParams& gp, const uint32_t bx, const uint32_t by, const uint32_t bz, char* smem,
-                                                 const uintptr_t x_base = 0, const uintptr_t dy_base = 0, const uintptr_t dw_base = 0) {
+                                                 const uintptr_t x_base, const uintptr_t dy_base, const uintptr_t dw_base) {
     struct {
         const elem_t* dy; const elem_t* x; float* dw; const IgTap* taps;
         int Hi, Wi, Ci, Co, M, wtaps, flags, ksplit, c_tiles, rows_valid;
@@ -512,13 +464,9 @@ __device__ __forceinline__ void wgrad_fast2_body(const WgParams& gp, const uint3
                                        __builtin_amdgcn_readfirstlane(tp0.widx)};
     const int toff = tp.dy * p.Wi + tp.dx;
     const bool center = tp.dy == 0 && tp.dx == 0;
-    const int ms_total = p.M / PX;                                    // (M % PX == 0: checked on the host)
-    const int per = (ms_total + p.ksplit - 1) / p.ksplit;
-    const int ms0 = bz * per;
-    int ms1 = ms0 + per;
-    if (ms1 > ms_total) ms1 = ms_total;
-    const int nsteps = ms1 > ms0 ? ms1 - ms0 : 0;
-    const size_t part_off = (size_t)bz * gp.part_stride;
+    const WgSplit split = wg_split<PX>(p.M, p.ksplit, bz, gp.part_stride);   // (M % PX == 0: checked on the host)
+    const int ms0 = split.ms0, nsteps = split.nsteps;
+    const size_t part_off = split.part_off;
     const unsigned w_mask = (unsigned)p.Wi - 1u, hw_mask = (unsigned)(p.Hi * p.Wi) - 1u;
     const int lgw = 31 - __builtin_clz((unsigned)p.Wi);
     // raw buffers over the two tensors; the x buffer starts at the tap's pixel offset (possibly in front of the tensor: every pixel
@@ -570,11 +518,8 @@ __device__ __forceinline__ void wgrad_fast2_body(const WgParams& gp, const uint3
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    int issued = 0;
-    w_static_for<NS - 1>([&](auto u) {
-        constexpr int U = decltype(u)::value;
-        if (U < nsteps) { issue_stage(U, u); ++issued; }
-    });
+    Ring<NS, LPS> ring;
+    ring.prologue(nsteps, issue_stage);
 
     const int g = lane >> 4, li = lane & 15, qq = li >> 2, pp = li & 3;
     // lane part of the fragment read offsets (the stage buffer, kk, h and the fragment index are compile-time constants)
@@ -585,12 +530,12 @@ __device__ __forceinline__ void wgrad_fast2_body(const WgParams& gp, const uint3
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const int col = wr * TR + i * 16 + 4 * pp;
-            a_lo[i][h] = row * C::PROW + ((((col >> 3) ^ wswz<RT>(row)) << 4) | ((col & 4) << 1));
+            a_lo[i][h] = wfrag_off<RT>(row, col);
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int col = wc * TC + j * 16 + 4 * pp;
-            b_lo[j][h] = C::P_BYTES + row * C::QROW + ((((col >> 3) ^ wswz<CT>(row)) << 4) | ((col & 4) << 1));
+            b_lo[j][h] = C::P_BYTES + wfrag_off<CT>(row, col);
         }
     }
 
@@ -601,19 +546,9 @@ __device__ __forceinline__ void wgrad_fast2_body(const WgParams& gp, const uint3
         for (int kk = 0; kk < PX / 32; ++kk) {
             elem8 af[MT], bfr[NT];
 #pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                union { struct { s16x4 a, b; } s; elem8 v; } u;
-                u.s.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, S + a_lo[i][0] + kk * 32 * C::PROW));
-                u.s.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, S + a_lo[i][1] + kk * 32 * C::PROW));
-                af[i] = u.v;
-            }
+            for (int i = 0; i < MT; ++i) af[i] = tr_frag(S + a_lo[i][0] + kk * 32 * C::PROW, S + a_lo[i][1] + kk * 32 * C::PROW);
 #pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                union { struct { s16x4 a, b; } s; elem8 v; } u;
-                u.s.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, S + b_lo[j][0] + kk * 32 * C::QROW));
-                u.s.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, S + b_lo[j][1] + kk * 32 * C::QROW));
-                bfr[j] = u.v;
-            }
+            for (int j = 0; j < NT; ++j) bfr[j] = tr_frag(S + b_lo[j][0] + kk * 32 * C::QROW, S + b_lo[j][1] + kk * 32 * C::QROW);
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -622,35 +557,9 @@ __device__ __forceinline__ void wgrad_fast2_body(const WgParams& gp, const uint3
         }
     };
 
-    for (int st0 = 0; st0 < nsteps; st0 += NS) {
-        w_static_for<NS>([&](auto u) {
-            constexpr int U = decltype(u)::value;
-            const int st = st0 + U;
-            if (st < nsteps) {
-                if (issued - st - 1 >= NS - 2) wg_wait_vmcnt<LPS*(NS - 2)>();
-                else wg_wait_vmcnt<0>();
-                __builtin_amdgcn_s_barrier();
-                if (issued < nsteps) { issue_stage(issued, WIC<(U + NS - 1) % NS>{}); ++issued; }
-                compute(u);
-            }
-        });
-    }
+    ring.run_unrolled(nsteps, issue_stage, compute, [](int) {});
 
-    const bool atomic = (p.flags & WG_FLAG_ATOMIC) != 0;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int rr = r0 + wr * TR + i * 16 + (lane >> 4) * 4 + r;
-                const int cc = c0 + wc * TC + j * 16 + (lane & 15);
-                if (rr >= p.Co || rr >= p.rows_valid || cc >= p.Ci) continue;
-                const size_t off = ((size_t)rr * p.wtaps + tp.widx) * p.Ci + cc + part_off;
-                const float v = acc[i][j][r];
-                if (atomic) atomicAdd(p.dw + off, v);
-                else p.dw[off] = v;
-            }
+    wg_store_tile(acc, lane, r0 + wr * TR, c0 + wc * TC, p.Co, p.rows_valid, p.Ci, p.wtaps, tp.widx, p.dw, part_off, (p.flags & WG_FLAG_ATOMIC) != 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -671,7 +580,7 @@ struct Row3Cfg {
 };
 template <int NS>
 __device__ __forceinline__ void wgrad_row3_body(const WgParams& gp, const uint32_t bx, const uint32_t by, const uint32_t bz, char* smem,
-                                                const uintptr_t x_base = 0, const uintptr_t dy_base = 0, const uintptr_t dw_base = 0) {
+                                                const uintptr_t x_base, const uintptr_t dy_base, const uintptr_t dw_base) {
     using R = Row3Cfg;
     constexpr int PX = R::PX, LPS = 5;                                 // 2 dy pieces + 3 x-window pieces per wave and stage
     struct {
@@ -685,13 +594,9 @@ __device__ __forceinline__ void wgrad_row3_body(const WgParams& gp, const uint32
     const int c_tile = bx % p.c_tiles, r_tile = bx / p.c_tiles;
     const int r0 = r_tile * 64, c0 = c_tile * 64;
     const int dyk = (int)by - 1;                                       // this work-group's filter row: dy = -1, 0, +1
-    const int ms_total = (p.M + PX - 1) / PX;
-    const int per = (ms_total + p.ksplit - 1) / p.ksplit;
-    const int ms0 = bz * per;
-    int ms1 = ms0 + per;
-    if (ms1 > ms_total) ms1 = ms_total;
-    const int nsteps = ms1 > ms0 ? ms1 - ms0 : 0;
-    const size_t part_off = (size_t)bz * gp.part_stride;
+    const WgSplit split = wg_split<PX>(p.M, p.ksplit, bz, gp.part_stride);
+    const int ms0 = split.ms0, nsteps = split.nsteps;
+    const size_t part_off = split.part_off;
     const char* zsrc = (const char*)g_wzero16;
     char* const dump = smem + NS * R::STAGE1;
     const unsigned w_mask = (unsigned)p.Wi - 1u, hw_mask = (unsigned)(p.Hi * p.Wi) - 1u;
@@ -711,8 +616,7 @@ __device__ __forceinline__ void wgrad_row3_body(const WgParams& gp, const uint32
             const bool ok = m < p.M && (unsigned)((int)(((unsigned)m & hw_mask) >> lgw) + dyk) < (unsigned)p.Hi;
             const unsigned od = __umul24((unsigned)m, (unsigned)p.Co) + (unsigned)(r0 + lc * 8);
             const char* sp = ok ? (const char*)p.dy + (size_t)od * 2 : zsrc;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sp,
-                                             (__attribute__((address_space(3))) void*)(P + (i * 4 + wid) * 1024), 16, 0, 0);
+            lds_dma16(sp, P + (i * 4 + wid) * 1024);
         }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -724,7 +628,7 @@ __device__ __forceinline__ void wgrad_row3_body(const WgParams& gp, const uint32
             const unsigned ox = __umul24((unsigned)(ok ? xp : 0), (unsigned)p.Ci) + (unsigned)(c0 + lc * 8);
             const char* sq = ok ? (const char*)p.x + (size_t)ox * 2 : zsrc;
             char* dst = k < 9 ? Q + k * 1024 : dump;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sq, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            lds_dma16(sq, dst);
         }
     };
 
@@ -736,10 +640,8 @@ __device__ __forceinline__ void wgrad_row3_body(const WgParams& gp, const uint32
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[t][i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    int issued = 0;
-#pragma unroll
-    for (int st = 0; st < NS - 1; ++st)
-        if (st < nsteps) { issue_stage(st, st); ++issued; }
+    Ring<NS, LPS> ring;
+    ring.prologue(nsteps, issue_stage);
 
     const int g = lane >> 4, li = lane & 15, qq = li >> 2, pp = li & 3;
     // fragment element e of a lane is pixel row 32*kk + 16*(e >> 2) + 4*g + (e & 3) of the stage; stages start at multiples of 64
@@ -760,12 +662,11 @@ __device__ __forceinline__ void wgrad_row3_body(const WgParams& gp, const uint32
             mL[kk][v] = l; mR[kk][v] = r;
         }
 
+    // (the loop skeleton around Ring::step and the fragment assembly below stay spelled out here: through Ring::run or tr_frag this body takes 132 / 136
+    // registers inside wgrad_dma_kernel<64, 64, 2, 2, 4>, which has no waves_per_eu attribute - 3 instead of 4 waves per SIMD, profiles/conv_once.txt)
     for (int st = 0; st < nsteps; ++st) {
         const int buf = st % NS;
-        if (issued - st - 1 >= NS - 2) wg_wait_vmcnt<LPS*(NS - 2)>();
-        else wg_wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        if (issued < nsteps) { issue_stage(issued, issued % NS); ++issued; }
+        ring.step(st, nsteps, issue_stage);
         const char* P = smem + buf * R::STAGE1;
         const char* Q = P + R::P_BYTES;
 #pragma unroll
@@ -778,7 +679,7 @@ __device__ __forceinline__ void wgrad_row3_body(const WgParams& gp, const uint32
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int row = 32 * kk + 16 * h + 4 * g + qq;
-                    const int off = row * 128 + ((((col >> 3) ^ wswz<64>(row)) << 4) | ((col & 4) << 1));
+                    const int off = wfrag_off<64>(row, col);
                     const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, P + off));
                     if (h == 0) af[i].s.a = v; else af[i].s.b = v;
                 }
@@ -792,7 +693,7 @@ __device__ __forceinline__ void wgrad_row3_body(const WgParams& gp, const uint32
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const int row = 32 * kk + 16 * h + 4 * g + qq + t;       // window row = pixel row + 1 + dx
-                        const int off = row * 128 + ((((col >> 3) ^ wswz<64>(row)) << 4) | ((col & 4) << 1));
+                        const int off = wfrag_off<64>(row, col);
                         const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, Q + off));
                         if (h == 0) bfr[j].s.a = v; else bfr[j].s.b = v;
                     }
@@ -809,23 +710,22 @@ __device__ __forceinline__ void wgrad_row3_body(const WgParams& gp, const uint32
         }
     }
 
-    const bool atomic = (p.flags & WG_FLAG_ATOMIC) != 0;
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int rr = r0 + wr * 32 + i * 16 + (lane >> 4) * 4 + r;
-                    const int cc = c0 + wc * 32 + j * 16 + (lane & 15);
-                    if (rr >= p.Co || rr >= p.rows_valid || cc >= p.Ci) continue;
-                    const size_t off = ((size_t)rr * p.wtaps + (3 * by + t)) * p.Ci + cc + part_off;      // tap (dy, dx) -> weight slab 3*(dy+1) + (dx+1)
-                    const float v = acc[t][i][j][r];
-                    if (atomic) atomicAdd(p.dw + off, v);
-                    else p.dw[off] = v;
-                }
+    for (int t = 0; t < 3; ++t)       // tap (dy, dx) -> weight slab 3*(dy+1) + (dx+1)
+        wg_store_tile(acc[t], lane, r0 + wr * 32, c0 + wc * 32, p.Co, p.rows_valid, p.Ci, p.wtaps, 3 * by + t, p.dw, part_off, (p.flags & WG_FLAG_ATOMIC) != 0);
+}
+
+// The body of problem p by its loader flags (the x / dy / dw bases: zero for a per-layer launch, the pass's arenas for a grouped one)
+template <int RT, int CT, int WR, int WC, int NS, int PX>
+__device__ __forceinline__ void wgrad_run_body(const WgParams& p, const uint32_t bx, const uint32_t by, const uint32_t bz, char* smem,
+                                               const uintptr_t x_base, const uintptr_t dy_base, const uintptr_t dw_base) {
+    if constexpr (RT == 64 && CT == 64 && PX == 64) {
+        if (p.flags & WG_FLAG_ROW3) { wgrad_row3_body<NS>(p, bx, by, bz, smem, x_base, dy_base, dw_base); return; }
+    }
+    if (p.flags & WG_FLAG_FAST2) wgrad_fast2_body<RT, CT, WR, WC, NS, PX>(p, bx, by, bz, smem, x_base, dy_base, dw_base);
+    else if (p.flags & WG_FLAG_FASTGEO) wgrad_dma_body<RT, CT, WR, WC, NS, PX, 1>(p, bx, by, bz, smem, x_base, dy_base, dw_base);
+    else if (p.flags & WG_FLAG_FASTGEO_S) wgrad_dma_body<RT, CT, WR, WC, NS, PX, 2>(p, bx, by, bz, smem, x_base, dy_base, dw_base);
+    else wgrad_dma_body<RT, CT, WR, WC, NS, PX>(p, bx, by, bz, smem, x_base, dy_base, dw_base);
 }
 
 template <int RT, int CT, int WR, int WC, int NS>
@@ -836,13 +736,7 @@ __global__ __launch_bounds__(256) void wgrad_dma_kernel(const WgParams p) {
     const uint32_t lin = xcd_remap(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), gxy * gridDim.z);
     const uint32_t bz = lin / gxy, bxy = lin - bz * gxy;
     const uint32_t by = bxy / gridDim.x, bx = bxy - by * gridDim.x;
-    if constexpr (RT == 64 && CT == 64) {
-        if (p.flags & WG_FLAG_ROW3) { wgrad_row3_body<NS>(p, bx, by, bz, smem); return; }
-    }
-    if (p.flags & WG_FLAG_FAST2) wgrad_fast2_body<RT, CT, WR, WC, NS, 64>(p, bx, by, bz, smem);
-    else if (p.flags & WG_FLAG_FASTGEO) wgrad_dma_body<RT, CT, WR, WC, NS, 64, 1>(p, bx, by, bz, smem);
-    else if (p.flags & WG_FLAG_FASTGEO_S) wgrad_dma_body<RT, CT, WR, WC, NS, 64, 2>(p, bx, by, bz, smem);
-    else wgrad_dma_body<RT, CT, WR, WC, NS>(p, bx, by, bz, smem);
+    wgrad_run_body<RT, CT, WR, WC, NS, 64>(p, bx, by, bz, smem, 0, 0, 0);
 }
 
 // Grouped form: ONE launch computes the weight gradients of many layers.  blk is an [8][per_xcd] table (work-group b runs
@@ -868,13 +762,7 @@ __device__ __forceinline__ void wgrad_group_dispatch(const WgParams* __restrict_
     const uint32_t gx = (uint32_t)(p.r_tiles * p.c_tiles), gxy = gx * (uint32_t)p.total_taps;
     const uint32_t bz = (uint32_t)b.local / gxy, bxy = (uint32_t)b.local - bz * gxy;
     const uint32_t by = bxy / gx, bx = bxy - by * gx;
-    if constexpr (RT == 64 && CT == 64 && PX == 64) {
-        if (p.flags & WG_FLAG_ROW3) { wgrad_row3_body<NS>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base); return; }
-    }
-    if (p.flags & WG_FLAG_FAST2) wgrad_fast2_body<RT, CT, WR, WC, NS, PX>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base);
-    else if (p.flags & WG_FLAG_FASTGEO) wgrad_dma_body<RT, CT, WR, WC, NS, PX, 1>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base);
-    else if (p.flags & WG_FLAG_FASTGEO_S) wgrad_dma_body<RT, CT, WR, WC, NS, PX, 2>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base);
-    else wgrad_dma_body<RT, CT, WR, WC, NS, PX>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base);
+    wgrad_run_body<RT, CT, WR, WC, NS, PX>(p, bx, by, bz, smem, (uintptr_t)x_base, (uintptr_t)dy_base, (uintptr_t)dw_base);
 }
 
 // STAMP (tuning, policy.timeline): every work-group also records when it started and ended - stamps[blockIdx.x][8] =
@@ -923,11 +811,7 @@ int launch_wd_group(const WgParams* d_tab, const WgGroupBlk* d_blk, int per_xcd,
                     const void* dy_base2 = nullptr, void* dw_base2 = nullptr, unsigned long long* stamps = nullptr) {
     using C = WdCfg<RT, CT, WR, WC, NS, PX>;
     constexpr int LDS = (RT == 64 && CT == 64 && PX == 64 && Row3Cfg::lds_bytes(NS) > C::LDS_BYTES) ? Row3Cfg::lds_bytes(NS) : C::LDS_BYTES;
-    static std::atomic<unsigned long long> attr_done{0};
-    static std::mutex attr_mu;
-    once_per_device(attr_done, attr_mu, [] {
-        (void)hipFuncSetAttribute((const void*)wgrad_dma_group_kernel<RT, CT, WR, WC, NS, PX, STAMP>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    });
+    max_dynamic_lds<wgrad_dma_group_kernel<RT, CT, WR, WC, NS, PX, STAMP>>(LDS);
     hipLaunchKernelGGL((wgrad_dma_group_kernel<RT, CT, WR, WC, NS, PX, STAMP>), dim3(8 * per_xcd * (d_tab2 ? 2 : 1)), dim3(256), LDS, stream, d_tab, d_blk,
                        (uint32_t)per_xcd, (const char*)x_base, (const char*)dy_base, (char*)dw_base, d_tab2, d_blk2, (const char*)x_base2,
                        (const char*)dy_base2, (char*)dw_base2, stamps);
@@ -942,11 +826,7 @@ int launch_wd(WgParams& p, hipStream_t stream) {
     const int Rdim = swap ? p.Ci : p.Co, Cdim = swap ? p.Co : p.Ci;
     p.r_tiles = (Rdim + RT - 1) / RT;
     p.c_tiles = (Cdim + CT - 1) / CT;
-    static std::atomic<unsigned long long> attr_done{0};
-    static std::mutex attr_mu;
-    once_per_device(attr_done, attr_mu, [] {
-        (void)hipFuncSetAttribute((const void*)wgrad_dma_kernel<RT, CT, WR, WC, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    });
+    max_dynamic_lds<wgrad_dma_kernel<RT, CT, WR, WC, NS>>(LDS);
     dim3 grid(p.r_tiles * p.c_tiles, p.total_taps, p.ksplit);
     hipLaunchKernelGGL((wgrad_dma_kernel<RT, CT, WR, WC, NS>), grid, dim3(256), LDS, stream, p);
     return udapose_check_launch();
@@ -1003,6 +883,22 @@ static bool wg_row3_ok(const WgParams& p, const Policy& pol) {
            p.Ci % 64 == 0 && p.Co % 64 == 0;
 }
 
+// the loader of a problem: sets or clears WG_FLAG_FASTGEO, WG_FLAG_FAST2 and WG_FLAG_FASTGEO_S (dma: an LDS-DMA tile, the only home of the strided one)
+static void wg_classify(WgParams& p, const Policy& pol, bool dma) {
+    if (wg_fastgeo_ok(p, pol)) p.flags |= WG_FLAG_FASTGEO; else p.flags &= ~WG_FLAG_FASTGEO;
+    if ((p.flags & WG_FLAG_FASTGEO) && !(p.flags & WG_FLAG_ROW3) && pol.wgrad_fastgeo >= 2 && p.M % 64 == 0) p.flags |= WG_FLAG_FAST2; else p.flags &= ~WG_FLAG_FAST2;
+    if (dma && wg_fastgeo_strided_ok(p, pol)) p.flags |= WG_FLAG_FASTGEO_S; else p.flags &= ~WG_FLAG_FASTGEO_S;
+}
+
+// split the pixel reduction (ms_total stages) until ~512 work-groups exist (2 per CU), keeping >= 16 (tile 0, 128x128) / 4 (64x64) stages
+// per split, below `cap` splits
+static int wg_split_count(long tiles, int ms_total, int tile, int cap) {
+    const int min_stages = tile == 0 ? 16 : 4;
+    int ks = 1;
+    while (ks < cap && tiles * ks < 512 && ms_total / (ks * 2) >= min_stages) ks *= 2;
+    return ks;
+}
+
 // tile ids: 0 = 128x128, 1 = 64x64, 2 = 64x32 (Ci==8 stem), 3 = 32x128 (narrow-row: head)
 int wgrad_pick_tile(int Rdim, int Cdim, int smallc, const Policy& pol) {
     if (smallc) return 2;
@@ -1033,11 +929,8 @@ int wgrad_launch(WgParams& p, int tile, int accumulate, hipStream_t stream, cons
                        (smallc ? p.total_taps / 4 : p.total_taps);
     const bool dma = !smallc && (tile == 0 || tile == 1) && (p.Ci % 64 == 0) && (p.Co % 64 == 0);
     const int ms_total = dma ? (p.M + 63) / 64 : (p.M + 31) / 32;
-    // split the pixel reduction until ~512 work-groups exist (2 per CU), keeping >= 16 (128x128) / 4 (64x64) stages per
-    // split; every extra split adds one fp32 atomic pass over the weight tensor (chip-wide atomic rate 1.3 TB/s)
-    const int min_stages = tile == 0 ? 16 : 4;
-    int ks = 1;
-    while (tiles * ks < 512 && ms_total / (ks * 2) >= min_stages) ks *= 2;
+    // (every extra split adds one fp32 atomic pass over the weight tensor: chip-wide atomic rate 1.3 TB/s)
+    int ks = wg_split_count(tiles, ms_total, tile, 1 << 30);
     if (pol.wgrad_ksplit > 0) { ks = pol.wgrad_ksplit; while (ks > 1 && ms_total / ks < 1) ks /= 2; }
     p.ksplit = ks;
     p.part_stride = 0;
@@ -1047,9 +940,7 @@ int wgrad_launch(WgParams& p, int tile, int accumulate, hipStream_t stream, cons
         const size_t n = (size_t)Rdim * p.wtaps * Cdim;
         if (pw_zero(stream, p.dw, n * sizeof(float)) != UDAPOSE_OK) return UDAPOSE_ERR_LAUNCH;
     }
-    if (wg_fastgeo_ok(p, pol)) p.flags |= WG_FLAG_FASTGEO; else p.flags &= ~WG_FLAG_FASTGEO;
-    if ((p.flags & WG_FLAG_FASTGEO) && !(p.flags & WG_FLAG_ROW3) && pol.wgrad_fastgeo >= 2 && p.M % 64 == 0) p.flags |= WG_FLAG_FAST2; else p.flags &= ~WG_FLAG_FAST2;
-    if (dma && wg_fastgeo_strided_ok(p, pol)) p.flags |= WG_FLAG_FASTGEO_S; else p.flags &= ~WG_FLAG_FASTGEO_S;
+    wg_classify(p, pol, dma);
     if (dma) return tile == 0 ? launch_wd<128, 128, 2, 2, 2>(p, stream) : launch_wd<64, 64, 2, 2, 4>(p, stream);
     switch (tile) {
         case 0: return launch_wg<128, 128, 2, 2>(p, stream);
@@ -1086,9 +977,7 @@ int wgrad_group_plan(WgParams& p, int accumulate, int stages_per_block, const Po
     p.part_stride = 0;              // (the caller turns a split problem into the partial-tile form: net.hip build_wg_group)
     p.msteps_per_split = (ms_total + ks - 1) / ks;
     if (ks > 1 || accumulate) p.flags |= WG_FLAG_ATOMIC; else p.flags &= ~WG_FLAG_ATOMIC;
-    if (wg_fastgeo_ok(p, pol)) p.flags |= WG_FLAG_FASTGEO; else p.flags &= ~WG_FLAG_FASTGEO;
-    if ((p.flags & WG_FLAG_FASTGEO) && !(p.flags & WG_FLAG_ROW3) && pol.wgrad_fastgeo >= 2 && p.M % 64 == 0) p.flags |= WG_FLAG_FAST2; else p.flags &= ~WG_FLAG_FAST2;
-    if (wg_fastgeo_strided_ok(p, pol)) p.flags |= WG_FLAG_FASTGEO_S; else p.flags &= ~WG_FLAG_FASTGEO_S;
+    wg_classify(p, pol, true);
     return tile;
 }
 
@@ -1118,9 +1007,7 @@ int wgrad_parts_plan(int M, int Ci, int Co, int total_taps, int* tile_out) {
     const int RT = tile == 0 ? 128 : 64;
     const long tiles = (long)((Co + RT - 1) / RT) * ((Ci + RT - 1) / RT) * total_taps;
     const int ms_total = (M + 63) / 64;
-    const int min_stages = tile == 0 ? 16 : 4;
-    int ks = 1;
-    while (ks < 64 && tiles * ks < 512 && ms_total / (ks * 2) >= min_stages) ks *= 2;
+    const int ks = wg_split_count(tiles, ms_total, tile, 64);
     if (tile_out) *tile_out = tile;
     return ks;
 }
