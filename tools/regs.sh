@@ -1,9 +1,11 @@
 # Dev tool: registers, scratch, LDS, instruction / MFMA counts and waves per SIMD of every kernel of csrc sources, from the device-only assembly.
 #   bash tools/regs.sh patchconv [-DUDAPOSE_ELEM_F16]     one source of this tree
 #   bash tools/regs.sh --ab [SOURCE...]                    parent (tools/_ab/oldtree, a git worktree of the parent commit) against this tree, both
-#                                                          builds: one line per kernel "parent -> tree" with identical / differs, then the conditions
-#                                                          (same kernel names, scratch stays 0, LDS and MFMA counts unchanged, no fewer waves per SIMD).
-#                                                          Default sources: the four convolution files and affine, fda, refine.  The parent's assembly is
+#                                                          builds.  Every source is first compared as a whole file (apart from the __hip_cuid_ lines):
+#                                                          "whole file identical"; only a file that differs gets one line per kernel "parent -> tree"
+#                                                          with identical / differs.  Then the conditions (same kernel names, scratch stays 0, LDS and
+#                                                          MFMA counts unchanged, no fewer waves per SIMD).  Default sources: the four convolution files
+#                                                          and affine, fda, refine.  The parent's assembly is
 #                                                          kept under /tmp/regs/parent and reused; remove that directory after moving the worktree.
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 asm() {     # asm TREE OUTDIR SOURCE FLAGS...: device-only assembly of one source
@@ -56,11 +58,9 @@ bad = 0
 for src in sys.argv[2:]:
     for b in ('bf16', 'fp16'):
         old, new = kernels('/tmp/regs/parent/%s/%s.s' % (b, src)), kernels('/tmp/regs/tree/%s/%s.s' % (b, src))
-        if src in ('affine', 'fda', 'refine'):      # whole file, apart from the per-file __hip_cuid_ symbol lines
-            strip = lambda p: [l for l in open(p) if '__hip_cuid_' not in l]
-            same = strip('/tmp/regs/parent/%s/%s.s' % (b, src)) == strip('/tmp/regs/tree/%s/%s.s' % (b, src))
-            print('## %s %s: whole file %s' % (src, b, 'identical' if same else 'DIFFERS'))
-            bad += not same
+        strip = lambda p: [l for l in open(p) if '__hip_cuid_' not in l]      # whole file, apart from the per-file __hip_cuid_ symbol lines
+        if strip('/tmp/regs/parent/%s/%s.s' % (b, src)) == strip('/tmp/regs/tree/%s/%s.s' % (b, src)):
+            print('## %s %s: whole file identical' % (src, b))
             continue
         print('## %s %s: %d kernels; names %s' % (src, b, len(new), 'equal' if set(old) == set(new) else 'DIFFER'))
         bad += set(old) != set(new)

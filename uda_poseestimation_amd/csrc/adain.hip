@@ -2,45 +2,10 @@
 // out = alpha*((c-mu_c)/sd_c*sd_s+mu_s) + (1-alpha)*c with per-(n,c) statistics over H*W.  HBM-bound: the algorithmic minimum
 // is content + style in, result out (201 MB for [32,512,32,32] fp32, 100 MB in bf16).
 #include "style.h"
+#include "storage8.h"
 
 namespace {
 constexpr int TPB = 256;
-
-// 8 consecutive channel values <-> fp32 registers, bf16 or fp32 storage (fp32: the reference's own precision for the style
-// path, train_human.py:347-356 runs it outside autocast)
-template <typename T> __device__ __forceinline__ void ld8(const T* p, float (&o)[8]);
-template <> __device__ __forceinline__ void ld8<elem_t>(const elem_t* p, float (&o)[8]) {
-    const elem8 v = *(const elem8*)p;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (float)v[e];
-}
-template <> __device__ __forceinline__ void ld8<float>(const float* p, float (&o)[8]) {
-    const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o[e] = a[e]; o[4 + e] = b[e]; }
-}
-template <> __device__ __forceinline__ void ld8<sp32>(const sp32* p, float (&o)[8]) {      // f16x2 split storage (common.h)
-    const char* c = (const char*)p;
-    sp_join8(*(const half8*)c, *(const half8*)(c + 16), o);
-}
-template <typename T> __device__ __forceinline__ void st8(T* p, const float (&v)[8]);
-template <> __device__ __forceinline__ void st8<sp32>(sp32* p, const float (&v)[8]) {
-    half8 h, l;
-    sp_split8(v, h, l);
-    char* c = (char*)p;
-    *(half8*)c = h;
-    *(half8*)(c + 16) = l;
-}
-template <> __device__ __forceinline__ void st8<elem_t>(elem_t* p, const float (&v)[8]) {
-    elem8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (elem_t)v[e];
-    *(elem8*)p = o;
-}
-template <> __device__ __forceinline__ void st8<float>(float* p, const float (&v)[8]) {
-    *(f32x4*)p = (f32x4){v[0], v[1], v[2], v[3]};
-    *(f32x4*)(p + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-}
 
 // One work-group of 1024 threads (16 waves: the CU's memory pipeline needs that many loads in flight - the 256-thread form
 // of round 1 moved 2.1 TB/s) per (image, 64-channel slab): 8 channel groups x 128 pixel lanes, every lane moves 16 (bf16) or 32
@@ -54,24 +19,6 @@ template <> __device__ __forceinline__ void st8<float>(float* p, const float (&v
 // The one-pass form about zero loses mean^2 / var of its precision (a channel at 100 +- 0.01 came out with a non-positive variance
 // and NaN outputs); about a pivot inside the data the loss is at most 1 + max|x - mean|^2 / var, whatever the mean.
 constexpr int ATPB = 1024, APL = ATPB / 8, CACHE = 8;
-
-// the cached pixels stay in their STORAGE form (4 registers per 8 bf16 values, 8 per 8 floats)
-template <typename T> struct Raw8;
-template <> struct Raw8<elem_t> { elem8 v; };
-template <> struct Raw8<float> { f32x4 a, b; };
-template <> struct Raw8<sp32> { half8 h, l; };
-__device__ __forceinline__ void ldraw(const sp32* p, Raw8<sp32>& r) { const char* c = (const char*)p; r.h = *(const half8*)c; r.l = *(const half8*)(c + 16); }
-__device__ __forceinline__ void unraw(const Raw8<sp32>& r, float (&o)[8]) { sp_join8(r.h, r.l, o); }
-__device__ __forceinline__ void ldraw(const elem_t* p, Raw8<elem_t>& r) { r.v = *(const elem8*)p; }
-__device__ __forceinline__ void ldraw(const float* p, Raw8<float>& r) { r.a = *(const f32x4*)p; r.b = *(const f32x4*)(p + 4); }
-__device__ __forceinline__ void unraw(const Raw8<elem_t>& r, float (&o)[8]) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (float)r.v[e];
-}
-__device__ __forceinline__ void unraw(const Raw8<float>& r, float (&o)[8]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o[e] = r.a[e]; o[4 + e] = r.b[e]; }
-}
 
 template <typename T>
 __global__ __launch_bounds__(ATPB) void adain_k(const T* __restrict__ content, const T* __restrict__ style, T* __restrict__ out, int HWc, int HWs,

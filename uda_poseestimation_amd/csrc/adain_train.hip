@@ -10,27 +10,12 @@
 // weight-gradient kernels on it with per-split partial tiles that one launch adds in split order: every reduction here is
 // bit-reproducible (no atomics in arrival order).
 #include "style.h"
+#include "storage8.h"
 
 namespace {
 constexpr int TPB = 256;
 
-inline int grid_for(size_t n) {
-    size_t b = (n + TPB - 1) / TPB;
-    return (int)(b > 65535u * 8 ? 65535u * 8 : (b ? b : 1));
-}
-
-__device__ __forceinline__ void ld8e(const elem_t* p, float (&o)[8]) {
-    const elem8 v = *(const elem8*)p;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (float)v[e];
-}
-__device__ __forceinline__ void st8e(elem_t* p, const float (&v)[8]) {
-    elem8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (elem_t)v[e];
-    *(elem8*)p = o;
-}
-__device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+constexpr size_t GRID_CAP = 65535u * 8;      // blocks of a grid-stride sweep
 
 // padded rows (of Hl + 2) that land on logical row l after ReflectionPad2d(1): l + 1, plus 0 when l == 1, plus Hl + 1 when l == Hl - 2
 __device__ __forceinline__ int pad_sources(int l, int Hl, int (&r)[3]) {
@@ -46,11 +31,8 @@ __global__ void reflect_gather_k(const elem_t* __restrict__ x, elem_t* __restric
     const int G = C >> 3, Hl = H << up, Wl = W << up, Hp = Hl + 2, Wp = Wl + 2;
     const size_t total = (size_t)N * Hp * Wp * G;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
-        const int g = (int)(i % G);
-        size_t r = i / G;
-        const int px = (int)(r % Wp); r /= Wp;
-        const int py = (int)(r % Hp);
-        const int n = (int)(r / Hp);
+        int n, py, px, g;
+        nhwg_of(i, G, Hp, Wp, n, py, px, g);
         const int sy = reflect1(py - 1, Hl) >> up, sx = reflect1(px - 1, Wl) >> up;
         *(elem8*)(P + i * 8) = *(const elem8*)(x + (((size_t)n * H + sy) * W + sx) * C + g * 8);
     }
@@ -71,11 +53,8 @@ __global__ void fold_k(const elem_t* __restrict__ dP, int up, const elem_t* __re
     const float kc = t ? term_scale * gs_c[0] * c_scale : 0.f;
     const float HW = (float)H * (float)W;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
-        const int g = (int)(i % G);
-        size_t r = i / G;
-        const int xw = (int)(r % W); r /= W;
-        const int y = (int)(r % H);
-        const int n = (int)(r / H);
+        int n, y, xw, g;
+        nhwg_of(i, G, H, W, n, y, xw, g);
         float acc[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] = 0.f;
@@ -90,7 +69,7 @@ __global__ void fold_k(const elem_t* __restrict__ dP, int up, const elem_t* __re
                     for (int ri = 0; ri < nr; ++ri)
                         for (int ci = 0; ci < nc; ++ci) {
                             float v[8];
-                            ld8e(dP + ((img + rows[ri]) * Wp + cols[ci]) * C + g * 8, v);
+                            ld8(dP + ((img + rows[ri]) * Wp + cols[ci]) * C + g * 8, v);
 #pragma unroll
                             for (int e = 0; e < 8; ++e) acc[e] += v[e];
                         }
@@ -98,7 +77,7 @@ __global__ void fold_k(const elem_t* __restrict__ dP, int up, const elem_t* __re
             }
         }
         float xv[8];
-        if (x) ld8e(x + i * 8, xv);
+        if (x) ld8(x + i * 8, xv);
         if (stats) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -109,7 +88,7 @@ __global__ void fold_k(const elem_t* __restrict__ dP, int up, const elem_t* __re
         }
         if (t) {
             float tv[8];
-            ld8e(t + i * 8, tv);
+            ld8(t + i * 8, tv);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] += kc * (xv[e] - tv[e]);
         }
@@ -124,7 +103,7 @@ __global__ void fold_k(const elem_t* __restrict__ dP, int up, const elem_t* __re
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] = xv[e] > 0.f ? acc[e] : 0.f;
         }
-        st8e(dx + i * 8, acc);
+        st8(dx + i * 8, acc);
     }
 }
 
@@ -136,11 +115,8 @@ __global__ void maxpool2x2_ceil_bwd_k(const elem_t* __restrict__ x, const elem_t
     const int G = C >> 3, Ho = (H + 1) / 2, Wo = (W + 1) / 2;
     const size_t total = (size_t)N * H * W * G;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
-        const int g = (int)(i % G);
-        size_t r = i / G;
-        const int ix = (int)(r % W); r /= W;
-        const int iy = (int)(r % H);
-        const int n = (int)(r / H);
+        int n, iy, ix, g;
+        nhwg_of(i, G, H, W, n, iy, ix, g);
         const int oy = iy >> 1, ox = ix >> 1, me = (iy & 1) * 2 + (ix & 1);
         float best[8];
         int arg[8];
@@ -151,7 +127,7 @@ __global__ void maxpool2x2_ceil_bwd_k(const elem_t* __restrict__ x, const elem_t
             const int h = oy * 2 + (k >> 1), w = ox * 2 + (k & 1);
             if (h >= H || w >= W) continue;
             float v[8];
-            ld8e(x + (((size_t)n * H + h) * W + w) * C + g * 8, v);
+            ld8(x + (((size_t)n * H + h) * W + w) * C + g * 8, v);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 if (arg[e] < 0 || v[e] > best[e] || v[e] != v[e]) { best[e] = v[e]; arg[e] = k; }
@@ -159,10 +135,10 @@ __global__ void maxpool2x2_ceil_bwd_k(const elem_t* __restrict__ x, const elem_t
             }
         }
         float d[8], o[8];
-        ld8e(dy + (((size_t)n * Ho + oy) * Wo + ox) * C + g * 8, d);
+        ld8(dy + (((size_t)n * Ho + oy) * Wo + ox) * C + g * 8, d);
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = (arg[e] == me && (!mask || mine[e] > 0.f)) ? d[e] : 0.f;
-        st8e(dx + i * 8, o);
+        st8(dx + i * 8, o);
     }
 }
 
@@ -180,7 +156,7 @@ __global__ __launch_bounds__(TPB) void colsum_part_k(const elem_t* __restrict__ 
     if (rl < lanes)
         for (int m = r0 + rl; m < r1; m += lanes) {
             float v[8];
-            ld8e(dy + (size_t)m * C + g * 8, v);
+            ld8(dy + (size_t)m * C + g * 8, v);
 #pragma unroll
             for (int e = 0; e < 8; ++e) s[e] += v[e];
         }
@@ -223,32 +199,20 @@ __global__ __launch_bounds__(TPB) void mse_part_k(const elem_t* __restrict__ a, 
     float s = 0.f;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < n8; i += (size_t)MSE_BLOCKS * TPB) {
         float va[8], vb[8];
-        ld8e(a + i * 8, va);
-        ld8e(b + i * 8, vb);
+        ld8(a + i * 8, va);
+        ld8(b + i * 8, vb);
 #pragma unroll
         for (int e = 0; e < 8; ++e) { const float d = va[e] - vb[e]; s += d * d; }
     }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < TPB / 64; ++w) t += red[w];
-        part[blockIdx.x] = t;
-    }
+    const float t = block_sum<TPB / 64>(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 __global__ __launch_bounds__(TPB) void mse_final_k(const float* __restrict__ part, float* __restrict__ out, float inv_n) {
     __shared__ float red[TPB / 64];
     float s = 0.f;
     for (int i = threadIdx.x; i < MSE_BLOCKS; i += TPB) s += part[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < TPB / 64; ++w) t += red[w];
-        out[0] = t * inv_n;
-    }
+    const float t = block_sum<TPB / 64>(s, red);
+    if (threadIdx.x == 0) out[0] = t * inv_n;
 }
 
 // style loss term from the statistics [R = N*C][4] = (m, sd, m_t, sd_t): out (+)= (sum (m - m_t)^2 + (sd - sd_t)^2) / R
@@ -260,14 +224,8 @@ __global__ __launch_bounds__(TPB) void style_loss_k(const float* __restrict__ st
         const float dm = st[0] - st[2], ds = st[1] - st[3];
         s += dm * dm + ds * ds;
     }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < TPB / 64; ++w) t += red[w];
-        out[0] = (accumulate ? out[0] : 0.f) + t / (float)R;
-    }
+    const float t = block_sum<TPB / 64>(s, red);
+    if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.f) + t / (float)R;
 }
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -317,7 +275,7 @@ int reflect_fold(hipStream_t s, const elem_t* dP, int up, const elem_t* x, int m
     if (dP && ((H << up) < 2 || (W << up) < 2)) return UDAPOSE_ERR_ARG;
     if ((mask || stats || t) && !x) return UDAPOSE_ERR_ARG;
     if ((stats && (!gs_s || H * W < 2)) || (t && !gs_c) || (add_nchw && (add_c < 1 || add_c > C))) return UDAPOSE_ERR_ARG;
-    hipLaunchKernelGGL(fold_k, dim3(grid_for((size_t)N * H * W * (C / 8))), dim3(TPB), 0, s, dP, up, x, mask, stats, gs_s, t, gs_c, c_scale, add_nchw,
+    hipLaunchKernelGGL(fold_k, dim3(grid_for((size_t)N * H * W * (C / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, dP, up, x, mask, stats, gs_s, t, gs_c, c_scale, add_nchw,
                        add_c, dx, N, H, W, C, term_scale);
     return udapose_check_launch();
 }
@@ -336,7 +294,7 @@ int conv_wgrad_reflect(hipStream_t s, const ConvGeom& g, const elem_t* dy, const
     const ConvGeom p = padded_geom(g);
     elem_t* P = (elem_t*)ws;
     float* parts = (float*)((char*)ws + padded_bytes(g));
-    hipLaunchKernelGGL(reflect_gather_k, dim3(grid_for((size_t)p.N * p.Hi * p.Wi * (p.Ci / 8))), dim3(TPB), 0, s, x, P, g.N, g.Hi, g.Wi, g.Ci,
+    hipLaunchKernelGGL(reflect_gather_k, dim3(grid_for((size_t)p.N * p.Hi * p.Wi * (p.Ci / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, x, P, g.N, g.Hi, g.Wi, g.Ci,
                        g.upsample);
     int rc = udapose_check_launch();
     if (rc != UDAPOSE_OK) return rc;
@@ -345,13 +303,13 @@ int conv_wgrad_reflect(hipStream_t s, const ConvGeom& g, const elem_t* dy, const
     if (rc != UDAPOSE_OK) return rc;
     rc = wgrad_launch_parts(wp, parts, s);
     if (rc != UDAPOSE_OK) return rc;
-    hipLaunchKernelGGL(wsplit_sum_k, dim3(grid_for((size_t)co_valid * g.Ci * 9)), dim3(TPB), 0, s, parts, dw, wp.ksplit, g.Co, 9, g.Ci, co_valid, out_scale);
+    hipLaunchKernelGGL(wsplit_sum_k, dim3(grid_for((size_t)co_valid * g.Ci * 9, TPB, GRID_CAP)), dim3(TPB), 0, s, parts, dw, wp.ksplit, g.Co, 9, g.Ci, co_valid, out_scale);
     return udapose_check_launch();
 }
 
 int maxpool2x2_ceil_bwd(hipStream_t s, const elem_t* x, const elem_t* dy, elem_t* dx, int N, int H, int W, int C, int mask) {
     if (!x || !dy || !dx || C % 8 || N < 1 || H < 1 || W < 1) return UDAPOSE_ERR_ARG;
-    hipLaunchKernelGGL(maxpool2x2_ceil_bwd_k, dim3(grid_for((size_t)N * H * W * (C / 8))), dim3(TPB), 0, s, x, dy, dx, N, H, W, C, mask);
+    hipLaunchKernelGGL(maxpool2x2_ceil_bwd_k, dim3(grid_for((size_t)N * H * W * (C / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, x, dy, dx, N, H, W, C, mask);
     return udapose_check_launch();
 }
 

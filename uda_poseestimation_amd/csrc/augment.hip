@@ -49,13 +49,8 @@ __global__ void aug_gray_mean_k(const unsigned char* __restrict__ img, const int
     const unsigned char* p = img + (size_t)n * HW * 3;
     unsigned long long s = 0;
     for (int i = threadIdx.x; i < HW; i += TPB) s += (unsigned long long)lum(p[(size_t)i * 3], p[(size_t)i * 3 + 1], p[(size_t)i * 3 + 2]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    const unsigned long long t = block_sum<TPB / 64>(s, red);
     if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int i = 0; i < TPB / 64; ++i) t += red[i];
         // int(t / HW + 0.5) with t / HW in double exactly as ImageStat computes it (sum / count), then truncation
         mean[n] = (int)((double)t / (double)HW + 0.5);
     }

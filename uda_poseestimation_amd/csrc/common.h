@@ -172,13 +172,37 @@ __device__ __forceinline__ void hm_block_best(float& bv, int& bi, float* sv, int
     bv = v; bi = i;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// The wave sum (float, double, unsigned long long): six xor steps, every lane returns the wave's sum.  Lane 0 adds the same pairs in the same
+// order as lane 0 of a __shfl_down tree (at each step lane i < offset holds a_i + a_(i + offset) in both).
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+// The block sum in a fixed order: wave_sum, one LDS slot per wave, then the WAVES waves' sums added to zero in wave order,
+// ((0 + w0) + w1) + ...; every thread returns the block's sum.  red: WAVES entries of LDS.  Barriers as hm_block_best: it opens with one
+// (red may still be read from the previous reduction), so every thread of the block must reach the call, and the caller may rely on that
+// barrier alone - none follows the last read of red.
+template <int WAVES, typename T>
+__device__ __forceinline__ T block_sum(T v, T* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T t = 0;
+    for (int w = 0; w < WAVES; ++w) t += red[w];
+    return t;
+}
+
+// ReflectionPad2d(1)'s source index of position i (in [-1, n]) on an axis of n >= 2
+__device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+// sign(v) with sign(0) = 0 (NaN: 0)
+__device__ __forceinline__ float sign_or_0(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+
+// Blocks of a grid-stride launch over n items at `per` items per block: at least 1, at most `cap` (the caps decide speed: every file keeps its own)
+constexpr size_t GRID_NO_CAP = 0x7fffffff;
+static inline int grid_for(size_t n, int per, size_t cap) {
+    const size_t b = (n + per - 1) / per;
+    return (int)(b > cap ? cap : (b ? b : 1));
 }

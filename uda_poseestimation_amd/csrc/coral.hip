@@ -202,7 +202,7 @@ __global__ __launch_bounds__(FT) void coral_finish_k(const double* __restrict__ 
         // (as products of sum and difference: exactly 0 for equal parts, whatever the compiler contracts into an fma)
         acc += (gc[0] - gc[1]) * (gc[0] + gc[1]) + (gc[3] - gc[2]) * (gc[3] + gc[2]);
     }
-    acc = wave_sum_d(acc);
+    acc = wave_sum(acc);
     if ((t & 63) == 0) red[t >> 6] = acc;
     __syncthreads();
     if (t == 0) {

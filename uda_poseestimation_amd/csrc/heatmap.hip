@@ -7,16 +7,6 @@
 namespace {
 constexpr int TPB = 256;
 
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-    v = wave_sum_d(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int i = 0; i < TPB / 64; ++i) t += red[i];
-    __syncthreads();
-    return t;
-}
-
 // rows[r] = 0.5 * w[r] * sum((p-g)^2) / HW           (JointsMSE 'none' rows; mean of rows = 'mean' loss)
 // rows[r] = m[r] * sum((s-t)^2) / HW                  (ConsLoss: mode 1)
 // `valid` (optional, ConsLoss(valid_mask=), loss.py:129-130): per-PIXEL selection [B][HW] shared by the Kc rows of an image;
@@ -41,7 +31,7 @@ __global__ void sqdiff_rows_k(const float* __restrict__ a, const float* __restri
     } else {
         for (int i = threadIdx.x; i < HW; i += TPB) { const float d = pa[i] - pb[i]; s += (double)(d * d); }
     }
-    const double t = block_sum_d(s, red);
+    const double t = block_sum<TPB / 64>(s, red);
     if (threadIdx.x == 0) {
         float f = half;
         if (w) f *= w[r];
@@ -55,7 +45,7 @@ __global__ void mean_rows_k(const float* __restrict__ rows, int R, float* __rest
     __shared__ double red[TPB / 64];
     double s = 0.0;
     for (int i = threadIdx.x; i < R; i += TPB) s += (double)rows[i];
-    const double t = block_sum_d(s, red);
+    const double t = block_sum<TPB / 64>(s, red);
     if (threadIdx.x == 0) out[0] = count ? (float)(t * HW / ((double)Kc * (double)count[0])) : (float)(t / R);
 }
 // count[0] = number of non-zero bytes of m[0..n)
@@ -63,7 +53,7 @@ __global__ void mask_count_k(const unsigned char* __restrict__ m, size_t n, floa
     __shared__ double red[TPB / 64];
     double s = 0.0;
     for (size_t i = threadIdx.x; i < n; i += TPB) s += m[i] ? 1.0 : 0.0;
-    const double t = block_sum_d(s, red);
+    const double t = block_sum<TPB / 64>(s, red);
     if (threadIdx.x == 0) count[0] = (float)t;
 }
 // da = gscale[0] * coef * f[r] * (a-b), f = w or mask (or 1).  E elements per thread and step: 4 (16-byte loads; the launcher sees to

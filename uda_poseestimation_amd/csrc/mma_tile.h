@@ -1,5 +1,5 @@
 // Device pieces shared by the convolution kernels (igemm.hip, wgrad.hip, patchconv.hip): each is stated here once.
-//   compile-time loops, counted vmcnt waits, the LDS-DMA instruction, the transposing-read fragment, the LDS chunk swizzle, reflection,
+//   compile-time loops, counted vmcnt waits, the LDS-DMA instruction, the transposing-read fragment, the LDS chunk swizzle,
 //   the f16x2 three-MFMA product, the row -> (n, i, j) -> output pixel maps of a tap plan, and the LDS ring of DMA stages.
 // Everything is __forceinline__ and takes the scalar fields it reads, never a whole parameter block.
 #pragma once
@@ -48,9 +48,6 @@ __device__ __forceinline__ elem8 tr_frag(const char* lo, const char* hi) {
 // XOR swizzle of the 16-byte chunk index inside a 128-byte LDS row: makes the ds_read_b128 fragment reads (lane l ->
 // row l&15, chunk l>>4) conflict-free (2 rows per 256-byte bank row; derivation in DESIGN.md)
 __device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
-
-// reflection padding of one coordinate (|overhang| < n)
-__device__ __forceinline__ int reflect1(int v, int n) { return v < 0 ? -v : (v >= n ? 2 * n - 2 - v : v); }
 
 // f16x2 product of one fragment pair (common.h): h.h into acc, the cross terms h.l + l.h (scaled by 2^11) into acc2
 __device__ __forceinline__ void sp_mfma3(const half8& ah, const half8& al, const half8& bh, const half8& bl, f32x4& acc, f32x4& acc2) {

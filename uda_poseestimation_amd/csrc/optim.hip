@@ -171,15 +171,6 @@ __global__ void scaler_update_k(float* __restrict__ state, float growth, float b
 struct ClipGroups { float* state[TAIL_GROUPS]; int begin[TAIL_GROUPS]; int end[TAIL_GROUPS]; };
 enum { CLIP_MAX_NORM = 0, CLIP_NORM = 1, CLIP_COEF = 2, CLIP_SAVED = 4 };
 
-// the block's sum in a fixed order: lane i += lane i + 32, 16, ... 1 inside each wave, then ((w0 + w1) + w2) + w3
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
-
 // partials[block] = sum over the block's chunk of fl32(g + g2)^2; the loads are grad_check_k's.  state != NULL: the loss scaler's found-inf check in
 // the same read (grad_check_k's test on the same values), so that an fp16 step reads its gradients once.
 __global__ __launch_bounds__(TPB) void grad_sumsq_k(MtTable t, float* __restrict__ state, long long g2, double* __restrict__ partials) {
@@ -213,7 +204,7 @@ __global__ __launch_bounds__(TPB) void grad_sumsq_k(MtTable t, float* __restrict
         acc += (double)v * (double)v;
     }
     if (state && bad) state[5] = 1.f;
-    const double s = block_sum(acc, lds);
+    const double s = block_sum<TPB / 64>(acc, lds);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
@@ -235,8 +226,7 @@ __global__ __launch_bounds__(TPB) void grad_clip_k(const double* __restrict__ pa
             for (int k = 0; k < 8; ++k) acc += v[k];
         }
         for (; i < G.end[g]; i += TPB) acc += partials[i];
-        const double S = block_sum(acc, lds);
-        __syncthreads();
+        const double S = block_sum<TPB / 64>(acc, lds);      // (opens with a barrier: lds is free again)
         if (threadIdx.x == 0) {          // (thread 0 alone reads the states it is about to write)
             const double gs = (double)G.state[g][4];
             total += gs * gs * S;

@@ -51,16 +51,6 @@ struct PtArgs {
     int HW, C, B, mode;
 };
 
-__device__ __forceinline__ float block_sum(float v) {
-    __shared__ float red[PT_THREADS / 64];
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = red[0];
-#pragma unroll
-    for (int w = 1; w < PT_THREADS / 64; ++w) t += red[w];
-    return t;
-}
 // the B partials of sample n, added in index order (a wave-uniform address: scalar loads)
 __device__ __forceinline__ float sum_partials(const float* part, int n, int B) {
     float t = 0.f;
@@ -68,7 +58,6 @@ __device__ __forceinline__ float sum_partials(const float* part, int n, int B) {
     return t;
 }
 __device__ __forceinline__ bool usable(float s) { return s > 0.f && s < __builtin_inff(); }        // (false for NaN)
-__device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 // the l2 displacement before the projection; ONE expression for the norm pass and the apply pass (the same bits in both)
 __device__ __forceinline__ float l2_disp(float x, float x0, float g, float c) { return __fmaf_rn(c, g, x - x0); }
 
@@ -106,7 +95,8 @@ __global__ __launch_bounds__(PT_THREADS) void perturb_sumsq_k(PtArgs a) {
             }
         }
     }
-    const float t = block_sum(acc);
+    __shared__ float red[PT_THREADS / 64];
+    const float t = block_sum<PT_THREADS / 64>(acc, red);
     if (threadIdx.x == 0) a.part_out[(size_t)n * a.B + b] = t;
 }
 
@@ -147,7 +137,7 @@ __global__ __launch_bounds__(PT_THREADS) void perturb_apply_k(PtArgs a) {
         for (int e = 0; e < V; ++e) {
             float o;
             if (!ok) o = xv[e];
-            else if (linf) o = zv[e] + fminf(fmaxf(__fmaf_rn(step, sgn(gv[e]), xv[e] - zv[e]), -eps), eps);
+            else if (linf) o = zv[e] + fminf(fmaxf(__fmaf_rn(step, sign_or_0(gv[e]), xv[e] - zv[e]), -eps), eps);
             else if (a.part_d) o = __fmaf_rn(f, l2_disp(xv[e], zv[e], gv[e], c), zv[e]);
             else o = __fmaf_rn(c, gv[e], xv[e]);            // the one-step form: x + eps * u
             ov[e] = clamp ? fminf(fmaxf(o, cl), ch) : o;

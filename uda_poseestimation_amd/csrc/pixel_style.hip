@@ -51,12 +51,6 @@ __device__ __forceinline__ Span span_of(const void* a, const void* b, int n, boo
 
 __device__ __forceinline__ float& lane_of(float4& v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(TPB) void pixel_clear_k(unsigned int* __restrict__ p, long long n) {
     const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
     if (i < n) p[i] = 0u;

@@ -4,51 +4,14 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "pointwise.h"
+#include "storage8.h"
 
 namespace {
 
 constexpr int TPB = 256;
-inline int nblk(size_t n, int per = TPB) { return (int)((n + per - 1) / per); }
+constexpr size_t GRID_CAP = 8192;      // blocks of a grid-stride sweep
 
 // ------------------------------------------------------------------ layout conversion
-// 8 consecutive activation values <-> fp32 registers, for bf16 or fp32 storage
-template <typename T> __device__ __forceinline__ void ld8(const T* p, float (&o)[8]);
-template <> __device__ __forceinline__ void ld8<elem_t>(const elem_t* p, float (&o)[8]) {
-    const elem8 v = *(const elem8*)p;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (float)v[e];
-}
-template <> __device__ __forceinline__ void ld8<float>(const float* p, float (&o)[8]) {
-    const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o[e] = a[e]; o[4 + e] = b[e]; }
-}
-template <> __device__ __forceinline__ void ld8<sp32>(const sp32* p, float (&o)[8]) {      // f16x2 split storage (common.h): 32 bytes = [8 h][8 l]
-    const char* c = (const char*)p;
-    sp_join8(*(const half8*)c, *(const half8*)(c + 16), o);
-}
-template <typename T> __device__ __forceinline__ void st8(T* p, const float (&v)[8]);
-template <> __device__ __forceinline__ void st8<sp32>(sp32* p, const float (&v)[8]) {
-    half8 h, l;
-    sp_split8(v, h, l);
-    char* c = (char*)p;
-    *(half8*)c = h;
-    *(half8*)(c + 16) = l;
-}
-template <typename T> __device__ __forceinline__ float ld1(const T* p, size_t i) { return (float)p[i]; }
-template <> __device__ __forceinline__ float ld1<sp32>(const sp32* p, size_t i) { return sp_load1(p, i); }
-template <typename T> __device__ __forceinline__ void st1(T* p, size_t i, float v) { p[i] = (T)v; }
-template <> __device__ __forceinline__ void st1<sp32>(sp32* p, size_t i, float v) { sp_store1(p, i, v); }
-template <> __device__ __forceinline__ void st8<elem_t>(elem_t* p, const float (&v)[8]) {
-    elem8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (elem_t)v[e];
-    *(elem8*)p = o;
-}
-template <> __device__ __forceinline__ void st8<float>(float* p, const float (&v)[8]) {
-    *(f32x4*)p = (f32x4){v[0], v[1], v[2], v[3]};
-    *(f32x4*)(p + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-}
 // 'strict' plans (net.hip): the f16x2 forward also leaves the fp16 tensors the 16-bit backward reads ("shadows").  One 16-byte store each:
 // an fp16 rounding of 8 fp32 values (the pre-BN y), and the split store whose h half is ALSO the fp16 shadow of z (returned for the mask)
 __device__ __forceinline__ void st8_f16(_Float16* p, const float (&v)[8]) {
@@ -877,14 +840,6 @@ __global__ __launch_bounds__(TPB) void bn_bwd_apply_pre_chunk_k(const DZ* __rest
 }
 
 // ------------------------------------------------------------------ max pooling (NHWC bf16)
-// 16-byte group i of an NHWC tensor with G groups per pixel -> (n, h, w, g)
-__device__ __forceinline__ void nhwg_of(size_t i, int G, int H, int W, int& n, int& h, int& w, int& g) {
-    g = (int)(i % G);
-    size_t r = i / G;
-    w = (int)(r % W); r /= W;
-    h = (int)(r % H);
-    n = (int)(r / H);
-}
 // The 3x3 stride-2 pad-1 window (ho, wo) of 8 channels: the maximum of tap(v) over the in-range taps and the winning tap (0..8, first
 // max in (kh,kw) scan order, a NaN wins: like ATen).  tap transforms a loaded value before it competes.
 template <typename T, typename F>
@@ -1031,21 +986,10 @@ __global__ __launch_bounds__(1024) void plane_sum_k(const float* __restrict__ x,
             for (int i = threadIdx.x; i < HW; i += 1024) s += (double)x[((size_t)n * C + c) * HW + i];
     }
     __shared__ double red[16];
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    const double t = block_sum<16>(s, red);
     if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < 16; ++i) t += red[i];
         out[c] = (beta != 0.f ? beta * out[c] : 0.f) + (float)t;
     }
-}
-
-inline int grid_for(size_t items) {
-    size_t b = (items + TPB - 1) / TPB;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
 }
 
 }  // namespace
@@ -1053,36 +997,36 @@ inline int grid_for(size_t items) {
 // ------------------------------------------------------------------ host launchers (internal C++ API; C-ABI wrappers in capi.hip)
 int pw_nchw_f32_to_nhwc_bf16(hipStream_t s, const float* src, elem_t* dst, int N, int C, int HW, int Cp) {
     if (Cp % 8) return UDAPOSE_ERR_ARG;
-    hipLaunchKernelGGL(nchw_f32_to_nhwc_k<elem_t>, dim3(grid_for((size_t)N * HW * (Cp / 8))), dim3(TPB), 0, s, src, dst, N, C, HW, Cp);
+    hipLaunchKernelGGL(nchw_f32_to_nhwc_k<elem_t>, dim3(grid_for((size_t)N * HW * (Cp / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, src, dst, N, C, HW, Cp);
     return udapose_check_launch();
 }
 int pw_nchw_f32_to_nhwc_f32(hipStream_t s, const float* src, float* dst, int N, int C, int HW, int Cp) {
     if (Cp % 8) return UDAPOSE_ERR_ARG;
-    hipLaunchKernelGGL(nchw_f32_to_nhwc_k<float>, dim3(grid_for((size_t)N * HW * (Cp / 8))), dim3(TPB), 0, s, src, dst, N, C, HW, Cp);
+    hipLaunchKernelGGL(nchw_f32_to_nhwc_k<float>, dim3(grid_for((size_t)N * HW * (Cp / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, src, dst, N, C, HW, Cp);
     return udapose_check_launch();
 }
 int pw_nchw_f32_to_nhwc_split(hipStream_t s, const float* src, void* dst, int N, int C, int HW, int Cp, void* dst16) {
     if (Cp % 8) return UDAPOSE_ERR_ARG;
     if (dst16)      // ('strict' plans: the fp16 image for the 16-bit backward in the same pass)
-        hipLaunchKernelGGL((nchw_f32_to_nhwc_k<sp32, true>), dim3(grid_for((size_t)N * HW * (Cp / 8))), dim3(TPB), 0, s, src, (sp32*)dst, N, C, HW, Cp,
+        hipLaunchKernelGGL((nchw_f32_to_nhwc_k<sp32, true>), dim3(grid_for((size_t)N * HW * (Cp / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, src, (sp32*)dst, N, C, HW, Cp,
                            (_Float16*)dst16);
     else
-        hipLaunchKernelGGL(nchw_f32_to_nhwc_k<sp32>, dim3(grid_for((size_t)N * HW * (Cp / 8))), dim3(TPB), 0, s, src, (sp32*)dst, N, C, HW, Cp);
+        hipLaunchKernelGGL(nchw_f32_to_nhwc_k<sp32>, dim3(grid_for((size_t)N * HW * (Cp / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, src, (sp32*)dst, N, C, HW, Cp);
     return udapose_check_launch();
 }
 // src_is_f32: 0 = element type, 1 = fp32, 2 = f16x2 split
 int pw_nhwc_to_nchw_f32(hipStream_t s, const void* src, int src_is_f32, float* dst, int N, int C, int HW, int Cs, const float* lo, const float* hi) {
     if (src_is_f32 == 2)
-        hipLaunchKernelGGL(nhwc_to_nchw_f32_k<sp32>, dim3(grid_for((size_t)N * HW)), dim3(TPB), 0, s, (const sp32*)src, dst, N, C, HW, Cs, lo, hi);
+        hipLaunchKernelGGL(nhwc_to_nchw_f32_k<sp32>, dim3(grid_for((size_t)N * HW, TPB, GRID_CAP)), dim3(TPB), 0, s, (const sp32*)src, dst, N, C, HW, Cs, lo, hi);
     else if (src_is_f32)
-        hipLaunchKernelGGL(nhwc_to_nchw_f32_k<float>, dim3(grid_for((size_t)N * HW)), dim3(TPB), 0, s, (const float*)src, dst, N, C, HW, Cs, lo, hi);
+        hipLaunchKernelGGL(nhwc_to_nchw_f32_k<float>, dim3(grid_for((size_t)N * HW, TPB, GRID_CAP)), dim3(TPB), 0, s, (const float*)src, dst, N, C, HW, Cs, lo, hi);
     else
-        hipLaunchKernelGGL(nhwc_to_nchw_f32_k<elem_t>, dim3(grid_for((size_t)N * HW)), dim3(TPB), 0, s, (const elem_t*)src, dst, N, C, HW, Cs, lo, hi);
+        hipLaunchKernelGGL(nhwc_to_nchw_f32_k<elem_t>, dim3(grid_for((size_t)N * HW, TPB, GRID_CAP)), dim3(TPB), 0, s, (const elem_t*)src, dst, N, C, HW, Cs, lo, hi);
     return udapose_check_launch();
 }
 int pw_cast_f32_bf16(hipStream_t s, const float* src, elem_t* dst, size_t n) {
     if (n % 8) return UDAPOSE_ERR_ARG;
-    hipLaunchKernelGGL(cast_f32_bf16_k, dim3(grid_for(n / 8)), dim3(TPB), 0, s, src, dst, n / 8);
+    hipLaunchKernelGGL(cast_f32_bf16_k, dim3(grid_for(n / 8, TPB, GRID_CAP)), dim3(TPB), 0, s, src, dst, n / 8);
     return udapose_check_launch();
 }
 int pw_transpose_cast(hipStream_t s, const float* src, elem_t* dst, int A, int T, int B) {
@@ -1110,12 +1054,12 @@ __global__ void split_to_f32_k(const sp32* src, float* dst, size_t n8) {
 }
 int pw_f32_to_split(hipStream_t s, const float* src, void* dst, size_t n) {
     if (n % 8) return UDAPOSE_ERR_ARG;
-    hipLaunchKernelGGL(f32_to_split_k, dim3(grid_for(n / 8)), dim3(TPB), 0, s, src, (sp32*)dst, n / 8);
+    hipLaunchKernelGGL(f32_to_split_k, dim3(grid_for(n / 8, TPB, GRID_CAP)), dim3(TPB), 0, s, src, (sp32*)dst, n / 8);
     return udapose_check_launch();
 }
 int pw_split_to_f32(hipStream_t s, const void* src, float* dst, size_t n) {
     if (n % 8) return UDAPOSE_ERR_ARG;
-    hipLaunchKernelGGL(split_to_f32_k, dim3(grid_for(n / 8)), dim3(TPB), 0, s, (const sp32*)src, dst, n / 8);
+    hipLaunchKernelGGL(split_to_f32_k, dim3(grid_for(n / 8, TPB, GRID_CAP)), dim3(TPB), 0, s, (const sp32*)src, dst, n / 8);
     return udapose_check_launch();
 }
 int pw_transpose_split(hipStream_t s, const float* src, void* dst, int A, int T, int B) {
@@ -1123,7 +1067,7 @@ int pw_transpose_split(hipStream_t s, const float* src, void* dst, int A, int T,
     return udapose_check_launch();
 }
 int pw_pack_strided_split(hipStream_t s, const float* src, void* dst, int A, int KH, int KWp, int KW, int Bp, int B, long sa, long skh, long skw, long sb) {
-    hipLaunchKernelGGL(pack_strided_k<sp32>, dim3(grid_for((size_t)A * KH * KWp * Bp)), dim3(TPB), 0, s, src, (sp32*)dst, A, KH, KWp, KW, Bp, B, sa, skh, skw, sb);
+    hipLaunchKernelGGL(pack_strided_k<sp32>, dim3(grid_for((size_t)A * KH * KWp * Bp, TPB, GRID_CAP)), dim3(TPB), 0, s, src, (sp32*)dst, A, KH, KWp, KW, Bp, B, sa, skh, skw, sb);
     return udapose_check_launch();
 }
 int pw_pack_multi(hipStream_t s, const void* jobs, const int* blk_job, const int* blk_sub, int nblocks) {
@@ -1132,15 +1076,15 @@ int pw_pack_multi(hipStream_t s, const void* jobs, const int* blk_job, const int
     return udapose_check_launch();
 }
 int pw_pack_strided(hipStream_t s, const float* src, elem_t* dst, int A, int KH, int KWp, int KW, int Bp, int B, long sa, long skh, long skw, long sb) {
-    hipLaunchKernelGGL(pack_strided_k<elem_t>, dim3(grid_for((size_t)A * KH * KWp * Bp)), dim3(TPB), 0, s, src, dst, A, KH, KWp, KW, Bp, B, sa, skh, skw, sb);
+    hipLaunchKernelGGL(pack_strided_k<elem_t>, dim3(grid_for((size_t)A * KH * KWp * Bp, TPB, GRID_CAP)), dim3(TPB), 0, s, src, dst, A, KH, KWp, KW, Bp, B, sa, skh, skw, sb);
     return udapose_check_launch();
 }
 int pw_pack_strided_f32(hipStream_t s, const float* src, float* dst, int A, int KH, int KWp, int KW, int Bp, int B, long sa, long skh, long skw, long sb) {
-    hipLaunchKernelGGL(pack_strided_k<float>, dim3(grid_for((size_t)A * KH * KWp * Bp)), dim3(TPB), 0, s, src, dst, A, KH, KWp, KW, Bp, B, sa, skh, skw, sb);
+    hipLaunchKernelGGL(pack_strided_k<float>, dim3(grid_for((size_t)A * KH * KWp * Bp, TPB, GRID_CAP)), dim3(TPB), 0, s, src, dst, A, KH, KWp, KW, Bp, B, sa, skh, skw, sb);
     return udapose_check_launch();
 }
 int pw_unpack_strided(hipStream_t s, const float* src, float* dst, int A, int KH, int KWp, int KW, int Bp, int B, long sa, long skh, long skw, long sb, float beta) {
-    hipLaunchKernelGGL(unpack_strided_k, dim3(grid_for((size_t)A * KH * KW * B)), dim3(TPB), 0, s, src, dst, A, KH, KWp, KW, Bp, B, sa, skh, skw, sb, beta);
+    hipLaunchKernelGGL(unpack_strided_k, dim3(grid_for((size_t)A * KH * KW * B, TPB, GRID_CAP)), dim3(TPB), 0, s, src, dst, A, KH, KWp, KW, Bp, B, sa, skh, skw, sb, beta);
     return udapose_check_launch();
 }
 int pw_bn_finalize(hipStream_t s, const float* slab, int rows, int C, double count, const float* gamma, const float* beta, float* rm, float* rv,
@@ -1210,11 +1154,11 @@ __global__ void bn_running_update_multi_k(const BnRunJob* __restrict__ jobs, con
     bn_running_update1(j.rm, j.rv, c, momentum, save[c], save[2 * j.C + c]);
 }
 int pw_bn_running_update_multi(hipStream_t s, const BnRunJob* d_jobs, int njobs, int maxC, const void* act, float momentum) {
-    hipLaunchKernelGGL(bn_running_update_multi_k, dim3(njobs, nblk(maxC)), dim3(TPB), 0, s, d_jobs, (const char*)act, momentum);
+    hipLaunchKernelGGL(bn_running_update_multi_k, dim3(njobs, grid_for(maxC, TPB, GRID_NO_CAP)), dim3(TPB), 0, s, d_jobs, (const char*)act, momentum);
     return udapose_check_launch();
 }
 int pw_bn_running_update(hipStream_t s, const float* save, int C, float* rm, float* rv, long long* nbt, float momentum) {
-    hipLaunchKernelGGL(bn_running_update_k, dim3(nblk(C)), dim3(TPB), 0, s, save, C, rm, rv, nbt, momentum);
+    hipLaunchKernelGGL(bn_running_update_k, dim3(grid_for(C, TPB, GRID_NO_CAP)), dim3(TPB), 0, s, save, C, rm, rv, nbt, momentum);
     return udapose_check_launch();
 }
 // clears several ranges in one launch: grid (jobs, 32); replaces one hipMemsetAsync node per split weight gradient
@@ -1286,18 +1230,18 @@ int pw_split_sum(hipStream_t s, const SumJob* d_jobs, const int* d_blk, int nblk
 }
 int pw_axpy(hipStream_t s, float* y, const float* x, size_t n) {
     const size_t n4 = n / 4;
-    if (n4) hipLaunchKernelGGL(axpy_k, dim3(grid_for(n4)), dim3(TPB), 0, s, y, x, n4);
+    if (n4) hipLaunchKernelGGL(axpy_k, dim3(grid_for(n4, TPB, GRID_CAP)), dim3(TPB), 0, s, y, x, n4);
     if (n % 4) hipLaunchKernelGGL(axpy_tail_k, dim3(1), dim3(64), 0, s, y + n4 * 4, x + n4 * 4, (int)(n % 4));
     return udapose_check_launch();
 }
 int pw_bn_eval_coeff(hipStream_t s, int C, const float* gamma, const float* beta, const float* rm, const float* rv, float eps, float* scale, float* shift) {
-    hipLaunchKernelGGL(bn_eval_coeff_k, dim3(nblk(C)), dim3(TPB), 0, s, C, gamma, beta, rm, rv, eps, scale, shift);
+    hipLaunchKernelGGL(bn_eval_coeff_k, dim3(grid_for(C, TPB, GRID_NO_CAP)), dim3(TPB), 0, s, C, gamma, beta, rm, rv, eps, scale, shift);
     return udapose_check_launch();
 }
 // grid of bn_apply_k: every thread must keep its channel group over the grid-stride loop -> (grid * TPB) % (C/8) == 0
 static int bn_apply_grid(size_t n8, int C) {
     const int G = C / 8;
-    int g = grid_for(n8);
+    int g = grid_for(n8, TPB, GRID_CAP);
     if (g > 2048) g = 2048;             // 8 work-groups per CU: threads of the large tensors loop, coefficients stay in registers
     if ((TPB % G) != 0) {               // C/8 not a divisor of the block size (e.g. C = 24): round the grid to a multiple of G
         g = (g / G) * G;
@@ -1394,7 +1338,7 @@ int pw_bn_bwd(hipStream_t s, const void* dz, int dz_is_f32, const elem_t* z, con
         using DZ = pointee_t<decltype(d)>;
         hipLaunchKernelGGL(bn_bwd_reduce_k<DZ>, dim3(rg.rows), dim3(TPB), 0, s, d, z, y, npix, C, mean, invstd, relu, slab, rg.ppb, gamma, beta);
         launch_bwd_finalize(s, slab, rg.rows, C, npix, gamma, invstd, dgamma, dbeta, beta_acc, coef);
-        hipLaunchKernelGGL(bn_bwd_apply_k<DZ>, dim3(grid_for(npix * G)), dim3(TPB), 0, s, d, z, y, dy, gout, npix * G, C, mean, invstd, coef, relu, gamma, beta);
+        hipLaunchKernelGGL(bn_bwd_apply_k<DZ>, dim3(grid_for(npix * G, TPB, GRID_CAP)), dim3(TPB), 0, s, d, z, y, dy, gout, npix * G, C, mean, invstd, coef, relu, gamma, beta);
     });
     return udapose_check_launch();
 }
@@ -1418,7 +1362,7 @@ int pw_bn_bwd_pre(hipStream_t s, const void* g, int g_is_f32, const elem_t* y, e
     launch_bwd_finalize(s, slab, rows, C, npix, gamma, invstd, dgamma, dbeta, beta_acc, coef);
     if (legacy) {
         with_grad_type(g, g_is_f32, [&](auto d) {
-            hipLaunchKernelGGL(bn_bwd_apply_k<pointee_t<decltype(d)>>, dim3(grid_for(npix * G)), dim3(TPB), 0, s, d, (const elem_t*)nullptr, y, dy, (elem_t*)nullptr,
+            hipLaunchKernelGGL(bn_bwd_apply_k<pointee_t<decltype(d)>>, dim3(grid_for(npix * G, TPB, GRID_CAP)), dim3(TPB), 0, s, d, (const elem_t*)nullptr, y, dy, (elem_t*)nullptr,
                                npix * G, C, mean, invstd, coef, 0, gamma, (const float*)nullptr);
         });
         return udapose_check_launch();
@@ -1432,14 +1376,14 @@ int pw_bn_bwd_pre(hipStream_t s, const void* g, int g_is_f32, const elem_t* y, e
 }
 int pw_maxpool3x3s2_fwd(hipStream_t s, const elem_t* x, elem_t* y, unsigned char* idx, int N, int H, int W, int C) {
     const int Ho = pool3x3s2_out(H), Wo = pool3x3s2_out(W);
-    hipLaunchKernelGGL(maxpool3x3s2_fwd_k<elem_t>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, x, y, idx, N, H, W, C, Ho, Wo);
+    hipLaunchKernelGGL(maxpool3x3s2_fwd_k<elem_t>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, x, y, idx, N, H, W, C, Ho, Wo);
     return udapose_check_launch();
 }
 int pw_bn_relu_maxpool3x3s2(hipStream_t s, const elem_t* x, elem_t* y, unsigned char* idx, int N, int H, int W, int C, const float* scale,
                             const float* shift) {
     if (C % 8 || !idx) return UDAPOSE_ERR_ARG;
     const int Ho = pool3x3s2_out(H), Wo = pool3x3s2_out(W);
-    hipLaunchKernelGGL(bn_relu_maxpool3x3s2_k, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, x, y, idx, N, H, W, C, Ho, Wo, scale, shift);
+    hipLaunchKernelGGL(bn_relu_maxpool3x3s2_k, dim3(grid_for((size_t)N * Ho * Wo * (C / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, x, y, idx, N, H, W, C, Ho, Wo, scale, shift);
     return udapose_check_launch();
 }
 // BN backward (relu mask recomputed from y) whose incoming gradient is the max-pool backward of (pool_dy, pool_idx), gathered on the
@@ -1454,44 +1398,44 @@ int pw_bn_bwd_pooled(hipStream_t s, const elem_t* pool_dy, const unsigned char* 
     hipLaunchKernelGGL((bn_bwd_reduce_k<elem_t, true>), dim3(rg.rows), dim3(TPB), 0, s, (const elem_t*)nullptr, (const elem_t*)nullptr, y, npix, C, mean, invstd,
                        2, slab, rg.ppb, gamma, beta, ps);
     launch_bwd_finalize(s, slab, rg.rows, C, npix, gamma, invstd, dgamma, dbeta, beta_acc, coef);
-    hipLaunchKernelGGL((bn_bwd_apply_k<elem_t, true>), dim3(grid_for(npix * G)), dim3(TPB), 0, s, (const elem_t*)nullptr, (const elem_t*)nullptr, y, dy,
+    hipLaunchKernelGGL((bn_bwd_apply_k<elem_t, true>), dim3(grid_for(npix * G, TPB, GRID_CAP)), dim3(TPB), 0, s, (const elem_t*)nullptr, (const elem_t*)nullptr, y, dy,
                        (elem_t*)nullptr, npix * G, C, mean, invstd, coef, 2, gamma, beta, ps);
     return udapose_check_launch();
 }
 int pw_maxpool3x3s2_fwd_f32(hipStream_t s, const float* x, float* y, unsigned char* idx, int N, int H, int W, int C) {
     const int Ho = pool3x3s2_out(H), Wo = pool3x3s2_out(W);
-    hipLaunchKernelGGL(maxpool3x3s2_fwd_k<float>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, x, y, idx, N, H, W, C, Ho, Wo);
+    hipLaunchKernelGGL(maxpool3x3s2_fwd_k<float>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, x, y, idx, N, H, W, C, Ho, Wo);
     return udapose_check_launch();
 }
 int pw_maxpool3x3s2_fwd_split(hipStream_t s, const void* x, void* y, unsigned char* idx, int N, int H, int W, int C, void* y16) {
     const int Ho = pool3x3s2_out(H), Wo = pool3x3s2_out(W);
     if (y16) {      // ('strict' plans: the pooled fp16 map as well)
-        hipLaunchKernelGGL((maxpool3x3s2_fwd_k<sp32, true>), dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, (const sp32*)x, (sp32*)y, idx, N, H, W,
+        hipLaunchKernelGGL((maxpool3x3s2_fwd_k<sp32, true>), dim3(grid_for((size_t)N * Ho * Wo * (C / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, (const sp32*)x, (sp32*)y, idx, N, H, W,
                            C, Ho, Wo, (_Float16*)y16);
         return udapose_check_launch();
     }
-    hipLaunchKernelGGL(maxpool3x3s2_fwd_k<sp32>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, (const sp32*)x, (sp32*)y, idx, N, H, W, C, Ho, Wo);
+    hipLaunchKernelGGL(maxpool3x3s2_fwd_k<sp32>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, (const sp32*)x, (sp32*)y, idx, N, H, W, C, Ho, Wo);
     return udapose_check_launch();
 }
 int pw_maxpool2x2_ceil_split(hipStream_t s, const void* x, void* y, int N, int H, int W, int C) {
     if (C % 8) return UDAPOSE_ERR_ARG;
     const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    hipLaunchKernelGGL(maxpool2x2_ceil_k<sp32>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, (const sp32*)x, (sp32*)y, N, H, W, C, Ho, Wo);
+    hipLaunchKernelGGL(maxpool2x2_ceil_k<sp32>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, (const sp32*)x, (sp32*)y, N, H, W, C, Ho, Wo);
     return udapose_check_launch();
 }
 int pw_maxpool3x3s2_bwd(hipStream_t s, const elem_t* dy, const unsigned char* idx, elem_t* dx, int N, int H, int W, int C) {
-    hipLaunchKernelGGL(maxpool3x3s2_bwd_k, dim3(grid_for((size_t)N * H * W * (C / 8))), dim3(TPB), 0, s, dy, idx, dx, N, H, W, C);
+    hipLaunchKernelGGL(maxpool3x3s2_bwd_k, dim3(grid_for((size_t)N * H * W * (C / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, dy, idx, dx, N, H, W, C);
     return udapose_check_launch();
 }
 int pw_maxpool2x2_ceil(hipStream_t s, const elem_t* x, elem_t* y, int N, int H, int W, int C) {
     const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    hipLaunchKernelGGL(maxpool2x2_ceil_k<elem_t>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, x, y, N, H, W, C, Ho, Wo);
+    hipLaunchKernelGGL(maxpool2x2_ceil_k<elem_t>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, x, y, N, H, W, C, Ho, Wo);
     return udapose_check_launch();
 }
 int pw_maxpool2x2_ceil_f32(hipStream_t s, const float* x, float* y, int N, int H, int W, int C) {
     if (C % 8) return UDAPOSE_ERR_ARG;
     const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    hipLaunchKernelGGL(maxpool2x2_ceil_k<float>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(TPB), 0, s, x, y, N, H, W, C, Ho, Wo);
+    hipLaunchKernelGGL(maxpool2x2_ceil_k<float>, dim3(grid_for((size_t)N * Ho * Wo * (C / 8), TPB, GRID_CAP)), dim3(TPB), 0, s, x, y, N, H, W, C, Ho, Wo);
     return udapose_check_launch();
 }
 int pw_plane_sum(hipStream_t s, const float* x, float* out, int N, int C, int HW, float beta) {

@@ -19,7 +19,6 @@ struct Taps { float t[MAX_TAPS]; };
 
 // every thread returns the block's best (value, flat index) under hm_better: common.h's block arg-max
 __device__ __forceinline__ void block_best(float& bv, int& bi, float* sv, int* si) { hm_block_best<TPB / 64>(bv, bi, sv, si); }
-__device__ __forceinline__ float sign_or_0(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }      // (NaN: 0)
 
 template <int MODE>
 __global__ __launch_bounds__(TPB) void refine_decode_k(const float* __restrict__ hm, int H, int W, int ksize, const Taps taps,

@@ -11,8 +11,8 @@ constexpr int REG_V = 4;     // f32x4 per thread kept in registers: rows of up t
 
 // sums of two values over the block (red: 2 * TPB / 64 doubles)
 __device__ __forceinline__ void block_sum2_d(double& a, double& b, double* red) {
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
+    a = wave_sum(a);
+    b = wave_sum(b);
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = a; red[TPB / 64 + (threadIdx.x >> 6)] = b; }
     __syncthreads();
     double ta = 0.0, tb = 0.0;

@@ -233,7 +233,7 @@ __global__ __launch_bounds__(TPB) void view_merge_k(MergeViews v, int k, int H, 
     }
     if (want_e) {
         // a thread's pixels in ascending index, the butterfly of a wave, the four waves in order: the same sum on every run
-        es = wave_sum_d(es);
+        es = wave_sum(es);
         if (lane == 0) se[wave] = es;
         __syncthreads();
         if (threadIdx.x == 0) {
