@@ -552,6 +552,11 @@ int udapose_refine_decode(void* stream, const float* hm, int R, int H, int W, in
 /* confidence mask (train_human.py:427-430): thr = k-th smallest of act[n]; mask[i] = (tea_mask[i]*act_local[i]) > thr */
 int udapose_kth_mask(void* stream, const float* act, const float* tea_mask, int n, int k, float* thr_out, unsigned char* mask,
                      const float* act_local, int n_local);
+/* The same launch with k read on the device: k_dev[0] is one int32 in device memory, loaded once at kernel entry and held inside 1 ... n, so
+ * that a captured launch follows a ramped mask_ratio through a 4-byte copy.  For the same k the same kernel body gives the same bits.
+ * UDAPOSE_ERR_ARG: a null act, k_dev or mask, n < 1 or n > 1 << 22. */
+int udapose_kth_mask_dev(void* stream, const float* act, const float* tea_mask, int n, const int* k_dev, float* thr_out, unsigned char* mask,
+                         const float* act_local, int n_local);
 /* ---- joint selection by an order statistic over [N,K] rows (csrc/select.hip).  One launch each, sums in double in a fixed order, no
  * atomics on global memory: capturable, and two calls give the same bits.
  * udapose_topk_select: top-k mining over the per-(n,k) loss rows of udapose_joints_mse_fwd (null mean_out) or udapose_cons_loss_fwd.
@@ -570,6 +575,8 @@ int udapose_kth_mask(void* stream, const float* act, const float* tea_mask, int 
  *   mask[i*K + j] = (tea_mask * act_local)[i*K + j] > thr_out[j] for the n_local rows of act_local (tea_mask may be null).  One work-group per
  *   joint, the radix select of udapose_kth_mask; NaN as there.  k < 1, k > n_pool, K < 1, a null pointer or more than 1 << 22 values:
  *   UDAPOSE_ERR_ARG.
+ * udapose_joint_kth_mask_dev: the same launch with k read on the device (k_dev[0], one int32, held inside 1 ... n_pool), as
+ *   udapose_kth_mask_dev; a null k_dev: UDAPOSE_ERR_ARG.
  * udapose_thr_mask: mask[i] = (tea_mask[i] * act[i]) > thr_dev[0], i < n; the threshold is read on the device. */
 int udapose_topk_select(void* stream, const float* rows, const float* wfac, const unsigned char* mfac, int N, int K, int topk, int largest,
                         unsigned char* sel, float* sample, float* mean_out);
@@ -577,6 +584,8 @@ int udapose_topk_sqdiff_bwd(void* stream, const float* a, const float* b, const 
                             int K, int HW, int topk, int half, float* da);
 int udapose_joint_kth_mask(void* stream, const float* pool, int n_pool, int K, int k, const float* tea_mask, const float* act_local,
                            int n_local, float* thr_out, unsigned char* mask);
+int udapose_joint_kth_mask_dev(void* stream, const float* pool, int n_pool, int K, const int* k_dev, const float* tea_mask, const float* act_local,
+                               int n_local, float* thr_out, unsigned char* mask);
 int udapose_thr_mask(void* stream, const float* act, const float* tea_mask, size_t n, const float* thr_dev, unsigned char* mask);
 /* PCK (lib/keypoint_detection.py:40-94) from decoded coordinates [B,K,2]; acc[K], avg_cnt[2] = (avg_acc, cnt) */
 int udapose_pck(void* stream, const float* pred_xy, const float* gt_xy, int B, int K, float norm_x, float norm_y, float thr, float* acc,
@@ -619,6 +628,11 @@ int udapose_multi_chunk(void);
 /* OldWeightEMA.step (utils.py:21-25): t = fl(fl(t*alpha) + fl(s*one_minus_alpha)), bit-exact two-rounding form */
 int udapose_ema_multi(void* stream, const long long* tgt_ptrs, const long long* src_ptrs, const long long* sizes, const int* blk_tensor,
                       const long long* blk_off, int nblocks, float alpha, float one_minus_alpha);
+/* The same sweep with the pair read on the device: ema_dev[0] = alpha, ema_dev[1] = one_minus_alpha, two fp32 values in device memory that
+ * the host rounded exactly as it rounds the by-value pair (1 - alpha in double, each then to fp32).  The same two values enter the same
+ * two-rounding expression: the same bits, and a captured launch follows a ramped teacher_alpha through an 8-byte copy. */
+int udapose_ema_multi_dev(void* stream, const long long* tgt_ptrs, const long long* src_ptrs, const long long* sizes, const int* blk_tensor,
+                          const long long* blk_off, int nblocks, const float* ema_dev);
 /* torch.optim.Adam.step (train_human.py:139,286).  dev_state (optional, 8 floats: [step, 1-b1^step, sqrt(1-b2^step), lr,
  * grad_scale, -, -, -]): the step counter and bias corrections are advanced by the call itself on the device, and lr /
  * grad_scale are READ from it instead of the by-value arguments, so that a captured call follows an lr scheduler
@@ -671,6 +685,16 @@ int udapose_net_fused_update_groups(udapose_net_t student, udapose_net_t teacher
                                     void* const* h_grads, void* const* h_state1, void* const* h_params_t, void* wpack_s, void* wpack_t,
                                     float beta1, float beta2, float eps, int nesterov, int n_groups, float* const* dev_states,
                                     const float* weight_decays, float alpha, float one_minus_alpha, int do_opt, long long grad2_delta_bytes);
+/* Both sweeps with the EMA pair read on the device (ema_dev: {alpha, one_minus_alpha} as for udapose_ema_multi_dev, loaded once at kernel
+ * entry in place of the by-value pair; null: UDAPOSE_ERR_ARG).  Everything else as the call of the same name without _dev, bit for bit. */
+int udapose_net_fused_update_dev(udapose_net_t student, udapose_net_t teacher, void* stream, void* const* h_params_s, void* const* h_grads,
+                                 void* const* h_exp_avg, void* const* h_params_t, void* wpack_s, void* wpack_t, float lr, float beta1,
+                                 float beta2, float eps, float weight_decay, int step, float grad_scale, float* dev_state,
+                                 const float* ema_dev, int do_adam, long long grad2_delta_bytes);
+int udapose_net_fused_update_groups_dev(udapose_net_t student, udapose_net_t teacher, void* stream, int kind, void* const* h_params_s,
+                                        void* const* h_grads, void* const* h_state1, void* const* h_params_t, void* wpack_s, void* wpack_t,
+                                        float beta1, float beta2, float eps, int nesterov, int n_groups, float* const* dev_states,
+                                        const float* weight_decays, const float* ema_dev, int do_opt, long long grad2_delta_bytes);
 
 /* Dynamic loss scaling = torch.cuda.amp.GradScaler (train_human.py:260,285-287,324,436-440) on the device, for the fp16 build.
  * dev_state is the optimizer's 8-float state: [5] = found_inf, [6] = loss scale S, [7] = growth tracker, [4] = 1/S.

@@ -121,6 +121,9 @@ _SIGS = {
     "udapose_net_fused_update": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, cf, cf, ci, ll]),
     "udapose_net_bind_update_groups": (ci, [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
     "udapose_net_fused_update_groups": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, ci, ci, vp, vp, cf, cf, ci, ll]),
+    # (the _dev forms: the EMA pair {alpha, 1 - alpha} as one device pointer in place of the two floats)
+    "udapose_net_fused_update_dev": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp, ci, ll]),
+    "udapose_net_fused_update_groups_dev": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, ci, ci, vp, vp, vp, ci, ll]),
     "udapose_joints_mse_fwd": (ci, [vp, vp, vp, vp, ci, ci, vp, vp]),
     "udapose_joints_mse_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, vp]),
     "udapose_cons_loss_fwd": (ci, [vp, vp, vp, vp, ci, ci, vp, vp]),
@@ -152,15 +155,18 @@ _SIGS = {
     "udapose_flip_merge": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
     "udapose_refine_decode": (ci, [vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, vp]),
     "udapose_kth_mask": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, ci]),
+    "udapose_kth_mask_dev": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, ci]),      # (k: an int32 in device memory)
     "udapose_topk_select": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
     "udapose_topk_sqdiff_bwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "udapose_joint_kth_mask": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, vp, vp]),
+    "udapose_joint_kth_mask_dev": (ci, [vp, vp, ci, ci, vp, vp, vp, ci, vp, vp]),
     "udapose_thr_mask": (ci, [vp, vp, vp, sz, vp, vp]),
     "udapose_pck": (ci, [vp, vp, vp, ci, ci, cf, cf, cf, vp, vp]),
     "udapose_pck_accumulate": (ci, [vp, vp, vp, vp, vp, ci, ci, cf, cf, vp, ci, vp]),
     "udapose_pck_accumulate_heatmaps": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, vp]),
     "udapose_multi_chunk": (ci, []),
     "udapose_ema_multi": (ci, [vp, vp, vp, vp, vp, vp, ci, cf, cf]),
+    "udapose_ema_multi_dev": (ci, [vp, vp, vp, vp, vp, vp, ci, vp]),
     "udapose_adam_multi": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, cf, cf, cf, cf, cf, ci, cf, vp]),
     "udapose_sgd_multi": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, cf, cf, cf, ci, ci, cf, vp]),
     "udapose_comm_pack_bf16": (ci, [vp, vp, ll, vp, ll]),

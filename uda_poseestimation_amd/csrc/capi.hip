@@ -306,7 +306,15 @@ int udapose_net_fused_update(udapose_net_t student, udapose_net_t teacher, void*
                              int do_adam, long long grad2_delta_bytes) {
     if (!student || !teacher) return UDAPOSE_ERR_ARG;
     return net_fused_update(student, teacher, S(stream), params_s, grads, exp_avg, params_t, wpack_s, wpack_t, lr, beta1, beta2, eps, weight_decay,
-                            step, grad_scale, dev_state, alpha, one_minus_alpha, do_adam, grad2_delta_bytes);
+                            step, grad_scale, dev_state, alpha, one_minus_alpha, do_adam, grad2_delta_bytes, nullptr);
+}
+int udapose_net_fused_update_dev(udapose_net_t student, udapose_net_t teacher, void* stream, void* const* params_s, void* const* grads,
+                                 void* const* exp_avg, void* const* params_t, void* wpack_s, void* wpack_t, float lr, float beta1, float beta2,
+                                 float eps, float weight_decay, int step, float grad_scale, float* dev_state, const float* ema_dev, int do_adam,
+                                 long long grad2_delta_bytes) {
+    if (!student || !teacher || !ema_dev) return UDAPOSE_ERR_ARG;
+    return net_fused_update(student, teacher, S(stream), params_s, grads, exp_avg, params_t, wpack_s, wpack_t, lr, beta1, beta2, eps, weight_decay,
+                            step, grad_scale, dev_state, 0.f, 0.f, do_adam, grad2_delta_bytes, ema_dev);
 }
 int udapose_net_bind_update_groups(udapose_net_t student, udapose_net_t teacher, int kind, void* const* params_s, void* const* grads,
                                    void* const* state1, void* const* state2, void* const* params_t, void* wpack_s, void* wpack_t,
@@ -321,7 +329,15 @@ int udapose_net_fused_update_groups(udapose_net_t student, udapose_net_t teacher
                                     float alpha, float one_minus_alpha, int do_opt, long long grad2_delta_bytes) {
     if (!student || !teacher || !params_s || !grads || !state1 || !params_t) return UDAPOSE_ERR_ARG;
     return net_fused_update_groups(student, teacher, S(stream), kind, params_s, grads, state1, params_t, wpack_s, wpack_t, beta1, beta2, eps, nesterov,
-                                   n_groups, dev_states, weight_decays, alpha, one_minus_alpha, do_opt, grad2_delta_bytes);
+                                   n_groups, dev_states, weight_decays, alpha, one_minus_alpha, do_opt, grad2_delta_bytes, nullptr);
+}
+int udapose_net_fused_update_groups_dev(udapose_net_t student, udapose_net_t teacher, void* stream, int kind, void* const* params_s,
+                                        void* const* grads, void* const* state1, void* const* params_t, void* wpack_s, void* wpack_t,
+                                        float beta1, float beta2, float eps, int nesterov, int n_groups, float* const* dev_states,
+                                        const float* weight_decays, const float* ema_dev, int do_opt, long long grad2_delta_bytes) {
+    if (!student || !teacher || !params_s || !grads || !state1 || !params_t || !ema_dev) return UDAPOSE_ERR_ARG;
+    return net_fused_update_groups(student, teacher, S(stream), kind, params_s, grads, state1, params_t, wpack_s, wpack_t, beta1, beta2, eps, nesterov,
+                                   n_groups, dev_states, weight_decays, 0.f, 0.f, do_opt, grad2_delta_bytes, ema_dev);
 }
 
 int udapose_joints_mse_fwd(void* stream, const float* pred, const float* gt, const float* w, int R, int HW, float* rows, float* mean_out) {
@@ -439,6 +455,10 @@ int udapose_kth_mask(void* stream, const float* act, const float* tm, int n, int
                      int n_local) {
     return hm_kth_mask(S(stream), act, tm, n, k, thr_out, mask, act_local, n_local);
 }
+int udapose_kth_mask_dev(void* stream, const float* act, const float* tm, int n, const int* k_dev, float* thr_out, unsigned char* mask,
+                         const float* act_local, int n_local) {
+    return hm_kth_mask_dev(S(stream), act, tm, n, k_dev, thr_out, mask, act_local, n_local);
+}
 int udapose_topk_select(void* stream, const float* rows, const float* wfac, const unsigned char* mfac, int N, int K, int topk, int largest,
                         unsigned char* sel, float* sample, float* mean_out) {
     return sel_topk(S(stream), rows, wfac, mfac, N, K, topk, largest, sel, sample, mean_out);
@@ -450,6 +470,10 @@ int udapose_topk_sqdiff_bwd(void* stream, const float* a, const float* b, const 
 int udapose_joint_kth_mask(void* stream, const float* pool, int n_pool, int K, int k, const float* tm, const float* act_local, int n_local,
                            float* thr_out, unsigned char* mask) {
     return sel_joint_kth_mask(S(stream), pool, n_pool, K, k, tm, act_local, n_local, thr_out, mask);
+}
+int udapose_joint_kth_mask_dev(void* stream, const float* pool, int n_pool, int K, const int* k_dev, const float* tm, const float* act_local,
+                               int n_local, float* thr_out, unsigned char* mask) {
+    return sel_joint_kth_mask_dev(S(stream), pool, n_pool, K, k_dev, tm, act_local, n_local, thr_out, mask);
 }
 int udapose_thr_mask(void* stream, const float* act, const float* tm, size_t n, const float* thr_dev, unsigned char* mask) {
     return sel_thr_mask(S(stream), act, tm, n, thr_dev, mask);
@@ -468,7 +492,12 @@ int udapose_pck_accumulate_heatmaps(void* stream, const float* out, const float*
 int udapose_multi_chunk(void) { return opt_chunk(); }
 int udapose_ema_multi(void* stream, const long long* t, const long long* s, const long long* sizes, const int* bt, const long long* bo, int nb,
                       float alpha, float oma) {
-    return opt_ema(S(stream), t, s, sizes, bt, bo, nb, alpha, oma);
+    return opt_ema(S(stream), t, s, sizes, bt, bo, nb, alpha, oma, nullptr);
+}
+int udapose_ema_multi_dev(void* stream, const long long* t, const long long* s, const long long* sizes, const int* bt, const long long* bo, int nb,
+                          const float* ema_dev) {
+    if (!ema_dev) return UDAPOSE_ERR_ARG;
+    return opt_ema(S(stream), t, s, sizes, bt, bo, nb, 0.f, 0.f, ema_dev);
 }
 int udapose_adam_multi(void* stream, const long long* p, const long long* g, const long long* m, const long long* v, const long long* sizes,
                        const int* bt, const long long* bo, int nb, float lr, float b1, float b2, float eps, float wd, int step, float gscale,

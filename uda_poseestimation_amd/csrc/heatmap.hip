@@ -126,11 +126,13 @@ __global__ void argmax_rectify_k(const float* __restrict__ hm, int H, int W, flo
 
 // k-th smallest (1-indexed) of n values, then mask[i] = (tm[i]*act[i]) > thr  (train_human.py:429-430), in ONE work-group:
 // hm_kth_smallest (kth_select.h) over the contiguous vector.  NaN orders as the largest value and a NaN threshold gives an
-// all-false mask, exactly like torch.kthvalue + `>`.
+// all-false mask, exactly like torch.kthvalue + `>`.  k_dev (hm_kth_mask_dev): k is read from device memory - one uniform load, the same
+// for every thread - and held inside 1 ... n, so that a captured launch follows a host change of mask_ratio.
 __global__ void kth_mask_k(const float* __restrict__ act, const float* __restrict__ tm, int n, int k, float* __restrict__ thr_out,
-                           unsigned char* __restrict__ mask, const float* __restrict__ act_local, int n_local) {
+                           unsigned char* __restrict__ mask, const float* __restrict__ act_local, int n_local, const int* __restrict__ k_dev) {
     __shared__ unsigned int hist[256];
     __shared__ unsigned int pick[2];
+    if (k_dev) k = hm_kth_clamp(k_dev[0], n);
     const float thr = hm_kth_smallest(act, 1, n, k, hist, pick);
     if (threadIdx.x == 0 && thr_out) thr_out[0] = thr;
     const float* al = act_local ? act_local : act;
@@ -201,7 +203,14 @@ int hm_argmax_rectify(hipStream_t s, const float* hm, int R, int H, int W, float
 int hm_kth_mask(hipStream_t s, const float* act, const float* tm, int n, int k, float* thr_out, unsigned char* mask, const float* act_local,
                 int n_local) {
     if (k < 1 || k > n || n > (1 << 22)) return UDAPOSE_ERR_ARG;
-    hipLaunchKernelGGL(kth_mask_k, dim3(1), dim3(1024), 0, s, act, tm, n, k, thr_out, mask, act_local, n_local);
+    hipLaunchKernelGGL(kth_mask_k, dim3(1), dim3(1024), 0, s, act, tm, n, k, thr_out, mask, act_local, n_local, nullptr);
+    return udapose_check_launch();
+}
+// the same launch with k in device memory (the host checked its range when it uploaded it; the kernel holds it inside 1 ... n)
+int hm_kth_mask_dev(hipStream_t s, const float* act, const float* tm, int n, const int* k_dev, float* thr_out, unsigned char* mask,
+                    const float* act_local, int n_local) {
+    if (!act || !k_dev || !mask || n < 1 || n > (1 << 22) || (act_local && n_local < 0)) return UDAPOSE_ERR_ARG;
+    hipLaunchKernelGGL(kth_mask_k, dim3(1), dim3(1024), 0, s, act, tm, n, 0, thr_out, mask, act_local, n_local, k_dev);
     return udapose_check_launch();
 }
 int hm_pck(hipStream_t s, const float* pred, const float* gt, int B, int K, float nh, float nw, float thr, float* acc, float* avg_cnt) {

@@ -14,6 +14,9 @@ __device__ __forceinline__ float hm_unkey(unsigned int k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
+// a k that was read from device memory, held inside the select's range 1 ... n
+__device__ __forceinline__ int hm_kth_clamp(int k, int n) { return k < 1 ? 1 : (k > n ? n : k); }
+
 // k-th smallest (1-indexed) of the n values base[i * stride], by ONE work-group (every thread calls it and gets the value).
 // MSB-first radix select: 4 passes of 8 bits, each a 256-bin LDS histogram of the keys that still match the prefix found so
 // far, then a scan of the bins for the one that holds rank k.  O(n) per pass (the previous rank-count form was O(n^2): 23 us

@@ -12,6 +12,8 @@ int hm_argmax_rectify(hipStream_t s, const float* hm, int R, int H, int W, float
                       int rad);
 int hm_kth_mask(hipStream_t s, const float* act, const float* tm, int n, int k, float* thr_out, unsigned char* mask, const float* act_local,
                 int n_local);
+int hm_kth_mask_dev(hipStream_t s, const float* act, const float* tm, int n, const int* k_dev, float* thr_out, unsigned char* mask,
+                    const float* act_local, int n_local);
 int hm_pck(hipStream_t s, const float* pred, const float* gt, int B, int K, float nh, float nw, float thr, float* acc, float* avg_cnt);
 // pck_curve.hip
 int pck_accumulate(hipStream_t s, const float* pred, const float* gt, const unsigned char* visible, const float* norm, int B, int K, float nh,
@@ -25,6 +27,8 @@ int sel_topk_sqdiff_bwd(hipStream_t s, const float* a, const float* b, const flo
                         int K, int HW, int topk, int half, float* da);
 int sel_joint_kth_mask(hipStream_t s, const float* pool, int n_pool, int K, int k, const float* tm, const float* act_local, int n_local,
                        float* thr_out, unsigned char* mask);
+int sel_joint_kth_mask_dev(hipStream_t s, const float* pool, int n_pool, int K, const int* k_dev, const float* tm, const float* act_local,
+                           int n_local, float* thr_out, unsigned char* mask);
 int sel_thr_mask(hipStream_t s, const float* act, const float* tm, size_t n, const float* thr_dev, unsigned char* mask);
 // softmax_loss.hip
 int sml_kl_fwd(hipStream_t st, const float* s, const float* g, const float* w, float eps, int R, int group, int HW, float* rows, float* stats,

@@ -37,10 +37,10 @@ int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grad
                     void* wpack_s_, void* wpack_t_);
 int net_fused_update(void* hs, void* ht, hipStream_t s, void* const* params_s, void* const* grads, void* const* h_m, void* const* params_t,
                      void* wpack_s_, void* wpack_t_, float lr, float beta1, float beta2, float eps, float wd, int step, float gscale,
-                     float* dev_state, float alpha, float oma, int do_adam, long long grad2_delta);
+                     float* dev_state, float alpha, float oma, int do_adam, long long grad2_delta, const float* ema_dev);
 int net_fused_update_groups(void* hs, void* ht, hipStream_t s, int kind, void* const* params_s, void* const* grads, void* const* h_m,
                             void* const* params_t, void* wpack_s_, void* wpack_t_, float beta1, float beta2, float eps, int nesterov, int ngroups,
-                            float* const* states, const float* wds, float alpha, float oma, int do_opt, long long grad2_delta);
+                            float* const* states, const float* wds, float alpha, float oma, int do_opt, long long grad2_delta, const float* ema_dev);
 // prof.hip
 int prof_before(hipStream_t s, int kind, double flops);
 void prof_after(hipStream_t s, int token);

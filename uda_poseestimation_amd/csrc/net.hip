@@ -1373,9 +1373,10 @@ int net_bind_update(void* hs, void* ht, void* const* params_s, void* const* grad
 
 namespace {
 // lr / step / gscale: the host's values, read only where states[0] is NULL (one Adam group without device state)
+// ema_dev: NULL, or {alpha, 1 - alpha} in device memory, read by the sweep in place of alpha / oma (the udapose_net_fused_update*_dev forms)
 int fused_update(void* hs, void* ht, hipStream_t s, int kind, void* const* params_s, void* const* grads, void* const* h_m, void* const* params_t,
                  void* wpack_s_, void* wpack_t_, float lr, float beta1, float beta2, float eps, int nesterov, int step, float gscale, int ngroups,
-                 float* const* states, const float* wds, float alpha, float oma, int do_adam, long long grad2_delta) {
+                 float* const* states, const float* wds, float alpha, float oma, int do_adam, long long grad2_delta, const float* ema_dev) {
     Net& n = *(Net*)hs;
     const Net& nt = *(const Net*)ht;
     DbgSyncScope dbg(n.policy.debug_sync);
@@ -1388,7 +1389,7 @@ int fused_update(void* hs, void* ht, hipStream_t s, int kind, void* const* param
     if (d.G && (d.G != n.upd_sum_group || d.gA != (char*)grads[0] || grad2_delta != (long long)(d.gB - d.gA))) return UDAPOSE_ERR_NOT_PREPARED;
     n.deferred = Net::Deferred{};
     CK(opt_tail(s, u.jobs.d, u.blk_job.d, u.blk_sub.d, u.nblocks(), kind, lr, beta1, beta2, eps, nesterov, step, gscale, ngroups, states, wds, alpha, oma, do_adam,
-                grad2_delta, 1, d.G ? d.wsA : nullptr, d.G ? d.wsB : nullptr));
+                grad2_delta, 1, d.G ? d.wsA : nullptr, d.G ? d.wsB : nullptr, ema_dev));
     // the two packs that are not a cast or a per-tap transpose of a whole tensor: the stem's 3 -> 8 channel gather (both
     // networks) and the head's zero-padded dgrad pack (student)
     if (n.strict)   // 'strict' student: its split forward packs (stem included) from the updated weights, one pack launch (net_bind's table)
@@ -1403,18 +1404,18 @@ int fused_update(void* hs, void* ht, hipStream_t s, int kind, void* const* param
 
 int net_fused_update(void* hs, void* ht, hipStream_t s, void* const* params_s, void* const* grads, void* const* h_m, void* const* params_t,
                      void* wpack_s_, void* wpack_t_, float lr, float beta1, float beta2, float eps, float wd, int step, float gscale,
-                     float* dev_state, float alpha, float oma, int do_adam, long long grad2_delta) {
+                     float* dev_state, float alpha, float oma, int do_adam, long long grad2_delta, const float* ema_dev) {
     return fused_update(hs, ht, s, 0, params_s, grads, h_m, params_t, wpack_s_, wpack_t_, lr, beta1, beta2, eps, 0, step, gscale, 1, &dev_state, &wd, alpha,
-                        oma, do_adam, grad2_delta);
+                        oma, do_adam, grad2_delta, ema_dev);
 }
 // kind 0: Adam (beta1, beta2, eps); kind 1: SGD (beta1 = momentum, nesterov).  Every group's device state is required: lr, grad_scale, the counter
 // and the found-inf mark are read from it.
 int net_fused_update_groups(void* hs, void* ht, hipStream_t s, int kind, void* const* params_s, void* const* grads, void* const* h_m,
                             void* const* params_t, void* wpack_s_, void* wpack_t_, float beta1, float beta2, float eps, int nesterov, int ngroups,
-                            float* const* states, const float* wds, float alpha, float oma, int do_opt, long long grad2_delta) {
+                            float* const* states, const float* wds, float alpha, float oma, int do_opt, long long grad2_delta, const float* ema_dev) {
     if (ngroups < 1 || ngroups > TAIL_GROUPS || !states || !wds) return UDAPOSE_ERR_ARG;
     for (int g = 0; g < ngroups; ++g)
         if (!states[g]) return UDAPOSE_ERR_ARG;
     return fused_update(hs, ht, s, kind, params_s, grads, h_m, params_t, wpack_s_, wpack_t_, 0.f, beta1, beta2, eps, nesterov, 0, 1.f, ngroups, states, wds,
-                        alpha, oma, do_opt, grad2_delta);
+                        alpha, oma, do_opt, grad2_delta, ema_dev);
 }

@@ -16,9 +16,10 @@ struct TailJob {
 constexpr int TAIL_GROUPS = 8;
 
 int opt_chunk();
+// ema_dev (opt_tail, opt_ema): NULL, or the pair {alpha, 1 - alpha} in device memory, read by the kernel in place of the by-value pair
 int opt_tail(hipStream_t s, const TailJob* d_jobs, const int* blk_job, const int* blk_sub, int nblocks, int kind, float lr, float beta1, float beta2,
              float eps, int nesterov, int step, float gscale, int ngroups, float* const* states, const float* wds, float alpha, float oma, int do_adam,
-             long long grad2_delta, int tick, const void* split_ws1, const void* split_ws2);
+             long long grad2_delta, int tick, const void* split_ws1, const void* split_ws2, const float* ema_dev);
 int opt_grad_check(hipStream_t s, const long long* g, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks,
                    float* dev_state, long long grad2_delta);
 int opt_scaler_update(hipStream_t s, float* dev_state, float growth, float backoff, int interval);
@@ -27,7 +28,7 @@ int opt_grad_sumsq(hipStream_t s, const long long* g, const long long* sizes, co
 int opt_grad_clip(hipStream_t s, const double* partials, const int* blk_begin, const int* blk_end, int ngroups, float* const* states, float* clip);
 int opt_grad_clip_restore(hipStream_t s, int ngroups, float* const* states, const float* clip);
 int opt_ema(hipStream_t s, const long long* tgt, const long long* src, const long long* sizes, const int* blk_tensor, const long long* blk_off,
-            int nblocks, float alpha, float one_minus_alpha);
+            int nblocks, float alpha, float one_minus_alpha, const float* ema_dev);
 int opt_adam(hipStream_t s, const long long* p, const long long* g, const long long* m, const long long* v, const long long* sizes,
              const int* blk_tensor, const long long* blk_off, int nblocks, float lr, float beta1, float beta2, float eps, float wd, int step,
              float gscale, float* dev_state);

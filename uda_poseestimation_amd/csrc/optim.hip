@@ -27,7 +27,9 @@ struct MtTable {
 };
 
 // teacher = fl(fl(teacher*alpha) + fl(student*(1-alpha)))  -- two roundings, exactly utils.py:21-25 (no FMA contraction)
-__global__ void ema_k(MtTable t, float alpha, float one_minus_alpha) {
+// ab_dev: the pair read from device memory (a captured launch follows a ramped teacher_alpha): the same two fp32 values, the same bits
+__global__ void ema_k(MtTable t, float alpha, float one_minus_alpha, const float* __restrict__ ab_dev) {
+    if (ab_dev) { alpha = ab_dev[0]; one_minus_alpha = ab_dev[1]; }
     const int ti = t.blk_tensor[blockIdx.x];
     const long long off = t.blk_off[blockIdx.x];
     float* tp = (float*)t.a[ti];
@@ -265,7 +267,8 @@ __global__ void grad_clip_restore_k(ClipGroups G, int ngroups, const float* __re
 // this sweep (udapose_net_wgrad_pair_defer): a split job's g and g + g2 are then NOT read - the sweep adds the partial tensors itself.
 // An SGD sweep (KIND_SGD) keeps its momentum buffer in TailJob.m, leaves v alone, and reads beta1 as the momentum.
 struct TailHyper { float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, gscale, alpha, oma; int do_adam; long long g2; const char* ws1; const char* ws2;
-                   int nesterov, first; };
+                   int nesterov, first; const float* ema; };
+// (ema: NULL, or {alpha, oma} in device memory, which then replace the by-value pair at kernel entry - uniform loads, like the group state's)
 // Parameter groups (PoseResNet.get_parameters: the backbone at a tenth of the rate): a job reads lr - and for Adam the bias corrections -
 // from its group's 8-float device state and weight_decay from this table, passed by value.  state[g] == NULL: the by-value TailHyper holds.
 struct TailGroups { const float* state[TAIL_GROUPS]; float wd[TAIL_GROUPS]; };
@@ -333,6 +336,7 @@ __global__ __launch_bounds__(TPB) void opt_tail_k(const TailJob* __restrict__ jo
         h.lr = dev_state[3]; h.gscale = dev_state[4];
         if (dev_state[5] != 0.f) h.do_adam = 0;          // inf / nan gradients: the optimizer step is skipped, the EMA is not
     }
+    if (h.ema) { h.alpha = h.ema[0]; h.oma = h.ema[1]; }
     const bool adam = j.adam && h.do_adam;
     if (j.A == 0) {
         const long long off = (long long)sub * CHUNK;
@@ -413,7 +417,7 @@ int opt_chunk() { return CHUNK; }
 // issued in two parts ticks with the first)
 int opt_tail(hipStream_t s, const TailJob* d_jobs, const int* blk_job, const int* blk_sub, int nblocks, int kind, float lr, float beta1, float beta2,
              float eps, int nesterov, int step, float gscale, int ngroups, float* const* states, const float* wds, float alpha, float oma, int do_adam,
-             long long grad2_delta, int tick, const void* split_ws1, const void* split_ws2) {
+             long long grad2_delta, int tick, const void* split_ws1, const void* split_ws2, const float* ema_dev) {
     if (grad2_delta % 16) return UDAPOSE_ERR_ARG;
     if ((split_ws1 == nullptr) != (split_ws2 == nullptr)) return UDAPOSE_ERR_ARG;
     if ((kind != KIND_ADAM && kind != KIND_SGD) || ngroups < 1 || ngroups > TAIL_GROUPS || !states || !wds) return UDAPOSE_ERR_ARG;
@@ -428,7 +432,7 @@ int opt_tail(hipStream_t s, const TailJob* d_jobs, const int* blk_job, const int
     else { bc1 = 1.0 - pow((double)beta1, (double)step); bc2 = 1.0 - pow((double)beta2, (double)step); }
     if (nblocks <= 0) return UDAPOSE_OK;
     TailHyper h{lr, beta1, beta2, eps, wds[0], (float)bc1, (float)sqrt(bc2), gscale, alpha, oma, do_adam, grad2_delta, (const char*)split_ws1, (const char*)split_ws2,
-                nesterov, 0};
+                nesterov, 0, ema_dev};
     const dim3 grid(nblocks), block(TPB);
     if (kind == KIND_SGD) hipLaunchKernelGGL((opt_tail_k<KIND_SGD, false>), grid, block, 0, s, d_jobs, blk_job, blk_sub, h, G);
     else if (split_ws1) hipLaunchKernelGGL((opt_tail_k<KIND_ADAM, true>), grid, block, 0, s, d_jobs, blk_job, blk_sub, h, G);
@@ -488,10 +492,10 @@ int opt_grad_clip_restore(hipStream_t s, int ngroups, float* const* states, cons
 }
 
 int opt_ema(hipStream_t s, const long long* tgt, const long long* src, const long long* sizes, const int* blk_tensor, const long long* blk_off,
-            int nblocks, float alpha, float one_minus_alpha) {
+            int nblocks, float alpha, float one_minus_alpha, const float* ema_dev) {
     MtTable t{tgt, src, nullptr, nullptr, sizes, blk_tensor, blk_off};
     if (nblocks <= 0) return UDAPOSE_OK;
-    hipLaunchKernelGGL(ema_k, dim3(nblocks), dim3(TPB), 0, s, t, alpha, one_minus_alpha);
+    hipLaunchKernelGGL(ema_k, dim3(nblocks), dim3(TPB), 0, s, t, alpha, one_minus_alpha, ema_dev);
     return udapose_check_launch();
 }
 int opt_adam(hipStream_t s, const long long* p, const long long* g, const long long* m, const long long* v, const long long* sizes,

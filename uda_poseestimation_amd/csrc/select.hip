@@ -106,10 +106,12 @@ __global__ __launch_bounds__(SEL_TPB) void topk_select_k(const float* __restrict
 // block j: thr_out[j] = k-th smallest of pool[i*K + j], i < n_pool; mask[i*K + j] = (tm * act_local)[i*K + j] > thr_out[j], i < n_local
 __global__ __launch_bounds__(KTH_TPB) void joint_kth_mask_k(const float* __restrict__ pool, int n_pool, int K, int k,
                                                             const float* __restrict__ tm, const float* __restrict__ act_local, int n_local,
-                                                            float* __restrict__ thr_out, unsigned char* __restrict__ mask) {
+                                                            float* __restrict__ thr_out, unsigned char* __restrict__ mask,
+                                                            const int* __restrict__ k_dev) {
     __shared__ unsigned int hist[256];
     __shared__ unsigned int pick[2];
     const int j = blockIdx.x;
+    if (k_dev) k = hm_kth_clamp(k_dev[0], n_pool);       // (sel_joint_kth_mask_dev: one uniform load, as in kth_mask_k)
     const float thr = hm_kth_smallest(pool + j, (size_t)K, n_pool, k, hist, pick);
     if (threadIdx.x == 0) thr_out[j] = thr;
     for (int i = threadIdx.x; i < n_local; i += blockDim.x) {
@@ -141,13 +143,23 @@ int sel_topk_sqdiff_bwd(hipStream_t s, const float* a, const float* b, const flo
     const float coef = (float)((half ? 1.0 : 2.0) / ((double)HW * topk * N));
     return hm_sqdiff_bwd(s, a, b, w, sel, gscale, coef, N * K, HW, da, nullptr, nullptr, 1);
 }
-int sel_joint_kth_mask(hipStream_t s, const float* pool, int n_pool, int K, int k, const float* tm, const float* act_local, int n_local,
-                       float* thr_out, unsigned char* mask) {
-    if (K < 1 || k < 1 || k > n_pool) return UDAPOSE_ERR_ARG;
+// k_dev != NULL: k is read on the device (sel_joint_kth_mask_dev) and the by-value k is not looked at
+static int joint_kth_mask(hipStream_t s, const float* pool, int n_pool, int K, int k, const int* k_dev, const float* tm, const float* act_local,
+                          int n_local, float* thr_out, unsigned char* mask) {
+    if (K < 1 || n_pool < 1 || (!k_dev && (k < 1 || k > n_pool))) return UDAPOSE_ERR_ARG;
     if (!pool || !act_local || !thr_out || !mask || n_local < 0 || (long long)n_pool * K > (1ll << 22) || (long long)n_local * K > (1ll << 22))
         return UDAPOSE_ERR_ARG;
-    hipLaunchKernelGGL(joint_kth_mask_k, dim3(K), dim3(KTH_TPB), 0, s, pool, n_pool, K, k, tm, act_local, n_local, thr_out, mask);
+    hipLaunchKernelGGL(joint_kth_mask_k, dim3(K), dim3(KTH_TPB), 0, s, pool, n_pool, K, k, tm, act_local, n_local, thr_out, mask, k_dev);
     return udapose_check_launch();
+}
+int sel_joint_kth_mask(hipStream_t s, const float* pool, int n_pool, int K, int k, const float* tm, const float* act_local, int n_local,
+                       float* thr_out, unsigned char* mask) {
+    return joint_kth_mask(s, pool, n_pool, K, k, nullptr, tm, act_local, n_local, thr_out, mask);
+}
+int sel_joint_kth_mask_dev(hipStream_t s, const float* pool, int n_pool, int K, const int* k_dev, const float* tm, const float* act_local,
+                           int n_local, float* thr_out, unsigned char* mask) {
+    if (!k_dev) return UDAPOSE_ERR_ARG;
+    return joint_kth_mask(s, pool, n_pool, K, 0, k_dev, tm, act_local, n_local, thr_out, mask);
 }
 int sel_thr_mask(hipStream_t s, const float* act, const float* tm, size_t n, const float* thr_dev, unsigned char* mask) {
     if (!act || !thr_dev || !mask) return UDAPOSE_ERR_ARG;

@@ -308,10 +308,18 @@ class MeanTeacherTrainer:
         # view_min views (None: all k) are inliers is taken out of the consistency mask, in every mask_mode (the gate is confidence_mask's
         # tea_mask=).  The skeleton prior, the occlusion picks, `activates`, rectify and the adversarial probe see the merged map as they see
         # the mean.  The step's dict gains view_agree, view_n_inliers, view_spread2.  Attributes like the ones above; view_radius lives in a
-        # device scalar refreshed outside any graph (sync_view_radius).  GraphedTrainStep stages one teacher view and refuses a trainer with
-        # view_merge set.  Data parallel: the views, their peaks and the gate are per rank and per sample; nothing is communicated.
+        # device scalar refreshed outside any graph (sync_view_radius).  GraphedTrainStep stages k views when it is built with a list of them
+        # and refuses a trainer with view_merge set only when built with a single view.  Data parallel: the views, their peaks and the gate
+        # are per rank and per sample; nothing is communicated.
         self.view_merge, self.view_radius, self.view_min = None, 2.0, None
         self._view_rad = None               # [device scalar, the host value it holds]
+        # scheduled: names out of SCHEDULABLE whose values the step - eager or captured - reads from DEVICE memory, so that
+        # a captured step follows a ramp of them (utils.sigmoid_rampup, ema_alpha_warmup ...) instead of refusing the change: the loss weights
+        # as 0-d fp32 tensors in loss_all, teacher_alpha as the fp32 pair (alpha, 1 - alpha) of the EMA sweeps, mask_ratio as the int32 k-th
+        # index of the mask's select.  sync_schedule() uploads what changed, outside any capture; GraphedTrainStep.step calls it.  An
+        # attribute like the ones above, set before a GraphedTrainStep is built and frozen afterwards; (): every launch is what it was.
+        self.scheduled = ()
+        self._sched, self._sched_pool = None, None      # [8 device words, the host bytes they hold] | the mask's pool size, once a step has seen it
         # precision: None keeps what the networks are set to (a new PoseResNet is 'auto': a differentiable forward outside
         # autocast runs bf16, the teacher's no-grad forward the fp32-grade 'f16x2' mode).
         # 'reference' = the reference's own precision mix (train_human.py:346-358,414): the student in fp16 (its autocast dtype)
@@ -413,6 +421,58 @@ class MeanTeacherTrainer:
             self._view_rad[0].copy_(torch.tensor(v, dtype=torch.float32), non_blocking=True)
             self._view_rad[1] = v
         return self._view_rad[0]
+
+    SCHEDULABLE = ("lambda_c", "lambda_ent", "lambda_coral", "teacher_alpha", "mask_ratio")
+    # the device words of sync_schedule(): fp32 [lambda_c, lambda_ent, lambda_coral, alpha, 1 - alpha], int32 [k], two spare
+    _SCHED_SLOT = {"lambda_c": 0, "lambda_ent": 1, "lambda_coral": 2, "teacher_alpha": 3, "mask_ratio": 5}
+
+    def _scheduled_names(self):
+        names = tuple(getattr(self, "scheduled", ()) or ())
+        if isinstance(getattr(self, "scheduled", ()), str):
+            names = (self.scheduled,)
+        bad = [n for n in names if n not in self.SCHEDULABLE]
+        if bad:
+            raise ValueError(f"trainer.scheduled = {names!r}: {bad} cannot be scheduled; the names are {self.SCHEDULABLE}")
+        return names
+
+    def _schedule_words(self, names):
+        """The eight 32-bit words the device holds for the scheduled names (slots of the others stay zero): an fp32 array whose word 5 is k's int32."""
+        w = np.zeros(8, dtype=np.float32)
+        for n in ("lambda_c", "lambda_ent", "lambda_coral"):
+            if n in names:
+                w[self._SCHED_SLOT[n]] = float(getattr(self, n))
+        if "teacher_alpha" in names:
+            w[3], w[4] = mt.ema_pair(self.tea_optimizer.alpha)      # (OldWeightEMA.step's pair: 1 - alpha in double, each rounded to fp32 here)
+        if "mask_ratio" in names and self.mask_mode != "threshold" and self._sched_pool is not None:
+            # ("threshold" ignores mask_ratio; before the first step the pool's size is unknown: that step uploads k before its own launch)
+            w.view(np.int32)[5] = mt.mask_kth_index(self.mask_ratio, self._sched_pool, self.mask_mode)
+        return w
+
+    def sync_schedule(self, device=None):
+        """The device words that hold the values of trainer.scheduled, uploaded when a host value changed (one stream-ordered 32-byte copy,
+        like sync_mask_threshold()); never inside a capture, whose launches read them.  -> None with nothing scheduled, else a dict of device
+        views: 0-d fp32 'lambda_c' / 'lambda_ent' / 'lambda_coral', fp32 [2] 'teacher_alpha' = (alpha, 1 - alpha), int32 [1] 'mask_ratio' = k."""
+        names = self._scheduled_names()
+        if not names:
+            if getattr(self.tea_optimizer, "alpha_dev", None) is not None:
+                self.tea_optimizer.alpha_dev = None
+            return None
+        w = self._schedule_words(names)
+        if self._sched is None or (device is not None and self._sched[0].device != torch.device(device)):
+            if device is None:
+                device = next(self.student.parameters()).device
+            self._sched = [torch.from_numpy(w.copy()).to(device), w.tobytes()]
+        elif w.tobytes() != self._sched[1] and not torch.cuda.is_current_stream_capturing():
+            self._sched[0].copy_(torch.from_numpy(w.copy()), non_blocking=True)
+            self._sched[1] = w.tobytes()
+        d = self._sched[0]
+        views = {n: d[self._SCHED_SLOT[n]] for n in ("lambda_c", "lambda_ent", "lambda_coral") if n in names}
+        if "teacher_alpha" in names:
+            views["teacher_alpha"] = d[3:5]
+        if "mask_ratio" in names:
+            views["mask_ratio"] = d.view(torch.int32)[5:6]
+        self.tea_optimizer.alpha_dev = views.get("teacher_alpha")
+        return views
 
     def _check_view_merge(self, k):
         """view_merge set: a mode warp.merge_views knows, and at least two teacher views to merge."""
@@ -681,23 +741,33 @@ class MeanTeacherTrainer:
             self._metrics_cb(st)                # (GraphedTrainStep: decode + PCK of the source batch on an idle side stream, under the backward)
         loss_s = self.criterion(st["y_s"], st["label_s"], st["weight_s"])
         self._check_scaler()
+        sched = None
+        if self.scheduled:
+            # the mask's pool: every gathered confidence ("global"), the gathered samples ("per_joint") - sync_schedule turns mask_ratio into k with it
+            pool = gathered_activates.numel() if gathered_activates is not None else st["activates"].numel()
+            self._sched_pool = pool // st["activates"].shape[1] if self.mask_mode == "per_joint" else pool
+            sched = self.sync_schedule(st["activates"].device)
         with torch.no_grad():
             # threshold = k-th value over the GLOBAL batch (all-gather of [N,K] floats when data parallel)
             thr_dev = self.sync_mask_threshold(st["activates"].device) if self.mask_mode == "threshold" else None
+            # (a scheduled mask_ratio: the int32 k in device memory in place of the ratio; "threshold" ignores either)
+            ratio = sched["mask_ratio"] if (sched and "mask_ratio" in sched and self.mask_mode != "threshold") else self.mask_ratio
             # (view_agree: the 0 / 1 agreement gate of the merged teacher views, absent with view_merge off)
-            tea_mask, _, mask_thr = mt.confidence_mask(st["y_t_tea_recon"], self.mask_ratio, st.get("view_agree"), gathered_activates,
+            tea_mask, _, mask_thr = mt.confidence_mask(st["y_t_tea_recon"], ratio, st.get("view_agree"), gathered_activates,
                                                        st["activates"], mode=self.mask_mode, threshold=thr_dev)
             y_t_tea_rect = st["y_t_tea_rect"] if st.get("y_t_tea_rect") is not None else mt.rectify(st["y_t_tea_recon"], sigma=self.sigma)
         loss_c = self.con_criterion(st["y_t_stu_recon"], y_t_tea_rect, tea_mask=tea_mask)
-        loss_all = loss_s + self.lambda_c * loss_c
+        # (a scheduled weight: the 0-d fp32 device tensor in place of the Python float, which the product rounds to the same fp32 value)
+        lam = {n: (sched[n] if sched and n in sched else getattr(self, n)) for n in ("lambda_c", "lambda_ent", "lambda_coral")}
+        loss_all = loss_s + lam["lambda_c"] * loss_c
         loss_ent = None
         if self.ent_criterion is not None:
             loss_ent = self.ent_criterion(st["y_t_stu_recon"])
-            loss_all = loss_all + self.lambda_ent * loss_ent
+            loss_all = loss_all + lam["lambda_ent"] * loss_ent
         loss_coral = None
         if self.coral_criterion is not None:
             loss_coral = self.coral_criterion(st["y_s"], st["y_t_stu"])
-            loss_all = loss_all + self.lambda_coral * loss_coral
+            loss_all = loss_all + lam["lambda_coral"] * loss_coral
         self.stu_optimizer.scale_loss(loss_all).backward()      # (scaler.scale(loss_all).backward(), train_human.py:436; identity in bf16)
         if s_stu is not main:
             main.wait_stream(s_stu)             # the target-domain backward ran on its own stream
@@ -753,6 +823,8 @@ class MeanTeacherTrainer:
     def _update(self):
         # the optimizer, the EMA and the next forwards' weight packs of both networks in ONE sweep when the layout allows ...
         fuse = self.fuse_tail and hasattr(self.stu_optimizer, "fused_tail_step")
+        if self.scheduled or getattr(self.tea_optimizer, "alpha_dev", None) is not None:
+            self.sync_schedule()            # (a scheduled teacher_alpha: the pair both EMA forms read; outside a capture only)
         self.fused_last = bool(fuse and self.stu_optimizer.fused_tail_step(self.student, self.teacher, self.tea_optimizer))
         if not self.fused_last:
             if hasattr(self.student, "finish_grads"):
@@ -940,7 +1012,19 @@ class GraphedTrainStep:
     Style transfer (train_human.py:345-358): each direction is its own small graph (content, style, alpha as a device scalar ->
     the step's effective input); the host draws the step's decisions in the reference's order and replays the direction(s) it
     drew, or copies the original images, before the main graph.  Occlusion (train_human.py:374-412): the decisions are taken
-    on the device from four uniform draws per sample (trainer.device_occlusion), inside the main graph."""
+    on the device from four uniform draws per sample (trainer.device_occlusion), inside the main graph.
+    Teacher views (train_human.py:361-372, `--k`): x_t_tea is one tensor, or a list / tuple of k <= 8 tensors [N,3,H,W] with aug_param_tea a
+    list of k collated tuples - here and in step() / step_async() / prefetch().  k is fixed at construction (a later call with another count:
+    ValueError).  Every view has its own static image buffer, effective-input buffer and re-warp matrices; the aug buffer is [1+k,N,6], still
+    one copy per step; the k teacher forwards, their re-warps and the one mean_views / merge_views launch stay on the teacher's stream, in
+    order, as in the eager step (the teacher's BatchNorm statistics advance k times).  trainer.view_merge needs k >= 2; a captured merge
+    follows trainer.view_radius (step() calls sync_view_radius()); view_merge, view_min and k are frozen.  Style: one pair of draws per step;
+    every view is summarised only when t2s was drawn (the first otherwise), t2s transfers every view into its own buffer.
+    Scheduled values (trainer.scheduled): lambda_c / lambda_ent / lambda_coral, teacher_alpha and mask_ratio named there are
+    read from device memory by the captured launches; step() calls trainer.sync_schedule() before the replay, and changing them is no
+    longer refused.  Names not listed stay frozen, and so does the list itself."""
+
+    k, _sfx = 1, [""]           # teacher views per step, and the suffix of view i's static keys ("" for view 0): set by the constructor
 
     def __init__(self, trainer, x_s, label_s, weight_s, x_t_stu, x_t_tea, aug_param_stu, aug_param_tea, warmup=2, split=None, metrics=True,
                  capture_comm=None):
@@ -952,6 +1036,7 @@ class GraphedTrainStep:
         self._mvec, self._mpin, self._mev, self._mi, self._mk, self._macc, self._mextra = None, None, [None, None], 0, 0, None, []
         # other threads (the RCCL watchdog of torch.distributed) may touch the runtime while this thread captures
         self._mode = "thread_local" if _dist_on() else "global"
+        x_t_tea, aug_param_tea = self._views(x_t_tea, aug_param_tea, fix_k=True)
         self._refuse_uncapturable(x_t_stu)
         self._allocate_static(x_s, label_s, weight_s, x_t_stu, x_t_tea, aug_param_stu, aug_param_tea)
         self._warm_up(warmup)
@@ -963,13 +1048,51 @@ class GraphedTrainStep:
         self._capture_update()
         self._after_capture()
 
+    @staticmethod
+    def _is_collated(ap):
+        """One collated aug_param, (angle, (tx, ty), (shear_x, shear_y), scale) - as against a list of them, one per view."""
+        try:
+            return len(ap) == 4 and len(ap[1]) == 2 and len(ap[2]) == 2
+        except TypeError:
+            return False
+
+    def _views(self, x_t_tea, aug_param_tea, fix_k=False):
+        """The two call forms of the teacher's side -> (list of k images | None, list of k collated aug_params | None).  fix_k: the
+        constructor's call, which sets self.k; afterwards another count is a ValueError naming both."""
+        single = x_t_tea is not None and not isinstance(x_t_tea, (list, tuple))
+        if single:
+            x_t_tea = [x_t_tea]
+        if aug_param_tea is not None:
+            if self._is_collated(aug_param_tea):
+                aug_param_tea = [aug_param_tea]
+            elif single and not (isinstance(aug_param_tea, (list, tuple)) and len(aug_param_tea) > 0
+                                 and all(self._is_collated(ap) for ap in aug_param_tea)):
+                # (with one image tensor anything that is not a list of collated tuples is taken as the tuple itself, as before:
+                # pack_aug_param names what is wrong with it; a list of them is counted below)
+                aug_param_tea = [aug_param_tea]
+        for name, v in (("x_t_tea", x_t_tea), ("aug_param_tea", aug_param_tea)):
+            if v is None:
+                continue
+            if len(v) > 8:
+                raise NotImplementedError("at most 8 teacher views per step (the reference's --k defaults to 1)")
+            if fix_k and name == "x_t_tea":
+                if len(v) < 1:
+                    raise ValueError("GraphedTrainStep: no teacher view given")
+                self.k = len(v)
+            if len(v) != self.k:
+                raise ValueError(f"GraphedTrainStep was built with k = {self.k} teacher view(s) per step and is called with {len(v)} in {name}: "
+                                 "k is fixed at construction - build a new GraphedTrainStep for another count")
+        return (list(x_t_tea) if x_t_tea is not None else None), (list(aug_param_tea) if aug_param_tea is not None else None)
+
     def _refuse_uncapturable(self, x_t_stu):
         t = self.t
         self._style = _StyleAdapter(t.style_net, captured=True) if t.style_net is not None else None     # (TypeError: a net with the plain call only)
-        if t.view_merge is not None:
-            raise ValueError(f"GraphedTrainStep stages a single teacher view per step, and trainer.view_merge = {t.view_merge!r} merges k >= 2 "
-                             "of them: use the eager train_step (the merge launch itself is capturable: warp.merge_views), or set "
-                             "trainer.view_merge = None before building the captured step")
+        if t.view_merge is not None and self.k < 2:
+            raise ValueError(f"GraphedTrainStep was given a single teacher view per step, and trainer.view_merge = {t.view_merge!r} merges "
+                             "k >= 2 of them: pass a list of k >= 2 target views (and their aug_params), or set trainer.view_merge = None "
+                             "before building the captured step")
+        t._check_view_merge(self.k)         # (a mode warp.merge_views does not know)
+        t._scheduled_names()                # (ValueError: a name that cannot be scheduled)
         self.styled, self.occl = self._style is not None, t.occlude_rate > -1
         if self.occl and not t.device_occlusion:
             raise RuntimeError("GraphedTrainStep with occlusion needs trainer.device_occlusion = True (the reference's host draws read "
@@ -986,16 +1109,22 @@ class GraphedTrainStep:
         dev, n = x_s.device, x_s.shape[0]
         self.n = n
         # The re-warp matrices are computed INSIDE the captured step (udapose_recon_thetas, double precision) from the batch's raw
-        # aug_param values: per step the host packs 2 x N x 6 doubles into a pinned buffer and issues one asynchronous copy.
-        st = self.static = {k: v.clone() for k, v in zip(_INPUTS, (x_s, label_s, weight_s, x_t_stu, x_t_tea))}
-        st.update(aug=torch.empty(2, n, 6, dtype=torch.float64, device=dev), theta_stu=torch.empty(n, 3, 6, dtype=torch.float32, device=dev),
-                  theta_tea=torch.empty(n, 3, 6, dtype=torch.float32, device=dev))
-        self._aug_pin = [torch.empty(2, n, 6, dtype=torch.float64).pin_memory() for _ in range(4)]
+        # aug_param values: per step the host packs (1 + k) x N x 6 doubles into a pinned buffer and issues one asynchronous copy.
+        # View i of the teacher has the static keys x_t_tea / x_t_tea_in / theta_tea with the suffix "" (view 0) or str(i).
+        k = self.k
+        self._sfx = [""] + [str(i) for i in range(1, k)]
+        self._in_keys = _INPUTS[:4] + tuple("x_t_tea" + s for s in self._sfx)
+        st = self.static = {key: v.clone() for key, v in zip(self._in_keys, (x_s, label_s, weight_s, x_t_stu) + tuple(x_t_tea))}
+        st.update(aug=torch.empty(1 + k, n, 6, dtype=torch.float64, device=dev), theta_stu=torch.empty(n, 3, 6, dtype=torch.float32, device=dev))
+        for s in self._sfx:
+            st["theta_tea" + s] = torch.empty(n, 3, 6, dtype=torch.float32, device=dev)
+        self._aug_pin = [torch.empty(1 + k, n, 6, dtype=torch.float64).pin_memory() for _ in range(4)]
         self._aug_ev, self._aug_i, self._aug_last = [None] * 4, 0, None
         self._stage_aug(aug_param_stu, aug_param_tea)
         # the main graph reads the step's EFFECTIVE inputs: the originals, or what the style graphs wrote
         st["x_s_in"] = st["x_s"].clone() if self.styled else st["x_s"]
-        st["x_t_tea_in"] = st["x_t_tea"].clone() if self.styled else st["x_t_tea"]
+        for s in self._sfx:
+            st["x_t_tea_in" + s] = st["x_t_tea" + s].clone() if self.styled else st["x_t_tea" + s]
         if self.styled:
             st["alpha_s2t"] = torch.ones(1, dtype=torch.float32, device=dev)
             st["alpha_t2s"] = torch.ones(1, dtype=torch.float32, device=dev)
@@ -1007,7 +1136,8 @@ class GraphedTrainStep:
     def _step_args(self):
         """What the trainer's _forward_backward / _forward_part are called with, in the warm-up steps and in every capture."""
         st = self.static
-        return st["x_s_in"], st["label_s"], st["weight_s"], st["x_t_stu"], [st["x_t_tea_in"]], st["theta_stu"], [st["theta_tea"]]
+        return (st["x_s_in"], st["label_s"], st["weight_s"], st["x_t_stu"], [st["x_t_tea_in" + s] for s in self._sfx], st["theta_stu"],
+                [st["theta_tea" + s] for s in self._sfx])
 
     def _warm_up(self, warmup):
         t, dev = self.t, self.static["x_s"].device
@@ -1016,7 +1146,7 @@ class GraphedTrainStep:
         self.g_style = {}
         self._cap = {"stream": torch.cuda.Stream(device=dev, priority=t.stream_priority)} if t.stream_priority else {}
         with torch.cuda.stream(side):
-            for which in ("enc", "s2t", "t2s") if self.styled else ():      # (the style net's plans and packs; no model state involved)
+            for which in self._style_graphs():      # (the style net's plans and packs; no model state involved)
                 self._style_pass(which)
             for _ in range(warmup):     # REAL steps (same host draws as step()): fill the plan / table caches, allocator steady state
                 self._thetas()
@@ -1053,8 +1183,15 @@ class GraphedTrainStep:
         finally:
             self.t._metrics_cb = None
 
+    def _style_graphs(self):
+        """The style graphs of this step, in the order they are first run: "enc_rest" (the summaries of views 1 .. k-1, needed by t2s alone)
+        exists only with k >= 2."""
+        if not self.styled:
+            return ()
+        return ("enc",) + (("enc_rest",) if self.k > 1 else ()) + ("s2t", "t2s")
+
     def _capture_style(self):
-        for which in ("enc", "s2t", "t2s") if self.styled else ():
+        for which in self._style_graphs():
             g = torch.cuda.CUDAGraph()
             with self._capturing(g, pool=self.g_style["enc"].pool() if self.g_style else None, origin=False):
                 self._style_pass(which)
@@ -1085,6 +1222,10 @@ class GraphedTrainStep:
             t.sync_mask_threshold(self.static["x_s"].device)    # (the captured mask launch reads this scalar: it exists, and is current, before the capture)
         if t.adv_eps is not None:
             t.sync_adv(self.static["x_s"].device)               # (likewise the perturbation's eps / step)
+        if t.view_merge is not None:
+            t.sync_view_radius(self.static["x_s"].device)       # (likewise the merge's radius)
+        if t.scheduled:
+            t.sync_schedule(self.static["x_s"].device)          # (likewise the words of the scheduled values)
         t.student._capture_token = t.teacher._capture_token = object()      # weight packs: captured once per network, unconditionally (pose_resnet._pack)
         self.g_fb, self.g_lb, self.g_lb2, self.g_up = torch.cuda.CUDAGraph(), None, None, None
         # overlap: the backward is cut after layer3 (two graph segments) and the finished gradient suffix is all-reduced on
@@ -1305,8 +1446,8 @@ class GraphedTrainStep:
         return {k: round(tot[k] / cnt[k], 3) for k in tot}
 
     def _stage_aug(self, aug_param_stu=None, aug_param_tea=None):
-        """The batch's raw aug_param values -> the static [2,N,6] float64 device buffer the captured udapose_recon_thetas launches
-        read (a ring of pinned host buffers and one asynchronous copy: nothing here waits for the device)."""
+        """The batch's raw aug_param values -> the static [1+k,N,6] float64 device buffer the captured udapose_recon_thetas launches
+        read (a ring of pinned host buffers and one asynchronous copy: nothing here waits for the device).  aug_param_tea: a list of k."""
         if aug_param_stu is None and aug_param_tea is None:
             return
         i = self._aug_i = (self._aug_i + 1) % len(self._aug_pin)
@@ -1317,8 +1458,8 @@ class GraphedTrainStep:
             pin.copy_(self._aug_last)                 # a side that is not given keeps its previous values
         if aug_param_stu is not None:
             warp.pack_aug_param(aug_param_stu, self.n, out=pin[0])
-        if aug_param_tea is not None:
-            warp.pack_aug_param(aug_param_tea, self.n, out=pin[1])
+        for v, ap in enumerate(aug_param_tea or ()):      # (view v; `i` stays the ring slot the event below is kept in)
+            warp.pack_aug_param(ap, self.n, out=pin[1 + v])
         self.static["aug"].copy_(pin, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -1330,17 +1471,20 @@ class GraphedTrainStep:
         of the stem's fp32 atomics often enough to break the bit-for-bit twins of tests/test_gpu_steps.py; reverted.)"""
         st, r = self.static, self.t.ratio
         warp.thetas_from_packed(st["aug"][0], r, want_fwd=True, want_back=self.occl, fwd=st["theta_stu"], back=st.get("theta_back"))
-        warp.thetas_from_packed(st["aug"][1], r, fwd=st["theta_tea"])
+        for i, s in enumerate(self._sfx):
+            warp.thetas_from_packed(st["aug"][1 + i], r, fwd=st["theta_tea" + s])
 
     def _style_pass(self, which):
         """"enc": the summaries (_StyleAdapter: relu4_1 features, or low-frequency spectra) of both ORIGINAL batches into static buffers, once per
-        step whichever directions are drawn; "s2t" / "t2s": one direction's transfer from those summaries into the main graph's input buffer."""
+        step whichever directions are drawn ("enc_rest": of the teacher's views 1 .. k-1, when t2s was drawn - _style_part's rule);
+        "s2t" / "t2s": one direction's transfer from those summaries into the main graph's input buffer(s), t2s for every view."""
         if which in self.g_style:       # (captured by now: replay it)
             return self.g_style[which].replay()
         st, style, (k_s, k_t) = self.static, self._style, self._style.keys
         with torch.no_grad():
-            if which == "enc":
-                for img, key in (("x_s", k_s), ("x_t_tea", k_t)):
+            if which in ("enc", "enc_rest"):
+                todo = (("x_s", k_s), ("x_t_tea", k_t)) if which == "enc" else tuple(("x_t_tea" + s, k_t + s) for s in self._sfx[1:])
+                for img, key in todo:
                     if key in st:
                         style.summarize(st[img], out=st[key])
                     else:       # (the first, uncaptured pass: a buffer of its own, not the net's arena)
@@ -1348,7 +1492,8 @@ class GraphedTrainStep:
             elif which == "s2t":
                 style.transfer(st["x_s"], st[k_s], st[k_t], st["alpha_s2t"], self.t.recover, out=st["x_s_in"])
             else:
-                style.transfer(st["x_t_tea"], st[k_t], st[k_s], st["alpha_t2s"], self.t.recover, out=st["x_t_tea_in"])
+                for s in self._sfx:
+                    style.transfer(st["x_t_tea" + s], st[k_t + s], st[k_s], st["alpha_t2s"], self.t.recover, out=st["x_t_tea_in" + s])
 
     def _draw_and_style(self):
         """The step's host draws, in the eager step's (= the reference's) order, and what follows from them: each style direction drawn runs (its
@@ -1358,12 +1503,16 @@ class GraphedTrainStep:
             decisions = self.t.draw_style_decisions()
             if any(a is not None for a in decisions):
                 self._style_pass("enc")
-            for which, a, src in zip(("s2t", "t2s"), decisions, (("x_s_in", "x_s"), ("x_t_tea_in", "x_t_tea"))):
+                if decisions[1] is not None and self.k > 1:
+                    self._style_pass("enc_rest")
+            pairs = ((("x_s_in", "x_s"),), tuple(("x_t_tea_in" + s, "x_t_tea" + s) for s in self._sfx))
+            for which, a, srcs in zip(("s2t", "t2s"), decisions, pairs):
                 if a is not None:
                     st["alpha_" + which].fill_(float(a))
                     self._style_pass(which)
                 else:
-                    st[src[0]].copy_(st[src[1]], non_blocking=True)
+                    for dst, src in srcs:
+                        st[dst].copy_(st[src], non_blocking=True)
         if self.occl:
             st["u"].copy_(self.t.draw_occlusion_uniforms(self.n), non_blocking=True)
 
@@ -1384,9 +1533,14 @@ class GraphedTrainStep:
 
     def _frozen_hyper(self):
         t, opt = self.t, self.t.stu_optimizer
-        frozen = [("teacher_alpha", float(t.tea_optimizer.alpha)), ("lambda_c", float(t.lambda_c)), ("mask_ratio", float(t.mask_ratio)),
-                  ("sigma", float(t.sigma)), ("bn_momentum", float(t.student.bn_momentum)), ("occlude_rate", float(t.occlude_rate)),
-                  ("occlude_thresh", float(t.occlude_thresh)), ("occlude_size", int(t.occlude_size)), ("warp_mode", str(t.warp_mode))]
+        # a name in trainer.scheduled is read from device memory by the captured launches (sync_schedule) and may change freely; the list itself
+        # decides which launches were captured and is frozen
+        scheduled = t._scheduled_names()
+        frozen = [("teacher_alpha", float(t.tea_optimizer.alpha)), ("lambda_c", float(t.lambda_c)), ("mask_ratio", float(t.mask_ratio))]
+        frozen = [f for f in frozen if f[0] not in scheduled]
+        frozen += [("sigma", float(t.sigma)), ("bn_momentum", float(t.student.bn_momentum)), ("occlude_rate", float(t.occlude_rate)),
+                   ("occlude_thresh", float(t.occlude_thresh)), ("occlude_size", int(t.occlude_size)), ("warp_mode", str(t.warp_mode)),
+                   ("scheduled", scheduled)]
         for gi, g in enumerate(opt.param_groups):
             for k in ("betas", "eps", "weight_decay", "momentum", "nesterov"):
                 if k in g:
@@ -1399,8 +1553,9 @@ class GraphedTrainStep:
         # live on the device and may change freely (sync_adv)
         frozen += [("adv_eps enabled", t.adv_eps is not None), ("adv_norm", str(t.adv_norm)), ("adv_steps", int(t.adv_steps)),
                    ("adv_step given", t.adv_step is not None)]
-        # the merge of k teacher views is refused at construction (_refuse_uncapturable): it cannot be switched on afterwards either
-        frozen.append(("view_merge", t.view_merge))
+        # the merge of k teacher views: on / off, the mode and view_min pick the launch and its arguments, k the static buffers; view_radius
+        # lives on the device and may change freely (sync_view_radius)
+        frozen += [("view_merge", t.view_merge), ("view_min", t.view_min), ("k", self.k)]
         for name, crit in (("criterion", t.criterion), ("con_criterion", t.con_criterion)):
             for k in ("topk", "largest"):
                 if hasattr(crit, k):
@@ -1410,21 +1565,23 @@ class GraphedTrainStep:
     def prefetch(self, x_s, label_s, weight_s, x_t_stu, x_t_tea):
         """Start copying the NEXT batch (pinned host tensors) into staging buffers on a copy stream; it overlaps with the
         replay of the current step.  The following step() call (with no tensors given) takes the staged batch with five
-        device-to-device copies (92 MB, ~30 us) instead of waiting for PCIe on the compute stream."""
+        device-to-device copies (92 MB, ~30 us) instead of waiting for PCIe on the compute stream.  x_t_tea: a tensor or a list of k."""
+        x_t_tea, _ = self._views(x_t_tea, None)
         if self._stage is None:
-            self._stage = {k: torch.empty_like(self.static[k]) for k in _INPUTS}
+            self._stage = {k: torch.empty_like(self.static[k]) for k in self._in_keys}
             self._copy_stream = torch.cuda.Stream(device=self.static["x_s"].device)
             self._staged, self._consumed = torch.cuda.Event(), None
         if self._consumed is not None:
             self._copy_stream.wait_event(self._consumed)     # the previous step's D2D reads of the staging buffers come first
         with torch.cuda.stream(self._copy_stream):
-            for k, v in zip(_INPUTS, (x_s, label_s, weight_s, x_t_stu, x_t_tea)):
+            for k, v in zip(self._in_keys, (x_s, label_s, weight_s, x_t_stu) + tuple(x_t_tea)):
                 self._stage[k].copy_(v, non_blocking=True)
             self._staged.record(self._copy_stream)
         self._have_staged = True
 
     def step(self, x_s=None, label_s=None, weight_s=None, x_t_stu=None, x_t_tea=None, aug_param_stu=None, aug_param_tea=None):
         st = self.static
+        x_t_tea, aug_param_tea = self._views(x_t_tea, aug_param_tea)
         if x_s is None and self._have_staged:
             torch.cuda.current_stream().wait_event(self._staged)
             for k in self._stage:
@@ -1432,13 +1589,14 @@ class GraphedTrainStep:
             self._consumed = torch.cuda.Event()
             self._consumed.record()
             self._have_staged = False
-        for k, v in zip(_INPUTS, (x_s, label_s, weight_s, x_t_stu, x_t_tea)):
+        for k, v in zip(self._in_keys, (x_s, label_s, weight_s, x_t_stu) + tuple(x_t_tea or (None,) * self.k)):
             if v is not None and v.data_ptr() != st[k].data_ptr():
                 st[k].copy_(v, non_blocking=True)
         self._stage_aug(aug_param_stu, aug_param_tea)
         frozen_now = self._frozen_hyper()
         if frozen_now != self._frozen:
-            changed = [a[0] for a, b in zip(frozen_now, self._frozen) if a != b]
+            old, now = dict(self._frozen), dict(frozen_now)     # (by name: a change of trainer.scheduled moves names in and out of the list)
+            changed = [n for n in now if n not in old or old[n] != now[n]] + [n for n in old if n not in now]
             raise RuntimeError(f"GraphedTrainStep: {changed} changed after capture; these are baked into the captured launches - "
                                "build a new GraphedTrainStep (lr and grad_scale may change freely)")
         if self._optimizer_key() != self._opt_key:
@@ -1460,6 +1618,10 @@ class GraphedTrainStep:
             self.t.sync_mask_threshold()         # a curriculum ramp of mask_threshold -> the device scalar the captured mask launch reads
         if self.t.adv_eps is not None:
             self.t.sync_adv()                    # adv_eps / adv_step -> the device scalars the captured perturb launches read
+        if self.t.view_merge is not None:
+            self.t.sync_view_radius()            # view_radius -> the device scalar the captured merge launch reads
+        if self.t.scheduled:
+            self.t.sync_schedule()               # ramped loss weights / teacher_alpha / mask_ratio -> the device words the captured launches read
         if self.one_graph:
             self.t.stu_optimizer.sync_hyper()    # lr scheduler / loss scale -> device state read by the captured sweep
         self.g_fb.replay()

@@ -337,9 +337,15 @@ class _FusedBase(torch.optim.Optimizer):
         self._pre_sweep(got[0][1], ents[0], delta)         # (loss scaling: one group)
         b1, b2, eps, nesterov = self._tail_hyper(groups[0])
         wds = (C.c_float * len(groups))(*[float(g["weight_decay"]) for g in groups])
-        check(hd_s.L.udapose_net_fused_update_groups(hd_s.h, hd_t.h, _hip.stream(), self._tail_kind, pa_s, ga, ma, pa_t, ptr(hd_s.wpack),
-                                                     ptr(hd_t.wpack), b1, b2, eps, nesterov, len(groups), states, wds, float(ema.alpha),
-                                                     float(1.0 - ema.alpha), 1, int(delta)), "net_fused_update_groups")
+        ema_dev = getattr(ema, "alpha_dev", None)
+        if ema_dev is not None:         # (a scheduled teacher_alpha: the sweep reads {alpha, 1 - alpha} from device memory - the same two fp32 values)
+            check(hd_s.L.udapose_net_fused_update_groups_dev(hd_s.h, hd_t.h, _hip.stream(), self._tail_kind, pa_s, ga, ma, pa_t, ptr(hd_s.wpack),
+                                                             ptr(hd_t.wpack), b1, b2, eps, nesterov, len(groups), states, wds, ptr(ema_dev), 1,
+                                                             int(delta)), "net_fused_update_groups_dev")
+        else:
+            check(hd_s.L.udapose_net_fused_update_groups(hd_s.h, hd_t.h, _hip.stream(), self._tail_kind, pa_s, ga, ma, pa_t, ptr(hd_s.wpack),
+                                                         ptr(hd_t.wpack), b1, b2, eps, nesterov, len(groups), states, wds, float(ema.alpha),
+                                                         float(1.0 - ema.alpha), 1, int(delta)), "net_fused_update_groups")
         if clip is not None:
             self._clip_end(clip)
         return self._tail_finish(student, teacher, hd_s, hd_t, ps, tps, t_split, ents[0])

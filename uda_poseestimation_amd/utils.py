@@ -50,6 +50,10 @@ class OldWeightEMA(object):
         self.target_params = list(target_net.parameters())
         self.source_params = list(source_net.parameters())
         self.alpha = alpha
+        # None, or a 2-element fp32 DEVICE tensor holding ema_pair(alpha): the sweeps then read the pair from it (udapose_ema_multi_dev, the
+        # _dev forms of the fused tail), so that a captured launch follows a ramped alpha.  Whoever sets it keeps it current
+        # (MeanTeacherTrainer.sync_schedule with "teacher_alpha" in trainer.scheduled).
+        self.alpha_dev = None
         self._table = None
         for p, src_p in zip(self.target_params, self.source_params):
             p.data[:] = src_p.data[:]
@@ -66,10 +70,64 @@ class OldWeightEMA(object):
         if self._table is None or self._table.key != key:
             self._table = _MultiTensorTable([tp, sp])
         t = self._table
-        one_minus_alpha = 1.0 - self.alpha
-        check(lib().udapose_ema_multi(_hip.stream(), ptr(t.ptrs[0]), ptr(t.ptrs[1]), ptr(t.sizes), ptr(t.blk_t), ptr(t.blk_o), t.nblocks,
-                                      float(self.alpha), float(one_minus_alpha)), "ema_multi")
+        if self.alpha_dev is not None:
+            check(lib().udapose_ema_multi_dev(_hip.stream(), ptr(t.ptrs[0]), ptr(t.ptrs[1]), ptr(t.sizes), ptr(t.blk_t), ptr(t.blk_o), t.nblocks,
+                                              ptr(self.alpha_dev)), "ema_multi_dev")
+        else:
+            alpha, one_minus_alpha = ema_pair(self.alpha)
+            check(lib().udapose_ema_multi(_hip.stream(), ptr(t.ptrs[0]), ptr(t.ptrs[1]), ptr(t.sizes), ptr(t.blk_t), ptr(t.blk_o), t.nblocks,
+                                          alpha, one_minus_alpha), "ema_multi")
         _bump_versions(self.target_params)
+
+
+def ema_pair(alpha):
+    """(alpha, 1 - alpha) as OldWeightEMA.step hands them to its kernel: the subtraction in Python double (utils.py:22), each value then
+    rounded to fp32 by the call (by-value) or by the upload (device form) - the same two fp32 numbers either way."""
+    return float(alpha), float(1.0 - alpha)
+
+
+# ---------------------------------------------------------------------- ramps (the names of utils.py:28-52), host scalars
+# Every value is formed by the same double-precision operations in the same order as the reference's, so the results are its bits
+# (tests/golden/ramps.npz); the clipping, the curve and the conversion to a Python float are stated once each.
+def _clipped(x, upper):
+    """x held inside [0, upper], as a numpy double."""
+    return np.clip(x, 0.0, upper)
+
+
+def _falling_logistic(z):
+    """1 / (1 + e^z): from 1 (z -> -inf) down to 0."""
+    return float(1.0 / (1.0 + np.exp(z)))
+
+
+def sigmoid_rampup(current, rampup_length):
+    """exp(-5 (1 - t / L)^2) with t = current clipped to [0, L]: the rise of Laine & Aila (arXiv:1610.02242) from exp(-5) to 1; L == 0: 1."""
+    if rampup_length == 0:
+        return 1.0
+    remaining = 1.0 - _clipped(current, rampup_length) / rampup_length      # the share of the ramp still ahead, 1 -> 0
+    return float(np.exp((-5.0 * remaining) * remaining))
+
+
+def cosine_rampdown(current, rampdown_length):
+    """(cos(pi t / L) + 1) / 2 with t = current clipped to [0, L]: the half cosine of SGDR (arXiv:1608.03983), 1 down to 0.  L == 0 is NaN,
+    the reference's 0 / 0."""
+    angle = (np.pi * _clipped(current, rampdown_length)) / rampdown_length   # 0 -> pi
+    return float(0.5 * (np.cos(angle) + 1.0))
+
+
+def rev_sigmoid(progress):
+    """1 / (1 + exp(10 p - 5)), p = progress clipped to [0, 1]: the logistic curve falling from ~0.993 to ~0.007."""
+    return _falling_logistic(10.0 * _clipped(progress, 1.0) - 5.0)
+
+
+def sigmoid(progress):
+    """1 / (1 + exp(5 - 10 p)), p = progress clipped to [0, 1]: the logistic curve rising from ~0.007 to ~0.993 (rev_sigmoid mirrored)."""
+    return _falling_logistic(5.0 - 10.0 * _clipped(progress, 1.0))
+
+
+def ema_alpha_warmup(step, alpha):
+    """min(1 - 1 / (step + 1), alpha): the EMA rate of the original mean teacher, which follows the student closely for the first steps
+    (0 at step 0: the teacher is the student) and settles at alpha."""
+    return min(1.0 - 1.0 / (step + 1), alpha)
 
 
 def _bump_versions(params):
@@ -123,6 +181,16 @@ def activations_and_rectify(recon, sigma):
 MASK_MODES = ("global", "per_joint", "threshold")
 
 
+def mask_kth_index(mask_ratio, n_pool, mode="global"):
+    """The k of confidence_mask: int(mask_ratio * n_pool), 1-indexed into the ascending order of the pool (n_pool: every pooled value in
+    "global" mode, the pooled samples in "per_joint" mode); outside 1 ... n_pool: ValueError."""
+    k = int(mask_ratio * n_pool)
+    if k < 1 or k > n_pool:
+        raise ValueError(f"confidence_mask(mode={mode!r}): k = int(mask_ratio * n_pool) = int({mask_ratio} * {n_pool}) = {k} is outside "
+                         f"1 ... {n_pool}")
+    return k
+
+
 def confidence_mask(recon, mask_ratio, tea_mask=None, gathered_activates=None, activates=None, *, mode="global", threshold=None):
     """train_human.py:427-430 without the host round trip: activates = amax_{hw}(recon); thr = k-th smallest with
     k = int(mask_ratio * numel); mask = (tea_mask * activates) > thr.  `gathered_activates` (all ranks' activates,
@@ -130,45 +198,59 @@ def confidence_mask(recon, mask_ratio, tea_mask=None, gathered_activates=None, a
     mode="global" is that, the reference's single batch-wide threshold.  mode="per_joint": one threshold per joint (class-balanced
     self-training) - thr[j] = the k-th smallest of joint j's confidences over the pool's samples (all ranks' with `gathered_activates`),
     k = int(mask_ratio * n_pool) >= 1, thr returned as [K].  mode="threshold": mask = (tea_mask * activates) > threshold, a float or a
-    0-d device tensor (read on the device: no synchronisation, and a captured launch follows its value); mask_ratio is ignored."""
+    0-d device tensor (read on the device: no synchronisation, and a captured launch follows its value); mask_ratio is ignored.
+    mask_ratio may also be a one-element int32 DEVICE tensor ("global" / "per_joint"): it then holds k itself,
+    k = mask_kth_index(ratio, n_pool, mode), and the launch reads it from device memory (udapose_kth_mask_dev /
+    udapose_joint_kth_mask_dev), so that a captured launch follows a ramped ratio."""
+    k_dev = None
+    if torch.is_tensor(mask_ratio):
+        k_dev = mask_ratio
     if mode not in MASK_MODES:
         raise ValueError(f"confidence_mask: mode {mode!r}: one of {MASK_MODES}")
     if mode == "threshold" and threshold is None:
         raise ValueError("confidence_mask: mode='threshold' needs threshold= (a float or a 0-d device tensor)")
+    if k_dev is not None and (k_dev.dtype != torch.int32 or k_dev.numel() != 1):
+        raise ValueError("confidence_mask: a tensor mask_ratio must be a one-element int32 device tensor that holds k")
     if mode != "global":
-        return _confidence_mask_select(recon, mask_ratio, tea_mask, gathered_activates, activates, mode, threshold)
+        return _confidence_mask_select(recon, mask_ratio, tea_mask, gathered_activates, activates, mode, threshold, k_dev)
     act = heatmap_activations(recon) if activates is None else activates
     B, K = act.shape
     pool = act.reshape(-1) if gathered_activates is None else gathered_activates.detach().float().reshape(-1).contiguous()
-    k = int(mask_ratio * pool.numel())
     mask = torch.empty(B, K, dtype=torch.uint8, device=act.device)
     thr = torch.empty((), dtype=torch.float32, device=act.device)
     tm = None if tea_mask is None else tea_mask.detach().float().contiguous()
+    if k_dev is not None:
+        _hip.require_cuda(k_dev)
+        check(lib().udapose_kth_mask_dev(_hip.stream(), ptr(pool), ptr(tm), pool.numel(), ptr(k_dev), ptr(thr), ptr(mask), ptr(act), B * K),
+              "kth_mask_dev")
+        return mask.view(torch.bool), act, thr
+    k = int(mask_ratio * pool.numel())
     check(lib().udapose_kth_mask(_hip.stream(), ptr(pool), ptr(tm), pool.numel(), k, ptr(thr), ptr(mask), ptr(act), B * K), "kth_mask")
     return mask.view(torch.bool), act, thr        # (the kernel writes 0 / 1: a bool view, not a conversion launch)
 
 
-def _confidence_mask_select(recon, mask_ratio, tea_mask, gathered_activates, activates, mode, threshold):
+def _confidence_mask_select(recon, mask_ratio, tea_mask, gathered_activates, activates, mode, threshold, k_dev=None):
     """The per-joint and fixed-threshold forms of confidence_mask (csrc/select.hip): one launch behind the arg-max sweep."""
     B, K = (activates if activates is not None else recon).shape[:2]
     if mode == "per_joint":
         if gathered_activates is not None and gathered_activates.numel() % K:
             raise ValueError(f"confidence_mask: gathered_activates has {gathered_activates.numel()} elements, no multiple of K = {K}")
         n_pool = B if gathered_activates is None else gathered_activates.numel() // K
-        k = int(mask_ratio * n_pool)
-        if k < 1 or k > n_pool:
-            raise ValueError(f"confidence_mask(mode='per_joint'): k = int(mask_ratio * n_pool) = int({mask_ratio} * {n_pool}) = {k} is outside "
-                             f"1 ... {n_pool}")
+        k = mask_kth_index(mask_ratio, n_pool, mode) if k_dev is None else 0
     elif torch.is_tensor(threshold) and threshold.numel() != 1:
         raise ValueError(f"confidence_mask: threshold must be a float or a 0-d tensor, got shape {tuple(threshold.shape)}")
-    _hip.require_cuda(recon, tea_mask, gathered_activates, activates, threshold if torch.is_tensor(threshold) else None)
+    _hip.require_cuda(recon, tea_mask, gathered_activates, activates, threshold if torch.is_tensor(threshold) else None, k_dev)
     act = heatmap_activations(recon) if activates is None else activates.detach().float().contiguous()
     mask = torch.empty(B, K, dtype=torch.uint8, device=act.device)
     tm = None if tea_mask is None else tea_mask.detach().float().contiguous()
     if mode == "per_joint":
         pool = act if gathered_activates is None else gathered_activates.detach().float().reshape(-1).contiguous()
         thr = torch.empty(K, dtype=torch.float32, device=act.device)
-        check(lib().udapose_joint_kth_mask(_hip.stream(), ptr(pool), n_pool, K, k, ptr(tm), ptr(act), B, ptr(thr), ptr(mask)), "joint_kth_mask")
+        if k_dev is not None:
+            check(lib().udapose_joint_kth_mask_dev(_hip.stream(), ptr(pool), n_pool, K, ptr(k_dev), ptr(tm), ptr(act), B, ptr(thr), ptr(mask)),
+                  "joint_kth_mask_dev")
+        else:
+            check(lib().udapose_joint_kth_mask(_hip.stream(), ptr(pool), n_pool, K, k, ptr(tm), ptr(act), B, ptr(thr), ptr(mask)), "joint_kth_mask")
     else:
         if torch.is_tensor(threshold):
             thr = threshold.detach().reshape(())
