@@ -871,6 +871,22 @@ int udapose_affine_nearest(void* stream, const float* src, float* dst, const flo
  * (UDAPOSE_ERR_UNSUPPORTED). */
 int udapose_affine_bilinear(void* stream, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage,
                             int backward);
+/* MIRRORED VIEWS: the two chains above for views that are A(M(base)), M = the reversal of the columns.  mirror [N] holds two
+ * bits per sample: UDAPOSE_MIRROR_OUT - dst[n][c][y][x] = chain(src[n][p(c)])[y][W-1-x], the mirror after the chain (a heat-map re-warp back to
+ * the base frame); UDAPOSE_MIRROR_IN - dst = chain(M(src[n][p(c)])), the mirror ahead of the chain (the way back to the view).  perm [C] int
+ * (may be NULL: p = identity) is the joint permutation of the flip, an INVOLUTION with values in [0, C) - the caller checks it; it is applied
+ * to a sample when exactly one of the two bits is set.  The mirror is an index map and does no arithmetic: forward and backward give the bits
+ * of the composition of the plain entry point with the column reversal and the channel selection, a sample whose byte is 0 the bits of the
+ * plain launch.  backward != 0: the exact transpose (src = d(out), dst = d(in)); the deterministic nearest form still adds in ascending index
+ * of the chain's own output pixel, the bilinear gather in the raster order of the chain's own output.  src and dst must not overlap.
+ * mirror == NULL: UDAPOSE_ERR_ARG.  Dispatch as for the plain entry points, except that a bilinear plane beyond the LDS budget
+ * (2 * H * W * 4 > 150 KB) is refused with UDAPOSE_ERR_UNSUPPORTED. */
+#define UDAPOSE_MIRROR_OUT 1
+#define UDAPOSE_MIRROR_IN 2
+int udapose_affine_nearest_mirror(void* stream, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage,
+                                  int backward, const unsigned char* mirror, const int* perm);
+int udapose_affine_bilinear_mirror(void* stream, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage,
+                                   int backward, const unsigned char* mirror, const int* perm);
 /* f16x2 (UDAPOSE_EPI_SPLIT / split tensors) range check: the number of split STORES, since the last reset, of a value outside fp16's range
  * (|v| > 65504, which the format saturates, or NaN) by any kernel of THIS library on the current device.  Synchronous (reads device
  * counters): call it at an evaluation boundary - engine.validate() does and warns - never inside a stream capture. */
@@ -932,6 +948,9 @@ int udapose_select_rows(void* stream, float* dst, const float* a, const float* b
  * gaussian_labels: generate_target (lib/datasets/util.py:12-70): kp [R][2] double pixels, vis [R] -> target [R][Hh][Wh],
  *   weight [R]; patch = the (2*rad+1)^2 Gaussian built by the caller as the reference builds it. */
 int udapose_aug_affine_u8(void* stream, const unsigned char* src, unsigned char* dst, const long long* coef, int N, int H, int W);
+/* the mirrored base crop of a flipped view, out of place: dst[n][y][x] = src[n][y][flag[n] ? W - 1 - x : x] (flag [N] bytes); aug_affine_u8 of
+ * the result is, byte for byte, aug_affine_u8 of the image reversed along its columns */
+int udapose_aug_hflip_u8(void* stream, const unsigned char* src, unsigned char* dst, const unsigned char* flag, int N, int H, int W);
 int udapose_aug_color_op(void* stream, unsigned char* img, const int* op, const float* factor, int* mean_scratch, int N, int HW);
 /* PIL.ImageFilter.GaussianBlur (T.GaussianBlur, lib/transforms/keypoint_detection.py:216-225) in place on img [N][H][W][3] uint8 through
  * the scratch buffer tmp (same size): three box-blur passes per direction in PIL's 8.24 fixed point, bit-exact.  prm[n] = (r, ww, fw)

@@ -202,6 +202,9 @@ _SIGS = {
     "udapose_prof_end": (ci, [vp]),
     "udapose_affine_nearest": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci]),
     "udapose_affine_bilinear": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci]),
+    "udapose_affine_nearest_mirror": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "udapose_affine_bilinear_mirror": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "udapose_aug_hflip_u8": (ci, [vp, vp, vp, vp, ci, ci, ci]),
     "udapose_recon_thetas": (ci, [vp, vp, ci, cd, vp, vp]),
     "udapose_conv_bwd_ws_bytes": (ll, [vp]),
     "udapose_conv_bwd_prepare": (ci, [vp]),

@@ -24,25 +24,46 @@ __device__ __forceinline__ bool step(const float* __restrict__ th, int W, int H,
     return true;
 }
 
+// MIRRORED VIEWS.  mirror[n] holds two bits per sample: MIRROR_OUT (bit 0) reverses the columns of the chain's OUTPUT,
+// MIRROR_IN (bit 1) those of its INPUT; with exactly one of them set and a joint permutation perm [C] given, the source plane of output
+// channel c is channel perm[c].  The mirror is an index map at one end of the chain and does no arithmetic: every value is a value of the
+// plain chain.  A kernel below takes the two tables as a trailing parameter pack `mir`: none for the plain launch - whose kernel then has the
+// parameters and, the bits being the constant 0, the instructions it had before the mirrored forms existed - or one Mirror.
+constexpr unsigned MIRROR_OUT = 1, MIRROR_IN = 2;
+struct Mirror { const unsigned char* bits; const int* perm; };
+__device__ __forceinline__ unsigned mirror_bits(int) { return 0u; }
+__device__ __forceinline__ unsigned mirror_bits(int n, const Mirror& mr) { return mr.bits[n] & 3u; }
+// the plane the launch reads for channel c of a sample (perm is an involution: the backward reads d(out) from the same plane)
+__device__ __forceinline__ int mirror_plane(unsigned, int c) { return c; }
+__device__ __forceinline__ int mirror_plane(unsigned m, int c, const Mirror& mr) {
+    return mr.perm && (m == MIRROR_OUT || m == MIRROR_IN) ? mr.perm[c] : c;
+}
+__device__ __forceinline__ int mirror_index(int i, int W) { return i + W - 1 - 2 * (i % W); }      // (y, x) -> (y, W - 1 - x), flat
+
 // nstage sequential warps (1..3); theta: [N][nstage][6] fp32 in application order (stage 0 applied first)
-template <bool BWD>
+template <bool BWD, class... M>
 __global__ void warp_chain_k(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ theta, int N, int C, int H, int W,
-                             int nstage) {
+                             int nstage, M... mir) {
     const size_t total = (size_t)N * H * W;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
         const int n = (int)(i / ((size_t)H * W));
         const int rem = (int)(i % ((size_t)H * W));
         int py = rem / W, px = rem % W;
+        const unsigned m = mirror_bits(n, mir...);
+        if (m & MIRROR_OUT) px = W - 1 - px;          // output pixel (y, x) is the chain's (y, W - 1 - x)
         bool ok = true;
         for (int s = nstage - 1; s >= 0 && ok; --s) ok = step(theta + ((size_t)n * nstage + s) * 6, W, H, px, py);
+        if (m & MIRROR_IN) px = W - 1 - px;                    // the chain read M(in): its pixel (y, x) is in's (y, W - 1 - x)
         const size_t o = (size_t)n * C * H * W;
         // (blockIdx.y strides the channels: the index map is cheap to recompute and the launch sits, alone on the device, between the
         // forwards and the backward of a step - 16 channel groups took the backward of [32,16,64,64] from 58 us to what one atomic costs)
         if (!BWD) {
-            for (int c = blockIdx.y; c < C; c += gridDim.y) dst[o + (size_t)c * H * W + rem] = ok ? src[o + (size_t)c * H * W + py * W + px] : 0.f;
+            for (int c = blockIdx.y; c < C; c += gridDim.y)
+                dst[o + (size_t)c * H * W + rem] = ok ? src[o + (size_t)mirror_plane(m, c, mir...) * H * W + py * W + px] : 0.f;
         } else if (ok) {
             // src = d(out), dst = d(in) (pre-zeroed): several outputs may read the same input pixel
-            for (int c = blockIdx.y; c < C; c += gridDim.y) atomicAdd(dst + o + (size_t)c * H * W + py * W + px, src[o + (size_t)c * H * W + rem]);
+            for (int c = blockIdx.y; c < C; c += gridDim.y)
+                atomicAdd(dst + o + (size_t)mirror_plane(m, c, mir...) * H * W + py * W + px, src[o + (size_t)c * H * W + rem]);
         }
     }
 }
@@ -57,8 +78,11 @@ __global__ void warp_chain_k(const float* __restrict__ src, float* __restrict__ 
 // the smallest pending indices, so the order stays ascending across epochs.  The loop's scales (<= 1 / 0.6 per axis) need one epoch, and
 // then the rounds and barriers are those of a single pass.  The plane is stored with plain coalesced stores (no clear of dst beforehand).
 // LDS: (int target + int slot + float acc) per pixel + 1 byte rank = 13 bytes per pixel (53 KB for 64x64, 120 KB for 96x96).
+// Mirrored (a Mirror in `mir`): i stays the index of the CHAIN'S OWN output pixel, so the ranks - the summation order - are those of the plain launch on the
+// un-mirrored gradient; MIRROR_OUT only moves where d(out)[i] is read, MIRROR_IN where the chain's target lies in d(in).
+template <class... M>
 __global__ __launch_bounds__(TPB) void warp_chain_bwd_det_k(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ theta,
-                                                            int C, int H, int W, int nstage) {
+                                                            int C, int H, int W, int nstage, M... mir) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int HW = H * W;
     int* tgt = (int*)smem;
@@ -66,16 +90,19 @@ __global__ __launch_bounds__(TPB) void warp_chain_bwd_det_k(const float* __restr
     float* acc = (float*)(slot + HW);
     unsigned char* rank = (unsigned char*)(acc + HW);
     const int n = blockIdx.x / C, c = blockIdx.x % C;
+    const unsigned m = mirror_bits(n, mir...);
     for (int i = threadIdx.x; i < HW; i += TPB) {
         int py = i / W, px = i % W;
         bool ok = true;
         for (int s = nstage - 1; s >= 0 && ok; --s) ok = step(theta + ((size_t)n * nstage + s) * 6, W, H, px, py);
+        if (m & MIRROR_IN) px = W - 1 - px;
         tgt[i] = ok ? py * W + px : -1;
         rank[i] = ok ? 255 : 254;          // 255: not ranked yet; 254: contributes nothing (or already added)
         acc[i] = 0.f;
     }
     __syncthreads();
-    const float* sp = src + ((size_t)n * C + c) * HW;
+    const float* sp = src + ((size_t)n * C + mirror_plane(m, c, mir...)) * HW;
+    const bool gm = m & MIRROR_OUT;
     for (bool more = true; more;) {
         more = false;
         int nrounds = 0;
@@ -94,7 +121,7 @@ __global__ __launch_bounds__(TPB) void warp_chain_bwd_det_k(const float* __restr
         }
         for (int r = 0; r < nrounds; ++r) {
             for (int i = threadIdx.x; i < HW; i += TPB)
-                if (rank[i] == r) { acc[tgt[i]] += sp[i]; rank[i] = 254; }        // (one writer per target and round)
+                if (rank[i] == r) { acc[tgt[i]] += sp[gm ? mirror_index(i, W) : i]; rank[i] = 254; }        // (one writer per target and round)
             __syncthreads();
         }
     }
@@ -224,28 +251,49 @@ int affine_recon_thetas(hipStream_t s, const double* params, int N, double ratio
     return udapose_check_launch();
 }
 
-int affine_warp_chain(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward) {
+// mirror == nullptr: the plain launches; otherwise their mirrored forms under the same dispatch rules
+static int warp_chain_dispatch(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward,
+                               const unsigned char* mirror, const int* perm) {
     if (nstage < 1 || nstage > 8) return UDAPOSE_ERR_ARG;
     const size_t total = (size_t)N * H * W;
     int blocks = (int)((total + TPB - 1) / TPB);
     if (blocks > 4096) blocks = 4096;
     const int cgroups = C >= 16 ? 16 : (C >= 4 ? 4 : 1);
+    const Mirror mir = {mirror, perm};
     if (backward) {
         // deterministic form (one work-group per (sample, channel) plane, ranks in LDS) wherever the plane fits, at any number of outputs per
         // input pixel (more than 254 - a zoom past ~15, a collapsed theta - take further ranking epochs); a plane beyond the LDS budget takes the
         // atomic form
         const size_t lds = (size_t)H * W * 13 + 16;
         if (lds <= 150 * 1024 && (long long)N * C < (1ll << 31)) {
-            max_dynamic_lds<warp_chain_bwd_det_k>(150 * 1024);
-            hipLaunchKernelGGL(warp_chain_bwd_det_k, dim3(N * C), dim3(TPB), (unsigned)((lds + 15) & ~(size_t)15), s, src, dst, theta, C, H, W, nstage);
+            const unsigned bytes = (unsigned)((lds + 15) & ~(size_t)15);
+            if (mirror) {
+                max_dynamic_lds<warp_chain_bwd_det_k<Mirror>>(150 * 1024);
+                hipLaunchKernelGGL(warp_chain_bwd_det_k<Mirror>, dim3(N * C), dim3(TPB), bytes, s, src, dst, theta, C, H, W, nstage, mir);
+            } else {
+                max_dynamic_lds<warp_chain_bwd_det_k<>>(150 * 1024);
+                hipLaunchKernelGGL(warp_chain_bwd_det_k<>, dim3(N * C), dim3(TPB), bytes, s, src, dst, theta, C, H, W, nstage);
+            }
             return udapose_check_launch();
         }
         if (pw_zero(s, dst, (size_t)N * C * H * W * sizeof(float)) != UDAPOSE_OK) return UDAPOSE_ERR_LAUNCH;
-        hipLaunchKernelGGL(warp_chain_k<true>, dim3(blocks, cgroups), dim3(TPB), 0, s, src, dst, theta, N, C, H, W, nstage);
+        if (mirror) hipLaunchKernelGGL((warp_chain_k<true, Mirror>), dim3(blocks, cgroups), dim3(TPB), 0, s, src, dst, theta, N, C, H, W, nstage, mir);
+        else hipLaunchKernelGGL(warp_chain_k<true>, dim3(blocks, cgroups), dim3(TPB), 0, s, src, dst, theta, N, C, H, W, nstage);
+    } else if (mirror) {
+        hipLaunchKernelGGL((warp_chain_k<false, Mirror>), dim3(blocks, cgroups), dim3(TPB), 0, s, src, dst, theta, N, C, H, W, nstage, mir);
     } else {
         hipLaunchKernelGGL(warp_chain_k<false>, dim3(blocks, cgroups), dim3(TPB), 0, s, src, dst, theta, N, C, H, W, nstage);
     }
     return udapose_check_launch();
+}
+int affine_warp_chain(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward) {
+    return warp_chain_dispatch(s, src, dst, theta, N, C, H, W, nstage, backward, nullptr, nullptr);
+}
+// src and dst must not overlap (a mirrored or permuted plane is not written where it is read)
+int affine_warp_chain_mirror(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward,
+                             const unsigned char* mirror, const int* perm) {
+    if (!mirror || !src || !dst || !theta || N <= 0 || C <= 0 || H <= 0 || W <= 0) return UDAPOSE_ERR_ARG;
+    return warp_chain_dispatch(s, src, dst, theta, N, C, H, W, nstage, backward, mirror, perm);
 }
 
 // ---------------------------------------------------------------- BILINEAR chain (tF.affine with InterpolationMode.BILINEAR per stage)
@@ -335,17 +383,21 @@ __device__ __forceinline__ float bilin_gather(const float* g, const BilinStage& 
 }
 // One work-group owns one (sample, channel) plane: it stages the plane in LDS and runs the stages ping-pong between two LDS planes (the
 // backward: the stages in reverse, each as the gather above); the last stage is stored with coalesced stores.  LDS: 2 * H * W * 4 bytes.
-template <bool BWD>
+// Mirrored (a Mirror in `mir`): the reversed row is taken on the LDS load (the forward's MIRROR_IN, the backward's MIRROR_OUT) or on the final store (the
+// other bit of each) - a stride of -1 dword, conflict-free - and the plane staged is channel perm[c]'s; the stages between are the plain ones.
+template <bool BWD, class... M>
 __global__ __launch_bounds__(TPB) void bilin_chain_lds_k(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ theta,
-                                                         int C, int H, int W, int nstage) {
+                                                         int C, int H, int W, int nstage, M... mir) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int HW = H * W;
     float* A = (float*)smem;
     float* B = A + HW;
     const int n = blockIdx.x / C;
-    const float* sp = src + (size_t)blockIdx.x * HW;
+    const unsigned mb = mirror_bits(n, mir...);
+    const bool m_load = mb & (BWD ? MIRROR_OUT : MIRROR_IN), m_store = mb & (BWD ? MIRROR_IN : MIRROR_OUT);
+    const float* sp = src + (sizeof...(M) ? (size_t)n * C + mirror_plane(mb, blockIdx.x % C, mir...) : (size_t)blockIdx.x) * HW;
     float* dp = dst + (size_t)blockIdx.x * HW;
-    for (int i = threadIdx.x; i < HW; i += TPB) A[i] = sp[i];
+    for (int i = threadIdx.x; i < HW; i += TPB) A[i] = sp[m_load ? mirror_index(i, W) : i];
     __syncthreads();
     for (int k = 0; k < nstage; ++k) {
         const float* th = theta + ((size_t)n * nstage + (BWD ? nstage - 1 - k : k)) * 6;
@@ -358,7 +410,7 @@ __global__ __launch_bounds__(TPB) void bilin_chain_lds_k(const float* __restrict
             float v;
             if (BWD) v = bilin_gather(A, m, box, W, H, px, py);
             else v = bilin_sample(A, m, W, H, px, py);
-            if (last) dp[i] = v; else B[i] = v;
+            if (last) dp[m_store ? py * W + (W - 1 - px) : i] = v; else B[i] = v;
         }
         __syncthreads();
         float* t = A; A = B; B = t;
@@ -389,7 +441,8 @@ __global__ __launch_bounds__(TPB) void bilin_stage_global_k(const float* __restr
 // src and dst must not overlap.  Planes within the LDS budget (2 * H * W * 4 <= 150 KB: every heat-map size) take one launch and allocate
 // nothing.  Larger planes run stage by stage from global memory; with more than one stage they go through one scratch tensor allocated
 // and freed in stream order - never inside a stream capture, where such planes are refused (UDAPOSE_ERR_UNSUPPORTED).
-int affine_warp_chain_bilinear(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward) {
+static int bilinear_dispatch(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward,
+                             const unsigned char* mirror, const int* perm) {
     if (nstage < 1 || nstage > 8 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || !src || !dst || !theta) return UDAPOSE_ERR_ARG;
     if ((long long)H * W > (1ll << 26) || (long long)N * C >= (1ll << 31)) return UDAPOSE_ERR_ARG;
     const int HW = H * W;
@@ -398,10 +451,19 @@ int affine_warp_chain_bilinear(hipStream_t s, const float* src, float* dst, cons
         max_dynamic_lds<bilin_chain_lds_k<false>>(150 * 1024);
         max_dynamic_lds<bilin_chain_lds_k<true>>(150 * 1024);
         const unsigned bytes = (unsigned)((lds + 15) & ~(size_t)15);
+        if (mirror) {
+            const Mirror mir = {mirror, perm};
+            max_dynamic_lds<bilin_chain_lds_k<false, Mirror>>(150 * 1024);
+            max_dynamic_lds<bilin_chain_lds_k<true, Mirror>>(150 * 1024);
+            if (backward) hipLaunchKernelGGL((bilin_chain_lds_k<true, Mirror>), dim3(N * C), dim3(TPB), bytes, s, src, dst, theta, C, H, W, nstage, mir);
+            else hipLaunchKernelGGL((bilin_chain_lds_k<false, Mirror>), dim3(N * C), dim3(TPB), bytes, s, src, dst, theta, C, H, W, nstage, mir);
+            return udapose_check_launch();
+        }
         if (backward) hipLaunchKernelGGL(bilin_chain_lds_k<true>, dim3(N * C), dim3(TPB), bytes, s, src, dst, theta, C, H, W, nstage);
         else hipLaunchKernelGGL(bilin_chain_lds_k<false>, dim3(N * C), dim3(TPB), bytes, s, src, dst, theta, C, H, W, nstage);
         return udapose_check_launch();
     }
+    if (mirror) return UDAPOSE_ERR_UNSUPPORTED;        // (the stage-by-stage global form has no mirrored counterpart)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cap) != hipSuccess) return UDAPOSE_ERR_LAUNCH;
     if (cap != hipStreamCaptureStatusNone) return UDAPOSE_ERR_UNSUPPORTED;
@@ -421,6 +483,15 @@ int affine_warp_chain_bilinear(hipStream_t s, const float* src, float* dst, cons
     }
     if (scratch && hipFreeAsync(scratch, s) != hipSuccess && rc == UDAPOSE_OK) rc = UDAPOSE_ERR_LAUNCH;
     return rc;
+}
+int affine_warp_chain_bilinear(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward) {
+    return bilinear_dispatch(s, src, dst, theta, N, C, H, W, nstage, backward, nullptr, nullptr);
+}
+// planes beyond the LDS budget: UDAPOSE_ERR_UNSUPPORTED
+int affine_warp_chain_bilinear_mirror(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage,
+                                      int backward, const unsigned char* mirror, const int* perm) {
+    if (!mirror) return UDAPOSE_ERR_ARG;
+    return bilinear_dispatch(s, src, dst, theta, N, C, H, W, nstage, backward, mirror, perm);
 }
 
 // mean over k re-warped teacher views (train_human.py:361-372 with --k > 1: `torch.mean(recons, dim=0)`): the k values of an element

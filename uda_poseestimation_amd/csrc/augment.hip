@@ -38,6 +38,20 @@ __global__ void aug_affine_u8_k(const unsigned char* __restrict__ src, unsigned 
     }
 }
 
+// dst[n][y][x][:] = src[n][y][flag[n] ? W - 1 - x : x][:]: the mirrored base crop of a flipped view (hflip, lib/transforms/keypoint_detection.py:108-116)
+// ahead of aug_affine_u8_k, whose fixed-point coefficients stay those of the un-mirrored warp (folding the mirror into them would move rounding ties)
+__global__ void aug_hflip_u8_k(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, const unsigned char* __restrict__ flag, int H, int W) {
+    const int n = blockIdx.y;
+    const bool f = flag[n] != 0;
+    const unsigned char* s = src + (size_t)n * H * W * 3;
+    unsigned char* d = dst + (size_t)n * H * W * 3;
+    for (int i = blockIdx.x * TPB + threadIdx.x; i < H * W; i += gridDim.x * TPB) {
+        const int x = i % W;
+        const unsigned char* p = s + (size_t)(f ? i + W - 1 - 2 * x : i) * 3;
+        d[(size_t)i * 3] = p[0]; d[(size_t)i * 3 + 1] = p[1]; d[(size_t)i * 3 + 2] = p[2];
+    }
+}
+
 __device__ __forceinline__ int lum(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
 
 // mean[n] = int(sum(L) / HW + 0.5) of image n (ImageStat.Stat(img.convert("L")).mean[0] rounded as ImageEnhance.Contrast does);
@@ -267,6 +281,13 @@ int aug_affine_u8(hipStream_t s, const unsigned char* src, unsigned char* dst, c
     int gx = (H * W + TPB - 1) / TPB;
     if (gx > 256) gx = 256;
     hipLaunchKernelGGL(aug_affine_u8_k, dim3(gx, N), dim3(TPB), 0, s, src, dst, coef, H, W);
+    return udapose_check_launch();
+}
+int aug_hflip_u8(hipStream_t s, const unsigned char* src, unsigned char* dst, const unsigned char* flag, int N, int H, int W) {
+    if (!src || !dst || !flag || src == dst || N <= 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL / 3) return UDAPOSE_ERR_ARG;
+    int gx = (H * W + TPB - 1) / TPB;
+    if (gx > 256) gx = 256;
+    hipLaunchKernelGGL(aug_hflip_u8_k, dim3(gx, N), dim3(TPB), 0, s, src, dst, flag, H, W);
     return udapose_check_launch();
 }
 int aug_color_op(hipStream_t s, unsigned char* img, const int* op, const float* factor, int* mean_scratch, int N, int HW) {

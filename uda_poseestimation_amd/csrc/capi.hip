@@ -616,6 +616,17 @@ int udapose_affine_nearest(void* stream, const float* src, float* dst, const flo
 int udapose_affine_bilinear(void* stream, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward) {
     return affine_warp_chain_bilinear(S(stream), src, dst, theta, N, C, H, W, nstage, backward);
 }
+int udapose_affine_nearest_mirror(void* stream, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward,
+                                  const unsigned char* mirror, const int* perm) {
+    return affine_warp_chain_mirror(S(stream), src, dst, theta, N, C, H, W, nstage, backward, mirror, perm);
+}
+int udapose_affine_bilinear_mirror(void* stream, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward,
+                                   const unsigned char* mirror, const int* perm) {
+    return affine_warp_chain_bilinear_mirror(S(stream), src, dst, theta, N, C, H, W, nstage, backward, mirror, perm);
+}
+int udapose_aug_hflip_u8(void* stream, const unsigned char* src, unsigned char* dst, const unsigned char* flag, int N, int H, int W) {
+    return aug_hflip_u8(S(stream), src, dst, flag, N, H, W);
+}
 
 int udapose_aug_affine_u8(void* stream, const unsigned char* src, unsigned char* dst, const long long* coef, int N, int H, int W) {
     if (!src || !dst || !coef) return UDAPOSE_ERR_ARG;

@@ -10,6 +10,10 @@ int patch_paste(hipStream_t s, float* img, const int* boxes, int n, int C, int H
 int affine_recon_thetas(hipStream_t s, const double* params, int N, double ratio, float* fwd, float* back);
 int affine_warp_chain(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward);
 int affine_warp_chain_bilinear(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward);
+int affine_warp_chain_mirror(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage, int backward,
+                             const unsigned char* mirror, const int* perm);
+int affine_warp_chain_bilinear_mirror(hipStream_t s, const float* src, float* dst, const float* theta, int N, int C, int H, int W, int nstage,
+                                      int backward, const unsigned char* mirror, const int* perm);
 int affine_mean_views(hipStream_t s, const float* const* srcs, int k, float* dst, size_t n);
 // view_merge.hip
 int affine_view_merge(hipStream_t s, const float* const* srcs, int k, int R, int H, int W, int mode, const float* radius_dev, int min_views,
@@ -19,6 +23,7 @@ int aug_resized_crop_u8(hipStream_t s, const unsigned char* src, unsigned char* 
                         const int* coef, int N, int Hs, int Ws, int S, int ksize);
 int aug_gaussian_blur_u8(hipStream_t s, unsigned char* img, unsigned char* tmp, const unsigned int* prm, int N, int H, int W);
 int aug_affine_u8(hipStream_t s, const unsigned char* src, unsigned char* dst, const long long* coef, int N, int H, int W);
+int aug_hflip_u8(hipStream_t s, const unsigned char* src, unsigned char* dst, const unsigned char* flag, int N, int H, int W);
 int aug_color_op(hipStream_t s, unsigned char* img, const int* op, const float* factor, int* mean_scratch, int N, int HW);
 int aug_to_tensor(hipStream_t s, const unsigned char* img, float* out, int N, int HW, const float* mean3, const float* std3);
 int aug_gaussian_labels(hipStream_t s, const double* kp, const float* vis, float* target, float* weight, int R, int Hh, int Wh, double stride_x,

@@ -22,6 +22,11 @@ ColorJitter + blur): `ViewConfig(strong_ops=k, strong_magnitude=m)` appends k op
 ImageOps.autocontrast / equalize / posterize / solarize and ImageEnhance.Sharpness, byte for byte PIL's results (csrc/strong_aug.hip) -
 between the colour jitter and the blur, and `ViewConfig(erase=p)` the reference's RandomErasing (lib/transforms/__init__.py:134-179) on the
 normalised tensor.  Both are off by default: nothing more is drawn or launched then.
+
+Mirrored views: `ViewConfig(flip=p)` mirrors a sample's base crop with probability p ahead of the view's affine warp - the
+view is A(M(base)) - with the key points following the reference's `hflip` (lib/transforms/keypoint_detection.py:108-116, x -> W - 1 - x)
+and re-indexed by the left / right joint pairs; the flags travel as a 5th entry of the view's `aug_param`, which the re-warps undo
+(warp.recon_heatmaps, the trainers).  Off by default: no draw, no launch, the reference's 4-entry aug_param.
 """
 import math
 import random
@@ -157,6 +162,18 @@ def transform_keypoints(kp, angle, shear_x, shear_y, trans_x, trans_y, scale, wi
     return kp
 
 
+def mirror_keypoints(keypoints, visible, width, flip_pairs):
+    """The key-point side of a horizontal flip for ONE sample: keypoints [K,2+] -> x becomes width - 1 - x (the reference's `hflip`), then rows
+    are re-indexed by the flip permutation (lib.keypoint_detection.flip_perm, an involution), so that row j holds the joint that looks like
+    j in the mirrored picture; visible [K,...] (or None) is re-indexed the same way.  -> (key points, visible), copies."""
+    from .lib import keypoint_detection as kd
+    kp = np.array(keypoints, dtype=np.float64, copy=True)
+    perm = kd.flip_perm(flip_pairs, kp.shape[0]).numpy()
+    kp[:, 0] = (width - 1) - kp[:, 0]
+    vis = None if visible is None else np.array(visible, copy=True)[perm]
+    return kp[perm], vis
+
+
 def strong_op_arrays(ops, params, N):
     """The host side of `TargetViewPipeline.strong_`: per-sample op / parameter lists, checked, -> four [L][N] arrays, one row per list
     position: the codes, the codes as udapose_aug_color_op reads them (everything but 1..3 is "none" there), the float parameters (factors
@@ -198,7 +215,7 @@ class ViewConfig:
     """Ranges of one view's augmentation = the reference's `--rotation_* --shear_* --translate_* --scale_* --color_*` flags
     (train_human.py:535-557)."""
 
-    def __init__(self, rotation=180, shear=(-30, 30), translate=(0.05, 0.05), scale=(0.6, 1.3), color=0.25, blur=0.0, strong_ops=0,
+    def __init__(self, rotation=180, shear=(-30, 30), translate=(0.05, 0.05), scale=(0.6, 1.3), color=0.25, blur=0.0, flip=0.0, strong_ops=0,
                  strong_magnitude=9, erase=0.0, erase_value=(0.4914, 0.4822, 0.4465)):
         self.degrees = (-rotation, rotation) if isinstance(rotation, (int, float)) else tuple(rotation)
         self.shear = (-shear, shear) if isinstance(shear, (int, float)) else tuple(shear)
@@ -214,6 +231,9 @@ class ViewConfig:
             raise ValueError(f"strong_ops must be >= 0 and strong_magnitude in 0..{STRONG_BINS - 1}")
         if not 0.0 <= self.erase <= 1.0 or len(self.erase_value) != 3:
             raise ValueError("erase is a probability and erase_value has one value per channel")
+        self.flip = float(flip)          # the probability, per sample, of a mirrored view (horizontal flip with left / right joint swap)
+        if not 0.0 <= self.flip <= 1.0:
+            raise ValueError("flip is a probability")
 
     def draw_blur(self, rng):
         """GaussianBlur.__call__ (keypoint_detection.py:221-223): one uniform radius per sample (the reference draws from np.random)."""
@@ -284,8 +304,17 @@ class ViewConfig:
         return 0, 0, 0, 0
 
 
+    def draw_flip(self, rng):
+        """One `rng.random() < flip` per sample -> 0 / 1; drawn after every other draw of the view, and not at all when flip == 0."""
+        return int(rng.random() < self.flip)
+
+
 class TargetViewPipeline:
     """Batched device pipeline for the `_mt` datasets' student / teacher views."""
+
+    # mirrored views: the left / right joint pairs (a sequence of pairs, possibly empty, or a key of lib.keypoint_detection.FLIP_PAIRS), set
+    # as an attribute after construction like MeanTeacherTrainer.flip_pairs; a view with flip > 0 needs it (ValueError before anything is drawn)
+    flip_pairs = None
 
     def __init__(self, image_size=256, heatmap_size=64, sigma=2, k=1, student=None, teacher=None, mean=IMAGENET_MEAN, std=IMAGENET_STD,
                  rng=None, resize_scale=(0.6, 1.3), np_rng=None, subpixel_labels=False):
@@ -332,6 +361,22 @@ class TargetViewPipeline:
         cdev = torch.tensor(coef, dtype=torch.int64).to(base_u8.device, non_blocking=True)
         out = torch.empty_like(base_u8)
         check(lib().udapose_aug_affine_u8(_hip.stream(), ptr(base_u8), ptr(out), ptr(cdev), N, H, W), "aug_affine_u8")
+        return out
+
+    def hflip(self, base_u8, flips):
+        """The mirrored base crops of the flagged samples (udapose_aug_hflip_u8, out of place): base_u8 [N,H,W,3] uint8 CUDA, flips = N
+        values 0 / 1.  No flag set: base_u8 itself, no launch."""
+        _hip.require_cuda(base_u8)
+        N, H, W, C3 = base_u8.shape
+        assert C3 == 3 and base_u8.dtype == torch.uint8 and base_u8.is_contiguous()
+        flips = [int(f) for f in flips]
+        if len(flips) != N or any(f not in (0, 1) for f in flips):
+            raise ValueError(f"flips: {N} values 0 / 1 expected, got {flips}")
+        if not any(flips):
+            return base_u8
+        fdev = torch.tensor(flips, dtype=torch.uint8).to(base_u8.device, non_blocking=True)
+        out = torch.empty_like(base_u8)
+        check(lib().udapose_aug_hflip_u8(_hip.stream(), ptr(base_u8), ptr(out), ptr(fdev), N, H, W), "aug_hflip_u8")
         return out
 
     def resized_crop(self, raw_u8, keypoints, boxes=None):
@@ -510,12 +555,26 @@ class TargetViewPipeline:
 
     # ------------------------------------------------------------------ one view of the whole batch
     def view(self, base_u8, keypoints, cfg, params=None, jitter=None, blur=None, strong=None, erase=None):
+        """One view of the whole batch, every draw not given made here (`view_with_flips` states the result and the order of the draws; the
+        flips of a configuration with flip > 0 are drawn)."""
+        return self.view_with_flips(base_u8, keypoints, cfg, None, params, jitter, blur, strong, erase)
+
+    def view_with_flips(self, base_u8, keypoints, cfg, flips, params=None, jitter=None, blur=None, strong=None, erase=None):
         """-> (image [N,3,H,W] fp32 normalised, key points [N,K,2], aug_param collated, target, weight)
         strong = per-sample (codes, parameters) as `draw_strong` returns them, erase = per-sample boxes as `draw_erase` does; both are drawn
         when None and the configuration has them on - after every other draw of the view (affine for every sample, jitter for every
         sample, blur), strong for every sample first, then erase: a seeded pipeline draws the same affine / jitter / blur values with the
-        strong view on as with it off.  Neither touches key points, aug_param, labels or weights (an erased key point stays labelled)."""
+        strong view on as with it off.  Neither touches key points, aug_param, labels or weights (an erased key point stays labelled).
+        flips = per-sample 0 / 1 (`draw_flip`), drawn last of all when None and cfg.flip > 0: a flagged sample's base crop is mirrored ahead
+        of the warp and its key points (and visibility) go through `mirror_keypoints` ahead of `transform_keypoints`: the returned key
+        points, labels and weights are the mirrored person's.  aug_param gets `flip` (int64 [N]) as a 5th entry when, and only when,
+        cfg.flip > 0 (flips for a configuration without: ValueError - the flags would be lost)."""
         N, H, W, _ = base_u8.shape
+        if cfg.flip > 0 and self.flip_pairs is None:
+            raise ValueError("a view with flip > 0 needs the pipeline's flip_pairs (pipe.flip_pairs = the left / right joint pairs, possibly "
+                             "empty, or a key of FLIP_PAIRS): a mirrored person's left joints are its right ones")
+        if cfg.flip == 0 and flips is not None:
+            raise ValueError("flips were given for a view whose configuration has flip = 0: its aug_param could not carry them")
         if params is None:
             params = [cfg.draw_affine(self.rng, (W, H)) for _ in range(N)]
         if jitter is None:
@@ -526,6 +585,15 @@ class TargetViewPipeline:
             strong = [cfg.draw_strong(self.rng) for _ in range(N)]
         if erase is None and cfg.erase > 0:
             erase = [cfg.draw_erase(self.rng, H, W) for _ in range(N)]
+        if flips is None and cfg.flip > 0:
+            flips = [cfg.draw_flip(self.rng) for _ in range(N)]
+        vis = np.ones((N, keypoints.shape[1], 1), np.float32)
+        if flips is not None:
+            base_u8 = self.hflip(base_u8, flips)
+            keypoints, vis = np.array(keypoints, dtype=np.float64, copy=True), vis.copy()
+            for i in range(N):
+                if int(flips[i]):
+                    keypoints[i], vis[i] = mirror_keypoints(keypoints[i], vis[i], W, self.flip_pairs)
         img = self.warp_images(base_u8, params)
         self.jitter_(img, [j[0] for j in jitter], [j[1] for j in jitter])
         if strong is not None:
@@ -541,7 +609,8 @@ class TargetViewPipeline:
                [torch.tensor([-p[3] for p in params], dtype=torch.int64), torch.tensor([-p[4] for p in params], dtype=torch.int64)],
                [torch.tensor([-p[1] for p in params], dtype=torch.float64), torch.tensor([-p[2] for p in params], dtype=torch.float64)],
                torch.tensor([1.0 / p[5] for p in params], dtype=torch.float64)]
-        vis = np.ones((N, keypoints.shape[1], 1), np.float32)
+        if flips is not None:
+            aug.append(torch.tensor([int(f) for f in flips], dtype=torch.int64))
         target, weight = self.labels(kp, vis, base_u8.device)
         return x, kp, aug, target, weight
 

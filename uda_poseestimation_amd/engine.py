@@ -370,6 +370,9 @@ class MeanTeacherTrainer:
         self.device_occlusion = False
         self.occl_rng = self.rng            # generator of the host-side occlusion draws (the reference: the global np.random)
         self._occl = None                   # ("host", aug_param_stu) | ("device", theta_back [N,1,6], u [N,4])
+        # mirrored views: the left / right joint pairs that un-mirroring a flagged sample's heat-maps swaps - a sequence of
+        # pairs (possibly empty) or a key of lib.keypoint_detection.FLIP_PAIRS; None: a batch with a flipped sample is refused
+        self.flip_pairs = None
         # data parallel: cut the backward after layer3 and all-reduce the finished 94 % of the gradient under the rest of it
         # (None: whenever a process group is active and the network has the layer3 boundary)
         self.overlap_allreduce = None
@@ -503,13 +506,31 @@ class MeanTeacherTrainer:
         d = self._adv_dev[0]
         return d[0], (None if (steps == 1 and self.adv_step is None) else d[1])
 
-    def _adversarial_part(self, x_t_stu, theta_stu, target):
+    def _mirror_perm(self, mirrors, num_joints, device):
+        """The joint permutation the step's mirrored re-warps take: None when no view carries a mirror tensor (the plain launches)."""
+        if all(m is None for m in mirrors):
+            return None
+        if self.flip_pairs is None:
+            raise ValueError("the batch has mirrored views (a flip entry in its aug_param) and trainer.flip_pairs is None: set it to the "
+                             "left / right joint pairs (a sequence of pairs, possibly empty, or a key of FLIP_PAIRS)")
+        return warp.mirror_perm(self.flip_pairs, num_joints, device)
+
+    def _mirror_tensors(self, aug_params, n, device):
+        """Per view: the flip flags of its aug_param on the device (uint8 [N]), None for a view without a flagged sample - whose warps are
+        then exactly the un-mirrored launches.  ValueError, before anything is launched, for a flagged sample without flip_pairs."""
+        flags = [warp.aug_mirror(ap, n) for ap in aug_params]
+        flags = [f if f is not None and bool(f.any()) else None for f in flags]
+        if self.flip_pairs is None and any(f is not None for f in flags):
+            self._mirror_perm(flags, 0, device)
+        return [f.to(device, non_blocking=True) if f is not None else None for f in flags]
+
+    def _adversarial_part(self, x_t_stu, theta_stu, target, mirror=None, perm=None):
         """(on the student's target stream, behind the teacher branch) the adversarial view of x_t_stu against the teacher's pseudo-labels."""
         eps, step = self.sync_adv(x_t_stu.device)
         cons = ConsLoss()
 
         def probe_loss(y):      # no mask, no rectify: nothing is communicated, nothing moves out of _loss_backward_part
-            return cons(warp.warp_chain(y, theta_stu, self.warp_mode), target)
+            return cons(warp.warp_chain(y, theta_stu, self.warp_mode, mirror, perm if mirror is not None else None), target)
         return adversarial.adversarial_view(self.student, x_t_stu, probe_loss, eps, norm=self.adv_norm, steps=self.adv_steps, step=step,
                                             clamp=self._adv_dev[2], grad_scale=self.stu_optimizer.loss_scale())
 
@@ -551,6 +572,7 @@ class MeanTeacherTrainer:
         n, dev = x_t_stu.shape[0], x_t_stu.device
         theta_stu = warp.recon_thetas(aug_param_stu, n, self.ratio, dev)
         thetas_tea = [warp.recon_thetas(ap, n, self.ratio, dev) for ap in aug_params_tea]
+        mirror_stu, *mirrors_tea = self._mirror_tensors([aug_param_stu] + list(aug_params_tea), n, dev)
         x_s_in, x_t_teas_in = self._style_part(x_s, list(x_t_teas))
         self._occl = None
         if self.occlude_rate > -1:
@@ -562,7 +584,9 @@ class MeanTeacherTrainer:
                                        "would take the ranks' common style decisions out of step - set trainer.device_occlusion = True "
                                        "or give the occlusion its own generator (trainer.occl_rng)")
                 self._occl = ("host", aug_param_stu)
-        out = self._forward_backward(x_s_in, label_s, weight_s, x_t_stu, x_t_teas_in, theta_stu, thetas_tea)
+        # (a step without a flagged sample makes the call it always made)
+        mirrors = (mirror_stu, mirrors_tea) if mirror_stu is not None or any(m is not None for m in mirrors_tea) else ()
+        out = self._forward_backward(x_s_in, label_s, weight_s, x_t_stu, x_t_teas_in, theta_stu, thetas_tea, *mirrors)
         self._sync_grads()
         self._update()
         if with_accuracy:
@@ -607,9 +631,11 @@ class MeanTeacherTrainer:
                 out_ts = [style.transfer(x_t, sum_t, sum_s, a_t2s, self.recover) for x_t, sum_t in zip(x_t_teas, sum_ts)]
         return out_s, out_ts
 
-    def _forward_part(self, x_s, label_s, weight_s, x_t_stu, x_t_teas, theta_stu, thetas_tea):
+    def _forward_part(self, x_s, label_s, weight_s, x_t_stu, x_t_teas, theta_stu, thetas_tea, mirror_stu=None, mirrors_tea=None):
         """All forwards of the step after the style pass (no host reads unless the occlusion draws on the host: capturable
-        in a hipGraph)."""
+        in a hipGraph).  mirror_stu / mirrors_tea: per view None or its flip flags on the device (uint8 [N]): every warp of a view that
+        has them takes its mirrored form (the heat-map re-warps with the joint permutation of trainer.flip_pairs, the occlusion's image
+        warps without), and a view without them the launches it always took."""
         student, teacher = self.student, self.teacher
         student.train()
         teacher.train()                     # the teacher's BN uses batch statistics too (train_human.py:321)
@@ -628,6 +654,8 @@ class MeanTeacherTrainer:
         occl = self._occl if self.occlude_rate > -1 else None
         adv, adv_gnorm = self.adv_eps is not None, None
         self._check_view_merge(len(x_t_teas))
+        mirrors_tea = list(mirrors_tea) if mirrors_tea is not None else [None] * len(x_t_teas)
+        perm = self._mirror_perm([mirror_stu] + mirrors_tea, label_s.shape[1], x_s.device)
         view_rad = self.sync_view_radius(x_s.device) if self.view_merge is not None else None      # (on `main`, before the branches fork)
         merged = None
         student.prepare(x_s)               # bf16 weight packs refreshed on `main` before the branches fork
@@ -637,7 +665,8 @@ class MeanTeacherTrainer:
         s_stu.wait_stream(main)
         with torch.cuda.stream(s_tea), torch.no_grad():
             y_t_teas = [teacher(x_t) for x_t in x_t_teas]
-            recons = [warp.warp_chain(y, th, self.warp_mode) for y, th in zip(y_t_teas, thetas_tea)]
+            recons = [warp.warp_chain(y, th, self.warp_mode, m, perm if m is not None else None)
+                      for y, th, m in zip(y_t_teas, thetas_tea, mirrors_tea)]
             if self.view_merge is None:
                 y_t_tea_recon = warp.mean_views(recons)      # (k teacher views, train_human.py:361-372: one launch; k = 1: the view itself)
                 tea_out = [y_t_tea_recon]
@@ -664,14 +693,15 @@ class MeanTeacherTrainer:
                     if occl[0] == "device":
                         x_t_stu, self.occluded = warp.occlude_keypoints_device(x_t_stu, y_t_tea_recon, theta_stu, occl[1], occl[2], self.ratio,
                                                                                self.image_px, self.occlude_rate, self.occlude_thresh,
-                                                                               self.occlude_size)
+                                                                               self.occlude_size, mirror=mirror_stu)
                     else:   # (one small D2H of confidences, as in the reference)
                         x_t_stu, self.occluded = warp.occlude_keypoints(x_t_stu, y_t_tea_recon, occl[1], self.ratio, self.image_px,
-                                                                        self.occlude_rate, self.occlude_thresh, self.occlude_size, self.occl_rng)
+                                                                        self.occlude_rate, self.occlude_thresh, self.occlude_size, self.occl_rng,
+                                                                        mirror=mirror_stu)
             if adv:
-                x_t_stu, adv_gnorm = self._adversarial_part(x_t_stu, theta_stu, y_t_tea_recon)
+                x_t_stu, adv_gnorm = self._adversarial_part(x_t_stu, theta_stu, y_t_tea_recon, mirror_stu, perm)
             y_t_stu = student.forward_deferred_bn(x_t_stu)     # separate forwards: separate BN statistics per domain
-            y_t_stu_recon = warp.warp_chain(y_t_stu, theta_stu, self.warp_mode)
+            y_t_stu_recon = warp.warp_chain(y_t_stu, theta_stu, self.warp_mode, mirror_stu, perm if mirror_stu is not None else None)
         if occl is None and not adv:
             y_s = student(x_s)
         main.wait_stream(s_stu)
@@ -804,8 +834,8 @@ class MeanTeacherTrainer:
             out["prior_map"], out["y_t_tea_raw"] = st["y_t_tea_recon"], st["y_t_tea_raw"]
         return out
 
-    def _forward_backward(self, x_s, label_s, weight_s, x_t_stu, x_t_teas, theta_stu, thetas_tea):
-        st = self._forward_part(x_s, label_s, weight_s, x_t_stu, x_t_teas, theta_stu, thetas_tea)
+    def _forward_backward(self, x_s, label_s, weight_s, x_t_stu, x_t_teas, theta_stu, thetas_tea, mirror_stu=None, mirrors_tea=None):
+        st = self._forward_part(x_s, label_s, weight_s, x_t_stu, x_t_teas, theta_stu, thetas_tea, mirror_stu, mirrors_tea)
         return self._loss_backward_part(st, gather_activates(st["activates"]))
 
     def _tail_sums_grads(self):
@@ -1022,8 +1052,13 @@ class GraphedTrainStep:
     every view is summarised only when t2s was drawn (the first otherwise), t2s transfers every view into its own buffer.
     Scheduled values (trainer.scheduled): lambda_c / lambda_ent / lambda_coral, teacher_alpha and mask_ratio named there are
     read from device memory by the captured launches; step() calls trainer.sync_schedule() before the replay, and changing them is no
-    longer refused.  Names not listed stay frozen, and so does the list itself."""
+    longer refused.  Names not listed stay frozen, and so does the list itself.
+    Mirrored views: built with trainer.flip_pairs set, the step keeps a static uint8 [1+k,N] buffer of flip flags, staged per step
+    like the aug_param values, and captures the mirrored form of every warp: a replay follows the flags of its batch (4-entry aug_params stage
+    zeros, and a sample whose flag is 0 gets the bits of the plain launch).  Built without, it captures the plain launches and refuses a batch
+    with a flagged sample (ValueError).  flip_pairs is frozen."""
 
+    mirrored = False            # built with trainer.flip_pairs set: the mirrored launch forms are captured and the flags staged per step
     k, _sfx = 1, [""]           # teacher views per step, and the suffix of view i's static keys ("" for view 0): set by the constructor
 
     def __init__(self, trainer, x_s, label_s, weight_s, x_t_stu, x_t_tea, aug_param_stu, aug_param_tea, warmup=2, split=None, metrics=True,
@@ -1052,7 +1087,7 @@ class GraphedTrainStep:
     def _is_collated(ap):
         """One collated aug_param, (angle, (tx, ty), (shear_x, shear_y), scale) - as against a list of them, one per view."""
         try:
-            return len(ap) == 4 and len(ap[1]) == 2 and len(ap[2]) == 2
+            return len(ap) in (4, 5) and len(ap[1]) == 2 and len(ap[2]) == 2       # (5: with the flip flags of mirrored views)
         except TypeError:
             return False
 
@@ -1120,6 +1155,13 @@ class GraphedTrainStep:
             st["theta_tea" + s] = torch.empty(n, 3, 6, dtype=torch.float32, device=dev)
         self._aug_pin = [torch.empty(1 + k, n, 6, dtype=torch.float64).pin_memory() for _ in range(4)]
         self._aug_ev, self._aug_i, self._aug_last = [None] * 4, 0, None
+        # mirrored views: the flip flags of the student's view and of the k teacher views, staged through a pinned ring beside `aug`
+        self.mirrored = self.t.flip_pairs is not None
+        if self.mirrored:
+            st["mirror"] = torch.zeros(1 + k, n, dtype=torch.uint8, device=dev)
+            self._mir_pin = [torch.zeros(1 + k, n, dtype=torch.uint8).pin_memory() for _ in range(4)]
+            self._mir_last = None
+            warp.mirror_perm(self.t.flip_pairs, label_s.shape[1], dev)      # (uploaded here, outside any capture; ValueError: a bad table)
         self._stage_aug(aug_param_stu, aug_param_tea)
         # the main graph reads the step's EFFECTIVE inputs: the originals, or what the style graphs wrote
         st["x_s_in"] = st["x_s"].clone() if self.styled else st["x_s"]
@@ -1136,8 +1178,11 @@ class GraphedTrainStep:
     def _step_args(self):
         """What the trainer's _forward_backward / _forward_part are called with, in the warm-up steps and in every capture."""
         st = self.static
-        return (st["x_s_in"], st["label_s"], st["weight_s"], st["x_t_stu"], [st["x_t_tea_in" + s] for s in self._sfx], st["theta_stu"],
+        args = (st["x_s_in"], st["label_s"], st["weight_s"], st["x_t_stu"], [st["x_t_tea_in" + s] for s in self._sfx], st["theta_stu"],
                 [st["theta_tea" + s] for s in self._sfx])
+        if self.mirrored:       # the static flip flags of the student's view and of the k teacher views
+            args += (st["mirror"][0], [st["mirror"][1 + i] for i in range(self.k)])
+        return args
 
     def _warm_up(self, warmup):
         t, dev = self.t, self.static["x_s"].device
@@ -1450,6 +1495,10 @@ class GraphedTrainStep:
         read (a ring of pinned host buffers and one asynchronous copy: nothing here waits for the device).  aug_param_tea: a list of k."""
         if aug_param_stu is None and aug_param_tea is None:
             return
+        flags = [warp.aug_mirror(ap, self.n) if ap is not None else None for ap in [aug_param_stu] + list(aug_param_tea or [None] * self.k)]
+        if not self.mirrored and any(f is not None and bool(f.any()) for f in flags):
+            raise ValueError("GraphedTrainStep was built without trainer.flip_pairs and captured the un-mirrored warps: it cannot take a batch "
+                             "with flipped samples - set trainer.flip_pairs and build a new GraphedTrainStep")
         i = self._aug_i = (self._aug_i + 1) % len(self._aug_pin)
         if self._aug_ev[i] is not None:
             self._aug_ev[i].synchronize()             # (the copy issued from this slot four steps ago: long done)
@@ -1461,6 +1510,15 @@ class GraphedTrainStep:
         for v, ap in enumerate(aug_param_tea or ()):      # (view v; `i` stays the ring slot the event below is kept in)
             warp.pack_aug_param(ap, self.n, out=pin[1 + v])
         self.static["aug"].copy_(pin, non_blocking=True)
+        if self.mirrored:
+            mpin = self._mir_pin[i]
+            if self._mir_last is not None:
+                mpin.copy_(self._mir_last)
+            for v, (ap, f) in enumerate(zip([aug_param_stu] + list(aug_param_tea or [None] * self.k), flags)):
+                if ap is not None:                    # (a 4-entry aug_param: an un-mirrored view, zeros)
+                    mpin[v] = f if f is not None else 0
+            self.static["mirror"].copy_(mpin, non_blocking=True)
+            self._mir_last = mpin
         ev = torch.cuda.Event()
         ev.record()
         self._aug_ev[i], self._aug_last = ev, pin
@@ -1540,7 +1598,8 @@ class GraphedTrainStep:
         frozen = [f for f in frozen if f[0] not in scheduled]
         frozen += [("sigma", float(t.sigma)), ("bn_momentum", float(t.student.bn_momentum)), ("occlude_rate", float(t.occlude_rate)),
                    ("occlude_thresh", float(t.occlude_thresh)), ("occlude_size", int(t.occlude_size)), ("warp_mode", str(t.warp_mode)),
-                   ("scheduled", scheduled)]
+                   ("scheduled", scheduled), ("flip_pairs", t.flip_pairs if t.flip_pairs is None or isinstance(t.flip_pairs, str)
+                                              else tuple(tuple(int(v) for v in pr) for pr in t.flip_pairs))]
         for gi, g in enumerate(opt.param_groups):
             for k in ("betas", "eps", "weight_decay", "momentum", "nesterov"):
                 if k in g:

@@ -60,7 +60,7 @@ def pack_aug_param(aug_param, n, out=None):
     """The collated aug_param structure -> one [N,6] float64 host tensor (angle, tx, ty, shear_x, shear_y, scale): what
     udapose_recon_thetas reads.  `out`: a (pinned) host tensor to fill instead of a new one."""
     import numpy as np
-    angle, (tx, ty), (sx, sy), scale = aug_param
+    angle, (tx, ty), (sx, sy), scale = aug_param[:4]
     cols = [np.asarray(_as_list(v, n), np.float64) for v in (angle, tx, ty, sx, sy, scale)]
     t = out if out is not None else torch.empty(n, 6, dtype=torch.float64)
     t.numpy()[...] = np.stack(cols, 1)
@@ -88,7 +88,7 @@ def recon_thetas(aug_param, n, ratio=1.0, device=None):
     import numpy as np
     if device is not None and torch.device(device).type == "cuda":
         return thetas_from_packed(pack_aug_param(aug_param, n).to(device), ratio)[0]
-    angle, (tx, ty), (sx, sy), scale = aug_param
+    angle, (tx, ty), (sx, sy), scale = aug_param[:4]
     angle, tx, ty, sx, sy, scale = (np.asarray(_as_list(v, n), np.float64) for v in (angle, tx, ty, sx, sy, scale))
     z, o = np.zeros(n), np.ones(n)
     th = np.stack([_inv_mats(z, tx / ratio, ty / ratio, o, z, z), _inv_mats(angle, z, z, scale, z, z), _inv_mats(z, z, z, o, sx, sy)], 1)
@@ -139,17 +139,36 @@ def _chain_call(mode, H, W):
     return lib().udapose_affine_bilinear
 
 
+MIRROR_OUT, MIRROR_IN = 1, 2            # UDAPOSE_MIRROR_OUT / UDAPOSE_MIRROR_IN: the two bits of a sample's `mirror` byte
+
+
+def _mirror_call(mode):
+    return lib().udapose_affine_nearest_mirror if mode == "nearest" else lib().udapose_affine_bilinear_mirror
+
+
+def _launch(mode, src, dst, th, mirror, perm, backward):
+    """The chain's launch, plain (mirror None: exactly the call of the un-mirrored package) or mirrored."""
+    N, C, H, W = src.shape
+    name = f"affine_{mode}" + ("_bwd" if backward else "")
+    if mirror is None:
+        check(_chain_call(mode, H, W)(_hip.stream(), ptr(src), ptr(dst), ptr(th), N, C, H, W, th.shape[1], backward), name)
+    else:
+        check(_mirror_call(mode)(_hip.stream(), ptr(src), ptr(dst), ptr(th), N, C, H, W, th.shape[1], backward, ptr(mirror), ptr(perm)),
+              name + "_mirror")
+
+
 class _WarpFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, theta, mode):
+    def forward(ctx, x, theta, mode, mirror=None, perm=None):
         _hip.require_cuda(x, theta)
         xin = x.detach().float().contiguous()
         N, C, H, W = xin.shape
         th = theta.detach().float().contiguous()
         assert th.shape[0] == N and th.shape[2] == 6
         out = torch.empty_like(xin)
-        check(_chain_call(mode, H, W)(_hip.stream(), ptr(xin), ptr(out), ptr(th), N, C, H, W, th.shape[1], 0), f"affine_{mode}")
+        _launch(mode, xin, out, th, mirror, perm, 0)
         ctx.save_for_backward(th)
+        ctx.mirror, ctx.perm = mirror, perm          # (not differentiable, never written by the package: kept as they are)
         ctx.in_dtype = x.dtype
         ctx.mode = mode
         return out.to(x.dtype)
@@ -158,18 +177,80 @@ class _WarpFn(torch.autograd.Function):
     def backward(ctx, g):
         (th,) = ctx.saved_tensors
         gin = g.detach().float().contiguous()
-        N, C, H, W = gin.shape
         dx = torch.empty_like(gin)
-        check(_chain_call(ctx.mode, H, W)(_hip.stream(), ptr(gin), ptr(dx), ptr(th), N, C, H, W, th.shape[1], 1), f"affine_{ctx.mode}_bwd")
-        return dx.to(ctx.in_dtype), None, None
+        _launch(ctx.mode, gin, dx, th, ctx.mirror, ctx.perm, 1)
+        return dx.to(ctx.in_dtype), None, None, None, None
 
 
-def warp_chain(x, theta, mode="nearest"):
+def mirror_perm(flip_pairs, num_channels, device):
+    """The joint permutation of a flip as a [C] int32 tensor on `device` (uploaded once per table and device): flip_pairs = a sequence of
+    pairs or a key of lib.keypoint_detection.FLIP_PAIRS; () - "hand21" - is the identity."""
+    from .lib import keypoint_detection as kd
+    perm = kd._perm_device(flip_pairs, num_channels, torch.device(device))
+    perm._udapose_involution = int(num_channels)          # (flip_perm builds an involution: _check_mirror need not read it back)
+    return perm
+
+
+def _check_mirror(x, mode, mirror, perm):
+    """Everything a mirrored launch relies on, before the launch: ValueError / NotImplementedError."""
+    N, C, H, W = x.shape
+    if not (torch.is_tensor(mirror) and mirror.is_cuda and mirror.dtype == torch.uint8 and tuple(mirror.shape) == (N,) and mirror.is_contiguous()):
+        raise ValueError(f"warp_chain: mirror must be a contiguous uint8 CUDA tensor of shape [{N}] (bit 0 MIRROR_OUT, bit 1 MIRROR_IN)")
+    if perm is not None:
+        if not (torch.is_tensor(perm) and perm.is_cuda and perm.dtype == torch.int32 and perm.dim() == 1 and perm.is_contiguous()):
+            raise ValueError("warp_chain: perm must be a contiguous int32 CUDA tensor [C]")
+        if perm.shape[0] != C:
+            raise ValueError(f"warp_chain: perm has {perm.shape[0]} entries for {C} channels")
+        if getattr(perm, "_udapose_involution", None) != C:
+            # read back once per tensor (mirror_perm's tables are cached, so a loop pays this once); a tensor first met inside a stream
+            # capture cannot be read: check it before capturing
+            if torch.cuda.is_current_stream_capturing():
+                raise ValueError("warp_chain: perm has not been checked yet and cannot be read inside a stream capture")
+            p = perm.cpu()
+            idx = torch.arange(C, dtype=torch.int32)
+            if bool(((p < 0) | (p >= C)).any()) or not torch.equal(p[p.long()], idx):
+                raise ValueError(f"warp_chain: perm {p.tolist()} is not an involution of 0..{C - 1} (a flip swaps joints in pairs)")
+            perm._udapose_involution = C
+    if mode == "bilinear" and not bilinear_fits_lds(H, W):
+        raise NotImplementedError(f"mirrored bilinear re-warp of {H}x{W} planes: two planes exceed the {BILINEAR_LDS_BYTES // 1024} KB LDS budget "
+                                  "and the stage-by-stage form has no mirrored counterpart")
+
+
+def warp_chain(x, theta, mode="nearest", mirror=None, perm=None):
     """x [N,C,H,W]; theta [N,S,6] inverse affine matrices applied in order 0..S-1 (zero fill); differentiable.  mode: "nearest" or
-    "bilinear" (the backward of either is deterministic)."""
+    "bilinear" (the backward of either is deterministic).
+    mirror: None (the plain launch), or a [N] uint8 CUDA tensor of two bits per sample: MIRROR_OUT reverses the columns of
+    the chain's output, MIRROR_IN those of its input; perm: None or the [C] int32 device tensor of the flip's joint permutation (an
+    involution, `mirror_perm`), applied to the samples with exactly one bit set: out[n, c] comes from x[n, perm[c]].  Forward and backward
+    give the bits of the composition of torch.flip(., [-1]), index_select by perm and the plain call."""
     if mode not in MODES:
         raise ValueError(f"warp mode {mode!r}: one of {MODES}")
-    return _WarpFn.apply(x, theta, mode)
+    if mirror is None:
+        if perm is not None:
+            raise ValueError("warp_chain: perm without mirror")
+        return _WarpFn.apply(x, theta, mode)
+    _hip.require_cuda(x, theta)
+    _check_mirror(x, mode, mirror, perm)
+    return _WarpFn.apply(x, theta, mode, mirror, perm)
+
+
+def aug_mirror(aug_param, n):
+    """The flip flags of a collated aug_param as a uint8 [N] host tensor: None for the reference's 4 entries; the optional 5th entry is
+    flip[N] with values 0 or 1 (data_gpu.ViewConfig(flip=)).  ValueError for anything else."""
+    if not isinstance(aug_param, (list, tuple)) or len(aug_param) not in (4, 5):
+        raise ValueError(f"aug_param: expected (angle, (tx, ty), (shear_x, shear_y), scale[, flip]), got {type(aug_param).__name__} of "
+                         f"{len(aug_param) if hasattr(aug_param, '__len__') else '?'} entries")
+    if len(aug_param) == 4:
+        return None
+    f = aug_param[4]
+    f = f.detach().cpu() if torch.is_tensor(f) else torch.as_tensor(f)
+    if f.dim() != 1 or f.shape[0] != n:
+        raise ValueError(f"aug_param: flip has shape {tuple(f.shape)} for a batch of {n}")
+    if f.dtype == torch.bool:
+        f = f.to(torch.uint8)
+    if not bool(((f == 0) | (f == 1)).all()):
+        raise ValueError(f"aug_param: flip flags must be 0 or 1, got {f.tolist()}")
+    return f.to(torch.uint8).contiguous()
 
 
 def mean_views(views):
@@ -256,12 +337,27 @@ def affine(img, angle, translate, scale, shear, interpolation=None, fill=None):
     return out.squeeze(0) if squeeze else out
 
 
-def recon_heatmaps(y, aug_param, ratio, mode="nearest"):
-    """The loop's heat-map re-warp (train_human.py:361-372 / 418-423) for the whole batch."""
-    return warp_chain(y, recon_thetas(aug_param, y.shape[0], ratio, y.device), mode)
+def recon_heatmaps(y, aug_param, ratio, mode="nearest", flip_pairs=None):
+    """The loop's heat-map re-warp (train_human.py:361-372 / 418-423) for the whole batch.  aug_param may carry the flip flags of mirrored
+    views as a 5th entry (`aug_mirror`): a flagged sample is un-mirrored after the chain, its left / right channels swapped by flip_pairs
+    (a sequence of pairs or a key of lib.keypoint_detection.FLIP_PAIRS; () is a valid table) - required then, ValueError before any launch."""
+    n = y.shape[0]
+    flags = aug_mirror(aug_param, n)
+    if flags is None or not bool(flags.any()):
+        return warp_chain(y, recon_thetas(aug_param, n, ratio, y.device), mode)
+    if flip_pairs is None:
+        raise ValueError("recon_heatmaps: the batch has mirrored samples: pass flip_pairs (a sequence of left / right joint pairs, possibly "
+                         "empty, or a key of FLIP_PAIRS)")
+    perm = mirror_perm(flip_pairs, y.shape[1], y.device)
+    return warp_chain(y, recon_thetas(aug_param, n, ratio, y.device), mode, flags.to(y.device), perm)
 
 
-def occlude_keypoints(x_t_stu, y_t_tea_recon, aug_param_stu, ratio, image_size, occlude_rate, occlude_thresh, occlude_size, rng):
+def _mirror_in(mirror):
+    """Flip flags (the MIRROR_OUT byte of the warp to the base frame) -> the MIRROR_IN byte of the warp back to the view."""
+    return None if mirror is None else mirror * MIRROR_IN
+
+
+def occlude_keypoints(x_t_stu, y_t_tea_recon, aug_param_stu, ratio, image_size, occlude_rate, occlude_thresh, occlude_size, rng, mirror=None):
     """Adaptive key-point occlusion of the student's target images (train_human.py:374-412), batched on the device.
 
     Host side (exactly the reference's draws, in its order, from `rng` = np.random): per sample with at least one confidence
@@ -270,6 +366,8 @@ def occlude_keypoints(x_t_stu, y_t_tea_recon, aug_param_stu, ratio, image_size, 
     re-warped to the canonical frame (three nearest warps, with the reference's translate/ratio quirk), a random patch
     of the same image is pasted over the chosen key-point, and one inverse warp takes them back.
     Naming follows the reference's index math, not its variable names: `left/right` slice ROWS, `upper/bottom` slice COLUMNS.
+    mirror: None, or the [N] uint8 CUDA flip flags of the student's view: a flagged image is un-mirrored after the warp to the canonical
+    frame (MIRROR_OUT) and mirrored again ahead of the warp back (MIRROR_IN); images have no joint permutation.
     """
     import numpy as np
     from . import utils as U
@@ -278,7 +376,7 @@ def occlude_keypoints(x_t_stu, y_t_tea_recon, aug_param_stu, ratio, image_size, 
     conf_np = conf.reshape(B, K).cpu().numpy()
     pos_np = preds.cpu().numpy().astype(np.int64)                   # [B,K,2] = (x, y)
     table = conf_np >= occlude_thresh
-    angle, (tx, ty), (sx, sy), scale = aug_param_stu
+    angle, (tx, ty), (sx, sy), scale = aug_param_stu[:4]
     a_, tx_, ty_, sx_, sy_, sc_ = (_as_list(v, B) for v in (angle, tx, ty, sx, sy, scale))
     sel, boxes = [], []
     for b in range(B):
@@ -301,12 +399,13 @@ def occlude_keypoints(x_t_stu, y_t_tea_recon, aug_param_stu, ratio, image_size, 
     fwd = recon_thetas([sub[0], [sub[1], sub[2]], [sub[3], sub[4]], sub[5]], n, ratio, dev)
     back = single_thetas([-v for v in sub[0]], ([-v / ratio for v in sub[1]], [-v / ratio for v in sub[2]]), [1.0 / v for v in sub[5]],
                          ([-v for v in sub[3]], [-v for v in sub[4]]), n, dev)
-    temp = warp_chain(x_t_stu.index_select(0, idx).float().contiguous(), fwd).contiguous()
+    msel = None if mirror is None else mirror.index_select(0, idx).contiguous()
+    temp = warp_chain(x_t_stu.index_select(0, idx).float().contiguous(), fwd, mirror=msel).contiguous()
     bx = torch.tensor(boxes, dtype=torch.int32, device=dev)
     maxel = int(max((b[1] - b[0]) * (b[3] - b[2]) for b in boxes)) * temp.shape[1]
     check(lib().udapose_patch_paste(_hip.stream(), ptr(temp), ptr(bx), n, temp.shape[1], temp.shape[2], temp.shape[3], maxel), "patch_paste")
     out = x_t_stu.clone()
-    out.index_copy_(0, idx, warp_chain(temp, back).to(x_t_stu.dtype))
+    out.index_copy_(0, idx, warp_chain(temp, back, mirror=_mirror_in(msel)).to(x_t_stu.dtype))
     return out, sel
 
 
@@ -314,17 +413,19 @@ def occlusion_back_thetas(aug_param_stu, n, ratio, device=None):
     """[N,1,6]: the warp back of the occlusion path (train_human.py:412): -angle, (-tx/ratio, -ty/ratio), 1/scale, (-shear)."""
     if device is not None and torch.device(device).type == "cuda":
         return thetas_from_packed(pack_aug_param(aug_param_stu, n).to(device), ratio, want_fwd=False, want_back=True)[1]
-    angle, (tx, ty), (sx, sy), scale = aug_param_stu
+    angle, (tx, ty), (sx, sy), scale = aug_param_stu[:4]
     a_, tx_, ty_, sx_, sy_, sc_ = (_as_list(v, n) for v in (angle, tx, ty, sx, sy, scale))
     return single_thetas([-v for v in a_], ([-v / ratio for v in tx_], [-v / ratio for v in ty_]), [1.0 / v for v in sc_],
                          ([-v for v in sx_], [-v for v in sy_]), n, device)
 
 
-def occlude_keypoints_device(x_t_stu, y_t_tea_recon, theta_fwd, theta_back, u, ratio, image_size, occlude_rate, occlude_thresh, occlude_size):
+def occlude_keypoints_device(x_t_stu, y_t_tea_recon, theta_fwd, theta_back, u, ratio, image_size, occlude_rate, occlude_thresh, occlude_size,
+                             mirror=None):
     """The same occlusion with its DECISIONS taken on the device (udapose_occlusion_pick): no read-back, fixed shapes - the step
     stays capturable.  theta_fwd = recon_thetas(aug_param_stu), theta_back = occlusion_back_thetas(aug_param_stu), u = [N,4]
     uniform [0,1) draws (rate test, key-point choice, patch row / column origin).  Every image goes through the warps; only the
-    selected samples keep the result (the others are returned bit-identical).  Returns (images, apply [N] uint8)."""
+    selected samples keep the result (the others are returned bit-identical).  mirror: as for occlude_keypoints.
+    Returns (images, apply [N] uint8)."""
     _hip.require_cuda(x_t_stu, y_t_tea_recon, theta_fwd, theta_back, u)
     B, K, h, w = y_t_tea_recon.shape
     hm = ha.f32c(y_t_tea_recon)
@@ -336,11 +437,11 @@ def occlude_keypoints_device(x_t_stu, y_t_tea_recon, theta_fwd, theta_back, u, r
     check(lib().udapose_occlusion_pick(_hip.stream(), ptr(peak.maxv), ptr(peak.idx), ptr(uu), B, K, w, float(ratio), int(image_size), float(occlude_rate),
                                        float(occlude_thresh), int(occlude_size), ptr(boxes), ptr(apply)), "occlusion_pick")
     x = x_t_stu.detach().float().contiguous()
-    temp = warp_chain(x, theta_fwd).contiguous()
+    temp = warp_chain(x, theta_fwd, mirror=mirror).contiguous()
     C_ = temp.shape[1]
     check(lib().udapose_patch_paste(_hip.stream(), ptr(temp), ptr(boxes), B, C_, temp.shape[2], temp.shape[3], 4 * occlude_size * occlude_size * C_),
           "patch_paste")
-    back = warp_chain(temp, theta_back).contiguous()
+    back = warp_chain(temp, theta_back, mirror=_mirror_in(mirror)).contiguous()
     out = torch.empty_like(x)
     check(lib().udapose_select_rows(_hip.stream(), ptr(out), ptr(back), ptr(x), ptr(apply), B, x[0].numel()), "select_rows")
     return out.to(x_t_stu.dtype), apply
