@@ -549,6 +549,30 @@ int udapose_flip_merge(void* stream, const float* a, const float* f, const int* 
 #define UDAPOSE_REFINE_MAX_PIXELS 19200
 int udapose_refine_decode(void* stream, const float* hm, int R, int H, int W, int mode, int kernel, float sigma, float* coords, float* maxvals,
                           int* flat_idx);
+/* Top-down inference, the image side: box crops (the reference's crop + Resize, lib/datasets/util.py:87-123, and crop_ori, util.py:235-287,
+ * on the device).  frames [F][Hs][Ws][3] uint8; frame_idx [M] int32 (several boxes may name one frame); boxes [M][5] fp32 =
+ * (cx, cy, bw, bh, rot_deg); mean3, std3 [3] fp32; all four are read from device memory, so a captured launch follows new boxes.
+ * out_f32 [M or 2M][3][Ho][Wo] fp32 normalised (udapose_aug_to_tensor's expression; may be NULL, mean3 / std3 may be NULL then),
+ * out_u8 [M or 2M][Ho][Wo][3] uint8 = min(255, floor(value + 0.5)) (may be NULL; not both); status [M] bytes.
+ * Pixel i covers [i, i + 1).  sx = bw / Wo, sy = bh / Ho, (c, s) = (cos, sin)(rot) - exact for multiples of 90 degrees, else the fp64 value
+ * rounded to fp32; tx = clamp(ceil(sx), 1, 8), ty likewise.  Output pixel (u, v) is the mean of tx * ty bilinear samples at
+ *   dx = ((u + (i + 0.5) / tx) - Wo / 2) * sx, dy = ((v + (j + 0.5) / ty) - Ho / 2) * sy, X = cx + c dx - s dy, Y = cy + s dx + c dy,
+ * each reading x0 = floor(X - 0.5) with weight X - 0.5 - x0 on x0 + 1 (the same in y); a tap outside the frame contributes 0 (zero padding
+ * in pixel values, ahead of the normalisation); samples are added j-major, then divided by tx * ty: no atomics, the same bits every time.
+ * A box more than 8 times the output size is under-sampled (the tap cap).  Exact in fp32 when sx, sy are in {1/2, 1, 2, 4, 8}, cx, cy are
+ * multiples of 1/8 and rot is a multiple of 90.  mirror = 1: images M .. 2M-1 are the column-reversed crops, from the same reads.
+ * status[m] = 1 and a crop of zero pixel values, with nothing of the frames read, for a box with a non-finite field, bw <= 0 or bh <= 0,
+ * or a frame index outside [0, F); 0 otherwise.  UDAPOSE_ERR_ARG (nothing launched): a null required pointer or both outputs null,
+ * F < 1, M < 1 or M > 65535, Ho or Wo outside [1, 1024], Hs or Ws outside [1, 8192], mirror other than 0 / 1. */
+int udapose_box_crop(void* stream, const unsigned char* frames_u8, int F, int Hs, int Ws, const int* frame_idx, const float* boxes, int M,
+                     int Ho, int Wo, const float* mean3, const float* std3, int mirror, float* out_f32, unsigned char* out_u8,
+                     unsigned char* status);
+/* The way back: coords [M][K][2] fp32 (x, y) in heat-map pixels of crop m (index i stands for input coordinate i * stride, generate_target's
+ * convention) -> out [M][K][2] in pixels of the frame: (cx, cy) + R(rot) (((x stride_x, y stride_y) - (Wo / 2, Ho / 2)) * (sx, sy)), with
+ * udapose_box_crop's sx, sy, c, s.  A refused box gives what its fields give (NaN for NaN).  UDAPOSE_ERR_ARG: a null pointer, M, K, Ho or
+ * Wo < 1. */
+int udapose_coords_to_image(void* stream, const float* coords, const float* boxes, int M, int K, float stride_x, float stride_y, int Ho, int Wo,
+                            float* out);
 /* confidence mask (train_human.py:427-430): thr = k-th smallest of act[n]; mask[i] = (tea_mask[i]*act_local[i]) > thr */
 int udapose_kth_mask(void* stream, const float* act, const float* tea_mask, int n, int k, float* thr_out, unsigned char* mask,
                      const float* act_local, int n_local);

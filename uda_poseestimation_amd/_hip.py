@@ -154,6 +154,8 @@ _SIGS = {
     "udapose_hflip_batch": (ci, [vp, vp, vp, ci, sz, ci, ci]),
     "udapose_flip_merge": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
     "udapose_refine_decode": (ci, [vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, vp]),
+    "udapose_box_crop": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp]),
+    "udapose_coords_to_image": (ci, [vp, vp, vp, ci, ci, cf, cf, ci, ci, vp]),
     "udapose_kth_mask": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, ci]),
     "udapose_kth_mask_dev": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, ci]),      # (k: an int32 in device memory)
     "udapose_topk_select": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),

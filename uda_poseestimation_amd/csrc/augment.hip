@@ -95,9 +95,9 @@ __global__ void aug_to_tensor_k(const unsigned char* __restrict__ img, float* __
     float* o = out + (size_t)n * 3 * HW;
     const float m0 = mean3[0], m1 = mean3[1], m2 = mean3[2], s0 = std3[0], s1 = std3[1], s2 = std3[2];
     for (int i = blockIdx.x * TPB + threadIdx.x; i < HW; i += gridDim.x * TPB) {
-        o[i] = ((float)p[(size_t)i * 3] / 255.f - m0) / s0;
-        o[HW + i] = ((float)p[(size_t)i * 3 + 1] / 255.f - m1) / s1;
-        o[2 * HW + i] = ((float)p[(size_t)i * 3 + 2] / 255.f - m2) / s2;
+        o[i] = to_tensor_norm((float)p[(size_t)i * 3], m0, s0);
+        o[HW + i] = to_tensor_norm((float)p[(size_t)i * 3 + 1], m1, s1);
+        o[2 * HW + i] = to_tensor_norm((float)p[(size_t)i * 3 + 2], m2, s2);
     }
 }
 

@@ -447,6 +447,14 @@ int udapose_flip_merge(void* stream, const float* a, const float* f, const int* 
                        float* maxvals, int* flat_idx, float* preds_xy) {
     return flip_merge(S(stream), a, f, perm, N, K, H, W, shift, mode, out, maxvals, flat_idx, preds_xy);
 }
+int udapose_box_crop(void* stream, const unsigned char* frames_u8, int F, int Hs, int Ws, const int* frame_idx, const float* boxes, int M, int Ho,
+                     int Wo, const float* mean3, const float* std3, int mirror, float* out_f32, unsigned char* out_u8, unsigned char* status) {
+    return box_crop(S(stream), frames_u8, F, Hs, Ws, frame_idx, boxes, M, Ho, Wo, mean3, std3, mirror, out_f32, out_u8, status);
+}
+int udapose_coords_to_image(void* stream, const float* coords, const float* boxes, int M, int K, float stride_x, float stride_y, int Ho, int Wo,
+                            float* out) {
+    return box_coords_to_image(S(stream), coords, boxes, M, K, stride_x, stride_y, Ho, Wo, out);
+}
 int udapose_refine_decode(void* stream, const float* hm, int R, int H, int W, int mode, int kernel, float sigma, float* coords, float* maxvals,
                           int* flat_idx) {
     return refine_decode(S(stream), hm, R, H, W, mode, kernel, sigma, coords, maxvals, flat_idx);

@@ -1,6 +1,10 @@
-// Host launchers of the data pipeline: warps, occlusion and patches (affine.hip), the merge of the teacher's views (view_merge.hip), image augmentation and label maps (augment.hip), the strong view's colour ops and erase (strong_aug.hip).
+// Host launchers of the data pipeline: warps, occlusion and patches (affine.hip), the merge of the teacher's views (view_merge.hip), image augmentation and label maps (augment.hip), box crops and their coordinate maps (box_crop.hip), the strong view's colour ops and erase (strong_aug.hip).
 #pragma once
 #include "common.h"
+
+// ToTensor + Normalize of one byte-range value v (0 .. 255; an integer in aug_to_tensor_k, any fp32 value in box_crop_k): float32 operations
+// in torch's order.  Stated once: wherever v is an integer, box_crop_k's normalised output has the bits of aug_to_tensor_k's.
+__device__ __forceinline__ float to_tensor_norm(float v, float mean, float std) { return (v / 255.f - mean) / std; }
 
 // affine.hip
 int occlusion_pick(hipStream_t s, const float* conf, const int* idx, const float* u, int N, int K, int w, double ratio, int image_size, float rate,
@@ -32,6 +36,11 @@ int aug_gaussian_labels_subpixel(hipStream_t s, const double* kp, const float* v
                                  double stride_x, double stride_y, double sigma, int rad);
 int aug_draw_labelmap_ori(hipStream_t s, const float* pt, const float* vis, const unsigned char* gate, float* target, float* weight, int R, int Hh,
                           int Wh, float r3, const float* patch, int psize);
+// box_crop.hip
+int box_crop(hipStream_t s, const unsigned char* frames, int F, int Hs, int Ws, const int* frame_idx, const float* boxes, int M, int Ho, int Wo,
+             const float* mean3, const float* std3, int mirror, float* out_f32, unsigned char* out_u8, unsigned char* status);
+int box_coords_to_image(hipStream_t s, const float* coords, const float* boxes, int M, int K, float stride_x, float stride_y, int Ho, int Wo,
+                        float* out);
 // strong_aug.hip
 int aug_point_op(hipStream_t s, unsigned char* img, const int* op, const int* param, const double* inv_scale, unsigned char* lut, int N, int HW);
 int aug_sharpness_u8(hipStream_t s, unsigned char* img, unsigned char* tmp, const int* op, const float* factor, int N, int H, int W);

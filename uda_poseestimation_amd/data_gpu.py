@@ -27,6 +27,10 @@ Mirrored views: `ViewConfig(flip=p)` mirrors a sample's base cr
 view is A(M(base)) - with the key points following the reference's `hflip` (lib/transforms/keypoint_detection.py:108-116, x -> W - 1 - x)
 and re-indexed by the left / right joint pairs; the flags travel as a 5th entry of the view's `aug_param`, which the re-warps undo
 (warp.recon_heatmaps, the trainers).  Off by default: no draw, no launch, the reference's 4-entry aug_param.
+
+Box crops: `box_crop` cuts boxes (cx, cy, bw, bh, rot_deg) that may leave the frame, be turned or non-square out of uint8
+frames and resizes them in one launch (csrc/box_crop.hip) - the device counterpart of the datasets' crop + Resize and crop_ori, the image
+side of `engine.predict`; `TargetViewPipeline.box_crop` hands such crops to `view()`.
 """
 import math
 import random
@@ -209,6 +213,110 @@ def strong_op_arrays(ops, params, N):
                     raise ValueError(f"strong_: solarize threshold {p!r} is not finite")
                 ipar[j, n] = min(256, max(0, math.ceil(p)))
     return code, color, fpar, ipar
+
+
+_NORM_CACHE = {}      # (device, mean, std) -> their fp32 device copies: a loop (and a captured launch) uploads them once
+
+
+def _norm_consts(device, mean, std):
+    """mean / std of a normalisation as fp32 [3] tensors on `device`: device tensors pass through, tuples are uploaded once."""
+    if torch.is_tensor(mean) and torch.is_tensor(std):
+        return mean.to(device=device, dtype=torch.float32).contiguous(), std.to(device=device, dtype=torch.float32).contiguous()
+    key = (device, tuple(float(v) for v in mean), tuple(float(v) for v in std))
+    c = _NORM_CACHE.get(key)
+    if c is None:
+        if len(key[1]) != 3 or len(key[2]) != 3:
+            raise ValueError("mean and std have one value per channel")
+        c = _NORM_CACHE[key] = (torch.tensor(key[1], dtype=torch.float32, device=device), torch.tensor(key[2], dtype=torch.float32, device=device))
+    return c
+
+
+def box_inputs(frames_u8, boxes, frame_idx):
+    """The arguments of a box crop, checked, as device tensors: (boxes [M,5] fp32, frame_idx [M] int32, host_checked).  Host boxes (numpy,
+    list) go through lib.keypoint_detection.check_boxes - a bad box raises ValueError naming its row, before any launch - and a host
+    frame_idx is checked against the frame count; CUDA tensors are taken as they are (the launch reports them in `status`).  frame_idx
+    None: box m crops frame m (M == F)."""
+    from .lib import keypoint_detection as kd
+    _hip.require_cuda(frames_u8)
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.dtype != torch.uint8 or not frames_u8.is_contiguous():
+        raise ValueError(f"frames must be a contiguous uint8 tensor [F,Hs,Ws,3], got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    F, dev = frames_u8.shape[0], frames_u8.device
+    host = not torch.is_tensor(boxes)
+    if host:
+        bd = torch.from_numpy(kd.check_boxes(boxes).astype(np.float32)).to(dev, non_blocking=True)
+    else:
+        _hip.require_cuda(boxes)
+        if boxes.dim() != 2 or boxes.shape[1] != 5 or boxes.shape[0] < 1 or boxes.device != dev:
+            raise ValueError(f"boxes must be [M,5] on {dev}, got {tuple(boxes.shape)} on {boxes.device}")
+        bd = boxes.detach().to(torch.float32).contiguous()
+    M = bd.shape[0]
+    if frame_idx is None:
+        if M != F:
+            raise ValueError(f"{M} boxes for {F} frames: give frame_idx [M]")
+        fd = torch.arange(M, dtype=torch.int32, device=dev)
+    elif torch.is_tensor(frame_idx) and frame_idx.is_cuda:
+        if tuple(frame_idx.shape) != (M,) or frame_idx.device != dev or frame_idx.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"frame_idx must be an integer tensor [{M}] on {dev}")
+        fd = frame_idx.to(torch.int32).contiguous()
+    else:
+        fi = np.asarray(frame_idx)
+        if fi.shape != (M,) or not np.issubdtype(fi.dtype, np.integer):
+            raise ValueError(f"frame_idx must be {M} integers, got {fi.dtype} {fi.shape}")
+        bad = np.nonzero((fi < 0) | (fi >= F))[0]
+        if bad.size:
+            raise ValueError(f"box {int(bad[0])} names frame {int(fi[bad[0]])} of {F}")
+        fd = torch.from_numpy(fi.astype(np.int32)).to(dev, non_blocking=True)
+    return bd, fd, host
+
+
+def box_crop_launch(frames_u8, boxes_d, fidx_d, Ho, Wo, mean_d, std_d, mirror, want_f32, want_u8):
+    """udapose_box_crop on checked device arguments -> (out_f32 or None, out_u8 or None, status [M] uint8)."""
+    F, Hs, Ws, _ = frames_u8.shape
+    M, dev = boxes_d.shape[0], frames_u8.device
+    n = 2 * M if mirror else M
+    of = torch.empty(n, 3, Ho, Wo, dtype=torch.float32, device=dev) if want_f32 else None
+    ou = torch.empty(n, Ho, Wo, 3, dtype=torch.uint8, device=dev) if want_u8 else None
+    status = torch.empty(M, dtype=torch.uint8, device=dev)
+    check(lib().udapose_box_crop(_hip.stream(), ptr(frames_u8), F, Hs, Ws, ptr(fidx_d), ptr(boxes_d), M, Ho, Wo, ptr(mean_d), ptr(std_d),
+                                 int(bool(mirror)), ptr(of), ptr(ou), ptr(status)), "box_crop")
+    return of, ou, status
+
+
+def box_crop(frames_u8, boxes, size, frame_idx=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, mirror=False, out="f32"):
+    """Top-down inference's image side (udapose_box_crop, one launch): boxes [M,5] = (cx, cy, bw, bh, rot_deg) in pixels of
+    frames_u8 [F,Hs,Ws,3] uint8 CUDA (pixel i covers [i, i + 1)), each resized to `size` = S or (Ho, Wo).  The padded / rotated /
+    non-square counterpart of the reference's crop + Resize and crop_ori: a box may leave the frame (zero padding in pixel values, ahead
+    of the normalisation), be turned by rot degrees (get_transform's sign) and have bw != bh.  Every output pixel is the mean of
+    tx * ty bilinear samples, tx = clamp(ceil(bw / Wo), 1, 8) - an area filter up to 8x reduction; beyond 8x the box is under-sampled (the
+    tap cap).  This is NOT PIL's resampling filter: `TargetViewPipeline.resized_crop` keeps PIL's bits for square boxes inside the frame.
+    frame_idx [M]: the frame of every box (several boxes may name one frame); None: box m crops frame m.
+    out="f32": [M,3,Ho,Wo] fp32, (value / 255 - mean) / std as `to_tensor`; out="u8": [M,Ho,Wo,3] uint8, min(255, floor(value + 0.5)).
+    mirror=True: 2M images, the crops followed by their column-reversed copies (ops.hflip_batch(keep_original=True)'s layout) out of the
+    same launch.  boxes as a numpy array or a list are checked on the host (ValueError naming the row; frame_idx likewise) and the crops
+    are returned; boxes as a CUDA tensor are not read here: (crops, status [M] uint8) comes back, status 1 = refused (a non-finite field,
+    bw or bh <= 0, a frame index outside the frames), its crop all zero pixel values."""
+    Ho, Wo = _crop_size(size)
+    if out not in ("f32", "u8"):
+        raise ValueError(f"out must be 'f32' or 'u8', got {out!r}")
+    bd, fd, host = box_inputs(frames_u8, boxes, frame_idx)
+    _check_frame_size(frames_u8)
+    md, sd = _norm_consts(frames_u8.device, mean, std)
+    of, ou, status = box_crop_launch(frames_u8, bd, fd, Ho, Wo, md, sd, mirror, out == "f32", out == "u8")
+    crops = of if out == "f32" else ou
+    return crops if host else (crops, status)
+
+
+def _crop_size(size):
+    from .lib import keypoint_detection as kd
+    Ho, Wo = kd._hw(size)
+    if Ho > 1024 or Wo > 1024:
+        raise ValueError(f"a box crop is at most 1024 x 1024, got {Ho} x {Wo}")
+    return Ho, Wo
+
+
+def _check_frame_size(frames_u8):
+    if frames_u8.shape[0] < 1 or not (1 <= frames_u8.shape[1] <= 8192 and 1 <= frames_u8.shape[2] <= 8192):
+        raise ValueError(f"frames of 1 .. 8192 pixels a side, at least one, got {tuple(frames_u8.shape)}")
 
 
 class ViewConfig:
@@ -420,6 +528,18 @@ class TargetViewPipeline:
             kp[n, :, 1] -= top
             kp[n] *= float(S) / float(w)
         return out, kp
+
+    def box_crop(self, frames_u8, keypoints, boxes, frame_idx=None):
+        """The padded / rotated counterpart of `resized_crop`, ready for `view()`: boxes [M,5] = (cx, cy, bw, bh, rot_deg) on the host
+        (lib.keypoint_detection.boxes_from_keypoints / boxes_from_center_scale make them; checked, ValueError naming a bad row) cut from
+        frames_u8 [F,Hs,Ws,3] uint8 CUDA (frame_idx [M]: the frame of every box, None: box m crops frame m) and resized to image_size by
+        `data_gpu.box_crop` - its own area filter, not PIL's; a box may leave the frame or be non-square.  keypoints [M,K,2] in pixels of
+        the frames -> (base_u8 [M,S,S,3], key points [M,K,2] in the crop, lib.keypoint_detection.to_crop_coords)."""
+        from .lib import keypoint_detection as kd
+        S = self.image_size
+        hb = kd.check_boxes(boxes)
+        kp = kd.to_crop_coords(keypoints, hb, (S, S))
+        return box_crop(frames_u8, hb, (S, S), frame_idx=frame_idx, out="u8"), kp
 
     def jitter_(self, img_u8, ops, factors):
         """ColorJitter in place: ops / factors = per-sample lists of three op codes / factors (applied in list order)."""

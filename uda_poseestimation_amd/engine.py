@@ -21,6 +21,7 @@ import torch
 import torch.distributed as dist
 
 from . import adversarial
+from . import data_gpu
 from . import ops
 from . import optim as fused_optim
 from . import utils as mt
@@ -1028,6 +1029,84 @@ def evaluate(batches, model, thresholds=kd.PCK_THRESHOLDS, groups=None, criterio
         warnings.warn(f"evaluate(): {sat} f16x2 stores saturated at |x| = 65504 (or were NaN) since the last check - activations outside fp16's "
                       "range; run the model with precision='fp32' (exact, slower) to rule the format out")
     return rep
+
+
+def predict(frames_u8, boxes, model, frame_idx=None, flip_pairs=None, shift_heatmap=False, decode="argmax", batch=32, input_size=None,
+            mean=data_gpu.IMAGENET_MEAN, std=data_gpu.IMAGENET_STD, return_heatmaps=False):
+    """Top-down inference on the device: pictures and boxes in, key points in the pictures' own pixels out.
+    frames_u8 [F,Hs,Ws,3] uint8 CUDA; boxes [M,5] = (cx, cy, bw, bh, rot_deg) in pixels of their frames (lib.keypoint_detection.
+    boxes_from_keypoints / boxes_from_center_scale make them) - a numpy array or a list, checked on the host (ValueError naming a bad
+    row, before any launch), or a CUDA tensor, which is not read here; frame_idx [M]: the frame of every box (None: box m is on frame m).
+    Per chunk of `batch` boxes: data_gpu's box crop to input_size (S or (H, W); None: 256, the reference's --image-size) normalised by
+    mean / std, the evaluation forward, the decode ("argmax", "soft", "quarter", "dark" or a callable, as in validate()) and
+    udapose_coords_to_image.  The last chunk is padded to `batch` with repeats of its first box and the padding rows are dropped: the
+    folded evaluation forward has no cross-image term, so one plan serves every chunk and the result does not depend on `batch`.
+    flip_pairs (a sequence of left / right joint pairs or a key of lib.keypoint_detection.FLIP_PAIRS; shift_heatmap as in flip_forward):
+    the flip test - the crop launch writes the mirrored crops behind the plain ones, one forward of 2 x batch images, udapose_flip_merge;
+    with decode="argmax" the merge launch's own decode is used.
+    Returns {"keypoints": [M,K,2] fp32 (x, y) in pixels of the frames, "confidence": [M,K] the (merged) map's maximum, "status": [M] uint8,
+    1 = the box was refused (its key points mean nothing), "heatmaps": [M,K,Hh,Wh] with return_heatmaps}, all on the device.  Eval mode
+    under no_grad, the model's mode restored.  Nothing is read back and, with device boxes, nothing is uploaded: a call can be captured
+    into a graph, and a replay follows new values in the same boxes tensor.  Outside a capture the call ends with validate()'s
+    saturation check of the f16x2 evaluation forward (the one host synchronisation, after the last launch)."""
+    Ho, Wo = data_gpu._crop_size(256 if input_size is None else input_size)
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    bd, fd, _ = data_gpu.box_inputs(frames_u8, boxes, frame_idx)
+    data_gpu._check_frame_size(frames_u8)
+    dev = frames_u8.device
+    K = model.num_keypoints
+    perm = kd._perm_device(flip_pairs, K, dev) if flip_pairs is not None else None      # (a bad table fails here, before any launch)
+    fused = perm is not None and isinstance(decode, str) and decode == "argmax"
+    md, sd = data_gpu._norm_consts(dev, mean, std)
+    M = bd.shape[0]
+    keypoints = torch.empty(M, K, 2, dtype=torch.float32, device=dev)
+    confidence = torch.empty(M, K, dtype=torch.float32, device=dev)
+    status = torch.empty(M, dtype=torch.uint8, device=dev)
+    heatmaps = None
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for i0 in range(0, M, batch):
+                n = min(batch, M - i0)
+                b, fi = bd[i0:i0 + n], fd[i0:i0 + n]
+                if n < batch:
+                    b = torch.cat([b, b[:1].expand(batch - n, 5)]).contiguous()
+                    fi = torch.cat([fi, fi[:1].expand(batch - n)]).contiguous()
+                x, _, st = data_gpu.box_crop_launch(frames_u8, b, fi, Ho, Wo, md, sd, perm is not None, True, False)
+                if perm is not None:
+                    y2 = model(x)
+                    y, preds, maxv = kd._flip_merge(y2[:batch], y2[batch:], perm, shift_heatmap, fused, out=y2[:batch])
+                    if fused:
+                        maxv = maxv.reshape(batch, K)
+                    else:
+                        preds, maxv = kd._decode_pred_max(y, decode)
+                else:
+                    y = model(x).float().contiguous()
+                    preds, maxv = kd._decode_pred_max(y, decode)
+                Hh, Wh = y.shape[2:]
+                keypoints[i0:i0 + n] = kd._coords_to_image(preds, b, Ho, Wo, Wo / Wh, Ho / Hh)[:n]
+                confidence[i0:i0 + n] = maxv[:n]
+                status[i0:i0 + n] = st[:n]
+                if return_heatmaps:
+                    if heatmaps is None:
+                        heatmaps = torch.empty(M, K, Hh, Wh, dtype=torch.float32, device=dev)
+                    heatmaps[i0:i0 + n] = y[:n]
+    finally:
+        if was_training:
+            model.train()
+    out = {"keypoints": keypoints, "confidence": confidence, "status": status}
+    if return_heatmaps:
+        out["heatmaps"] = heatmaps
+    if not torch.cuda.is_current_stream_capturing():
+        sat = mt.split_saturations(reset=True)          # (as validate(): the evaluation forward runs the f16x2 mode under 'auto')
+        if sat:
+            import warnings
+            warnings.warn(f"predict(): {sat} f16x2 stores saturated at |x| = 65504 (or were NaN) since the last check - activations outside "
+                          "fp16's range; run the model with precision='fp32' (exact, slower) to rule the format out")
+    return out
 
 
 class GraphedTrainStep:

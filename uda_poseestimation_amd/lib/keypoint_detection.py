@@ -3,7 +3,9 @@ decode the reference lacks (`soft_argmax`, csrc/softargmax.hip: sub-pixel coordi
 decodes (`quarter_decode`, `dark_decode`, csrc/refine.hip: one launch, not differentiable), and the flip test's heat-map side
 (`flip_perm`, `flip_back`, `flip_merge`, csrc/flip.hip: flip back, swap left / right joints, average, decode - one launch), and the
 evaluation report of a whole set (`PCKMeter`, `PCK_THRESHOLDS`, `JOINT_GROUPS`, `group_accuracy`, csrc/pck_curve.hip: a PCK curve, its
-AUC, the end-point error and the reference's joint groups from integer counts kept on the device).
+AUC, the end-point error and the reference's joint groups from integer counts kept on the device)), and the geometry of top-down inference
+(`boxes_from_keypoints`, `boxes_from_center_scale`, `to_crop_coords`, `to_image_coords`, csrc/box_crop.hip: the reference's boxes and
+get_transform, and the way back from heat-map pixels to image pixels on the device).
 
 The reference takes numpy arrays (it is called on `.cpu().numpy()` copies, train_human.py:289,443).  The same calls work
 here; torch CUDA tensors are accepted as well and avoid the 2 x 8.4 MB device->host copy per iteration: decode and PCK
@@ -171,16 +173,20 @@ def _dev_f32c(a, like):
     return a.detach().to(device=like.device, dtype=torch.float32)
 
 
-def _decode_pred(o, decode):
-    """The prediction's coordinates under `decode`: "argmax", "soft" (soft_argmax(beta=10, window=5)), "quarter" (quarter_decode), "dark"
-    (dark_decode(kernel=11)) or a callable hm -> (coords, maxvals).  The soft decodes get the reference's `maxval > 0` zeroing, so every
-    decode agrees on which joints are absent ("quarter" and "dark" zero them in their own launch)."""
+def _decode_pred_max(o, decode):
+    """The prediction's coordinates and maxima under `decode`: "argmax", "soft" (soft_argmax(beta=10, window=5)), "quarter" (quarter_decode),
+    "dark" (dark_decode(kernel=11)) or a callable hm -> (coords, maxvals).  The soft decodes get the reference's `maxval > 0` zeroing, so
+    every decode agrees on which joints are absent ("quarter" and "dark" zero them in their own launch).  -> (coords [B,K,2], maxvals [B,K])"""
+    B, K = o.shape[:2]
     if decode == "argmax":
-        return _decode(o)[0]
+        coords, maxv = _decode(o)
+        return coords, maxv.reshape(B, K)
     if decode == "quarter":
-        return _refine(o, 0)[0]
+        coords, maxv = _refine(o, 0)
+        return coords, maxv.reshape(B, K)
     if decode == "dark":
-        return _refine(o, 1, *_dark_args(11, None, *o.shape[2:]))[0]
+        coords, maxv = _refine(o, 1, *_dark_args(11, None, *o.shape[2:]))
+        return coords, maxv.reshape(B, K)
     if decode == "soft":
         coords, maxv = _SoftArgmaxFn.apply(o, 10.0, 5)
     elif callable(decode):
@@ -188,8 +194,13 @@ def _decode_pred(o, decode):
         coords, maxv = _dev_f32c(coords, o), _dev_f32c(maxv, o)
     else:
         raise ValueError(f"decode must be 'argmax', 'soft', 'quarter', 'dark' or a callable, got {decode!r}")
-    B, K = o.shape[:2]
-    return (coords.detach().reshape(B, K, 2) * (maxv.detach().reshape(B, K, 1) > 0).to(torch.float32)).contiguous()
+    maxv = maxv.detach().reshape(B, K)
+    return (coords.detach().reshape(B, K, 2) * (maxv.unsqueeze(-1) > 0).to(torch.float32)).contiguous(), maxv
+
+
+def _decode_pred(o, decode):
+    """`_decode_pred_max`'s coordinates."""
+    return _decode_pred_max(o, decode)[0]
 
 
 def accuracy_device(output, target, thr=0.5, decode="argmax"):
@@ -510,3 +521,154 @@ class PCKMeter:
                 rep["groups"][name] = {"pck": pck[ix].sum(0) / len(ix), "auc": float(rep["auc_per_joint"][ix].sum() / len(ix)) if T > 1 else None,
                                        "epe": float(epe[ix].sum() / len(ix))}
         return rep
+
+
+# ---------------------------------------------------------------------------------------------------------------- top-down inference: boxes
+# A box is (cx, cy, bw, bh, rot_deg) in pixels of its frame, where pixel i covers [i, i + 1); its crop of Ho x Wo pixels is what
+# data_gpu.box_crop / udapose_box_crop samples.  Conventions, the reference's own: a heat-map index i stands for input
+# coordinate i * stride (generate_target, lib/datasets/util.py:39); crop and resize move key points by (kp - left) * S / w
+# (lib/transforms/keypoint_detection.py:47-64); rot has the sign of get_transform's (lib/datasets/util.py:289-316).
+def _hw(size):
+    """An int S or (H, W) as (H, W) ints >= 1."""
+    h, w = (size, size) if isinstance(size, (int, np.integer)) else size
+    if int(h) != h or int(w) != w or h < 1 or w < 1:
+        raise ValueError(f"a size is a positive int or (height, width), got {size!r}")
+    return int(h), int(w)
+
+
+def check_boxes(boxes):
+    """Host boxes as a float64 array [M,5], checked as the device checks them: ValueError naming the first row that has a non-finite
+    field or a side that is not positive (as fp32, the device's type)."""
+    b = np.asarray(boxes, dtype=np.float64)
+    if b.ndim != 2 or b.shape[1] != 5 or b.shape[0] < 1:
+        raise ValueError(f"boxes must be [M,5] = (cx, cy, bw, bh, rot_deg) with M >= 1, got shape {b.shape}")
+    with np.errstate(over="ignore"):
+        b32 = b.astype(np.float32)
+    for m in range(b.shape[0]):
+        if not np.isfinite(b32[m]).all():
+            raise ValueError(f"box {m} has a non-finite field: {b[m].tolist()}")
+        if not (b32[m, 2] > 0 and b32[m, 3] > 0):
+            raise ValueError(f"box {m} has a side that is not positive: bw = {b[m, 2]}, bh = {b[m, 3]}")
+    return b
+
+
+def box_rotation(rot_deg):
+    """(cos, sin) of an array of angles in degrees, float64; exact for multiples of 90, as the device takes them from a table."""
+    rot = np.asarray(rot_deg, dtype=np.float64)
+    c, s = np.cos(np.deg2rad(rot)), np.sin(np.deg2rad(rot))
+    r = np.mod(rot, 360.0)
+    for deg, (ce, se) in ((0.0, (1.0, 0.0)), (90.0, (0.0, 1.0)), (180.0, (-1.0, 0.0)), (270.0, (0.0, -1.0))):
+        c, s = np.where(r == deg, ce, c), np.where(r == deg, se, s)
+    return c, s
+
+
+def to_crop_coords(kp_img, boxes, size):
+    """Key points [M,K,2] (x, y) in pixels of the frame -> in pixels of box m's crop of `size` = S or (Ho, Wo), on the host in float64:
+    R(rot)^T (kp - (cx, cy)) / (sx, sy) + (Wo / 2, Ho / 2) with sx = bw / Wo, sy = bh / Ho.  For a square box bw = bh = 200 s this is
+    the reference's get_transform(c, s, res, rot) @ [x, y, 1] (without transform()'s -1, +1 and int()); for an upright box it is crop +
+    resize's (kp - left) * S / w.  Divide by the stride for heat-map pixels."""
+    Ho, Wo = _hw(size)
+    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 5)
+    kp = np.asarray(kp_img, dtype=np.float64)
+    if kp.ndim != 3 or kp.shape[2] != 2 or kp.shape[0] != b.shape[0]:
+        raise ValueError(f"key points must be [M,K,2] for {b.shape[0]} boxes, got {kp.shape}")
+    c, s = (a[:, None] for a in box_rotation(b[:, 4]))
+    dx, dy = kp[..., 0] - b[:, None, 0], kp[..., 1] - b[:, None, 1]
+    x = (c * dx + s * dy) / (b[:, None, 2] / Wo) + Wo / 2
+    y = (-s * dx + c * dy) / (b[:, None, 3] / Ho) + Ho / 2
+    return np.stack([x, y], axis=-1)
+
+
+def _coords_to_image(coords, boxes, Ho, Wo, stride_x, stride_y):
+    """udapose_coords_to_image on fp32 contiguous CUDA tensors: coords [M,K,2], boxes [M,5] -> [M,K,2]."""
+    M, K = coords.shape[:2]
+    out = torch.empty(M, K, 2, dtype=torch.float32, device=coords.device)
+    check(lib().udapose_coords_to_image(_hip.stream(), ptr(coords), ptr(boxes), M, K, float(stride_x), float(stride_y), Ho, Wo, ptr(out)),
+          "coords_to_image")
+    return out
+
+
+def to_image_coords(coords, boxes, input_size, heatmap_size):
+    """The way back, on the device (udapose_coords_to_image): coords [M,K,2] (x, y) in heat-map pixels of the crops (what the decodes
+    return) -> pixels of the frames, (cx, cy) + R(rot) (((x, y) * stride - (Wo / 2, Ho / 2)) * (sx, sy)), stride = input_size /
+    heatmap_size per axis.  The inverse of `to_crop_coords(.) / stride`.  coords and boxes: CUDA tensors or numpy arrays (numpy coords in ->
+    numpy out); host boxes are checked (`check_boxes`), a device tensor is not."""
+    Ho, Wo = _hw(input_size)
+    Hh, Wh = _hw(heatmap_size)
+    is_np = isinstance(coords, np.ndarray)
+    if not is_np and not torch.is_tensor(coords):
+        raise ValueError("coords must be a numpy array or a tensor [M,K,2]")
+    if coords.ndim != 3 or coords.shape[2] != 2 or coords.shape[0] < 1 or coords.shape[1] < 1:
+        raise ValueError(f"coords must be [M,K,2], got {tuple(coords.shape)}")
+    if not torch.is_tensor(boxes):
+        hb = check_boxes(boxes)
+    if tuple(boxes.shape if torch.is_tensor(boxes) else hb.shape) != (coords.shape[0], 5):
+        raise ValueError(f"boxes must be [{coords.shape[0]},5], got {tuple(boxes.shape if torch.is_tensor(boxes) else hb.shape)}")
+    if is_np:
+        if not torch.cuda.is_available():
+            raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
+        c = torch.from_numpy(np.ascontiguousarray(coords, dtype=np.float32)).cuda()
+    else:
+        _hip.require_cuda(coords)
+        c = ha.f32c(coords.detach())
+    if torch.is_tensor(boxes):
+        _hip.require_cuda(boxes)
+        bd = ha.f32c(boxes.detach())
+    else:
+        bd = torch.from_numpy(hb.astype(np.float32)).to(c.device)
+    return _like_input(coords, _coords_to_image(c, bd, Ho, Wo, Wo / Wh, Ho / Hh))
+
+
+def boxes_from_center_scale(c, s, rot=0):
+    """The animal sets' (centre, scale, rotation) crop as boxes [M,5] float64: centre c [M,2] (or [2]), side 200 * s (get_transform's
+    `h = 200 * scale`, lib/datasets/util.py:294), rot in degrees with the reference's sign."""
+    c = np.asarray(c, dtype=np.float64).reshape(-1, 2)
+    s = np.broadcast_to(np.asarray(s, dtype=np.float64).reshape(-1), (c.shape[0],))
+    rot = np.broadcast_to(np.asarray(rot, dtype=np.float64).reshape(-1), (c.shape[0],))
+    return np.stack([c[:, 0], c[:, 1], 200.0 * s, 200.0 * s, rot], axis=1)
+
+
+def boxes_from_keypoints(kp, visible, image_size, style="human"):
+    """Boxes [M,5] float64 (rot 0) round key points [M,K,2] as the reference's datasets make them.  image_size = (height, width) of the
+    frame; visible [M,K] (non-zero = use the joint) or None.
+      "human"   get_bounding_box + scale_box(.., 1.5), pad=False (lib/datasets/util.py:87-123, human36m_mt.py:210-213): the square of
+                side min(round(1.5 max(w, h)), min(width, height)) moved inside the frame; its pixels left .. right are [left, right + 1)
+                here, so cx = left + side / 2.  visible None: every joint counts, as in the reference.
+      "animal"  the +-15 px clip and s = max(w, h) / 200 * 1.25 (real_animal_all_mt.py:219-230): extremes of the joints with a
+                coordinate > 0 (visible None; the reference's own test, per axis), widened by 15 px and clipped to the frame; centre their
+                midpoint, side 1.25 max(w, h) - such boxes leave the frame routinely.
+    ValueError for a sample without a joint to use."""
+    kp = np.asarray(kp, dtype=np.float64)
+    if kp.ndim == 2:
+        kp = kp[None]
+    if kp.ndim != 3 or kp.shape[2] < 2:
+        raise ValueError(f"key points must be [M,K,2], got {kp.shape}")
+    height, width = _hw(image_size)
+    M = kp.shape[0]
+    vis = None if visible is None else np.asarray(visible).reshape(M, -1) != 0
+    if style not in ("human", "animal"):
+        raise ValueError(f"style must be 'human' or 'animal', got {style!r}")
+    out = np.zeros((M, 5), np.float64)
+    for m in range(M):
+        if style == "human":
+            use = np.ones(kp.shape[1], bool) if vis is None else vis[m]
+            xs, ys = kp[m, use, 0], kp[m, use, 1]
+        else:
+            xs = kp[m, kp[m, :, 0] > 0, 0] if vis is None else kp[m, vis[m], 0]
+            ys = kp[m, kp[m, :, 1] > 0, 1] if vis is None else kp[m, vis[m], 1]
+        if xs.size == 0 or ys.size == 0:
+            raise ValueError(f"sample {m} has no joint to build a box from")
+        if style == "human":
+            left, upper, right, lower = float(xs.min()), float(ys.min()), float(xs.max()), float(ys.max())
+            center_x, center_y = (left + right) / 2, (upper + lower) / 2
+            side = min(round(1.5 * max(right - left, lower - upper)), min(width, height))
+            left, upper = round(center_x - side / 2), round(center_y - side / 2)
+            left = min(max(left, 0), width - side)          # (pad=False: moved inside the frame, left edge first as the reference tests it)
+            upper = min(max(upper, 0), height - side)
+            out[m] = (left + side / 2.0, upper + side / 2.0, side, side, 0.0)
+        else:
+            y_min, y_max = max(float(ys.min()) - 15, 0.0), min(float(ys.max()) + 15, float(height))
+            x_min, x_max = max(float(xs.min()) - 15, 0.0), min(float(xs.max()) + 15, float(width))
+            side = 200.0 * (max(x_max - x_min, y_max - y_min) / 200.0 * 1.25)
+            out[m] = ((x_min + x_max) / 2.0, (y_min + y_max) / 2.0, side, side, 0.0)
+    return out
