@@ -573,6 +573,48 @@ int udapose_box_crop(void* stream, const unsigned char* frames_u8, int F, int Hs
  * Wo < 1. */
 int udapose_coords_to_image(void* stream, const float* coords, const float* boxes, int M, int K, float stride_x, float stride_y, int Ho, int Wo,
                             float* out);
+/* Top-down inference, the instance layer: one pose per box -> distinct, scored poses (Simple Baselines' rescoring and greedy OKS-NMS; none in the
+ * reference; csrc/pose_nms.hip).  No atomics, the same bits on every run.  Everywhere: 1 <= M <= UDAPOSE_NMS_MAX_POSES,
+ * 1 <= K <= UDAPOSE_NMS_MAX_KEYPOINTS, else UDAPOSE_ERR_ARG with nothing launched, as for a null required pointer.
+ * kp [M][K][2] fp32 (x, y) in frame pixels (8-byte aligned); conf [M][K]; boxes [M][5] = udapose_box_crop's; status [M] bytes (may be NULL: all
+ * 0); box_score [M] (may be NULL: all 1); vis_thr, oks_thr [1] fp32 and sigmas [K] fp32 in device memory: a captured launch follows new values.
+ * udapose_pose_rescore:
+ *   score[m] = kscore * box_score[m], kscore = (sum of conf[m][k] over k with conf[m][k] > vis_thr, ascending k, fp32) / their count, 0 for none;
+ *   area[m] = bw * bh (the fp32 product); refused[m] = 1 when status[m] != 0, a coordinate of kp[m], area[m] or score[m] is not finite, or
+ *   area[m] <= 0; 0 otherwise.  order [M] int32: the poses by descending score (-0 = +0), equal scores by ascending index; refused poses last,
+ *   by ascending index, whatever their scores.  order[rank] = m with rank = the number of poses ahead of m, counted over keys in LDS.
+ *   All four outputs are required. */
+#define UDAPOSE_NMS_MAX_POSES 4096
+#define UDAPOSE_NMS_MAX_KEYPOINTS 64
+int udapose_pose_rescore(void* stream, const float* kp, const float* conf, const float* boxes, const unsigned char* status, const float* box_score,
+                         const float* vis_thr, int M, int K, float* score, int* order, float* area, unsigned char* refused);
+/* Object-key-point similarity.  v_k = (2 sigmas[k])^2, d2_k = (x_i - x_j)^2 + (y_i - y_j)^2, e_k = d2_k / v_k / A * 0.5f, every step fp32 without
+ * contraction, sums in ascending k.
+ * Self form (kp_b, area_b, visible_b NULL, Mb = Ma): A = (area_i + area_j) * 0.5f + FLT_EPSILON, oks = (sum_k expf(-e_k)) / K; oks(i, j) and
+ *   oks(j, i) are the same bits.  out [Ma][Ma] fp32 (may be NULL).  mask [Ma][ceil(Ma / 64)] 64-bit words (may be NULL; needs oks_thr): bit
+ *   (j & 63) of word (j >> 6) of row i is set when i != j, frame_idx[i] == frame_idx[j] (frame_idx [Ma] int32, may be NULL: one frame),
+ *   neither pose is refused (refused [Ma] bytes, may be NULL: none) and oks(i, j) > oks_thr; the bits past Ma are clear.
+ * Rectangular form (kp_b [Mb][K][2], area_b [Mb] given; mask, frame_idx, refused NULL): predictions a against labelled poses b, COCO's
+ *   convention: A = area_b[j] + FLT_EPSILON, oks = (sum of expf(-e_k) over k with visible_b[j][k] > 0) / their count, 0 for none
+ *   (visible_b [Mb][K] fp32, may be NULL: every joint counts).  out [Ma][Mb] fp32.  area_a is not used and may be NULL.
+ * A non-finite operand gives what the expressions give.  UDAPOSE_ERR_ARG as well when both outputs are NULL. */
+int udapose_oks_matrix(void* stream, const float* kp_a, const float* area_a, int Ma, const float* kp_b, const float* area_b, const float* visible_b,
+                       int Mb, int K, const float* sigmas, const int* frame_idx, const unsigned char* refused, const float* oks_thr, float* out,
+                       unsigned long long* mask);
+/* Greedy NMS over the self form's mask, by one wave: walk order[0 .. M); a pose that is not refused (refused may be NULL: none) and has not been
+ * removed is kept, and removes every pose whose bit is set in its mask row.  (The mask holds same-frame pairs only, so one walk is per-frame
+ * NMS.)  keep [M] bytes 0 / 1; n_keep [1] int32 = their sum; suppressed_by [M] int32 (may be NULL): the kept pose that removed m, -1 for a
+ * kept and for a refused pose.  An entry of order outside [0, M) is passed over. */
+int udapose_pose_nms_sweep(void* stream, const unsigned long long* mask, const int* order, const unsigned char* refused, int M, unsigned char* keep,
+                           int* n_keep, int* suppressed_by);
+/* The three launches behind one entry: rescore, the self form's mask (and the matrix into oks_out [M][M], may be NULL), the walk.  ws: device
+ * memory of udapose_pose_nms_ws_bytes(M) bytes, 8-byte aligned (the mask, the areas, the refused flags; 0 bytes for an M out of range).
+ * score, order, keep, n_keep are required, suppressed_by may be NULL.  Every argument is checked before the first launch: an error leaves
+ * nothing written. */
+long long udapose_pose_nms_ws_bytes(int M);
+int udapose_pose_nms(void* stream, const float* kp, const float* conf, const float* boxes, const int* frame_idx, const unsigned char* status,
+                     const float* box_score, const float* sigmas, const float* vis_thr, const float* oks_thr, int M, int K, void* ws, float* score,
+                     int* order, unsigned char* keep, int* n_keep, int* suppressed_by, float* oks_out);
 /* confidence mask (train_human.py:427-430): thr = k-th smallest of act[n]; mask[i] = (tea_mask[i]*act_local[i]) > thr */
 int udapose_kth_mask(void* stream, const float* act, const float* tea_mask, int n, int k, float* thr_out, unsigned char* mask,
                      const float* act_local, int n_local);

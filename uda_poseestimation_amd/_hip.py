@@ -156,6 +156,11 @@ _SIGS = {
     "udapose_refine_decode": (ci, [vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, vp]),
     "udapose_box_crop": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp]),
     "udapose_coords_to_image": (ci, [vp, vp, vp, ci, ci, cf, cf, ci, ci, vp]),
+    "udapose_pose_rescore": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]),
+    "udapose_oks_matrix": (ci, [vp, vp, vp, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp]),
+    "udapose_pose_nms_sweep": (ci, [vp, vp, vp, vp, ci, vp, vp, vp]),
+    "udapose_pose_nms_ws_bytes": (ll, [ci]),
+    "udapose_pose_nms": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
     "udapose_kth_mask": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, ci]),
     "udapose_kth_mask_dev": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, ci]),      # (k: an int32 in device memory)
     "udapose_topk_select": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),

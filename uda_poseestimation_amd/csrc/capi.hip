@@ -455,6 +455,26 @@ int udapose_coords_to_image(void* stream, const float* coords, const float* boxe
                             float* out) {
     return box_coords_to_image(S(stream), coords, boxes, M, K, stride_x, stride_y, Ho, Wo, out);
 }
+int udapose_pose_rescore(void* stream, const float* kp, const float* conf, const float* boxes, const unsigned char* status, const float* box_score,
+                         const float* vis_thr, int M, int K, float* score, int* order, float* area, unsigned char* refused) {
+    return pose_rescore(S(stream), kp, conf, boxes, status, box_score, vis_thr, M, K, score, order, area, refused);
+}
+int udapose_oks_matrix(void* stream, const float* kp_a, const float* area_a, int Ma, const float* kp_b, const float* area_b, const float* visible_b,
+                       int Mb, int K, const float* sigmas, const int* frame_idx, const unsigned char* refused, const float* oks_thr, float* out,
+                       unsigned long long* mask) {
+    return oks_matrix(S(stream), kp_a, area_a, Ma, kp_b, area_b, visible_b, Mb, K, sigmas, frame_idx, refused, oks_thr, out, mask);
+}
+int udapose_pose_nms_sweep(void* stream, const unsigned long long* mask, const int* order, const unsigned char* refused, int M, unsigned char* keep,
+                           int* n_keep, int* suppressed_by) {
+    return pose_nms_sweep(S(stream), mask, order, refused, M, keep, n_keep, suppressed_by);
+}
+long long udapose_pose_nms_ws_bytes(int M) { return (long long)pose_nms_ws_bytes(M); }
+int udapose_pose_nms(void* stream, const float* kp, const float* conf, const float* boxes, const int* frame_idx, const unsigned char* status,
+                     const float* box_score, const float* sigmas, const float* vis_thr, const float* oks_thr, int M, int K, void* ws, float* score,
+                     int* order, unsigned char* keep, int* n_keep, int* suppressed_by, float* oks_out) {
+    return pose_nms(S(stream), kp, conf, boxes, frame_idx, status, box_score, sigmas, vis_thr, oks_thr, M, K, ws, score, order, keep, n_keep,
+                    suppressed_by, oks_out);
+}
 int udapose_refine_decode(void* stream, const float* hm, int R, int H, int W, int mode, int kernel, float sigma, float* coords, float* maxvals,
                           int* flat_idx) {
     return refine_decode(S(stream), hm, R, H, W, mode, kernel, sigma, coords, maxvals, flat_idx);

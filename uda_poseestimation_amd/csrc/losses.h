@@ -67,3 +67,15 @@ int flip_merge(hipStream_t s, const float* a, const float* f, const int* perm, i
                float* maxv, int* idx, float* preds);
 // refine.hip
 int refine_decode(hipStream_t s, const float* hm, int R, int H, int W, int mode, int kernel, float sigma, float* coords, float* maxv, int* idx);
+// pose_nms.hip
+int pose_rescore(hipStream_t s, const float* kp, const float* conf, const float* boxes, const unsigned char* status, const float* box_score,
+                 const float* vis_thr, int M, int K, float* score, int* order, float* area, unsigned char* refused);
+int oks_matrix(hipStream_t s, const float* kp_a, const float* area_a, int Ma, const float* kp_b, const float* area_b, const float* visible_b, int Mb,
+               int K, const float* sigmas, const int* frame_idx, const unsigned char* refused, const float* oks_thr, float* out,
+               unsigned long long* mask);
+int pose_nms_sweep(hipStream_t s, const unsigned long long* mask, const int* order, const unsigned char* refused, int M, unsigned char* keep,
+                   int* n_keep, int* suppressed_by);
+size_t pose_nms_ws_bytes(int M);
+int pose_nms(hipStream_t s, const float* kp, const float* conf, const float* boxes, const int* frame_idx, const unsigned char* status,
+             const float* box_score, const float* sigmas, const float* vis_thr, const float* oks_thr, int M, int K, void* ws, float* score, int* order,
+             unsigned char* keep, int* n_keep, int* suppressed_by, float* oks_out);

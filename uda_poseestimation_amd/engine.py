@@ -1032,7 +1032,7 @@ def evaluate(batches, model, thresholds=kd.PCK_THRESHOLDS, groups=None, criterio
 
 
 def predict(frames_u8, boxes, model, frame_idx=None, flip_pairs=None, shift_heatmap=False, decode="argmax", batch=32, input_size=None,
-            mean=data_gpu.IMAGENET_MEAN, std=data_gpu.IMAGENET_STD, return_heatmaps=False):
+            mean=data_gpu.IMAGENET_MEAN, std=data_gpu.IMAGENET_STD, return_heatmaps=False, box_scores=None, nms=None):
     """Top-down inference on the device: pictures and boxes in, key points in the pictures' own pixels out.
     frames_u8 [F,Hs,Ws,3] uint8 CUDA; boxes [M,5] = (cx, cy, bw, bh, rot_deg) in pixels of their frames (lib.keypoint_detection.
     boxes_from_keypoints / boxes_from_center_scale make them) - a numpy array or a list, checked on the host (ValueError naming a bad
@@ -1048,7 +1048,20 @@ def predict(frames_u8, boxes, model, frame_idx=None, flip_pairs=None, shift_heat
     1 = the box was refused (its key points mean nothing), "heatmaps": [M,K,Hh,Wh] with return_heatmaps}, all on the device.  Eval mode
     under no_grad, the model's mode restored.  Nothing is read back and, with device boxes, nothing is uploaded: a call can be captured
     into a graph, and a replay follows new values in the same boxes tensor.  Outside a capture the call ends with validate()'s
-    saturation check of the f16x2 evaluation forward (the one host synchronisation, after the last launch)."""
+    saturation check of the f16x2 evaluation forward (the one host synchronisation, after the last launch).
+    nms: None - one pose per box, as above, and exactly those launches; True or a dict of lib.keypoint_detection.oks_nms's
+    keyword arguments (sigmas, oks_thr, vis_thr, want_matrix) - the poses are rescored (box_scores [M]: the detector's scores, a CUDA
+    tensor or host numbers; None: 1) and thinned per frame by greedy OKS-NMS on the device, with the boxes' areas, frame_idx and status: the
+    dict gains "score" [M], "keep" [M] uint8, "order" [M] int32, "n_keep" [1] int32 and "suppressed_by" [M] (and "oks" with
+    want_matrix).  Shapes stay [M], nothing is compacted or read back, so a capture stays valid; at most 4096 boxes a call with nms."""
+    nms_args = None
+    if nms is not None and nms is not False:
+        nms_args = {} if nms is True else dict(nms)
+        bad = sorted(set(nms_args) - {"sigmas", "oks_thr", "vis_thr", "want_matrix"})
+        if bad:
+            raise ValueError(f"nms: {bad} are not oks_nms arguments predict() passes on (sigmas, oks_thr, vis_thr, want_matrix)")
+    elif box_scores is not None:
+        raise ValueError("box_scores are used by the rescoring of nms: give nms=True or a dict")
     Ho, Wo = data_gpu._crop_size(256 if input_size is None else input_size)
     batch = int(batch)
     if batch < 1:
@@ -1061,6 +1074,11 @@ def predict(frames_u8, boxes, model, frame_idx=None, flip_pairs=None, shift_heat
     fused = perm is not None and isinstance(decode, str) and decode == "argmax"
     md, sd = data_gpu._norm_consts(dev, mean, std)
     M = bd.shape[0]
+    if nms_args is not None:
+        if M > kd.NMS_MAX_POSES:
+            raise ValueError(f"nms takes at most {kd.NMS_MAX_POSES} boxes a call, got {M}")
+        if box_scores is not None and not torch.is_tensor(box_scores):
+            box_scores = torch.from_numpy(np.ascontiguousarray(box_scores, dtype=np.float32)).to(dev, non_blocking=True)
     keypoints = torch.empty(M, K, 2, dtype=torch.float32, device=dev)
     confidence = torch.empty(M, K, dtype=torch.float32, device=dev)
     status = torch.empty(M, dtype=torch.uint8, device=dev)
@@ -1100,6 +1118,9 @@ def predict(frames_u8, boxes, model, frame_idx=None, flip_pairs=None, shift_heat
     out = {"keypoints": keypoints, "confidence": confidence, "status": status}
     if return_heatmaps:
         out["heatmaps"] = heatmaps
+    if nms_args is not None:
+        res = kd.oks_nms(keypoints, confidence, bd, frame_idx=fd, status=status, box_scores=box_scores, **nms_args)
+        out.update({k: res[k] for k in ("score", "keep", "order", "n_keep", "suppressed_by", "oks") if k in res})
     if not torch.cuda.is_current_stream_capturing():
         sat = mt.split_saturations(reset=True)          # (as validate(): the evaluation forward runs the f16x2 mode under 'auto')
         if sat:

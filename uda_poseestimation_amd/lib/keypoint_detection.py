@@ -5,7 +5,9 @@ decodes (`quarter_decode`, `dark_decode`, csrc/refine.hip: one launch, not diffe
 evaluation report of a whole set (`PCKMeter`, `PCK_THRESHOLDS`, `JOINT_GROUPS`, `group_accuracy`, csrc/pck_curve.hip: a PCK curve, its
 AUC, the end-point error and the reference's joint groups from integer counts kept on the device)), and the geometry of top-down inference
 (`boxes_from_keypoints`, `boxes_from_center_scale`, `to_crop_coords`, `to_image_coords`, csrc/box_crop.hip: the reference's boxes and
-get_transform, and the way back from heat-map pixels to image pixels on the device).
+get_transform, and the way back from heat-map pixels to image pixels on the device), and the instance layer behind `engine.predict`
+(`rescore`, `oks_matrix`, `oks_nms`, `OKS_SIGMAS`, csrc/pose_nms.hip: Simple Baselines' pose rescoring and greedy NMS under object-key-point
+similarity, on the device).
 
 The reference takes numpy arrays (it is called on `.cpu().numpy()` copies, train_human.py:289,443).  The same calls work
 here; torch CUDA tensors are accepted as well and avoid the 2 x 8.4 MB device->host copy per iteration: decode and PCK
@@ -671,4 +673,181 @@ def boxes_from_keypoints(kp, visible, image_size, style="human"):
             x_min, x_max = max(float(xs.min()) - 15, 0.0), min(float(xs.max()) + 15, float(width))
             side = 200.0 * (max(x_max - x_min, y_max - y_min) / 200.0 * 1.25)
             out[m] = ((x_min + x_max) / 2.0, (y_min + y_max) / 2.0, side, side, 0.0)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- top-down inference: instances
+# One pose per box -> distinct, scored poses (csrc/pose_nms.hip): Simple Baselines' rescoring and greedy NMS under
+# object-key-point similarity.  The reference has neither.  Everything stays on the device: shapes are [M], nothing is compacted.
+NMS_MAX_POSES = 4096          # UDAPOSE_NMS_MAX_POSES (include/udapose.h): 64 mask words, one per lane of the walking wave
+NMS_MAX_KEYPOINTS = 64        # UDAPOSE_NMS_MAX_KEYPOINTS
+# COCO's per-joint constants (cocoapi, PythonAPI/pycocotools/cocoeval.py, `kpt_oks_sigmas`), in COCO's joint order
+OKS_SIGMAS = {"coco17": (.026, .025, .025, .035, .035, .079, .079, .072, .072, .062, .062, .107, .107, .087, .087, .089, .089)}
+OKS_UNIFORM_SIGMA = 0.0669    # the mean of COCO's seventeen (1.138 / 17), for skeletons without a published table
+_SIGMA_CACHE = {}             # (table, device) -> its device copy
+_NMS_THR = {}                 # (name, device) -> [device scalar, the host value it holds]
+
+
+def oks_sigmas(K):
+    """The table for a skeleton of K joints: COCO's for K = 17, else K times OKS_UNIFORM_SIGMA."""
+    if int(K) != K or not 1 <= K <= NMS_MAX_KEYPOINTS:
+        raise ValueError(f"K must be in [1, {NMS_MAX_KEYPOINTS}], got {K!r}")
+    return OKS_SIGMAS["coco17"] if K == 17 else (OKS_UNIFORM_SIGMA,) * int(K)
+
+
+def _device_key(device):
+    """torch.device(device) with the index spelled out ("cuda" and "cuda:0" name one device: one cache slot)."""
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def _sigmas_device(sigmas, K, device):
+    """sigmas: None (oks_sigmas(K)), a key of OKS_SIGMAS, K positive numbers, or a CUDA tensor [K] (taken as it is) -> fp32 [K] on the device."""
+    if torch.is_tensor(sigmas):
+        _hip.require_cuda(sigmas)
+        if tuple(sigmas.shape) != (K,):
+            raise ValueError(f"sigmas must be [{K}], got {tuple(sigmas.shape)}")
+        return ha.f32c(sigmas)
+    if sigmas is None:
+        sigmas = oks_sigmas(K)
+    elif isinstance(sigmas, str):
+        if sigmas not in OKS_SIGMAS:
+            raise ValueError(f"sigmas {sigmas!r}: the tables are {tuple(OKS_SIGMAS)}")
+        sigmas = OKS_SIGMAS[sigmas]
+    table = tuple(float(v) for v in sigmas)
+    if len(table) != K or not all(np.isfinite(v) and v > 0 for v in table):
+        raise ValueError(f"sigmas must be {K} positive numbers, got {table}")
+    key = (table, _device_key(device))
+    if key not in _SIGMA_CACHE:
+        _SIGMA_CACHE[key] = torch.tensor(table, dtype=torch.float32, device=key[1])
+    return _SIGMA_CACHE[key]
+
+
+def nms_threshold(name, value, device):
+    """The device scalar that holds threshold `name` ("oks_thr" or "vis_thr") on `device`, uploaded when the host value changed (a
+    stream-ordered 4-byte copy, the pattern of MeanTeacherTrainer.sync_view_radius); never inside a capture, whose launches read the scalar.
+    There is one scalar per name and device: a captured rescore / oks_nms / predict(nms=) follows a later `nms_threshold(name, new, device)`,
+    and follows as well any later eager call that gives another value.  A CUDA tensor of one element is taken as it is (a scalar of the
+    caller's own, which nothing here writes).  The first call for a device creates the scalar (an upload): make it, or one eager call
+    of the function to capture, ahead of the capture."""
+    if name not in ("oks_thr", "vis_thr"):
+        raise ValueError(f"the thresholds are 'oks_thr' and 'vis_thr', got {name!r}")
+    if torch.is_tensor(value):
+        _hip.require_cuda(value)
+        if value.numel() != 1 or value.dtype != torch.float32:
+            raise ValueError(f"{name} as a tensor must be one fp32 element, got {value.dtype} {tuple(value.shape)}")
+        return value
+    v = float(value)
+    if not np.isfinite(v):
+        raise ValueError(f"{name} must be finite, got {value!r}")
+    key = (name, _device_key(device))
+    slot = _NMS_THR.get(key)
+    if slot is None:
+        _NMS_THR[key] = slot = [torch.tensor(v, dtype=torch.float32, device=key[1]), v]
+    elif v != slot[1] and not torch.cuda.is_current_stream_capturing():
+        slot[0].copy_(torch.tensor(v, dtype=torch.float32), non_blocking=True)
+        slot[1] = v
+    return slot[0]
+
+
+def _pose_tensor(t, shape, what, dtype=torch.float32):
+    """A CUDA tensor of `shape` (None entries are free) as contiguous `dtype` (itself where it already is: a capture follows it)."""
+    if not torch.is_tensor(t):
+        raise ValueError(f"{what} must be a CUDA tensor, got {type(t).__name__}")
+    _hip.require_cuda(t)
+    if t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
+        raise ValueError(f"{what} must be {list(shape)}, got {tuple(t.shape)}")
+    return t.detach().to(dtype).contiguous()
+
+
+def _check_mk(M, K):
+    if not 1 <= M <= NMS_MAX_POSES:
+        raise ValueError(f"1 to {NMS_MAX_POSES} poses a call, got {M}")
+    if not 1 <= K <= NMS_MAX_KEYPOINTS:
+        raise ValueError(f"1 to {NMS_MAX_KEYPOINTS} key points, got {K}")
+
+
+def rescore(confidence, box_scores=None, vis_thr=0.2):
+    """Simple Baselines' pose score on the device (udapose_pose_rescore): confidence [M,K] CUDA -> score [M] fp32 = the mean of the
+    confidences above vis_thr (added in ascending k; 0 when there is none) times box_scores[m] (None: 1)."""
+    c = _pose_tensor(confidence, (None, None), "confidence")
+    M, K = c.shape
+    _check_mk(M, K)
+    dev = c.device
+    bs = None if box_scores is None else _pose_tensor(box_scores, (M,), "box_scores")
+    kp = torch.zeros(M, K, 2, dtype=torch.float32, device=dev)
+    boxes = torch.ones(M, 5, dtype=torch.float32, device=dev)
+    score, area = torch.empty(M, dtype=torch.float32, device=dev), torch.empty(M, dtype=torch.float32, device=dev)
+    order, refused = torch.empty(M, dtype=torch.int32, device=dev), torch.empty(M, dtype=torch.uint8, device=dev)
+    check(lib().udapose_pose_rescore(_hip.stream(), ptr(kp), ptr(c), ptr(boxes), None, ptr(bs), ptr(nms_threshold("vis_thr", vis_thr, dev)), M, K,
+                                     ptr(score), ptr(order), ptr(area), ptr(refused)), "pose_rescore")
+    return score
+
+
+def oks_matrix(kp_a, area_a, kp_b=None, area_b=None, visible_b=None, sigmas=None):
+    """Object-key-point similarity on the device (udapose_oks_matrix), fp32.  kp_a [Ma,K,2] (x, y), area_a [Ma]; sigmas as oks_nms takes them.
+    Self form (kp_b None): [Ma,Ma], oks(i, j) = mean_k exp(-d2_k / (2 sigma_k)^2 / ((area_i + area_j) / 2 + eps) / 2), bit-symmetric.
+    Rectangular form, predictions against labelled poses kp_b [Mb,K,2], area_b [Mb], visible_b [Mb,K] (None: every joint): [Ma,Mb] with
+    COCO's convention - the label's area, the mean over the label's visible joints, 0 for a label without one."""
+    a = _pose_tensor(kp_a, (None, None, 2), "kp_a")
+    Ma, K = a.shape[:2]
+    _check_mk(Ma, K)
+    dev = a.device
+    sg = _sigmas_device(sigmas, K, dev)
+    if kp_b is None:
+        if area_b is not None or visible_b is not None:
+            raise ValueError("area_b and visible_b belong to the rectangular form: give kp_b")
+        ar = _pose_tensor(area_a, (Ma,), "area_a")
+        out = torch.empty(Ma, Ma, dtype=torch.float32, device=dev)
+        check(lib().udapose_oks_matrix(_hip.stream(), ptr(a), ptr(ar), Ma, None, None, None, Ma, K, ptr(sg), None, None, None, ptr(out), None),
+              "oks_matrix")
+        return out
+    b = _pose_tensor(kp_b, (None, K, 2), "kp_b")
+    Mb = b.shape[0]
+    _check_mk(Mb, K)
+    if area_b is None:
+        raise ValueError("the rectangular form needs area_b, the labelled poses' areas")
+    arb = _pose_tensor(area_b, (Mb,), "area_b")
+    vis = None if visible_b is None else _pose_tensor(visible_b, (Mb, K), "visible_b")
+    out = torch.empty(Ma, Mb, dtype=torch.float32, device=dev)
+    check(lib().udapose_oks_matrix(_hip.stream(), ptr(a), None, Ma, ptr(b), ptr(arb), ptr(vis), Mb, K, ptr(sg), None, None, None, ptr(out), None),
+          "oks_matrix")
+    return out
+
+
+def oks_nms(keypoints, confidence, boxes, frame_idx=None, status=None, box_scores=None, sigmas=None, oks_thr=0.9, vis_thr=0.2,
+            want_matrix=False):
+    """Rescoring and greedy OKS-NMS on the device (udapose_pose_nms: three launches, nothing read back, capturable).  CUDA tensors:
+    keypoints [M,K,2] (x, y) in frame pixels, confidence [M,K], boxes [M,5] (area = bw * bh) - engine.predict's outputs and boxes;
+    frame_idx [M] integers (None: all poses on one frame), status [M] uint8 (non-zero: refused; None: none), box_scores [M] (None: 1).
+    sigmas: None (COCO's table for K = 17, else uniform OKS_UNIFORM_SIGMA), a key of OKS_SIGMAS, K numbers or a CUDA tensor [K].
+    oks_thr, vis_thr: floats, kept in the device scalars of `nms_threshold` (or one-element CUDA tensors of the caller's).
+    A pose is refused when its status is non-zero, a coordinate, its area or its score is not finite, or its area is <= 0: it is never
+    kept and removes nothing.  The walk: descending score, equal scores by ascending index; a pose not yet removed is kept and removes
+    every later pose of its own frame with oks > oks_thr.
+    Returns {"score" [M] fp32, "order" [M] int32 (refused poses last), "keep" [M] uint8, "n_keep" [1] int32, "suppressed_by" [M] int32 (the
+    kept pose that removed m; -1 for kept and refused poses), "oks" [M,M] fp32 with want_matrix}."""
+    kp = _pose_tensor(keypoints, (None, None, 2), "keypoints")
+    M, K = kp.shape[:2]
+    _check_mk(M, K)
+    dev = kp.device
+    conf = _pose_tensor(confidence, (M, K), "confidence")
+    bx = _pose_tensor(boxes, (M, 5), "boxes")
+    fi = None if frame_idx is None else _pose_tensor(frame_idx, (M,), "frame_idx", torch.int32)
+    st = None if status is None else _pose_tensor(status, (M,), "status", torch.uint8)
+    bs = None if box_scores is None else _pose_tensor(box_scores, (M,), "box_scores")
+    sg = _sigmas_device(sigmas, K, dev)
+    othr, vthr = nms_threshold("oks_thr", oks_thr, dev), nms_threshold("vis_thr", vis_thr, dev)
+    L = lib()
+    ws = torch.empty(L.udapose_pose_nms_ws_bytes(M) // 8 + 1, dtype=torch.int64, device=dev)
+    out = {"score": torch.empty(M, dtype=torch.float32, device=dev), "order": torch.empty(M, dtype=torch.int32, device=dev),
+           "keep": torch.empty(M, dtype=torch.uint8, device=dev), "n_keep": torch.empty(1, dtype=torch.int32, device=dev),
+           "suppressed_by": torch.empty(M, dtype=torch.int32, device=dev)}
+    if want_matrix:
+        out["oks"] = torch.empty(M, M, dtype=torch.float32, device=dev)
+    check(L.udapose_pose_nms(_hip.stream(), ptr(kp), ptr(conf), ptr(bx), ptr(fi), ptr(st), ptr(bs), ptr(sg), ptr(vthr), ptr(othr), M, K, ptr(ws),
+                             ptr(out["score"]), ptr(out["order"]), ptr(out["keep"]), ptr(out["n_keep"]), ptr(out["suppressed_by"]),
+                             ptr(out.get("oks"))), "pose_nms")
     return out
