@@ -615,6 +615,51 @@ long long udapose_pose_nms_ws_bytes(int M);
 int udapose_pose_nms(void* stream, const float* kp, const float* conf, const float* boxes, const int* frame_idx, const unsigned char* status,
                      const float* box_score, const float* sigmas, const float* vis_thr, const float* oks_thr, int M, int K, void* ws, float* score,
                      int* order, unsigned char* keep, int* n_keep, int* suppressed_by, float* oks_out);
+/* Key-point AP under OKS, COCO-style (cocoapi's evaluateImg + accumulate for key points; csrc/pose_ap.hip).  Detections
+ * against labelled poses per frame -> records on the device -> precision / recall tables.  Integer atomics on the int64 counters only, no
+ * floating-point atomics, nothing read back: every launch can be captured, and a replay appends again.
+ * udapose_ap_match, one update.  Detections: kp [M][K][2] fp32 (8-byte aligned), score [M], frame_idx [M] int32, valid [M] bytes (may be
+ *   NULL: all valid), area [M] (may be NULL: (max_k x - min_k x) * (max_k y - min_k y) in fp32).  Labels: gt_kp [G][K][2], gt_visible [G][K]
+ *   fp32, > 0 counts (may be NULL: every joint), gt_area [G], gt_frame [G] int32, gt_ignore [G] bytes (may be NULL: none).  Frame ids are in
+ *   [0, F).  sigmas [K], thresholds [T] (strictly ascending, the CALLER's duty) and ranges [A][2] = (lo, hi) are fp32 in device memory.
+ *   Refused (counted, never in a curve): valid == 0, a score, coordinate or given area that is not finite, a frame outside [0, F).  A label on
+ *   a frame outside [0, F) is dropped and counted.  Per frame the non-refused detections in descending score (-0 = +0), equal scores by
+ *   ascending index; the first max_dets take part, the rest count in `cut`; a frame with more than UDAPOSE_AP_MAX_LABELS_PER_FRAME labels is
+ *   left out whole (its labels and detections count nowhere but in `overflow_frames`).  oks(d, g): the bits of udapose_oks_matrix's
+ *   rectangular form.  Per (t, a): label g is ignored when gt_ignore[g] != 0, it has no visible joint, gt_area[g] < lo or > hi; a detection
+ *   starts with best = thresholds[t] and takes, over the not yet matched labels, counted ones first by ascending index and ignored ones only
+ *   when no counted one was taken, every label whose oks is not < best (best = oks; among equal values the later label); matched, it takes
+ *   its label's ignore flag; unmatched, it is ignored when its area is < lo or > hi.
+ *   A record per detection that took part: rec_score, and bit a * T + t of rec_matched / rec_ignored.  Records are appended at
+ *   counters[0] in ascending frame id, then in-frame order; those at or beyond `capacity` are dropped and counted.
+ *   counters: int64 [UDAPOSE_AP_COUNTERS + A] = records, dropped, refused, cut, overflow_frames, bad_labels, then npig[a] (the counted labels
+ *   of range a over all counted frames); the caller zeroes them once, a call adds.
+ *   ws: udapose_ap_match_ws_bytes(M, G, F) bytes, 8-byte aligned (0 for sizes out of range).
+ *   UDAPOSE_ERR_ARG, every check ahead of the first launch and nothing written: a null required pointer, M, G outside
+ *   [1, UDAPOSE_NMS_MAX_POSES], F outside [1, UDAPOSE_AP_MAX_FRAMES], K outside [1, UDAPOSE_NMS_MAX_KEYPOINTS], T or A < 1 or
+ *   T * A > UDAPOSE_AP_MAX_COMBOS, max_dets outside [1, UDAPOSE_AP_MAX_DETS], capacity outside [1, UDAPOSE_AP_MAX_CAPACITY].
+ * udapose_ap_curve, the tables of the N = counters[0] records: sorted by descending score, equal scores by sequence number (stable); per
+ *   (t, a) in fp64: tp = cumsum(matched & ~ignored), fp = cumsum(~matched & ~ignored), rc = tp / npig[a], pr = tp / (fp + tp + DBL_EPSILON),
+ *   pr[i] = max(pr[i:]); per recall point r the first index q with rc[q] >= recall_points[r]: precision [T][R][A] fp64 = pr[q],
+ *   scores [T][R][A] fp32 = the score of record q, both 0 without such an index; recall [T][A] fp64 = rc[N - 1], 0 for N = 0.  Where
+ *   npig[a] == 0 all three are -1.  recall_points [R] fp64 in device memory, R <= UDAPOSE_AP_MAX_RECALL_POINTS.
+ *   ws: udapose_ap_curve_ws_bytes(capacity, T, A) bytes, 8-byte aligned.  The records are not changed: more updates may follow. */
+#define UDAPOSE_AP_MAX_FRAMES 4096
+#define UDAPOSE_AP_MAX_LABELS_PER_FRAME 64
+#define UDAPOSE_AP_MAX_DETS 64
+#define UDAPOSE_AP_MAX_COMBOS 64
+#define UDAPOSE_AP_MAX_RECALL_POINTS 128
+#define UDAPOSE_AP_MAX_CAPACITY 262144
+#define UDAPOSE_AP_COUNTERS 6
+long long udapose_ap_match_ws_bytes(int M, int G, int F);
+int udapose_ap_match(void* stream, const float* kp, const float* score, const int* frame_idx, const unsigned char* valid, const float* area, int M,
+                     const float* gt_kp, const float* gt_visible, const float* gt_area, const int* gt_frame, const unsigned char* gt_ignore, int G,
+                     int K, int F, const float* sigmas, const float* thresholds, int T, const float* ranges, int A, int max_dets, void* ws,
+                     float* rec_score, unsigned long long* rec_matched, unsigned long long* rec_ignored, int capacity, long long* counters);
+long long udapose_ap_curve_ws_bytes(int capacity, int T, int A);
+int udapose_ap_curve(void* stream, const float* rec_score, const unsigned long long* rec_matched, const unsigned long long* rec_ignored,
+                     int capacity, const long long* counters, int T, int A, const double* recall_points, int R, void* ws, double* precision,
+                     float* scores, double* recall);
 /* confidence mask (train_human.py:427-430): thr = k-th smallest of act[n]; mask[i] = (tea_mask[i]*act_local[i]) > thr */
 int udapose_kth_mask(void* stream, const float* act, const float* tea_mask, int n, int k, float* thr_out, unsigned char* mask,
                      const float* act_local, int n_local);

@@ -161,6 +161,10 @@ _SIGS = {
     "udapose_pose_nms_sweep": (ci, [vp, vp, vp, vp, ci, vp, vp, vp]),
     "udapose_pose_nms_ws_bytes": (ll, [ci]),
     "udapose_pose_nms": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
+    "udapose_ap_match_ws_bytes": (ll, [ci, ci, ci]),
+    "udapose_ap_match": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp, vp, ci, vp]),
+    "udapose_ap_curve_ws_bytes": (ll, [ci, ci, ci]),
+    "udapose_ap_curve": (ci, [vp, vp, vp, vp, ci, vp, ci, ci, vp, ci, vp, vp, vp, vp]),
     "udapose_kth_mask": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, ci]),
     "udapose_kth_mask_dev": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, ci]),      # (k: an int32 in device memory)
     "udapose_topk_select": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),

@@ -468,6 +468,20 @@ int udapose_pose_nms_sweep(void* stream, const unsigned long long* mask, const i
                            int* n_keep, int* suppressed_by) {
     return pose_nms_sweep(S(stream), mask, order, refused, M, keep, n_keep, suppressed_by);
 }
+long long udapose_ap_match_ws_bytes(int M, int G, int F) { return (long long)ap_match_ws_bytes(M, G, F); }
+int udapose_ap_match(void* stream, const float* kp, const float* score, const int* frame_idx, const unsigned char* valid, const float* area, int M,
+                     const float* gt_kp, const float* gt_visible, const float* gt_area, const int* gt_frame, const unsigned char* gt_ignore, int G,
+                     int K, int F, const float* sigmas, const float* thresholds, int T, const float* ranges, int A, int max_dets, void* ws,
+                     float* rec_score, unsigned long long* rec_matched, unsigned long long* rec_ignored, int capacity, long long* counters) {
+    return ap_match(S(stream), kp, score, frame_idx, valid, area, M, gt_kp, gt_visible, gt_area, gt_frame, gt_ignore, G, K, F, sigmas, thresholds, T,
+                    ranges, A, max_dets, ws, rec_score, rec_matched, rec_ignored, capacity, counters);
+}
+long long udapose_ap_curve_ws_bytes(int capacity, int T, int A) { return (long long)ap_curve_ws_bytes(capacity, T, A); }
+int udapose_ap_curve(void* stream, const float* rec_score, const unsigned long long* rec_matched, const unsigned long long* rec_ignored,
+                     int capacity, const long long* counters, int T, int A, const double* recall_points, int R, void* ws, double* precision,
+                     float* scores, double* recall) {
+    return ap_curve(S(stream), rec_score, rec_matched, rec_ignored, capacity, counters, T, A, recall_points, R, ws, precision, scores, recall);
+}
 long long udapose_pose_nms_ws_bytes(int M) { return (long long)pose_nms_ws_bytes(M); }
 int udapose_pose_nms(void* stream, const float* kp, const float* conf, const float* boxes, const int* frame_idx, const unsigned char* status,
                      const float* box_score, const float* sigmas, const float* vis_thr, const float* oks_thr, int M, int K, void* ws, float* score,

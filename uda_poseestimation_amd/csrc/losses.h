@@ -79,3 +79,13 @@ size_t pose_nms_ws_bytes(int M);
 int pose_nms(hipStream_t s, const float* kp, const float* conf, const float* boxes, const int* frame_idx, const unsigned char* status,
              const float* box_score, const float* sigmas, const float* vis_thr, const float* oks_thr, int M, int K, void* ws, float* score, int* order,
              unsigned char* keep, int* n_keep, int* suppressed_by, float* oks_out);
+// pose_ap.hip
+size_t ap_match_ws_bytes(int M, int G, int F);
+int ap_match(hipStream_t s, const float* kp, const float* score, const int* frame_idx, const unsigned char* valid, const float* area, int M,
+             const float* gt_kp, const float* gt_visible, const float* gt_area, const int* gt_frame, const unsigned char* gt_ignore, int G, int K,
+             int F, const float* sigmas, const float* thresholds, int T, const float* ranges, int A, int max_dets, void* ws, float* rec_score,
+             unsigned long long* rec_matched, unsigned long long* rec_ignored, int capacity, long long* counters);
+size_t ap_curve_ws_bytes(int capacity, int T, int A);
+int ap_curve(hipStream_t s, const float* rec_score, const unsigned long long* rec_matched, const unsigned long long* rec_ignored, int capacity,
+             const long long* counters, int T, int A, const double* recall_points, int R, void* ws, double* precision, float* scores,
+             double* recall);

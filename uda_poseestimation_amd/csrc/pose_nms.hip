@@ -8,6 +8,7 @@
 // No atomics; every sum is added in ascending k: the same bits on every run.  M <= 4096 poses (64 mask words = one per lane), K <= 64.
 #include <float.h>
 #include "losses.h"
+#include "pose_pair.h"
 
 // no FMA contraction: oks(i, j) and oks(j, i) are the same expression tree on swapped operands, and stay the same bits
 #pragma clang fp contract(off)
@@ -16,11 +17,9 @@ namespace {
 typedef unsigned long long u64;
 constexpr int MAX_M = UDAPOSE_NMS_MAX_POSES, MAX_K = UDAPOSE_NMS_MAX_KEYPOINTS;
 
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
-
 // ---------------------------------------------------------------------------------------------------------------- rescoring and the order
 constexpr int RS_TPB = 1024, RS_POSES = 256, RS_PARTS = RS_TPB / RS_POSES;      // a block ranks 256 poses; each of 4 thread groups scans a quarter of the keys
-constexpr unsigned int KEY_REFUSED = 0xffffffffu;
+constexpr unsigned int KEY_REFUSED = POSE_KEY_REFUSED;
 
 struct PoseScore {
     float score, area;
@@ -60,14 +59,6 @@ __device__ __forceinline__ PoseScore pose_score(int m, const float* __restrict__
     r.area = boxes[(size_t)m * 5 + 2] * boxes[(size_t)m * 5 + 3];
     r.refused = bad || (status && status[m] != 0) || !finite_f(r.area) || !(r.area > 0.f) || !finite_f(r.score);
     return r;
-}
-
-// a key that orders poses as the walk does: smaller = earlier.  Scores descending (-0 = +0); every refused pose shares the last key
-__device__ __forceinline__ unsigned int order_key(float score, bool refused) {
-    if (refused) return KEY_REFUSED;
-    const unsigned int u = __float_as_uint(score + 0.f);
-    const unsigned int asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ~asc;      // (0xffffffff would need u = 0xffffffff, a NaN: refused)
 }
 
 __global__ __launch_bounds__(RS_TPB) void pose_rescore_k(const float* __restrict__ kp, const float* __restrict__ conf, const float* __restrict__ boxes,
@@ -154,8 +145,7 @@ __global__ __launch_bounds__(OK_TPB) void oks_matrix_k(const float* __restrict__
         ti[e] = i < Ma ? ((const float2*)kp_a)[(size_t)i * K + (e - ii * K)] : make_float2(0.f, 0.f);
     }
     for (int k = t; k < K; k += OK_TPB) {
-        const float s2 = 2.f * sigmas[k];
-        vk[k] = s2 * s2;
+        vk[k] = oks_sigma_sq(sigmas[k]);
     }
     if (t < OK_TJ) {
         const int j = j0 + t;
@@ -191,7 +181,7 @@ __global__ __launch_bounds__(OK_TPB) void oks_matrix_k(const float* __restrict__
         float A[OK_ROWS], acc[OK_ROWS];
 #pragma unroll
         for (int r = 0; r < OK_ROWS; ++r) {
-            A[r] = RECT ? aj + FLT_EPSILON : (area_i[r0 + r] + aj) * 0.5f + FLT_EPSILON;
+            A[r] = RECT ? oks_rect_area(aj) : (area_i[r0 + r] + aj) * 0.5f + FLT_EPSILON;
             acc[r] = 0.f;
         }
         for (int k = 0; k < K; ++k) {
@@ -200,18 +190,14 @@ __global__ __launch_bounds__(OK_TPB) void oks_matrix_k(const float* __restrict__
             const bool use = !RECT || ((vb >> k) & 1ull);
 #pragma unroll
             for (int r = 0; r < OK_ROWS; ++r) {
-                const float2 pi = ti[(r0 + r) * K + k];
-                const float dx = pi.x - pj.x, dy = pi.y - pj.y;
-                const float d2 = dx * dx + dy * dy;
-                const float e = d2 / v / A[r] * 0.5f;
-                const float term = expf(-e);
+                const float term = oks_term(ti[(r0 + r) * K + k], pj, v, A[r]);      // (pose_pair.h: the expression pose_ap.hip matches with)
                 if (use) acc[r] += term;
             }
         }
 #pragma unroll
         for (int r = 0; r < OK_ROWS; ++r) {
             const int i = i0 + r0 + r;
-            const float oks = RECT ? (nvis ? acc[r] / (float)nvis : 0.f) : acc[r] / (float)K;
+            const float oks = RECT ? oks_rect_mean(acc[r], nvis) : acc[r] / (float)K;
             if (i < Ma) {      // (uniform in the wave: all 64 lanes reach the ballot)
                 if (out && j < Mb) out[(size_t)i * Mb + j] = oks;
                 if (!RECT && mask) {

@@ -1130,6 +1130,29 @@ def predict(frames_u8, boxes, model, frame_idx=None, flip_pairs=None, shift_heat
     return out
 
 
+def evaluate_ap(batches, model, meter=None, nms=True, **predict_kwargs):
+    """Key-point AP under OKS of predict()'s poses over a labelled set: per batch `predict(..., nms=nms)` and
+    lib.keypoint_detection.APMeter.update_predict, then the meter's report - AP / AP50 / AP75 / APM / APL / AR and the tables.  Each batch
+    is a dict: "frames" [F,Hs,Ws,3] uint8 CUDA, "boxes" [M,5], "frame_idx" [M] (the frame of every box, within the batch's frames),
+    "box_scores" [M] (or None), and the labelled poses of those frames "gt_keypoints" [G,K,2] in frame pixels, "gt_visible" [G,K],
+    "gt_area" [G], "gt_frame" [G], optionally "gt_ignore" [G].  meter: an APMeter to add to (None: one with the defaults for the model's key
+    points); nms: True or a dict of oks_nms's arguments, as predict() takes it; predict_kwargs go to predict().  Nothing is read back before
+    the report."""
+    if nms is None or nms is False:
+        raise ValueError("evaluate_ap() scores predict()'s rescored, thinned poses: nms must be True or a dict of oks_nms's arguments")
+    dev = next(model.parameters()).device
+    if meter is None:
+        meter = kd.APMeter(model.num_keypoints, sigmas=nms.get("sigmas") if isinstance(nms, dict) else None, device=dev)
+    for batch in batches:
+        fi = batch["frame_idx"]
+        if not torch.is_tensor(fi):
+            fi = torch.from_numpy(np.ascontiguousarray(fi, dtype=np.int32)).to(dev, non_blocking=True)
+        res = predict(batch["frames"], batch["boxes"], model, frame_idx=fi, box_scores=batch.get("box_scores"), nms=nms, **predict_kwargs)
+        meter.update_predict(res, fi, batch["gt_keypoints"], batch["gt_visible"], batch["gt_area"], batch["gt_frame"],
+                             num_frames=batch["frames"].shape[0], gt_ignore=batch.get("gt_ignore"))
+    return meter.compute()
+
+
 class GraphedTrainStep:
     """The mean-teacher step captured into hipGraphs: ~1300 kernel launches per step are replayed by ONE graph launch on one
     rank (forwards, losses, backward, Adam + EMA + packs), which removes the host launch gaps.

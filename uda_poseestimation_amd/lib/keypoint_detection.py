@@ -851,3 +851,241 @@ def oks_nms(keypoints, confidence, boxes, frame_idx=None, status=None, box_score
                              ptr(out["score"]), ptr(out["order"]), ptr(out["keep"]), ptr(out["n_keep"]), ptr(out["suppressed_by"]),
                              ptr(out.get("oks"))), "pose_nms")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- key-point AP under OKS
+# COCO-style evaluation of predict(nms=True)'s poses against labelled ones (csrc/pose_ap.hip): cocoapi's evaluateImg +
+# accumulate for key points, on the device.  The defaults are cocoapi's Params for iouType = 'keypoints'.
+AP_OKS_THRESHOLDS = tuple(np.linspace(.5, .95, 10))
+AP_AREA_RANGES = {"all": (0, 1e10), "medium": (32 ** 2, 96 ** 2), "large": (96 ** 2, 1e10)}
+AP_RECALL_POINTS = tuple(np.linspace(.0, 1.00, int(np.round(1.00 / .01)) + 1))
+AP_MAX_COMBOS = 64             # UDAPOSE_AP_MAX_COMBOS (include/udapose.h): thresholds x ranges, one per lane of the matching wave
+AP_MAX_DETS = 64               # UDAPOSE_AP_MAX_DETS
+AP_MAX_RECALL_POINTS = 128     # UDAPOSE_AP_MAX_RECALL_POINTS
+AP_MAX_CAPACITY = 1 << 18      # UDAPOSE_AP_MAX_CAPACITY
+AP_MAX_FRAMES = 4096           # UDAPOSE_AP_MAX_FRAMES
+AP_COUNTS = ("records", "dropped", "refused", "cut", "overflow_frames", "bad_labels")      # counters[0 .. UDAPOSE_AP_COUNTERS)
+
+
+def _check_ap_thresholds(thresholds):
+    """T OKS thresholds as the kernel takes them, a float32 array: each in (0, 1), strictly ascending AS fp32.  ValueError otherwise."""
+    try:
+        t64 = np.asarray([float(t) for t in thresholds], dtype=np.float64)
+    except TypeError:
+        raise ValueError(f"thresholds must be a sequence of numbers, got {thresholds!r}") from None
+    t32 = t64.astype(np.float32)
+    if t32.size < 1 or not (np.isfinite(t32).all() and (t32 > 0).all() and (t32 < 1).all()):
+        raise ValueError(f"OKS thresholds must be in (0, 1) as fp32, at least one of them, got {list(thresholds)!r}")
+    if not (t32[1:] > t32[:-1]).all():
+        raise ValueError(f"OKS thresholds must be strictly ascending as fp32, got {list(thresholds)!r}")
+    return t32
+
+
+class APMeter:
+    """Key-point AP under OKS over a whole set, COCO-style, kept on the device (csrc/pose_ap.hip).  An update matches the
+    detections of its frames to the labelled poses (cocoapi's evaluateImg: per frame the `max_dets` best detections, greedily, at every
+    threshold and in every area range) and appends one record per detection - its score and a matched / ignored bit per (range, threshold),
+    bit a * T + t - to record arrays on the device; `compute()` sorts the records, forms the precision / recall tables (cocoapi's
+    accumulate, fp64) and reads them back once.  Nothing else is read back, so an update can be captured, and a replay appends again.
+
+    sigmas: as oks_nms takes them.  thresholds: T values in (0, 1), strictly ascending as fp32.  area_ranges: A named (lo, hi) pairs of
+    label areas, the first one the range the headline numbers are taken from; T * A <= 64.  max_dets: 1 .. 64.  recall_points: at most 128,
+    uploaded as the fp64 numbers given.  capacity: the records kept, at most 2^18; later ones are dropped and counted.
+    Deviations from cocoapi: a label without a visible joint is ignored in every range and matches nothing (cocoapi falls back to a
+    box distance); a frame with more than 64 labels is left out whole and counted in `overflow_frames`; no crowd regions."""
+
+    def __init__(self, num_keypoints, sigmas=None, thresholds=AP_OKS_THRESHOLDS, area_ranges=None, max_dets=20, recall_points=AP_RECALL_POINTS,
+                 capacity=65536, device=None):
+        self.num_keypoints = int(num_keypoints)
+        if not 1 <= self.num_keypoints <= NMS_MAX_KEYPOINTS:
+            raise ValueError(f"APMeter takes 1 to {NMS_MAX_KEYPOINTS} key points (UDAPOSE_NMS_MAX_KEYPOINTS), got {num_keypoints}")
+        self._thr32 = _check_ap_thresholds(thresholds)
+        self.thresholds = tuple(float(t) for t in thresholds)
+        ranges = dict(AP_AREA_RANGES if area_ranges is None else area_ranges)
+        self.area_ranges = {str(n): (float(lo), float(hi)) for n, (lo, hi) in ranges.items()}
+        if not self.area_ranges or any(np.isnan(v) for r in self.area_ranges.values() for v in r):
+            raise ValueError(f"area_ranges must be named (lo, hi) pairs, at least one, got {area_ranges!r}")
+        T, A = len(self._thr32), len(self.area_ranges)
+        if T * A > AP_MAX_COMBOS:
+            raise ValueError(f"thresholds x area ranges must be at most {AP_MAX_COMBOS} (UDAPOSE_AP_MAX_COMBOS), got {T} x {A} = {T * A}")
+        self.max_dets = int(max_dets)
+        if not 1 <= self.max_dets <= AP_MAX_DETS or self.max_dets != max_dets:
+            raise ValueError(f"max_dets must be an integer in [1, {AP_MAX_DETS}], got {max_dets!r}")
+        self._rp64 = np.asarray([float(r) for r in recall_points], dtype=np.float64)
+        if not 1 <= self._rp64.size <= AP_MAX_RECALL_POINTS or np.isnan(self._rp64).any():
+            raise ValueError(f"1 to {AP_MAX_RECALL_POINTS} recall points, got {self._rp64.size}")
+        self.recall_points = tuple(float(r) for r in self._rp64)
+        self.capacity = int(capacity)
+        if not 1 <= self.capacity <= AP_MAX_CAPACITY or self.capacity != capacity:
+            raise ValueError(f"capacity must be an integer in [1, {AP_MAX_CAPACITY}], got {capacity!r}")
+        self._sigmas_arg = sigmas
+        if sigmas is not None and not torch.is_tensor(sigmas) and not isinstance(sigmas, str):
+            table = tuple(float(v) for v in sigmas)
+            if len(table) != self.num_keypoints or not all(np.isfinite(v) and v > 0 for v in table):
+                raise ValueError(f"sigmas must be {self.num_keypoints} positive numbers, got {table}")
+        self._st = None
+        if device is not None or torch.cuda.is_available():
+            self._allocate(torch.device("cuda" if device is None else device))
+
+    def _allocate(self, device):
+        if device.type != "cuda":
+            raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
+        T, A, R, cap = len(self._thr32), len(self.area_ranges), self._rp64.size, self.capacity
+        ranges = np.asarray(list(self.area_ranges.values()), dtype=np.float64).astype(np.float32)
+        # (the record arrays have one more slot than capacity: merge() sends what does not fit there)
+        self._st = {"thr": torch.from_numpy(self._thr32).to(device), "ranges": torch.from_numpy(ranges).to(device),
+                    "rp": torch.from_numpy(self._rp64).to(device), "sigmas": _sigmas_device(self._sigmas_arg, self.num_keypoints, device),
+                    "score": torch.zeros(cap + 1, dtype=torch.float32, device=device),
+                    "matched": torch.zeros(cap + 1, dtype=torch.int64, device=device),
+                    "ignored": torch.zeros(cap + 1, dtype=torch.int64, device=device),
+                    "counters": torch.zeros(len(AP_COUNTS) + A, dtype=torch.int64, device=device)}
+
+    def _on_device(self, like=None):
+        if self._st is None:
+            if like is None or not like.is_cuda:
+                raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
+            self._allocate(like.device)
+        return self._st
+
+    def reset(self):
+        """Zero the counters (in place: a captured update keeps appending to the same memory); the records behind the count mean nothing."""
+        self._on_device()["counters"].zero_()
+
+    def state(self):
+        """The raw state on the device, the meter's own tensors: {"score" fp32, "matched", "ignored" int64 words (bit a * T + t), each
+        [capacity + 1] with the first counters[0] entries in use; "counters" int64 [6 + A]: AP_COUNTS, then npig per range}."""
+        st = self._on_device()
+        return {k: st[k] for k in ("score", "matched", "ignored", "counters")}
+
+    def update(self, keypoints, score, frame_idx, gt_keypoints, gt_visible, gt_area, gt_frame, *, num_frames, area=None, valid=None,
+               gt_ignore=None):
+        """Match one update's detections (keypoints [M,K,2] in frame pixels, score [M], frame_idx [M] integers; valid [M], non-zero = takes
+        part, None: all; area [M], None: the key points' extent (max x - min x) * (max y - min y)) to its labelled poses (gt_keypoints
+        [G,K,2], gt_visible [G,K], > 0 counts, gt_area [G], gt_frame [G]; gt_ignore [G], non-zero = ignored, None: none) on frames
+        [0, num_frames), and append the records.  1 <= M, G, num_frames <= 4096.  CUDA tensors only; shape errors raise ValueError before
+        any launch; nothing is read back."""
+        kp = _pose_tensor(keypoints, (None, self.num_keypoints, 2), "keypoints")
+        M, K = kp.shape[:2]
+        _check_mk(M, K)
+        sc = _pose_tensor(score, (M,), "score")
+        fi = _pose_tensor(frame_idx, (M,), "frame_idx", torch.int32)
+        va = None if valid is None else _pose_tensor(valid != 0 if torch.is_tensor(valid) else valid, (M,), "valid", torch.uint8)
+        ar = None if area is None else _pose_tensor(area, (M,), "area")
+        gk = _pose_tensor(gt_keypoints, (None, K, 2), "gt_keypoints")
+        G = gk.shape[0]
+        if not 1 <= G <= NMS_MAX_POSES:
+            raise ValueError(f"1 to {NMS_MAX_POSES} labelled poses a call, got {G}")
+        gv = _pose_tensor(gt_visible, (G, K), "gt_visible")
+        ga = _pose_tensor(gt_area, (G,), "gt_area")
+        gf = _pose_tensor(gt_frame, (G,), "gt_frame", torch.int32)
+        gi = None if gt_ignore is None else _pose_tensor(gt_ignore != 0 if torch.is_tensor(gt_ignore) else gt_ignore, (G,), "gt_ignore", torch.uint8)
+        F = int(num_frames)
+        if not 1 <= F <= AP_MAX_FRAMES or F != num_frames:
+            raise ValueError(f"num_frames must be an integer in [1, {AP_MAX_FRAMES}], got {num_frames!r}")
+        st = self._on_device(kp)
+        dev = st["counters"].device
+        if any(t is not None and t.device != dev for t in (kp, sc, fi, va, ar, gk, gv, ga, gf, gi)):
+            raise ValueError(f"the meter's state lives on {dev}: every tensor of an update must")
+        L = lib()
+        ws = torch.empty(L.udapose_ap_match_ws_bytes(M, G, F) // 8 + 1, dtype=torch.int64, device=dev)      # (a capture keeps its own)
+        check(L.udapose_ap_match(_hip.stream(), ptr(kp), ptr(sc), ptr(fi), ptr(va), ptr(ar), M, ptr(gk), ptr(gv), ptr(ga), ptr(gf), ptr(gi), G, K, F,
+                                 ptr(st["sigmas"]), ptr(st["thr"]), len(self._thr32), ptr(st["ranges"]), len(self.area_ranges), self.max_dets,
+                                 ptr(ws), ptr(st["score"]), ptr(st["matched"]), ptr(st["ignored"]), self.capacity, ptr(st["counters"])),
+              "ap_match")
+
+    def update_predict(self, result, frame_idx, gt_keypoints, gt_visible, gt_area, gt_frame, *, num_frames, gt_ignore=None):
+        """update() on engine.predict(nms=True)'s dict: its key points, its rescored "score", valid = keep & (status == 0), the area from the
+        key points."""
+        missing = [k for k in ("keypoints", "score", "keep", "status") if k not in result]
+        if missing:
+            raise ValueError(f"update_predict() takes predict(nms=True)'s dict: {missing} are missing")
+        valid = (result["keep"] != 0) & (result["status"] == 0)
+        self.update(result["keypoints"], result["score"], frame_idx, gt_keypoints, gt_visible, gt_area, gt_frame, num_frames=num_frames,
+                    valid=valid, gt_ignore=gt_ignore)
+
+    def merge(self, other):
+        """Append another meter's records (same tables and capacity rules; any device) after this one's, and add its counts: ranks or
+        shards of one set.  Reads the other's record count - the one read-back outside compute()."""
+        if not isinstance(other, APMeter):
+            raise ValueError("merge() takes an APMeter")
+        if (other._thr32.tolist(), other.area_ranges, other.max_dets, other.num_keypoints) != \
+                (self._thr32.tolist(), self.area_ranges, self.max_dets, self.num_keypoints):
+            raise ValueError("merge() takes a meter with the same thresholds, area ranges, max_dets and key points")
+        st, ot = self._on_device(), other._on_device()
+        dev = st["counters"].device
+        oc = ot["counters"].to(dev)
+        n = int(ot["counters"][0])
+        c = st["counters"]
+        if n:
+            at = torch.clamp(torch.arange(n, device=dev) + c[0], max=self.capacity)      # (what does not fit lands in the spare slot)
+            for k in ("score", "matched", "ignored"):
+                st[k].index_copy_(0, at, ot[k][:n].to(dev))
+        total = c[0] + oc[0]
+        stored = torch.clamp(total, max=self.capacity)
+        c[1:] += oc[1:]
+        c[1] += total - stored
+        c[0] = stored
+
+    def compute(self):
+        """The curve launches (udapose_ap_curve), the one read-back, then `report()`.  Warns when records were dropped or frames left out."""
+        st = self._on_device()
+        dev = st["counters"].device
+        T, A, R = len(self._thr32), len(self.area_ranges), self._rp64.size
+        L = lib()
+        ws = torch.empty(L.udapose_ap_curve_ws_bytes(self.capacity, T, A) // 8 + 1, dtype=torch.int64, device=dev)
+        precision = torch.empty(T, R, A, dtype=torch.float64, device=dev)
+        recall = torch.empty(T, A, dtype=torch.float64, device=dev)
+        scores = torch.empty(T, R, A, dtype=torch.float32, device=dev)
+        check(L.udapose_ap_curve(_hip.stream(), ptr(st["score"]), ptr(st["matched"]), ptr(st["ignored"]), self.capacity, ptr(st["counters"]), T, A,
+                                 ptr(st["rp"]), R, ptr(ws), ptr(precision), ptr(scores), ptr(recall)), "ap_curve")
+        parts = [precision.reshape(-1).view(torch.uint8), recall.reshape(-1).view(torch.uint8), st["counters"].view(torch.uint8),
+                 scores.reshape(-1).view(torch.uint8)]
+        host = torch.cat(parts).cpu().numpy()
+        cut = np.cumsum([p.numel() for p in parts])
+        p = host[:cut[0]].view(np.float64).reshape(T, R, A)
+        r = host[cut[0]:cut[1]].view(np.float64).reshape(T, A)
+        cnt = host[cut[1]:cut[2]].view(np.int64)
+        s = host[cut[2]:].view(np.float32).reshape(T, R, A)
+        rep = APMeter.report(p, r, s, cnt[len(AP_COUNTS):], cnt[:len(AP_COUNTS)], thresholds=self.thresholds, area_ranges=tuple(self.area_ranges))
+        if rep["counts"]["dropped"] or rep["counts"]["overflow_frames"]:
+            import warnings
+            warnings.warn(f"APMeter: {rep['counts']['dropped']} records beyond capacity {self.capacity} were dropped and "
+                          f"{rep['counts']['overflow_frames']} frames with more than 64 labels were left out: the numbers are not the whole set's")
+        return rep
+
+    @staticmethod
+    def report(precision, recall, scores, npig, counts, thresholds=AP_OKS_THRESHOLDS, area_ranges=tuple(AP_AREA_RANGES)):
+        """The report of the tables, in fp64 on the host (pure: no device, no side effect), cocoapi's summarize for key points:
+          AP            the mean of precision[:, :, first range] over the entries > -1, -1 without one; AR the same over recall
+          AP50, AP75    the same at the threshold nearest .5 / .75 (absent when no threshold is within 1e-6 of it); AR50, AR75
+          AP_<range>, AR_<range>   for every range; APM / APL (ARM / ARL) alias the ranges named "medium" / "large"
+          precision [T,R,A], recall [T,A], scores [T,R,A]; npig [A] int64; counts {records, dropped, refused, cut, overflow_frames,
+          bad_labels}; thresholds, area_ranges as given"""
+        thr = np.asarray([float(t) for t in thresholds], dtype=np.float64)
+        names = tuple(area_ranges)
+        p, r, s = np.asarray(precision, dtype=np.float64), np.asarray(recall, dtype=np.float64), np.asarray(scores)
+        T, A = thr.size, len(names)
+        if p.ndim != 3 or p.shape[0] != T or p.shape[2] != A or r.shape != (T, A) or s.shape != p.shape:
+            raise ValueError(f"report() takes precision / scores [{T},R,{A}] and recall [{T},{A}], got {p.shape}, {s.shape}, {r.shape}")
+        cnt = np.asarray(counts, dtype=np.int64).reshape(-1)
+        if cnt.size != len(AP_COUNTS) or np.asarray(npig).size != A:
+            raise ValueError(f"report() takes {len(AP_COUNTS)} counts and npig [{A}]")
+
+        def mean(x):
+            x = x[x > -1]
+            return float(x.mean()) if x.size else -1.0
+
+        rep = {"AP": mean(p[:, :, 0]), "AR": mean(r[:, 0])}
+        for tag, want in (("50", .5), ("75", .75)):
+            t = int(np.abs(thr - want).argmin())
+            if abs(thr[t] - want) < 1e-6:
+                rep["AP" + tag], rep["AR" + tag] = mean(p[t, :, 0]), mean(r[t, 0:1])
+        for a, name in enumerate(names):
+            rep["AP_" + name], rep["AR_" + name] = mean(p[:, :, a]), mean(r[:, a])
+        for short, name in (("M", "medium"), ("L", "large")):
+            if name in names:
+                rep["AP" + short], rep["AR" + short] = rep["AP_" + name], rep["AR_" + name]
+        rep.update({"precision": p, "recall": r, "scores": s, "npig": np.asarray(npig, dtype=np.int64).copy(),
+                    "counts": {n: int(v) for n, v in zip(AP_COUNTS, cnt)}, "thresholds": tuple(float(t) for t in thresholds),
+                    "area_ranges": names})
+        return rep
