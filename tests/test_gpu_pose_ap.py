@@ -174,6 +174,26 @@ def test_equal_scores_across_rank_tiles(N):
     assert want.counts["records"] == N and len(set(want.records()[0].tolist())) == 3
 
 
+def test_sort_across_its_key_tile():
+    """4096 + 19 records: the sort streams its keys through LDS 4096 at a time, so the second tile's index base is past zero.  Three score
+    levels: equal keys lie on both sides of the tile boundary and the sequence number places them."""
+    F = 256
+    updates = [scene(17, [4] * F, [16] * F, levels=3), scene(17, [3, 5], [9, 10], levels=3)]
+    meter, want = _both(17, updates, thresholds=(0.5, 0.75), area_ranges={"all": (0, 1e10)})
+    _same(meter, want)
+    s = want.records()[0]
+    assert want.counts["records"] == 4096 + 19 and len(set(s.tolist())) == 3 and set(s[4096:].tolist()) == set(s[:4096].tolist())
+
+
+def test_record_offsets_across_the_waves_of_the_frame_scan():
+    """259 frames, one label and one or two detections each: a thread of the frame kernel owns 4 frames, so threads 0 .. 64 hold them and the
+    offsets of the last frames take the first wave's sum."""
+    F = 259
+    meter, want = _both(17, [scene(17, [1] * F, [1 + f % 2 for f in range(F)])])
+    _same(meter, want)
+    assert want.counts["records"] == F + F // 2
+
+
 def test_label_and_detection_limits_of_a_frame():
     meter, want = _both(17, [scene(17, [64, 65, 2], [6, 6, 6])], thresholds=(0.5, 0.75))
     with pytest.warns(UserWarning, match="left out"):

@@ -108,6 +108,20 @@ def test_key_point_counts(K):
     _run_and_check(kp, conf, boxes, frame=frame)
 
 
+@pytest.mark.parametrize("M", [17, 257])
+def test_rank_across_the_group_boundary_and_the_padding(M):
+    """Distinct poses on one frame, scores from three levels: the index decides nearly every place of the order.  M = 17 ranks beside 15
+    padding keys (the keys are padded to 32); M = 257 spans two 256-pose work-groups, with equal keys on both sides of the boundary."""
+    K = 17
+    level = np.asarray([0.5, 0.7, 0.9], np.float32)[np.arange(M) % 3]
+    kp, conf, boxes = _poses([ref.base_pose(i, K) for i in range(M)], level)
+    out, r = _run_and_check(kp, conf, boxes)
+    assert len(set(r["score"].tolist())) == 3 and r["n_keep"] == M
+    assert sorted(r["order"].tolist()) == list(range(M)) and r["order"].tolist()[:3] == [2, 5, 8]
+    if M > 256:
+        assert set(r["score"][256:].tolist()) <= set(r["score"][:256].tolist())
+
+
 def test_full_size_without_the_matrix():
     kp, conf, boxes, frame = ref.grouped_case(4096, 17)
     out, r = _run_and_check(kp, conf, boxes, frame=frame)

@@ -195,6 +195,38 @@ __device__ __forceinline__ T block_sum(T v, T* red) {
     return t;
 }
 
+// The wave inclusive scan in lane order (int, unsigned int): six __shfl_up steps, lane l returns v_0 + ... + v_l.
+template <typename T>
+__device__ __forceinline__ T wave_scan_incl(T v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T up = __shfl_up(v, o, 64);
+        if ((int)(threadIdx.x & 63) >= o) v += up;
+    }
+    return v;
+}
+// The block inclusive scan in thread order: wave_scan_incl, one LDS slot per wave, then the sums of the waves before the thread's own added
+// in wave order; every thread returns its prefix and gets the block's sum in `total`.  red: WAVES entries of LDS.  Barriers as block_sum: it
+// opens with one, every thread of the block must reach the call, the caller may rely on that barrier alone, none follows the last read of red.
+template <int WAVES, typename T>
+__device__ __forceinline__ T block_scan_incl(T v, T* red, T& total) {
+    v = wave_scan_incl(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T before = 0;
+    total = 0;
+    for (int w = 0; w < WAVES; ++w) {
+        if (w < (int)(threadIdx.x >> 6)) before += red[w];
+        total += red[w];
+    }
+    return v + before;
+}
+// v added to a 64-bit counter of device memory (an integer atomic; nothing is issued for v == 0): the evaluation meters' states
+__device__ __forceinline__ void counter_add(long long* __restrict__ p, long long v) {
+    if (v) atomicAdd((unsigned long long*)p, (unsigned long long)v);
+}
+
 // ReflectionPad2d(1)'s source index of position i (in [-1, n]) on an axis of n >= 2
 __device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 // sign(v) with sign(0) = 0 (NaN: 0)

@@ -3,12 +3,10 @@
 #pragma once
 #include "common.h"
 
+// the sign-flip transform: a float's bits -> a uint32 that ascends with the value (-0 just below +0).  hm_key and pose_pair.h's order_key
+__device__ __forceinline__ unsigned int hm_key_bits(unsigned int b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 // order-preserving float -> uint32 key (NaN -> 0xffffffff, the largest: torch.kthvalue's order)
-__device__ __forceinline__ unsigned int hm_key(float v) {
-    if (v != v) return 0xffffffffu;
-    const unsigned int b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
+__device__ __forceinline__ unsigned int hm_key(float v) { return v != v ? 0xffffffffu : hm_key_bits(__float_as_uint(v)); }
 __device__ __forceinline__ float hm_unkey(unsigned int k) {
     if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);

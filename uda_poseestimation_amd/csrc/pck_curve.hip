@@ -58,10 +58,6 @@ __device__ __forceinline__ int pck_first_hit(float d, const float* thr, int T) {
     return lo;
 }
 
-__device__ __forceinline__ void state_add(long long* __restrict__ p, long long v) {
-    if (v) atomicAdd((unsigned long long*)p, (unsigned long long)v);
-}
-
 // Block (k, y): joint k, samples b = y * TPB + lane, + gridDim.y * TPB, ...  A lane keeps count / nonfinite / epe_q in registers and drops
 // each pair's first hit into an LDS histogram; the waves' sums meet in LDS, column j of row k gets the histogram's prefix sum.
 __global__ __launch_bounds__(TPB) void pck_accumulate_k(const float* __restrict__ pred, const float* __restrict__ gt,
@@ -112,7 +108,7 @@ __global__ __launch_bounds__(TPB) void pck_accumulate_k(const float* __restrict_
         } else {
             v = tid == T ? (long long)s_cnt : (tid == T + 1 ? (long long)s_q : (long long)s_nf);
         }
-        state_add(state + (size_t)k * (T + 3) + tid, v);
+        counter_add(state + (size_t)k * (T + 3) + tid, v);
     }
 }
 
@@ -163,7 +159,7 @@ __global__ __launch_bounds__(TPB) void pck_accumulate_heatmaps_k(const float* __
     long long v;
     if (tid < T) v = tid >= pck_first_hit(p.d, s_thr, T) ? 1 : 0;
     else v = tid == T ? 1 : (tid == T + 1 ? p.q : (long long)p.nonfinite);
-    state_add(state + (size_t)k * (T + 3) + tid, v);
+    counter_add(state + (size_t)k * (T + 3) + tid, v);
 }
 
 int check_sizes(int B, int K, int T) {

@@ -1,16 +1,18 @@
 // Key-point AP under OKS on the device (fp32 / fp64 / integers only: both builds of the library export identical code).
 // One update (udapose_ap_match), three launches:
 //   ap_rank_k   : a detection's area, whether it is refused, and the order of all M (descending score, equal scores by ascending index,
-//                 refused ones last) by counting over keys staged in LDS - pose_rescore_k's method and key
-//   ap_frames_k : one work-group: detections and labels per frame (LDS integer counts), the record offset of every frame by an exclusive
-//                 scan in ascending frame id - the sequence order is part of the result, nothing is appended in arrival order - and the counts
+//                 refused ones last): pose_pair.h's key and rank by counting, keys staged once in LDS, as in pose_rescore_k
+//   ap_frames_k : one work-group: detections and labels per frame (LDS integer counts), the record offset of every frame by common.h's
+//                 block scan in ascending frame id - the sequence order is part of the result, nothing is appended in arrival order - and
+//                 the counts
 //   ap_match_k  : a wave per frame.  Phase 1, lane = label: the OKS tile [<= max_dets][64] in LDS, the labels' key points staged [K][64]
-//                 as oks_matrix_k stages its columns, the per-joint term the one of pose_pair.h.  Phase 2, lane = (range a, threshold t):
-//                 cocoapi's greedy walk, the matched set and the range's ignore set one 64-bit register each, a loop over set bits,
-//                 non-ignored labels first; the record's two words are two ballots
+//                 as oks_matrix_k stages its columns; the per-joint term and the visibility word are pose_pair.h's, the ones of
+//                 oks_matrix_k.  Phase 2, lane = (range a, threshold t): cocoapi's greedy walk, the matched set and the range's ignore
+//                 set one 64-bit register each, one loop over set bits run for the counted labels, then for the ignored ones; the
+//                 record's two words are two ballots
 // The tables (udapose_ap_curve), two launches, N read from the device counter:
-//   ap_sort_k   : a work-group ranks 256 records against all N keys streamed through LDS in tiles (broadcast reads, O(N^2) compares,
-//                 stable, deterministic), then scatters the three record fields into sorted order
+//   ap_sort_k   : a work-group ranks 256 records against all N keys streamed through LDS in tiles (the same rank by counting: O(N^2)
+//                 compares, stable, deterministic), then scatters the three record fields into sorted order
 //   ap_curve_k  : a work-group per (t, a): block scans of the integer tp / fp flags, pr and rc in fp64 with the one IEEE division each,
 //                 the envelope as per-chunk maxima and their suffix maxima, per recall point a bisection on the monotone rc
 // Integer atomics on the int64 counters only; no floating-point atomics; nothing is read back: capturable, a replay appends again.
@@ -18,28 +20,19 @@
 #include <math.h>
 #include "losses.h"
 #include "pose_pair.h"
+#include "pose_ws.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-typedef unsigned long long u64;
-constexpr int MAX_M = UDAPOSE_NMS_MAX_POSES, MAX_K = UDAPOSE_NMS_MAX_KEYPOINTS, MAX_F = UDAPOSE_AP_MAX_FRAMES;
+constexpr int MAX_M = UDAPOSE_NMS_MAX_POSES, MAX_F = UDAPOSE_AP_MAX_FRAMES;
 constexpr int MAX_L = UDAPOSE_AP_MAX_LABELS_PER_FRAME, MAX_C = UDAPOSE_AP_MAX_COMBOS, MAX_R = UDAPOSE_AP_MAX_RECALL_POINTS;
 constexpr int MAX_CAP = UDAPOSE_AP_MAX_CAPACITY, NCNT = UDAPOSE_AP_COUNTERS;
 static_assert(MAX_L == 64 && MAX_C == 64, "a lane per label, a lane per (range, threshold)");
 enum { C_RECORDS = 0, C_DROPPED, C_REFUSED, C_CUT, C_OVERFLOW, C_BAD_LABELS };
 
-__device__ __forceinline__ void counter_add(long long* __restrict__ p, long long v) {
-    if (v) atomicAdd((unsigned long long*)p, (unsigned long long)v);
-}
-
 // ---------------------------------------------------------------------------------------------------------------- the order of an update
-constexpr int RK_TPB = 1024, RK_DETS = 256, RK_PARTS = RK_TPB / RK_DETS;
-
-struct DetInfo {
-    float area;
-    bool refused;
-};
+struct DetInfo { float area; bool refused; };
 
 // area: the given one, or (max_k x - min_k x) * (max_k y - min_k y) over all K joints (cocoapi loadRes); refused: valid == 0, a score,
 // coordinate or given area that is not finite, a frame outside [0, F)
@@ -61,39 +54,29 @@ __device__ __forceinline__ DetInfo det_info(int m, const float* __restrict__ kp,
     return r;
 }
 
-__global__ __launch_bounds__(RK_TPB) void ap_rank_k(const float* __restrict__ kp, const float* __restrict__ score, const int* __restrict__ frame,
-                                                    const unsigned char* __restrict__ valid, const float* __restrict__ area, int M, int K, int F,
-                                                    int* __restrict__ order, int* __restrict__ ofr, float* __restrict__ darea) {
+__global__ __launch_bounds__(RANK_TPB) void ap_rank_k(const float* __restrict__ kp, const float* __restrict__ score, const int* __restrict__ frame,
+                                                      const unsigned char* __restrict__ valid, const float* __restrict__ area, int M, int K, int F,
+                                                      int* __restrict__ order, int* __restrict__ ofr, float* __restrict__ darea) {
     __shared__ __attribute__((aligned(16))) unsigned int keys[MAX_M];
-    __shared__ int part[RK_PARTS][RK_DETS];
-    const int t = threadIdx.x, i0 = blockIdx.x * RK_DETS;
-    const int Mpad = (M + 4 * RK_PARTS - 1) / (4 * RK_PARTS) * (4 * RK_PARTS);      // (<= MAX_M: it is a multiple of 16)
-    for (int m = t; m < Mpad; m += RK_TPB) {
+    __shared__ int part[RANK_PARTS][RANK_ITEMS];
+    const int t = threadIdx.x, i0 = blockIdx.x * RANK_ITEMS;
+    const int Mpad = rank_padded(M);
+    for (int m = t; m < Mpad; m += RANK_TPB) {
         unsigned int key = POSE_KEY_REFUSED;
         if (m < M) {
             const DetInfo r = det_info(m, kp, score, frame, valid, area, K, F);
             key = order_key(score[m], r.refused);
-            if (m >= i0 && m < i0 + RK_DETS) darea[m] = r.area;
+            if (m >= i0 && m < i0 + RANK_ITEMS) darea[m] = r.area;
         }
         keys[m] = key;
     }
     __syncthreads();
-    const int p = t & (RK_DETS - 1), q = t / RK_DETS, i = i0 + p;
+    const int p = t & (RANK_ITEMS - 1), q = t / RANK_ITEMS, i = i0 + p;
     const unsigned int ki = i < M ? keys[i] : 0u;
-    const int per = Mpad / RK_PARTS, j0 = q * per;
-    int count = 0;
-    for (int j = j0; j < j0 + per; j += 4) {
-        const uint4 kj = *(const uint4*)&keys[j];
-        count += (kj.x < ki || (kj.x == ki && j < i)) + (kj.y < ki || (kj.y == ki && j + 1 < i)) + (kj.z < ki || (kj.z == ki && j + 2 < i)) +
-                 (kj.w < ki || (kj.w == ki && j + 3 < i));
-    }
-    part[q][p] = count;
-    __syncthreads();
+    const int per = Mpad / RANK_PARTS;
+    const int rank = rank_finish(part, q, p, rank_count(keys + q * per, per, q * per, ki, i));
     if (q == 0 && i < M) {
-        int rank = 0;
-#pragma unroll
-        for (int e = 0; e < RK_PARTS; ++e) rank += part[e][p];
-        order[rank] = i;      // (the order is total: every rank in [0, M) is taken once)
+        order[rank] = i;
         ofr[rank] = ki == POSE_KEY_REFUSED ? -1 : frame[i];
     }
 }
@@ -107,7 +90,7 @@ __global__ __launch_bounds__(FR_TPB) void ap_frames_k(const int* __restrict__ of
     __shared__ int wsum[FR_TPB / 64];
     __shared__ int tot[4];      // refused, bad labels, cut, overflow frames
     __shared__ long long s_base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     for (int f = t; f < F; f += FR_TPB) { cd[f] = 0; cl[f] = 0; }
     if (t < 4) tot[t] = 0;
     if (t == 0) s_base = counters[C_RECORDS];
@@ -135,28 +118,14 @@ __global__ __launch_bounds__(FR_TPB) void ap_frames_k(const int* __restrict__ of
         }
         local += n[e];
     }
-    int inc = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += v;
+    const int tally[4] = {refused, bad, cut, over};
+    for (int e = 0; e < 4; ++e) {
+        const int v = wave_sum(tally[e]);
+        if ((t & 63) == 0 && v) atomicAdd(&tot[e], v);
     }
-    if (lane == 63) wsum[wave] = inc;
-    refused = wave_sum(refused); bad = wave_sum(bad); cut = wave_sum(cut); over = wave_sum(over);
-    if (lane == 0) {
-        if (refused) atomicAdd(&tot[0], refused);
-        if (bad) atomicAdd(&tot[1], bad);
-        if (cut) atomicAdd(&tot[2], cut);
-        if (over) atomicAdd(&tot[3], over);
-    }
-    __syncthreads();
-    int wbase = 0, total = 0;
-    for (int w = 0; w < FR_TPB / 64; ++w) {
-        if (w < wave) wbase += wsum[w];
-        total += wsum[w];
-    }
+    int total;      // (the scan's barriers publish tot as well)
+    int excl = block_scan_incl<FR_TPB / 64>(local, wsum, total) - local;
     const long long base = s_base;
-    int excl = wbase + inc - local;
 #pragma unroll
     for (int e = 0; e < FR_PER; ++e) {
         const int f = t * FR_PER + e;
@@ -225,14 +194,7 @@ __global__ __launch_bounds__(64) void ap_match_k(const float* __restrict__ kp, c
     }
     const bool have = lane < nl;
     const int g = have ? labl[lane] : 0;
-    u64 vb = 0ull;
-    if (have) {
-        if (gt_visible) {
-            for (int k = 0; k < K; ++k) vb |= (u64)(gt_visible[(size_t)g * K + k] > 0.f) << k;
-        } else {
-            vb = K < 64 ? (1ull << K) - 1ull : ~0ull;
-        }
-    }
+    const u64 vb = !have ? 0ull : gt_visible ? visible_bits(gt_visible + (size_t)g * K, K) : full_bits(K);
     const int nvis = __popcll(vb);
     const float ga = have ? gt_area[g] : 0.f;
     const float Aj = oks_rect_area(ga);
@@ -242,7 +204,7 @@ __global__ __launch_bounds__(64) void ap_match_k(const float* __restrict__ kp, c
         const int m = detl[d];
         for (int k = lane; k < K; k += 64) td[k] = ((const float2*)kp)[(size_t)m * K + k];
         __syncthreads();
-        float acc = 0.f;
+        float acc = 0.f;      // (written out, as oks_matrix_k's four-row loop is: see there)
         for (int k = 0; k < K; ++k) {
             const float term = oks_term(td[k], tl[k * MAX_L + lane], vk[k], Aj);      // (prediction, label: oks_matrix_k's operand order)
             if ((vb >> k) & 1ull) acc += term;
@@ -260,16 +222,15 @@ __global__ __launch_bounds__(64) void ap_match_k(const float* __restrict__ kp, c
         const u64 w = __ballot(have && (base_ign || ga < l2 || ga > h2));
         if (aa == a) ign = w;
     }
-    const u64 all = nl == 64 ? ~0ull : (1ull << nl) - 1ull;
-    const u64 nonign = all & ~ign;
+    const u64 nonign = full_bits(nl) & ~ign;
     if (active && t == 0) counter_add(counters + NCNT + a, (long long)__popcll(nonign));
     u64 matched = 0ull;
     for (int d = 0; d < nd; ++d) {
         const int m = detl[d];
         float best = thr_t;
         int mg = -1;
-        if (active) {
-            u64 w = nonign & ~matched;
+        // the last label of set w, in ascending index, whose oks is not below the best so far
+        auto walk = [&](u64 w) {
             while (w) {
                 const int j = __ffsll((long long)w) - 1;
                 w &= w - 1ull;
@@ -278,17 +239,10 @@ __global__ __launch_bounds__(64) void ap_match_k(const float* __restrict__ kp, c
                 best = o;
                 mg = j;
             }
-            if (mg < 0) {      // an ignored label is reached only when no counted one was
-                w = ign & ~matched;
-                while (w) {
-                    const int j = __ffsll((long long)w) - 1;
-                    w &= w - 1ull;
-                    const float o = tile[d * MAX_L + j];
-                    if (o < best) continue;
-                    best = o;
-                    mg = j;
-                }
-            }
+        };
+        if (active) {
+            walk(nonign & ~matched);
+            if (mg < 0) walk(ign & ~matched);      // an ignored label is reached only when no counted one was
         }
         const float da = darea[m];
         const bool dm = mg >= 0;
@@ -305,7 +259,7 @@ __global__ __launch_bounds__(64) void ap_match_k(const float* __restrict__ kp, c
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the sort of the records
-constexpr int SO_TPB = 1024, SO_RECS = 256, SO_PARTS = SO_TPB / SO_RECS, SO_TILE = 4096, SO_PER = SO_TILE / SO_PARTS;
+constexpr int SO_TILE = 4096, SO_PER = SO_TILE / RANK_PARTS;
 
 __device__ __forceinline__ int record_count(const long long* __restrict__ counters, int capacity) {
     const long long n = counters[C_RECORDS];
@@ -313,35 +267,24 @@ __device__ __forceinline__ int record_count(const long long* __restrict__ counte
 }
 
 // rank(i) = #{j: key_j < key_i, or equal with j < i}; the index is the sequence number (records are appended in sequence order)
-__global__ __launch_bounds__(SO_TPB) void ap_sort_k(const float* __restrict__ rs, const u64* __restrict__ rm, const u64* __restrict__ ri,
-                                                    const long long* __restrict__ counters, int capacity, float* __restrict__ ss,
-                                                    u64* __restrict__ sm, u64* __restrict__ si) {
+__global__ __launch_bounds__(RANK_TPB) void ap_sort_k(const float* __restrict__ rs, const u64* __restrict__ rm, const u64* __restrict__ ri,
+                                                      const long long* __restrict__ counters, int capacity, float* __restrict__ ss,
+                                                      u64* __restrict__ sm, u64* __restrict__ si) {
     __shared__ __attribute__((aligned(16))) unsigned int tile[SO_TILE];
-    __shared__ int part[SO_PARTS][SO_RECS];
-    const int N = record_count(counters, capacity), i0 = blockIdx.x * SO_RECS;
+    __shared__ int part[RANK_PARTS][RANK_ITEMS];
+    const int N = record_count(counters, capacity), i0 = blockIdx.x * RANK_ITEMS;
     if (i0 >= N) return;
-    const int t = threadIdx.x, p = t & (SO_RECS - 1), q = t / SO_RECS, i = i0 + p;
+    const int t = threadIdx.x, p = t & (RANK_ITEMS - 1), q = t / RANK_ITEMS, i = i0 + p;
     const unsigned int ki = i < N ? order_key(rs[i], false) : 0u;
     int count = 0;
     for (int j0 = 0; j0 < N; j0 += SO_TILE) {
         __syncthreads();
-        for (int e = t; e < SO_TILE; e += SO_TPB) tile[e] = j0 + e < N ? order_key(rs[j0 + e], false) : POSE_KEY_REFUSED;      // (padding: never ahead)
+        for (int e = t; e < SO_TILE; e += RANK_TPB) tile[e] = j0 + e < N ? order_key(rs[j0 + e], false) : POSE_KEY_REFUSED;
         __syncthreads();
-        if (j0 + q * SO_PER < N) {
-            for (int e = q * SO_PER; e < (q + 1) * SO_PER; e += 4) {
-                const uint4 kj = *(const uint4*)&tile[e];
-                const int j = j0 + e;
-                count += (kj.x < ki || (kj.x == ki && j < i)) + (kj.y < ki || (kj.y == ki && j + 1 < i)) + (kj.z < ki || (kj.z == ki && j + 2 < i)) +
-                         (kj.w < ki || (kj.w == ki && j + 3 < i));
-            }
-        }
+        if (j0 + q * SO_PER < N) count += rank_count(tile + q * SO_PER, SO_PER, j0 + q * SO_PER, ki, i);
     }
-    part[q][p] = count;
-    __syncthreads();
+    const int rank = rank_finish(part, q, p, count);
     if (q == 0 && i < N) {
-        int rank = 0;
-#pragma unroll
-        for (int e = 0; e < SO_PARTS; ++e) rank += part[e][p];
         ss[rank] = rs[i];
         sm[rank] = rm[i];
         si[rank] = ri[i];
@@ -373,7 +316,7 @@ __global__ __launch_bounds__(CV_TPB) void ap_curve_k(const float* __restrict__ s
     __shared__ double wmax[CV_WAVES];
     __shared__ double sufmax[CV_MAX_CHUNKS + 1];
     __shared__ int s_q[MAX_R];
-    const int b = blockIdx.x, a = b / T, t = b - a * T, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, a = b / T, t = b - a * T, tid = threadIdx.x;
     const int N = record_count(counters, capacity);
     const long long npig = counters[NCNT + a];
     if (npig <= 0) {
@@ -392,21 +335,8 @@ __global__ __launch_bounds__(CV_TPB) void ap_curve_k(const float* __restrict__ s
         const int i = c * CV_TPB + tid;
         int fl = 0;      // tp in the low half, fp in the high half: a chunk holds at most 1024 of either
         if (i < N && !((si[i] >> b) & 1ull)) fl = ((sm[i] >> b) & 1ull) ? 1 : 0x10000;
-        int inc = fl;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += v;
-        }
-        __syncthreads();
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int wb = 0, total = 0;
-        for (int w = 0; w < CV_WAVES; ++w) {
-            if (w < wave) wb += wsum[w];
-            total += wsum[w];
-        }
-        inc += wb;
+        int total;
+        const int inc = block_scan_incl<CV_WAVES>(fl, wsum, total);
         const int ctp = btp + (inc & 0xffff), cfp = bfp + (inc >> 16);
         double pr = -1.0;
         if (i < N) {
@@ -453,13 +383,11 @@ __global__ __launch_bounds__(CV_TPB) void ap_curve_k(const float* __restrict__ s
 }
 
 bool bad_table(int T, int A) { return T < 1 || A < 1 || T * A > MAX_C; }
-size_t pad8(size_t n) { return (n + 7) / 8 * 8; }
+bool bad_update(int M, int G, int F) { return bad_poses(M) || bad_poses(G) || F < 1 || F > MAX_F; }
+bool bad_capacity(int capacity) { return capacity < 1 || capacity > MAX_CAP; }
 }  // namespace
 
-size_t ap_match_ws_bytes(int M, int G, int F) {
-    if (M < 1 || M > MAX_M || G < 1 || G > MAX_M || F < 1 || F > MAX_F) return 0;
-    return pad8((size_t)(3 * M + F) * sizeof(int));      // the order, the ordered frames, the areas, the record offsets
-}
+size_t ap_match_ws_bytes(int M, int G, int F) { return bad_update(M, G, F) ? 0 : ApMatchWs(nullptr, M, F).bytes; }
 
 int ap_match(hipStream_t s, const float* kp, const float* score, const int* frame_idx, const unsigned char* valid, const float* area, int M,
              const float* gt_kp, const float* gt_visible, const float* gt_area, const int* gt_frame, const unsigned char* gt_ignore, int G, int K,
@@ -469,45 +397,37 @@ int ap_match(hipStream_t s, const float* kp, const float* score, const int* fram
     if (!kp || !score || !frame_idx || !gt_kp || !gt_area || !gt_frame || !sigmas || !thresholds || !ranges || !ws || !rec_score || !rec_matched ||
         !rec_ignored || !counters)
         return UDAPOSE_ERR_ARG;
-    if (M < 1 || M > MAX_M || G < 1 || G > MAX_M || F < 1 || F > MAX_F || K < 1 || K > MAX_K || bad_table(T, A)) return UDAPOSE_ERR_ARG;
-    if (max_dets < 1 || max_dets > 64 || capacity < 1 || capacity > MAX_CAP || ((uintptr_t)ws & 7u)) return UDAPOSE_ERR_ARG;
-    int* order = (int*)ws;
-    int* ofr = order + M;
-    float* darea = (float*)(ofr + M);
-    int* rec_off = (int*)(darea + M);
-    hipLaunchKernelGGL(ap_rank_k, dim3((M + RK_DETS - 1) / RK_DETS), dim3(RK_TPB), 0, s, kp, score, frame_idx, valid, area, M, K, F, order, ofr, darea);
+    if (bad_update(M, G, F) || bad_keypoints(K) || bad_table(T, A)) return UDAPOSE_ERR_ARG;
+    if (max_dets < 1 || max_dets > 64 || bad_capacity(capacity) || ((uintptr_t)ws & 7u)) return UDAPOSE_ERR_ARG;
+    const ApMatchWs w(ws, M, F);
+    hipLaunchKernelGGL(ap_rank_k, dim3((M + RANK_ITEMS - 1) / RANK_ITEMS), dim3(RANK_TPB), 0, s, kp, score, frame_idx, valid, area, M, K, F, w.order,
+                       w.ofr, w.darea);
     int e = udapose_check_launch();
     if (e != UDAPOSE_OK) return e;
-    hipLaunchKernelGGL(ap_frames_k, dim3(1), dim3(FR_TPB), 0, s, ofr, M, gt_frame, G, F, max_dets, capacity, rec_off, counters);
+    hipLaunchKernelGGL(ap_frames_k, dim3(1), dim3(FR_TPB), 0, s, w.ofr, M, gt_frame, G, F, max_dets, capacity, w.rec_off, counters);
     e = udapose_check_launch();
     if (e != UDAPOSE_OK) return e;
-    hipLaunchKernelGGL(ap_match_k, dim3(F), dim3(64), match_lds_bytes(K, max_dets), s, kp, score, darea, order, ofr, M, gt_kp, gt_visible, gt_area,
-                       gt_frame, gt_ignore, G, K, sigmas, thresholds, T, ranges, A, max_dets, rec_off, rec_score, rec_matched, rec_ignored, capacity,
+    hipLaunchKernelGGL(ap_match_k, dim3(F), dim3(64), match_lds_bytes(K, max_dets), s, kp, score, w.darea, w.order, w.ofr, M, gt_kp, gt_visible, gt_area,
+                       gt_frame, gt_ignore, G, K, sigmas, thresholds, T, ranges, A, max_dets, w.rec_off, rec_score, rec_matched, rec_ignored, capacity,
                        counters);
     return udapose_check_launch();
 }
 
 size_t ap_curve_ws_bytes(int capacity, int T, int A) {
-    if (capacity < 1 || capacity > MAX_CAP || bad_table(T, A)) return 0;
-    // the sorted records (score, matched, ignored), then tp and fp counts per (t, a)
-    return pad8((size_t)capacity * sizeof(float)) + 2 * (size_t)capacity * sizeof(u64) + 2 * (size_t)T * A * capacity * sizeof(int);
+    return (bad_capacity(capacity) || bad_table(T, A)) ? 0 : ApCurveWs(nullptr, capacity, T, A).bytes;
 }
 
 int ap_curve(hipStream_t s, const float* rec_score, const unsigned long long* rec_matched, const unsigned long long* rec_ignored, int capacity,
              const long long* counters, int T, int A, const double* recall_points, int R, void* ws, double* precision, float* scores,
              double* recall) {
     if (!rec_score || !rec_matched || !rec_ignored || !counters || !recall_points || !ws || !precision || !scores || !recall) return UDAPOSE_ERR_ARG;
-    if (capacity < 1 || capacity > MAX_CAP || bad_table(T, A) || R < 1 || R > MAX_R || ((uintptr_t)ws & 7u)) return UDAPOSE_ERR_ARG;
-    u64* sm = (u64*)((char*)ws + pad8((size_t)capacity * sizeof(float)));
-    u64* si = sm + capacity;
-    int* tpc = (int*)(si + capacity);
-    int* fpc = tpc + (size_t)T * A * capacity;
-    float* ss = (float*)ws;
-    hipLaunchKernelGGL(ap_sort_k, dim3((capacity + SO_RECS - 1) / SO_RECS), dim3(SO_TPB), 0, s, rec_score, rec_matched, rec_ignored, counters, capacity,
-                       ss, sm, si);
+    if (bad_capacity(capacity) || bad_table(T, A) || R < 1 || R > MAX_R || ((uintptr_t)ws & 7u)) return UDAPOSE_ERR_ARG;
+    const ApCurveWs w(ws, capacity, T, A);
+    hipLaunchKernelGGL(ap_sort_k, dim3((capacity + RANK_ITEMS - 1) / RANK_ITEMS), dim3(RANK_TPB), 0, s, rec_score, rec_matched, rec_ignored, counters,
+                       capacity, w.ss, w.sm, w.si);
     const int e = udapose_check_launch();
     if (e != UDAPOSE_OK) return e;
-    hipLaunchKernelGGL(ap_curve_k, dim3(T * A), dim3(CV_TPB), 0, s, ss, sm, si, counters, capacity, T, A, recall_points, R, tpc, fpc, precision, scores,
-                       recall);
+    hipLaunchKernelGGL(ap_curve_k, dim3(T * A), dim3(CV_TPB), 0, s, w.ss, w.sm, w.si, counters, capacity, T, A, recall_points, R, w.tpc, w.fpc, precision,
+                       scores, recall);
     return udapose_check_launch();
 }

@@ -1,30 +1,26 @@
 // The instance layer behind predict() (fp32 only: both builds of the library export identical code).
 //   pose_rescore_k : a pose's score from its key-point confidences and its box score, its area, whether it is refused, and the walk order
-//                    (descending score, ties by ascending index, refused poses last) by counting over keys staged in LDS
-//   oks_matrix_k   : object-key-point similarity of every pair of a tile, key points staged once in LDS; the fp32 matrix (self or
-//                    rectangular form) and / or, for the self form, the suppression bit mask, one wave64 __ballot per 64-bit word
+//                    (descending score, ties by ascending index, refused poses last): pose_pair.h's rank by counting, keys staged once in LDS
+//   oks_matrix_k   : object-key-point similarity of every pair of a tile, key points staged once in LDS (the per-joint term and the
+//                    visibility word are pose_pair.h's, shared with pose_ap.hip); the fp32 matrix (self or rectangular form)
+//                    and / or, for the self form, the suppression bit mask, one wave64 __ballot per 64-bit word
 //   nms_sweep_k    : the greedy walk by one wave: lane l holds word l of the removed set in a register, membership is a cross-lane read,
 //                    the mask rows of the next 2 * SWEEP_GROUP poses of the order are in flight while the walk decides the current one
 // No atomics; every sum is added in ascending k: the same bits on every run.  M <= 4096 poses (64 mask words = one per lane), K <= 64.
 #include <float.h>
 #include "losses.h"
 #include "pose_pair.h"
+#include "pose_ws.h"
 
 // no FMA contraction: oks(i, j) and oks(j, i) are the same expression tree on swapped operands, and stay the same bits
 #pragma clang fp contract(off)
 
 namespace {
-typedef unsigned long long u64;
-constexpr int MAX_M = UDAPOSE_NMS_MAX_POSES, MAX_K = UDAPOSE_NMS_MAX_KEYPOINTS;
+constexpr int MAX_M = UDAPOSE_NMS_MAX_POSES;
 
 // ---------------------------------------------------------------------------------------------------------------- rescoring and the order
-constexpr int RS_TPB = 1024, RS_POSES = 256, RS_PARTS = RS_TPB / RS_POSES;      // a block ranks 256 poses; each of 4 thread groups scans a quarter of the keys
-constexpr unsigned int KEY_REFUSED = POSE_KEY_REFUSED;
 
-struct PoseScore {
-    float score, area;
-    bool refused;
-};
+struct PoseScore { float score, area; bool refused; };
 
 // score = (sum of conf > vis_thr, ascending k) / their count (0 for none) * box_score; refused: status != 0, a non-finite coordinate, area
 // or score, area <= 0
@@ -61,22 +57,22 @@ __device__ __forceinline__ PoseScore pose_score(int m, const float* __restrict__
     return r;
 }
 
-__global__ __launch_bounds__(RS_TPB) void pose_rescore_k(const float* __restrict__ kp, const float* __restrict__ conf, const float* __restrict__ boxes,
-                                                         const unsigned char* __restrict__ status, const float* __restrict__ box_score,
-                                                         const float* __restrict__ vis_thr_dev, int M, int K, float* __restrict__ score,
-                                                         int* __restrict__ order, float* __restrict__ area, unsigned char* __restrict__ refused) {
+__global__ __launch_bounds__(RANK_TPB) void pose_rescore_k(const float* __restrict__ kp, const float* __restrict__ conf, const float* __restrict__ boxes,
+                                                           const unsigned char* __restrict__ status, const float* __restrict__ box_score,
+                                                           const float* __restrict__ vis_thr_dev, int M, int K, float* __restrict__ score,
+                                                           int* __restrict__ order, float* __restrict__ area, unsigned char* __restrict__ refused) {
     __shared__ __attribute__((aligned(16))) unsigned int keys[MAX_M];
-    __shared__ int part[RS_PARTS][RS_POSES];
-    const int t = threadIdx.x, i0 = blockIdx.x * RS_POSES;
+    __shared__ int part[RANK_PARTS][RANK_ITEMS];
+    const int t = threadIdx.x, i0 = blockIdx.x * RANK_ITEMS;
     const float vis_thr = vis_thr_dev[0];
-    const int Mpad = (M + 4 * RS_PARTS - 1) / (4 * RS_PARTS) * (4 * RS_PARTS);      // every part a whole number of uint4 (<= MAX_M: it is a multiple of 16)
+    const int Mpad = rank_padded(M);
     // every block forms all M keys (M K confidences and 2 M K coordinates out of L2); it writes the results of its own poses
-    for (int m = t; m < Mpad; m += RS_TPB) {
-        unsigned int key = KEY_REFUSED;      // (padding: never ahead of a pose, its index is past every pose's)
+    for (int m = t; m < Mpad; m += RANK_TPB) {
+        unsigned int key = POSE_KEY_REFUSED;
         if (m < M) {
             const PoseScore r = pose_score(m, kp, conf, boxes, status, box_score, vis_thr, K);
             key = order_key(r.score, r.refused);
-            if (m >= i0 && m < i0 + RS_POSES) {
+            if (m >= i0 && m < i0 + RANK_ITEMS) {
                 score[m] = r.score;
                 area[m] = r.area;
                 refused[m] = r.refused ? 1 : 0;
@@ -85,24 +81,11 @@ __global__ __launch_bounds__(RS_TPB) void pose_rescore_k(const float* __restrict
         keys[m] = key;
     }
     __syncthreads();
-    // rank[i] = #{j ahead of i}: j is ahead when its key is smaller, or equal with j < i.  The lanes of a wave read one address (a broadcast)
-    const int p = t & (RS_POSES - 1), q = t / RS_POSES, i = i0 + p;
+    const int p = t & (RANK_ITEMS - 1), q = t / RANK_ITEMS, i = i0 + p;
     const unsigned int ki = i < M ? keys[i] : 0u;
-    const int per = Mpad / RS_PARTS, j0 = q * per;
-    int count = 0;
-    for (int j = j0; j < j0 + per; j += 4) {
-        const uint4 kj = *(const uint4*)&keys[j];
-        count += (kj.x < ki || (kj.x == ki && j < i)) + (kj.y < ki || (kj.y == ki && j + 1 < i)) + (kj.z < ki || (kj.z == ki && j + 2 < i)) +
-                 (kj.w < ki || (kj.w == ki && j + 3 < i));
-    }
-    part[q][p] = count;
-    __syncthreads();
-    if (q == 0 && i < M) {
-        int rank = 0;
-#pragma unroll
-        for (int e = 0; e < RS_PARTS; ++e) rank += part[e][p];
-        order[rank] = i;      // (the order is total: every rank in [0, M) is taken once)
-    }
+    const int per = Mpad / RANK_PARTS;
+    const int rank = rank_finish(part, q, p, rank_count(keys + q * per, per, q * per, ki, i));
+    if (q == 0 && i < M) order[rank] = i;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the OKS matrix and the mask
@@ -144,22 +127,14 @@ __global__ __launch_bounds__(OK_TPB) void oks_matrix_k(const float* __restrict__
         const int ii = e / K, i = i0 + ii;
         ti[e] = i < Ma ? ((const float2*)kp_a)[(size_t)i * K + (e - ii * K)] : make_float2(0.f, 0.f);
     }
-    for (int k = t; k < K; k += OK_TPB) {
-        vk[k] = oks_sigma_sq(sigmas[k]);
-    }
+    for (int k = t; k < K; k += OK_TPB) vk[k] = oks_sigma_sq(sigmas[k]);
     if (t < OK_TJ) {
         const int j = j0 + t;
         const bool in = j < Mb;
         area_j[t] = in ? area_b[j] : 1.f;
         frame_j[t] = (in && frame) ? frame[j] : 0;
         ok_j[t] = (in && !(refused && refused[j])) ? 1.f : 0.f;
-        u64 bits = ~0ull;
-        if (RECT && visible_b) {
-            bits = 0ull;
-            if (in)
-                for (int k = 0; k < K; ++k) bits |= (u64)(visible_b[(size_t)j * K + k] > 0.f) << k;
-        }
-        vis_j[t] = bits;
+        vis_j[t] = (RECT && visible_b) ? (in ? visible_bits(visible_b + (size_t)j * K, K) : 0ull) : ~0ull;
     } else if (t < OK_TJ + OK_TI) {
         const int ii = t - OK_TJ, i = i0 + ii;
         const bool in = i < Ma;
@@ -174,8 +149,7 @@ __global__ __launch_bounds__(OK_TPB) void oks_matrix_k(const float* __restrict__
     const int fj = frame_j[lane];
     const bool okj = ok_j[lane] != 0.f;
     const float thr = mask ? oks_thr_dev[0] : 0.f;
-    int nvis = K;
-    if (RECT) nvis = __popcll(K < 64 ? (vb & ((1ull << K) - 1ull)) : vb);
+    const int nvis = RECT ? __popcll(vb & full_bits(K)) : K;
 #pragma unroll 1
     for (int r0 = wave * OK_WAVE_ROWS; r0 < (wave + 1) * OK_WAVE_ROWS; r0 += OK_ROWS) {
         float A[OK_ROWS], acc[OK_ROWS];
@@ -184,6 +158,8 @@ __global__ __launch_bounds__(OK_TPB) void oks_matrix_k(const float* __restrict__
             A[r] = RECT ? oks_rect_area(aj) : (area_i[r0 + r] + aj) * 0.5f + FLT_EPSILON;
             acc[r] = 0.f;
         }
+        // (this loop and the staging above are written out here and in ap_match_k: through one shared function of pose_pair.h the self
+        // form measured 0.2 to 0.3 us slower at M <= 512, profiles/pose_once.txt; the term itself is the one of pose_pair.h)
         for (int k = 0; k < K; ++k) {
             const float2 pj = tj[k * OK_TJ + lane];
             const float v = vk[k];
@@ -299,13 +275,13 @@ __global__ __launch_bounds__(64) void nms_sweep_k(const u64* __restrict__ mask, 
     if (lane == 0) n_keep[0] = total;
 }
 
-bool bad_sizes(int M, int K) { return M < 1 || M > MAX_M || K < 1 || K > MAX_K; }
+bool bad_sizes(int M, int K) { return bad_poses(M) || bad_keypoints(K); }
 }  // namespace
 
 int pose_rescore(hipStream_t s, const float* kp, const float* conf, const float* boxes, const unsigned char* status, const float* box_score,
                  const float* vis_thr, int M, int K, float* score, int* order, float* area, unsigned char* refused) {
     if (!kp || !conf || !boxes || !vis_thr || !score || !order || !area || !refused || bad_sizes(M, K)) return UDAPOSE_ERR_ARG;
-    hipLaunchKernelGGL(pose_rescore_k, dim3((M + RS_POSES - 1) / RS_POSES), dim3(RS_TPB), 0, s, kp, conf, boxes, status, box_score, vis_thr, M, K,
+    hipLaunchKernelGGL(pose_rescore_k, dim3((M + RANK_ITEMS - 1) / RANK_ITEMS), dim3(RANK_TPB), 0, s, kp, conf, boxes, status, box_score, vis_thr, M, K,
                        score, order, area, refused);
     return udapose_check_launch();
 }
@@ -330,19 +306,13 @@ int oks_matrix(hipStream_t s, const float* kp_a, const float* area_a, int Ma, co
 
 int pose_nms_sweep(hipStream_t s, const unsigned long long* mask, const int* order, const unsigned char* refused, int M, unsigned char* keep,
                    int* n_keep, int* suppressed_by) {
-    if (!mask || !order || !keep || !n_keep || M < 1 || M > MAX_M) return UDAPOSE_ERR_ARG;
-    if (suppressed_by)
-        hipLaunchKernelGGL(nms_sweep_k<true>, dim3(1), dim3(64), 0, s, mask, order, refused, M, (M + 63) / 64, keep, n_keep, suppressed_by);
-    else
-        hipLaunchKernelGGL(nms_sweep_k<false>, dim3(1), dim3(64), 0, s, mask, order, refused, M, (M + 63) / 64, keep, n_keep, suppressed_by);
+    if (!mask || !order || !keep || !n_keep || bad_poses(M)) return UDAPOSE_ERR_ARG;
+    hipLaunchKernelGGL(suppressed_by ? nms_sweep_k<true> : nms_sweep_k<false>, dim3(1), dim3(64), 0, s, mask, order, refused, M, (M + 63) / 64, keep,
+                       n_keep, suppressed_by);
     return udapose_check_launch();
 }
 
-size_t pose_nms_ws_bytes(int M) {
-    if (M < 1 || M > MAX_M) return 0;
-    const size_t W = (size_t)(M + 63) / 64;
-    return (size_t)M * W * sizeof(u64) + (size_t)M * sizeof(float) + (size_t)M;      // the mask, the areas, the refused flags
-}
+size_t pose_nms_ws_bytes(int M) { return bad_poses(M) ? 0 : PoseNmsWs(nullptr, M).bytes; }
 
 int pose_nms(hipStream_t s, const float* kp, const float* conf, const float* boxes, const int* frame_idx, const unsigned char* status,
              const float* box_score, const float* sigmas, const float* vis_thr, const float* oks_thr, int M, int K, void* ws, float* score, int* order,
@@ -351,13 +321,10 @@ int pose_nms(hipStream_t s, const float* kp, const float* conf, const float* box
     if (!kp || !conf || !boxes || !sigmas || !vis_thr || !oks_thr || !ws || !score || !order || !keep || !n_keep || bad_sizes(M, K))
         return UDAPOSE_ERR_ARG;
     if ((uintptr_t)ws & 7u) return UDAPOSE_ERR_ARG;
-    const size_t W = (size_t)(M + 63) / 64;
-    u64* mask = (u64*)ws;
-    float* area = (float*)(mask + (size_t)M * W);
-    unsigned char* refused = (unsigned char*)(area + M);
-    int e = pose_rescore(s, kp, conf, boxes, status, box_score, vis_thr, M, K, score, order, area, refused);
+    const PoseNmsWs w(ws, M);
+    int e = pose_rescore(s, kp, conf, boxes, status, box_score, vis_thr, M, K, score, order, w.area, w.refused);
     if (e != UDAPOSE_OK) return e;
-    e = oks_matrix(s, kp, area, M, nullptr, nullptr, nullptr, M, K, sigmas, frame_idx, refused, oks_thr, oks_out, mask);
+    e = oks_matrix(s, kp, w.area, M, nullptr, nullptr, nullptr, M, K, sigmas, frame_idx, w.refused, oks_thr, oks_out, w.mask);
     if (e != UDAPOSE_OK) return e;
-    return pose_nms_sweep(s, mask, order, refused, M, keep, n_keep, suppressed_by);
+    return pose_nms_sweep(s, w.mask, order, w.refused, M, keep, n_keep, suppressed_by);
 }

@@ -37,15 +37,30 @@ def _like_input(src, t, in_dtype=False):
     return a.astype(src.dtype, copy=False) if in_dtype else a
 
 
+def _need_gpu():
+    raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
+
+
+def _to_device_f32(a):
+    """A numpy array (copied to the current CUDA device) or a CUDA tensor as a detached contiguous fp32 tensor; a CPU tensor is refused."""
+    if isinstance(a, np.ndarray):
+        if not torch.cuda.is_available():
+            _need_gpu()
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    _hip.require_cuda(a)
+    return ha.f32c(a)
+
+
+def _workspace(nbytes, device):      # 8-byte aligned device memory for a launcher
+    return torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+
+
 def _dev_f32(a):
     if isinstance(a, np.ndarray):
         assert a.ndim == 4, 'batch_images should be 4-ndim'
-        if not torch.cuda.is_available():
-            raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-    assert torch.is_tensor(a) and a.dim() == 4, 'batch_heatmaps should be numpy.ndarray or a 4-d tensor'
-    _hip.require_cuda(a)
-    return ha.f32c(a)
+    else:
+        assert torch.is_tensor(a) and a.dim() == 4, 'batch_heatmaps should be numpy.ndarray or a 4-d tensor'
+    return _to_device_f32(a)
 
 
 def _decode(hm):
@@ -349,22 +364,46 @@ def group_accuracy(acc, groups):
     return {name: sum(acc[i] for i in idx) / len(idx) for name, idx in _joint_groups(groups).items()}
 
 
-def _check_thresholds(thresholds):
-    """The thresholds as the kernels take them, a float32 array [T]: 1 .. PCK_MAX_THRESHOLDS of them, finite, > 0 and strictly ascending
-    AS fp32 (the device compares in fp32 and finds the first hit by bisection).  ValueError otherwise."""
+def _ascending_f32(thresholds, what, check_range):
+    """Numbers as a float32 array that ascends strictly AS fp32 (the device's type) and passes the caller's check_range(t32), or ValueError."""
     try:
         t64 = np.asarray([float(t) for t in thresholds], dtype=np.float64)
     except TypeError:
         raise ValueError(f"thresholds must be a sequence of numbers, got {thresholds!r}") from None
-    if not 1 <= t64.size <= PCK_MAX_THRESHOLDS:
-        raise ValueError(f"a PCK curve takes 1 to {PCK_MAX_THRESHOLDS} thresholds, got {t64.size}")
     with np.errstate(over="ignore"):
         t32 = t64.astype(np.float32)
-    if not (np.isfinite(t32).all() and (t32 > 0).all()):
-        raise ValueError(f"thresholds must be finite and > 0 as fp32, got {list(thresholds)!r}")
+    check_range(t32)
     if not (t32[1:] > t32[:-1]).all():
-        raise ValueError(f"thresholds must be strictly ascending as fp32, got {list(thresholds)!r}")
+        raise ValueError(f"{what} must be strictly ascending as fp32, got {list(thresholds)!r}")
     return t32
+
+
+def _check_thresholds(thresholds):
+    """A float32 array [T]: 1 .. PCK_MAX_THRESHOLDS of them, finite, > 0, strictly ascending (the device finds the first hit by bisection)."""
+    def check_range(t32):
+        if not 1 <= t32.size <= PCK_MAX_THRESHOLDS:
+            raise ValueError(f"a PCK curve takes 1 to {PCK_MAX_THRESHOLDS} thresholds, got {t32.size}")
+        if not (np.isfinite(t32).all() and (t32 > 0).all()):
+            raise ValueError(f"thresholds must be finite and > 0 as fp32, got {list(thresholds)!r}")
+    return _ascending_f32(thresholds, "thresholds", check_range)
+
+
+class _LazyDeviceState:
+    """A meter's tensors on the device, `_st`: None until the subclass's _make(device) returns them, when the meter is built (given a
+    device, or with a GPU present) or on the first use that brings a CUDA tensor; refused without either."""
+    _st = None
+
+    def _init_device(self, device):
+        if device is not None or torch.cuda.is_available():
+            self._on_device(torch.device("cuda" if device is None else device))
+
+    def _on_device(self, like=None):      # like: a device, or a tensor that lives on one, to make the state on
+        if self._st is None:
+            device = getattr(like, "device", like)
+            if device is None or device.type != "cuda":
+                _need_gpu()
+            self._st = self._make(device)
+        return self._st
 
 
 def _nan_div(a, b):
@@ -378,7 +417,7 @@ def _trapezoid(y, x):
     return ((y[..., 1:] + y[..., :-1]) * 0.5 * np.diff(x)).sum(-1) / (x[-1] - x[0])
 
 
-class PCKMeter:
+class PCKMeter(_LazyDeviceState):
     """The evaluation report of a whole set, accumulated on the device (csrc/pck_curve.hip): per joint the hits at every threshold of a PCK
     curve, the visible count and the end-point error, kept as int64 counts (`state()`: [K, T + 3], columns hits[0..T-1], count, epe_q,
     nonfinite - include/udapose.h).  An update only adds integers, so the state after a set is the same bits whatever the batch size, and
@@ -394,22 +433,12 @@ class PCKMeter:
             raise ValueError(f"PCKMeter takes 1 to 256 key points (UDAPOSE_PCK_MAX_KEYPOINTS), got {num_keypoints}")
         self._thr32 = _check_thresholds(thresholds)
         self.thresholds = tuple(float(t) for t in thresholds)
-        self._state = self._thr = None
-        if device is not None or torch.cuda.is_available():
-            self._allocate(torch.device("cuda" if device is None else device))
+        self._thr = None
+        self._init_device(device)
 
-    def _allocate(self, device):
-        if device.type != "cuda":
-            raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
+    def _make(self, device):
         self._thr = torch.from_numpy(self._thr32).to(device)
-        self._state = torch.zeros(self.num_keypoints, len(self._thr32) + 3, dtype=torch.int64, device=device)
-
-    def _on_device(self, like=None):
-        if self._state is None:
-            if like is None or not like.is_cuda:
-                raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
-            self._allocate(like.device)
-        return self._state
+        return torch.zeros(self.num_keypoints, len(self._thr32) + 3, dtype=torch.int64, device=device)
 
     def reset(self):
         """Zero the state (in place: a captured update keeps adding to the same memory)."""
@@ -431,7 +460,7 @@ class PCKMeter:
         """udapose_pck_accumulate on fp32 contiguous CUDA coordinates [B,K,2]."""
         B, K = pred.shape[:2]
         check(lib().udapose_pck_accumulate(_hip.stream(), ptr(pred), ptr(gt), ptr(visible), ptr(norm), B, K, nh, nw, ptr(self._thr),
-                                           len(self._thr32), ptr(self._state)), "pck_accumulate")
+                                           len(self._thr32), ptr(self._st)), "pck_accumulate")
 
     def update(self, output, target=None, *, decode="argmax", target_coords=None, visible=None, norm=None):
         """Add a batch.  output: the network's heat-maps [B,K,H,W]; exactly one of target (heat-maps [B,K,H,W], scored against their
@@ -461,8 +490,8 @@ class PCKMeter:
         if norm is not None and tuple(norm.shape) != (B,):
             raise ValueError(f"norm must be [{B}], got {tuple(norm.shape)}")
         self._on_device(output)
-        if any(a.device != self._state.device for a in given):
-            raise ValueError(f"the meter's state lives on {self._state.device}: every tensor of an update must")
+        if any(a.device != self._st.device for a in given):
+            raise ValueError(f"the meter's state lives on {self._st.device}: every tensor of an update must")
         o = output.detach().float().contiguous()
         if norm is not None:
             norm = norm.detach().float().contiguous()
@@ -470,7 +499,7 @@ class PCKMeter:
             pred = torch.empty(B, K, 2, dtype=torch.float32, device=o.device)
             t = target.detach().float().contiguous()
             check(lib().udapose_pck_accumulate_heatmaps(_hip.stream(), ptr(o), ptr(t), ptr(norm), B, K, H, W, ptr(self._thr),
-                                                        len(self._thr32), ptr(self._state), ptr(pred)), "pck_accumulate_heatmaps")
+                                                        len(self._thr32), ptr(self._st), ptr(pred)), "pck_accumulate_heatmaps")
             return pred
         pred = _decode_pred(o, decode)
         if target is not None:
@@ -597,8 +626,7 @@ def to_image_coords(coords, boxes, input_size, heatmap_size):
     numpy out); host boxes are checked (`check_boxes`), a device tensor is not."""
     Ho, Wo = _hw(input_size)
     Hh, Wh = _hw(heatmap_size)
-    is_np = isinstance(coords, np.ndarray)
-    if not is_np and not torch.is_tensor(coords):
+    if not isinstance(coords, np.ndarray) and not torch.is_tensor(coords):
         raise ValueError("coords must be a numpy array or a tensor [M,K,2]")
     if coords.ndim != 3 or coords.shape[2] != 2 or coords.shape[0] < 1 or coords.shape[1] < 1:
         raise ValueError(f"coords must be [M,K,2], got {tuple(coords.shape)}")
@@ -606,18 +634,8 @@ def to_image_coords(coords, boxes, input_size, heatmap_size):
         hb = check_boxes(boxes)
     if tuple(boxes.shape if torch.is_tensor(boxes) else hb.shape) != (coords.shape[0], 5):
         raise ValueError(f"boxes must be [{coords.shape[0]},5], got {tuple(boxes.shape if torch.is_tensor(boxes) else hb.shape)}")
-    if is_np:
-        if not torch.cuda.is_available():
-            raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
-        c = torch.from_numpy(np.ascontiguousarray(coords, dtype=np.float32)).cuda()
-    else:
-        _hip.require_cuda(coords)
-        c = ha.f32c(coords.detach())
-    if torch.is_tensor(boxes):
-        _hip.require_cuda(boxes)
-        bd = ha.f32c(boxes.detach())
-    else:
-        bd = torch.from_numpy(hb.astype(np.float32)).to(c.device)
+    c = _to_device_f32(coords)
+    bd = _to_device_f32(boxes) if torch.is_tensor(boxes) else torch.from_numpy(hb.astype(np.float32)).to(c.device)
     return _like_input(coords, _coords_to_image(c, bd, Ho, Wo, Wo / Wh, Ho / Hh))
 
 
@@ -840,16 +858,15 @@ def oks_nms(keypoints, confidence, boxes, frame_idx=None, status=None, box_score
     bs = None if box_scores is None else _pose_tensor(box_scores, (M,), "box_scores")
     sg = _sigmas_device(sigmas, K, dev)
     othr, vthr = nms_threshold("oks_thr", oks_thr, dev), nms_threshold("vis_thr", vis_thr, dev)
-    L = lib()
-    ws = torch.empty(L.udapose_pose_nms_ws_bytes(M) // 8 + 1, dtype=torch.int64, device=dev)
+    ws = _workspace(lib().udapose_pose_nms_ws_bytes(M), dev)
     out = {"score": torch.empty(M, dtype=torch.float32, device=dev), "order": torch.empty(M, dtype=torch.int32, device=dev),
            "keep": torch.empty(M, dtype=torch.uint8, device=dev), "n_keep": torch.empty(1, dtype=torch.int32, device=dev),
            "suppressed_by": torch.empty(M, dtype=torch.int32, device=dev)}
     if want_matrix:
         out["oks"] = torch.empty(M, M, dtype=torch.float32, device=dev)
-    check(L.udapose_pose_nms(_hip.stream(), ptr(kp), ptr(conf), ptr(bx), ptr(fi), ptr(st), ptr(bs), ptr(sg), ptr(vthr), ptr(othr), M, K, ptr(ws),
-                             ptr(out["score"]), ptr(out["order"]), ptr(out["keep"]), ptr(out["n_keep"]), ptr(out["suppressed_by"]),
-                             ptr(out.get("oks"))), "pose_nms")
+    check(lib().udapose_pose_nms(_hip.stream(), ptr(kp), ptr(conf), ptr(bx), ptr(fi), ptr(st), ptr(bs), ptr(sg), ptr(vthr), ptr(othr), M, K,
+                                 ptr(ws), ptr(out["score"]), ptr(out["order"]), ptr(out["keep"]), ptr(out["n_keep"]), ptr(out["suppressed_by"]),
+                                 ptr(out.get("oks"))), "pose_nms")
     return out
 
 
@@ -869,19 +886,13 @@ AP_COUNTS = ("records", "dropped", "refused", "cut", "overflow_frames", "bad_lab
 
 def _check_ap_thresholds(thresholds):
     """T OKS thresholds as the kernel takes them, a float32 array: each in (0, 1), strictly ascending AS fp32.  ValueError otherwise."""
-    try:
-        t64 = np.asarray([float(t) for t in thresholds], dtype=np.float64)
-    except TypeError:
-        raise ValueError(f"thresholds must be a sequence of numbers, got {thresholds!r}") from None
-    t32 = t64.astype(np.float32)
-    if t32.size < 1 or not (np.isfinite(t32).all() and (t32 > 0).all() and (t32 < 1).all()):
-        raise ValueError(f"OKS thresholds must be in (0, 1) as fp32, at least one of them, got {list(thresholds)!r}")
-    if not (t32[1:] > t32[:-1]).all():
-        raise ValueError(f"OKS thresholds must be strictly ascending as fp32, got {list(thresholds)!r}")
-    return t32
+    def check_range(t32):
+        if t32.size < 1 or not (np.isfinite(t32).all() and (t32 > 0).all() and (t32 < 1).all()):
+            raise ValueError(f"OKS thresholds must be in (0, 1) as fp32, at least one of them, got {list(thresholds)!r}")
+    return _ascending_f32(thresholds, "OKS thresholds", check_range)
 
 
-class APMeter:
+class APMeter(_LazyDeviceState):
     """Key-point AP under OKS over a whole set, COCO-style, kept on the device (csrc/pose_ap.hip).  An update matches the
     detections of its frames to the labelled poses (cocoapi's evaluateImg: per frame the `max_dets` best detections, greedily, at every
     threshold and in every area range) and appends one record per detection - its score and a matched / ignored bit per (range, threshold),
@@ -923,29 +934,18 @@ class APMeter:
             table = tuple(float(v) for v in sigmas)
             if len(table) != self.num_keypoints or not all(np.isfinite(v) and v > 0 for v in table):
                 raise ValueError(f"sigmas must be {self.num_keypoints} positive numbers, got {table}")
-        self._st = None
-        if device is not None or torch.cuda.is_available():
-            self._allocate(torch.device("cuda" if device is None else device))
+        self._init_device(device)
 
-    def _allocate(self, device):
-        if device.type != "cuda":
-            raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
+    def _make(self, device):
         T, A, R, cap = len(self._thr32), len(self.area_ranges), self._rp64.size, self.capacity
         ranges = np.asarray(list(self.area_ranges.values()), dtype=np.float64).astype(np.float32)
         # (the record arrays have one more slot than capacity: merge() sends what does not fit there)
-        self._st = {"thr": torch.from_numpy(self._thr32).to(device), "ranges": torch.from_numpy(ranges).to(device),
-                    "rp": torch.from_numpy(self._rp64).to(device), "sigmas": _sigmas_device(self._sigmas_arg, self.num_keypoints, device),
-                    "score": torch.zeros(cap + 1, dtype=torch.float32, device=device),
-                    "matched": torch.zeros(cap + 1, dtype=torch.int64, device=device),
-                    "ignored": torch.zeros(cap + 1, dtype=torch.int64, device=device),
-                    "counters": torch.zeros(len(AP_COUNTS) + A, dtype=torch.int64, device=device)}
-
-    def _on_device(self, like=None):
-        if self._st is None:
-            if like is None or not like.is_cuda:
-                raise RuntimeError("uda_poseestimation_amd.lib.keypoint_detection needs the MI355X (no CPU fallback)")
-            self._allocate(like.device)
-        return self._st
+        return {"thr": torch.from_numpy(self._thr32).to(device), "ranges": torch.from_numpy(ranges).to(device),
+                "rp": torch.from_numpy(self._rp64).to(device), "sigmas": _sigmas_device(self._sigmas_arg, self.num_keypoints, device),
+                "score": torch.zeros(cap + 1, dtype=torch.float32, device=device),
+                "matched": torch.zeros(cap + 1, dtype=torch.int64, device=device),
+                "ignored": torch.zeros(cap + 1, dtype=torch.int64, device=device),
+                "counters": torch.zeros(len(AP_COUNTS) + A, dtype=torch.int64, device=device)}
 
     def reset(self):
         """Zero the counters (in place: a captured update keeps appending to the same memory); the records behind the count mean nothing."""
@@ -986,12 +986,11 @@ class APMeter:
         dev = st["counters"].device
         if any(t is not None and t.device != dev for t in (kp, sc, fi, va, ar, gk, gv, ga, gf, gi)):
             raise ValueError(f"the meter's state lives on {dev}: every tensor of an update must")
-        L = lib()
-        ws = torch.empty(L.udapose_ap_match_ws_bytes(M, G, F) // 8 + 1, dtype=torch.int64, device=dev)      # (a capture keeps its own)
-        check(L.udapose_ap_match(_hip.stream(), ptr(kp), ptr(sc), ptr(fi), ptr(va), ptr(ar), M, ptr(gk), ptr(gv), ptr(ga), ptr(gf), ptr(gi), G, K, F,
-                                 ptr(st["sigmas"]), ptr(st["thr"]), len(self._thr32), ptr(st["ranges"]), len(self.area_ranges), self.max_dets,
-                                 ptr(ws), ptr(st["score"]), ptr(st["matched"]), ptr(st["ignored"]), self.capacity, ptr(st["counters"])),
-              "ap_match")
+        ws = _workspace(lib().udapose_ap_match_ws_bytes(M, G, F), dev)      # (a capture keeps its own)
+        check(lib().udapose_ap_match(_hip.stream(), ptr(kp), ptr(sc), ptr(fi), ptr(va), ptr(ar), M, ptr(gk), ptr(gv), ptr(ga), ptr(gf), ptr(gi), G, K,
+                                     F, ptr(st["sigmas"]), ptr(st["thr"]), len(self._thr32), ptr(st["ranges"]), len(self.area_ranges),
+                                     self.max_dets, ptr(ws), ptr(st["score"]), ptr(st["matched"]), ptr(st["ignored"]), self.capacity,
+                                     ptr(st["counters"])), "ap_match")
 
     def update_predict(self, result, frame_idx, gt_keypoints, gt_visible, gt_area, gt_frame, *, num_frames, gt_ignore=None):
         """update() on engine.predict(nms=True)'s dict: its key points, its rescored "score", valid = keep & (status == 0), the area from the
@@ -1031,13 +1030,12 @@ class APMeter:
         st = self._on_device()
         dev = st["counters"].device
         T, A, R = len(self._thr32), len(self.area_ranges), self._rp64.size
-        L = lib()
-        ws = torch.empty(L.udapose_ap_curve_ws_bytes(self.capacity, T, A) // 8 + 1, dtype=torch.int64, device=dev)
+        ws = _workspace(lib().udapose_ap_curve_ws_bytes(self.capacity, T, A), dev)
         precision = torch.empty(T, R, A, dtype=torch.float64, device=dev)
         recall = torch.empty(T, A, dtype=torch.float64, device=dev)
         scores = torch.empty(T, R, A, dtype=torch.float32, device=dev)
-        check(L.udapose_ap_curve(_hip.stream(), ptr(st["score"]), ptr(st["matched"]), ptr(st["ignored"]), self.capacity, ptr(st["counters"]), T, A,
-                                 ptr(st["rp"]), R, ptr(ws), ptr(precision), ptr(scores), ptr(recall)), "ap_curve")
+        check(lib().udapose_ap_curve(_hip.stream(), ptr(st["score"]), ptr(st["matched"]), ptr(st["ignored"]), self.capacity, ptr(st["counters"]), T,
+                                     A, ptr(st["rp"]), R, ptr(ws), ptr(precision), ptr(scores), ptr(recall)), "ap_curve")
         parts = [precision.reshape(-1).view(torch.uint8), recall.reshape(-1).view(torch.uint8), st["counters"].view(torch.uint8),
                  scores.reshape(-1).view(torch.uint8)]
         host = torch.cat(parts).cpu().numpy()
